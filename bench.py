@@ -16,10 +16,13 @@ detected-cell records of a step are all-gathered by ONE asynchronous collective 
 for a step later, off the critical path.  --input-host feeds the same batches from page-locked HOST
 memory (lcs_batch_enqueue_host: PCIe inside the timed region).
 
-The run verifies itself: every batch collected inside the timed, pipelined region must return the
-same bytes as a sequential single-context run of the same buffers afterwards, and 16 buffers (12 of
-the timed batch, 4 of the dense band) are checked against the CPU oracle ("verified" in the JSON line;
-tools/parity_population.py checks every timed buffer and 512 more).
+A plain run sets up, warms up, times --steps steps and prints the result line.  Every collect of a
+distinct batch inside the timed, pipelined region must return the same bytes as that batch's first
+collect ("verified" in the JSON line).  --full adds everything else: a sequential single-context run
+of the same buffers afterwards that must return those bytes too, 16 buffers (12 of the timed batch, 4
+of the dense band) checked against the CPU oracle, the CPU baseline, the dense-band line, the
+isolated kernel time and the power probe (tools/parity_population.py checks every timed buffer and
+512 more).  --dump-outputs DIR writes the cell records of the last timed step as DIR/*.npy (float64).
 
 Prints ONE JSON line on rank 0.
 """
@@ -161,17 +164,19 @@ def stream_bench(pkg, args, rank, world, local_rank, dist):
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the same buffers through the eager (launch by launch) chain, for the graph-vs-launches comparison
-    E = pkg.Searcher(local_rank if world > 1 else 0)
-    d_one = torch.from_numpy(np.stack(host)).to(torch.device("cuda", local_rank if world > 1 else 0))
-    fz = np.array([0.0])
-    for i in range(3):
-        E.search_batch(d_one[i % 4].data_ptr(), pkg.FMT_IQ_U8, 1, N_CAP, fz, fc, fc, FS, pkg.STAGE_FULL)
-    t0 = time.perf_counter()
-    for i in range(20):
-        E.search_batch(d_one[i % 4].data_ptr(), pkg.FMT_IQ_U8, 1, N_CAP, fz, fc, fc, FS, pkg.STAGE_FULL)
-    eager_ms = 1e3 * (time.perf_counter() - t0) / 20
-    E.close()
+    # --full: the same buffers through the eager (launch by launch) chain, for the graph-vs-launches comparison
+    eager_ms = None
+    if args.full:
+        E = pkg.Searcher(local_rank if world > 1 else 0)
+        d_one = torch.from_numpy(np.stack(host)).to(torch.device("cuda", local_rank if world > 1 else 0))
+        fz = np.array([0.0])
+        for i in range(3):
+            E.search_batch(d_one[i % 4].data_ptr(), pkg.FMT_IQ_U8, 1, N_CAP, fz, fc, fc, FS, pkg.STAGE_FULL)
+        t0 = time.perf_counter()
+        for i in range(20):
+            E.search_batch(d_one[i % 4].data_ptr(), pkg.FMT_IQ_U8, 1, N_CAP, fz, fc, fc, FS, pkg.STAGE_FULL)
+        eager_ms = 1e3 * (time.perf_counter() - t0) / 20
+        E.close()
     if rank == 0:
         value = world * args.steps / dt
         print(json.dumps({
@@ -248,23 +253,28 @@ def single_bench(pkg, args, rank, world, local_rank, dist):
         S.search_batch(d_one[i % 8].data_ptr(), pkg.FMT_IQ_U8, 1, N_CAP, f, fc, fc, FS, pkg.STAGE_FULL)
     res_ms = 1e3 * (time.perf_counter() - t1) / 20
     xc_ms = S.last_xcorr_ms()[0]
-    # the hypothesis-split form of the same search (lcs_foe_partial + lcs_foe_finish, SURVEY 8e latency mode) on this one GPU:
-    # what the split costs before any second GPU helps (the packed words make a round trip through a device buffer, the
+    # --full: the hypothesis-split form of the same search (lcs_foe_partial + lcs_foe_finish, SURVEY 8e latency mode) on this one
+    # GPU: what the split costs before any second GPU helps (the packed words make a round trip through a device buffer, the
     # peak search runs on the unpacked arrays); at world 2 each rank would correlate half the hypotheses between the two calls
-    words = torch.empty(3 * 9600, dtype=torch.int64, device=torch.device("cuda", dev_i))
-    meta = torch.empty(9601, dtype=torch.float64, device=torch.device("cuda", dev_i))
-    for i in range(23):
-        if i == 3:
-            t1 = time.perf_counter()
-        S.foe_partial(caps[i % 8], f, 0, f.size, fc, fc, FS, words.data_ptr(), meta.data_ptr())
-        S.foe_finish(words.data_ptr(), meta.data_ptr(), f)
-    foe_ms = 1e3 * (time.perf_counter() - t1) / 20
-    half = []
-    for i in range(23):
-        if i == 3:
-            t1 = time.perf_counter()
-        S.foe_partial(caps[i % 8], f, 0, (f.size + 1) // 2, fc, fc, FS, words.data_ptr(), meta.data_ptr())
-    foe_half_ms = 1e3 * (time.perf_counter() - t1) / 20
+    foe_split = None
+    if args.full:
+        words = torch.empty(3 * 9600, dtype=torch.int64, device=torch.device("cuda", dev_i))
+        meta = torch.empty(9601, dtype=torch.float64, device=torch.device("cuda", dev_i))
+        for i in range(23):
+            if i == 3:
+                t1 = time.perf_counter()
+            S.foe_partial(caps[i % 8], f, 0, f.size, fc, fc, FS, words.data_ptr(), meta.data_ptr())
+            S.foe_finish(words.data_ptr(), meta.data_ptr(), f)
+        foe_ms = 1e3 * (time.perf_counter() - t1) / 20
+        for i in range(23):
+            if i == 3:
+                t1 = time.perf_counter()
+            S.foe_partial(caps[i % 8], f, 0, (f.size + 1) // 2, fc, fc, FS, words.data_ptr(), meta.data_ptr())
+        foe_half_ms = 1e3 * (time.perf_counter() - t1) / 20
+        foe_split = {"world1_partial_plus_finish_ms": foe_ms, "partial_with_half_the_hypotheses_ms": foe_half_ms,
+                     "note": "lcs_foe_partial + lcs_foe_finish on one GPU with all hypotheses (no collective), and the "
+                             "partial call alone with half of them (a rank's share at world 2; RCCL's 230 KB all-reduce and "
+                             "77 KB broadcast come on top)"}
     if rank == 0:
         value = world * args.steps / dt
         flops = 8.0 * 137 * 3 * (N_CAP - 136) * f.size
@@ -280,10 +290,7 @@ def single_bench(pkg, args, rank, world, local_rank, dist):
                        "n_f": int(f.size), "latency_ms": {"min": float(la.min()), "median": float(np.median(la)), "max": float(la.max())},
                        "xcorr_kernel": kname, "cells_per_buffer": n_cells / max(1, args.steps),
                        "ms_per_buffer_resident_u8_input": res_ms, "xcorr_kernel_ms_one_buffer": xc_ms,
-                       "foe_split": {"world1_partial_plus_finish_ms": foe_ms, "partial_with_half_the_hypotheses_ms": foe_half_ms,
-                                     "note": "lcs_foe_partial + lcs_foe_finish on one GPU with all hypotheses (no collective), and the "
-                                             "partial call alone with half of them (a rank's share at world 2; RCCL's 230 KB all-reduce and "
-                                             "77 KB broadcast come on top)"},
+                       "foe_split": foe_split,
                        "parallelism": "replicas" if world > 1 else "single GPU"},
             "roofline": {"bound": "launch/latency", "achieved": flops / (xc_ms * 1e-3) / 1e12, "peak": PEAK_I8_TOPS, "unit": "TOP/s",
                          "frac": flops / (xc_ms * 1e-3) / 1e12 / PEAK_I8_TOPS, "traffic": None,
@@ -616,6 +623,33 @@ def digest(rec, cnt):
     return b"".join([cnt.tobytes()] + [rec[b, :cnt[b]].tobytes() for b in range(len(cnt))])
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, collected, prefix=""):
+    """--dump-outputs: what the caller of the timed path received in the last timed step -- the (records, counts) of its
+    batches, in collect order -- as float64 arrays: batch_index (the batch's position in the step), cell_counts [batch][buffer]
+    and one cell_<field> array per lcs_cell field over the valid records in (batch, buffer, slot) order.  Above
+    DUMP_LIMIT_BYTES in all, a fixed, seeded sample of the batches is written instead."""
+    def arrays(sel):
+        part = [collected[i] for i in sel]
+        out = {"batch_index": sel.astype(np.float64), "cell_counts": np.stack([c for _, c in part]).astype(np.float64)}
+        valid = np.concatenate([r[np.arange(r.shape[1])[None, :] < c[:, None]] for r, c in part])
+        for name in valid.dtype.names:
+            if name != "reserved":
+                out["cell_" + name] = valid[name].astype(np.float64)
+        return out
+
+    sel = np.arange(len(collected))
+    out = arrays(sel)
+    while sum(a.nbytes + 128 for a in out.values()) > DUMP_LIMIT_BYTES and sel.size > 1:      # (+ the .npy header)
+        sel = np.sort(np.random.default_rng(0).choice(len(collected), sel.size // 2, replace=False))
+        out = arrays(sel)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -661,7 +695,19 @@ def main():
     ap.add_argument("--no-dense", action="store_true", help="skip the dense-band line (2-3 cells planted in every buffer) reported in config.dense_band")
     ap.add_argument("--dense-main", action="store_true",
                     help="developer / profiling runs: the MAIN workload is the dense band (2-3 cells planted in every buffer); the line says so in config.workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sequential and CPU-oracle verification, the CPU baseline, "
+                         "the dense-band line, the isolated kernel time, the power probe and the other stages' side measurements "
+                         "(the --no-* options above deselect single legs of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (the collected cell records) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.stage in ("stream", "single", "track"):
+        ap.error(f"--dump-outputs covers the batch path (--stage full or pss), not --stage {args.stage}")
+    if not args.full:
+        args.no_cpu_baseline = args.no_dense = args.no_power_probe = True
     if args.batch is None:
         args.batch = 64 if args.stage == "track" else 128
     if args.pipeline is None:
@@ -810,9 +856,10 @@ def main():
         gather_dev[step_idx % 2].copy_(gather_in[step_idx % 2], non_blocking=True)
         pending["work"] = dist.all_gather_into_tensor(gather_out[step_idx % 2].view(-1), gather_dev[step_idx % 2], async_op=True)
 
-    def run(n_steps, xc_ms=None, gather=True, step_ms=None, first_step=0):
+    def run(n_steps, xc_ms=None, gather=True, step_ms=None, first_step=0, keep=None):
         """n_steps steps of K batches each, software-pipelined over the contexts: batch i is enqueued before batch
-        i-(depth-1) is collected, so nothing but the stream of the collected batch ever blocks."""
+        i-(depth-1) is collected, so nothing but the stream of the collected batch ever blocks.  keep: a list that
+        receives the (records, counts) of the last step's K batches."""
         depth = len(ctxs)
         total = n_steps * K
         recs, last = [], None
@@ -823,6 +870,8 @@ def main():
             j = i - (depth - 1)
             if j >= 0:
                 last = collect(j)
+                if keep is not None and j >= total - K:
+                    keep.append(last)
                 if multi and gather:
                     recs.append(pack_records(*last))
                 if xc_ms is not None and not args.no_xc_timing:
@@ -847,11 +896,12 @@ def main():
     if args.warmup:
         run(args.warmup, first_step=0)
     xc_ms, step_ms = [], []
+    last_step = [] if args.dump_outputs else None
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    last = run(args.steps, xc_ms, step_ms=step_ms, first_step=args.warmup)
+    last = run(args.steps, xc_ms, step_ms=step_ms, first_step=args.warmup, keep=last_step)
     if pending["work"] is not None:
         pending["work"].wait()
         pending["work"] = None
@@ -885,27 +935,33 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step, "" if rank == 0 else f"rank{rank}_")
+
     probe = None
     if rank == 0 and not multi and not args.no_power_probe:
         probe = power_probe(lambda: run(1, gather=False), 0)
 
     # ---- verification (outside the timed region) -------------------------------------------------------------
     # (1) every pipelined collect of a distinct batch returned identical bytes (state["mismatch"] == 0);
-    # (2) a sequential, single-context, synchronous run of each distinct batch returns those bytes too;
+    # --full: (2) a sequential, single-context, synchronous run of each distinct batch returns those bytes too;
     # (3) buffer 0 of batch 0 against the CPU oracle (done in the cpu_baseline leg below, rank 0).
     seq_ok = True
     iso_ms = []
-    n_cells_per_batch = []
-    for d in range(D):
-        ctxs[0].batch_enqueue(d_caps[d].data_ptr(), fmt, B, N_CAP, f, fcs, fcs, FS, stage_mask)
-        rec, cnt = ctxs[0].batch_collect_raw(B, MAXC)
-        iso_ms.append(float('nan') if args.no_xc_timing else ctxs[0].last_xcorr_ms()[0])       # the dominant kernel alone on the GPU (nothing overlaps it here)
-        n_cells_per_batch.append(int(cnt.sum()))
-        seq_ok = seq_ok and (seen.get(d) == digest(rec, cnt))
-        if d == 0:
-            rec0, cnt0 = rec.copy(), cnt.copy()
+    n_cells_per_batch = None
+    st_main = None
+    if args.full:
+        n_cells_per_batch = []
+        for d in range(D):
+            ctxs[0].batch_enqueue(d_caps[d].data_ptr(), fmt, B, N_CAP, f, fcs, fcs, FS, stage_mask)
+            rec, cnt = ctxs[0].batch_collect_raw(B, MAXC)
+            iso_ms.append(float('nan') if args.no_xc_timing else ctxs[0].last_xcorr_ms()[0])       # the dominant kernel alone on the GPU (nothing overlaps it here)
+            n_cells_per_batch.append(int(cnt.sum()))
+            seq_ok = seq_ok and (seen.get(d) == digest(rec, cnt))
+            if d == 0:
+                rec0, cnt0 = rec.copy(), cnt.copy()
+        st_main = ctxs[0].last_batch_stats() if stage_mask == pkg.STAGE_FULL and hasattr(pkg.capi.load(), "lcs_last_batch_stats") else None
     kname, executed_ops = ctxs[0].last_xcorr_info()
-    st_main = ctxs[0].last_batch_stats() if stage_mask == pkg.STAGE_FULL and hasattr(pkg.capi.load(), "lcs_last_batch_stats") else None
     # ---- dense band (reported next to the default, never part of `value`): 2-3 cells planted in EVERY buffer, so the
     # per-cell stages carry ~8x the cells of the band-scan workload above
     dense, dense_rec, dense_host = None, None, None
@@ -946,7 +1002,10 @@ def main():
     mem_free, _ = torch.cuda.mem_get_info(dev)
     hbm_in_use["after_dense_band_GB"] = (mem_total - mem_free) / 1e9      # the dense batches grow the per-cell buffers (512 -> 1024 cells per context)
     verify = {"pipelined_collects": state["collected"], "pipelined_mismatches": state["mismatch"],
-              "sequential_run_identical": bool(seq_ok), "oracle_buffer0": None, "oracle_buffers_checked": [], "oracle_buffers_differing": []}
+              "sequential_run_identical": bool(seq_ok) if args.full else None, "oracle_buffer0": None, "oracle_buffers_checked": [],
+              "oracle_buffers_differing": []}
+    if not args.full:
+        verify["note"] = "plain run: the pipelined collects of each distinct batch against its first collect; --full adds the sequential run and the CPU oracle"
 
     if rank == 0:
         n_f = f.size
@@ -958,7 +1017,7 @@ def main():
         flops_per_buf = 8.0 * 137 * 3 * (N_CAP - 136) * n_f
         flops_consumed = 8.0 * 137 * 3 * 9600 * 15 * n_f
         k_ms = float(np.mean(xc_ms)) if xc_ms else float('nan')
-        k_iso = float(np.mean(iso_ms))
+        k_iso = float(np.mean(iso_ms)) if iso_ms else float('nan')
         i8 = kname.startswith("k_xcorr_i8")
         f16 = kname.startswith("k_xcorr_f16")
         peak = PEAK_I8_TOPS if i8 else (PEAK_BF16_TFLOPS if f16 else PEAK_FP32_TFLOPS)
@@ -1011,7 +1070,7 @@ def main():
                                         "gathered_fc_min_max_per_rank": state.get("gathered_fc"), "gather_out_shape": state.get("gather_shape")} if multi else None),
                        "baseline_note": "vs_baseline = value / (1 buffer per ~6 s), doc/CellSearch.html:52-54 (dual-core i7-2640, ppm 100; BASELINE.md section 1)",
                        "cells_per_distinct_batch": n_cells_per_batch,
-                       "cells_per_buffer": float(np.mean(n_cells_per_batch)) / B,
+                       "cells_per_buffer": float(np.mean(n_cells_per_batch)) / B if n_cells_per_batch else None,
                        "cells_past_sss_per_buffer": (st_main["cells_past_sss"] / B) if st_main else None,
                        "pbch_candidates_decoded_per_cell_past_sss": (st_main["pbch_candidates_decoded"] / max(1, st_main["cells_past_sss"])) if st_main else None,
                        "dense_band": dense,
@@ -1040,9 +1099,9 @@ def main():
                                  ("achieved = SURVEY 8(d) algorithmic flops of one launch / the kernel's mean duration in the timed region, against the dense "
                                   "fp16 MFMA peak (2.5 PFLOP/s); frac_executed counts the MFMA work issued (x3 products, 160 of 137 taps, 96 of 93 columns)") if f16 else
                                  "achieved = SURVEY 8(d) algorithmic flops / kernel time, against the fp32 MFMA peak",
-                         "kernel": kname, "kernel_ms": k_ms, "kernel_ms_isolated": k_iso,
-                         "frac_isolated": flops_per_buf * B / (k_iso * 1e-3) / 1e12 / peak,
-                         "frac_executed_isolated": (executed_ops / (k_iso * 1e-3) / 1e12 / peak) if executed_ops else None,
+                         "kernel": kname, "kernel_ms": k_ms, "kernel_ms_isolated": k_iso if iso_ms else None,
+                         "frac_isolated": flops_per_buf * B / (k_iso * 1e-3) / 1e12 / peak if iso_ms else None,
+                         "frac_executed_isolated": (executed_ops / (k_iso * 1e-3) / 1e12 / peak) if executed_ops and iso_ms else None,
                          "flops_per_launch": flops_per_buf * B, "executed_ops_per_launch": executed_ops or None,
                          "traffic_source": traffic_src,
                          "traffic_note": "HBM bytes per launch from rocprofv3 PMC (2*FETCH_SIZE+WRITE_SIZE)*1024, reported only when the committed "

@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 (cd "$REPO" && timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -6) > "$OUT/pytest_gpu.log"
 cd /tmp; export TMPDIR=/tmp
-B="python $REPO/bench.py"
+B="python $REPO/bench.py --full"
 SHORT="--steps 2 --warmup 1 --batches-per-step 8 --no-cpu-baseline --no-dense --no-power-probe"
 # every kernel alone, per 64-buffer batch (the unit of DESIGN 3.2's table since round 1), then the bench's default command
 # (128 buffers per launch, two contexts in flight): the correlation kernel's average duration there is what bench.py's

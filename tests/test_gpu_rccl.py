@@ -28,7 +28,7 @@ def test_bench_forced_dist_over_rccl():
     """bench.py --gpus 1 --force-dist --dist-backend nccl takes the world > 1 branch with one rank: same verified result,
     collectives reported, and a rate close to the plain run's (the all-gather is asynchronous and waited for a step later)."""
     steps, K = 4, 12
-    common = ["--steps", str(steps), "--warmup", "1", "--batch", "64", "--batches-per-step", str(K), "--no-cpu-baseline", "--no-dense"]
+    common = ["--steps", str(steps), "--warmup", "1", "--batch", "64", "--batches-per-step", str(K), "--full", "--no-cpu-baseline", "--no-dense"]
     plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, env=ENV, capture_output=True, text=True, timeout=900)
     assert plain.returncode == 0, plain.stderr[-3000:]
     forced = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl"] + common,

@@ -28,7 +28,7 @@ def test_bench_world_8_on_one_gpu():
     batches in flight, packs its step's records, and the asynchronous all-gather brings 8 x (1 + 5 MAXREC) doubles to everyone."""
     B, K, steps = 8, 2, 2
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu0", "--dist-backend", "gloo", "--steps", str(steps),
-                        "--warmup", "1", "--batch", str(B), "--batches-per-step", str(K), "--no-cpu-baseline", "--no-dense", "--no-power-probe"],
+                        "--warmup", "1", "--batch", str(B), "--batches-per-step", str(K), "--full", "--no-cpu-baseline", "--no-dense", "--no-power-probe"],
                        env=dict(ENV, MASTER_PORT="29571"), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

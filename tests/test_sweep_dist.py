@@ -271,7 +271,7 @@ def test_bench_gpus_2_starts_two_ranks_itself():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu0", "--dist-backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--batch", "8", "--batches-per-step", "3", "--no-cpu-baseline", "--no-dense"], env=env,
+                        "--warmup", "1", "--batch", "8", "--batches-per-step", "3", "--full", "--no-cpu-baseline", "--no-dense"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

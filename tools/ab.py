@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Developer A/B runner (GPU box): tools/ab.py TAG 'bench args' ... -> one compact line per run in gpurun_out/ab_TAG.txt"""
-import json, os, subprocess, sys, time
+import json, os, subprocess, sys, tempfile, time
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 out = os.path.join(root, "gpurun_out", f"ab_{tag}.txt")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 for spec in sys.argv[2:]:
     t0 = time.time()
-    p = subprocess.run(f"timeout 240 python {root}/bench.py --no-cpu-baseline --no-power-probe --synth-cache /tmp/synth {spec}", shell=True, capture_output=True, text=True, cwd="/tmp")
+    tmp = tempfile.gettempdir()
+    p = subprocess.run(f"timeout 240 python {root}/bench.py --full --no-cpu-baseline --no-power-probe --synth-cache {os.path.join(tmp, 'synth')} {spec}",
+                       shell=True, capture_output=True, text=True, cwd=tmp)
     line = f"{spec:60s} "
     try:
         j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
