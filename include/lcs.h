@@ -444,6 +444,35 @@ int lcs_track_stream_block(lcs_ctx *ctx, lcs_track_cell *cells, int n_cells, int
                            uint64_t *mib_bits, int max_off, int64_t *mib_from, int32_t *n_mib);
 int lcs_track_stream_reset(lcs_ctx *ctx);
 
+/* ---- wideband channelizer: one SDR capture in HBM feeds a whole band search ----------------
+ * A digital down-converter per carrier (mix, low-pass, decimate) in front of lcs_batch_enqueue: ONE wideband capture x[n] at
+ * fs_in = decim * fs_out (2 <= decim <= 16) resident in HBM becomes n_ch narrowband buffers at fs_out, the batch layout
+ * LCS_FMT_C64 of lcs_batch_enqueue.  Output k is, exactly ("valid" mode, nothing is zero-padded, T = 16 * decim),
+ *
+ *   y_k[m] = sum_{t=0}^{T-1} h[t] * x[m*decim + T-1-t] * exp(-2 pi i * f_shift[k] / fs_in * (m*decim + T-1-t)),  m = 0 .. n_out-1
+ *
+ * with the fixed low-pass h[t] = sinc((t - (T-1)/2) / decim) * kaiser(T, beta = 7.75)[t], normalised to sum(h) = 1 (computed in
+ * double, handed to the device as float): at fs_out = 1.92 Msps the passband |f| <= 0.66 MHz ripples by <= 0.0034 dB and
+ * everything that aliases into it (|f| >= 1.26 MHz) is down by 71.5 dB (decim 2), 75.6 dB (3), >= 78 dB (4 .. 16).  The carrier
+ * phase is kept in 64-bit fixed point (2^64 = one turn), so sample 2.4 M of an 80 ms capture is as exact as sample 0.
+ *   d_wide   DEVICE, n_in samples of fmt: LCS_FMT_C64, LCS_FMT_IQ_S8 (interleaved signed 8-bit, value v / 128) or
+ *            LCS_FMT_IQ_S16 (interleaved signed 16-bit, value v / 32768), aligned to one sample
+ *   f_shift  HOST [n_ch], Hz: carrier centre minus capture centre, |f_shift| <= fs_in / 2
+ *   d_out    DEVICE [n_ch][n_out] complex<float>, 16-byte aligned; n_in >= (n_out - 1) * decim + 16 * decim
+ * The kernels are queued on the context's stream and the call returns without waiting for them: an lcs_batch_enqueue on the
+ * same context that reads d_out is ordered behind them.  d_wide and d_out stay the caller's.  LCS_ERR_BAD_ARG (with an
+ * lcs_last_error text) for a null pointer, decim outside 2..16, n_ch < 1, a capture too short for n_out, a shift beyond
+ * fs_in / 2, an unknown fmt or a misaligned buffer; nothing is launched then.  fp32 matrix cores, fp32 accumulation: within
+ * 1e-5 of the largest output of a channel against the sum evaluated in double. */
+#define LCS_FMT_IQ_S8 3
+#define LCS_FMT_IQ_S16 4
+/* ctx-free, like the lcs_table_* accessors: the T = 16 * decim taps h[t] */
+int lcs_channelizer_taps(int decim, double *taps /*[16*decim]*/);
+int lcs_channelize(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim,
+                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out);
+/* HIP-event time (ms) of the last lcs_channelize of the context (filter-bank build + the channelizer kernel), as lcs_last_xcorr_ms */
+int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);
+
 /* Stream the context launches on (hipStream_t as void*), for external event timing. */
 void *lcs_stream(lcs_ctx *ctx);
 int lcs_sync(lcs_ctx *ctx);

@@ -237,6 +237,19 @@ class Searcher {
       for (int i = 0; i < cnt[b] && i < max_cells_per_buf; ++i) cells[b].push_back(Cell(out[(size_t)b * max_cells_per_buf + i]));
     pending_ = 0;
   }
+  // Wideband channelizer (lcs_channelize): one wideband capture in DEVICE memory (n_in samples of LCS_FMT_C64 / LCS_FMT_IQ_S8 /
+  // LCS_FMT_IQ_S16 at fs_in) -> f_shift.size() narrowband buffers [n_ch][n_out] complex<float> at fs_in / decim in DEVICE memory,
+  // the LCS_FMT_C64 batch layout.  Queued on the context's stream; a batch enqueued on this Searcher afterwards is ordered behind it.
+  void channelize(const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const std::vector<double> &f_shift, void *d_out,
+                  uint32_t n_out) {
+    check(lcs_channelize(h_, d_wide, fmt, n_in, fs_in, decim, f_shift.empty() ? 0 : &f_shift[0], (int)f_shift.size(), d_out, n_out));
+  }
+  float last_channelize_ms() { float ms = 0; check(lcs_last_channelize_ms(h_, &ms)); return ms; }
+  static std::vector<double> channelizer_taps(int decim) {
+    std::vector<double> h(decim >= 2 && decim <= 16 ? 16 * decim : 0);
+    if (lcs_channelizer_taps(decim, h.empty() ? 0 : &h[0]) != LCS_OK) throw error("lcs_channelizer_taps: decim outside 2..16");
+    return h;
+  }
   void *host_alloc(size_t bytes) { void *p = 0; check(lcs_host_alloc(h_, bytes, &p)); return p; }
   void host_free(void *p) { check(lcs_host_free(h_, p)); }
   static int device_count() { return lcs_device_count(); }

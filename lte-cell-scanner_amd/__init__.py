@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, FMT_C64, FMT_IQ_U8, FMT_C128, STAGE_PSS, STAGE_FULL, MAX_PEAKS
+from .capi import LcsCell, LcsTrackCell, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -67,6 +67,7 @@ class Searcher:
         if rc != 0:
             raise SearcherError(f"lcs_create failed: {capi.ERRORS.get(rc, rc)} (an MI355X is required; no CPU fallback)")
         self._h = h
+        self.device = device
 
     def close(self):
         if getattr(self, "_h", None):
@@ -473,6 +474,22 @@ class Searcher:
     def stream_close(self):
         self._chk(self._lib.lcs_stream_close(self._h), "lcs_stream_close")
 
+    # ---- wideband channelizer (lcs_channelize, include/lcs.h) ---------------------------
+    def channelize(self, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, f_shift, d_out_ptr: int, n_out: int):
+        """One wideband capture in HBM (n_in samples of FMT_C64 / FMT_IQ_S8 / FMT_IQ_S16 at fs_in) -> len(f_shift) narrowband
+        buffers [n_ch][n_out] complex64 at fs_in / decim in HBM at d_out_ptr: mixed down by f_shift (Hz, carrier minus capture
+        centre), low-passed by channelizer_taps(decim), decimated.  Queued on the context's stream; returns at once -- a
+        batch_enqueue(d_out_ptr, FMT_C64, n_ch, n_out, ...) on the same Searcher is ordered behind it."""
+        f = np.ascontiguousarray(np.atleast_1d(f_shift), np.float64)
+        self._chk(self._lib.lcs_channelize(self._h, C.c_void_p(d_wide_ptr), int(fmt), int(n_in), float(fs_in), int(decim), _dp(f), int(f.size),
+                                           C.c_void_p(d_out_ptr), int(n_out)), "lcs_channelize")
+
+    def last_channelize_ms(self) -> float:
+        """HIP-event time (ms) of the last channelize call of this context (lcs_last_channelize_ms)."""
+        ms = C.c_float(0)
+        self._chk(self._lib.lcs_last_channelize_ms(self._h, C.byref(ms)), "lcs_last_channelize_ms")
+        return ms.value
+
     def last_xcorr_ms(self):
         ms, n = C.c_float(0), C.c_int(0)
         self._chk(self._lib.lcs_last_xcorr_ms(self._h, C.byref(ms), C.byref(n)), "lcs_last_xcorr_ms")
@@ -580,3 +597,12 @@ def table_lte_pn(c_init, n):
 
 def chi2cdf_inv(p, k):
     return capi.load().lcs_chi2cdf_inv(p, k)
+
+
+def channelizer_taps(decim: int) -> np.ndarray:
+    """The 16 * decim taps of the channelizer's low-pass (lcs_channelizer_taps): sinc x Kaiser(7.75), sum 1."""
+    o = np.empty(16 * max(int(decim), 0))
+    rc = capi.load().lcs_channelizer_taps(int(decim), _dp(o))
+    if rc != 0:
+        raise SearcherError(f"lcs_channelizer_taps({decim}): {capi.ERRORS.get(rc, rc)}")
+    return o

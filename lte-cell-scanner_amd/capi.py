@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "liblcs_amd.so")
 
 LCS_OK = 0
 FMT_C64, FMT_IQ_U8, FMT_C128 = 0, 1, 2      # FMT_C128: lcs_track_cut only
+FMT_IQ_S8, FMT_IQ_S16 = 3, 4                # wideband captures of lcs_channelize: interleaved signed 8 / 16 bit
 STAGE_PSS, STAGE_FULL = 1, 3
 MAX_PEAKS = 104            # LCS_MAX_PEAKS: the longest list peak_search can return (include/lcs.h)
 ERRORS = {-1: "LCS_ERR_NO_DEVICE", -2: "LCS_ERR_BAD_ARG", -3: "LCS_ERR_HIP", -4: "LCS_ERR_OVERFLOW", -5: "LCS_ERR_NOMEM"}
@@ -68,7 +69,7 @@ EXPORTS = [
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
     "lcs_foe_partial", "lcs_foe_finish", "lcs_foe_contend", "lcs_foe_resolve", "lcs_track_block", "lcs_track_stats", "lcs_track_stream_block", "lcs_track_stream_reset", "lcs_track_cut", "lcs_stream_open", "lcs_stream_push", "lcs_stream_collect", "lcs_stream_close",
     "lcs_last_xcorr_ms", "lcs_last_xcorr_info", "lcs_last_frq_repairs", "lcs_last_frq_repair_stats", "lcs_last_batch_stats", "lcs_last_collect_host_us", "lcs_stream", "lcs_sync", "lcs_table_pss_td", "lcs_table_pss_fd", "lcs_table_sss_fd",
-    "lcs_table_lte_pn", "lcs_chi2cdf_inv",
+    "lcs_table_lte_pn", "lcs_chi2cdf_inv", "lcs_channelizer_taps", "lcs_channelize", "lcs_last_channelize_ms",
 ]
 
 _lib = None
@@ -158,6 +159,9 @@ def load() -> C.CDLL:
         L.lcs_last_batch_stats.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "lcs_last_frq_repair_stats"):
         L.lcs_last_frq_repair_stats.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lcs_channelizer_taps.argtypes = [C.c_int, dp]
+    L.lcs_channelize.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_double, C.c_int, dp, C.c_int, vp, C.c_uint32]
+    L.lcs_last_channelize_ms.argtypes = [vp, fp]
     L.lcs_stream.argtypes = [vp]
     L.lcs_stream.restype = vp
     L.lcs_sync.argtypes = [vp]

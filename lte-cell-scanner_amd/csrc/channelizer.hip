@@ -1,0 +1,289 @@
+// channelizer.hip -- wideband channelizer: one wideband capture in HBM -> n_ch narrowband buffers at fs_in / D, each the
+// input mixed down by its carrier's shift, low-passed by the fixed T = 16 D tap filter and decimated (include/lcs.h,
+// lcs_channelize).  Output k, sample m:
+//
+//     y_k[m] = sum_t h[t] x[mD + T-1-t] exp(-i w_k (mD + T-1-t))
+//            = exp(-i w_k mD) * sum_j g_k[j] x[mD + j],          g_k[j] = h[T-1-j] exp(-i w_k j),  j = T-1-t
+//
+// The sum is a strided-Toeplitz GEMM and runs on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, a
+// k-ordered fma chain).  As a REAL product: the interleaved (re, im) float stream xf of the capture is the B operand as it
+// stands -- B[kk][m] = xf[2 D m + kk], kk = 2 j + c -- and a carrier is two rows of A over kk:
+//     row (k, re): [ g_re(j), -g_im(j) ]      row (k, im): [ g_im(j),  g_re(j) ]
+// A tile of A is 32 rows = 16 carriers; a workgroup (4 waves) owns 16 carriers x 256 outputs, each wave two 32 x 32 tiles
+// that share one A operand.  The (256 + 15) D input samples the workgroup's windows span are converted to float once and
+// staged in LDS as rows of D samples with an odd row stride (2 D + 1 floats): lane (m, c) of a B operand reads row
+// m + j / D, column 2 (j % D) + c, so the 32 columns of a tile fall into different banks for every D.  The filter bank
+// k_chan_tables builds per call sits in the context's table in the lane order of the A operand, four k-steps to a
+// 16-byte load, and is read through the caches (64 KB per 16 carriers at D = 16, the same for every workgroup of a row
+// block).  The carrier phase of output m is step_k * (m D) in 64-bit fixed point (2^64 = one turn), wrapped exactly; its
+// top 32 bits feed sinpif / cospif.  The per-tap phases of g_k come from the same accumulator through double sinpi / cospi.
+#include "channelizer.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <unordered_map>
+
+typedef float ch_f32x16 __attribute__((ext_vector_type(16)));
+typedef float ch_f32x4 __attribute__((ext_vector_type(4)));
+
+#define CH_CARRIERS 16                 // carriers per A tile (32 rows)
+#define CH_NT 256                      // outputs per workgroup: 4 waves x 2 tiles x 32 columns
+#define CH_XROWS (CH_NT + 15)          // LDS rows of D samples: the windows of CH_NT outputs span (CH_NT + 15) D samples
+#define CH_SMAX (2 * 16 + 1)           // row stride in floats at D = 16
+
+// Kaiser window's I0 by its power series (x <= 7.75: 40 terms reach 1e-17 relative)
+static double chan_i0(double x) {
+  const double q = 0.25 * x * x;
+  double term = 1.0, sum = 1.0;
+  for (int k = 1; k < 64; ++k) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < 1e-18 * sum) break;
+  }
+  return sum;
+}
+
+// h[t] = sinc((t - (T-1)/2) / D) * kaiser(T, 7.75)[t], normalised to sum 1 (include/lcs.h)
+void lcs_chan_taps(int decim, double *taps) {
+  const int T = 16 * decim;
+  const double alpha = 0.5 * (T - 1), beta = 7.75, i0b = chan_i0(beta);
+  double sum = 0;
+  for (int t = 0; t < T; ++t) {
+    const double y = M_PI * ((t - alpha) / decim);      // never 0: T is even
+    const double r = (t - alpha) / alpha;
+    taps[t] = std::sin(y) / y * (chan_i0(beta * std::sqrt(1.0 - r * r)) / i0b);
+    sum += taps[t];
+  }
+  for (int t = 0; t < T; ++t) taps[t] /= sum;
+}
+
+// 2^64 x frac(df / fs_in), |df / fs_in| <= 1/2 (two's complement: a negative shift is its own wrap-around)
+unsigned long long lcs_chan_step(double f_shift, double fs_in) {
+  const double v = std::ldexp(f_shift / fs_in, 64);
+  if (v >= 0x1p63) return 1ull << 63;
+  return (unsigned long long)(long long)std::llrint(v);
+}
+
+// The filter bank in A-operand order: tab[((rb * T/4 + s4) * 64 + lane) * 4 + i] = A[row lane & 31 of block rb][kk = 2 (4 s4 + i) + (lane >> 5)]
+__global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *__restrict__ step, const float *__restrict__ taps,
+                                                     int n_ch, int D, int n_rb, float *__restrict__ tab) {
+  const int T = 16 * D, q4 = T / 4;
+  const size_t total = (size_t)n_rb * T * 64;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e & 3), l = (int)((e >> 2) & 63);
+    const size_t rest = e >> 8;
+    const int s4 = (int)(rest % q4), rb = (int)(rest / q4);
+    const int s = 4 * s4 + i, r = l & 31, c = l >> 5;
+    const int ch = rb * CH_CARRIERS + (r >> 1), ri = r & 1;
+    float v = 0.f;
+    if (ch < n_ch) {
+      const unsigned long long ph = step[ch] * (unsigned long long)s;
+      const double ht = 2.0 * ((double)(long long)ph * 0x1p-64);      // half-turns, [-1, 1)
+      const double h = (double)taps[T - 1 - s];
+      const double g_re = h * cospi(ht), g_im = -h * sinpi(ht);
+      v = (float)(ri == 0 ? (c == 0 ? g_re : -g_im) : (c == 0 ? g_im : g_re));
+    }
+    tab[e] = v;
+  }
+}
+
+template <int FMT>
+__device__ __forceinline__ float2 chan_sample(const void *x, unsigned long long n) {
+  if (FMT == LCS_FMT_C64) return ((const float2 *)x)[n];
+  if (FMT == LCS_FMT_IQ_S16) {
+    const uint32_t p = ((const uint32_t *)x)[n];
+    return make_float2((float)(int)(int16_t)(p & 0xFFFFu) * (1.f / 32768.f), (float)(int)(int16_t)(p >> 16) * (1.f / 32768.f));
+  }
+  const uint32_t p = ((const uint16_t *)x)[n];
+  return make_float2((float)(int)(int8_t)(p & 255u) * (1.f / 128.f), (float)(int)(int8_t)(p >> 8) * (1.f / 128.f));
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, unsigned long long n_in, int D,
+                                                    const float *__restrict__ tab, const unsigned long long *__restrict__ step,
+                                                    int n_ch, float2 *__restrict__ out, unsigned n_out) {
+  __shared__ float xs[CH_XROWS * CH_SMAX];
+  const int S = 2 * D + 1, T = 16 * D;
+  const unsigned m0 = blockIdx.x * CH_NT;
+  const int rb = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the samples [m0 D, (m0 + CH_XROWS) D) as floats; beyond the capture's end zeros (only outputs >= n_out read them)
+  const unsigned long long n0 = (unsigned long long)m0 * D;
+  for (int idx = tid; idx < CH_XROWS * D; idx += 256) {
+    const int row = idx / D, p = idx - row * D;
+    const unsigned long long n = n0 + (unsigned)idx;
+    const float2 v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
+    xs[row * S + 2 * p] = v.x;
+    xs[row * S + 2 * p + 1] = v.y;
+  }
+  __syncthreads();
+  ch_f32x16 acc0, acc1;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; }
+  const ch_f32x4 *ap = (const ch_f32x4 *)tab + (size_t)rb * (T / 4) * 64 + lane;
+  const float *b0 = xs + (wave * 64 + (lane & 31)) * S + (lane >> 5);
+  const float *b1 = b0 + 32 * S;
+  int q = 0, p = 0;      // k-step s = q D + p (uniform)
+  ch_f32x4 a_next = ap[0];
+  for (int s4 = 0; s4 < T / 4; ++s4) {
+    const ch_f32x4 a = a_next;
+    a_next = ap[(size_t)std::min(s4 + 1, T / 4 - 1) * 64];      // the next four k-steps' operands load under this step's MFMAs
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int off = q * S + 2 * p;
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b0[off], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b1[off], acc1, 0, 0, 0);
+      if (++p == D) { p = 0; ++q; }
+    }
+  }
+  // register v of a lane: row (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of the tile, column lane & 31; row = 2 carrier + (re | im)
+  const int h = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const unsigned m = m0 + wave * 64 + t * 32 + (lane & 31);
+    if (m >= n_out) continue;
+    const unsigned long long nd = (unsigned long long)m * (unsigned)D;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+      for (int bb = 0; bb < 2; ++bb) {
+        const int ch = rb * CH_CARRIERS + 4 * a + 2 * h + bb;
+        if (ch >= n_ch) continue;
+        const unsigned long long ph = step[ch] * nd;
+        const float ht = (float)(int)(unsigned)(ph >> 32) * 0x1p-31f;      // half-turns of the carrier phase at sample m D
+        const float sn = sinpif(ht), cs = cospif(ht);
+        const float re = t ? acc1[4 * a + 2 * bb] : acc0[4 * a + 2 * bb];
+        const float im = t ? acc1[4 * a + 2 * bb + 1] : acc0[4 * a + 2 * bb + 1];
+        out[(size_t)ch * n_out + m] = make_float2(re * cs + im * sn, im * cs - re * sn);
+      }
+    }
+  }
+}
+
+// Per-context state, kept here (keyed by the context) and released by lcs_chan_free from lcs_destroy
+struct ChanState {
+  void *chan_par = nullptr;                     // device: [n_ch] phase steps, then the taps
+  size_t chan_par_bytes = 0;
+  float *chan_tab = nullptr;                    // device: the filter bank in A-operand order
+  size_t chan_tab_floats = 0;
+  void *chan_hpin[2] = {nullptr, nullptr};      // page-locked parameter slots, used in turn
+  size_t chan_hpin_bytes[2] = {0, 0};
+  hipEvent_t ev_chan_slot[2] = {nullptr, nullptr};
+  int chan_slot = 0;
+  hipEvent_t ev_chan0 = nullptr, ev_chan1 = nullptr;
+  bool chan_timed = false;
+};
+static std::mutex g_chan_mu;
+static std::unordered_map<const lcs_ctx *, ChanState *> g_chan;
+
+static ChanState *chan_state(const lcs_ctx *c, bool create) {
+  std::lock_guard<std::mutex> lk(g_chan_mu);
+  auto it = g_chan.find(c);
+  if (it != g_chan.end()) return it->second;
+  if (!create) return nullptr;
+  ChanState *st = new ChanState();
+  g_chan[c] = st;
+  return st;
+}
+
+// One call's parameters on their way to the device: [n_ch] phase steps, then T taps as float.  Two page-locked slots used in
+// turn, each guarded by the event behind its copy, so a call never waits for the GPU unless three calls are in flight.
+static int chan_slot(lcs_ctx *c, ChanState *st, size_t bytes, int *slot) {
+  const int k = st->chan_slot ^= 1;
+  if (!st->ev_chan_slot[k]) HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan_slot[k], hipEventDisableTiming));
+  else HIPCHK(c, hipEventSynchronize(st->ev_chan_slot[k]));
+  if (bytes > st->chan_hpin_bytes[k]) {
+    if (st->chan_hpin[k]) (void)hipHostFree(st->chan_hpin[k]);
+    st->chan_hpin[k] = nullptr; st->chan_hpin_bytes[k] = 0;
+    HIPCHK(c, hipHostMalloc(&st->chan_hpin[k], bytes, hipHostMallocDefault));
+    st->chan_hpin_bytes[k] = bytes;
+  }
+  *slot = k;
+  return LCS_OK;
+}
+
+int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
+                          int n_ch, void *d_out, uint32_t n_out) {
+  ChanState *st = chan_state(c, true);
+  const int T = 16 * decim, n_rb = (n_ch + CH_CARRIERS - 1) / CH_CARRIERS;
+  const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 256 * sizeof(float);
+  const size_t tab_floats = (size_t)n_rb * 64 * T;
+  if (par_bytes > st->chan_par_bytes || tab_floats > st->chan_tab_floats) {      // grown on demand (earlier calls may still read the old ones)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (par_bytes > st->chan_par_bytes) {
+      if (st->chan_par) (void)hipFree(st->chan_par);
+      st->chan_par = nullptr; st->chan_par_bytes = 0;
+      HIPCHK(c, hipMalloc((void **)&st->chan_par, par_bytes));
+      st->chan_par_bytes = par_bytes;
+    }
+    if (tab_floats > st->chan_tab_floats) {
+      if (st->chan_tab) (void)hipFree(st->chan_tab);
+      st->chan_tab = nullptr; st->chan_tab_floats = 0;
+      HIPCHK(c, hipMalloc((void **)&st->chan_tab, tab_floats * sizeof(float)));
+      st->chan_tab_floats = tab_floats;
+    }
+  }
+  if (!st->ev_chan0) {
+    HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan0, LCS_EVENT_NOFENCE));
+    HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan1, LCS_EVENT_NOFENCE));
+  }
+  int k = 0, rc = chan_slot(c, st, par_bytes, &k);
+  if (rc) return rc;
+  unsigned long long *h_step = (unsigned long long *)st->chan_hpin[k];
+  float *h_taps = (float *)(h_step + n_ch);
+  for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);
+  double taps[256];
+  lcs_chan_taps(decim, taps);
+  for (int t = 0; t < T; ++t) h_taps[t] = (float)taps[t];
+  const size_t up = (size_t)n_ch * sizeof(unsigned long long) + T * sizeof(float);
+  HIPCHK(c, hipMemcpyAsync(st->chan_par, h_step, up, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(st->ev_chan_slot[k], c->stream));
+  const unsigned long long *d_step = (const unsigned long long *)st->chan_par;
+  const float *d_taps = (const float *)(d_step + n_ch);
+  HIPCHK(c, hipEventRecord(st->ev_chan0, c->stream));
+  const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_chan_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, decim, n_rb, st->chan_tab);
+  const dim3 grid((n_out + CH_NT - 1) / CH_NT, n_rb);
+  if (fmt == LCS_FMT_C64)
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_C64>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+                       d_step, n_ch, (float2 *)d_out, n_out);
+  else if (fmt == LCS_FMT_IQ_S16)
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S16>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+                       d_step, n_ch, (float2 *)d_out, n_out);
+  else
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S8>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+                       d_step, n_ch, (float2 *)d_out, n_out);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(st->ev_chan1, c->stream));
+  st->chan_timed = true;
+  return LCS_OK;
+}
+
+int lcs_chan_last_ms(lcs_ctx *c, float *ms) {
+  ChanState *st = chan_state(c, false);
+  if (!st || !st->chan_timed) { c->err = "lcs_last_channelize_ms: no lcs_channelize call on this context yet"; return LCS_ERR_BAD_ARG; }
+  HIPCHK(c, hipEventSynchronize(st->ev_chan1));
+  HIPCHK(c, hipEventElapsedTime(ms, st->ev_chan0, st->ev_chan1));
+  return LCS_OK;
+}
+
+void lcs_chan_free(lcs_ctx *c) {
+  ChanState *st = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(g_chan_mu);
+    auto it = g_chan.find(c);
+    if (it == g_chan.end()) return;
+    st = it->second;
+    g_chan.erase(it);
+  }
+  if (st->chan_par) (void)hipFree(st->chan_par);
+  if (st->chan_tab) (void)hipFree(st->chan_tab);
+  for (int k = 0; k < 2; ++k) {
+    if (st->chan_hpin[k]) (void)hipHostFree(st->chan_hpin[k]);
+    if (st->ev_chan_slot[k]) (void)hipEventDestroy(st->ev_chan_slot[k]);
+  }
+  if (st->ev_chan0) (void)hipEventDestroy(st->ev_chan0);
+  if (st->ev_chan1) (void)hipEventDestroy(st->ev_chan1);
+  delete st;
+}

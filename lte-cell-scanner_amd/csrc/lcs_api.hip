@@ -8,6 +8,7 @@
 #include <chrono>
 
 #include "lcs_internal.h"
+#include "channelizer.h"
 
 namespace {
 
@@ -412,6 +413,7 @@ void lcs_destroy(lcs_ctx *c) {
                   c->trk_meta, c->trk_rs, c->trk_fmeta, c->trk_pw, c->trk_idx, c->trk_small, c->trk_cells, c->trk_acfd, c->trk_actd,
                   c->trk_syncce, c->trk_sync, c->d_flag, c->trk_cut_hit, c->trk_cut_meta, c->c64_u8};
   for (void *p : ptrs) if (p) (void)hipFree(p);
+  lcs_chan_free(c);
   if (c->h_pinned) (void)hipHostFree(c->h_pinned);
   if (c->res_pack) (void)hipFree(c->res_pack);
   if (c->h_res) (void)hipHostFree(c->h_res);
@@ -1368,6 +1370,38 @@ int lcs_last_xcorr_info(lcs_ctx *c, double *executed_ops, const char **kernel) {
   if (executed_ops) *executed_ops = c->last_xc_ops;
   if (kernel) *kernel = c->last_xc_kernel;
   return LCS_OK;
+}
+
+// ----------------------------------------------------------------------- channelizer
+int lcs_channelizer_taps(int decim, double *taps) {
+  if (decim < 2 || decim > 16 || !taps) return LCS_ERR_BAD_ARG;
+  lcs_chan_taps(decim, taps);
+  return LCS_OK;
+}
+
+int lcs_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift, int n_ch,
+                   void *d_out, uint32_t n_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  auto bad = [&](const char *what) { c->err = std::string("lcs_channelize: ") + what; return LCS_ERR_BAD_ARG; };
+  if (!d_wide || !f_shift || !d_out) return bad("null pointer");
+  if (decim < 2 || decim > 16) return bad("decim outside 2..16");
+  if (n_ch < 1) return bad("n_ch < 1");
+  if (n_out < 1) return bad("n_out < 1");
+  if (!(fs_in > 0) || !std::isfinite(fs_in)) return bad("fs_in is not a positive rate");
+  if (n_in < ((uint64_t)n_out - 1) * decim + 16ull * decim) return bad("n_in < (n_out-1)*decim + 16*decim: the capture is too short for n_out outputs");
+  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_S8 && fmt != LCS_FMT_IQ_S16) return bad("unknown sample format");
+  for (int k = 0; k < n_ch; ++k)
+    if (!(std::fabs(f_shift[k]) <= 0.5 * fs_in)) return bad("|f_shift| > fs_in/2");
+  if (reinterpret_cast<uintptr_t>(d_out) & 15) return bad("d_out is not 16-byte aligned");
+  const uintptr_t in_align = fmt == LCS_FMT_C64 ? 7 : fmt == LCS_FMT_IQ_S16 ? 3 : 1;
+  if (reinterpret_cast<uintptr_t>(d_wide) & in_align) return bad("d_wide is not aligned to its sample size");
+  HIPCHK(c, hipSetDevice(c->device));
+  return lcs_launch_channelize(c, d_wide, fmt, n_in, fs_in, decim, f_shift, n_ch, d_out, n_out);
+}
+
+int lcs_last_channelize_ms(lcs_ctx *c, float *ms) {
+  if (!c || !ms) return LCS_ERR_BAD_ARG;
+  return lcs_chan_last_ms(c, ms);
 }
 
 // ---------------------------------------------------------------------------- tables

@@ -368,3 +368,54 @@ def make_batch_u8(n_buf, seed, fc_list, occupied_every=4, n_distinct=8, cells_cy
         else:
             out[b] = np.clip(np.rint(rng.normal(127.0, 19.0, 2 * N_CAP)), 0, 255).astype(np.uint8)
     return out
+
+
+def make_wideband(seed, fc_centre, decim, placed, snr_db=10.0, fmt=capi.FMT_IQ_S16, n_in=None, rms=0.15):
+    """One wideband capture at decim x 1.92 Msps centred on fc_centre, as a wideband front end (USRP, HackRF, bladeRF, an sc16 / sc8
+    recording) would deliver it: what lcs_channelize takes.
+
+    placed: list of (carrier_hz, cells) -- cells as for make_capbuf.  Every carrier's noise-free 1.92 Msps signal comes from
+    make_signal (n_in / decim samples), is band-limited-interpolated by decim (its spectrum zero-stuffed to the wide rate), shifted
+    by carrier_hz - fc_centre and summed.  Then ONE AWGN at the wide rate -- snr_db below the PSS/SSS sample power of a cell with
+    gain_db = 0 inside a 1.92 MHz channel, i.e. decim times that over the whole band -- AGC to `rms` and quantisation:
+    fmt FMT_IQ_S8 (interleaved int8, value v / 128), FMT_IQ_S16 (interleaved int16, v / 32768) or FMT_C64 (complex64, none).
+    Returns (capture, truth): truth is a list of (carrier_hz, make_signal's truth of that carrier)."""
+    decim = int(decim)
+    n_in = N_CAP * decim if n_in is None else int(n_in)
+    n_nb = -(-n_in // decim)
+    n_nb += n_nb & 1
+    n_w = n_nb * decim
+    rng = np.random.default_rng(seed)
+    n = np.arange(n_w, dtype=np.float64)
+    fs_in = FS * decim
+    wide = np.zeros(n_w, np.complex128)
+    truth = []
+    for carrier, cells in placed:
+        sig, _, tr = make_signal(rng, float(carrier), cells, n_nb)
+        X = np.fft.fft(sig)
+        Xw = np.zeros(n_w, np.complex128)
+        Xw[:n_nb // 2] = X[:n_nb // 2]
+        Xw[-(n_nb // 2) + 1:] = X[n_nb // 2 + 1:]          # (the Nyquist bin of the narrow signal is dropped)
+        wide += (np.fft.ifft(Xw) * decim) * np.exp(2j * np.pi * ((float(carrier) - float(fc_centre)) / fs_in) * n)
+        truth.append((float(carrier), tr))
+    noise_pow = decim * (62.0 / 128.0) / 10 ** (snr_db / 10)
+    x = (wide + np.sqrt(noise_pow / 2) * (rng.standard_normal(n_w) + 1j * rng.standard_normal(n_w)))[:n_in]
+    x *= rms / np.sqrt(np.mean(np.abs(x) ** 2))
+    if fmt == capi.FMT_C64:
+        return x.astype(np.complex64), truth
+    if fmt not in (capi.FMT_IQ_S8, capi.FMT_IQ_S16):
+        raise ValueError("make_wideband: fmt is FMT_IQ_S8, FMT_IQ_S16 or FMT_C64")
+    dt, sc = (np.int8, 128.0) if fmt == capi.FMT_IQ_S8 else (np.int16, 32768.0)
+    iq = np.empty(2 * n_in, dt)
+    iq[0::2] = np.clip(np.rint(sc * x.real), -sc, sc - 1).astype(dt)
+    iq[1::2] = np.clip(np.rint(sc * x.imag), -sc, sc - 1).astype(dt)
+    return iq, truth
+
+
+def wideband_to_complex(iq, fmt):
+    """The values a wideband capture stands for (what lcs_channelize makes of it on the device)."""
+    if fmt == capi.FMT_C64:
+        return np.asarray(iq, np.complex64).astype(np.complex128)
+    sc = 128.0 if fmt == capi.FMT_IQ_S8 else 32768.0
+    a = np.asarray(iq, np.int8 if fmt == capi.FMT_IQ_S8 else np.int16).astype(np.float64)
+    return (a[0::2] + 1j * a[1::2]) / sc

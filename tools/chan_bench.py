@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Wideband channelizer against the stage it feeds, on one GPU in one process.
+
+(a) lcs_last_channelize_ms of one call: decim 16, s16 capture of 80 ms at 30.72 Msps, 256 carriers on the 100 kHz raster,
+    n_out = 153584.
+(b) GPU time of search_batch on those 256 LCS_FMT_C64 buffers at n_f = 31, full chain, as two batches of 128 (the batch
+    size bench.py and sweep.search_wideband use): HIP events on the context's stream around enqueue .. collect.
+Both are medians of 20 timings after 3 warm-ups.  The wideband pipeline keeps 1 / (1 + a / b) of the float path's buffer
+rate; the target is a <= 0.25 b.  Writes one JSON document (--out) and prints it.
+
+    python tools/chan_bench.py --out profiles/channelizer/chan_bench.json
+"""
+import argparse
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def sclk_sampler(device, samples, stop):
+    while not stop.is_set():
+        try:
+            p = subprocess.run(["rocm-smi", "-d", str(device), "--showclocks", "--json"], capture_output=True, text=True, timeout=5)
+            card = next(iter(json.loads(p.stdout).values()))
+            v = next((v for k, v in card.items() if "sclk" in k.lower() and "mhz" in str(v).lower()), None)
+            if v is not None:
+                samples.append(float("".join(ch for ch in str(v) if ch.isdigit() or ch == ".")))
+        except Exception:
+            return
+        stop.wait(0.2)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channelizer", "chan_bench.json"))
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--cells", type=int, default=8, help="cells planted across the band (every 32nd carrier)")
+    args = ap.parse_args()
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    D, N_CH, N_OUT, FC0 = 16, 256, 153584, 740.0e6
+    fs_in, n_in = D * 1.92e6, 153600 * D
+    carriers = FC0 + 100e3 * (np.arange(N_CH) - N_CH // 2)
+    rng = np.random.default_rng(5)
+    placed = [(float(carriers[16 + 32 * i]), [dict(n_id_1=int(rng.integers(0, 168)), n_id_2=int(rng.integers(0, 3)), cp_normal=bool(i % 4 != 3),
+                                                   n_ports=int((1, 2, 2, 4)[i % 4]), n_rb_dl=int((6, 15, 25, 50, 75, 100)[i % 6]),
+                                                   f_off=float(rng.uniform(-60e3, 60e3)), gain_db=float(rng.uniform(0, 6)))]) for i in range(args.cells)]
+    iq, _ = pkg.synth.make_wideband(77, FC0, D, placed, 10.0, pkg.FMT_IQ_S16)
+    dev = torch.device("cuda", args.device)
+    d_wide = torch.from_numpy(iq).to(dev)
+    d_out = torch.empty((N_CH, N_OUT), dtype=torch.complex64, device=dev)
+    f = pkg.f_search_set_for(739e6, 100)
+    torch.cuda.synchronize(dev)
+    samples, stop = [], threading.Event()
+    th = threading.Thread(target=sclk_sampler, args=(args.device, samples, stop), daemon=True)
+    with pkg.Searcher(args.device) as s:
+        stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
+        th.start()
+        a_ms = []
+        for i in range(args.warmup + args.reps):
+            s.channelize(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, D, carriers - FC0, d_out.data_ptr(), N_OUT)
+            a_ms.append(s.last_channelize_ms())
+        s.sync()
+        b_ms, n_cells = [], 0
+        for i in range(args.warmup + args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            n_cells = 0
+            for h in range(2):
+                sl = slice(128 * h, 128 * h + 128)
+                cells = s.search_batch(d_out[128 * h].data_ptr(), pkg.FMT_C64, 128, N_OUT, f, carriers[sl], carriers[sl], 1.92e6, pkg.STAGE_FULL)
+                n_cells += sum(len(c) for c in cells)
+            e1.record(stream)
+            e1.synchronize()
+            b_ms.append(e0.elapsed_time(e1))
+        stop.set()
+        th.join(timeout=10)
+    a, b = float(np.median(a_ms[args.warmup:])), float(np.median(b_ms[args.warmup:]))
+    spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "tools", "code_objects.py"))
+    co = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(co)
+    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items() if "k_channelize" in k or "k_chan_tables" in k}
+    res = {"a_channelize_ms": a, "b_search_256_ms": b, "ratio_a_over_b": a / b, "target_ratio": 0.25, "meets_target": bool(a <= 0.25 * b),
+           "buffer_rate_kept": 1.0 / (1.0 + a / b),
+           "config": {"decim": D, "fmt": "s16", "n_ch": N_CH, "n_in": n_in, "n_out": N_OUT, "raster_hz": 100e3, "n_f": int(f.size), "batches": "2 x 128",
+                      "stage": "full", "reps": args.reps, "warmup": args.warmup, "cells_planted": args.cells, "cells_decoded_per_256": n_cells},
+           "a_ms_min_max": [float(min(a_ms[args.warmup:])), float(max(a_ms[args.warmup:]))],
+           "b_ms_min_max": [float(min(b_ms[args.warmup:])), float(max(b_ms[args.warmup:]))],
+           "channelizer_tflops_fp32": 8.0 * N_CH * 16 * D * N_OUT / (a * 1e-3) / 1e12,
+           "sclk_mhz_median": (sorted(samples)[len(samples) // 2] if samples else None), "sclk_samples": len(samples),
+           "device": torch.cuda.get_device_name(dev), "kernels": ks}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
