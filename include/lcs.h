@@ -111,7 +111,7 @@ int lcs_set_max_cells_in_flight(lcs_ctx *ctx, int n);
  * themselves and correlate the bytes (int8 kernel); for device-resident LCS_FMT_C64 batches the same check is opt-in, because it costs
  * lcs_batch_enqueue a host synchronisation: with on != 0 every such batch is first checked on the device (one pass that also writes the
  * bytes; the host waits for the verdict while the other contexts' kernels keep the GPU busy) and, if every component of every buffer
- * is on the 8-bit grid, takes the u8 route from there -- the same numbers through the int8 kernel (1.4 x the fp16 kernel's rate) and
+ * compares equal to one of the 256 values (one ulp beside one, or a tiny value, is no dongle data), takes the u8 route from there -- the same numbers through the int8 kernel (1.4 x the fp16 kernel's rate) and
  * the caller's buffer is not read again after the call returns; anything else takes the fp16 kernel as before (and the next fifteen
  * batches of the context are not checked).  Off by default.  Results do not depend on it. */
 int lcs_set_float_batch_probe(lcs_ctx *ctx, int on);
@@ -275,11 +275,16 @@ int lcs_batch_readback(lcs_ctx *ctx, int buf, float *xc_incoherent_single /*[3][
 int lcs_last_frq_repairs(lcs_ctx *ctx, int *n_positions);
 /* The repair's work is bounded: real captures list ~2 positions per buffer, but a degenerate input (duplicated entries of
  * f_search_set make every position an exact tie) lists all 3 x 9600.  Once a call lists more than 32 positions per repair
- * workgroup (256 for one buffer, 16384 for a 128-buffer batch) only positions whose power reaches their Z_th1 -- the ones a peak can
+ * workgroup (2048 for up to eight buffers, 16384 for a 128-buffer batch) only positions whose power reaches their Z_th1 -- the ones a peak can
  * come from -- are recomputed, and each workgroup stops after 256 candidates; *n_unrepaired counts the listed positions left with
  * the correlation kernel's own arg-max (0 on any real data; for exact duplicates that arg-max is the reference's anyway:
  * identical templates give identical values and the first one wins). */
 int lcs_last_frq_repair_stats(lcs_ctx *ctx, int *n_listed, int *n_unrepaired);
+/* The relative margin below which the two best hypotheses of a position count as a near-tie and are listed for the repair.  The
+ * listing catches every position where the correlation kernels could order two hypotheses differently from the reference iff every
+ * compared value lies within HALF this margin (relative) of the reference's: the bound the test suite asserts on
+ * xc_incoherent_single, the array the compared box-filter means are formed from. */
+double lcs_frq_tie_eps(void);
 /* HIP-event time (ms) of the PSS correlation kernel launches of the last enqueue, and the
  * number of launches it covers; used by bench.py for the roofline figure. */
 int lcs_last_xcorr_ms(lcs_ctx *ctx, float *ms, int *n_launches);

@@ -509,6 +509,11 @@ class Searcher:
         self._chk(self._lib.lcs_last_frq_repair_stats(self._h, C.byref(a), C.byref(b)), "lcs_last_frq_repair_stats")
         return a.value, b.value
 
+    @staticmethod
+    def frq_tie_eps() -> float:
+        """The library's near-tie margin (lcs_frq_tie_eps): the correlation kernels must hold half of it on xc_incoherent_single."""
+        return frq_tie_eps()
+
     def last_batch_stats(self):
         """Counters of the last collected batch (lcs_last_batch_stats): dict with cells_past_sss and pbch_candidates_decoded among them."""
         a = (C.c_int * 8)()
@@ -539,6 +544,11 @@ class Searcher:
 
     def sync(self):
         self._chk(self._lib.lcs_sync(self._h), "lcs_sync")
+
+
+def frq_tie_eps() -> float:
+    """Relative margin below which the two best hypotheses of a position are a near-tie for the repair (lcs_frq_tie_eps)."""
+    return float(capi.load().lcs_frq_tie_eps())
 
 
 def device_count() -> int:

@@ -9,6 +9,7 @@
 
 #include "lcs_internal.h"
 #include "channelizer.h"
+#include "lte_device.h"
 
 namespace {
 
@@ -263,22 +264,19 @@ constexpr int kMaxTapsI8 = LCS_I8_MAX_TAPS;                               // int
 constexpr int kMaxTapsF32 = 2 * (LCS_KP2_MAX - LCS_KP2_UNROLL);          // fp32 kernel: 124 tap pairs
 
 // lcs_set_float_batch_probe: is a batch of complex<float> buffers dongle data -- every component exactly (u8 - 127) / 128 (ref
-// src/capbuf.cpp:172-181)?  One pass: the byte each component would have come from, and whether it reproduces the component exactly
-// (x 128 + 127 is exact in fp32 for such values; NaN, infinities and anything off the 8-bit grid fail).  The bytes are then handed to
-// the u8 route unchanged (int8 copies, int8 correlation kernel, the fp64 stages on the int8 pairs): the same numbers, the faster kernel.
+// src/capbuf.cpp:172-181)?  One pass: per component dongle_component_f32 (lte_device.h) decides on the exact product x * 128 and
+// names the byte it came from; a component that does not compare equal to one of the 256 values -- one ulp beside one, tiny, NaN,
+// infinite -- clears the flag.  The bytes are then handed to the u8 route unchanged (int8 copies, int8 correlation kernel, the
+// fp64 stages on the int8 pairs): the same numbers, the faster kernel.
 __global__ __launch_bounds__(256) void k_c64_probe_u8(const float *__restrict__ src, size_t n_comp, uint8_t *__restrict__ dst, int *__restrict__ flag) {
   bool ok = true;
   for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n_comp; i += (size_t)gridDim.x * blockDim.x * 4) {
     const float4 x = *reinterpret_cast<const float4 *>(src + i);      // (n_comp = 2 n_cap n_buf is a multiple of 4 for the batch shapes the library takes: checked by the caller)
-    const float v[4] = {x.x * 128.0f + 127.0f, x.y * 128.0f + 127.0f, x.z * 128.0f + 127.0f, x.w * 128.0f + 127.0f};
+    const float v[4] = {x.x, x.y, x.z, x.w};
     uchar4 b;
     unsigned char *pb = reinterpret_cast<unsigned char *>(&b);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float r = rintf(v[q]);
-      ok = ok && v[q] == r && r >= 0.0f && r <= 255.0f;
-      pb[q] = (unsigned char)(int)fminf(fmaxf(r, 0.0f), 255.0f);
-    }
+    for (int q = 0; q < 4; ++q) ok = dongle_component_f32(v[q], pb + q) && ok;
     *reinterpret_cast<uchar4 *>(dst + i) = b;
   }
   if (__any(!ok) && (threadIdx.x & 63) == 0) atomicAnd(flag, 0);
@@ -1353,6 +1351,8 @@ int lcs_last_frq_repairs(lcs_ctx *c, int *n_positions) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
 }
+
+double lcs_frq_tie_eps(void) { return (double)LCS_FRQ_TIE_EPS; }
 
 int lcs_last_frq_repair_stats(lcs_ctx *c, int *n_listed, int *n_unrepaired) {
   if (!c || !n_listed || !n_unrepaired || !c->n_fix) return LCS_ERR_BAD_ARG;

@@ -39,8 +39,9 @@
 #define LCS_PS 336           // LDS plane stride in floats: >= 64 + 2*KP2_MAX, == 16 (mod 32)
 #define LCS_MAXP LCS_MAX_PEAKS   // peaks kept per capture buffer: the most peak_search can return (lcs.h)
 // xc_incoherent_collapsed_frq: positions whose two best hypotheses lie within this (relative) of each other are recomputed in the
-// reference's arithmetic (k_frq_repair, pss_xcorr.hip).  The correlation kernels' values deviate from the reference's by ~1e-7
-// (worst element ever measured: 1e-6 of the buffer's largest); two values further apart than this keep their order.
+// reference's arithmetic (k_frq_repair, pss_xcorr.hip).  Two values further apart than this keep their order as long as every
+// element of xc_incoherent_single is within HALF of it (relative) of the reference's: the suite asserts that on every array it
+// compares (worst measured 1.8e-6: the int8 kernel on a two-window buffer).  lcs_frq_tie_eps() hands it out.
 #define LCS_FRQ_TIE_EPS 4e-6f
 #define LCS_I8_KB 5          // 32-tap blocks of the int8 correlation kernel
 #define LCS_I8_OFF 16        // int8 kernel: a template column's delay inside its group (window-start spread) stays below this

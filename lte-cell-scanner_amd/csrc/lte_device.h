@@ -32,6 +32,24 @@ __host__ __device__ __forceinline__ cd2 cis_small(double x) {
   c_ = fma(c_, z, 1.0);
   return mk(c_, x * s_);
 }
+// Is one component of a capture a dongle sample, (b - 127) / 128 for a byte b (ref src/capbuf.cpp:172-181)?  Accepted iff it
+// COMPARES EQUAL to one of those 256 values (-0.0 as 0.0 -> b = 127); *byte = b only then (127 otherwise).  The decision is made
+// on k = x * 128: a power-of-two scale is exact in either type (a subnormal only grows), where x * 128 + 127 rounds -- in fp32
+// it takes everything within half an ulp of the sum onto a grid point, every |x| < 2^-25 onto byte 127.  NaN and the infinities
+// fail the comparisons; subnormals stay off the grid (the library is built without flush-to-zero: tests/test_gpu_configs.py plants one).
+// k_c64_probe_u8 (float batches) and k_ingest_c128 (host buffers) decide by it; tests/test_probe_host.py runs the float
+// flavour over all 2^32 bit patterns on the host.
+__host__ __device__ __forceinline__ float dongle_rint(float k) { return rintf(k); }
+__host__ __device__ __forceinline__ double dongle_rint(double k) { return rint(k); }
+template <typename T>
+__host__ __device__ __forceinline__ bool dongle_component(T x, unsigned char *byte) {
+  const T k = x * (T)128;
+  const bool ok = k == dongle_rint(k) && k >= (T)-127 && k <= (T)128;
+  *byte = ok ? (unsigned char)((int)k + 127) : (unsigned char)127;
+  return ok;
+}
+__host__ __device__ __forceinline__ bool dongle_component_f32(float x, unsigned char *byte) { return dongle_component<float>(x, byte); }
+__host__ __device__ __forceinline__ bool dongle_component_f64(double x, unsigned char *byte) { return dongle_component<double>(x, byte); }
 // WRAP of the reference (include/macros.h): x folded into [sm, lg)
 __host__ __device__ __forceinline__ double trk_wrap(double x, double sm, double lg) {
   const double k = x - sm, n = lg - sm;

@@ -20,6 +20,7 @@
 // k-ordered fma chain): 4-wave workgroups, A operands are Toeplitz slices read straight from LDS planes, B
 // operands (template rows) stream through LDS.
 #include "lcs_internal.h"
+#include "lte_device.h"
 #include <algorithm>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -115,9 +116,9 @@ __global__ __launch_bounds__(256) void k_ingest_c128(const double2 *__restrict__
       if (i0 + j < n_cap) {
         const double2 s = cap64[i0 + j];
         if (j < 8) cap32[i0 + j] = make_float2((float)s.x, (float)s.y);
-        const double kr = s.x * 128.0, ki = s.y * 128.0;          // exact: a power of two
-        const bool ok = kr == rint(kr) && ki == rint(ki) && kr >= -127.0 && kr <= 128.0 && ki >= -127.0 && ki <= 128.0;
-        if (ok) x = ((uint32_t)(-(int)kr) & 255u) | (((uint32_t)(-(int)ki) & 255u) << 8);
+        unsigned char br, bi;                                     // the bytes (k + 127) the components came from: lte_device.h
+        const bool okr = dongle_component_f64(s.x, &br), oki = dongle_component_f64(s.y, &bi);
+        if (okr && oki) x = ((uint32_t)(127 - (int)br) & 255u) | (((uint32_t)(127 - (int)bi) & 255u) << 8);
         else bad = true;
       }
       v[j] = x;
@@ -1224,7 +1225,9 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
     // near-ties of the arg-max, recomputed in the reference's arithmetic (a few positions per buffer; the kernel loops over the list)
     if (!c->skip_frq_repair && geo.n_f > 1) {             // (one hypothesis -- the streaming mode -- has no arg-max to repair: one graph node less)
       const CapSrc cs = lcs_cap_src(c, geo.n_cap);
-      const int ng = std::min(512, 8 * n_buf);
+      // at least 64 workgroups: a single buffer on a dense raster lists a few hundred genuine near-ties (tests/test_gpu_frq_ties.py:
+      // 336 on a one-window buffer), which 8 workgroups (crowded beyond 256) would have left to the bound meant for degenerate grids
+      const int ng = std::min(512, std::max(64, 8 * n_buf));
 #define REPAIR_LAUNCH(KIND) hipLaunchKernelGGL((k_frq_repair<KIND, false>), dim3(ng), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, \
                                                c->n_fix, cs, c->params, c->fset, c->d_pss_td, c->start, c->pow_, pow32, c->frq, nullptr, nullptr, c->zth, c->n_fix + 1, geo)
       if (cs.c8) REPAIR_LAUNCH(0);

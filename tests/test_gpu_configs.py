@@ -389,3 +389,119 @@ def test_float_batches_of_dongle_data_take_the_u8_route(pkg):
         S.set_float_batch_probe(True)
         S.search_batch(d32.data_ptr(), pkg.FMT_C64, 4, 153600, f, fcs, fcs, FS, pkg.STAGE_PSS)
         assert S.last_xcorr_info()[0] == "k_xcorr_i8x3"
+
+
+def _probe_codes():
+    """The byte codes whose neighbours are planted: both ends, the three around zero (126, 127, 128: below byte 128 the old sum
+    x * 128 + 127 had a finer ulp than above), 129, and 24 seeded others."""
+    rng = np.random.default_rng(2024)
+    named = [0, 1, 126, 127, 128, 129, 254, 255]
+    others = rng.choice(np.setdiff1d(np.arange(256), named), 24, replace=False)
+    return named + sorted(int(b) for b in others)
+
+
+def test_float_batch_probe_decides_on_the_exact_value(pkg):
+    """The predicate of lcs_set_float_batch_probe at its edge (tests/test_probe_host.py pins it over all 2^32 patterns on the host;
+    here the kernel that uses it): ONE component of a resident complex<float> batch moved 1 or 2 ulps off a code, set to 2^-30, to
+    a subnormal or to the first value beyond the range sends the batch to the fp16 kernel -- a probe that decides after rounding
+    x * 128 + 127 took most of these for bytes; a whole batch scaled by 2^-30 is a weak float front end, not all-zero bytes: its
+    peaks are the oracle's.  A batch with all 256 codes in both components and a -0.0 is dongle data: the int8 kernel and the
+    records of the same capture handed over as bytes."""
+    import torch
+    n = 153600
+    f = f_search_set_for(FC, 100)
+    fcs = np.array([FC])
+    iq = pkg.synth.make_capbuf(905, FC, [dict(n_id_1=31, n_id_2=1, f_off=22e3), dict(n_id_1=140, n_id_2=0, f_off=-48e3, gain_db=-3)], 5.0)[0].copy()
+    iq[20000:20512] = np.repeat(np.arange(256, dtype=np.uint8), 2)          # samples 10000 .. 10255: I = Q = every code
+    h32 = iq_u8_to_capbuf(iq).astype(np.complex64)[None]
+    d8 = torch.from_numpy(iq[None]).cuda()
+    d32 = torch.from_numpy(h32).cuda()
+    comp = torch.view_as_real(d32).view(-1)                                 # the 2 n float components, resident
+    assert comp.data_ptr() == d32.data_ptr() and comp.numel() == 2 * n
+    host = h32.view(np.float32).reshape(-1)
+    rng = np.random.default_rng(2025)
+
+    def run(S, stage=pkg.STAGE_PSS):
+        S.set_float_batch_probe(True)                                       # (resets the skip counter: every call is probed)
+        res = S.search_batch(d32.data_ptr(), pkg.FMT_C64, 1, n, f, fcs, fcs, FS, stage)
+        return res, S.last_xcorr_info()[0]
+
+    with pkg.Searcher(0) as S:
+        as_bytes = S.search_batch(d8.data_ptr(), pkg.FMT_IQ_U8, 1, n, f, fcs, fcs, FS, pkg.STAGE_FULL)
+        assert len(as_bytes[0]) >= 1
+        # positive: every code in both components, and a -0.0 where a 0.0 (code 127) stood
+        zero_at = 2 * 10127                                                 # sample 10127 carries code 127: 0.0
+        assert host[zero_at] == 0.0
+        comp[zero_at] = torch.tensor(-0.0, dtype=torch.float32)
+        assert np.signbit(comp[zero_at].item())
+        routed, kernel = run(S, pkg.STAGE_FULL)
+        assert kernel == "k_xcorr_i8x3"
+        assert [bytes(c) for c in routed[0]] == [bytes(c) for c in as_bytes[0]]
+        # off the grid by one component: the planted values, each at a seeded component (first and last of the buffer among them)
+        plant = []
+        for b in _probe_codes():
+            x = np.float32((b - 127) / 128.0)
+            for away in (np.float32(-np.inf), np.float32(np.inf)):
+                y = x
+                for ulps in (1, 2):
+                    y = np.nextafter(y, away)
+                    plant.append((f"code {b} {'+' if away > 0 else '-'}{ulps} ulp", y))
+        plant += [("2^-30", np.float32(2.0 ** -30)), ("-2^-30", np.float32(-2.0 ** -30)), ("2^-25", np.float32(2.0 ** -25)),
+                  ("subnormal", np.float32(1e-40)), ("1 + 1/128", np.float32(1 + 1 / 128)), ("-1", np.float32(-1.0))]
+        where = [0, 2 * n - 1] + [int(i) for i in rng.integers(0, 2 * n, len(plant) - 2)]
+        vals = torch.from_numpy(np.array([v for _, v in plant], np.float32)).cuda()
+        keep = comp.clone()
+        assert len(plant) == 32 * 4 + 6
+        for k, ((name, v), i) in enumerate(zip(plant, where)):
+            comp[i] = vals[k]
+            assert comp[i].item() == float(v) and float(v) not in [(b - 127) / 128.0 for b in range(256)], name
+            _, kernel = run(S)
+            comp[i] = keep[i]
+            assert kernel == "k_xcorr_f16x3", f"{name} = {float(v)!r} at component {i} was taken for a byte"
+        assert torch.equal(comp, keep)
+        routed, kernel = run(S, pkg.STAGE_FULL)                             # restored: dongle data again, the same records
+        assert kernel == "k_xcorr_i8x3" and [bytes(c) for c in routed[0]] == [bytes(c) for c in as_bytes[0]]
+        # a weak float front end: the whole batch scaled by 2^-30 (exact) -- every component far below half a step
+        d32.mul_(2.0 ** -30)
+        scaled = (h32[0].astype(np.complex128)) * 2.0 ** -30
+        got, kernel = run(S)
+        assert kernel == "k_xcorr_f16x3" and not S.last_overflow
+        ro = O.xcorr_pss(scaled, f, 2, FC, FC, FS)
+        po = O.peak_search(ro["pow"], ro["frq"], O.z_th1(ro["sp_incoherent"], ro["n_comb_xc"]), f, FC, FC, ro["single"], 2)
+        assert len(po) >= 2 and [(c.n_id_2, c.ind, c.freq) for c in got[0]] == [(c.n_id_2, c.ind, c.freq) for c in po]
+        for a, b in zip(got[0], po):
+            assert abs(a.pss_pow - b.pss_pow) <= 1e-5 * b.pss_pow
+
+
+def test_host_buffers_are_dongle_data_only_on_the_exact_codes(S, pkg):
+    """The complex<double> twin (k_ingest_c128, the host entry points): a buffer with every code in both components and a -0.0 takes
+    the int8 kernel; one component 1 or 2 ulps (of a double) beside a code, tiny, or beyond the range takes the fp32 kernel."""
+    n = 3 * 9600 + 400
+    f = np.array([30e3, 35e3, 40e3])
+    iq = pkg.synth.make_capbuf(906, FC, [dict(n_id_1=31, n_id_2=1, f_off=35e3)], 5.0)[0][:2 * n].copy()
+    iq[2000:2512] = np.repeat(np.arange(256, dtype=np.uint8), 2)
+    cap = iq_u8_to_capbuf(iq)
+    comp = cap.view(np.float64)
+    assert comp[2 * 1127] == 0.0
+    comp[2 * 1127] = -0.0
+    S.xcorr_pss(cap, f, 2, FC, FC, FS, want_incoherent=False)
+    assert S.last_xcorr_info()[0] == "k_xcorr_i8x3"
+    rng = np.random.default_rng(2026)
+    plant = []
+    for b in _probe_codes():
+        x = (b - 127) / 128.0
+        for away in (-np.inf, np.inf):
+            y = x
+            for ulps in (1, 2):
+                y = float(np.nextafter(y, away))
+                plant.append(y)
+    plant += [2.0 ** -30, -2.0 ** -30, 5e-324, np.finfo(np.float64).tiny, 1 + 1 / 128, -1.0]
+    where = [0, 2 * n - 1] + [int(i) for i in rng.integers(0, 2 * n, len(plant) - 2)]
+    for v, i in zip(plant, where):
+        old = comp[i]
+        comp[i] = v
+        S.xcorr_pss(cap, f, 2, FC, FC, FS, want_incoherent=False)
+        comp[i] = old
+        assert S.last_xcorr_info()[0].startswith("k_xcorr_mfma_blk"), f"{v!r} at component {i} was taken for a byte"
+    S.xcorr_pss(cap, f, 2, FC, FC, FS, want_incoherent=False)
+    assert S.last_xcorr_info()[0] == "k_xcorr_i8x3"

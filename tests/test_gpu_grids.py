@@ -95,7 +95,7 @@ def test_host_entry_point_at_a_high_band_grid(S, pkg, fc, n_f):
     ro = O.xcorr_pss(cap, f, 2, fc, fc, FS)
     r = S.xcorr_pss(cap, f, 2, fc, fc, FS)
     assert S.last_xcorr_info()[0] == "k_xcorr_i8x3"
-    _check_xcorr(r, ro, f"host int8 n_f={n_f}")
+    _check_xcorr(S, r, ro, f"host int8 n_f={n_f}")
     r32 = S.xcorr_pss(0.5 * cap, f, 2, fc, fc, FS, want_incoherent=False)
     assert S.last_xcorr_info()[0].startswith("k_xcorr_mfma_blk")
     assert np.array_equal(r32["frq"], ro["frq"])

@@ -66,7 +66,7 @@ def test_random_shape_host_entry_points(S, pkg, seed):
     r = S.xcorr_pss(cap, d["f"], d["ds"], d["fc"], d["fcp"], d["fsp"])
     ro = O.xcorr_pss(cap, d["f"], d["ds"], d["fc"], d["fcp"], d["fsp"])
     assert r["n_comb_xc"] == d["n_win"]
-    _check_xcorr(r, ro, tag)
+    _check_xcorr(S, r, ro, tag)
     Z = pkg.z_th1(r["sp_incoherent"], r["n_comb_xc"], d["ds"])
     Zo = O.z_th1(ro["sp_incoherent"], ro["n_comb_xc"], d["ds"])
     assert (np.abs(Z - Zo) / Zo).max() < 1e-10, tag

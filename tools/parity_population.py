@@ -35,6 +35,9 @@ process per host core):
   per peak                       found / rejected by sss_detect, by decode_mib: EQUAL
   per cell                       n_id_1, cp_type, n_ports, n_rb_dl, phich_duration, phich_resource, sfn EQUAL;
                                  frame_start 1e-6 samples, freq_fine 1e-4 Hz, freq_superfine 1e-3 Hz
+  xc_incoherent_single           every element: the worst relative error per group is RECORDED next to lcs_frq_tie_eps() and the summed
+                                 lcs_last_frq_repair_stats (n_listed / n_unrepaired); a worst error >= eps / 2 or an unrepaired position
+                                 breaks the premise of the exact arg-max: exit status 1, as for a disagreement
 Every disagreement is reported with the oracle's own margin to the threshold that decides it.  Writes one JSON file.
 
 TEST TOOLING (it imports oracle/): used by tests/test_gpu_population.py and run by hand for profiles/r05/.
@@ -272,7 +275,7 @@ def oracle_job(it):
                 rec["arrays"] = dict(c2=cell_to_dict(c2), c3=cell_to_dict(c3), tfg=tfg, ts=ts, tfgc=tfgc, ce=[x[0] for x in ce], np=[float(x[1]) for x in ce])
         out_peaks.append(rec)
     return dict(name=it["name"], frq=ro["frq"].astype(np.int16), pow=ro["pow"].astype(np.float32), zth=Z, peaks=out_peaks,
-                z_rejected=z_rejected, seconds=time.perf_counter() - t0, frq_margin=_frq_margins(ro))
+                z_rejected=z_rejected, seconds=time.perf_counter() - t0, frq_margin=_frq_margins(ro), single=ro["single"])
 
 
 def _frq_margins(ro):
@@ -288,19 +291,21 @@ def _frq_margins(ro):
 
 # -------------------------------------------------------------------------------------------------------- GPU side
 def gpu_pass(pkg, items, batch=128, input_fmt="u8"):
-    """Every buffer through the batched, device-resident chain; buffers that share (grid, fs_programmed) share batches.
+    """Every buffer through the batched, device-resident chain; buffers of a group that share (grid, fs_programmed) share batches
+    (per group: lcs_last_frq_repair_stats counts a whole batch, and the report keeps the counts by group).
     input_fmt "c64": the same samples handed over as complex<float> ((u8 - 127) / 128 is exact in fp32) -- LCS_FMT_C64 batches take
     the fp16 three-product kernel (k_xcorr_f16x3) and every later stage reads the float buffer in place."""
     import torch
     out = [None] * len(items)
     keys = {}
     for i, it in enumerate(items):
-        keys.setdefault((it["f"].tobytes(), it["fs_prog"]), []).append(i)
+        keys.setdefault((it["group"], it["f"].tobytes(), it["fs_prog"]), []).append(i)
     n_repairs = 0
+    ties = {}          # group -> [positions listed as near-ties, listed positions left unrepaired], summed over its batches
     t_gpu = 0.0
     kernels = set()
     with pkg.Searcher(0) as S:
-        for (_, fs), idx in keys.items():
+        for (group, _, fs), idx in keys.items():
             f = items[idx[0]]["f"]
             for a in range(0, len(idx), batch):
                 ids = idx[a:a + batch]
@@ -317,14 +322,16 @@ def gpu_pass(pkg, items, batch=128, input_fmt="u8"):
                 pk = S.search_batch(d.data_ptr(), fmt, len(ids), N_CAP, f, fr, fp, fs, pkg.STAGE_PSS, max_cells_per_buf=pkg.MAX_PEAKS)
                 kernels.add(S.last_xcorr_info()[0])
                 n_repairs += S.last_frq_repairs()
+                listed, left = S.last_frq_repair_stats()
+                ties[group] = [ties.get(group, [0, 0])[0] + listed, ties.get(group, [0, 0])[1] + left]
                 arr = [S.batch_readback(b, f.size) for b in range(len(ids))]
                 full = S.search_batch(d.data_ptr(), fmt, len(ids), N_CAP, f, fr, fp, fs, pkg.STAGE_FULL, max_cells_per_buf=pkg.MAX_PEAKS)
                 t_gpu += time.perf_counter() - t0
                 assert not S.last_overflow
                 for b, i in enumerate(ids):
-                    out[i] = dict(frq=arr[b]["frq"], pow=arr[b]["pow"], zth=arr[b]["z_th1"], peaks=[cell_to_dict(c) for c in pk[b]],
+                    out[i] = dict(frq=arr[b]["frq"], pow=arr[b]["pow"], zth=arr[b]["z_th1"], single=arr[b]["single"], peaks=[cell_to_dict(c) for c in pk[b]],
                                   cells=[cell_to_dict(c) for c in full[b]])
-    return out, n_repairs, t_gpu, sorted(kernels)
+    return out, n_repairs, t_gpu, sorted(kernels), ties
 
 
 def compare_arrays(pkg, S, it, o):
@@ -439,13 +446,18 @@ def run(groups=("synthetic", "bench", "dense"), limit=None, workers=None, out_pa
     items = build_population(pkg, groups, limit, dense_limit, seed_offset, pool)
     t_built = time.perf_counter()
     res_async = pool.imap(oracle_job, items, chunksize=1)
-    gpu, n_repairs, t_gpu, kernels = gpu_pass(pkg, items, batch=batch, input_fmt=input_fmt)
+    gpu, n_repairs, t_gpu, kernels, ties = gpu_pass(pkg, items, batch=batch, input_fmt=input_fmt)
+    eps = pkg.frq_tie_eps()
+    single_worst = {}      # group -> worst relative error of an xc_incoherent_single element: the premise of the near-tie listing is < eps / 2
     # results are taken as they arrive: the stage arrays of the `channels` group (a few MB per decoded cell) are compared through
     # the GPU's stage entry points at once and dropped
     orc, arr_dis, arr_cells = [], [], 0
     arr_worst = dict(tfg=0.0, tfg_comp=0.0, ce_tfg=0.0, np=0.0)
     with pkg.Searcher(0) as S_arr:
-        for it, o in zip(items, res_async):
+        for it, g_, o in zip(items, gpu, res_async):
+            so = o.pop("single").astype(np.float64)
+            single_worst[it["group"]] = max(single_worst.get(it["group"], 0.0), float((np.abs(g_.pop("single").astype(np.float64) - so) / so).max()))
+            del so
             if it.get("arrays"):
                 d_, n_, w_ = compare_arrays(pkg, S_arr, it, o)
                 arr_dis += d_
@@ -476,6 +488,9 @@ def run(groups=("synthetic", "bench", "dense"), limit=None, workers=None, out_pa
         if cnt["min_z_ratio"] is not None:
             min_z = cnt["min_z_ratio"] if min_z is None else min(min_z, cnt["min_z_ratio"])
         min_frq = cnt["frq_min_margin"] if min_frq is None else min(min_frq, cnt["frq_min_margin"])
+    for grp, pg in per_group.items():
+        pg.update(single_worst_rel_err=single_worst[grp], n_listed=ties[grp][0], n_unrepaired=ties[grp][1])
+    premise_ok = all(pg["n_unrepaired"] == 0 and pg["single_worst_rel_err"] < eps / 2 for pg in per_group.values())
     by_stage = {}
     for d in all_dis:
         by_stage[d["stage"]] = by_stage.get(d["stage"], 0) + 1
@@ -485,6 +500,9 @@ def run(groups=("synthetic", "bench", "dense"), limit=None, workers=None, out_pa
         totals=tot, per_group=per_group, disagreements=len(all_dis), disagreements_by_stage=by_stage,
         disagreement_rate_per_buffer=len(all_dis) / max(1, tot["buffers"]),
         gpu_frq_positions_repaired=n_repairs,
+        frq_tie_eps=eps, tie_premise=dict(ok=premise_ok, single_worst_rel_err=max(single_worst.values()), bound=eps / 2, n_listed=sum(v[0] for v in ties.values()),
+                                          n_unrepaired=sum(v[1] for v in ties.values()),
+                                          note="the near-tie listing catches every disagreement iff xc_incoherent_single is within eps/2 of the oracle (DESIGN 3.2a)"),
         stage_arrays=dict(cells_compared=arr_cells, disagreements=len(arr_dis), worst_relative_deviation=arr_worst,
                           tolerances=dict(tfg=1e-10, tfg_comp=1e-9, ce_tfg=1e-9, np=1e-11),
                           note="channels / highband groups: extract_tfg / tfoec / chan_est (every port) of every cell the oracle decoded, GPU stage entry points on the oracle's inputs"),
@@ -515,4 +533,4 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "parity_population.json"))
     a = ap.parse_args()
     r = run(tuple(a.groups.split(",")), a.limit, a.workers, a.out, dense_limit=a.dense_limit, seed_offset=a.seed_offset, input_fmt=a.input, batch=a.batch)
-    sys.exit(0 if r["disagreements"] == 0 else 1)
+    sys.exit(0 if r["disagreements"] == 0 and r["tie_premise"]["ok"] else 1)
