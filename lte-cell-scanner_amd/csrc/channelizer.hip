@@ -21,8 +21,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 typedef float ch_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ch_f32x4 __attribute__((ext_vector_type(4)));
@@ -161,129 +159,63 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
   }
 }
 
-// Per-context state, kept here (keyed by the context) and released by lcs_chan_free from lcs_destroy
-struct ChanState {
-  void *chan_par = nullptr;                     // device: [n_ch] phase steps, then the taps
-  size_t chan_par_bytes = 0;
-  float *chan_tab = nullptr;                    // device: the filter bank in A-operand order
-  size_t chan_tab_floats = 0;
-  void *chan_hpin[2] = {nullptr, nullptr};      // page-locked parameter slots, used in turn
-  size_t chan_hpin_bytes[2] = {0, 0};
-  hipEvent_t ev_chan_slot[2] = {nullptr, nullptr};
-  int chan_slot = 0;
-  hipEvent_t ev_chan0 = nullptr, ev_chan1 = nullptr;
-  bool chan_timed = false;
-};
-static std::mutex g_chan_mu;
-static std::unordered_map<const lcs_ctx *, ChanState *> g_chan;
-
-static ChanState *chan_state(const lcs_ctx *c, bool create) {
-  std::lock_guard<std::mutex> lk(g_chan_mu);
-  auto it = g_chan.find(c);
-  if (it != g_chan.end()) return it->second;
-  if (!create) return nullptr;
-  ChanState *st = new ChanState();
-  g_chan[c] = st;
-  return st;
-}
-
 // One call's parameters on their way to the device: [n_ch] phase steps, then T taps as float.  Two page-locked slots used in
 // turn, each guarded by the event behind its copy, so a call never waits for the GPU unless three calls are in flight.
-static int chan_slot(lcs_ctx *c, ChanState *st, size_t bytes, int *slot) {
-  const int k = st->chan_slot ^= 1;
-  if (!st->ev_chan_slot[k]) HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan_slot[k], hipEventDisableTiming));
-  else HIPCHK(c, hipEventSynchronize(st->ev_chan_slot[k]));
-  if (bytes > st->chan_hpin_bytes[k]) {
-    if (st->chan_hpin[k]) (void)hipHostFree(st->chan_hpin[k]);
-    st->chan_hpin[k] = nullptr; st->chan_hpin_bytes[k] = 0;
-    HIPCHK(c, hipHostMalloc(&st->chan_hpin[k], bytes, hipHostMallocDefault));
-    st->chan_hpin_bytes[k] = bytes;
-  }
+static int chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
+  const int k = c->chan_slot ^= 1;
+  if (!c->ev_chan_slot[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan_slot[k], hipEventDisableTiming));
+  else HIPCHK(c, hipEventSynchronize(c->ev_chan_slot[k]));
   *slot = k;
-  return LCS_OK;
+  return c->chan_hpin[k].reserve(c, bytes);
 }
 
 int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
                           int n_ch, void *d_out, uint32_t n_out) {
-  ChanState *st = chan_state(c, true);
   const int T = 16 * decim, n_rb = (n_ch + CH_CARRIERS - 1) / CH_CARRIERS;
   const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 256 * sizeof(float);
   const size_t tab_floats = (size_t)n_rb * 64 * T;
-  if (par_bytes > st->chan_par_bytes || tab_floats > st->chan_tab_floats) {      // grown on demand (earlier calls may still read the old ones)
+  int k = 0, rc;
+  if (par_bytes > c->chan_par.capacity() || tab_floats > c->chan_tab.capacity())      // grown on demand (earlier calls may still read the old ones)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (par_bytes > st->chan_par_bytes) {
-      if (st->chan_par) (void)hipFree(st->chan_par);
-      st->chan_par = nullptr; st->chan_par_bytes = 0;
-      HIPCHK(c, hipMalloc((void **)&st->chan_par, par_bytes));
-      st->chan_par_bytes = par_bytes;
-    }
-    if (tab_floats > st->chan_tab_floats) {
-      if (st->chan_tab) (void)hipFree(st->chan_tab);
-      st->chan_tab = nullptr; st->chan_tab_floats = 0;
-      HIPCHK(c, hipMalloc((void **)&st->chan_tab, tab_floats * sizeof(float)));
-      st->chan_tab_floats = tab_floats;
-    }
+  if ((rc = c->chan_par.reserve(c, par_bytes)) || (rc = c->chan_tab.reserve(c, tab_floats))) return rc;
+  if (!c->ev_chan0) {
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan0, LCS_EVENT_NOFENCE));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan1, LCS_EVENT_NOFENCE));
   }
-  if (!st->ev_chan0) {
-    HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan0, LCS_EVENT_NOFENCE));
-    HIPCHK(c, hipEventCreateWithFlags(&st->ev_chan1, LCS_EVENT_NOFENCE));
-  }
-  int k = 0, rc = chan_slot(c, st, par_bytes, &k);
-  if (rc) return rc;
-  unsigned long long *h_step = (unsigned long long *)st->chan_hpin[k];
+  if ((rc = chan_slot(c, par_bytes, &k))) return rc;
+  unsigned long long *h_step = reinterpret_cast<unsigned long long *>(c->chan_hpin[k].get());
   float *h_taps = (float *)(h_step + n_ch);
   for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);
   double taps[256];
   lcs_chan_taps(decim, taps);
   for (int t = 0; t < T; ++t) h_taps[t] = (float)taps[t];
   const size_t up = (size_t)n_ch * sizeof(unsigned long long) + T * sizeof(float);
-  HIPCHK(c, hipMemcpyAsync(st->chan_par, h_step, up, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(st->ev_chan_slot[k], c->stream));
-  const unsigned long long *d_step = (const unsigned long long *)st->chan_par;
+  HIPCHK(c, hipMemcpyAsync(c->chan_par, h_step, up, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_chan_slot[k], c->stream));
+  const unsigned long long *d_step = reinterpret_cast<const unsigned long long *>(c->chan_par.get());
   const float *d_taps = (const float *)(d_step + n_ch);
-  HIPCHK(c, hipEventRecord(st->ev_chan0, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev_chan0, c->stream));
   const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_chan_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, decim, n_rb, st->chan_tab);
+  hipLaunchKernelGGL(k_chan_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, decim, n_rb, c->chan_tab);
   const dim3 grid((n_out + CH_NT - 1) / CH_NT, n_rb);
   if (fmt == LCS_FMT_C64)
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_C64>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_C64>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
                        d_step, n_ch, (float2 *)d_out, n_out);
   else if (fmt == LCS_FMT_IQ_S16)
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S16>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S16>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
                        d_step, n_ch, (float2 *)d_out, n_out);
   else
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S8>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)st->chan_tab,
+    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S8>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
                        d_step, n_ch, (float2 *)d_out, n_out);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(st->ev_chan1, c->stream));
-  st->chan_timed = true;
+  HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));
+  c->chan_timed = true;
   return LCS_OK;
 }
 
 int lcs_chan_last_ms(lcs_ctx *c, float *ms) {
-  ChanState *st = chan_state(c, false);
-  if (!st || !st->chan_timed) { c->err = "lcs_last_channelize_ms: no lcs_channelize call on this context yet"; return LCS_ERR_BAD_ARG; }
-  HIPCHK(c, hipEventSynchronize(st->ev_chan1));
-  HIPCHK(c, hipEventElapsedTime(ms, st->ev_chan0, st->ev_chan1));
+  if (!c->chan_timed) { c->err = "lcs_last_channelize_ms: no lcs_channelize call on this context yet"; return LCS_ERR_BAD_ARG; }
+  HIPCHK(c, hipEventSynchronize(c->ev_chan1));
+  HIPCHK(c, hipEventElapsedTime(ms, c->ev_chan0, c->ev_chan1));
   return LCS_OK;
-}
-
-void lcs_chan_free(lcs_ctx *c) {
-  ChanState *st = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_chan_mu);
-    auto it = g_chan.find(c);
-    if (it == g_chan.end()) return;
-    st = it->second;
-    g_chan.erase(it);
-  }
-  if (st->chan_par) (void)hipFree(st->chan_par);
-  if (st->chan_tab) (void)hipFree(st->chan_tab);
-  for (int k = 0; k < 2; ++k) {
-    if (st->chan_hpin[k]) (void)hipHostFree(st->chan_hpin[k]);
-    if (st->ev_chan_slot[k]) (void)hipEventDestroy(st->ev_chan_slot[k]);
-  }
-  if (st->ev_chan0) (void)hipEventDestroy(st->ev_chan0);
-  if (st->ev_chan1) (void)hipEventDestroy(st->ev_chan1);
-  delete st;
 }

@@ -13,26 +13,6 @@
 
 namespace {
 
-
-
-template <typename T>
-int dev_alloc(lcs_ctx *c, T **p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (n == 0) return LCS_OK;
-  HIPCHK(c, hipMalloc((void **)p, n * sizeof(T)));
-  return LCS_OK;
-}
-
-int pinned(lcs_ctx *c, size_t bytes) {
-  if (bytes <= c->h_pinned_bytes) return LCS_OK;
-  if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-  c->h_pinned = nullptr;
-  c->h_pinned_bytes = 0;
-  HIPCHK(c, hipHostMalloc(&c->h_pinned, bytes, hipHostMallocDefault));
-  c->h_pinned_bytes = bytes;
-  return LCS_OK;
-}
-
 XcGeom make_geo(uint32_t n_cap, int n_f, int ds, int cpg = LCS_TG) {
   XcGeom g;
   g.n_cap = n_cap;
@@ -63,45 +43,24 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
   const size_t S = n_slots, NE = 3 * LCS_N_IDX;
   const int G = std::max(std::max(G_need, c->cap_G), (3 * n_f + LCS_TG - 1) / LCS_TG);
   int rc;
-#define A(p, n) if ((rc = dev_alloc(c, &c->p, (n))) != LCS_OK) return rc
-  A(cap32, S * n_cap);
-  A(cap64, (size_t)n_cap);
-  A(params, S);
-  // per-hypothesis / per-group tables: sized for the largest grid seen; every call lays its own grid out with its own
-  // strides n_f and G (k_prep_tables rebuilds them per call)
-  A(fset, (size_t)n_f);
-  A(tmpl, S * n_f * 3 * 137);
-  A(start, S * LCS_NW_MAX * n_f);
-  A(smin, S * LCS_NW_MAX * G);
-  A(kp2, S * LCS_NW_MAX * G);
-  if (c->btab) { (void)hipFree(c->btab); c->btab = nullptr; }      // fp32 kernel's operand tables (0.5 MB per slot and group): allocated by its first launch (lcs_launch_xcorr)
-  c->btab_elems = 0;
-  A(single, S * G * LCS_N_IDX * LCS_TG);
-  A(sref, NE * n_f);
-  A(sp, S * LCS_NW_MAX * LCS_N_IDX);
-  A(pow_, S * NE);
-  A(work, S * NE);
-  A(frq, S * NE);
-  A(fix_list, S * NE);
-  A(n_fix, 4);
-  A(second32, S * NE);
-  A(spinc, S * LCS_N_IDX);
-  A(zth, S * LCS_N_IDX);
-  A(peaks, S * LCS_MAXP);
-  A(npeaks, S);
-  if (debug) {
-    A(incoh, S * NE * n_f);
-  }
-#undef A
-  if (c->cap8) { (void)hipFree(c->cap8); c->cap8 = nullptr; }
-  if (c->cap8s) { (void)hipFree(c->cap8s); c->cap8s = nullptr; }
-  if (c->brow8) { (void)hipFree(c->brow8); c->brow8 = nullptr; }
-  if (c->tq) { (void)hipFree(c->tq); c->tq = nullptr; }
-  if (c->tsc) { (void)hipFree(c->tsc); c->tsc = nullptr; }
-  c->i8_ready = false;
-  for (void **q : {(void **)&c->cap16h, (void **)&c->cap16l, (void **)&c->brow16, (void **)&c->texp16, (void **)&c->tsc16, (void **)&c->xmax16, (void **)&c->xpart16})
-    if (*q) { (void)hipFree(*q); *q = nullptr; }
-  c->f16_ready = false;
+  c->params = nullptr;      // the views follow their owners
+  c->fset = nullptr;
+  c->btab.reset();          // fp32 kernel's operand tables (0.5 MB per slot and group): allocated by its first launch (lcs_launch_xcorr)
+  c->i8 = I8Set();          // the int8 and fp16 sets were sized for the old workspace: gone, allocated again on first use
+  c->f16 = F16Set();
+  // the per-hypothesis / per-group tables (fset .. kp2, single, sref) are sized for the largest grid seen; every call lays its
+  // own grid out with its own strides n_f and G (k_prep_tables rebuilds them per call)
+  if ((rc = c->cap32.alloc(c, S * n_cap)) || (rc = c->cap64.alloc(c, (size_t)n_cap)) || (rc = c->params_ws.alloc(c, S)) ||
+      (rc = c->fset_ws.alloc(c, (size_t)n_f)) || (rc = c->tmpl.alloc(c, S * n_f * 3 * 137)) || (rc = c->start.alloc(c, S * LCS_NW_MAX * n_f)) ||
+      (rc = c->smin.alloc(c, S * LCS_NW_MAX * G)) || (rc = c->kp2.alloc(c, S * LCS_NW_MAX * G)) ||
+      (rc = c->single.alloc(c, S * G * LCS_N_IDX * LCS_TG)) || (rc = c->sref.alloc(c, NE * n_f)) || (rc = c->sp.alloc(c, S * LCS_NW_MAX * LCS_N_IDX)) ||
+      (rc = c->pow_.alloc(c, S * NE)) || (rc = c->work.alloc(c, S * NE)) || (rc = c->frq.alloc(c, S * NE)) || (rc = c->fix_list.alloc(c, S * NE)) ||
+      (rc = c->n_fix.alloc(c, 4)) || (rc = c->second32.alloc(c, S * NE)) || (rc = c->spinc.alloc(c, S * LCS_N_IDX)) ||
+      (rc = c->zth.alloc(c, S * LCS_N_IDX)) || (rc = c->peaks.alloc(c, S * LCS_MAXP)) || (rc = c->npeaks.alloc(c, S)) ||
+      (debug && (rc = c->incoh.alloc(c, S * NE * n_f))))
+    return rc;
+  c->params = c->params_ws;
+  c->fset = c->fset_ws;
   c->foe_ready = false;      // (a pending lcs_foe_partial result lived in the buffers just replaced)
   c->cap_slots = n_slots;
   c->cap_n_cap = n_cap;
@@ -113,32 +72,31 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
 
 // Buffers of the int8 correlation path (u8 sources), sized like the current workspace.
 int ensure_i8(lcs_ctx *c) {
-  if (c->i8_ready) return LCS_OK;
+  if (c->i8.ready) return LCS_OK;
   if (c->st_open) { c->err = "int8 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
   const size_t S = (size_t)c->cap_slots;
   const int G = c->cap_G;
   int rc;
   const size_t n8 = S * lcs_cap8_stride(c->cap_n_cap);
-  if ((rc = dev_alloc(c, &c->cap8, n8)) || (rc = dev_alloc(c, &c->cap8s, n8))) return rc;
-  if ((rc = dev_alloc(c, &c->brow8, S * G * (size_t)LCS_I8_IMG))) return rc;
-  if ((rc = dev_alloc(c, &c->tq, S * G * LCS_TG))) return rc;
-  if ((rc = dev_alloc(c, &c->tsc, S * G * LCS_TG))) return rc;
-  c->i8_ready = true;
+  if ((rc = c->i8.cap8.alloc(c, n8)) || (rc = c->i8.cap8s.alloc(c, n8)) || (rc = c->i8.brow8.alloc(c, S * G * (size_t)LCS_I8_IMG)) ||
+      (rc = c->i8.tq.alloc(c, S * G * LCS_TG)) || (rc = c->i8.tsc.alloc(c, S * G * LCS_TG)))
+    return rc;
+  c->i8.ready = true;
   return LCS_OK;
 }
 
 // Buffers of the fp16 three-product correlation path (complex<float> sources of the batch entry points).
 int ensure_f16(lcs_ctx *c) {
-  if (c->f16_ready) return LCS_OK;
+  if (c->f16.ready) return LCS_OK;
   if (c->st_open) { c->err = "fp16 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
   const size_t S = (size_t)c->cap_slots;
   int rc;
   const size_t n16 = S * lcs_cap8_stride(c->cap_n_cap);
-  if ((rc = dev_alloc(c, &c->cap16h, n16)) || (rc = dev_alloc(c, &c->cap16l, n16))) return rc;
-  if ((rc = dev_alloc(c, &c->brow16, S * c->cap_G * (size_t)LCS_F16_IMG))) return rc;
-  if ((rc = dev_alloc(c, &c->texp16, S * c->cap_G * LCS_TG)) || (rc = dev_alloc(c, &c->tsc16, S * c->cap_G * LCS_TG))) return rc;
-  if ((rc = dev_alloc(c, &c->xmax16, S)) || (rc = dev_alloc(c, &c->xpart16, S * 128))) return rc;
-  c->f16_ready = true;
+  if ((rc = c->f16.cap16h.alloc(c, n16)) || (rc = c->f16.cap16l.alloc(c, n16)) || (rc = c->f16.brow16.alloc(c, S * c->cap_G * (size_t)LCS_F16_IMG)) ||
+      (rc = c->f16.texp16.alloc(c, S * c->cap_G * LCS_TG)) || (rc = c->f16.tsc16.alloc(c, S * c->cap_G * LCS_TG)) ||
+      (rc = c->f16.xmax16.alloc(c, S)) || (rc = c->f16.xpart16.alloc(c, S * 128)))
+    return rc;
+  c->f16.ready = true;
   return LCS_OK;
 }
 
@@ -149,19 +107,11 @@ int alloc_percell(lcs_ctx *c, size_t W) {
   const size_t GRID = (size_t)LCS_TFG_ROWS * LCS_TFG_NSC;
   c->percell_ready = false;      // until every buffer exists: a failure part-way leaves a context that allocates again, not one
   c->percell_cap = 0;            // that runs kernels on a null pointer
-#define A(p, n) if ((rc = dev_alloc(c, &c->p, (n))) != LCS_OK) return rc
-  A(work_items, W);
-  A(n_work, 4);
-  A(tfg, W * GRID);
-  A(tfg_comp, W * GRID);
-  A(ce, W * 4 * GRID);
-  A(tfg_desc, W * (size_t)LCS_TFG_DESC_BYTES);
-  A(tfg_ts, W * LCS_TFG_ROWS);
-  A(tfg_ts_comp, W * LCS_TFG_ROWS);
-  A(cell_scratch, W * LCS_CELL_SCRATCH);
-  A(cells_out, W);
-  A(d_dbg, 2048);
-#undef A
+  if ((rc = c->work_items.alloc(c, W)) || (rc = c->n_work.alloc(c, 4)) || (rc = c->tfg.alloc(c, W * GRID)) || (rc = c->tfg_comp.alloc(c, W * GRID)) ||
+      (rc = c->ce.alloc(c, W * 4 * GRID)) || (rc = c->tfg_desc.alloc(c, W * (size_t)LCS_TFG_DESC_BYTES)) || (rc = c->tfg_ts.alloc(c, W * LCS_TFG_ROWS)) ||
+      (rc = c->tfg_ts_comp.alloc(c, W * LCS_TFG_ROWS)) || (rc = c->cell_scratch.alloc(c, W * LCS_CELL_SCRATCH)) || (rc = c->cells_out.alloc(c, W)) ||
+      (rc = c->d_dbg.alloc(c, 2048)))
+    return rc;
   c->percell_ready = true;
   c->percell_cap = (int)W;
   return LCS_OK;
@@ -188,15 +138,12 @@ int ensure_percell(lcs_ctx *c) {
 // of n_buf buffers (every buffer LCS_MAXP records): allocated when a larger batch arrives, never inside lcs_batch_collect.
 int ensure_res_pack(lcs_ctx *c, int n_buf) {
   const size_t need = lcs_pack_rec_offset(n_buf) + (size_t)n_buf * LCS_MAXP * sizeof(lcs_cell);
-  if (need <= c->res_pack_bytes) return LCS_OK;
+  if (need <= c->res_pack.capacity() && need <= c->h_res.capacity()) return LCS_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));      // (the streaming mode's graph does not reference this block: it may grow under an open stream)
-  if (c->res_pack) (void)hipFree(c->res_pack);
-  if (c->h_res) (void)hipHostFree(c->h_res);
-  c->res_pack = c->h_res = nullptr;
-  c->res_pack_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->res_pack, need));
-  HIPCHK(c, hipHostMalloc(&c->h_res, need, hipHostMallocDefault));
-  c->res_pack_bytes = need;
+  c->res_pack.reset();      // both go before either comes back, as ever
+  c->h_res.reset();
+  int rc;
+  if ((rc = c->res_pack.alloc(c, need)) || (rc = c->h_res.alloc(c, need))) return rc;
   return LCS_OK;
 }
 
@@ -293,7 +240,7 @@ int upload_host_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const d
   c->foe_ready = false;      // slot 0 is overwritten: a pending lcs_foe_partial result is gone (lcs_foe_partial sets it again)
   if ((rc = ensure_ws(c, 1, n_cap, n_f, debug, std::max(geo32.G, geo8.G)))) return rc;
   // the int8 copies cannot be (re)allocated under an open stream's graph: such a context keeps the fp32 kernel
-  const bool can_i8 = c->i8_ready || !c->st_open;
+  const bool can_i8 = c->i8.ready || !c->st_open;
   if (can_i8 && (rc = ensure_i8(c))) return rc;
   c->h_params = SlotParams{fc_req, fc_prog, fs_prog};
   HIPCHK(c, hipMemcpyAsync(c->cap64, capbuf, sizeof(double2) * n_cap, hipMemcpyHostToDevice, c->stream));
@@ -378,14 +325,14 @@ int lcs_create(int device, lcs_ctx **out) {
   }
   uint32_t pn_jump[32];
   lcs_tables::pn_jump_table(1600 + 2 * (110 - 6), pn_jump);
-  bool ok = hipMalloc((void **)&c->d_pss_td, td.size() * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&c->d_flag, sizeof(int)) == hipSuccess &&
-            hipMalloc((void **)&c->d_pn_jump, sizeof(pn_jump)) == hipSuccess &&
+  bool ok = c->d_pss_td.alloc(c, td.size() / 2) == LCS_OK &&
+            c->d_flag.alloc(c, 1) == LCS_OK &&
+            c->d_pn_jump.alloc(c, 32) == LCS_OK &&
             hipMemcpy(c->d_pn_jump, pn_jump, sizeof(pn_jump), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMalloc((void **)&c->d_pss_fd, fd.size() * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&c->d_sss_fd, sss.size()) == hipSuccess &&
-            hipMalloc((void **)&c->d_pbch_scr, scr.size()) == hipSuccess &&
-            hipMalloc((void **)&c->d_derm_inv, derm.size() * sizeof(int16_t)) == hipSuccess &&
+            c->d_pss_fd.alloc(c, fd.size() / 2) == LCS_OK &&
+            c->d_sss_fd.alloc(c, sss.size()) == LCS_OK &&
+            c->d_pbch_scr.alloc(c, scr.size()) == LCS_OK &&
+            c->d_derm_inv.alloc(c, derm.size()) == LCS_OK &&
             hipMemcpy(c->d_derm_inv, derm.data(), derm.size() * sizeof(int16_t), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(c->d_pss_td, td.data(), td.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(c->d_pss_fd, fd.data(), fd.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
@@ -396,38 +343,23 @@ int lcs_create(int device, lcs_ctx **out) {
   return LCS_OK;
 }
 
-void lcs_destroy(lcs_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->st_open) (void)lcs_stream_close(c);
-  lcs_track_stream_free(c);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->stream_xc) (void)hipStreamSynchronize(c->stream_xc);
-  void *ptrs[] = {c->cap32, c->cap64, c->params, c->fset, c->tmpl, c->start, c->smin, c->kp2, c->btab, c->single,
-                  c->incoh, c->sref, c->pow_, c->work, c->spinc, c->zth, c->sp, c->frq, c->fix_list, c->n_fix, c->second32, c->fset_g, c->peaks, c->npeaks, c->xc,
-                  c->work_items, c->n_work, c->tfg, c->tfg_comp, c->ce, c->tfg_ts, c->tfg_desc, c->tfg_ts_comp, c->cell_scratch,
-                  c->cells_out, c->d_pss_td, c->d_pss_fd, c->d_sss_fd, c->d_pbch_scr, c->d_derm_inv, c->d_dbg, c->pk_items, c->n_pk,
-                  c->sss_ws, c->d_pn_jump, c->cap8, c->cap8s, c->brow8, c->tq, c->tsc, c->cap16h, c->cap16l, c->brow16, c->texp16, c->tsc16, c->xmax16, c->xpart16, c->h2d, c->trk_td, c->trk_syms, c->trk_raw, c->trk_ce,
-                  c->trk_meta, c->trk_rs, c->trk_fmeta, c->trk_pw, c->trk_idx, c->trk_small, c->trk_cells, c->trk_acfd, c->trk_actd,
-                  c->trk_syncce, c->trk_sync, c->d_flag, c->trk_cut_hit, c->trk_cut_meta, c->c64_u8};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  lcs_chan_free(c);
-  if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-  if (c->res_pack) (void)hipFree(c->res_pack);
-  if (c->h_res) (void)hipHostFree(c->h_res);
-  if (c->trk_hpin) free(c->trk_hpin);
-  for (int k = 0; k < 2; ++k) {
-    if (c->h_stage[k]) (void)hipHostFree(c->h_stage[k]);
-    if (c->ev_stage[k]) (void)hipEventDestroy(c->ev_stage[k]);
-  }
-  if (c->ev_xc0) (void)hipEventDestroy(c->ev_xc0);
-  if (c->ev_xc1) (void)hipEventDestroy(c->ev_xc1);
-  if (c->ev_pre) (void)hipEventDestroy(c->ev_pre);
-  if (c->ev_post) (void)hipEventDestroy(c->ev_post);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->stream_xc) (void)hipStreamDestroy(c->stream_xc);
-  delete c;
+// The order of a context's end (lcs_internal.h, at lcs_ctx): this body, then the members -- the owners free their memory --, then
+// the base with the events and the streams.
+lcs_ctx::~lcs_ctx() {
+  (void)hipSetDevice(device);
+  if (st_open) (void)lcs_stream_close(this);      // graphs first
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (stream_xc) (void)hipStreamSynchronize(stream_xc);
 }
+
+lcs_ctx_queues::~lcs_ctx_queues() {
+  for (hipEvent_t e : {ev_stage[0], ev_stage[1], ev_chan_slot[0], ev_chan_slot[1], ev_chan0, ev_chan1, ev_xc0, ev_xc1, ev_pre, ev_post})
+    if (e) (void)hipEventDestroy(e);
+  if (stream) (void)hipStreamDestroy(stream);
+  if (stream_xc) (void)hipStreamDestroy(stream_xc);
+}
+
+void lcs_destroy(lcs_ctx *c) { delete c; }
 
 const char *lcs_last_error(const lcs_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
@@ -478,7 +410,7 @@ int lcs_xcorr_pss(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double
   if (sp) HIPCHK(c, hipMemcpyAsync(sp, c->sp, sizeof(double) * ncsp * LCS_N_IDX, hipMemcpyDeviceToHost, c->stream));
   if (xc) {
     const size_t n = 3 * (size_t)(n_cap - 136) * n_f;
-    if (n > c->xc_elems) { if ((rc = dev_alloc(c, &c->xc, n))) return rc; c->xc_elems = n; }
+    if ((rc = c->xc.reserve(c, n))) return rc;
     if ((rc = lcs_launch_xc_debug(c, geo))) return rc;
     HIPCHK(c, hipMemcpyAsync(xc, c->xc, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
   }
@@ -546,8 +478,8 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
                                n_buf, fs_programmed, kMaxTapsI8);      // the fp16 kernel holds 160 taps per group and shares the int8 kernel's packing
   if ((rc = ensure_ws(c, n_buf, n_cap, n_f, false, geo.G))) return rc;
   if ((rc = ensure_res_pack(c, n_buf))) return rc;
-  if ((rc = pinned(c, sizeof(SlotParams) * n_buf + sizeof(double) * n_f))) return rc;
-  SlotParams *hp = (SlotParams *)c->h_pinned;
+  if ((rc = c->h_pinned.reserve(c, sizeof(SlotParams) * n_buf + sizeof(double) * n_f))) return rc;
+  SlotParams *hp = reinterpret_cast<SlotParams *>(c->h_pinned.get());
   double *hf = (double *)(hp + n_buf);
   for (int i = 0; i < n_buf; ++i) hp[i] = SlotParams{fc_requested[i], fc_programmed[i], fs_programmed};
   std::memcpy(hf, f_search_set, sizeof(double) * n_f);
@@ -557,17 +489,12 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   // lcs_set_float_batch_probe: a complex<float> batch that is dongle data becomes the u8 batch it came from (one pass + one small
   // read-back: the host waits for it -- while the other contexts' kernels keep the GPU busy -- before it knows which kernels to queue)
   c->last_c64_routed = false;
-  if (fmt == LCS_FMT_C64 && c->c64_probe && (c->i8_ready || !c->st_open) && ((size_t)n_buf * n_cap) % 2 == 0 && (reinterpret_cast<uintptr_t>(d_capbufs) & 15) == 0) {
+  if (fmt == LCS_FMT_C64 && c->c64_probe && (c->i8.ready || !c->st_open) && ((size_t)n_buf * n_cap) % 2 == 0 && (reinterpret_cast<uintptr_t>(d_capbufs) & 15) == 0) {
     if (c->c64_skip > 0) --c->c64_skip;
     else {
       const size_t n_comp = (size_t)2 * n_cap * n_buf;
-      if (n_comp > c->c64_u8_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->c64_u8) (void)hipFree(c->c64_u8);
-        c->c64_u8 = nullptr; c->c64_u8_bytes = 0;
-        HIPCHK(c, hipMalloc((void **)&c->c64_u8, n_comp));
-        c->c64_u8_bytes = n_comp;
-      }
+      if (n_comp > c->c64_u8.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+      if ((rc = c->c64_u8.reserve(c, n_comp))) return rc;
       int flag = 1;
       HIPCHK(c, hipMemcpyAsync(c->d_flag, &flag, sizeof(int), hipMemcpyHostToDevice, c->stream));
       hipLaunchKernelGGL(k_c64_probe_u8, dim3(2048), dim3(256), 0, c->stream, (const float *)d_capbufs, n_comp, c->c64_u8, c->d_flag);
@@ -581,7 +508,7 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   c->use_i8 = fmt == LCS_FMT_IQ_U8;
   // complex<float> sources: fp16 hi / lo operands, three products (pss_xcorr_f16.hip) -- unless its buffers would have to be
   // allocated under an open stream's graph: such a context keeps the fp32 kernel for them (160 taps per group fit it too)
-  c->use_f16 = fmt == LCS_FMT_C64 && (c->f16_ready || !c->st_open);
+  c->use_f16 = fmt == LCS_FMT_C64 && (c->f16.ready || !c->st_open);
   if (fmt == LCS_FMT_IQ_U8 && (rc = ensure_i8(c))) return rc;      // int8 copies: every u8 source (the fp64 stages read them)
   if (c->use_f16 && (rc = ensure_f16(c))) return rc;
   if (c->use_f16) { if ((rc = lcs_launch_ingest_f16(c, d_capbufs, n_buf, n_cap))) return rc; }
@@ -631,9 +558,9 @@ int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n
   const int nb = c->last_n_buf;
   const bool full = (c->last_stage_mask & 2) != 0;
   const size_t rec_off = lcs_pack_rec_offset(nb);
-  const int *hdr = static_cast<const int *>(c->h_res);
+  const int *hdr = reinterpret_cast<const int *>(c->h_res.get());
   const int *cnt = hdr + 8;
-  const lcs_cell *rec = reinterpret_cast<const lcs_cell *>(static_cast<const char *>(c->h_res) + rec_off);
+  const lcs_cell *rec = reinterpret_cast<const lcs_cell *>(c->h_res + rec_off);
   int rc = LCS_OK;
   double host_us = 0;                                   // host time of this call outside the wait for the GPU (lcs_last_collect_host_us)
   auto t_sync_done = std::chrono::steady_clock::now();
@@ -658,8 +585,7 @@ int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n
     }
     const int total = hdr[0];
     if ((size_t)total > first) {
-      HIPCHK(c, hipMemcpyAsync(static_cast<char *>(c->h_res) + rec_off + first * sizeof(lcs_cell),
-                               static_cast<const char *>(c->res_pack) + rec_off + first * sizeof(lcs_cell),
+      HIPCHK(c, hipMemcpyAsync(c->h_res + rec_off + first * sizeof(lcs_cell), c->res_pack + rec_off + first * sizeof(lcs_cell),
                                ((size_t)total - first) * sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -760,13 +686,11 @@ int lcs_batch_enqueue_host(lcs_ctx *c, const void *h_capbufs, int fmt, int n_buf
   if (!h_capbufs || n_buf < 1 || (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8)) { c->err = "bad argument"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)n_buf * n_cap * (fmt == LCS_FMT_IQ_U8 ? 2 : sizeof(float2));
-  if (bytes > c->h2d_bytes) {
+  if (bytes > c->h2d.capacity()) {
     if (c->st_open) { c->err = "lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->h2d) (void)hipFree(c->h2d);
-    c->h2d = nullptr; c->h2d_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->h2d, bytes));
-    c->h2d_bytes = bytes;
+    int rc;
+    if ((rc = c->h2d.reserve(c, bytes))) return rc;
   }
   hipPointerAttribute_t at;
   const bool locked = hipPointerGetAttributes(&at, h_capbufs) == hipSuccess && at.type == hipMemoryTypeHost;
@@ -777,7 +701,8 @@ int lcs_batch_enqueue_host(lcs_ctx *c, const void *h_capbufs, int fmt, int n_buf
     constexpr size_t CH = (size_t)4 << 20;
     for (int k = 0; k < 2; ++k)
       if (!c->h_stage[k]) {
-        HIPCHK(c, hipHostMalloc(&c->h_stage[k], CH, hipHostMallocDefault));
+        int rc;
+        if ((rc = c->h_stage[k].alloc(c, CH))) return rc;
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_stage[k], hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_stage[k], c->stream));
       }
@@ -786,7 +711,7 @@ int lcs_batch_enqueue_host(lcs_ctx *c, const void *h_capbufs, int fmt, int n_buf
       const size_t n = std::min(CH, bytes - off);
       HIPCHK(c, hipEventSynchronize(c->ev_stage[k]));          // the DMA that last read this slot is done
       std::memcpy(c->h_stage[k], (const char *)h_capbufs + off, n);
-      HIPCHK(c, hipMemcpyAsync((char *)c->h2d + off, c->h_stage[k], n, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->h2d + off, c->h_stage[k], n, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipEventRecord(c->ev_stage[k], c->stream));
     }
   }
@@ -1092,14 +1017,10 @@ int lcs_foe_contend(lcs_ctx *c, const double *f_search_set, uint16_t n_f, const 
   if (!c->foe_ready) { c->err = "lcs_foe_contend needs the lcs_foe_partial call of the same buffer first"; return LCS_ERR_BAD_ARG; }
   if (!f_search_set || !d_words || !d_words2 || n_f < 1 || n_f > LCS_NF_LIMIT) { c->err = "bad argument"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
-  if (n_f > c->fset_g_cap) {      // the whole grid (fset holds this rank's share)
-    int rc_;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc_ = dev_alloc(c, &c->fset_g, (size_t)n_f))) return rc_;
-    c->fset_g_cap = n_f;
-  }
-  HIPCHK(c, hipMemcpyAsync(c->fset_g, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   int rc;
+  if (n_f > c->fset_g.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = c->fset_g.reserve(c, (size_t)n_f))) return rc;      // the whole grid (fset holds this rank's share)
+  HIPCHK(c, hipMemcpyAsync(c->fset_g, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   if ((rc = lcs_launch_foe_contend(c, c->foe_geo, c->fset_g, static_cast<const long long *>(d_words), static_cast<long long *>(d_words2)))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's collective runs on another stream (and f_search_set may go away)
   return LCS_OK;
@@ -1176,7 +1097,7 @@ int stream_chain(lcs_ctx *c, int k) {
   // the workspace arrays the other entry points fill: the context's pointers are swapped while the launches are issued / recorded
   SlotParams *params = c->params;
   double *fset = c->fset;
-  c->params = reinterpret_cast<SlotParams *>(c->st_dmirror + offsetof(StreamHost, p));
+  c->params = reinterpret_cast<SlotParams *>(c->st_dmirror + offsetof(StreamHost, p));      // (views: lcs_internal.h)
   c->fset = reinterpret_cast<double *>(c->st_dmirror + offsetof(StreamHost, f));
   const int rc = stream_chain_launches(c, k);
   c->params = params;
@@ -1215,15 +1136,15 @@ int lcs_stream_close(lcs_ctx *c) {
   for (int k = 0; k < 2; ++k) {
     if (c->st_exec[k]) (void)hipGraphExecDestroy(c->st_exec[k]);
     if (c->st_graph[k]) (void)hipGraphDestroy(c->st_graph[k]);
-    if (c->st_hin[k]) (void)hipHostFree(c->st_hin[k]);
-    if (c->st_host[k]) (void)hipHostFree(c->st_host[k]);
+    c->st_hin[k].reset();
+    c->st_host[k].reset();
     if (c->st_ev0[k]) (void)hipEventDestroy(c->st_ev0[k]);
     if (c->st_ev1[k]) (void)hipEventDestroy(c->st_ev1[k]);
-    c->st_exec[k] = nullptr; c->st_graph[k] = nullptr; c->st_hin[k] = nullptr; c->st_host[k] = nullptr; c->st_ev0[k] = c->st_ev1[k] = nullptr;
+    c->st_exec[k] = nullptr; c->st_graph[k] = nullptr; c->st_ev0[k] = c->st_ev1[k] = nullptr;
   }
-  if (c->st_din) (void)hipFree(c->st_din);
-  if (c->st_dmirror) (void)hipFree(c->st_dmirror);
-  c->st_din = nullptr; c->st_dtracked = nullptr; c->st_dntracked = nullptr; c->st_dmirror = nullptr;
+  c->st_din.reset();
+  c->st_dmirror.reset();
+  c->st_dtracked = nullptr; c->st_dntracked = nullptr;
   c->st_open = false;
   c->st_head = c->st_count = 0;
   c->single_stream = false;
@@ -1233,12 +1154,9 @@ int lcs_stream_close(lcs_ctx *c) {
 // Two slots: the chain is captured twice, once per pinned input buffer + parameter / result block, so that the host may
 // fill and launch buffer i + 1 while the graph of buffer i is still running (the launches themselves serialise on the
 // context's stream and share the device workspace).
-int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed) {
-  int rc = check_common(c, n_cap, 1);
-  if (rc) return rc;
-  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
-  if (c->st_open) lcs_stream_close(c);
-  HIPCHK(c, hipSetDevice(c->device));
+namespace {
+int stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed) {
+  int rc;
   if ((rc = ensure_ws(c, 1, n_cap, 1, false))) return rc;
   if ((rc = ensure_percell(c))) return rc;
   if (fmt == LCS_FMT_IQ_U8 && (rc = ensure_i8(c))) return rc;
@@ -1246,25 +1164,23 @@ int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, do
   c->st_fmt = fmt;
   c->st_n_cap = n_cap;
   c->st_in_bytes = (size_t)n_cap * (fmt == LCS_FMT_IQ_U8 ? 2 : sizeof(float2));
-  HIPCHK(c, hipMalloc(&c->st_din, c->st_in_bytes));
-  HIPCHK(c, hipMalloc((void **)&c->st_dmirror, LCS_STREAM_IN_BYTES));
+  if ((rc = c->st_din.alloc(c, c->st_in_bytes)) || (rc = c->st_dmirror.alloc(c, LCS_STREAM_IN_BYTES))) return rc;
   c->st_dntracked = reinterpret_cast<int *>(c->st_dmirror + offsetof(StreamHost, n_tracked));
   c->st_dtracked = reinterpret_cast<int16_t *>(c->st_dmirror + offsetof(StreamHost, tracked));
   for (int k = 0; k < 2; ++k) {
-    HIPCHK(c, hipHostMalloc(&c->st_hin[k], c->st_in_bytes, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void **)&c->st_host[k], sizeof(StreamHost), hipHostMallocDefault));
+    if ((rc = c->st_hin[k].alloc(c, c->st_in_bytes)) || (rc = c->st_host[k].alloc(c, 1))) return rc;
     HIPCHK(c, hipEventCreate(&c->st_ev0[k]));
     HIPCHK(c, hipEventCreate(&c->st_ev1[k]));
     std::memset(c->st_hin[k], fmt == LCS_FMT_IQ_U8 ? 127 : 0, c->st_in_bytes);
     std::memset(c->st_host[k], 0, sizeof(StreamHost));
-    c->st_host[k]->p = SlotParams{fc_requested, fc_programmed, fs_programmed};
+    c->st_host[k].get()->p = SlotParams{fc_requested, fc_programmed, fs_programmed};
   }
   c->cap64_valid = false;
   c->single_stream = true;
   c->st_open = true;
   c->st_head = c->st_count = 0;
   // one eager pass (lazy allocations, function attributes), then the same call sequence under capture, per slot
-  if ((rc = stream_chain(c, 0))) { lcs_stream_close(c); return rc; }
+  if ((rc = stream_chain(c, 0))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < 2; ++k) {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -1273,13 +1189,23 @@ int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, do
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (rc || e != hipSuccess || !g) {
       if (!rc) { c->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); rc = LCS_ERR_HIP; }
-      lcs_stream_close(c);
       return rc;
     }
     c->st_graph[k] = g;
     HIPCHK(c, hipGraphInstantiate(&c->st_exec[k], c->st_graph[k], nullptr, nullptr, 0));
   }
   return LCS_OK;
+}
+}  // namespace
+
+int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed) {
+  int rc = check_common(c, n_cap, 1);
+  if (rc) return rc;
+  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open) lcs_stream_close(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = stream_open(c, fmt, n_cap, fc_requested, fc_programmed, fs_programmed))) lcs_stream_close(c);      // whatever a failed open got hold of goes again
+  return rc;
 }
 
 int lcs_stream_push(lcs_ctx *c, const void *samples, double f_off, const int16_t *tracked_ids, int n_tracked) {
@@ -1290,9 +1216,10 @@ int lcs_stream_push(lcs_ctx *c, const void *samples, double f_off, const int16_t
   c->foe_ready = false;      // the graph overwrites slot 0
   const int k = (c->st_head + c->st_count) & 1;
   std::memcpy(c->st_hin[k], samples, c->st_in_bytes);
-  c->st_host[k]->f = f_off;
-  c->st_host[k]->n_tracked = n_tracked;
-  for (int i = 0; i < n_tracked; ++i) c->st_host[k]->tracked[i] = tracked_ids[i];
+  StreamHost *h = c->st_host[k];
+  h->f = f_off;
+  h->n_tracked = n_tracked;
+  for (int i = 0; i < n_tracked; ++i) h->tracked[i] = tracked_ids[i];
   HIPCHK(c, hipEventRecord(c->st_ev0[k], c->stream));
   HIPCHK(c, hipGraphLaunch(c->st_exec[k], c->stream));
   HIPCHK(c, hipEventRecord(c->st_ev1[k], c->stream));

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 #include "../../include/lcs.h"
+#include "lcs_mem.h"
 
 #define LCS_NW_MAX 16        // incoherent-combining windows (15 for a 153600-sample buffer)
 // Frequency hypotheses per call: the reference loops over whatever f_search_set holds (src/searcher.cpp:113-174; CellSearch builds
@@ -157,11 +158,69 @@ struct StreamHost {
 
 #define LCS_STREAM_IN_BYTES (offsetof(StreamHost, f) + sizeof(double))
 
-struct lcs_ctx {
+// The continuous tracker's carried state (tracker.hip: lcs_track_stream_block)
+struct TrkStreamCell {
+  std::vector<double> fo, ft, late;          // metadata of the carried symbols
+  double bpo_before_tail = 0;                // bulk phase before the first carried symbol
+  long long tail_start = 0;                  // stream index of the first carried symbol (a frame boundary)
+  long long n_seen = 0;                      // symbols delivered so far
+  long long next_raw[4] = {1, 1, 1, 1};      // per port: reference-symbol row (counted from the stream start) whose filter is emitted next
+  long long ce_upto[4] = {0, 0, 0, 0};       // per port: channel estimates emitted for symbols below this
+  long long mib_next = 0;                    // first frame offset not attempted yet
+  int cp_type = 0, n_id_1 = -1, n_id_2 = -1, n_ports = 0;
+};
+// The carried symbols themselves stay on the DEVICE, already transformed: per CP type the frequency-domain rows
+// [cells of that type][carried symbols][72] of the previous call (round 3 kept the time-domain samples on the host and ran
+// them through get_fd again with every call).
+struct TrkStream {
+  std::vector<TrkStreamCell> cells;
+  // indexed by LCS_CP_NORMAL / LCS_CP_EXTENDED: the carried rows, and a second buffer the next call's tail is written into
+  // before the two change places at the commit (no allocation or release -- a device-wide synchronisation -- per call)
+  DevBuf<double2> d_tail[3], d_spare[3];
+};
+
+// Buffers of the int8 correlation path (u8 sources) and of the fp16 three-product path (complex<float> sources of the batch
+// entry points): each set is sized like the workspace, exists as a whole or not at all (`ready`), and goes with the workspace
+// it was sized for (ensure_ws assigns an empty set).
+struct I8Set {
+  DevBuf<uint16_t> cap8;             // capture buffers as (re, im) int8 pairs 127 - u8, slot stride lcs_cap8_stride (pss_xcorr_i8.hip)
+  DevBuf<uint16_t> cap8s;            // the same shifted down by one sample: cap8s[i] = cap8[i + 1]
+  DevBuf<uint32_t> brow8;            // int8 three-digit template operands: one image of resident rows per (slot, group)
+  DevBuf<double> tq;                 // per template: integer scale q
+  DevBuf<float> tsc;                 // per template: 1 / (128 q)
+  bool ready = false;
+};
+struct F16Set {
+  DevBuf<uint32_t> cap16h, cap16l;   // (re, im) fp16 pairs, hi and lo parts, slot stride lcs_cap8_stride
+  DevBuf<uint32_t> brow16;           // template operands, hi and lo terms: one image of resident rows per (slot, group)
+  DevBuf<int> texp16;                // per template column: power-of-two scale exponent
+  DevBuf<float> tsc16;               // per template column: 2^-(k_x + k_t)
+  DevBuf<unsigned> xmax16;           // per slot: bits of the largest |component|
+  DevBuf<unsigned> xpart16;          // per slot: 128 partial maxima (one per workgroup of the read-only maximum pass)
+  bool ready = false;
+};
+
+// The streams and events of a context (the streaming mode's own events and graphs: lcs_stream_close).  A BASE of lcs_ctx,
+// because a base is destroyed after every member of the struct derived from it: see the note on ownership at lcs_ctx.
+struct lcs_ctx_queues {
   int device = 0;
   hipStream_t stream = nullptr;      // everything except the PSS correlation (highest priority)
   hipStream_t stream_xc = nullptr;   // the PSS correlation kernel (lowest priority), see lcs_launch_xcorr
   hipEvent_t ev_pre = nullptr, ev_post = nullptr;
+  hipEvent_t ev_xc0 = nullptr, ev_xc1 = nullptr;
+  hipEvent_t ev_stage[2] = {nullptr, nullptr};      // guard the pinned slots h_stage
+  hipEvent_t ev_chan_slot[2] = {nullptr, nullptr};  // channelizer.hip: guard the page-locked parameter slots chan_hpin
+  hipEvent_t ev_chan0 = nullptr, ev_chan1 = nullptr;
+  ~lcs_ctx_queues();                 // lcs_api.hip: the events, then the streams
+};
+
+// Ownership.  Every block of device or page-locked memory of a context is a Buf member (lcs_mem.h) of this struct or of a struct
+// that is one, and nothing else frees it; a plain pointer member is a VIEW of memory owned elsewhere and says so.  lcs_destroy
+// is `delete`: ~lcs_ctx makes the context's device current, closes an open stream (graphs first) and synchronises both
+// streams; then the members go, the owners freeing their memory; the base goes last, with the events and then the streams --
+// the order the hand-written tear-down had.
+struct lcs_ctx : lcs_ctx_queues {
+  ~lcs_ctx();                        // lcs_api.hip
   std::string err;
 
   // capacity the workspace is currently sized for
@@ -172,73 +231,59 @@ struct lcs_ctx {
   bool cap_debug = false;
 
   // device buffers
-  float2 *cap32 = nullptr;
-  uint16_t *cap8 = nullptr;          // capture buffers as (re, im) int8 pairs 127 - u8, slot stride lcs_cap8_stride (pss_xcorr_i8.hip)
-  uint16_t *cap8s = nullptr;         // the same shifted down by one sample: cap8s[i] = cap8[i + 1]
-  uint32_t *brow8 = nullptr;         // int8 three-digit template operands: one image of resident rows per (slot, group)
-  double *tq = nullptr;              // per template: integer scale q
-  float *tsc = nullptr;              // per template: 1 / (128 q)
-  bool i8_ready = false, use_i8 = false;
-  // fp16 three-product path (pss_xcorr_f16.hip): complex<float> sources of the batched device entry points
-  uint32_t *cap16h = nullptr, *cap16l = nullptr;   // (re, im) fp16 pairs, hi and lo parts, slot stride lcs_cap8_stride
-  uint32_t *brow16 = nullptr;        // template operands, hi and lo terms: one image of resident rows per (slot, group)
-  int *texp16 = nullptr;             // per template column: power-of-two scale exponent
-  float *tsc16 = nullptr;            // per template column: 2^-(k_x + k_t)
-  unsigned *xmax16 = nullptr;        // per slot: bits of the largest |component|
-  unsigned *xpart16 = nullptr;       // per slot: 128 partial maxima (one per workgroup of the read-only maximum pass)
-  bool f16_ready = false, use_f16 = false;
+  DevBuf<float2> cap32;
+  I8Set i8;
+  F16Set f16;
+  bool use_i8 = false, use_f16 = false;
   bool src_u8 = false;               // the resident buffers came from a u8 source: the fp64 stages read cap8
-  const float2 *src32 = nullptr;     // complex<float> batches read in place: the CALLER's buffers, which the fp64 stages read (no cap32 copy)
-  double2 *cap64 = nullptr;          // slot 0 only: fp64 copy for the host (complex<double>) entry points
+  const float2 *src32 = nullptr;     // VIEW: complex<float> batches read in place: the CALLER's buffers, which the fp64 stages read (no cap32 copy)
+  DevBuf<double2> cap64;             // slot 0 only: fp64 copy for the host (complex<double>) entry points
   bool cap64_valid = false;
-  SlotParams *params = nullptr;
-  double *fset = nullptr;
-  float2 *tmpl = nullptr;
-  int *start = nullptr, *smin = nullptr, *kp2 = nullptr;
-  float *btab = nullptr;             // fp32 kernel only: allocated by its first launch for the workspace's slots and groups
-  size_t btab_elems = 0;
-  float *single = nullptr, *incoh = nullptr, *sref = nullptr;
-  double *pow_ = nullptr, *work = nullptr, *spinc = nullptr, *zth = nullptr, *sp = nullptr;
-  int *frq = nullptr;
-  unsigned *fix_list = nullptr;      // [S][3][9600]: positions (slot * 3 + t) * 9600 + idx whose arg-max is a near-tie (capacity: every position)
-  int *n_fix = nullptr;              // [4]: entries on the list (zeroed by k_prep_tables)
-  float *second32 = nullptr;         // [S][3][9600]: the runner-up of the collapse's maximum (written for lcs_foe_partial only: lcs_foe_contend reads it)
-  double *fset_g = nullptr;          // the whole grid, for lcs_foe_contend (fset holds the rank's share then)
-  int fset_g_cap = 0;
+  DevBuf<SlotParams> params_ws;      // the workspace's parameter records and hypotheses (ensure_ws) ...
+  DevBuf<double> fset_ws;
+  SlotParams *params = nullptr;      // ... and the VIEWS every launcher and upload reads: of params_ws / fset_ws, except while the
+  double *fset = nullptr;            // streaming chain is issued or recorded -- then of the stream's device mirror (stream_chain)
+  DevBuf<float2> tmpl;
+  DevBuf<int> start, smin, kp2;
+  DevBuf<float> btab;                // fp32 kernel only: allocated by its first launch for the workspace's slots and groups
+  DevBuf<float> single, incoh, sref;
+  DevBuf<double> pow_, work, spinc, zth, sp;
+  DevBuf<int> frq;
+  DevBuf<unsigned> fix_list;         // [S][3][9600]: positions (slot * 3 + t) * 9600 + idx whose arg-max is a near-tie (capacity: every position)
+  DevBuf<int> n_fix;                 // [4]: entries on the list (zeroed by k_prep_tables)
+  DevBuf<float> second32;            // [S][3][9600]: the runner-up of the collapse's maximum (written for lcs_foe_partial only: lcs_foe_contend reads it)
+  DevBuf<double> fset_g;             // the whole grid, for lcs_foe_contend (fset holds the rank's share then)
   bool repair_peaks_only = false;    // lcs_search_capbuf / the streaming chain: list only the near-ties at or above their position's Z_th1 (pss_xcorr.hip: collapse_flag)
   bool skip_frq_repair = false;      // lcs_foe_partial: a rank sees only its share of the hypotheses (a near-tie may span two ranks)
-  lcs_cell *peaks = nullptr;
-  int *npeaks = nullptr;
-  float2 *xc = nullptr;             // debug: raw correlations [3][n_cap-136][n_f]
-  size_t xc_elems = 0;
+  DevBuf<lcs_cell> peaks;
+  DevBuf<int> npeaks;
+  DevBuf<float2> xc;                // debug: raw correlations [3][n_cap-136][n_f]
   // SSS / FOE stage (sss_foe.hip): work list of (buffer, peak) pairs and per-(peak, occurrence) records
-  WorkItem *pk_items = nullptr;
-  int *n_pk = nullptr;
-  double *sss_ws = nullptr;
-  size_t sss_ws_items = 0;
+  DevBuf<WorkItem> pk_items;
+  DevBuf<int> n_pk;
+  DevBuf<double> sss_ws;
   // per-cell stage buffers
-  WorkItem *work_items = nullptr;
-  int *n_work = nullptr;
-  double2 *tfg = nullptr;           // [MAX_WORK][854][72]
-  double2 *tfg_comp = nullptr;      // [MAX_WORK][854][72]
-  double2 *ce = nullptr;            // [MAX_WORK][4][854][72]
-  char *tfg_desc = nullptr;         // [MAX_WORK][LCS_TFG_DESC_BYTES]: per cell 856 window records in k_tfg's job order + 128 position factors (k_cell_prep)
-  double *tfg_ts = nullptr;         // [MAX_WORK][854]
-  double *tfg_ts_comp = nullptr;    // [MAX_WORK][854]
-  double *cell_scratch = nullptr;   // [MAX_WORK][CELL_SCRATCH]
-  lcs_cell *cells_out = nullptr;    // [MAX_WORK]
+  DevBuf<WorkItem> work_items;
+  DevBuf<int> n_work;
+  DevBuf<double2> tfg;              // [MAX_WORK][854][72]
+  DevBuf<double2> tfg_comp;         // [MAX_WORK][854][72]
+  DevBuf<double2> ce;               // [MAX_WORK][4][854][72]
+  DevBuf<char> tfg_desc;            // [MAX_WORK][LCS_TFG_DESC_BYTES]: per cell 856 window records in k_tfg's job order + 128 position factors (k_cell_prep)
+  DevBuf<double> tfg_ts;            // [MAX_WORK][854]
+  DevBuf<double> tfg_ts_comp;       // [MAX_WORK][854]
+  DevBuf<double> cell_scratch;      // [MAX_WORK][CELL_SCRATCH]
+  DevBuf<lcs_cell> cells_out;       // [MAX_WORK]
   // constant tables on the device
-  double2 *d_pss_td = nullptr;      // [3][137]
-  double2 *d_pss_fd = nullptr;      // [3][62]
-  int8_t *d_sss_fd = nullptr;       // [168][3][2][62]
-  uint8_t *d_pbch_scr = nullptr;    // [504][1920]
-  uint32_t *d_pn_jump = nullptr;    // [32]: Gold-sequence jump-ahead by 1600 + 208 clocks (lcs_tables::pn_jump_table)
-  int16_t *d_derm_inv = nullptr;    // [2][120][16]: for every coded bit (stream*40+col) the rate-matched PBCH bit positions carrying it (ascending, -1 padded)
-  double *d_dbg = nullptr;          // debug outputs of the single-cell stage entry points
-  int *d_flag = nullptr;            // exactness verdict of k_ingest_c128
+  DevBuf<double2> d_pss_td;         // [3][137]
+  DevBuf<double2> d_pss_fd;         // [3][62]
+  DevBuf<int8_t> d_sss_fd;          // [168][3][2][62]
+  DevBuf<uint8_t> d_pbch_scr;       // [504][1920]
+  DevBuf<uint32_t> d_pn_jump;       // [32]: Gold-sequence jump-ahead by 1600 + 208 clocks (lcs_tables::pn_jump_table)
+  DevBuf<int16_t> d_derm_inv;       // [2][120][16]: for every coded bit (stream*40+col) the rate-matched PBCH bit positions carrying it (ascending, -1 padded)
+  DevBuf<double> d_dbg;             // debug outputs of the single-cell stage entry points
+  DevBuf<int> d_flag;               // exactness verdict of k_ingest_c128
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
-  uint8_t *c64_u8 = nullptr;        // ... the bytes such a batch is turned into
-  size_t c64_u8_bytes = 0;
+  DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
   bool last_c64_routed = false;     // the last lcs_batch_enqueue of a complex<float> batch took the u8 route
   bool percell_ready = false;
@@ -249,46 +294,48 @@ struct lcs_ctx {
   int st_head = 0, st_count = 0;                  // two slots: oldest buffer in flight, number in flight
   int st_fmt = 0;
   uint32_t st_n_cap = 0;
-  void *st_hin[2] = {nullptr, nullptr};           // pinned copies of the pushed buffers
-  void *st_din = nullptr;                         // device copy (shared: the graph launches serialise)
-  size_t st_in_bytes = 0;
-  struct StreamHost *st_host[2] = {nullptr, nullptr};   // pinned parameter + result blocks
-  int16_t *st_dtracked = nullptr;     // (both point into st_dmirror)
+  PinnedBuf<char> st_hin[2];                      // pinned copies of the pushed buffers
+  DevBuf<char> st_din;                            // device copy (shared: the graph launches serialise)
+  size_t st_in_bytes = 0;                         // bytes of one pushed buffer
+  PinnedBuf<StreamHost> st_host[2];               // pinned parameter + result blocks
+  int16_t *st_dtracked = nullptr;     // VIEWS (both point into st_dmirror)
   int *st_dntracked = nullptr;
-  char *st_dmirror = nullptr;        // device mirror of StreamHost's input part
+  DevBuf<char> st_dmirror;           // device mirror of StreamHost's input part
   hipGraph_t st_graph[2] = {nullptr, nullptr};
   hipGraphExec_t st_exec[2] = {nullptr, nullptr};
   hipEvent_t st_ev0[2] = {nullptr, nullptr}, st_ev1[2] = {nullptr, nullptr};
   // tracker block pipeline (tracker.hip): workspace laid out for one (n_cells, n_sym) block shape
-  double2 *trk_td = nullptr, *trk_syms = nullptr, *trk_raw = nullptr, *trk_ce = nullptr;
-  double *trk_meta = nullptr, *trk_rs = nullptr, *trk_fmeta = nullptr, *trk_pw = nullptr;
-  int *trk_idx = nullptr, *trk_small = nullptr;
-  lcs_track_cell *trk_cells = nullptr;
+  DevBuf<double2> trk_td, trk_syms, trk_raw, trk_ce;
+  DevBuf<double> trk_meta, trk_rs, trk_fmeta, trk_pw;
+  DevBuf<int> trk_idx, trk_small;
+  DevBuf<lcs_track_cell> trk_cells;
   int trk_cells_cap = 0, trk_sym_cap = 0;     // the workspace holds any block of up to this many cells x symbols
   int trk_last_cells = 0, trk_last_sym = 0;   // shape of the block the last lcs_track_block call processed (lcs_track_stats reads it)
-  double2 *trk_acfd = nullptr, *trk_actd = nullptr, *trk_syncce = nullptr;   // lcs_track_stats outputs
-  double *trk_sync = nullptr;
+  DevBuf<double2> trk_acfd, trk_actd, trk_syncce;   // lcs_track_stats outputs
+  DevBuf<double> trk_sync;
   int trk_stat_cells = 0, trk_stat_sym = 0;   // capacity of the statistics buffers
-  void *trk_stream = nullptr;        // carried state of lcs_track_stream_block (tracker.hip)
-  void *trk_hpin = nullptr;          // reusable host staging block of lcs_track_block (malloc): metadata up, measurement tables down
-  size_t trk_hpin_bytes = 0;
-  int *trk_cut_hit = nullptr;       // lcs_track_cut: first sample of every symbol [cells][symbols], per-cell flag / count behind it
-  double *trk_cut_meta = nullptr;   // lcs_track_cut: late [cells][symbols], then frame_timing, freq_off [cells]
-  size_t trk_cut_cap = 0;           // symbols x cells the two hold
-  int trk_cut_cells_cap = 0;
+  TrkStream trk_stream;              // carried state of lcs_track_stream_block (tracker.hip)
+  Buf<char, LcsPageableMem> trk_hpin;   // reusable host staging block of lcs_track_block (pageable): metadata up, measurement tables down
+  DevBuf<int> trk_cut_hit;          // lcs_track_cut: first sample of every symbol [cells][symbols], per-cell flag / count behind it
+  DevBuf<double> trk_cut_meta;      // lcs_track_cut: late [cells][symbols], then frame_timing, freq_off [cells]
+  size_t trk_cut_cap = 0;           // the SHAPE the two are laid out for (as trk_cells_cap / trk_sym_cap): symbols x cells ...
+  int trk_cut_cells_cap = 0;        // ... and cells
+  // wideband channelizer (channelizer.hip)
+  DevBuf<char> chan_par;            // [n_ch] phase steps, then the taps
+  DevBuf<float> chan_tab;           // the filter bank in A-operand order
+  PinnedBuf<char> chan_hpin[2];     // page-locked parameter slots, used in turn
+  int chan_slot = 0;
+  bool chan_timed = false;
   // results of a batch, compacted on the device (k_pack_results): [8 ints header][n_buf counts][records]; h_res = its page-locked mirror
-  void *res_pack = nullptr, *h_res = nullptr;
-  size_t res_pack_bytes = 0;
+  DevBuf<char> res_pack;
+  PinnedBuf<char> h_res;
   double last_collect_host_us = 0;   // host time of the last lcs_batch_collect outside its wait for the GPU
   int collect_hint = 0;              // records the last collected batch returned: sizes the first copy of the next collect
   // host staging
   SlotParams h_params{};             // source of asynchronous parameter uploads of the single-buffer entry points
-  void *h_pinned = nullptr;
-  size_t h_pinned_bytes = 0;
-  void *h2d = nullptr;               // device staging of lcs_batch_enqueue_host
-  void *h_stage[2] = {nullptr, nullptr};        // pinned slots for host sources that are not page-locked
-  hipEvent_t ev_stage[2] = {nullptr, nullptr};
-  size_t h2d_bytes = 0;
+  PinnedBuf<char> h_pinned;
+  DevBuf<char> h2d;                  // device staging of lcs_batch_enqueue_host
+  PinnedBuf<char> h_stage[2];        // pinned slots for host sources that are not page-locked
 
   // last batch bookkeeping
   int last_n_buf = 0;
@@ -307,7 +354,6 @@ struct lcs_ctx {
   XcGeom foe_geo{};                  // lcs_foe_partial -> lcs_foe_finish: this rank's share of the hypotheses
   bool foe_ready = false;
   uint32_t foe_n_cap = 0;
-  hipEvent_t ev_xc0 = nullptr, ev_xc1 = nullptr;
   int last_xc_launches = 0;
   double last_xc_ops = 0;            // matrix-core operations (2 x MACs) the correlation launches of the last batch executed
   const char *last_xc_kernel = "";
@@ -317,13 +363,14 @@ struct lcs_ctx {
 #define LCS_EVENT_NOFENCE hipEventDisableSystemFence
 #endif
 
+inline int lcs_hip_error(lcs_ctx *c, const char *call, hipError_t e) {
+  c->err = std::string(call) + ": " + hipGetErrorString(e);
+  return LCS_ERR_HIP;
+}
 #define HIPCHK(ctx, call)                                                        \
   do {                                                                           \
     hipError_t e_ = (call);                                                      \
-    if (e_ != hipSuccess) {                                                      \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);            \
-      return LCS_ERR_HIP;                                                        \
-    }                                                                            \
+    if (e_ != hipSuccess) return lcs_hip_error((ctx), #call, e_);                \
   } while (0)
 
 // ---- host tables (lte_tables.cpp) --------------------------------------------------
@@ -336,8 +383,6 @@ void pn_jump_table(uint32_t steps, uint32_t out[32]);
 double chi2cdf_inv(double p, double k);
 void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.cpp:409-463 via :473-478
 }  // namespace lcs_tables
-
-void lcs_track_stream_free(lcs_ctx *c);   // tracker.hip
 
 // ---- kernel launchers (one per .hip file) -------------------------------------------
 // pss_xcorr.hip

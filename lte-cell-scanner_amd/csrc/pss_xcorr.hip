@@ -1062,7 +1062,7 @@ __global__ __launch_bounds__(256) void k_foe_resolve(long long *__restrict__ wor
 CapSrc lcs_cap_src(const lcs_ctx *c, uint32_t n_cap) {
   CapSrc s{nullptr, nullptr, nullptr, n_cap};
   if (c->cap64_valid) s.c64 = c->cap64;
-  else if (c->src_u8) s.c8 = c->cap8;
+  else if (c->src_u8) s.c8 = c->i8.cap8;
   else s.c32 = c->src32 ? c->src32 : c->cap32;
   return s;
 }
@@ -1074,7 +1074,7 @@ int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact) {
   c->src32 = nullptr;
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
-  hipLaunchKernelGGL(k_ingest_c128, dim3(nb), dim3(256), 0, c->stream, c->cap64, n_cap, c->cap32, c->cap8, c->cap8s, c->d_flag);
+  hipLaunchKernelGGL(k_ingest_c128, dim3(nb), dim3(256), 0, c->stream, c->cap64, n_cap, c->cap32, c->i8.cap8, c->i8.cap8s, c->d_flag);
   HIPCHK(c, hipGetLastError());
   int flag = 1;
   HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1088,7 +1088,7 @@ int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_
   c->src32 = nullptr;
   if (fmt == LCS_FMT_IQ_U8) {
     const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
-    hipLaunchKernelGGL(k_ingest_u8, dim3(nb, n_buf), dim3(256), 0, c->stream, (const uint8_t *)d_src, n_cap, c->cap8, c->cap8s);
+    hipLaunchKernelGGL(k_ingest_u8, dim3(nb, n_buf), dim3(256), 0, c->stream, (const uint8_t *)d_src, n_cap, c->i8.cap8, c->i8.cap8s);
   } else {
     hipLaunchKernelGGL(k_ingest, dim3(128, n_buf), dim3(256), 0, c->stream, d_src, fmt, n_cap, c->cap32, c->cap64);
   }
@@ -1108,14 +1108,10 @@ static hipEvent_t g_xc_done[64] = {};
 // The fp32 kernel's operand tables: one per (slot, window, group), 0.5 MB each -- only contexts that take this kernel pay for them.
 int lcs_ensure_btab(lcs_ctx *c) {
   const size_t need = (size_t)c->cap_slots * LCS_NW_MAX * c->cap_G * LCS_KP2_MAX * 64;
-  if (need <= c->btab_elems) return LCS_OK;
+  if (need <= c->btab.capacity()) return LCS_OK;
   if (c->st_open) { c->err = "the fp32 correlation tables cannot be allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->btab) (void)hipFree(c->btab);
-  c->btab = nullptr; c->btab_elems = 0;
-  HIPCHK(c, hipMalloc((void **)&c->btab, need * sizeof(float)));
-  c->btab_elems = need;
-  return LCS_OK;
+  return c->btab.reserve(c, need);
 }
 
 int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, bool time_it) {
@@ -1148,7 +1144,7 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
   a.rx_cutoff = (6 * 12 * 15e3 / 2 + 4 * 15e3) / (30720000.0 / 16 / 2);
   auto launch_sp = [&](hipStream_t st) {
     if (c->src_u8 && !c->cap64_valid) {
-      hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, st, c->cap8, geo.n_cap, c->spinc, c->zth, a);
+      hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, st, c->i8.cap8, geo.n_cap, c->spinc, c->zth, a);
     } else {
       hipLaunchKernelGGL(k_sp_sums, dim3(((LCS_N_IDX + SP_TILE - 1) / SP_TILE) * a.n_comb_sp * n_buf), dim3(64), 0,
                          st, lcs_cap_src(c, geo.n_cap), c->sp, geo.n_cap, a.n_comb_sp, n_buf);       // one-wave workgroups
@@ -1214,7 +1210,7 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
   {
     const dim3 grid((LCS_N_IDX / 64) * n_buf), block(256);
     float *incoh = want_incoh ? c->incoh : nullptr;
-    float *pow32 = reinterpret_cast<float *>(c->work);
+    float *pow32 = reinterpret_cast<float *>(c->work.get());
     const double *zf = c->repair_peaks_only ? c->zth : nullptr;      // fused single-buffer chains: only near-ties that can become a peak
     float *s2 = c->skip_frq_repair ? c->second32 : nullptr;          // lcs_foe_partial: the runner-up values for lcs_foe_contend
     if (geo.ds == 2 && !incoh && geo.cpg == LCS_TG)
@@ -1243,7 +1239,7 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
 // lcs_foe_contend / lcs_foe_resolve (lcs_api.hip): fset_g = the WHOLE grid on the device
 int lcs_launch_foe_contend(lcs_ctx *c, const XcGeom &geo, const double *fset_g, const long long *d_words, long long *d_words2) {
   HIPCHK(c, hipMemsetAsync(c->n_fix, 0, 2 * sizeof(int), c->stream));
-  float *pow32 = reinterpret_cast<float *>(c->work);
+  float *pow32 = reinterpret_cast<float *>(c->work.get());
   hipLaunchKernelGGL(k_foe_flag, dim3((3 * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, d_words, pow32, c->second32, d_words2, c->fix_list, c->n_fix, geo);
   const CapSrc cs = lcs_cap_src(c, geo.n_cap);
 #define CONTEND_LAUNCH(KIND) hipLaunchKernelGGL((k_frq_repair<KIND, true>), dim3(512), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, cs, \

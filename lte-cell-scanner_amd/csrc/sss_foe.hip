@@ -537,13 +537,12 @@ __global__ __launch_bounds__(64) void k_foe_fin(lcs_cell *__restrict__ peaks, co
 // mode bit 0: run sss_detect, bit 1: run pss_sss_foe (only for cells whose SSS was found)
 static int run_sss_foe(lcs_ctx *c, int n_buf, uint32_t n_cap, double thresh2, int mode, double *dbg) {
   const size_t cap_items = (size_t)n_buf * LCS_MAXP;
-  if (cap_items > c->sss_ws_items) {
-    if (c->sss_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->sss_ws); c->sss_ws = nullptr; }
-    if (c->pk_items) { (void)hipFree(c->pk_items); c->pk_items = nullptr; }
-    HIPCHK(c, hipMalloc((void **)&c->sss_ws, cap_items * SW_ITEM * sizeof(double)));
-    HIPCHK(c, hipMalloc((void **)&c->pk_items, cap_items * sizeof(WorkItem)));
-    if (!c->n_pk) HIPCHK(c, hipMalloc((void **)&c->n_pk, 4 * sizeof(int)));
-    c->sss_ws_items = cap_items;
+  if (cap_items > c->pk_items.capacity() || cap_items * SW_ITEM > c->sss_ws.capacity()) {      // the two grow together
+    int rc;
+    if (c->sss_ws || c->pk_items) HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sss_ws.reset();
+    c->pk_items.reset();
+    if ((rc = c->sss_ws.alloc(c, cap_items * SW_ITEM)) || (rc = c->pk_items.alloc(c, cap_items)) || (rc = c->n_pk.reserve(c, 4))) return rc;
   }
   const CapSrc src = lcs_cap_src(c, n_cap);
   // enough workgroups for every (peak, occurrence) of a typical batch to be resident at once; the

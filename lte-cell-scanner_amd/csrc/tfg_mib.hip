@@ -1023,9 +1023,9 @@ int lcs_launch_gather_work(lcs_ctx *c, int n_buf, int skip, int limit) {
   return LCS_OK;
 }
 int lcs_launch_pack_results(lcs_ctx *c, int n_buf, bool full) {
-  int *hdr = reinterpret_cast<int *>(c->res_pack);
+  int *hdr = reinterpret_cast<int *>(c->res_pack.get());
   hipLaunchKernelGGL(k_pack_results, dim3(1), dim3(64), 0, c->stream, c->peaks, c->npeaks, n_buf, full ? 1 : 0, full ? c->n_work : nullptr, hdr, hdr + 8,
-                     reinterpret_cast<lcs_cell *>(reinterpret_cast<char *>(c->res_pack) + lcs_pack_rec_offset(n_buf)));
+                     reinterpret_cast<lcs_cell *>(c->res_pack + lcs_pack_rec_offset(n_buf)));
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

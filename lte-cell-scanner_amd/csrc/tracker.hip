@@ -710,12 +710,6 @@ struct TrkLayout {
     d_mibfirst = c->trk_small + C4 * 2 + (size_t)n_cells * (n_off + 1) * 3;
   }
 };
-template <typename T>
-int trk_alloc(lcs_ctx *c, T **p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIPCHK(c, hipMalloc((void **)p, n * sizeof(T)));
-  return LCS_OK;
-}
 }  // namespace
 
 namespace {
@@ -740,11 +734,11 @@ int trk_ensure_ws(lcs_ctx *c, int n_cells, int n_sym) {
     // the caps describe a complete workspace or nothing: if an allocation below fails, later calls must not take the
     // half-replaced buffers for the old shape
     c->trk_cells_cap = c->trk_sym_cap = 0;
-    if ((rc = trk_alloc(c, &c->trk_td, N * 128)) || (rc = trk_alloc(c, &c->trk_meta, N * 4)) || (rc = trk_alloc(c, &c->trk_cells, (size_t)cc)) ||
-        (rc = trk_alloc(c, &c->trk_syms, N * 72)) || (rc = trk_alloc(c, &c->trk_rs, (size_t)cc * 140 * 28)) ||
-        (rc = trk_alloc(c, &c->trk_idx, C4 * (rs_cap + 1))) || (rc = trk_alloc(c, &c->trk_raw, C4 * rs_cap * 24)) ||
-        (rc = trk_alloc(c, &c->trk_fmeta, C4 * rs_cap * (4 + TRK_MEAS))) || (rc = trk_alloc(c, &c->trk_ce, C4 * cs * 72)) ||
-        (rc = trk_alloc(c, &c->trk_pw, C4 * cs * 4)) || (rc = trk_alloc(c, &c->trk_small, C4 * 2 + (size_t)cc * (n_off + 1) * 3 + cc)))
+    if ((rc = c->trk_td.alloc(c, N * 128)) || (rc = c->trk_meta.alloc(c, N * 4)) || (rc = c->trk_cells.alloc(c, (size_t)cc)) ||
+        (rc = c->trk_syms.alloc(c, N * 72)) || (rc = c->trk_rs.alloc(c, (size_t)cc * 140 * 28)) ||
+        (rc = c->trk_idx.alloc(c, C4 * (rs_cap + 1))) || (rc = c->trk_raw.alloc(c, C4 * rs_cap * 24)) ||
+        (rc = c->trk_fmeta.alloc(c, C4 * rs_cap * (4 + TRK_MEAS))) || (rc = c->trk_ce.alloc(c, C4 * cs * 72)) ||
+        (rc = c->trk_pw.alloc(c, C4 * cs * 4)) || (rc = c->trk_small.alloc(c, C4 * 2 + (size_t)cc * (n_off + 1) * 3 + cc)))
       return rc;
     c->trk_cells_cap = cc; c->trk_sym_cap = cs;
   }
@@ -779,15 +773,11 @@ int trk_block(lcs_ctx *c, lcs_track_cell *cells, int n_cells, int n_sym, const v
   const size_t n_meas_d = C4 * rs_cap * TRK_MEAS, n_small = C4 * 2 + (size_t)n_cells * n_off, n_bits = (size_t)n_cells * n_off + 1;
   const size_t up_bytes = sizeof(double) * 3 * N + sizeof(lcs_track_cell) * n_cells;
   const size_t down_bytes = sizeof(double) * n_meas_d + sizeof(unsigned long long) * n_bits + sizeof(int) * n_small + sizeof(lcs_track_cell) * n_cells;
-  if (up_bytes + down_bytes + 64 > c->trk_hpin_bytes) {
-    if (c->trk_hpin) { HIPCHK(c, hipStreamSynchronize(c->stream)); free(c->trk_hpin); c->trk_hpin = nullptr; c->trk_hpin_bytes = 0; }
-    c->trk_hpin = malloc(up_bytes + down_bytes + 64);
-    if (!c->trk_hpin) { c->err = "out of host memory"; return LCS_ERR_HIP; }
-    c->trk_hpin_bytes = up_bytes + down_bytes + 64;
-  }
-  double *h_up = static_cast<double *>(c->trk_hpin);
+  if (c->trk_hpin && up_bytes + down_bytes + 64 > c->trk_hpin.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = c->trk_hpin.reserve(c, up_bytes + down_bytes + 64))) return rc;
+  double *h_up = reinterpret_cast<double *>(c->trk_hpin.get());
   lcs_track_cell *h_cells_up = reinterpret_cast<lcs_track_cell *>(h_up + 3 * N);
-  double *h_meas = reinterpret_cast<double *>(static_cast<char *>(c->trk_hpin) + ((up_bytes + 15) & ~(size_t)15));
+  double *h_meas = reinterpret_cast<double *>(c->trk_hpin + ((up_bytes + 15) & ~(size_t)15));
   unsigned long long *h_bits = reinterpret_cast<unsigned long long *>(h_meas + n_meas_d);
   int *h_small = reinterpret_cast<int *>(h_bits + n_bits);
   lcs_track_cell *h_cells_down = reinterpret_cast<lcs_track_cell *>(h_small + ((n_small + 1) & ~(size_t)1));
@@ -884,7 +874,7 @@ extern "C" int lcs_track_cut(lcs_ctx *c, const void *d_capbuf, int fmt, uint32_t
     const int capC = std::max(n_cells, c->trk_cut_cells_cap);
     c->trk_cut_cap = 0; c->trk_cut_cells_cap = 0;
     int rc;
-    if ((rc = trk_alloc(c, &c->trk_cut_hit, capN + 4 * (size_t)capC + 2)) || (rc = trk_alloc(c, &c->trk_cut_meta, capN + 5 * (size_t)capC))) return rc;
+    if ((rc = c->trk_cut_hit.alloc(c, capN + 4 * (size_t)capC + 2)) || (rc = c->trk_cut_meta.alloc(c, capN + 5 * (size_t)capC))) return rc;
     HIPCHK(c, hipMemsetAsync(c->trk_cut_hit, 0, sizeof(int) * (capN + 4 * (size_t)capC + 2), c->stream));      // the per-cell flags start at zero
     c->trk_cut_cap = capN; c->trk_cut_cells_cap = capC;
   }
@@ -933,8 +923,8 @@ extern "C" int lcs_track_stats(lcs_ctx *c, int n_cells, int n_sym, double *ac_fd
     const size_t C4c = (size_t)cc * 4, rsc = (size_t)cs / 3 + 4, hfc = (size_t)cs / 60 + 2;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->trk_stat_cells = c->trk_stat_sym = 0;
-    if ((rc = trk_alloc(c, &c->trk_acfd, C4c * rsc * 12)) || (rc = trk_alloc(c, &c->trk_actd, C4c * rsc * 72)) ||
-        (rc = trk_alloc(c, &c->trk_sync, (size_t)cc * hfc * 4)) || (rc = trk_alloc(c, &c->trk_syncce, (size_t)cc * hfc * 72)))
+    if ((rc = c->trk_acfd.alloc(c, C4c * rsc * 12)) || (rc = c->trk_actd.alloc(c, C4c * rsc * 72)) ||
+        (rc = c->trk_sync.alloc(c, (size_t)cc * hfc * 4)) || (rc = c->trk_syncce.alloc(c, (size_t)cc * hfc * 72)))
       return rc;
     c->trk_stat_cells = cc; c->trk_stat_sym = cs;
   }
@@ -992,42 +982,9 @@ extern "C" int lcs_track_stats(lcs_ctx *c, int n_cells, int n_sym, double *ac_fd
 // whole stream.  The carried frames are not transformed again (k_trk_fd starts behind them; the rows are the ones the
 // previous call computed, bit for bit) and frame offsets an earlier call attempted are not decoded again (k_trk_mib skips
 // them); the per-port passes of k_trk_ce still run over them (the raw estimates and filter windows they rebuild are cheap).
-namespace {
-struct TrkStreamCell {
-  std::vector<double> fo, ft, late;          // metadata of the carried symbols
-  double bpo_before_tail = 0;                // bulk phase before the first carried symbol
-  long long tail_start = 0;                  // stream index of the first carried symbol (a frame boundary)
-  long long n_seen = 0;                      // symbols delivered so far
-  long long next_raw[4] = {1, 1, 1, 1};      // per port: reference-symbol row (counted from the stream start) whose filter is emitted next
-  long long ce_upto[4] = {0, 0, 0, 0};       // per port: channel estimates emitted for symbols below this
-  long long mib_next = 0;                    // first frame offset not attempted yet
-  int cp_type = 0, n_id_1 = -1, n_id_2 = -1, n_ports = 0;
-};
-// The carried symbols themselves stay on the DEVICE, already transformed: per CP type the frequency-domain rows
-// [cells of that type][carried symbols][72] of the previous call (round 3 kept the time-domain samples on the host and ran
-// them through get_fd again with every call).
-struct TrkStream {
-  std::vector<TrkStreamCell> cells;
-  // indexed by LCS_CP_NORMAL / LCS_CP_EXTENDED: the carried rows, and a second buffer the next call's tail is written into
-  // before the two change places at the commit (no allocation or hipFree -- a device-wide synchronisation -- per call)
-  double2 *d_tail[3] = {nullptr, nullptr, nullptr}, *d_spare[3] = {nullptr, nullptr, nullptr};
-  size_t tail_cap[3] = {0, 0, 0}, spare_cap[3] = {0, 0, 0};      // capacities in double2
-};
-}  // namespace
-
-void lcs_track_stream_free(lcs_ctx *c) {
-  TrkStream *st = static_cast<TrkStream *>(c->trk_stream);
-  if (st) {
-    for (double2 *p : st->d_tail) if (p) (void)hipFree(p);
-    for (double2 *p : st->d_spare) if (p) (void)hipFree(p);
-  }
-  delete st;
-  c->trk_stream = nullptr;
-}
-
 extern "C" int lcs_track_stream_reset(lcs_ctx *c) {
   if (!c) return LCS_ERR_BAD_ARG;
-  lcs_track_stream_free(c);
+  c->trk_stream = TrkStream();      // (the carried rows on the device go with it)
   return LCS_OK;
 }
 
@@ -1042,8 +999,7 @@ extern "C" int lcs_track_stream_block(lcs_ctx *c, lcs_track_cell *cells, int n_c
     c->err = "bad argument";
     return LCS_ERR_BAD_ARG;
   }
-  TrkStream *st = static_cast<TrkStream *>(c->trk_stream);
-  if (!st) { st = new TrkStream(); c->trk_stream = st; }
+  TrkStream *st = &c->trk_stream;
   if (st->cells.empty()) {
     st->cells.resize(n_cells);
     for (int i = 0; i < n_cells; ++i) {
@@ -1136,13 +1092,8 @@ extern "C" int lcs_track_stream_block(lcs_ctx *c, lcs_track_cell *cells, int n_c
     std::vector<double> bpo_at(G, 0.0);
     {
       const size_t need = (size_t)72 * n_keep * G;
-      if (need > st->spare_cap[cp]) {
-        if (st->d_spare[cp]) { (void)hipFree(st->d_spare[cp]); st->d_spare[cp] = nullptr; st->spare_cap[cp] = 0; }
-        const size_t cap = need + need / 4;               // head room: the tail's length varies by up to a frame from call to call
-        const hipError_t e = hipMalloc((void **)&st->d_spare[cp], sizeof(double2) * cap);
-        if (e != hipSuccess) { st->d_spare[cp] = nullptr; c->err = std::string("hipMalloc (carried symbols): ") + hipGetErrorString(e); return fail(LCS_ERR_HIP); }
-        st->spare_cap[cp] = cap;
-      }
+      // head room: the tail's length varies by up to a frame from call to call
+      if (need > st->d_spare[cp].capacity() && (rc = st->d_spare[cp].alloc(c, need + need / 4))) return fail(rc);
       const TrkLayout Lay(c, G, L);
       hipError_t e2 = hipMemcpy2DAsync(st->d_spare[cp], sizeof(double2) * 72 * n_keep, c->trk_syms + keep_from * 72, sizeof(double2) * 72 * (size_t)L,
                                        sizeof(double2) * 72 * n_keep, G, hipMemcpyDeviceToDevice, c->stream);
@@ -1220,7 +1171,7 @@ extern "C" int lcs_track_stream_block(lcs_ctx *c, lcs_track_cell *cells, int n_c
   // commit
   st->cells.swap(next);
   for (int cp = LCS_CP_NORMAL; cp <= LCS_CP_EXTENDED; ++cp)
-    if (group_done[cp]) { std::swap(st->d_tail[cp], st->d_spare[cp]); std::swap(st->tail_cap[cp], st->spare_cap[cp]); }
+    if (group_done[cp]) std::swap(st->d_tail[cp], st->d_spare[cp]);
   if (rc_all) c->err = "more rows than the output arrays hold (rows beyond the capacity were dropped)";
   return rc_all;
 }

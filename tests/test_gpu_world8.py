@@ -138,6 +138,78 @@ def test_contexts_give_their_memory_back():
     assert abs(free1 - free0) < 64 << 20, (free0, free1)
 
 
+def context_lifetime_cycles(n_cycles=8):
+    """One warm-up cycle (the runtime's own lazy allocations), then n_cycles more, each a context's whole life: create; a u8 batch; a larger
+    complex<float> batch (the workspace, the fp16 set and the result block grow); one host buffer through lcs_search_capbuf; lcs_stream_open /
+    push / collect / lcs_stream_close; one channelizer call; one small tracker block; destroy.  Returns every reading of the device's free
+    memory taken on the way (one after each entry point of each cycle) and the readings before and after the n_cycles."""
+    import torch
+    from conftest import f_search_set_for
+    pkg = load_pkg()
+    iq = golden("capbuf_0000")["iq_u8"]
+    cap = iq_u8_to_capbuf(iq)
+    FC, FS = 739e6, 1.92e6
+    f = f_search_set_for(FC, 100)
+    d8 = torch.from_numpy(np.ascontiguousarray(np.stack([iq] * 4))).cuda()
+    d32 = torch.from_numpy(np.stack([cap.astype(np.complex64)] * 8)).cuda()
+    n_out, D, n_ch = 256, 8, 40
+    d_wide = torch.zeros((n_out - 1) * D + 16 * D, dtype=torch.complex64, device="cuda")
+    d_nb = torch.zeros((n_ch, n_out), dtype=torch.complex64, device="cuda")
+    rng = np.random.default_rng(5)
+    n_sym = 280
+    td = 0.1 * (rng.standard_normal((1, n_sym, 128)) + 1j * rng.standard_normal((1, n_sym, 128)))
+    tracked = pkg.new_cell(n_id_1=92, n_id_2=1, cp_type=1, n_ports=2, n_rb_dl=6, phich_duration=1, phich_resource=1)
+    torch.cuda.synchronize()
+    readings = []
+
+    def free():
+        torch.cuda.synchronize()
+        readings.append(torch.cuda.mem_get_info()[0])
+        return readings[-1]
+
+    def one():
+        with pkg.Searcher(0) as S:
+            S.search_batch(d8.data_ptr(), pkg.FMT_IQ_U8, 4, 153600, f[:9], np.full(4, FC), np.full(4, FC), FS, pkg.STAGE_FULL)
+            free()
+            S.search_batch(d32.data_ptr(), pkg.FMT_C64, 8, 153600, f, np.full(8, FC), np.full(8, FC), FS, pkg.STAGE_FULL)
+            free()
+            S.search_capbuf(cap, np.array([30e3, 35e3, 40e3]), FC, FC, FS)
+            free()
+            S.stream_open(pkg.FMT_IQ_U8, 153600, FC, FC, FS)
+            S.stream_push(iq, 35e3)
+            S.stream_collect()
+            S.stream_close()
+            free()
+            S.channelize(d_wide.data_ptr(), pkg.FMT_C64, d_wide.numel(), D * FS, D, np.linspace(-0.4, 0.4, n_ch) * D * FS, d_nb.data_ptr(), n_out)
+            free()
+            S.track_block([tracked], td, np.full((1, n_sym), 35e3), np.zeros((1, n_sym)), np.zeros((1, n_sym)), FC, FC, FS, want_ce=False)
+            free()
+        free()
+
+    one()
+    free0 = free()
+    for _ in range(n_cycles):
+        one()
+    return readings, free0, free()
+
+
+# What context_lifetime_cycles measured at the commit before the context's memory got its owning type (hand-written free lists in
+# lcs_destroy, lcs_stream_close, the channelizer's map): free memory lost over the 8 cycles, and the allocation granule -- the smallest
+# non-zero step between two consecutive readings of that run (free memory stood at 308352647168 bytes before and after the 8 cycles).
+LIFETIME_DRIFT_BEFORE = 0
+LIFETIME_GRANULE = 2 << 20
+
+
+def test_context_lifetime_leaves_no_memory_behind():
+    """Eight whole context lifetimes (context_lifetime_cycles) lose no more of the device's free memory than they did when every buffer
+    was freed by hand, plus one allocation granule: a buffer that a context fails to give back shows up eight times over."""
+    readings, free0, free1 = context_lifetime_cycles(8)
+    drift = free0 - free1
+    steps = sorted({abs(b - a) for a, b in zip(readings, readings[1:])} - {0})
+    print(f"lifetime: drift over 8 cycles {drift} bytes; smallest step of free memory {steps[0] if steps else None}; free0 {free0} free1 {free1}")
+    assert drift <= LIFETIME_DRIFT_BEFORE + LIFETIME_GRANULE, (drift, free0, free1)
+
+
 def test_searcher_and_tracker_contexts_side_by_side_from_two_threads():
     """A searcher context (full-chain batches) and a tracker context (cutter + block) driven from two host threads at once -- the shape of
     LTE-Tracker's searcher and tracker threads on one GPU: every result identical to the same calls made alone."""
