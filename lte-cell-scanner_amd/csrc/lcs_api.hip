@@ -43,8 +43,6 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
   const size_t S = n_slots, NE = 3 * LCS_N_IDX;
   const int G = std::max(std::max(G_need, c->cap_G), (3 * n_f + LCS_TG - 1) / LCS_TG);
   int rc;
-  c->params = nullptr;      // the views follow their owners
-  c->fset = nullptr;
   c->btab.reset();          // fp32 kernel's operand tables (0.5 MB per slot and group): allocated by its first launch (lcs_launch_xcorr)
   c->i8 = I8Set();          // the int8 and fp16 sets were sized for the old workspace: gone, allocated again on first use
   c->f16 = F16Set();
@@ -59,9 +57,8 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
       (rc = c->zth.alloc(c, S * LCS_N_IDX)) || (rc = c->peaks.alloc(c, S * LCS_MAXP)) || (rc = c->npeaks.alloc(c, S)) ||
       (debug && (rc = c->incoh.alloc(c, S * NE * n_f))))
     return rc;
-  c->params = c->params_ws;
-  c->fset = c->fset_ws;
   c->foe_ready = false;      // (a pending lcs_foe_partial result lived in the buffers just replaced)
+  c->batch = BatchRecord();  // ... and so did the last batch: its record points into them (lcs_batch_collect / _readback then refuse)
   c->cap_slots = n_slots;
   c->cap_n_cap = n_cap;
   c->cap_n_f = n_f;
@@ -147,10 +144,13 @@ int ensure_res_pack(lcs_ctx *c, int n_buf) {
   return LCS_OK;
 }
 
-// Largest tap count (137 + the spread of the window starts inside one template group, see k_prep_tables) of a frequency
-// grid packed `cpg` template columns per group.
-int grid_taps(const XcGeom &geo, const double *fset, double fc_req, double fc_prog, double fs_prog) {
-  int worst = 137;
+// One walk over the (window, group) pairs of a frequency grid packed `cpg` template columns per group: the largest spread of the
+// window starts inside one template group (see k_prep_tables; the correlation kernels hold 137 taps + that spread), and the number
+// of leading combining windows in which every group's spread stays within LCS_NARROW_SPREAD samples (the spread grows with the
+// window index; the count stops at the first window that exceeds it).
+struct GridSpread { int worst, n_narrow; };
+GridSpread grid_spread(const XcGeom &geo, const double *fset, double fc_req, double fc_prog, double fs_prog) {
+  GridSpread r{0, geo.n_comb};
   for (int w = 0; w < geo.n_comb; ++w)
     for (int g = 0; g < geo.G; ++g) {
       const int c_hi = std::min(g * geo.cpg + geo.cpg - 1, geo.n_tmpl - 1);
@@ -161,27 +161,10 @@ int grid_taps(const XcGeom &geo, const double *fset, double fc_req, double fc_pr
         const int s = (int)std::rint((((double)w * .005) * kf) * fs_prog);
         if (f == f_lo) { mn = mx = s; } else { mn = std::min(mn, s); mx = std::max(mx, s); }
       }
-      worst = std::max(worst, 137 + (mx - mn));
+      r.worst = std::max(r.worst, mx - mn);
+      if (mx - mn > LCS_NARROW_SPREAD) r.n_narrow = std::min(r.n_narrow, w);
     }
-  return worst;
-}
-
-// Number of leading combining windows in which the window starts of every group's hypotheses stay within LCS_NARROW_SPREAD
-// samples (the spread grows with the window index; the count stops at the first window that exceeds it).
-int grid_narrow_windows(const XcGeom &geo, const double *fset, double fc_req, double fc_prog, double fs_prog) {
-  for (int w = 0; w < geo.n_comb; ++w)
-    for (int g = 0; g < geo.G; ++g) {
-      const int c_hi = std::min(g * geo.cpg + geo.cpg - 1, geo.n_tmpl - 1);
-      const int f_lo = (g * geo.cpg) / 3, f_hi = c_hi / 3;
-      int mn = 0, mx = 0;
-      for (int f = f_lo; f <= f_hi; ++f) {
-        const double kf = (fc_req - fset[f]) / fc_prog;
-        const int s = (int)std::rint((((double)w * .005) * kf) * fs_prog);
-        if (f == f_lo) { mn = mx = s; } else { mn = std::min(mn, s); mx = std::max(mx, s); }
-      }
-      if (mx - mn > LCS_NARROW_SPREAD) return w;
-    }
-  return geo.n_comb;
+  return r;
 }
 
 // Choose how the 3 n_f templates are packed into 16-column groups: densely when the window starts of a group's
@@ -192,16 +175,14 @@ XcGeom pack_grid(uint32_t n_cap, int n_f, int ds, const double *fset, const doub
   static const int packings[] = {LCS_TG, 15, 12, 9, 6, 3};
   for (int cpg : packings) {
     XcGeom geo = make_geo(n_cap, n_f, ds, cpg);
-    bool fits = true;
-    for (int i = 0; i < n_buf && fits; ++i)
-      if (i == 0 || fc_req[i] != fc_req[i - 1] || fc_prog[i] != fc_prog[i - 1])
-        fits = grid_taps(geo, fset, fc_req[i], fc_prog[i], fs_prog) <= max_taps;
-    if (fits || cpg == 3) {
-      int nn = geo.n_comb;
-      for (int i = 0; i < n_buf && nn > 0; ++i)
-        if (i == 0 || fc_req[i] != fc_req[i - 1] || fc_prog[i] != fc_prog[i - 1])
-          nn = std::min(nn, grid_narrow_windows(geo, fset, fc_req[i], fc_prog[i], fs_prog));
-      geo.n_narrow = nn;
+    GridSpread all{0, geo.n_comb};
+    for (int i = 0; i < n_buf && (cpg == 3 || 137 + all.worst <= max_taps); ++i)      // (a packing that does not fit is left at once)
+      if (i == 0 || fc_req[i] != fc_req[i - 1] || fc_prog[i] != fc_prog[i - 1]) {
+        const GridSpread s = grid_spread(geo, fset, fc_req[i], fc_prog[i], fs_prog);
+        all = GridSpread{std::max(all.worst, s.worst), std::min(all.n_narrow, s.n_narrow)};
+      }
+    if (137 + all.worst <= max_taps || cpg == 3) {
+      geo.n_narrow = all.n_narrow;
       return geo;
     }
   }
@@ -229,11 +210,28 @@ __global__ __launch_bounds__(256) void k_c64_probe_u8(const float *__restrict__ 
   if (__any(!ok) && (threadIdx.x & 63) == 0) atomicAnd(flag, 0);
 }
 
+// The one place a Launch is built: n_buf buffers of n_cap samples that the fp64 stages read from `src`, parameters and hypotheses in
+// the workspace's arrays, 64 workgroups per work-list axis.  The entry point then sets what differs for its call.  Two things a
+// context with an OPEN STREAM hands to every launch made on it, not only to the stream's own chain: everything runs on one
+// stream, and k_gather_work leaves out the identities on the stream's tracked list.
+Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &src) {
+  Launch L;
+  L.n_buf = n_buf;
+  L.n_cap = n_cap;
+  L.src = src;
+  L.params = c->params_ws;
+  L.fset = c->fset_ws;
+  L.round_cells = std::min(c->max_work, c->percell_cap);
+  L.single_stream = c->st_open;
+  if (c->st_open) { L.tracked = c->st_dtracked; L.n_tracked = c->st_dntracked; }
+  return L;
+}
+
 // complex<double> host buffer -> device (cap64, slot 0) and the choice of the correlation kernel: a buffer whose every
 // component is exactly (u8 - 127) / 128 -- any dongle capture -- takes the int8 kernel, anything else the fp32 one.
-// Returns the geometry to correlate with; c->use_i8 is set accordingly.
+// *out: the launch to correlate with (geometry, kernel, source).
 int upload_host_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double *f_search_set, int n_f, int ds, double fc_req,
-                       double fc_prog, double fs_prog, bool debug, XcGeom *geo_out) {
+                       double fc_prog, double fs_prog, bool debug, Launch *out) {
   const XcGeom geo32 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, kMaxTapsF32);
   const XcGeom geo8 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, kMaxTapsI8);
   int rc;
@@ -244,16 +242,69 @@ int upload_host_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const d
   if (can_i8 && (rc = ensure_i8(c))) return rc;
   c->h_params = SlotParams{fc_req, fc_prog, fs_prog};
   HIPCHK(c, hipMemcpyAsync(c->cap64, capbuf, sizeof(double2) * n_cap, hipMemcpyHostToDevice, c->stream));
-  c->cap64_valid = true;
-  HIPCHK(c, hipMemcpyAsync(c->fset, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->params, &c->h_params, sizeof(SlotParams), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->fset_ws, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->params_ws, &c->h_params, sizeof(SlotParams), hipMemcpyHostToDevice, c->stream));
   bool exact = false;
-  if (can_i8) { if ((rc = lcs_launch_ingest_c128(c, n_cap, &exact))) return rc; }
-  else if ((rc = lcs_launch_ingest(c, nullptr, 2, 1, n_cap))) return rc;
-  c->use_i8 = exact;
-  c->use_f16 = false;
-  *geo_out = exact ? geo8 : geo32;
+  CapSrc src;
+  if (can_i8) { if ((rc = lcs_launch_ingest_c128(c, n_cap, &exact, &src))) return rc; }
+  else if ((rc = lcs_launch_ingest(c, nullptr, LCS_FMT_C128, 1, n_cap, &src))) return rc;
+  *out = make_launch(c, 1, n_cap, src);
+  out->geo = exact ? geo8 : geo32;
+  out->xc = exact ? XcKernel::i8 : XcKernel::fp32;
   return LCS_OK;
+}
+
+// The workspace of the stage entry points that take no capture buffer (a fresh context: the kernels read the slot's parameter record).
+int ensure_stage_ws(lcs_ctx *c, int n_f = 1) { return ensure_ws(c, 1, std::max<uint32_t>(c->cap_n_cap, 153600), n_f, false); }
+
+// The per-peak chain of a launch: sss_detect + pss_sss_foe on every peak (with the first round), then per round of L.round_cells
+// cells the work list, the grids, the frequency / timing correction and the MIB.  Rounds [r0, r1).
+int launch_per_peak(lcs_ctx *c, const Launch &L, int r0, int r1) {
+  int rc;
+  if (r0 == 0 && (rc = lcs_launch_sss_foe(c, L, 3.0 /* THRESH2_N_SIGMA, ref src/CellSearch.cpp:528 */, nullptr))) return rc;
+  for (int r = r0; r < r1; ++r)
+    if ((rc = lcs_launch_gather_work(c, L, r * L.round_cells)) || (rc = lcs_launch_tfg(c, L, true)) || (rc = lcs_launch_tfoec(c, L, false)) ||
+        (rc = lcs_launch_mib(c, L, true)))
+      return rc;
+  return LCS_OK;
+}
+
+// The peak table of slot 0, read back (one synchronisation): *np entries, of which tmp holds the first LCS_MAXP.
+int read_peak_table(lcs_ctx *c, std::vector<lcs_cell> &tmp, int *np) {
+  tmp.resize(LCS_MAXP);
+  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->peaks, sizeof(lcs_cell) * LCS_MAXP, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(np, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+// ... and handed out after the fused chain: `peaks` gets the peak_search view of every record (PSS fields only), `cells` the
+// decoded ones.  With `order` (lcs_foe_finish) a peak won by another rank's hypothesis -- the fused peak search marks it in
+// `reserved` -- has no `ind` here and is nobody's cell on this rank; order[k] is the peak index of cells[k].
+int read_cells_and_peaks(lcs_ctx *c, lcs_cell *cells, int32_t *order, int max_cells, int *n_cells, lcs_cell *peaks, int max_peaks, int *n_peaks) {
+  std::vector<lcs_cell> tmp;
+  int np = 0, rc;
+  if ((rc = read_peak_table(c, tmp, &np))) return rc;
+  if (np > LCS_MAXP) { np = LCS_MAXP; rc = LCS_ERR_OVERFLOW; }
+  int n = 0;
+  for (int i = 0; i < np; ++i) {
+    const bool mine = !order || tmp[i].reserved == 0;
+    if (peaks && i < max_peaks) {
+      lcs_cell pk;
+      lcs_cell_init(&pk);
+      pk.fc_requested = tmp[i].fc_requested; pk.fc_programmed = tmp[i].fc_programmed; pk.pss_pow = tmp[i].pss_pow;
+      pk.ind = mine ? tmp[i].ind : -1; pk.freq = tmp[i].freq; pk.n_id_2 = tmp[i].n_id_2;
+      if (order) pk.reserved = tmp[i].reserved;
+      peaks[i] = pk;
+    }
+    if (!mine || tmp[i].n_id_1 == -1 || tmp[i].n_rb_dl == -1) continue;
+    if (n < max_cells) { cells[n] = tmp[i]; if (order) order[n] = i; } else rc = LCS_ERR_OVERFLOW;
+    ++n;
+  }
+  if (n_peaks) *n_peaks = np;
+  *n_cells = n;
+  if (rc) c->err = "more results than the output arrays hold";
+  return rc;
 }
 
 int check_common(lcs_ctx *c, uint32_t n_cap, int n_f) {
@@ -396,10 +447,10 @@ int lcs_xcorr_pss(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double
   if (ds_comb_arm > 8) { c->err = "ds_comb_arm > 8 is not supported (the reference uses 2)"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const bool debug = incoh != nullptr;
-  XcGeom geo;
-  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set, n_f, ds_comb_arm, fc_req, fc_prog, fs_prog, debug, &geo))) return rc;
-  if ((rc = lcs_launch_xcorr(c, 1, geo, incoh != nullptr, false))) return rc;
-  if ((rc = lcs_launch_single_layout(c, geo, 0, c->sref, 1))) return rc;
+  Launch L;
+  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set, n_f, ds_comb_arm, fc_req, fc_prog, fs_prog, debug, &L))) return rc;
+  if ((rc = lcs_launch_xcorr(c, L, incoh != nullptr, false))) return rc;
+  if ((rc = lcs_launch_single_layout(c, L, 0, c->sref, 1))) return rc;
   const size_t NE = 3 * LCS_N_IDX;
   HIPCHK(c, hipMemcpyAsync(pow_, c->pow_, sizeof(double) * NE, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(frq, c->frq, sizeof(int) * NE, hipMemcpyDeviceToHost, c->stream));
@@ -411,11 +462,11 @@ int lcs_xcorr_pss(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double
   if (xc) {
     const size_t n = 3 * (size_t)(n_cap - 136) * n_f;
     if ((rc = c->xc.reserve(c, n))) return rc;
-    if ((rc = lcs_launch_xc_debug(c, geo))) return rc;
+    if ((rc = lcs_launch_xc_debug(c, L))) return rc;
     HIPCHK(c, hipMemcpyAsync(xc, c->xc, sizeof(float2) * n, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (n_comb_xc) *n_comb_xc = (uint16_t)geo.n_comb;
+  if (n_comb_xc) *n_comb_xc = (uint16_t)L.geo.n_comb;
   if (n_comb_sp) *n_comb_sp = (uint16_t)ncsp;
   return LCS_OK;
 }
@@ -429,23 +480,22 @@ int lcs_peak_search(lcs_ctx *c, const double *pow_, const int32_t *frq, const do
   if (!pow_ || !frq || !Z_th1 || !f_search_set || !single || !n_cells || (max_cells > 0 && !cells)) { c->err = "null argument"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_ws(c, 1, std::max<uint32_t>(c->cap_n_cap, 153600), n_f, false))) return rc;
+  if ((rc = ensure_stage_ws(c, n_f))) return rc;
   const size_t NE = 3 * LCS_N_IDX;
   SlotParams p{fc_req, fc_prog, 0.0};
   HIPCHK(c, hipMemcpyAsync(c->pow_, pow_, sizeof(double) * NE, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->frq, frq, sizeof(int) * NE, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->zth, Z_th1, sizeof(double) * LCS_N_IDX, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->fset, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->fset_ws, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->sref, single, sizeof(float) * NE * n_f, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->params, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
-  XcGeom geo = make_geo(153600, n_f, ds_comb_arm);
-  if ((rc = lcs_launch_single_layout(c, geo, 0, c->sref, 0))) return rc;
-  if ((rc = lcs_launch_peak_search(c, 1, geo, std::pow(10.0, -12.0 / 10.0), false))) return rc;
-  std::vector<lcs_cell> tmp(LCS_MAXP);
+  HIPCHK(c, hipMemcpyAsync(c->params_ws, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
+  Launch L = make_launch(c, 1, 153600, CapSrc{});
+  L.geo = make_geo(153600, n_f, ds_comb_arm);
+  if ((rc = lcs_launch_single_layout(c, L, 0, c->sref, 0))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), false))) return rc;
+  std::vector<lcs_cell> tmp;
   int n = 0;
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->peaks, sizeof(lcs_cell) * LCS_MAXP, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&n, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = read_peak_table(c, tmp, &n))) return rc;
   *n_cells = n;
   const int lim = std::min(std::min(n, max_cells), (int)LCS_MAXP);
   for (int i = 0; i < lim; ++i) cells[i] = tmp[i];
@@ -454,14 +504,6 @@ int lcs_peak_search(lcs_ctx *c, const double *pow_, const int32_t *frq, const do
 }
 
 // ------------------------------------------------------------------- batched chain
-static int percell_round(lcs_ctx *c, int n_buf, uint32_t n_cap, int r) {
-  int rc;
-  if ((rc = lcs_launch_gather_work(c, n_buf, r * c->round_cells, c->round_cells))) return rc;
-  if ((rc = lcs_launch_tfg(c, n_cap, true))) return rc;
-  if ((rc = lcs_launch_tfoec(c, false, 2))) return rc;
-  return lcs_launch_mib(c, true);
-}
-
 int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const double *f_search_set,
                       uint16_t n_f, const double *fc_requested, const double *fc_programmed, double fs_programmed,
                       int stage_mask) {
@@ -483,9 +525,8 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   double *hf = (double *)(hp + n_buf);
   for (int i = 0; i < n_buf; ++i) hp[i] = SlotParams{fc_requested[i], fc_programmed[i], fs_programmed};
   std::memcpy(hf, f_search_set, sizeof(double) * n_f);
-  HIPCHK(c, hipMemcpyAsync(c->params, hp, sizeof(SlotParams) * n_buf, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->fset, hf, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
-  c->cap64_valid = false;
+  HIPCHK(c, hipMemcpyAsync(c->params_ws, hp, sizeof(SlotParams) * n_buf, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->fset_ws, hf, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   // lcs_set_float_batch_probe: a complex<float> batch that is dongle data becomes the u8 batch it came from (one pass + one small
   // read-back: the host waits for it -- while the other contexts' kernels keep the GPU busy -- before it knows which kernels to queue)
   c->last_c64_routed = false;
@@ -505,16 +546,22 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
     }
   }
   const int fmt_in = c->last_c64_routed ? LCS_FMT_C64 : fmt;      // what the caller handed over: the hint bookkeeping goes by it
-  c->use_i8 = fmt == LCS_FMT_IQ_U8;
   // complex<float> sources: fp16 hi / lo operands, three products (pss_xcorr_f16.hip) -- unless its buffers would have to be
   // allocated under an open stream's graph: such a context keeps the fp32 kernel for them (160 taps per group fit it too)
-  c->use_f16 = fmt == LCS_FMT_C64 && (c->f16.ready || !c->st_open);
+  const bool use_f16 = fmt == LCS_FMT_C64 && (c->f16.ready || !c->st_open);
   if (fmt == LCS_FMT_IQ_U8 && (rc = ensure_i8(c))) return rc;      // int8 copies: every u8 source (the fp64 stages read them)
-  if (c->use_f16 && (rc = ensure_f16(c))) return rc;
-  if (c->use_f16) { if ((rc = lcs_launch_ingest_f16(c, d_capbufs, n_buf, n_cap))) return rc; }
-  else if ((rc = lcs_launch_ingest(c, d_capbufs, fmt, n_buf, n_cap))) return rc;
-  if ((rc = lcs_launch_xcorr(c, n_buf, geo, false, true))) return rc;
-  if ((rc = lcs_launch_peak_search(c, n_buf, geo, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if (use_f16 && (rc = ensure_f16(c))) return rc;
+  CapSrc src;
+  if (use_f16) { if ((rc = lcs_launch_ingest_f16(c, d_capbufs, n_buf, n_cap, &src))) return rc; }
+  else if ((rc = lcs_launch_ingest(c, d_capbufs, fmt, n_buf, n_cap, &src))) return rc;
+  Launch L = make_launch(c, n_buf, n_cap, src);
+  L.geo = geo;
+  L.xc = fmt == LCS_FMT_IQ_U8 ? XcKernel::i8 : use_f16 ? XcKernel::f16 : XcKernel::fp32;
+  L.needed_rows_only = true;
+  L.tfoec_parts = 2;
+  if ((rc = lcs_launch_xcorr(c, L, false, true))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  int rounds = 0;
   if (stage_mask & 2) {
     // The per-cell stages hold max_work cells at a time, in rounds.  Round 4: the batch before is the predictor for how many
     // rounds to enqueue and how wide the per-cell grids are.  A busy band carries 4-5 cells per buffer past SSS: with the
@@ -530,21 +577,14 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
     if (!c->max_work_pinned && !c->st_open && hint > c->max_work && c->max_work < LCS_MAX_WORK)
       c->max_work = std::min<int>(LCS_MAX_WORK, 2 * c->max_work);
     if ((rc = ensure_percell(c))) return rc;
-    if ((rc = lcs_launch_sss_foe(c, n_buf, n_cap, 3.0 /* THRESH2_N_SIGMA, ref src/CellSearch.cpp:528 */, nullptr))) return rc;
-    c->needed_rows_only = true;
-    c->round_cells = std::min(c->max_work, c->percell_cap);      // fixed for this batch
+    L.round_cells = std::min(c->max_work, c->percell_cap);      // fixed for this batch
+    L.grid_items = std::min(L.round_cells, std::max(64, std::max(n_buf / 2, hint + hint / 8)));
     const int expect = std::max(n_buf, hint + hint / 4);
-    c->grid_items = std::min(c->round_cells, std::max(64, std::max(n_buf / 2, hint + hint / 8)));
-    const int rounds = std::min(8, (expect + c->round_cells - 1) / c->round_cells);
-    for (int r = 0; r < rounds; ++r)
-      if ((rc = percell_round(c, n_buf, n_cap, r))) return rc;
-    c->last_cell_rounds = rounds;
+    rounds = std::min(8, (expect + L.round_cells - 1) / L.round_cells);
+    if ((rc = launch_per_peak(c, L, 0, rounds))) return rc;
   }
-  if ((rc = lcs_launch_pack_results(c, n_buf, (stage_mask & 2) != 0))) return rc;
-  c->last_n_buf = n_buf;
-  c->last_stage_mask = stage_mask;
-  c->last_fmt = fmt_in;
-  c->last_geo = geo;
+  if ((rc = lcs_launch_pack_results(c, L, (stage_mask & 2) != 0))) return rc;
+  c->batch = BatchRecord{L, stage_mask, fmt_in, rounds};
   return LCS_OK;
 }
 
@@ -553,10 +593,12 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
 // context, one synchronisation; a second copy only when the batch returned more.  No allocation, no pageable staging
 // (rounds 1-4 copied n_buf x 64 records, 786 KB per 128-buffer batch, into a vector built inside the call).
 int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n_cells) {
-  if (!c || !n_cells || c->last_n_buf <= 0 || max_cells_per_buf < 0 || (!cells && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
+  if (!c || !n_cells || c->batch.l.n_buf <= 0 || max_cells_per_buf < 0 || (!cells && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  const int nb = c->last_n_buf;
-  const bool full = (c->last_stage_mask & 2) != 0;
+  BatchRecord &batch = c->batch;
+  const Launch &L = batch.l;
+  const int nb = L.n_buf;
+  const bool full = (batch.stage_mask & 2) != 0;
   const size_t rec_off = lcs_pack_rec_offset(nb);
   const int *hdr = reinterpret_cast<const int *>(c->h_res.get());
   const int *cnt = hdr + 8;
@@ -573,14 +615,14 @@ int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n
     t_sync_done = std::chrono::steady_clock::now();
     host_us += std::chrono::duration<double, std::micro>(t_b - t_a).count();
     const int work_total = hdr[5];
-    if (full && pass == 0) { c->work_hint = work_total; c->hint_n_buf = nb; c->hint_fmt = c->last_fmt; c->hint_stage = c->last_stage_mask; }
-    if (full && pass == 0 && work_total > c->last_cell_rounds * c->round_cells) {
-      // more cells passed SSS than the enqueued rounds decode: run the remaining rounds now (rare: the first dense batch)
-      const int rounds = (work_total + c->round_cells - 1) / c->round_cells;
-      for (int r = c->last_cell_rounds; r < rounds; ++r)
-        if ((rc = percell_round(c, nb, c->last_geo.n_cap, r))) return rc;
-      c->last_cell_rounds = rounds;
-      if ((rc = lcs_launch_pack_results(c, nb, true))) return rc;
+    if (full && pass == 0) { c->work_hint = work_total; c->hint_n_buf = nb; c->hint_fmt = batch.fmt; c->hint_stage = batch.stage_mask; }
+    if (full && pass == 0 && work_total > batch.cell_rounds * L.round_cells) {
+      // more cells passed SSS than the enqueued rounds decode: run the remaining rounds now, as the batch was enqueued (rare: the
+      // first dense batch)
+      const int rounds = (work_total + L.round_cells - 1) / L.round_cells;
+      if ((rc = launch_per_peak(c, L, batch.cell_rounds, rounds))) return rc;
+      batch.cell_rounds = rounds;
+      if ((rc = lcs_launch_pack_results(c, L, true))) return rc;
       continue;
     }
     const int total = hdr[0];
@@ -602,14 +644,14 @@ int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n
     at += (size_t)n;
     n_cells[b] = n;
   }
-  c->src32 = nullptr;      // complex<float> batches were read in place: the caller's buffers are no longer referenced
+  if (batch.l.src.c32) batch.l.src.c32 = c->cap32;      // complex<float> batches were read in place: the caller's buffers are no longer referenced
   c->last_collect_host_us = host_us + std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_sync_done).count();
   if (rc) c->err = "more results than the output array holds";
   return rc;
 }
 
 int lcs_last_batch_stats(lcs_ctx *c, int stats[8]) {
-  if (!c || !stats || !c->h_res || c->last_n_buf <= 0) return LCS_ERR_BAD_ARG;
+  if (!c || !stats || !c->h_res || c->batch.l.n_buf <= 0) return LCS_ERR_BAD_ARG;
   std::memcpy(stats, c->h_res, 8 * sizeof(int));      // the header lcs_batch_collect brought over (k_pack_results)
   return LCS_OK;
 }
@@ -729,13 +771,13 @@ int lcs_search_batch_host(lcs_ctx *c, const void *h_capbufs, int fmt, int n_buf,
 
 // Debug readback: the xcorr_pss outputs of buffer `buf` of the last batch, in the reference's layouts.
 int lcs_batch_readback(lcs_ctx *c, int buf, float *single, double *pow_, int32_t *frq, double *sp_incoherent, double *z_th1) {
-  if (!c || c->last_n_buf <= 0 || buf < 0 || buf >= c->last_n_buf) { if (c) c->err = "no such buffer in the last batch"; return LCS_ERR_BAD_ARG; }
+  if (!c || buf < 0 || buf >= c->batch.l.n_buf) { if (c) c->err = "no such buffer in the last batch"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
-  const XcGeom &geo = c->last_geo;
+  const XcGeom &geo = c->batch.l.geo;
   const size_t NE = 3 * LCS_N_IDX;
   int rc;
   if (single) {
-    if ((rc = lcs_launch_single_layout(c, geo, buf, c->sref, 1))) return rc;
+    if ((rc = lcs_launch_single_layout(c, c->batch.l, buf, c->sref, 1))) return rc;
     HIPCHK(c, hipMemcpyAsync(single, c->sref, sizeof(float) * NE * geo.n_f, hipMemcpyDeviceToHost, c->stream));
   }
   if (pow_) HIPCHK(c, hipMemcpyAsync(pow_, c->pow_ + (size_t)buf * NE, sizeof(double) * NE, hipMemcpyDeviceToHost, c->stream));
@@ -748,15 +790,15 @@ int lcs_batch_readback(lcs_ctx *c, int buf, float *single, double *pow_, int32_t
 
 // ---------------------------------------------------------- single-cell stage entry points
 namespace {
-int upload_cap_and_params(lcs_ctx *c, const double *capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog) {
+int upload_cap_and_params(lcs_ctx *c, const double *capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog, Launch *out) {
   int rc;
   if (!capbuf || n_cap < 128) { c->err = "bad capture buffer"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = ensure_ws(c, 1, n_cap, std::max(1, c->cap_n_f), false))) return rc;
   c->h_params = SlotParams{fc_req, fc_prog, fs_prog};      // outlives the asynchronous copy (the callers synchronise later)
   HIPCHK(c, hipMemcpyAsync(c->cap64, capbuf, sizeof(double2) * n_cap, hipMemcpyHostToDevice, c->stream));
-  c->cap64_valid = true;
-  HIPCHK(c, hipMemcpyAsync(c->params, &c->h_params, sizeof(SlotParams), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->params_ws, &c->h_params, sizeof(SlotParams), hipMemcpyHostToDevice, c->stream));
+  *out = make_launch(c, 1, n_cap, CapSrc{nullptr, c->cap64, nullptr, n_cap});      // the stages read the fp64 copy itself
   return LCS_OK;
 }
 int put_single_work_item(lcs_ctx *c, const lcs_cell *cell, int n_ofdm) {
@@ -783,13 +825,14 @@ int lcs_sss_detect(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint3
   if (!c || !cell || !cell_out) return LCS_ERR_BAD_ARG;
   if (cell->n_id_2 < 0 || cell->n_id_2 > 2) { c->err = "cell.n_id_2 must be 0..2"; return LCS_ERR_BAD_ARG; }
   int rc;
-  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog))) return rc;
+  Launch L;
+  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog, &L))) return rc;
   if ((rc = ensure_percell(c))) return rc;
   const int one = 1;
   HIPCHK(c, hipMemcpyAsync(c->peaks, cell, sizeof(lcs_cell), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->npeaks, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, sizeof(double) * 2048, c->stream));
-  if ((rc = lcs_launch_sss_only(c, n_cap, thresh2_n_sigma, c->d_dbg))) return rc;
+  if ((rc = lcs_launch_sss_only(c, L, thresh2_n_sigma, c->d_dbg))) return rc;
   std::vector<double> dbg(1292);
   HIPCHK(c, hipMemcpyAsync(cell_out, c->peaks, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(dbg.data(), c->d_dbg, sizeof(double) * dbg.size(), hipMemcpyDeviceToHost, c->stream));
@@ -813,11 +856,12 @@ int lcs_pss_sss_foe(lcs_ctx *c, const lcs_cell *cell_in, const double *capbuf, u
     return LCS_ERR_BAD_ARG;
   }
   int rc;
-  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog))) return rc;
+  Launch L;
+  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog, &L))) return rc;
   const int one = 1;
   HIPCHK(c, hipMemcpyAsync(c->peaks, cell_in, sizeof(lcs_cell), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->npeaks, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_foe_only(c, n_cap))) return rc;
+  if ((rc = lcs_launch_foe_only(c, L))) return rc;
   HIPCHK(c, hipMemcpyAsync(cell_out, c->peaks, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
@@ -829,10 +873,10 @@ int lcs_extract_tfg(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint
   const int no = n_ofdm_for(cell);
   if (no < 0) { c->err = "extract_tfg needs a known cp_type"; return LCS_ERR_BAD_ARG; }   // ref :883 throws
   int rc;
-  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog))) return rc;
+  Launch L;
+  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog, &L))) return rc;
   if ((rc = put_single_work_item(c, cell, no))) return rc;
-  c->needed_rows_only = false;
-  if ((rc = lcs_launch_tfg(c, n_cap, false))) return rc;
+  if ((rc = lcs_launch_tfg(c, L, false))) return rc;
   double oob = 0;
   HIPCHK(c, hipMemcpyAsync(tfg, c->tfg, sizeof(double2) * no * LCS_TFG_NSC, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(tfg_timestamp, c->tfg_ts, sizeof(double) * no, hipMemcpyDeviceToHost, c->stream));
@@ -852,15 +896,15 @@ int lcs_tfoec(lcs_ctx *c, const lcs_cell *cell, const double *tfg, const double 
   }
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_ws(c, 1, std::max<uint32_t>(c->cap_n_cap, 153600), std::max(1, c->cap_n_f), false))) return rc;
+  if ((rc = ensure_stage_ws(c))) return rc;
   SlotParams p{fc_req, fc_prog, 0.0};
-  HIPCHK(c, hipMemcpyAsync(c->params, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->params_ws, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
   if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->tfg, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->tfg_ts, tfg_timestamp, sizeof(double) * n_ofdm, hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_rs_build(c))) return rc;
-  c->needed_rows_only = false;
-  if ((rc = lcs_launch_tfoec(c, true))) return rc;
+  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  if ((rc = lcs_launch_tfoec(c, L, true))) return rc;
   HIPCHK(c, hipMemcpyAsync(tfg_comp, c->tfg_comp, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(tfg_comp_timestamp, c->tfg_ts_comp, sizeof(double) * n_ofdm, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(cell_out, c->cells_out, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
@@ -877,12 +921,13 @@ int lcs_decode_mib(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
   }
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_ws(c, 1, std::max<uint32_t>(c->cap_n_cap, 153600), std::max(1, c->cap_n_f), false))) return rc;      // (a fresh context: the kernels read the slot's parameter record)
+  if ((rc = ensure_stage_ws(c))) return rc;
   if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->tfg_comp, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_rs_build(c))) return rc;
-  c->needed_rows_only = true;      // decode_mib reads the channel estimate on PBCH rows only
-  if ((rc = lcs_launch_mib(c, false))) return rc;
+  Launch L = make_launch(c, 1, 0, CapSrc{});
+  L.needed_rows_only = true;      // decode_mib reads the channel estimate on PBCH rows only
+  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  if ((rc = lcs_launch_mib(c, L, false))) return rc;
   HIPCHK(c, hipMemcpyAsync(cell_out, c->cells_out, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
@@ -900,12 +945,12 @@ int lcs_chan_est(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm
   }
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_ws(c, 1, std::max<uint32_t>(c->cap_n_cap, 153600), std::max(1, c->cap_n_f), false))) return rc;      // (a fresh context: the kernels read the slot's parameter record)
+  if ((rc = ensure_stage_ws(c))) return rc;
   if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->tfg_comp, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_rs_build(c))) return rc;
-  c->needed_rows_only = false;
-  if ((rc = lcs_launch_chan_est(c))) return rc;
+  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  if ((rc = lcs_launch_chan_est(c, L))) return rc;
   int first, per_port, n_rs_at;
   lcs_chan_est_np_layout(&first, &per_port, &n_rs_at);
   std::vector<double> sc(LCS_CELL_SCRATCH);
@@ -926,44 +971,15 @@ int lcs_search_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const do
   if (rc) return rc;
   if (!capbuf || !f_search_set || !n_cells || (max_cells > 0 && !cells)) { c->err = "null argument"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
-  XcGeom geo;
-  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set, n_f, 2, fc_req, fc_prog, fs_prog, false, &geo))) return rc;
-  if ((rc = ensure_percell(c))) return rc;
-  c->repair_peaks_only = true;      // no array leaves this call: the peak list is what has to be exact
-  rc = lcs_launch_xcorr(c, 1, geo, false, false);
-  c->repair_peaks_only = false;
-  if (rc) return rc;
-  if ((rc = lcs_launch_peak_search(c, 1, geo, std::pow(10.0, -12.0 / 10.0), true))) return rc;
-  if ((rc = lcs_launch_sss_foe(c, 1, n_cap, 3.0, nullptr))) return rc;
-  c->needed_rows_only = true;
-  if ((rc = lcs_launch_gather_work(c, 1, 0))) return rc;
-  if ((rc = lcs_launch_tfg(c, n_cap, true))) return rc;
-  if ((rc = lcs_launch_tfoec(c, false))) return rc;
-  if ((rc = lcs_launch_mib(c, true))) return rc;
-  std::vector<lcs_cell> tmp(LCS_MAXP);
-  int np = 0;
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->peaks, sizeof(lcs_cell) * LCS_MAXP, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&np, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = LCS_OK;
-  if (np > LCS_MAXP) { np = LCS_MAXP; rc = LCS_ERR_OVERFLOW; }
-  int n = 0;
-  for (int i = 0; i < np; ++i) {
-    if (peaks && i < max_peaks) {   // the peak_search view of the record (PSS fields only)
-      lcs_cell pk;
-      lcs_cell_init(&pk);
-      pk.fc_requested = tmp[i].fc_requested; pk.fc_programmed = tmp[i].fc_programmed; pk.pss_pow = tmp[i].pss_pow;
-      pk.ind = tmp[i].ind; pk.freq = tmp[i].freq; pk.n_id_2 = tmp[i].n_id_2;
-      peaks[i] = pk;
-    }
-    if (tmp[i].n_id_1 == -1 || tmp[i].n_rb_dl == -1) continue;
-    if (n < max_cells) cells[n] = tmp[i]; else rc = LCS_ERR_OVERFLOW;
-    ++n;
-  }
-  if (n_peaks) *n_peaks = np;
-  *n_cells = n;
-  if (rc) c->err = "more results than the output arrays hold";
-  return rc;
+  if ((rc = ensure_percell(c))) return rc;      // before the Launch is built: it takes the cells per round from the per-cell buffers' capacity
+  Launch L;
+  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set, n_f, 2, fc_req, fc_prog, fs_prog, false, &L))) return rc;
+  L.repair = FrqRepair::peaks_only;      // no array leaves this call: the peak list is what has to be exact
+  L.needed_rows_only = true;
+  if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
+  return read_cells_and_peaks(c, cells, nullptr, max_cells, n_cells, peaks, max_peaks, n_peaks);
 }
 
 // ------------------------------------------------------------------- one buffer, hypotheses split over GPUs
@@ -986,21 +1002,19 @@ int lcs_foe_partial(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const doub
   // a rank without hypotheses still takes part: it correlates one (the first) so that its buffer, tables and power
   // estimate exist, and contributes words that never win
   const int cnt = std::max(1, f_count), first = f_count ? f_first : 0;
-  XcGeom geo;
-  if ((rc = ensure_ws(c, 1, n_cap, n_f, false))) return rc;      // lcs_foe_finish puts the WHOLE grid into fset (this rank correlates its share only)
-  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set + first, cnt, 2, fc_req, fc_prog, fs_prog, false, &geo))) return rc;
-  if ((rc = ensure_percell(c))) return rc;
+  if ((rc = ensure_ws(c, 1, n_cap, n_f, false))) return rc;      // lcs_foe_finish puts the WHOLE grid into fset_ws (this rank correlates its share only)
+  if ((rc = ensure_percell(c))) return rc;      // before the Launch is built, as in lcs_search_capbuf; lcs_foe_finish keeps this call's cells per round
+  Launch L;
+  if ((rc = upload_host_capbuf(c, capbuf, n_cap, f_search_set + first, cnt, 2, fc_req, fc_prog, fs_prog, false, &L))) return rc;
   // no tie repair here: a near-tie may span two ranks' shares -- lcs_foe_contend settles them after the all-reduce, identically
   // for every split; the collapse keeps the runner-up values for it
-  c->skip_frq_repair = true;
-  rc = lcs_launch_xcorr(c, 1, geo, false, false);
-  c->skip_frq_repair = false;
-  if (rc) return rc;
-  geo.foi0 = f_count ? f_first : -1;            // -1: owns nothing
-  if ((rc = lcs_launch_foe_pack(c, geo, static_cast<long long *>(d_words), d_meta))) return rc;
+  L.repair = FrqRepair::none_keep_2nd;
+  L.needed_rows_only = true;
+  if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
+  L.geo.foi0 = f_count ? f_first : -1;            // -1: owns nothing
+  if ((rc = lcs_launch_foe_pack(c, L, static_cast<long long *>(d_words), d_meta))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));    // the caller's collective runs on another stream
-  c->foe_geo = geo;
-  c->foe_n_cap = n_cap;
+  c->foe = L;
   c->foe_ready = true;
   return LCS_OK;
 }
@@ -1019,9 +1033,9 @@ int lcs_foe_contend(lcs_ctx *c, const double *f_search_set, uint16_t n_f, const 
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   if (n_f > c->fset_g.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if ((rc = c->fset_g.reserve(c, (size_t)n_f))) return rc;      // the whole grid (fset holds this rank's share)
+  if ((rc = c->fset_g.reserve(c, (size_t)n_f))) return rc;      // the whole grid (fset_ws holds this rank's share)
   HIPCHK(c, hipMemcpyAsync(c->fset_g, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_foe_contend(c, c->foe_geo, c->fset_g, static_cast<const long long *>(d_words), static_cast<long long *>(d_words2)))) return rc;
+  if ((rc = lcs_launch_foe_contend(c, c->foe, c->fset_g, static_cast<const long long *>(d_words), static_cast<long long *>(d_words2)))) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));      // the caller's collective runs on another stream (and f_search_set may go away)
   return LCS_OK;
 }
@@ -1042,44 +1056,14 @@ int lcs_foe_finish(lcs_ctx *c, const void *d_words, const double *d_meta, const 
   if (!d_words || !d_meta || !f_search_set || !n_cells || (max_cells > 0 && (!cells || !order)) || n_f < 1 || n_f > LCS_NF_LIMIT) { c->err = "bad argument"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   c->foe_ready = false;
-  const XcGeom geo = c->foe_geo;
-  const uint32_t n_cap = c->foe_n_cap;
+  const Launch &L = c->foe;
   int rc;
   // peak_search names the winning hypothesis by its GLOBAL index: the whole grid now, not this rank's share
-  HIPCHK(c, hipMemcpyAsync(c->fset, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
-  if ((rc = lcs_launch_foe_unpack(c, geo, static_cast<const long long *>(d_words), d_meta))) return rc;
-  if ((rc = lcs_launch_peak_search(c, 1, geo, std::pow(10.0, -12.0 / 10.0), true))) return rc;
-  if ((rc = lcs_launch_sss_foe(c, 1, n_cap, 3.0, nullptr))) return rc;
-  c->needed_rows_only = true;
-  if ((rc = lcs_launch_gather_work(c, 1, 0))) return rc;
-  if ((rc = lcs_launch_tfg(c, n_cap, true))) return rc;
-  if ((rc = lcs_launch_tfoec(c, false))) return rc;
-  if ((rc = lcs_launch_mib(c, true))) return rc;
-  std::vector<lcs_cell> tmp(LCS_MAXP);
-  int np = 0;
-  HIPCHK(c, hipMemcpyAsync(tmp.data(), c->peaks, sizeof(lcs_cell) * LCS_MAXP, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&np, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = LCS_OK;
-  if (np > LCS_MAXP) { np = LCS_MAXP; rc = LCS_ERR_OVERFLOW; }
-  int n = 0;
-  for (int i = 0; i < np; ++i) {
-    const bool mine = tmp[i].reserved == 0;                   // the fused peak search marks peaks won by another rank's hypothesis
-    if (peaks && i < max_peaks) {
-      lcs_cell pk;
-      lcs_cell_init(&pk);
-      pk.fc_requested = tmp[i].fc_requested; pk.fc_programmed = tmp[i].fc_programmed; pk.pss_pow = tmp[i].pss_pow;
-      pk.ind = mine ? tmp[i].ind : -1; pk.freq = tmp[i].freq; pk.n_id_2 = tmp[i].n_id_2; pk.reserved = tmp[i].reserved;
-      peaks[i] = pk;
-    }
-    if (!mine || tmp[i].n_id_1 == -1 || tmp[i].n_rb_dl == -1) continue;
-    if (n < max_cells) { cells[n] = tmp[i]; order[n] = i; } else rc = LCS_ERR_OVERFLOW;
-    ++n;
-  }
-  if (n_peaks) *n_peaks = np;
-  *n_cells = n;
-  if (rc) c->err = "more results than the output arrays hold";
-  return rc;
+  HIPCHK(c, hipMemcpyAsync(c->fset_ws, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
+  if ((rc = lcs_launch_foe_unpack(c, L, static_cast<const long long *>(d_words), d_meta))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
+  return read_cells_and_peaks(c, cells, order, max_cells, n_cells, peaks, max_peaks, n_peaks);
 }
 
 // ---------------------------------------------------------------------------- streaming mode
@@ -1090,38 +1074,26 @@ int lcs_foe_finish(lcs_ctx *c, const void *d_words, const double *d_meta, const 
 // pushes (samples, frequency offset, tracked identities) travels through fixed pinned host buffers
 // that the graph's copy nodes read at execution time.
 namespace {
-// the chain as slot k sees it: its own pinned input buffer and parameter / result block, the shared device workspace
-int stream_chain_launches(lcs_ctx *c, int k);
+// the chain as slot k sees it: its own pinned input buffer and parameter / result block, the shared device workspace.  Its kernels
+// take the slot parameters and the hypothesis from the stream's device mirror (one copy per push), not from the workspace arrays the
+// other entry points fill.
 int stream_chain(lcs_ctx *c, int k) {
-  // the chain's kernels take the slot parameters and the hypothesis from the stream's device mirror (one copy per push), not from
-  // the workspace arrays the other entry points fill: the context's pointers are swapped while the launches are issued / recorded
-  SlotParams *params = c->params;
-  double *fset = c->fset;
-  c->params = reinterpret_cast<SlotParams *>(c->st_dmirror + offsetof(StreamHost, p));      // (views: lcs_internal.h)
-  c->fset = reinterpret_cast<double *>(c->st_dmirror + offsetof(StreamHost, f));
-  const int rc = stream_chain_launches(c, k);
-  c->params = params;
-  c->fset = fset;
-  return rc;
-}
-int stream_chain_launches(lcs_ctx *c, int k) {
   StreamHost *h = c->st_host[k];
-  const XcGeom geo = make_geo(c->st_n_cap, 1, 2);
   int rc;
-  c->use_i8 = c->st_fmt == LCS_FMT_IQ_U8;      // one hypothesis: no window-start spread, the int8 kernel always fits
-  c->use_f16 = false;
   c->foe_ready = false;
   HIPCHK(c, hipMemcpyAsync(c->st_din, c->st_hin[k], c->st_in_bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->st_dmirror, h, LCS_STREAM_IN_BYTES, hipMemcpyHostToDevice, c->stream));      // parameters, tracked list, hypothesis: one copy
-  if ((rc = lcs_launch_ingest(c, c->st_din, c->st_fmt, 1, c->st_n_cap))) return rc;
-  if ((rc = lcs_launch_xcorr(c, 1, geo, false, false))) return rc;
-  if ((rc = lcs_launch_peak_search(c, 1, geo, std::pow(10.0, -12.0 / 10.0), true))) return rc;
-  if ((rc = lcs_launch_sss_foe(c, 1, c->st_n_cap, 3.0, nullptr))) return rc;
-  c->needed_rows_only = true;
-  if ((rc = lcs_launch_gather_work(c, 1, 0))) return rc;
-  if ((rc = lcs_launch_tfg(c, c->st_n_cap, true))) return rc;
-  if ((rc = lcs_launch_tfoec(c, false))) return rc;
-  if ((rc = lcs_launch_mib(c, true))) return rc;
+  CapSrc src;
+  if ((rc = lcs_launch_ingest(c, c->st_din, c->st_fmt, 1, c->st_n_cap, &src))) return rc;
+  Launch L = make_launch(c, 1, c->st_n_cap, src);
+  L.geo = make_geo(c->st_n_cap, 1, 2);
+  L.params = reinterpret_cast<const SlotParams *>(c->st_dmirror + offsetof(StreamHost, p));
+  L.fset = reinterpret_cast<const double *>(c->st_dmirror + offsetof(StreamHost, f));
+  L.xc = c->st_fmt == LCS_FMT_IQ_U8 ? XcKernel::i8 : XcKernel::fp32;      // one hypothesis: no window-start spread, the int8 kernel always fits
+  L.needed_rows_only = true;
+  if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
   HIPCHK(c, hipMemcpyAsync(h->res, c->peaks, sizeof(h->res), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&h->n_peaks, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(h->n_work, c->n_work, sizeof(h->n_work), hipMemcpyDeviceToHost, c->stream));
@@ -1145,9 +1117,12 @@ int lcs_stream_close(lcs_ctx *c) {
   c->st_din.reset();
   c->st_dmirror.reset();
   c->st_dtracked = nullptr; c->st_dntracked = nullptr;
+  // the saved launches of a batch or an lcs_foe_partial made while the stream was open borrowed its tracked list: what is left of
+  // them (late rounds of lcs_batch_collect, lcs_foe_finish) runs without a filter, as every launch on a context without a stream
+  c->batch.l.tracked = c->foe.tracked = nullptr;
+  c->batch.l.n_tracked = c->foe.n_tracked = nullptr;
   c->st_open = false;
   c->st_head = c->st_count = 0;
-  c->single_stream = false;
   return LCS_OK;
 }
 
@@ -1175,8 +1150,6 @@ int stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, double
     std::memset(c->st_host[k], 0, sizeof(StreamHost));
     c->st_host[k].get()->p = SlotParams{fc_requested, fc_programmed, fs_programmed};
   }
-  c->cap64_valid = false;
-  c->single_stream = true;
   c->st_open = true;
   c->st_head = c->st_count = 0;
   // one eager pass (lazy allocations, function attributes), then the same call sequence under capture, per slot

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <cstddef>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/lcs.h"
 #include "lcs_mem.h"
@@ -108,6 +109,13 @@ struct CapView {
   const double2 *c64;
   const uint16_t *c8;
 };
+// The kernels that read the capture buffers are templates over the kind of source (0: int8 pairs, 1: fp32, 2: fp64):
+// lcs_by_cap_kind(src, [&](auto kind) { launch k<decltype(kind)::value> }) picks the instantiation for a CapSrc.
+template <class F> inline void lcs_by_cap_kind(const CapSrc &s, F &&launch) {
+  if (s.c8) launch(std::integral_constant<int, 0>{});
+  else if (s.c32) launch(std::integral_constant<int, 1>{});
+  else launch(std::integral_constant<int, 2>{});
+}
 #ifdef __HIPCC__
 // Hand-over of LDS data between the lanes of ONE wave (the wave-local FFT stages): the wave barrier alone is IntrNoMem --
 // no memory fence -- so the ordering of the LDS accesses around it is pinned by a release / acquire fence pair at
@@ -141,10 +149,43 @@ struct WorkItem {
   int peak;      // index into peaks[slot]
 };
 
+// Everything a launcher needs to know about the call it serves, apart from the context's memory: built by the entry point
+// (lcs_api.hip: make_launch) and handed to every lcs_launch_* function.  No launcher reads a mode from lcs_ctx.
+enum class XcKernel { fp32, i8, f16 };      // k_xcorr_mfma_blk / k_xcorr_i8x3 (u8 sources) / k_xcorr_f16x3 (complex<float> batches)
+enum class FrqRepair {
+  all,            // every near-tie of the arg-max is recomputed in the reference's arithmetic (the arrays leave the call)
+  peaks_only,     // only the near-ties at or above their position's Z_th1: the peak list is what has to be exact (lcs_search_capbuf)
+  none_keep_2nd   // no repair, the collapse keeps the runner-up: a rank sees only its share of the hypotheses (lcs_foe_partial)
+};
+struct Launch {
+  int n_buf = 0;
+  uint32_t n_cap = 0;
+  XcGeom geo{};
+  const SlotParams *params = nullptr;   // per-slot parameter records and the hypotheses: the workspace's arrays (params_ws / fset_ws),
+  const double *fset = nullptr;         // or the device mirror of the streaming mode's pinned block
+  XcKernel xc = XcKernel::fp32;
+  CapSrc src{};                         // what the fp64 stages read: decided where the data is ingested (lcs_launch_ingest*)
+  FrqRepair repair = FrqRepair::all;
+  bool single_stream = false;           // everything on `stream`, no hand-over to stream_xc (a context with an open stream)
+  bool needed_rows_only = false;        // fused chains: compute only the grid rows later stages read (tfg_mib.hip)
+  int grid_items = 64;                  // workgroups per work-list axis of the per-cell kernels (they loop over the list)
+  int round_cells = 0;                  // cells per per-cell round (k_gather_work's limit)
+  int tfoec_parts = 4;                  // workgroups per cell for the timing estimate: 2 in batches
+  const int16_t *tracked = nullptr;     // identities k_gather_work leaves out (the streaming mode's tracked list), null: no filter
+  const int *n_tracked = nullptr;
+};
+// The last enqueued batch: lcs_batch_collect (its late per-cell rounds), lcs_batch_readback and lcs_last_batch_stats read it.
+struct BatchRecord {
+  Launch l;                             // l.n_buf == 0: no batch yet, or its workspace has been replaced since (ensure_ws)
+  int stage_mask = 0;
+  int fmt = 0;                          // the format the caller handed over
+  int cell_rounds = 0;                  // per-cell rounds launched so far (l.round_cells cells each)
+};
+
 // Pinned block shared with the captured graph of the streaming mode.
 // The first LCS_STREAM_IN_BYTES of it (parameters, tracked identities, the frequency hypothesis LAST) go to a device mirror of the same
 // layout in ONE copy per push (rounds 2-5: four copy nodes per replay); the captured chain's kernels read their parameters and
-// hypothesis from that mirror (stream_chain points the context's `params` / `fset` at it while the launches are recorded).
+// hypothesis from that mirror (stream_chain builds its Launch with `params` / `fset` pointing into it).
 struct StreamHost {
   SlotParams p;
   int n_tracked;
@@ -215,7 +256,11 @@ struct lcs_ctx_queues {
 };
 
 // Ownership.  Every block of device or page-locked memory of a context is a Buf member (lcs_mem.h) of this struct or of a struct
-// that is one, and nothing else frees it; a plain pointer member is a VIEW of memory owned elsewhere and says so.  lcs_destroy
+// that is one, and nothing else frees it; a plain pointer member is a VIEW of memory owned elsewhere and says so.  What a launch
+// depends on beyond memory travels in a Launch, not in fields of this struct; the two records kept here (`batch`, `foe`) are saved
+// copies of the Launch of a call whose work a later call continues, and a saved copy's pointers end with what they point into:
+// ensure_ws drops both records when it replaces the workspace, lcs_stream_close takes the stream's tracked list out of them,
+// lcs_batch_collect the caller's complex<float> buffers.  lcs_destroy
 // is `delete`: ~lcs_ctx makes the context's device current, closes an open stream (graphs first) and synchronises both
 // streams; then the members go, the owners freeing their memory; the base goes last, with the events and then the streams --
 // the order the hand-written tear-down had.
@@ -234,15 +279,9 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<float2> cap32;
   I8Set i8;
   F16Set f16;
-  bool use_i8 = false, use_f16 = false;
-  bool src_u8 = false;               // the resident buffers came from a u8 source: the fp64 stages read cap8
-  const float2 *src32 = nullptr;     // VIEW: complex<float> batches read in place: the CALLER's buffers, which the fp64 stages read (no cap32 copy)
   DevBuf<double2> cap64;             // slot 0 only: fp64 copy for the host (complex<double>) entry points
-  bool cap64_valid = false;
-  DevBuf<SlotParams> params_ws;      // the workspace's parameter records and hypotheses (ensure_ws) ...
-  DevBuf<double> fset_ws;
-  SlotParams *params = nullptr;      // ... and the VIEWS every launcher and upload reads: of params_ws / fset_ws, except while the
-  double *fset = nullptr;            // streaming chain is issued or recorded -- then of the stream's device mirror (stream_chain)
+  DevBuf<SlotParams> params_ws;      // the workspace's parameter records and hypotheses (ensure_ws): what every entry point but the
+  DevBuf<double> fset_ws;            // streaming chain uploads to and hands to its launches (Launch::params / fset)
   DevBuf<float2> tmpl;
   DevBuf<int> start, smin, kp2;
   DevBuf<float> btab;                // fp32 kernel only: allocated by its first launch for the workspace's slots and groups
@@ -252,9 +291,7 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<unsigned> fix_list;         // [S][3][9600]: positions (slot * 3 + t) * 9600 + idx whose arg-max is a near-tie (capacity: every position)
   DevBuf<int> n_fix;                 // [4]: entries on the list (zeroed by k_prep_tables)
   DevBuf<float> second32;            // [S][3][9600]: the runner-up of the collapse's maximum (written for lcs_foe_partial only: lcs_foe_contend reads it)
-  DevBuf<double> fset_g;             // the whole grid, for lcs_foe_contend (fset holds the rank's share then)
-  bool repair_peaks_only = false;    // lcs_search_capbuf / the streaming chain: list only the near-ties at or above their position's Z_th1 (pss_xcorr.hip: collapse_flag)
-  bool skip_frq_repair = false;      // lcs_foe_partial: a rank sees only its share of the hypotheses (a near-tie may span two ranks)
+  DevBuf<double> fset_g;             // the whole grid, for lcs_foe_contend (fset_ws holds the rank's share then)
   DevBuf<lcs_cell> peaks;
   DevBuf<int> npeaks;
   DevBuf<float2> xc;                // debug: raw correlations [3][n_cap-136][n_f]
@@ -289,8 +326,7 @@ struct lcs_ctx : lcs_ctx_queues {
   bool percell_ready = false;
   // streaming mode (lcs_stream_*): the one-buffer, n_f = 1 chain captured once as a hipGraph; every
   // per-push input reaches the device through fixed pinned buffers, so the graph never changes
-  bool single_stream = false;        // launch everything on `stream`, no cross-stream events
-  bool st_open = false;
+  bool st_open = false;              // the captured graph holds the workspace's addresses: nothing it reads may be reallocated
   int st_head = 0, st_count = 0;                  // two slots: oldest buffer in flight, number in flight
   int st_fmt = 0;
   uint32_t st_n_cap = 0;
@@ -337,23 +373,15 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<char> h2d;                  // device staging of lcs_batch_enqueue_host
   PinnedBuf<char> h_stage[2];        // pinned slots for host sources that are not page-locked
 
-  // last batch bookkeeping
-  int last_n_buf = 0;
-  int last_stage_mask = 0;
-  int last_fmt = 0;
-  bool needed_rows_only = false;     // fused chains: compute only the grid rows later stages read (tfg_mib.hip)
+  // launch records that outlive the call that built them
+  BatchRecord batch;                 // the last enqueued batch
+  Launch foe;                        // lcs_foe_partial -> lcs_foe_contend / lcs_foe_finish: this rank's share of the hypotheses (valid while foe_ready)
+  bool foe_ready = false;
   int max_work = LCS_WORK_DEFAULT;   // cells per per-cell round (lcs_set_max_cells_in_flight; grows to LCS_MAX_WORK by itself unless the caller set it)
   bool max_work_pinned = false;      // the caller set the limit: it stays
   int percell_cap = 0;               // cells the per-cell buffers are allocated for
-  int last_cell_rounds = 0;          // per-cell rounds launched for the last batch (round_cells cells each)
-  int round_cells = LCS_WORK_DEFAULT; // max_work as it was when the last batch was enqueued
-  int grid_items = 64;               // workgroups per work-list axis of the per-cell kernels (they loop over the list)
   int work_hint = 0;                 // cells the last collected batch carried into the per-cell stages: sizes the next batch's rounds and grids
   int hint_n_buf = 0, hint_fmt = -1, hint_stage = 0;   // the batch shape the hint was measured on
-  XcGeom last_geo{};
-  XcGeom foe_geo{};                  // lcs_foe_partial -> lcs_foe_finish: this rank's share of the hypotheses
-  bool foe_ready = false;
-  uint32_t foe_n_cap = 0;
   int last_xc_launches = 0;
   double last_xc_ops = 0;            // matrix-core operations (2 x MACs) the correlation launches of the last batch executed
   const char *last_xc_kernel = "";
@@ -386,39 +414,39 @@ void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.c
 
 // ---- kernel launchers (one per .hip file) -------------------------------------------
 // pss_xcorr.hip
-CapSrc lcs_cap_src(const lcs_ctx *c, uint32_t n_cap);   // which copy of the capture buffers the fp64 stages read
-int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap);
-int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact);   // cap64 -> cap32 + int8 copies; exact: every component is (u8 - 127) / 128
-int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, bool time_it);
+// The ingest launchers say what the fp64 stages read afterwards (*src): the int8 pairs of a u8 source, the fp32 copy, the
+// caller's own complex<float> buffers read in place (lcs_launch_ingest_f16), or cap64.
+int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap, CapSrc *src);
+int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src);   // cap64 -> cap32 + int8 copies; exact: every component is (u8 - 127) / 128
+int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it);
 int lcs_ensure_btab(lcs_ctx *c);   // fp32 kernel's operand tables for the current workspace (allocated on first use)
-int lcs_launch_single_layout(lcs_ctx *c, const XcGeom &geo, int slot, float *ref_layout, int to_ref);   // group-major <-> [t][idx][foi]
-int lcs_launch_foe_contend(lcs_ctx *c, const XcGeom &geo, const double *fset_g, const long long *d_words, long long *d_words2);
+int lcs_launch_single_layout(lcs_ctx *c, const Launch &L, int slot, float *ref_layout, int to_ref);   // group-major <-> [t][idx][foi]
+int lcs_launch_foe_contend(lcs_ctx *c, const Launch &L, const double *fset_g, const long long *d_words, long long *d_words2);
 int lcs_launch_foe_resolve(lcs_ctx *c, long long *d_words, const long long *d_words2);
 // pss_xcorr_i8.hip
-int lcs_launch_fill_brow_i8(lcs_ctx *c, int n_buf, const XcGeom &geo);
-int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const XcGeom &geo, int slot0, int n_slots, int xcd_map);
+int lcs_launch_fill_brow_i8(lcs_ctx *c, const Launch &L);
+int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map);
 // pss_xcorr_f16.hip
-int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap);   // complex<float> -> cap32 + fp16 hi / lo pairs + per-buffer scale
-int lcs_launch_fill_brow_f16(lcs_ctx *c, int n_buf, const XcGeom &geo);
-int lcs_launch_xcorr_f16(lcs_ctx *c, hipStream_t sxc, const XcGeom &geo, int slot0, int n_slots, int xcd_map);
+int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap, CapSrc *src);   // complex<float> -> fp16 hi / lo pairs + per-buffer scale (+ cap32 unless read in place)
+int lcs_launch_fill_brow_f16(lcs_ctx *c, const Launch &L);
+int lcs_launch_xcorr_f16(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map);
 
-int lcs_launch_xc_debug(lcs_ctx *c, const XcGeom &geo);   // raw xc for slot 0 (debug output only)
+int lcs_launch_xc_debug(lcs_ctx *c, const Launch &L);   // raw xc for slot 0 (debug output only)
 // peak_search.hip
-int lcs_launch_peak_search(lcs_ctx *c, int n_buf, const XcGeom &geo, double udb10_m12, bool fp32_exact);
-int lcs_launch_foe_pack(lcs_ctx *c, const XcGeom &geo, long long *d_words, double *d_meta);      // collapsed (pow, frq) -> packed words
-int lcs_launch_foe_unpack(lcs_ctx *c, const XcGeom &geo, const long long *d_words, const double *d_meta);
+int lcs_launch_peak_search(lcs_ctx *c, const Launch &L, double udb10_m12, bool fp32_exact);
+int lcs_launch_foe_pack(lcs_ctx *c, const Launch &L, long long *d_words, double *d_meta);      // collapsed (pow, frq) -> packed words
+int lcs_launch_foe_unpack(lcs_ctx *c, const Launch &L, const long long *d_words, const double *d_meta);
 // sss_foe.hip
-int lcs_launch_sss_foe(lcs_ctx *c, int n_buf, uint32_t n_cap, double thresh2_n_sigma, double *dbg /*device, nullable*/);
-int lcs_launch_sss_only(lcs_ctx *c, uint32_t n_cap, double thresh2_n_sigma, double *dbg);
-int lcs_launch_foe_only(lcs_ctx *c, uint32_t n_cap);
+int lcs_launch_sss_foe(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg /*device, nullable*/);
+int lcs_launch_sss_only(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg);
+int lcs_launch_foe_only(lcs_ctx *c, const Launch &L);
 // tfg_mib.hip
-int lcs_launch_gather_work(lcs_ctx *c, int n_buf, int skip /* cells already handled by earlier rounds */,
-                           int limit = 0 /* cells of this round; 0: max_work */);
+int lcs_launch_gather_work(lcs_ctx *c, const Launch &L, int skip /* cells already handled by earlier rounds */);
 __host__ __device__ static inline size_t lcs_pack_rec_offset(int n_buf) { return ((size_t)(8 + n_buf) * sizeof(int) + 63) & ~(size_t)63; }
-int lcs_launch_pack_results(lcs_ctx *c, int n_buf, bool full);   // peaks / npeaks (+ n_work) -> c->res_pack
-int lcs_launch_rs_build(lcs_ctx *c);
-int lcs_launch_tfg(lcs_ctx *c, uint32_t n_cap, bool with_rs /* also build RS_DL (the fused chain) */);
-int lcs_launch_tfoec(lcs_ctx *c, bool apply_grid, int parts = 4 /* workgroups per cell for the timing estimate: 2 in batches */);
-int lcs_launch_mib(lcs_ctx *c, bool fused);   // chan_est + PBCH candidates + selection (+ record back into the peak table)
-int lcs_launch_chan_est(lcs_ctx *c);
+int lcs_launch_pack_results(lcs_ctx *c, const Launch &L, bool full);   // peaks / npeaks (+ n_work) -> c->res_pack
+int lcs_launch_rs_build(lcs_ctx *c, const Launch &L);
+int lcs_launch_tfg(lcs_ctx *c, const Launch &L, bool with_rs /* also build RS_DL (the fused chain) */);
+int lcs_launch_tfoec(lcs_ctx *c, const Launch &L, bool apply_grid);
+int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused);   // chan_est + PBCH candidates + selection (+ record back into the peak table)
+int lcs_launch_chan_est(lcs_ctx *c, const Launch &L);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

@@ -241,13 +241,15 @@ __global__ __launch_bounds__(PSR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
   if (tid == 0) npeaks[slot] = n;
 }
 
-int lcs_launch_peak_search(lcs_ctx *c, int n_buf, const XcGeom &geo, double udb10_m12, bool fp32_exact) {
+int lcs_launch_peak_search(lcs_ctx *c, const Launch &L, double udb10_m12, bool fp32_exact) {
+  const int n_buf = L.n_buf;
+  const XcGeom &geo = L.geo;
   if (fp32_exact) {
     hipLaunchKernelGGL(k_peak_search_reg, dim3(n_buf), dim3(PSR_THREADS), 0, c->stream, reinterpret_cast<const float *>(c->work.get()), c->frq, c->zth, c->single,
-                       c->fset, c->params, c->peaks, c->npeaks, geo, udb10_m12);
+                       L.fset, L.params, c->peaks, c->npeaks, geo, udb10_m12);
   } else
     hipLaunchKernelGGL(k_peak_search, dim3(n_buf), dim3(PS_THREADS), 0, c->stream, c->pow_, c->frq, c->zth, c->single,
-                       c->fset, c->params, c->work, c->peaks, c->npeaks, geo, udb10_m12);
+                       L.fset, L.params, c->work, c->peaks, c->npeaks, geo, udb10_m12);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
@@ -284,13 +286,15 @@ __global__ __launch_bounds__(256) void k_foe_unpack(const long long *__restrict_
     zth[i] = R_th1 * v / rx_cutoff / 137 / 2 / (int)meta[LCS_N_IDX] / (2 * ds + 1);      // src/CellSearch.cpp:500-503, as k_sp_fold
   }
 }
-int lcs_launch_foe_pack(lcs_ctx *c, const XcGeom &geo, long long *d_words, double *d_meta) {
+int lcs_launch_foe_pack(lcs_ctx *c, const Launch &L, long long *d_words, double *d_meta) {
+  const XcGeom &geo = L.geo;
   hipLaunchKernelGGL(k_foe_pack, dim3((3 * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<const float *>(c->work.get()), c->frq, c->spinc,
                      d_words, d_meta, geo);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_foe_unpack(lcs_ctx *c, const XcGeom &geo, const long long *d_words, const double *d_meta) {
+int lcs_launch_foe_unpack(lcs_ctx *c, const Launch &L, const long long *d_words, const double *d_meta) {
+  const XcGeom &geo = L.geo;
   const double R_th1 = lcs_tables::chi2cdf_inv(1 - pow(10.0, -12), 2.0 * geo.n_comb * (2 * geo.ds + 1));
   const double rx_cutoff = (6 * 12 * 15e3 / 2 + 4 * 15e3) / (30720000.0 / 16 / 2);
   hipLaunchKernelGGL(k_foe_unpack, dim3((3 * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, d_words, d_meta, c->pow_, reinterpret_cast<float *>(c->work.get()),

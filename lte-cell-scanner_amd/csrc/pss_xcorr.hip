@@ -1059,19 +1059,10 @@ __global__ __launch_bounds__(256) void k_foe_resolve(long long *__restrict__ wor
 }
 
 // ------------------------------------------------------------------------------ launch
-CapSrc lcs_cap_src(const lcs_ctx *c, uint32_t n_cap) {
-  CapSrc s{nullptr, nullptr, nullptr, n_cap};
-  if (c->cap64_valid) s.c64 = c->cap64;
-  else if (c->src_u8) s.c8 = c->i8.cap8;
-  else s.c32 = c->src32 ? c->src32 : c->cap32;
-  return s;
-}
-
 // complex<double> in cap64 (slot 0): fp32 copy + int8 copies + exactness verdict (one small readback: the caller picks
-// the correlation kernel from it).  Needs the int8 buffers (ensure_i8 in lcs_api.hip).
-int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact) {
-  c->src_u8 = false;
-  c->src32 = nullptr;
+// the correlation kernel from it).  Needs the int8 buffers (ensure_i8 in lcs_api.hip).  The fp64 stages read cap64 itself.
+int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src) {
+  *src = CapSrc{nullptr, c->cap64, nullptr, n_cap};
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
   hipLaunchKernelGGL(k_ingest_c128, dim3(nb), dim3(256), 0, c->stream, c->cap64, n_cap, c->cap32, c->i8.cap8, c->i8.cap8s, c->d_flag);
@@ -1083,9 +1074,12 @@ int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact) {
   return LCS_OK;
 }
 
-int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap) {
-  c->src_u8 = fmt == LCS_FMT_IQ_U8;
-  c->src32 = nullptr;
+// fmt LCS_FMT_C128: cap64 (slot 0, uploaded by the caller) -> cap32
+int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap, CapSrc *src) {
+  *src = CapSrc{nullptr, nullptr, nullptr, n_cap};
+  if (fmt == LCS_FMT_IQ_U8) src->c8 = c->i8.cap8;
+  else if (fmt == LCS_FMT_C128) src->c64 = c->cap64;
+  else src->c32 = c->cap32;
   if (fmt == LCS_FMT_IQ_U8) {
     const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
     hipLaunchKernelGGL(k_ingest_u8, dim3(nb, n_buf), dim3(256), 0, c->stream, (const uint8_t *)d_src, n_cap, c->i8.cap8, c->i8.cap8s);
@@ -1114,17 +1108,20 @@ int lcs_ensure_btab(lcs_ctx *c) {
   return c->btab.reserve(c, need);
 }
 
-int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, bool time_it) {
-  hipLaunchKernelGGL(k_prep_tables, dim3(n_buf, 4), dim3(256), 0, c->stream, c->params, c->fset, c->d_pss_td, c->tmpl,
+int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it) {
+  const int n_buf = L.n_buf;
+  const XcGeom &geo = L.geo;
+  const CapSrc &cs = L.src;
+  hipLaunchKernelGGL(k_prep_tables, dim3(n_buf, 4), dim3(256), 0, c->stream, L.params, L.fset, c->d_pss_td, c->tmpl,
                      c->start, c->smin, c->kp2, c->n_fix, geo);
   // one combining window: every element in the reference's own arithmetic (k_single_exact); no operand tables needed
   const bool exact_single = geo.n_comb == 1;
   if (exact_single) ;
-  else if (c->use_i8) {
-    int rc_ = lcs_launch_fill_brow_i8(c, n_buf, geo);
+  else if (L.xc == XcKernel::i8) {
+    int rc_ = lcs_launch_fill_brow_i8(c, L);
     if (rc_) return rc_;
-  } else if (c->use_f16) {
-    int rc_ = lcs_launch_fill_brow_f16(c, n_buf, geo);
+  } else if (L.xc == XcKernel::f16) {
+    int rc_ = lcs_launch_fill_brow_f16(c, L);
     if (rc_) return rc_;
   } else {
     { int rc_ = lcs_ensure_btab(c); if (rc_) return rc_; }
@@ -1143,11 +1140,11 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
   a.R_th1 = lcs_tables::chi2cdf_inv(1 - pow(10.0, -12), 2.0 * geo.n_comb * (2 * geo.ds + 1));
   a.rx_cutoff = (6 * 12 * 15e3 / 2 + 4 * 15e3) / (30720000.0 / 16 / 2);
   auto launch_sp = [&](hipStream_t st) {
-    if (c->src_u8 && !c->cap64_valid) {
+    if (cs.c8) {
       hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, st, c->i8.cap8, geo.n_cap, c->spinc, c->zth, a);
     } else {
       hipLaunchKernelGGL(k_sp_sums, dim3(((LCS_N_IDX + SP_TILE - 1) / SP_TILE) * a.n_comb_sp * n_buf), dim3(64), 0,
-                         st, lcs_cap_src(c, geo.n_cap), c->sp, geo.n_cap, a.n_comb_sp, n_buf);       // one-wave workgroups
+                         st, cs, c->sp, geo.n_cap, a.n_comb_sp, n_buf);       // one-wave workgroups
       hipLaunchKernelGGL(k_sp_fold, dim3((n_buf * LCS_N_IDX + 255) / 256), dim3(256), 0, st, c->sp, c->spinc, c->zth, a, n_buf);
     }
   };
@@ -1155,7 +1152,7 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
   // slots [0, n8) with the XCD-aware mapping, the remainder with the plain one
   const int n8 = (n_buf >= 8) ? (n_buf & ~7) : 0;
   // main stream -> correlation stream hand-off (tables and capture buffer are ready)
-  const bool single_stream = c->single_stream;
+  const bool single_stream = L.single_stream;
   hipStream_t sxc = single_stream ? c->stream : c->stream_xc;
   if (!single_stream) {
     HIPCHK(c, hipEventRecord(c->ev_pre, c->stream));
@@ -1174,22 +1171,21 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
   c->last_xc_ops = 0;
   c->last_xc_kernel = "k_xcorr_mfma_blk<4,4,32>";
   if (exact_single) {
-    const CapSrc cs = lcs_cap_src(c, geo.n_cap);
     const dim3 grid(EXS_CHUNKS, geo.G, n_buf);
-    if (cs.c8) hipLaunchKernelGGL(k_single_exact<0>, grid, dim3(256), 0, sxc, cs, c->params, c->fset, c->d_pss_td, c->start, c->single, geo);
-    else if (cs.c32) hipLaunchKernelGGL(k_single_exact<1>, grid, dim3(256), 0, sxc, cs, c->params, c->fset, c->d_pss_td, c->start, c->single, geo);
-    else hipLaunchKernelGGL(k_single_exact<2>, grid, dim3(256), 0, sxc, cs, c->params, c->fset, c->d_pss_td, c->start, c->single, geo);
+    lcs_by_cap_kind(cs, [&](auto kind) {
+      hipLaunchKernelGGL(k_single_exact<decltype(kind)::value>, grid, dim3(256), 0, sxc, cs, L.params, L.fset, c->d_pss_td, c->start, c->single, geo);
+    });
     c->last_xc_kernel = "k_single_exact";
     launches = 1;
   }
   for (int part = 0; part < 2 && !exact_single; ++part) {
     const int s0 = part ? n8 : 0, ns = part ? n_buf - n8 : n8;
     if (ns <= 0) continue;
-    if (c->use_i8) {                                                            // u8 sources: int8 three-digit kernel
-      int rc_ = lcs_launch_xcorr_i8(c, sxc, geo, s0, ns, part ? 0 : 1);
+    if (L.xc == XcKernel::i8) {                                                 // u8 sources: int8 three-digit kernel
+      int rc_ = lcs_launch_xcorr_i8(c, sxc, L, s0, ns, part ? 0 : 1);
       if (rc_) return rc_;
-    } else if (c->use_f16) {                                                    // complex<float> batches: fp16 three-product kernel
-      int rc_ = lcs_launch_xcorr_f16(c, sxc, geo, s0, ns, part ? 0 : 1);
+    } else if (L.xc == XcKernel::f16) {                                         // complex<float> batches: fp16 three-product kernel
+      int rc_ = lcs_launch_xcorr_f16(c, sxc, L, s0, ns, part ? 0 : 1);
       if (rc_) return rc_;
     } else {                                                                    // fp32: 4-wave workgroups, B through LDS
       constexpr int NWV = 4;
@@ -1211,25 +1207,22 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
     const dim3 grid((LCS_N_IDX / 64) * n_buf), block(256);
     float *incoh = want_incoh ? c->incoh : nullptr;
     float *pow32 = reinterpret_cast<float *>(c->work.get());
-    const double *zf = c->repair_peaks_only ? c->zth : nullptr;      // fused single-buffer chains: only near-ties that can become a peak
-    float *s2 = c->skip_frq_repair ? c->second32 : nullptr;          // lcs_foe_partial: the runner-up values for lcs_foe_contend
+    const double *zf = L.repair == FrqRepair::peaks_only ? c->zth : nullptr;         // only near-ties that can become a peak
+    float *s2 = L.repair == FrqRepair::none_keep_2nd ? c->second32 : nullptr;        // the runner-up values for lcs_foe_contend
     if (geo.ds == 2 && !incoh && geo.cpg == LCS_TG)
       hipLaunchKernelGGL(k_collapse_arm2, dim3((LCS_N_IDX / (4 * COLLAPSE_OUT)) * n_buf), block, 0, c->stream, c->single, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
     else if (geo.ds == 2 && !incoh) hipLaunchKernelGGL((k_collapse<2, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
     else if (!incoh) hipLaunchKernelGGL((k_collapse<-1, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);   // any arm, no debug copy
     else hipLaunchKernelGGL((k_collapse<-1, true>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
     // near-ties of the arg-max, recomputed in the reference's arithmetic (a few positions per buffer; the kernel loops over the list)
-    if (!c->skip_frq_repair && geo.n_f > 1) {             // (one hypothesis -- the streaming mode -- has no arg-max to repair: one graph node less)
-      const CapSrc cs = lcs_cap_src(c, geo.n_cap);
+    if (L.repair != FrqRepair::none_keep_2nd && geo.n_f > 1) {      // (one hypothesis -- the streaming mode -- has no arg-max to repair: one graph node less)
       // at least 64 workgroups: a single buffer on a dense raster lists a few hundred genuine near-ties (tests/test_gpu_frq_ties.py:
       // 336 on a one-window buffer), which 8 workgroups (crowded beyond 256) would have left to the bound meant for degenerate grids
       const int ng = std::min(512, std::max(64, 8 * n_buf));
-#define REPAIR_LAUNCH(KIND) hipLaunchKernelGGL((k_frq_repair<KIND, false>), dim3(ng), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, \
-                                               c->n_fix, cs, c->params, c->fset, c->d_pss_td, c->start, c->pow_, pow32, c->frq, nullptr, nullptr, c->zth, c->n_fix + 1, geo)
-      if (cs.c8) REPAIR_LAUNCH(0);
-      else if (cs.c32) REPAIR_LAUNCH(1);
-      else REPAIR_LAUNCH(2);
-#undef REPAIR_LAUNCH
+      lcs_by_cap_kind(cs, [&](auto kind) {
+        hipLaunchKernelGGL((k_frq_repair<decltype(kind)::value, false>), dim3(ng), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, cs,
+                           L.params, L.fset, c->d_pss_td, c->start, c->pow_, pow32, c->frq, nullptr, nullptr, c->zth, c->n_fix + 1, geo);
+      });
     }
   }
   HIPCHK(c, hipGetLastError());
@@ -1237,17 +1230,16 @@ int lcs_launch_xcorr(lcs_ctx *c, int n_buf, const XcGeom &geo, bool want_incoh, 
 }
 
 // lcs_foe_contend / lcs_foe_resolve (lcs_api.hip): fset_g = the WHOLE grid on the device
-int lcs_launch_foe_contend(lcs_ctx *c, const XcGeom &geo, const double *fset_g, const long long *d_words, long long *d_words2) {
+int lcs_launch_foe_contend(lcs_ctx *c, const Launch &L, const double *fset_g, const long long *d_words, long long *d_words2) {
+  const XcGeom &geo = L.geo;
+  const CapSrc &cs = L.src;
   HIPCHK(c, hipMemsetAsync(c->n_fix, 0, 2 * sizeof(int), c->stream));
   float *pow32 = reinterpret_cast<float *>(c->work.get());
   hipLaunchKernelGGL(k_foe_flag, dim3((3 * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, d_words, pow32, c->second32, d_words2, c->fix_list, c->n_fix, geo);
-  const CapSrc cs = lcs_cap_src(c, geo.n_cap);
-#define CONTEND_LAUNCH(KIND) hipLaunchKernelGGL((k_frq_repair<KIND, true>), dim3(512), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, cs, \
-                                                c->params, fset_g, c->d_pss_td, c->start, c->pow_, pow32, c->frq, d_words, d_words2, c->zth, c->n_fix + 1, geo)
-  if (cs.c8) CONTEND_LAUNCH(0);
-  else if (cs.c32) CONTEND_LAUNCH(1);
-  else CONTEND_LAUNCH(2);
-#undef CONTEND_LAUNCH
+  lcs_by_cap_kind(cs, [&](auto kind) {
+    hipLaunchKernelGGL((k_frq_repair<decltype(kind)::value, true>), dim3(512), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, cs,
+                       L.params, fset_g, c->d_pss_td, c->start, c->pow_, pow32, c->frq, d_words, d_words2, c->zth, c->n_fix + 1, geo);
+  });
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
@@ -1257,15 +1249,17 @@ int lcs_launch_foe_resolve(lcs_ctx *c, long long *d_words, const long long *d_wo
   return LCS_OK;
 }
 
-int lcs_launch_single_layout(lcs_ctx *c, const XcGeom &geo, int slot, float *ref_layout, int to_ref) {
+int lcs_launch_single_layout(lcs_ctx *c, const Launch &L, int slot, float *ref_layout, int to_ref) {
+  const XcGeom &geo = L.geo;
   float *sg = c->single + (size_t)slot * geo.G * LCS_N_IDX * LCS_TG;      // the kernel sees one slot
   hipLaunchKernelGGL(k_single_to_ref, dim3(256, 1), dim3(256), 0, c->stream, sg, ref_layout, geo, to_ref);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
 
-int lcs_launch_xc_debug(lcs_ctx *c, const XcGeom &geo) {
-  hipLaunchKernelGGL(k_xc_debug, dim3(64, geo.n_f, 3), dim3(256), 0, c->stream, c->cap64, c->params, c->fset,
+int lcs_launch_xc_debug(lcs_ctx *c, const Launch &L) {
+  const XcGeom &geo = L.geo;
+  hipLaunchKernelGGL(k_xc_debug, dim3(64, geo.n_f, 3), dim3(256), 0, c->stream, c->cap64, L.params, L.fset,
                      c->d_pss_td, c->xc, geo);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;

@@ -42,7 +42,7 @@ __device__ __forceinline__ void f16_split(float v, _Float16 &hi, _Float16 &lo) {
 
 // ---- per buffer: the power of two that brings the largest sample component into [512, 1024).
 // Round 4: no copy at all when the caller's buffers can be read in place (even n_cap, 16-byte aligned): the fp64 stages read
-// them through CapSrc (lcs_cap_src), so only the per-buffer maximum is taken here -- a read-only pass with four 16-byte loads
+// them through the CapSrc lcs_launch_ingest_f16 hands back, so only the per-buffer maximum is taken here -- a read-only pass with four 16-byte loads
 // in flight per lane.
 #define F16_MAX_ILP 4           // independent 16-byte loads per lane, all in flight before the first use
 #define F16_MAXP 128            // partial maxima per buffer (workgroups of k_f16_max4 per buffer: 75 for 153600 samples)
@@ -364,22 +364,20 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_f16x3(const uint32_t *__restri
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
 // d_src: the caller's complex<float> buffers (LCS_FMT_C64, device memory); replaces lcs_launch_ingest for these batches
-int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap) {
-  c->src_u8 = false;
-  c->src32 = nullptr;
+int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap, CapSrc *src) {
   HIPCHK(c, hipMemsetAsync(c->f16.xmax16, 0, sizeof(unsigned) * n_buf, c->stream));
   if ((n_cap & 1u) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 15u) == 0) {
     // read in place: no copy into cap32; the fp64 stages read the caller's buffers (they stay valid until the batch is
     // collected, include/lcs.h), the maximum is a read-only pass
-    c->src32 = static_cast<const float2 *>(d_src);
+    *src = CapSrc{static_cast<const float2 *>(d_src), nullptr, nullptr, n_cap};
     const unsigned per_wg = 256 * F16_MAX_ILP, n_part = (n_cap / 2 + per_wg - 1) / per_wg;
     if (n_part > F16_MAXP) { c->err = "capture buffer too long for the fp16 path's partial maxima"; return LCS_ERR_BAD_ARG; }     // > 262144 samples: check_common refuses those
     hipLaunchKernelGGL(k_f16_max4, dim3(n_part, n_buf), dim3(256), 0, c->stream, static_cast<const float4 *>(d_src), n_cap, c->f16.xpart16);
     hipLaunchKernelGGL(k_f16_max_fold, dim3(n_buf), dim3(128), 0, c->stream, c->f16.xpart16, (int)n_part, c->f16.xmax16);
-    hipLaunchKernelGGL((k_f16_ingest<true>), dim3((unsigned)((lcs_cap8_stride(n_cap) / 2 + per_wg - 1) / per_wg), n_buf), dim3(256), 0, c->stream, c->src32,
+    hipLaunchKernelGGL((k_f16_ingest<true>), dim3((unsigned)((lcs_cap8_stride(n_cap) / 2 + per_wg - 1) / per_wg), n_buf), dim3(256), 0, c->stream, src->c32,
                        n_cap, c->f16.xmax16, c->f16.cap16h, c->f16.cap16l);
   } else {
-    int rc = lcs_launch_ingest(c, d_src, LCS_FMT_C64, n_buf, n_cap);
+    int rc = lcs_launch_ingest(c, d_src, LCS_FMT_C64, n_buf, n_cap, src);
     if (rc) return rc;
     hipLaunchKernelGGL(k_f16_max, dim3(32, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->f16.xmax16);
     hipLaunchKernelGGL((k_f16_ingest<false>), dim3(64, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->f16.xmax16, c->f16.cap16h, c->f16.cap16l);
@@ -387,13 +385,16 @@ int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_c
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_fill_brow_f16(lcs_ctx *c, int n_buf, const XcGeom &geo) {
+int lcs_launch_fill_brow_f16(lcs_ctx *c, const Launch &L) {
+  const int n_buf = L.n_buf;
+  const XcGeom &geo = L.geo;
   hipLaunchKernelGGL(k_f16_scales, dim3(n_buf), dim3(256), 0, c->stream, c->tmpl, c->f16.xmax16, c->f16.texp16, c->f16.tsc16, geo);
   hipLaunchKernelGGL(k_fill_brow_f16, dim3((LCS_TG * F16R_RLEN + 255) / 256, geo.G, n_buf), dim3(256), 0, c->stream, c->tmpl, c->f16.texp16, c->f16.brow16, geo);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_xcorr_f16(lcs_ctx *c, hipStream_t sxc, const XcGeom &geo, int slot0, int n_slots, int xcd_map) {
+int lcs_launch_xcorr_f16(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map) {
+  const XcGeom &geo = L.geo;
   const unsigned grid = (unsigned)(F16_TILES * geo.G * n_slots);
   const bool narrow = geo.n_narrow >= geo.n_comb;
   if (narrow)

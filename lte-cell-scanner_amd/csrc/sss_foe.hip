@@ -535,7 +535,9 @@ __global__ __launch_bounds__(64) void k_foe_fin(lcs_cell *__restrict__ peaks, co
 
 // ------------------------------------------------------------------ launchers
 // mode bit 0: run sss_detect, bit 1: run pss_sss_foe (only for cells whose SSS was found)
-static int run_sss_foe(lcs_ctx *c, int n_buf, uint32_t n_cap, double thresh2, int mode, double *dbg) {
+static int run_sss_foe(lcs_ctx *c, const Launch &L, double thresh2, int mode, double *dbg) {
+  const int n_buf = L.n_buf;
+  const uint32_t n_cap = L.n_cap;
   const size_t cap_items = (size_t)n_buf * LCS_MAXP;
   if (cap_items > c->pk_items.capacity() || cap_items * SW_ITEM > c->sss_ws.capacity()) {      // the two grow together
     int rc;
@@ -544,41 +546,37 @@ static int run_sss_foe(lcs_ctx *c, int n_buf, uint32_t n_cap, double thresh2, in
     c->pk_items.reset();
     if ((rc = c->sss_ws.alloc(c, cap_items * SW_ITEM)) || (rc = c->pk_items.alloc(c, cap_items)) || (rc = c->n_pk.reserve(c, 4))) return rc;
   }
-  const CapSrc src = lcs_cap_src(c, n_cap);
+  const CapSrc &src = L.src;
   // enough workgroups for every (peak, occurrence) of a typical batch to be resident at once; the
   // kernels loop over the work list, so larger batches only take more rounds
   const int win_grid = (int)std::min<size_t>((cap_items + 3) / 4, LCS_WIN_GRID);      // a wave per peak, four waves per workgroup
   const int item_grid = (int)std::min<size_t>(cap_items, LCS_ITEM_GRID);
   if (!(mode & 1)) hipLaunchKernelGGL(k_peak_list, dim3(1), dim3(64), 0, c->stream, c->npeaks, n_buf, c->pk_items, c->n_pk);
   if (mode & 1) {
-#define SSW_LAUNCH(KIND) hipLaunchKernelGGL(k_sss_win<KIND>, dim3(win_grid), dim3(SW_THREADS), 0, c->stream, c->peaks, c->npeaks, n_buf, c->pk_items, c->n_pk, src, \
-                                            n_cap, c->params, c->d_pss_fd, c->sss_ws)
-    if (src.c8) SSW_LAUNCH(0);
-    else if (src.c32) SSW_LAUNCH(1);
-    else SSW_LAUNCH(2);
-#undef SSW_LAUNCH
+    lcs_by_cap_kind(src, [&](auto kind) {
+      hipLaunchKernelGGL(k_sss_win<decltype(kind)::value>, dim3(win_grid), dim3(SW_THREADS), 0, c->stream, c->peaks, c->npeaks, n_buf, c->pk_items, c->n_pk, src,
+                         n_cap, L.params, c->d_pss_fd, c->sss_ws);
+    });
     hipLaunchKernelGGL(k_sss_ml, dim3(item_grid), dim3(SF_THREADS), 0, c->stream, c->peaks, c->pk_items, c->n_pk, n_cap,
-                       c->params, thresh2, c->d_sss_fd, c->sss_ws, dbg);
+                       L.params, thresh2, c->d_sss_fd, c->sss_ws, dbg);
   }
   if (mode & 2) {
-#define FOW_LAUNCH(KIND) hipLaunchKernelGGL(k_foe_win<KIND>, dim3((int)std::min<size_t>((cap_items * FW_QUADS + 3) / 4, LCS_WIN_GRID)), dim3(FW_THREADS), 0, c->stream, \
-                                            c->peaks, c->pk_items, c->n_pk, src, n_cap, c->params, c->d_pss_fd, c->d_sss_fd, c->sss_ws)
-    if (src.c8) FOW_LAUNCH(0);
-    else if (src.c32) FOW_LAUNCH(1);
-    else FOW_LAUNCH(2);
-#undef FOW_LAUNCH
+    lcs_by_cap_kind(src, [&](auto kind) {
+      hipLaunchKernelGGL(k_foe_win<decltype(kind)::value>, dim3((int)std::min<size_t>((cap_items * FW_QUADS + 3) / 4, LCS_WIN_GRID)), dim3(FW_THREADS), 0, c->stream,
+                         c->peaks, c->pk_items, c->n_pk, src, n_cap, L.params, c->d_pss_fd, c->d_sss_fd, c->sss_ws);
+    });
     hipLaunchKernelGGL(k_foe_fin, dim3((unsigned)((cap_items + 63) / 64)), dim3(64), 0, c->stream, c->peaks, c->pk_items,
-                       c->n_pk, n_cap, c->params, c->sss_ws);
+                       c->n_pk, n_cap, L.params, c->sss_ws);
   }
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
 
-int lcs_launch_sss_foe(lcs_ctx *c, int n_buf, uint32_t n_cap, double thresh2_n_sigma, double *dbg) {
-  return run_sss_foe(c, n_buf, n_cap, thresh2_n_sigma, 3, dbg);
+int lcs_launch_sss_foe(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg) {
+  return run_sss_foe(c, L, thresh2_n_sigma, 3, dbg);
 }
 // Single-cell helpers for the stage entry points: peaks[0] of slot 0 holds the cell (npeaks[0] = 1).
-int lcs_launch_sss_only(lcs_ctx *c, uint32_t n_cap, double thresh2_n_sigma, double *dbg) {
-  return run_sss_foe(c, 1, n_cap, thresh2_n_sigma, 1, dbg);
+int lcs_launch_sss_only(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg) {
+  return run_sss_foe(c, L, thresh2_n_sigma, 1, dbg);
 }
-int lcs_launch_foe_only(lcs_ctx *c, uint32_t n_cap) { return run_sss_foe(c, 1, n_cap, 0.0, 2, nullptr); }
+int lcs_launch_foe_only(lcs_ctx *c, const Launch &L) { return run_sss_foe(c, L, 0.0, 2, nullptr); }

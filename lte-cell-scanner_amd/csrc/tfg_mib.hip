@@ -1014,66 +1014,64 @@ __global__ __launch_bounds__(64) void k_mib_select(lcs_cell *__restrict__ cells,
 }
 
 // ------------------------------------------------------------------------------ launch
-// workgroups loop over the work list; c->grid_items of them per list axis (64: a typical 64-buffer batch in one round)
-int lcs_launch_gather_work(lcs_ctx *c, int n_buf, int skip, int limit) {
-  hipLaunchKernelGGL(k_gather_work, dim3(1), dim3(64), 0, c->stream, c->peaks, c->npeaks, n_buf, skip, limit > 0 ? limit : std::min(c->max_work, c->percell_cap),
-                     c->st_open ? c->st_dtracked : nullptr, c->st_dntracked, c->work_items, c->n_work,
+// workgroups loop over the work list; L.grid_items of them per list axis (64: a typical 64-buffer batch in one round)
+int lcs_launch_gather_work(lcs_ctx *c, const Launch &L, int skip) {
+  hipLaunchKernelGGL(k_gather_work, dim3(1), dim3(64), 0, c->stream, c->peaks, c->npeaks, L.n_buf, skip, L.round_cells,
+                     L.tracked, L.n_tracked, c->work_items, c->n_work,
                      c->cells_out);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_pack_results(lcs_ctx *c, int n_buf, bool full) {
+int lcs_launch_pack_results(lcs_ctx *c, const Launch &L, bool full) {
+  const int n_buf = L.n_buf;
   int *hdr = reinterpret_cast<int *>(c->res_pack.get());
   hipLaunchKernelGGL(k_pack_results, dim3(1), dim3(64), 0, c->stream, c->peaks, c->npeaks, n_buf, full ? 1 : 0, full ? c->n_work : nullptr, hdr, hdr + 8,
                      reinterpret_cast<lcs_cell *>(c->res_pack + lcs_pack_rec_offset(n_buf)));
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_tfg(lcs_ctx *c, uint32_t n_cap, bool with_rs) {
-  hipLaunchKernelGGL(k_cell_prep, dim3(c->grid_items), dim3(CP_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work, c->params,
-                     c->d_pn_jump, c->tfg_ts, c->cell_scratch, c->tfg_desc, with_rs ? 3 : 1, c->needed_rows_only ? 1 : 0);
-  const CapSrc cs = lcs_cap_src(c, n_cap);
-#define TFG_LAUNCH(KIND) hipLaunchKernelGGL(k_tfg<KIND>, dim3(LCS_TFG_GRID), dim3(TFG_THREADS), 0, c->stream, c->work_items, c->n_work, cs, n_cap, \
-                                            c->cell_scratch, c->tfg_desc, c->tfg, c->needed_rows_only ? 1 : 0)
-  if (cs.c8) TFG_LAUNCH(0);
-  else if (cs.c32) TFG_LAUNCH(1);
-  else TFG_LAUNCH(2);
-#undef TFG_LAUNCH
+int lcs_launch_tfg(lcs_ctx *c, const Launch &L, bool with_rs) {
+  hipLaunchKernelGGL(k_cell_prep, dim3(L.grid_items), dim3(CP_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work, L.params,
+                     c->d_pn_jump, c->tfg_ts, c->cell_scratch, c->tfg_desc, with_rs ? 3 : 1, L.needed_rows_only ? 1 : 0);
+  lcs_by_cap_kind(L.src, [&](auto kind) {
+    hipLaunchKernelGGL(k_tfg<decltype(kind)::value>, dim3(LCS_TFG_GRID), dim3(TFG_THREADS), 0, c->stream, c->work_items, c->n_work, L.src, L.n_cap,
+                       c->cell_scratch, c->tfg_desc, c->tfg, L.needed_rows_only ? 1 : 0);
+  });
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_rs_build(lcs_ctx *c) {
-  hipLaunchKernelGGL(k_cell_prep, dim3(c->grid_items), dim3(CP_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work, c->params,
+int lcs_launch_rs_build(lcs_ctx *c, const Launch &L) {
+  hipLaunchKernelGGL(k_cell_prep, dim3(L.grid_items), dim3(CP_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work, L.params,
                      c->d_pn_jump, c->tfg_ts, c->cell_scratch, c->tfg_desc, 2, 0);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
 // apply_grid: also write the corrected grid (the stage entry point); the fused chain leaves the correction to k_chan_est
-int lcs_launch_tfoec(lcs_ctx *c, bool apply_grid, int parts) {
-  hipLaunchKernelGGL(k_tfoec_est, dim3(c->grid_items, std::min(std::max(parts, 1), TF_PARTS)), dim3(TF_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work,
-                     c->params, c->tfg, c->tfg_ts, c->cell_scratch, c->tfg_ts_comp);
+int lcs_launch_tfoec(lcs_ctx *c, const Launch &L, bool apply_grid) {
+  hipLaunchKernelGGL(k_tfoec_est, dim3(L.grid_items, std::min(std::max(L.tfoec_parts, 1), TF_PARTS)), dim3(TF_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work,
+                     L.params, c->tfg, c->tfg_ts, c->cell_scratch, c->tfg_ts_comp);
   if (apply_grid) hipLaunchKernelGGL(k_tfoec_apply, dim3(LCS_TFA_GRID), dim3(TFA_THREADS), 0, c->stream, c->n_work, c->tfg, c->tfg_ts, c->cell_scratch,
-                     c->cells_out, c->tfg_comp, c->needed_rows_only ? 1 : 0);
+                     c->cells_out, c->tfg_comp, L.needed_rows_only ? 1 : 0);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
-int lcs_launch_chan_est(lcs_ctx *c) {
-  hipLaunchKernelGGL(k_chan_est, dim3(c->grid_items, 4, CE_NCHUNK), dim3(CE_THREADS), 0, c->stream, c->cells_out, c->n_work,
-                     c->tfg_comp, (const double2 *)nullptr, (const double *)nullptr, c->cell_scratch, c->ce, c->needed_rows_only ? 1 : 0);
+int lcs_launch_chan_est(lcs_ctx *c, const Launch &L) {
+  hipLaunchKernelGGL(k_chan_est, dim3(L.grid_items, 4, CE_NCHUNK), dim3(CE_THREADS), 0, c->stream, c->cells_out, c->n_work,
+                     c->tfg_comp, (const double2 *)nullptr, (const double *)nullptr, c->cell_scratch, c->ce, L.needed_rows_only ? 1 : 0);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first) { *first = CS_NPP; *per_port = 8; *n_rs_first = CS_NRS; }
 // fused: the chain's form -- the grid comes uncorrected from k_tfg (k_chan_est applies k_tfoec_est's corrections to what it
 // and k_pbch read), and the finished records go back into the peak table
-int lcs_launch_mib(lcs_ctx *c, bool fused) {
+int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused) {
   const bool scatter_back = fused;
-  hipLaunchKernelGGL(k_chan_est, dim3(c->grid_items, 4, CE_NCHUNK), dim3(CE_THREADS), 0, c->stream, c->cells_out, c->n_work,
+  hipLaunchKernelGGL(k_chan_est, dim3(L.grid_items, 4, CE_NCHUNK), dim3(CE_THREADS), 0, c->stream, c->cells_out, c->n_work,
                      c->tfg_comp, fused ? (const double2 *)c->tfg : (const double2 *)nullptr, (const double *)c->tfg_ts, c->cell_scratch,
-                     c->ce, c->needed_rows_only ? 1 : 0);
+                     c->ce, L.needed_rows_only ? 1 : 0);
   // one launch: independent waves on a candidate-major task list (k_pbch), one task per wave when the work list is as long as the
   // previous batch said (grid_items ~ cells expected + 1/8); a longer list only makes the waves loop
-  hipLaunchKernelGGL(k_pbch, dim3(std::max(32, 3 * c->grid_items)), dim3(PB_THREADS * PB_CANDS), 0, c->stream, c->cells_out, c->n_work, c->tfg_comp,
+  hipLaunchKernelGGL(k_pbch, dim3(std::max(32, 3 * L.grid_items)), dim3(PB_THREADS * PB_CANDS), 0, c->stream, c->cells_out, c->n_work, c->tfg_comp,
                      c->ce, c->cell_scratch, c->d_pbch_scr, c->d_derm_inv);
   hipLaunchKernelGGL(k_mib_select, dim3((LCS_MAX_WORK + 63) / 64), dim3(64), 0, c->stream, c->cells_out, c->n_work,
                      c->cell_scratch, scatter_back ? c->peaks : nullptr, c->work_items);

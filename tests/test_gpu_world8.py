@@ -210,6 +210,114 @@ def test_context_lifetime_leaves_no_memory_behind():
     assert drift <= LIFETIME_DRIFT_BEFORE + LIFETIME_GRANULE, (drift, free0, free1)
 
 
+def test_results_do_not_depend_on_what_a_context_ran_before():
+    """History independence.  The records of search_capbuf on the golden capture, of a streamed push of the same buffer and of a small
+    u8 batch, each taken on a fresh context, equal -- field for field, bit for bit -- the records of the same three calls made on ONE
+    context that has first run a dense batch three times (576 cells past SSS: the first collect launches the late per-cell rounds, the
+    second enqueue doubles the cells per round and widens the per-cell grids), a complex<float> batch and extract_tfg.  Whatever a
+    launch depends on is an argument of that launch; what a context keeps from earlier calls (capacities, hints) changes no result."""
+    import torch
+    from conftest import f_search_set_for
+    pkg = load_pkg()
+    iq = golden("capbuf_0000")["iq_u8"]
+    cap = iq_u8_to_capbuf(iq)
+    FC, FS = 739e6, 1.92e6
+    f = f_search_set_for(FC, 100)
+    n_dense = 288
+    small = np.ascontiguousarray(np.stack([iq, np.roll(iq, 2 * 4321), iq]))
+    d_small = torch.from_numpy(small).cuda()
+    d_dense = torch.from_numpy(np.ascontiguousarray(np.stack([iq] * n_dense))).cuda()
+    d32 = torch.from_numpy(np.stack([cap.astype(np.complex64)] * 8)).cuda()
+    torch.cuda.synchronize()
+    raw = lambda cells: [bytes(c) for c in cells]
+
+    def capbuf_records(S):
+        cells, peaks = S.search_capbuf(cap, f, FC, FC, FS)
+        return raw(cells), raw(peaks)
+
+    def stream_records(S):
+        S.stream_open(pkg.FMT_IQ_U8, 153600, FC, FC, FS)
+        S.stream_push(iq, 35e3)
+        cells, again, _ms = S.stream_collect()
+        S.stream_close()
+        return raw(cells), again
+
+    def batch_records(S):
+        return [raw(b) for b in S.search_batch(d_small.data_ptr(), pkg.FMT_IQ_U8, 3, 153600, f, np.full(3, FC), np.full(3, FC), FS, pkg.STAGE_FULL)]
+
+    takes = (capbuf_records, stream_records, batch_records)
+    fresh = []
+    for take in takes:
+        with pkg.Searcher(0) as S:
+            fresh.append(take(S))
+    first = pkg.LcsCell.from_buffer_copy(fresh[0][0][0])
+    with pkg.Searcher(0) as S:
+        for _ in range(3):
+            dense = S.search_batch(d_dense.data_ptr(), pkg.FMT_IQ_U8, n_dense, 153600, f, np.full(n_dense, FC), np.full(n_dense, FC), FS, pkg.STAGE_FULL)
+            assert S.last_batch_stats()["cells_past_sss"] > 512, S.last_batch_stats()      # more than a round of a fresh context holds
+        S.search_batch(d32.data_ptr(), pkg.FMT_C64, 8, 153600, f, np.full(8, FC), np.full(8, FC), FS, pkg.STAGE_FULL)
+        S.extract_tfg(first, cap, FC, FC, FS)
+        used = [take(S) for take in takes]
+    assert all([c.n_id_cell() for c in b] == [277, 271] for b in dense)
+    assert len(fresh[0][0]) == 2 and len(fresh[1][0]) == 2 and len(fresh[2][0]) == len(fresh[2][2]) == 2
+    for name, a, b in zip(("search_capbuf", "stream", "batch"), fresh, used):
+        assert a == b, name
+
+
+def test_saved_launches_outlive_the_stream_and_not_the_workspace():
+    """What a later call continues is a saved copy of the launch.  (a) lcs_foe_partial and (b) a batch whose per-cell rounds are
+    finished by lcs_batch_collect, both begun while a stream is open and ended after lcs_stream_close -- which frees the tracked
+    list the open stream lent them: the records equal those of the same calls on a context that never had a stream.  (c) A call that
+    replaces the workspace ends the last batch: lcs_batch_collect and lcs_batch_readback refuse instead of reading the new buffers."""
+    import torch
+    from conftest import f_search_set_for
+    pkg = load_pkg()
+    iq = golden("capbuf_0000")["iq_u8"]
+    cap = iq_u8_to_capbuf(iq)
+    FC, FS = 739e6, 1.92e6
+    f = f_search_set_for(FC, 100)
+    d3 = torch.from_numpy(np.ascontiguousarray(np.stack([iq] * 3))).cuda()
+    words = torch.empty(3 * 9600, dtype=torch.int64, device="cuda")
+    meta = torch.empty(9601, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    raw = lambda cells: [bytes(c) for c in cells]
+
+    def run(S, with_stream):
+        # an open stream's graph holds the workspace's addresses: size it first for everything that follows (no cell count is learnt
+        # from a PSS-only batch, so the full batch below enqueues one round per buffer)
+        S.search_batch(d3.data_ptr(), pkg.FMT_IQ_U8, 3, 153600, f, FC, FC, FS, pkg.STAGE_PSS)
+        S.search_capbuf(cap, f, FC, FC, FS)
+        if with_stream:
+            S.stream_open(pkg.FMT_IQ_U8, 153600, FC, FC, FS)
+        S.foe_partial(cap, f, 0, f.size, FC, FC, FS, words.data_ptr(), meta.data_ptr())
+        if with_stream:
+            S.stream_close()
+        cells, order, peaks = S.foe_finish(words.data_ptr(), meta.data_ptr(), f)
+        S.set_max_cells_in_flight(1)      # 3 rounds enqueued for 6 cells past SSS: the collect launches the rest
+        if with_stream:
+            S.stream_open(pkg.FMT_IQ_U8, 153600, FC, FC, FS)
+        S.batch_enqueue(d3.data_ptr(), pkg.FMT_IQ_U8, 3, 153600, f, FC, FC, FS, pkg.STAGE_FULL)
+        if with_stream:
+            S.stream_close()
+        batch = S.batch_collect(3)
+        assert S.last_batch_stats()["cells_past_sss"] > 3
+        return raw(cells), order.tolist(), raw(peaks), [raw(b) for b in batch]
+
+    with pkg.Searcher(0) as S:
+        want = run(S, False)
+    with pkg.Searcher(0) as S:
+        got = run(S, True)
+        assert got == want
+        assert len(want[0]) == 2 and all(len(b) == 2 for b in want[3])
+        # (c) a longer grid replaces the workspace under the collected batch
+        S.batch_enqueue(d3.data_ptr(), pkg.FMT_IQ_U8, 3, 153600, f, FC, FC, FS, pkg.STAGE_FULL)
+        S.search_capbuf(cap, f_search_set_for(2.6e9, 120), FC, FC, FS)
+        with pytest.raises(pkg.SearcherError):
+            S.batch_collect(3)
+        with pytest.raises(pkg.SearcherError):
+            S.batch_readback(0, f.size)
+
+
 def test_searcher_and_tracker_contexts_side_by_side_from_two_threads():
     """A searcher context (full-chain batches) and a tracker context (cutter + block) driven from two host threads at once -- the shape of
     LTE-Tracker's searcher and tracker threads on one GPU: every result identical to the same calls made alone."""
