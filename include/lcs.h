@@ -475,7 +475,31 @@ int lcs_track_stream_reset(lcs_ctx *ctx);
 int lcs_channelizer_taps(int decim, double *taps /*[16*decim]*/);
 int lcs_channelize(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim,
                    const double *f_shift, int n_ch, void *d_out, uint32_t n_out);
-/* HIP-event time (ms) of the last lcs_channelize of the context (filter-bank build + the channelizer kernel), as lcs_last_xcorr_ms */
+/* The same stage at a rational rate change, for front ends that do not run at a multiple of 1.92 Msps (HackRF 10 / 20 Msps,
+ * Airspy 2.5 / 6 / 10, SDRplay 6 / 8 / 10, a dongle at 2.048 / 2.4 / 2.56): fs_out = fs_in * up / down, gcd(up, down) = 1.  It is
+ * lcs_channelize applied to the capture zero-stuffed by `up`: with Tg = 16 * down and g[t] the rule of lcs_channelizer_taps at
+ * D = down for ANY down (lcs_channelizer_proto: sinc((t - (Tg-1)/2) / down) * kaiser(Tg, 7.75)[t], sum 1, computed in double,
+ * handed to the device as float), exactly, in "valid" mode,
+ *
+ *   y_k[m] = up * sum_n g[m*down + Tg-1 - n*up] * x[n] * exp(-2 pi i * f_shift[k] / fs_in * n),   m = 0 .. n_out-1,
+ *            over the n with 0 <= m*down + Tg-1 - n*up < Tg, i.e. n = ceil(m*down / up) .. floor((m*down + Tg-1) / up)
+ *
+ * and needs n_in >= floor(((n_out-1)*down + Tg-1) / up) + 1.  For up = 1 this is lcs_channelize term for term, and a call with
+ * up = 1 and down in 2..16 IS that call (forwarded, bit-identical).  g is the same design at the fine rate up * fs_in
+ * = down * fs_out, so at fs_out = 1.92 Msps it has the figures stated above for decim 4 .. 16: passband (|f| <= 0.66 MHz) ripple
+ * <= 0.0022 dB, and everything from 1.26 MHz outward -- the images of the zero-stuffing included -- at -78.1 dB or below
+ * (down = 4, 5, 16, 25, 125, 128).  The carrier phase is kept in 64-bit fixed point per input sample n.
+ *   1 < down / up <= 16,  2 <= down <= 128,  1 <= up <= 127;  20 Msps is 12/125, 10 Msps 24/125, 8 Msps 6/25, 6 Msps 8/25,
+ *   2.56 Msps 3/4, 2.5 Msps 96/125, 2.4 Msps 4/5, 2.048 Msps 15/16.
+ * Formats, alignment, the shift limit |f_shift| <= fs_in / 2, stream ordering, ownership and the 1e-5 bar are lcs_channelize's.
+ * LCS_ERR_BAD_ARG (with an lcs_last_error text, nothing launched) for a ratio above 16, down > 128, a common factor, up >= down
+ * (no interpolation), a capture one sample too short, and everything lcs_channelize refuses.  lcs_channelizer_proto is ctx-free
+ * and refuses down outside 2..128 or a null pointer. */
+int lcs_channelizer_proto(int down, double *taps /*[16*down]*/);
+int lcs_channelize_rational(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
+                            const double *f_shift, int n_ch, void *d_out, uint32_t n_out);
+/* HIP-event time (ms) of the last lcs_channelize or lcs_channelize_rational of the context (filter-bank build + the channelizer
+ * kernel), as lcs_last_xcorr_ms */
 int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);
 
 /* Stream the context launches on (hipStream_t as void*), for external event timing. */

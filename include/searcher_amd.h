@@ -244,6 +244,16 @@ class Searcher {
                   uint32_t n_out) {
     check(lcs_channelize(h_, d_wide, fmt, n_in, fs_in, decim, f_shift.empty() ? 0 : &f_shift[0], (int)f_shift.size(), d_out, n_out));
   }
+  // The same at the rational rate change fs_out = fs_in * up / down (lcs_channelize_rational; 20 Msps -> 1.92 Msps is 12/125)
+  void channelize_rational(const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const std::vector<double> &f_shift,
+                           void *d_out, uint32_t n_out) {
+    check(lcs_channelize_rational(h_, d_wide, fmt, n_in, fs_in, up, down, f_shift.empty() ? 0 : &f_shift[0], (int)f_shift.size(), d_out, n_out));
+  }
+  static std::vector<double> channelizer_proto(int down) {
+    std::vector<double> g(down >= 2 && down <= 128 ? 16 * down : 0);
+    if (lcs_channelizer_proto(down, g.empty() ? 0 : &g[0]) != LCS_OK) throw error("lcs_channelizer_proto: down outside 2..128");
+    return g;
+  }
   float last_channelize_ms() { float ms = 0; check(lcs_last_channelize_ms(h_, &ms)); return ms; }
   static std::vector<double> channelizer_taps(int decim) {
     std::vector<double> h(decim >= 2 && decim <= 16 ? 16 * decim : 0);

@@ -484,8 +484,16 @@ class Searcher:
         self._chk(self._lib.lcs_channelize(self._h, C.c_void_p(d_wide_ptr), int(fmt), int(n_in), float(fs_in), int(decim), _dp(f), int(f.size),
                                            C.c_void_p(d_out_ptr), int(n_out)), "lcs_channelize")
 
+    def channelize_rational(self, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, up: int, down: int, f_shift, d_out_ptr: int, n_out: int):
+        """channelize at the rational rate change fs_out = fs_in * up / down (lcs_channelize_rational: gcd(up, down) = 1,
+        1 < down / up <= 16, down <= 128 -- 20 Msps -> 1.92 Msps is 12/125), low-passed by channelizer_proto(down) at the fine rate
+        up * fs_in; needs n_in >= ((n_out - 1) * down + 16 * down - 1) // up + 1.  Queued and ordered like channelize."""
+        f = np.ascontiguousarray(np.atleast_1d(f_shift), np.float64)
+        self._chk(self._lib.lcs_channelize_rational(self._h, C.c_void_p(d_wide_ptr), int(fmt), int(n_in), float(fs_in), int(up), int(down), _dp(f),
+                                                    int(f.size), C.c_void_p(d_out_ptr), int(n_out)), "lcs_channelize_rational")
+
     def last_channelize_ms(self) -> float:
-        """HIP-event time (ms) of the last channelize call of this context (lcs_last_channelize_ms)."""
+        """HIP-event time (ms) of the last channelize / channelize_rational call of this context (lcs_last_channelize_ms)."""
         ms = C.c_float(0)
         self._chk(self._lib.lcs_last_channelize_ms(self._h, C.byref(ms)), "lcs_last_channelize_ms")
         return ms.value
@@ -615,4 +623,14 @@ def channelizer_taps(decim: int) -> np.ndarray:
     rc = capi.load().lcs_channelizer_taps(int(decim), _dp(o))
     if rc != 0:
         raise SearcherError(f"lcs_channelizer_taps({decim}): {capi.ERRORS.get(rc, rc)}")
+    return o
+
+
+def channelizer_proto(down: int) -> np.ndarray:
+    """The 16 * down taps of the rational channelizer's low-pass at the fine rate (lcs_channelizer_proto): the rule of
+    channelizer_taps for any down in 2..128."""
+    o = np.empty(16 * max(int(down), 0))
+    rc = capi.load().lcs_channelizer_proto(int(down), _dp(o))
+    if rc != 0:
+        raise SearcherError(f"lcs_channelizer_proto({down}): {capi.ERRORS.get(rc, rc)}")
     return o

@@ -87,17 +87,6 @@ __global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *_
 }
 
 template <int FMT>
-__device__ __forceinline__ float2 chan_sample(const void *x, unsigned long long n) {
-  if (FMT == LCS_FMT_C64) return ((const float2 *)x)[n];
-  if (FMT == LCS_FMT_IQ_S16) {
-    const uint32_t p = ((const uint32_t *)x)[n];
-    return make_float2((float)(int)(int16_t)(p & 0xFFFFu) * (1.f / 32768.f), (float)(int)(int16_t)(p >> 16) * (1.f / 32768.f));
-  }
-  const uint32_t p = ((const uint16_t *)x)[n];
-  return make_float2((float)(int)(int8_t)(p & 255u) * (1.f / 128.f), (float)(int)(int8_t)(p >> 8) * (1.f / 128.f));
-}
-
-template <int FMT>
 __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, unsigned long long n_in, int D,
                                                     const float *__restrict__ tab, const unsigned long long *__restrict__ step,
                                                     int n_ch, float2 *__restrict__ out, unsigned n_out) {
@@ -161,7 +150,7 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
 
 // One call's parameters on their way to the device: [n_ch] phase steps, then T taps as float.  Two page-locked slots used in
 // turn, each guarded by the event behind its copy, so a call never waits for the GPU unless three calls are in flight.
-static int chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
+int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
   const int k = c->chan_slot ^= 1;
   if (!c->ev_chan_slot[k]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan_slot[k], hipEventDisableTiming));
   else HIPCHK(c, hipEventSynchronize(c->ev_chan_slot[k]));
@@ -182,7 +171,7 @@ int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan0, LCS_EVENT_NOFENCE));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan1, LCS_EVENT_NOFENCE));
   }
-  if ((rc = chan_slot(c, par_bytes, &k))) return rc;
+  if ((rc = lcs_chan_slot(c, par_bytes, &k))) return rc;
   unsigned long long *h_step = reinterpret_cast<unsigned long long *>(c->chan_hpin[k].get());
   float *h_taps = (float *)(h_step + n_ch);
   for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);

@@ -75,26 +75,39 @@ def dedup(detected: Sequence[Sequence[dict]]) -> List[dict]:
 
 
 def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, fc_centre: float, carriers, f_search_set,
-                    n_out: int = 153584, chunk: int = 128, max_cells_per_buf: int = 16):
+                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None):
     """A band search from ONE wideband capture resident in HBM (n_in samples of fmt at fs_in, centred on fc_centre): the
     carriers (absolute Hz, e.g. fc_search_set(...)) are channelized `chunk` at a time (Searcher.channelize: mix, low-pass,
     decimate by decim) into a torch buffer this function owns, and every chunk goes through the full chain as a
     complex<float> batch with fc_requested = fc_programmed = the carrier and fs_programmed = fs_in / decim -- the batch
     is queued right behind the channelizer on the searcher's stream, nothing waits in between.  n_out is even (the float
     batch needs an even n_cap); 153584 = the most an 80 ms capture gives, rounded down: 15 combining windows as for a
-    dongle buffer.  Returns one list of cells (LcsCell) per carrier, in the order of `carriers`:
-    ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's."""
+    dongle buffer.  rate = (up, down) takes a capture at any rate with fs_in * up / down = 1.92 Msps (20 Msps: (12, 125))
+    through Searcher.channelize_rational instead: decim is ignored, fs_programmed = fs_in * up / down, and n_out -- unless
+    given -- is the largest even count the capture holds (without rate it is 153584).  Returns one list of cells (LcsCell)
+    per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's."""
     import torch
     from . import capi
     carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
-    fs_out = float(fs_in) / int(decim)
+    if rate is not None:
+        up, down = int(rate[0]), int(rate[1])
+        fs_out = float(fs_in) * up / down
+        if n_out is None:      # what the capture holds: (n_out - 1) * down + 16 * down <= n_in * up
+            n_out = ((int(n_in) * up - 16 * down) // down + 1) & ~1
+    else:
+        fs_out = float(fs_in) / int(decim)
+        if n_out is None:
+            n_out = 153584
     chunk = max(1, min(int(chunk), carriers.size))
     dev = getattr(searcher, "device", -1)
     buf = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
     out = []
     for a in range(0, carriers.size, chunk):
         fc = carriers[a:a + chunk]
-        searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, decim, fc - float(fc_centre), buf.data_ptr(), n_out)
+        if rate is not None:
+            searcher.channelize_rational(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
+        else:
+            searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, decim, fc - float(fc_centre), buf.data_ptr(), n_out)
         out += searcher.search_batch(buf.data_ptr(), capi.FMT_C64, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
                                      max_cells_per_buf)
     return out

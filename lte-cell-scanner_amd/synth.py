@@ -412,6 +412,50 @@ def make_wideband(seed, fc_centre, decim, placed, snr_db=10.0, fmt=capi.FMT_IQ_S
     return iq, truth
 
 
+def make_wideband_rate(seed, fc_centre, up, down, placed, snr_db=10.0, fmt=capi.FMT_IQ_S16, n_in=None, rms=0.15):
+    """make_wideband for a front end whose rate is no multiple of 1.92 Msps: one capture at 1.92 Msps * down / up (HackRF at
+    20 Msps: up / down = 12 / 125) centred on fc_centre -- what lcs_channelize_rational takes.
+
+    The generator is make_wideband's with the spectrum of every carrier's n_nb-sample signal zero-stuffed to n_nb * down / up
+    bins, so n_nb is a multiple of up (and even): 153600 by default, rounded up to the next such count where it is not one
+    (15/16: 153600 is a multiple of 15), or the least such count that covers a given n_in.  The noise is snr_db below a
+    gain_db = 0 cell inside a 1.92 MHz channel, i.e. down / up times that over the whole band.  Returns (capture, truth) as
+    make_wideband; the capture has n_in = n_nb * down / up samples unless n_in says less."""
+    up, down = int(up), int(down)
+    if not (1 <= up < down) or np.gcd(up, down) != 1:
+        raise ValueError("make_wideband_rate: 1 <= up < down with gcd(up, down) = 1")
+    unit = up * (2 if up & 1 else 1)                      # n_nb: a multiple of up, and even
+    n_nb = N_CAP if n_in is None else -(-int(n_in) * up // down)
+    n_nb = -(-n_nb // unit) * unit
+    n_w = n_nb // up * down
+    n_in = n_w if n_in is None else int(n_in)
+    rng = np.random.default_rng(seed)
+    n = np.arange(n_w, dtype=np.float64)
+    fs_in = FS * down / up
+    wide = np.zeros(n_w, np.complex128)
+    truth = []
+    for carrier, cells in placed:
+        sig, _, tr = make_signal(rng, float(carrier), cells, n_nb)
+        X = np.fft.fft(sig)
+        Xw = np.zeros(n_w, np.complex128)
+        Xw[:n_nb // 2] = X[:n_nb // 2]
+        Xw[-(n_nb // 2) + 1:] = X[n_nb // 2 + 1:]          # (the Nyquist bin of the narrow signal is dropped)
+        wide += (np.fft.ifft(Xw) * (n_w / n_nb)) * np.exp(2j * np.pi * ((float(carrier) - float(fc_centre)) / fs_in) * n)
+        truth.append((float(carrier), tr))
+    noise_pow = (down / up) * (62.0 / 128.0) / 10 ** (snr_db / 10)
+    x = (wide + np.sqrt(noise_pow / 2) * (rng.standard_normal(n_w) + 1j * rng.standard_normal(n_w)))[:n_in]
+    x *= rms / np.sqrt(np.mean(np.abs(x) ** 2))
+    if fmt == capi.FMT_C64:
+        return x.astype(np.complex64), truth
+    if fmt not in (capi.FMT_IQ_S8, capi.FMT_IQ_S16):
+        raise ValueError("make_wideband_rate: fmt is FMT_IQ_S8, FMT_IQ_S16 or FMT_C64")
+    dt, sc = (np.int8, 128.0) if fmt == capi.FMT_IQ_S8 else (np.int16, 32768.0)
+    iq = np.empty(2 * n_in, dt)
+    iq[0::2] = np.clip(np.rint(sc * x.real), -sc, sc - 1).astype(dt)
+    iq[1::2] = np.clip(np.rint(sc * x.imag), -sc, sc - 1).astype(dt)
+    return iq, truth
+
+
 def wideband_to_complex(iq, fmt):
     """The values a wideband capture stands for (what lcs_channelize makes of it on the device)."""
     if fmt == capi.FMT_C64:

@@ -8,7 +8,13 @@
 Both are medians of 20 timings after 3 warm-ups.  The wideband pipeline keeps 1 / (1 + a / b) of the float path's buffer
 rate; the target is a <= 0.25 b.  Writes one JSON document (--out) and prints it.
 
+--rate up/down measures lcs_channelize_rational instead: (a) one call on an s16 capture of 80 ms at 1.92 Msps * down / up
+(12/125: 20 Msps) with the carriers of the 100 kHz raster within 0.45 fs_in of the centre (12/125: 181, +-9 MHz), (b) search_batch
+on those buffers as batches of at most 128.  Its record goes under the key "rational" of the same document; the integer
+record at the top level stays as it is (and a plain run keeps the "rational" record).
+
     python tools/chan_bench.py --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --rate 12/125 --out profiles/channelizer/chan_bench.json
 """
 import argparse
 import importlib.util
@@ -44,18 +50,28 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cells", type=int, default=8, help="cells planted across the band (every 32nd carrier)")
+    ap.add_argument("--rate", default=None, metavar="UP/DOWN", help="measure lcs_channelize_rational at this rate change, e.g. 12/125")
     args = ap.parse_args()
+    rate = tuple(int(v) for v in args.rate.split("/")) if args.rate else None
     import torch
     from __graft_entry__ import load_package
     pkg = load_package()
     D, N_CH, N_OUT, FC0 = 16, 256, 153584, 740.0e6
     fs_in, n_in = D * 1.92e6, 153600 * D
+    if rate:
+        up, down = rate
+        fs_in, n_in = 1.92e6 * down / up, -(-153600 // up) * down
+        N_CH = 2 * int(0.45 * fs_in / 100e3) + 1
     carriers = FC0 + 100e3 * (np.arange(N_CH) - N_CH // 2)
+    args.cells = min(args.cells, (N_CH - 17) // 32 + 1)
     rng = np.random.default_rng(5)
     placed = [(float(carriers[16 + 32 * i]), [dict(n_id_1=int(rng.integers(0, 168)), n_id_2=int(rng.integers(0, 3)), cp_normal=bool(i % 4 != 3),
                                                    n_ports=int((1, 2, 2, 4)[i % 4]), n_rb_dl=int((6, 15, 25, 50, 75, 100)[i % 6]),
                                                    f_off=float(rng.uniform(-60e3, 60e3)), gain_db=float(rng.uniform(0, 6)))]) for i in range(args.cells)]
-    iq, _ = pkg.synth.make_wideband(77, FC0, D, placed, 10.0, pkg.FMT_IQ_S16)
+    if rate:
+        iq, _ = pkg.synth.make_wideband_rate(77, FC0, up, down, placed, 10.0, pkg.FMT_IQ_S16, n_in=n_in)
+    else:
+        iq, _ = pkg.synth.make_wideband(77, FC0, D, placed, 10.0, pkg.FMT_IQ_S16)
     dev = torch.device("cuda", args.device)
     d_wide = torch.from_numpy(iq).to(dev)
     d_out = torch.empty((N_CH, N_OUT), dtype=torch.complex64, device=dev)
@@ -68,7 +84,10 @@ def main():
         th.start()
         a_ms = []
         for i in range(args.warmup + args.reps):
-            s.channelize(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, D, carriers - FC0, d_out.data_ptr(), N_OUT)
+            if rate:
+                s.channelize_rational(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, up, down, carriers - FC0, d_out.data_ptr(), N_OUT)
+            else:
+                s.channelize(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, D, carriers - FC0, d_out.data_ptr(), N_OUT)
             a_ms.append(s.last_channelize_ms())
         s.sync()
         b_ms, n_cells = [], 0
@@ -76,9 +95,9 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             n_cells = 0
-            for h in range(2):
-                sl = slice(128 * h, 128 * h + 128)
-                cells = s.search_batch(d_out[128 * h].data_ptr(), pkg.FMT_C64, 128, N_OUT, f, carriers[sl], carriers[sl], 1.92e6, pkg.STAGE_FULL)
+            for h in range(-(-N_CH // 128)):
+                sl = slice(128 * h, min(128 * h + 128, N_CH))
+                cells = s.search_batch(d_out[128 * h].data_ptr(), pkg.FMT_C64, sl.stop - sl.start, N_OUT, f, carriers[sl], carriers[sl], 1.92e6, pkg.STAGE_FULL)
                 n_cells += sum(len(c) for c in cells)
             e1.record(stream)
             e1.synchronize()
@@ -89,19 +108,32 @@ def main():
     spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "tools", "code_objects.py"))
     co = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(co)
-    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items() if "k_channelize" in k or "k_chan_tables" in k}
-    res = {"a_channelize_ms": a, "b_search_256_ms": b, "ratio_a_over_b": a / b, "target_ratio": 0.25, "meets_target": bool(a <= 0.25 * b),
+    mine = ("k_channelize_rate", "k_chan_rate_tables") if rate else ("k_channelizeI", "k_chan_tables")
+    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items() if any(m in k for m in mine)}
+    batches = " + ".join(str(min(128, N_CH - 128 * h)) for h in range(-(-N_CH // 128))) if rate else "2 x 128"
+    taps_per_output = 16.0 * down / up if rate else 16.0 * D
+    res = {"a_channelize_ms": a, ("b_search_%d_ms" % N_CH): b, "ratio_a_over_b": a / b, "target_ratio": 0.25, "meets_target": bool(a <= 0.25 * b),
            "buffer_rate_kept": 1.0 / (1.0 + a / b),
-           "config": {"decim": D, "fmt": "s16", "n_ch": N_CH, "n_in": n_in, "n_out": N_OUT, "raster_hz": 100e3, "n_f": int(f.size), "batches": "2 x 128",
-                      "stage": "full", "reps": args.reps, "warmup": args.warmup, "cells_planted": args.cells, "cells_decoded_per_256": n_cells},
+           "config": {**({"up": up, "down": down, "fs_in": fs_in} if rate else {"decim": D}), "fmt": "s16", "n_ch": N_CH, "n_in": n_in, "n_out": N_OUT,
+                      "raster_hz": 100e3, "n_f": int(f.size), "batches": batches,
+                      "stage": "full", "reps": args.reps, "warmup": args.warmup, "cells_planted": args.cells, ("cells_decoded_per_%d" % N_CH): n_cells},
            "a_ms_min_max": [float(min(a_ms[args.warmup:])), float(max(a_ms[args.warmup:]))],
            "b_ms_min_max": [float(min(b_ms[args.warmup:])), float(max(b_ms[args.warmup:]))],
-           "channelizer_tflops_fp32": 8.0 * N_CH * 16 * D * N_OUT / (a * 1e-3) / 1e12,
+           "channelizer_tflops_fp32": 8.0 * N_CH * taps_per_output * N_OUT / (a * 1e-3) / 1e12,
            "sclk_mhz_median": (sorted(samples)[len(samples) // 2] if samples else None), "sclk_samples": len(samples),
            "device": torch.cuda.get_device_name(dev), "kernels": ks}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    try:
+        with open(args.out) as fh:
+            old = json.load(fh)
+    except (OSError, ValueError):
+        old = {}
+    if rate:
+        doc = dict(old, rational=res)
+    else:
+        doc = dict(res, **({"rational": old["rational"]} if "rational" in old else {}))
     with open(args.out, "w") as fh:
-        json.dump(res, fh, indent=1)
+        json.dump(doc, fh, indent=1)
         fh.write("\n")
     print(json.dumps(res))
 
