@@ -492,6 +492,11 @@ int lcs_channelize(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, dou
  *   1 < down / up <= 16,  2 <= down <= 128,  1 <= up <= 127;  20 Msps is 12/125, 10 Msps 24/125, 8 Msps 6/25, 6 Msps 8/25,
  *   2.56 Msps 3/4, 2.5 Msps 96/125, 2.4 Msps 4/5, 2.048 Msps 15/16.
  * Formats, alignment, the shift limit |f_shift| <= fs_in / 2, stream ordering, ownership and the 1e-5 bar are lcs_channelize's.
+ * Non-finite samples (LCS_FMT_C64 only): the kernel multiplies every output's window out to a whole number of four-sample steps,
+ * 4 * ceil(ceil(Tg / up) / 4) samples from n = ceil(m*down / up) on, with zero taps behind the last real one, and 0 * Inf is NaN.  An
+ * Inf or NaN sample therefore makes every output whose sum above holds it non-finite, as the sum says, and MAY also spoil the
+ * outputs whose window ends up to 4 samples before it (samples behind the capture's end count as zeros); every other output is
+ * what it is without that sample.
  * LCS_ERR_BAD_ARG (with an lcs_last_error text, nothing launched) for a ratio above 16, down > 128, a common factor, up >= down
  * (no interpolation), a capture one sample too short, and everything lcs_channelize refuses.  lcs_channelizer_proto is ctx-free
  * and refuses down outside 2..128 or a null pointer. */

@@ -15,7 +15,7 @@ int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context'
 
 // sample n of a capture of format FMT as (re, im) floats
 template <int FMT>
-__device__ __forceinline__ float2 chan_sample(const void *x, unsigned long long n) {
+__host__ __device__ __forceinline__ float2 chan_sample(const void *x, unsigned long long n) {
   if (FMT == LCS_FMT_C64) return ((const float2 *)x)[n];
   if (FMT == LCS_FMT_IQ_S16) {
     const uint32_t p = ((const uint32_t *)x)[n];
@@ -23,4 +23,110 @@ __device__ __forceinline__ float2 chan_sample(const void *x, unsigned long long 
   }
   const uint32_t p = ((const uint16_t *)x)[n];
   return make_float2((float)(int)(int8_t)(p & 255u) * (1.f / 128.f), (float)(int)(int8_t)(p >> 8) * (1.f / 128.f));
+}
+
+// ---- the rational form's bookkeeping (channelizer_rate.hip): where every tap, sample and output goes for a rate U / D.  The
+// kernels and the launcher decide by these, and tests/host/chan_rate_host.cpp walks a workgroup on the CPU with the same ones
+// (a host build supplies sinpi / cospi / sinpif / cospif itself where its libm has none).
+#define CR_CARRIERS 16                 // carriers per A tile (32 rows)
+#define CR_LDS_MAX (48 * 1024)         // NI grows only while the staged samples stay below this
+
+struct cr_geom { int G, NI, xrows; size_t lds_bytes; };
+struct cr_tile { int q, it, sq; };                 // residue, column block of the workgroup, s_q = ceil(q D / U)
+struct cr_pos { int rr, p; };                      // window position s_q + j = rr D + p
+struct cr_col { unsigned long long m, nd; };       // output index, first sample of its window (the sample its phase is taken at)
+
+// floats of LDS a workgroup with NI column tiles per residue stages, and its rows
+static inline size_t cr_lds_floats(int D, int G, int ni, int *rows) {
+  *rows = (32 * ni * D + 4 * G + D - 1) / D;
+  return (size_t)*rows * (2 * D + 1);
+}
+static inline cr_geom cr_geometry(int up, int down) {
+  cr_geom g;
+  g.G = ((16 * down + up - 1) / up + 3) / 4;      // k-step groups per residue: ceil(16 D / U) taps, padded to fours
+  // column tiles per residue: at least two tiles for every wave, and a whole number per wave where LDS allows
+  int ni = 1, rows_next = 0;
+  while ((up * ni < 8 || ((up * ni) & 3)) && up * ni < 32 && cr_lds_floats(down, g.G, ni + 1, &rows_next) * sizeof(float) <= CR_LDS_MAX) ++ni;
+  g.NI = ni;
+  g.lds_bytes = cr_lds_floats(down, g.G, ni, &g.xrows) * sizeof(float);
+  return g;
+}
+// workgroups along the outputs: each owns 32 NI columns of every residue
+static inline unsigned cr_grid_x(unsigned n_out, int up, int ni) {
+  const unsigned n_i = (n_out + up - 1) / up;      // columns of residue 0, the longest
+  return (n_i + 32 * ni - 1) / (32 * ni);
+}
+
+__host__ __device__ __forceinline__ int cr_sq(int q, int U, int D) { return (q * D + U - 1) / U; }
+
+// tab[((((rb * U + q) * G + s4) * 64 + lane) * 4 + i] = A[row lane & 31 of block rb][kk = 2 (4 s4 + i) + (lane >> 5)] of residue q
+__host__ __device__ __forceinline__ float cr_table_value(size_t e, const unsigned long long *__restrict__ step, const float *__restrict__ taps,
+                                                         int n_ch, int U, int D, int G) {
+  const int Tg = 16 * D;
+  const int i = (int)(e & 3), l = (int)((e >> 2) & 63);
+  size_t rest = e >> 8;
+  const int s4 = (int)(rest % G);
+  rest /= G;
+  const int q = (int)(rest % U), rb = (int)(rest / U);
+  const int j = 4 * s4 + i, r = l & 31, c = l >> 5;
+  const int ch = rb * CR_CARRIERS + (r >> 1), ri = r & 1;
+  const int sq = cr_sq(q, U, D);
+  const int t = Tg - 1 - ((sq + j) * U - q * D);      // <= Tg - 1 by the choice of s_q
+  float v = 0.f;
+  if (ch < n_ch && t >= 0) {
+    const unsigned long long ph = step[ch] * (unsigned long long)j;
+    const double ht = 2.0 * ((double)(long long)ph * 0x1p-64);      // half-turns, [-1, 1)
+    const double h = (double)U * (double)taps[t];
+    const double g_re = h * cospi(ht), g_im = -h * sinpi(ht);
+    v = (float)(ri == 0 ? (c == 0 ? g_re : -g_im) : (c == 0 ? g_im : g_re));
+  }
+  return v;
+}
+
+// the 16-byte group of four k-steps 4 s4 .. 4 s4 + 3 a lane loads as its A operands, in float4 units of the table
+__host__ __device__ __forceinline__ size_t cr_a_group(int rb, int q, int s4, int lane, int U, int G) {
+  return (((size_t)rb * U + q) * G + s4) * 64 + lane;
+}
+// staged sample idx (capture sample i0 D + idx) -> its float offset in LDS: rows of D samples, odd row stride 2 D + 1
+__host__ __device__ __forceinline__ int cr_stage_offset(int idx, int D) {
+  const int row = idx / D, p = idx - row * D;
+  return row * (2 * D + 1) + 2 * p;
+}
+// tile t of a workgroup: residue t % U, columns i0 + 32 (t / U) + 0..31
+__host__ __device__ __forceinline__ cr_tile cr_tile_of(int t, int U, int D) {
+  cr_tile r;
+  r.it = t / U;
+  r.q = t - r.it * U;
+  r.sq = cr_sq(r.q, U, D);
+  return r;
+}
+// a lane's B operand at k-step j of a tile is xs[cr_b_base + cr_b_step]: column lane & 31, (re | im) = lane >> 5; the window walks on
+__host__ __device__ __forceinline__ int cr_b_base(const cr_tile &t, int lane, int D) { return (t.it * 32 + (lane & 31)) * (2 * D + 1) + (lane >> 5); }
+__host__ __device__ __forceinline__ cr_pos cr_b_first(const cr_tile &t, int D) {
+  cr_pos w;
+  w.rr = t.sq / D;
+  w.p = t.sq - w.rr * D;
+  return w;
+}
+__host__ __device__ __forceinline__ int cr_b_step(const cr_pos &w, int D) { return w.rr * (2 * D + 1) + 2 * w.p; }
+__host__ __device__ __forceinline__ void cr_b_next(cr_pos &w, int D) {
+  if (++w.p == D) { w.p = 0; ++w.rr; }
+}
+// the tile's column of a lane: output m = i U + q of column i = i0 + 32 it + (lane & 31), its window starts at sample i D + s_q
+__host__ __device__ __forceinline__ cr_col cr_col_of(unsigned long long i0, const cr_tile &t, int lane, int U, int D) {
+  const unsigned long long i = i0 + (unsigned)(t.it * 32 + (lane & 31));
+  cr_col r;
+  r.m = i * (unsigned)U + (unsigned)t.q;
+  r.nd = i * (unsigned)D + (unsigned)t.sq;
+  return r;
+}
+// accumulator register v of a lane: row (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of the tile, column lane & 31; row = 2 carrier + (re | im)
+__host__ __device__ __forceinline__ int cr_acc_row(int v, int lane) { return (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5); }
+__host__ __device__ __forceinline__ int cr_acc_carrier(int rb, int v, int lane) { return rb * CR_CARRIERS + (cr_acc_row(v, lane) >> 1); }
+// (re, im) of a carrier's sum, turned by the carrier phase at sample nd (64-bit fixed point, wrapped exactly)
+__host__ __device__ __forceinline__ float2 cr_rotate(float re, float im, unsigned long long step, unsigned long long nd) {
+  const unsigned long long ph = step * nd;
+  const float ht = (float)(int)(unsigned)(ph >> 32) * 0x1p-31f;      // half-turns of the carrier phase at sample s_q + i D
+  const float sn = sinpif(ht), cs = cospif(ht);
+  return make_float2(re * cs + im * sn, im * cs - re * sn);
 }

@@ -27,34 +27,12 @@
 typedef float cr_f32x16 __attribute__((ext_vector_type(16)));
 typedef float cr_f32x4 __attribute__((ext_vector_type(4)));
 
-#define CR_CARRIERS 16                 // carriers per A tile (32 rows)
-#define CR_LDS_MAX (48 * 1024)         // NI grows only while the staged samples stay below this
-
-// tab[((((rb * U + q) * G + s4) * 64 + lane) * 4 + i] = A[row lane & 31 of block rb][kk = 2 (4 s4 + i) + (lane >> 5)] of residue q
+// the context's table in A-operand lane order (cr_table_value)
 __global__ __launch_bounds__(256) void k_chan_rate_tables(const unsigned long long *__restrict__ step, const float *__restrict__ taps,
                                                           int n_ch, int U, int D, int G, int n_rb, float *__restrict__ tab) {
-  const int Tg = 16 * D;
   const size_t total = (size_t)n_rb * U * G * 256;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int i = (int)(e & 3), l = (int)((e >> 2) & 63);
-    size_t rest = e >> 8;
-    const int s4 = (int)(rest % G);
-    rest /= G;
-    const int q = (int)(rest % U), rb = (int)(rest / U);
-    const int j = 4 * s4 + i, r = l & 31, c = l >> 5;
-    const int ch = rb * CR_CARRIERS + (r >> 1), ri = r & 1;
-    const int sq = (q * D + U - 1) / U;
-    const int t = Tg - 1 - ((sq + j) * U - q * D);      // <= Tg - 1 by the choice of s_q
-    float v = 0.f;
-    if (ch < n_ch && t >= 0) {
-      const unsigned long long ph = step[ch] * (unsigned long long)j;
-      const double ht = 2.0 * ((double)(long long)ph * 0x1p-64);      // half-turns, [-1, 1)
-      const double h = (double)U * (double)taps[t];
-      const double g_re = h * cospi(ht), g_im = -h * sinpi(ht);
-      v = (float)(ri == 0 ? (c == 0 ? g_re : -g_im) : (c == 0 ? g_im : g_re));
-    }
-    tab[e] = v;
-  }
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
+    tab[e] = cr_table_value(e, step, taps, n_ch, U, D, G);
 }
 
 template <int FMT>
@@ -63,77 +41,56 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
                                                          const unsigned long long *__restrict__ step, int n_ch,
                                                          float2 *__restrict__ out, unsigned n_out) {
   extern __shared__ float xs[];      // xrows rows of D samples, row stride 2 D + 1
-  const int S = 2 * D + 1;
   const unsigned long long i0 = (unsigned long long)blockIdx.x * (32u * NI);
   const int rb = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the samples [i0 D, (i0 + xrows) D) as floats; beyond the capture's end zeros (only zero taps and outputs >= n_out read them)
   const unsigned long long n0 = i0 * (unsigned)D;
   for (int idx = tid; idx < xrows * D; idx += 256) {
-    const int row = idx / D, p = idx - row * D;
+    const int o = cr_stage_offset(idx, D);
     const unsigned long long n = n0 + (unsigned)idx;
     const float2 v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
-    xs[row * S + 2 * p] = v.x;
-    xs[row * S + 2 * p + 1] = v.y;
+    xs[o] = v.x;
+    xs[o + 1] = v.y;
   }
   __syncthreads();
-  const int h = lane >> 5;
   for (int t = wave; t < U * NI; t += 4) {      // uniform per wave
-    const int it = t / U, q = t - it * U;
-    const int sq = (q * D + U - 1) / U;
+    const cr_tile tl = cr_tile_of(t, U, D);
     cr_f32x16 acc;
 #pragma unroll
     for (int v = 0; v < 16; ++v) acc[v] = 0.f;
-    const cr_f32x4 *ap = (const cr_f32x4 *)tab + ((size_t)rb * U + q) * G * 64 + lane;
-    const float *b = xs + (it * 32 + (lane & 31)) * S + h;
-    int rr = sq / D, p = sq - rr * D;      // window position s_q + j = rr D + p
+    const cr_f32x4 *ap = (const cr_f32x4 *)tab + cr_a_group(rb, tl.q, 0, lane, U, G);
+    const float *b = xs + cr_b_base(tl, lane, D);
+    cr_pos w = cr_b_first(tl, D);
     cr_f32x4 a_next = ap[0];
     for (int s4 = 0; s4 < G; ++s4) {
       const cr_f32x4 a = a_next;
       a_next = ap[(size_t)std::min(s4 + 1, G - 1) * 64];      // the next four k-steps' operands load under this step's MFMAs
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[rr * S + 2 * p], acc, 0, 0, 0);
-        if (++p == D) { p = 0; ++rr; }
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[cr_b_step(w, D)], acc, 0, 0, 0);
+        cr_b_next(w, D);
       }
     }
-    // register v of a lane: row (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of the tile, column lane & 31; row = 2 carrier + (re | im)
-    const unsigned long long i = i0 + (unsigned)(it * 32 + (lane & 31));
-    const unsigned long long m = i * (unsigned)U + (unsigned)q;
-    if (m >= n_out) continue;
-    const unsigned long long nd = i * (unsigned)D + (unsigned)sq;
+    const cr_col col = cr_col_of(i0, tl, lane, U, D);
+    if (col.m >= n_out) continue;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-#pragma unroll
-      for (int bb = 0; bb < 2; ++bb) {
-        const int ch = rb * CR_CARRIERS + 4 * a + 2 * h + bb;
-        if (ch >= n_ch) continue;
-        const unsigned long long ph = step[ch] * nd;
-        const float ht = (float)(int)(unsigned)(ph >> 32) * 0x1p-31f;      // half-turns of the carrier phase at sample s_q + i D
-        const float sn = sinpif(ht), cs = cospif(ht);
-        const float re = acc[4 * a + 2 * bb], im = acc[4 * a + 2 * bb + 1];
-        out[(size_t)ch * n_out + m] = make_float2(re * cs + im * sn, im * cs - re * sn);
-      }
+    for (int v = 0; v < 16; v += 2) {      // registers v, v + 1: (re, im) of one carrier (cr_acc_row)
+      const int ch = cr_acc_carrier(rb, v, lane);
+      if (ch >= n_ch) continue;
+      out[(size_t)ch * n_out + col.m] = cr_rotate(acc[v], acc[v + 1], step[ch], col.nd);
     }
   }
-}
-
-// floats of LDS a workgroup with NI column tiles per residue stages, and its rows
-static size_t rate_lds_floats(int D, int G, int ni, int *rows) {
-  *rows = (32 * ni * D + 4 * G + D - 1) / D;
-  return (size_t)*rows * (2 * D + 1);
 }
 
 int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
                                    const double *f_shift, int n_ch, void *d_out, uint32_t n_out) {
   const int Tg = 16 * down, n_rb = (n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
-  const int G = ((Tg + up - 1) / up + 3) / 4;      // k-step groups per residue: ceil(16 D / U) taps, padded to fours
+  const cr_geom geo = cr_geometry(up, down);
+  const int G = geo.G, ni = geo.NI, xrows = geo.xrows;
+  const size_t lds_bytes = geo.lds_bytes;
   const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 16 * 128 * sizeof(float);
   const size_t tab_floats = (size_t)n_rb * up * G * 256;
-  // column tiles per residue: at least two tiles for every wave, and a whole number per wave where LDS allows
-  int ni = 1, xrows = 0, rows_next = 0;
-  while ((up * ni < 8 || ((up * ni) & 3)) && up * ni < 32 && rate_lds_floats(down, G, ni + 1, &rows_next) * sizeof(float) <= CR_LDS_MAX) ++ni;
-  const size_t lds_bytes = rate_lds_floats(down, G, ni, &xrows) * sizeof(float);
   int k = 0, rc;
   if (par_bytes > c->chan_par.capacity() || tab_floats > c->chan_tab.capacity())      // grown on demand (earlier calls may still read the old ones)
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -157,8 +114,7 @@ int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint
   HIPCHK(c, hipEventRecord(c->ev_chan0, c->stream));
   const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
   hipLaunchKernelGGL(k_chan_rate_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, up, down, G, n_rb, c->chan_tab);
-  const unsigned n_i = (n_out + up - 1) / up;      // columns of residue 0, the longest
-  const dim3 grid((n_i + 32 * ni - 1) / (32 * ni), n_rb);
+  const dim3 grid(cr_grid_x(n_out, up, ni), n_rb);
   if (fmt == LCS_FMT_C64)
     hipLaunchKernelGGL(k_channelize_rate<LCS_FMT_C64>, grid, dim3(256), lds_bytes, c->stream, d_wide, (unsigned long long)n_in, up, down, G, ni, xrows,
                        (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out);

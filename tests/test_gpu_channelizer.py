@@ -41,10 +41,8 @@ def _run(pkg, s, q, fmt, n_in, fs_in, D, shifts, n_out):
     return d_out.cpu().numpy()
 
 
-@pytest.mark.parametrize("D", [2, 8, 16])
-@pytest.mark.parametrize("fmt", ["s8", "s16", "c64"])
-def test_arrays_match_the_double_reference(pkg, fmt, D):
-    fs_in, n_out = D * FS_OUT, 4096
+def _arrays_match(pkg, fmt, D, n_out):
+    fs_in = D * FS_OUT
     n_in = (n_out - 1) * D + 16 * D          # exactly what "valid" mode needs: the last window ends on the last sample
     shifts = np.array([0.0, 100e3, -100e3, 1234567.8, -987654.3, 0.45 * fs_in, -0.45 * fs_in, 0.5 * fs_in, 333333.3])
     q, xq = R.quantise(_noise_and_tones(100 * D + len(fmt), n_in, fs_in), fmt)
@@ -53,8 +51,20 @@ def test_arrays_match_the_double_reference(pkg, fmt, D):
         y = _run(pkg, s, q, _fmt(pkg, fmt), n_in, fs_in, D, shifts, n_out)
         assert s.last_channelize_ms() > 0
     ratios = [float(np.abs(y[k] - ref[k]).max() / np.abs(ref[k]).max()) for k in range(len(shifts))]
-    print(f"channelizer {fmt} D={D}: worst max|y - y_ref| / max|y_ref| per channel = {max(ratios):.3e}")
+    print(f"channelizer {fmt} D={D} n_out={n_out}: worst max|y - y_ref| / max|y_ref| per channel = {max(ratios):.3e}")
     assert max(ratios) <= RTOL, ratios
+
+
+@pytest.mark.parametrize("D", [2, 8, 16])
+@pytest.mark.parametrize("fmt", ["s8", "s16", "c64"])
+def test_arrays_match_the_double_reference(pkg, fmt, D):
+    _arrays_match(pkg, fmt, D, 4096)
+
+
+@pytest.mark.parametrize("D", range(2, 17))
+def test_every_decimation_matches_the_double_reference(pkg, D):
+    """s16, every D the integer kernel takes, one workgroup of 256 outputs plus one output."""
+    _arrays_match(pkg, "s16", D, 257)
 
 
 def test_full_length_capture_keeps_its_phase_to_the_last_sample(pkg):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import chan_rate_ref as RR
+import chan_rate_twin as T
 import chan_ref as R
 from conftest import load_pkg
 
@@ -23,20 +24,7 @@ def _fmt(pkg, name):
     return {"c64": pkg.FMT_C64, "s8": pkg.FMT_IQ_S8, "s16": pkg.FMT_IQ_S16}[name]
 
 
-def _noise_and_tones(seed, n_in, fs_in):
-    """the signal of tests/test_gpu_channelizer.py"""
-    rng = np.random.default_rng(seed)
-    x = 0.1 * (rng.standard_normal(n_in) + 1j * rng.standard_normal(n_in))
-    n = np.arange(n_in, dtype=np.float64)
-    for f, a in ((0.013e6, 0.2), (-0.31e6, 0.15), (0.21 * fs_in, 0.25), (-0.449 * fs_in, 0.2)):
-        x += a * np.exp(2j * np.pi * (f / fs_in) * n + 1j * rng.uniform(0, 2 * np.pi))
-    return x
-
-
-def _shifts17(fs_in):
-    """one full block of 16 carriers plus one: 0, +-100 kHz, two off the raster, +-0.45 fs_in, the Nyquist edge, nine more"""
-    return np.array([0.0, 100e3, -100e3, 0.0617283 * fs_in, -0.0493827 * fs_in, 0.45 * fs_in, -0.45 * fs_in, 0.5 * fs_in]
-                    + [(-0.41 + 0.097 * k) * fs_in for k in range(9)])
+_noise_and_tones, _shifts17 = T.noise_and_tones, T.shifts17      # the signal and the 17 carriers the host twin's tests share
 
 
 def _run(s, q, fmt, n_in, fs_in, up, down, shifts, n_out):
@@ -84,6 +72,87 @@ def test_a_call_smaller_than_one_residue_cycle(pkg):
     ratios = _worst(y, ref)
     print(f"rational channelizer, n_out = 5, one carrier: {max(ratios):.3e}")
     assert max(ratios) <= RTOL, ratios
+
+
+def _against_twin(pkg, y, q, fmt, n_in, fs_in, up, down, shifts, n_out, ref):
+    """max|gpu - twin| / max|ref| per channel, the worst: the kernel against its walk on the CPU (tests/host/chan_rate_host.cpp) -- the
+    same indices, tables built in the same arithmetic, one fma per k.  A figure to read, not a bound: how the matrix core rounds
+    inside one instruction is not something this project has measured."""
+    tw = T.run(q, fmt, n_in, up, down, T.steps(shifts, fs_in), pkg.channelizer_proto(down), n_out)
+    return max(float(np.abs(y[k] - tw[k]).max() / np.abs(ref[k]).max()) for k in range(len(ref)))
+
+
+@pytest.mark.parametrize("up,down,fmt", T.CORNERS)
+def test_corners_of_the_rate_domain(pkg, up, down, fmt):
+    """The pairs at which the launcher's bookkeeping is at an edge (tests/chan_rate_twin.py: CORNERS), each with one full workgroup, a
+    second nearly empty one and a partial residue cycle: n_out = 32 NI up + up + 1, the capture no longer than that needs."""
+    n_out = T.corner_n_out(up, down)
+    fs_in, n_in = FS_OUT * down / up, RR.n_in_min(n_out, up, down)
+    shifts = _shifts17(fs_in)
+    q, xq = R.quantise(_noise_and_tones(100 * down + up + len(fmt), n_in, fs_in), fmt)
+    ref = RR.channelize_rate_ref(xq, fs_in, up, down, shifts, n_out)
+    with pkg.Searcher(0) as s:
+        y = _run(s, q, _fmt(pkg, fmt), n_in, fs_in, up, down, shifts, n_out)
+    ratios = _worst(y, ref)
+    print(f"rational channelizer corner {fmt} {up}/{down} n_out={n_out}: worst max|y - y_ref| / max|y_ref| per channel = {max(ratios):.3e}; "
+          f"max|gpu - twin| / max|y_ref| = {_against_twin(pkg, y, q, fmt, n_in, fs_in, up, down, shifts, n_out, ref):.3e}")
+    assert max(ratios) <= RTOL, ratios
+
+
+@pytest.mark.parametrize("n_ch", [1, 15, 16, 31, 33])
+def test_carrier_counts_around_a_block_of_16_write_nothing_else(pkg, n_ch):
+    """2/3, s8: a carrier count below, at and above whole blocks of 16 carriers.  The output is the contiguous [n_ch][n_out] head of a
+    tensor of n_ch + 1 rows of n_out + 4: everything behind it -- a guard row and the guard columns -- keeps its sentinel."""
+    import torch
+    up, down = 2, 3
+    n_out = T.corner_n_out(up, down)
+    fs_in, n_in = FS_OUT * down / up, RR.n_in_min(n_out, up, down)
+    shifts = np.resize(_shifts17(fs_in), n_ch)
+    q, xq = R.quantise(_noise_and_tones(23 + n_ch, n_in, fs_in), "s8")
+    ref = RR.channelize_rate_ref(xq, fs_in, up, down, shifts, n_out)
+    d_in = torch.from_numpy(q).cuda()
+    sentinel = complex(-7.25, 1234.5)
+    d_out = torch.full((n_ch + 1, n_out + 4), sentinel, dtype=torch.complex64, device="cuda")
+    torch.cuda.synchronize()
+    with pkg.Searcher(0) as s:
+        s.channelize_rational(d_in.data_ptr(), pkg.FMT_IQ_S8, n_in, fs_in, up, down, shifts, d_out.data_ptr(), n_out)
+        s.sync()
+    flat = d_out.cpu().numpy().reshape(-1)
+    y, guard = flat[:n_ch * n_out].reshape(n_ch, n_out), flat[n_ch * n_out:]
+    assert guard.size == n_out + 4 * (n_ch + 1) and (guard == np.complex64(sentinel)).all(), np.flatnonzero(guard != np.complex64(sentinel))[:8]
+    ratios = _worst(y, ref)
+    print(f"rational channelizer s8 2/3, {n_ch} carriers: worst ratio = {max(ratios):.3e}; "
+          f"max|gpu - twin| / max|y_ref| = {_against_twin(pkg, y, q, 's8', n_in, fs_in, up, down, shifts, n_out, ref):.3e}")
+    assert max(ratios) <= RTOL, ratios
+
+
+@pytest.mark.parametrize("n_out", [1, 126])
+def test_fewer_outputs_than_residues(pkg, n_out):
+    """127/128 with n_out = 1 and n_out = up - 1: most tiles of the only workgroup have no output at all."""
+    up, down = 127, 128
+    fs_in, n_in = FS_OUT * down / up, RR.n_in_min(n_out, up, down)
+    shifts = _shifts17(fs_in)
+    q, xq = R.quantise(_noise_and_tones(127 + n_out, n_in, fs_in), "s16")
+    ref = RR.channelize_rate_ref(xq, fs_in, up, down, shifts, n_out)
+    with pkg.Searcher(0) as s:
+        y = _run(s, q, pkg.FMT_IQ_S16, n_in, fs_in, up, down, shifts, n_out)
+    ratios = _worst(y, ref)
+    print(f"rational channelizer s16 127/128, n_out = {n_out}: worst ratio = {max(ratios):.3e}; "
+          f"max|gpu - twin| / max|y_ref| = {_against_twin(pkg, y, q, 's16', n_in, fs_in, up, down, shifts, n_out, ref):.3e}")
+    assert max(ratios) <= RTOL, ratios
+
+
+def test_a_non_finite_sample_spoils_its_padded_windows_only(pkg):
+    """include/lcs.h, lcs_channelize_rational: 3/4, c64, one Inf in mid-capture.  Outputs whose padded window [s, s + 4 G) does not hold
+    the sample are finite and within the bar; outputs whose taps meet it are non-finite; the positions between are unconstrained
+    (0 * Inf at a zero tap).  The host twin meets the same rule in tests/test_channelizer_rate_twin_host.py."""
+    x, n_in, fs_in, shifts, n_out, clean, dirty = T.nonfinite_case()
+    with np.errstate(invalid="ignore", over="ignore"):
+        ref = RR.channelize_rate_ref(x.astype(np.complex128), fs_in, 3, 4, shifts, n_out)
+    with pkg.Searcher(0) as s:
+        y = _run(s, x, pkg.FMT_C64, n_in, fs_in, 3, 4, shifts, n_out)
+    worst = T.check_nonfinite(y, ref, clean, dirty, RTOL)
+    print(f"rational channelizer c64 3/4 with one Inf sample: worst ratio over the {int(clean.sum())} clean outputs = {worst:.3e}")
 
 
 def test_full_length_capture_keeps_its_phase_to_the_last_sample(pkg):
