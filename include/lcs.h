@@ -503,8 +503,31 @@ int lcs_channelize(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, dou
 int lcs_channelizer_proto(int down, double *taps /*[16*down]*/);
 int lcs_channelize_rational(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
                             const double *f_shift, int n_ch, void *d_out, uint32_t n_out);
-/* HIP-event time (ms) of the last lcs_channelize or lcs_channelize_rational of the context (filter-bank build + the channelizer
- * kernel), as lcs_last_xcorr_ms */
+/* The same stage with 8-bit carriers: d_out is the LCS_FMT_IQ_U8 batch layout of lcs_batch_enqueue, so a band search from one
+ * wideband capture takes the int8 correlation kernel and holds a quarter of the bytes per carrier.  y_k[m] is the sum defined
+ * above: lcs_channelize's (decim = down) when up == 1 and down is in 2..16, lcs_channelize_rational's otherwise; the argument rules
+ * and the refusals (LCS_ERR_BAD_ARG, an lcs_last_error text, nothing launched) are those of that call.  Carrier k is scaled by a
+ * power of two of its own and rounded to bytes:
+ *   Power.   With P_k = (1/n_out) sum_m |y_k[m]|^2, the exponent e_k is the integer for which the component rms of 2^e_k * y_k lies
+ *            in (16, 32]:  16^2 < 4^e_k * P_k / 2 <= 32^2.
+ *   Code.    code = clamp(127 + rint(2^e_k * component), 0, 255), ties rounding to even; I then Q, the dongle convention
+ *            (u8 - 127) / 128 of LCS_FMT_IQ_U8.
+ *   Gain.    d_gain[k] = 2^e_k, an exact float (DEVICE [n_ch], or NULL): what converts reported powers back.
+ *   Zero or non-finite power.  P_k equal to zero or not finite gives e_k = 0.  A non-finite component gives code 127.
+ *   Layout.  d_out is DEVICE [n_ch][n_out][2] bytes: rows lie 2 * n_out bytes apart, so a row may start at any even address when
+ *            n_out is odd; d_out itself is 16-byte aligned; any n_out >= 1 is accepted, as the float form accepts.
+ *   Stream.  Everything is queued on the context's stream and the call returns without waiting; lcs_last_channelize_ms then spans
+ *            the call through its last kernel.
+ * Every threshold of the chain is relative to the buffer's own power, so the gain changes no decision; the quantisation noise
+ * (1/12 per component) lies 38 dB or more below the carrier.  P_k is summed from the float outputs (fp32 per workgroup, double
+ * across workgroups, one fixed order: two calls give the same bytes).  The float outputs live in a scratch buffer of the context
+ * ([n_ch][n_out] complex<float>, grown on demand, freed with the context).  LCS_FMT_IQ_U8 is an OUTPUT here: as an input format it
+ * is refused like any unknown one. */
+int lcs_channelize_u8(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
+                      const double *f_shift, int n_ch, void *d_out /*DEVICE [n_ch][n_out][2] u8*/, uint32_t n_out,
+                      float *d_gain /*DEVICE [n_ch] or NULL*/);
+/* HIP-event time (ms) of the last lcs_channelize, lcs_channelize_rational or lcs_channelize_u8 of the context (filter-bank build
+ * through the call's last kernel), as lcs_last_xcorr_ms */
 int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);
 
 /* Stream the context launches on (hipStream_t as void*), for external event timing. */

@@ -249,6 +249,12 @@ class Searcher {
                            void *d_out, uint32_t n_out) {
     check(lcs_channelize_rational(h_, d_wide, fmt, n_in, fs_in, up, down, f_shift.empty() ? 0 : &f_shift[0], (int)f_shift.size(), d_out, n_out));
   }
+  // Either form with 8-bit carriers (lcs_channelize_u8): d_out is [n_ch][n_out][2] bytes, the LCS_FMT_IQ_U8 batch layout; up = 1 and
+  // down in 2..16 is channelize, any other rate channelize_rational.  d_gain: DEVICE [n_ch] floats for the gains 2^e, or 0.
+  void channelize_u8(const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const std::vector<double> &f_shift, void *d_out,
+                     uint32_t n_out, float *d_gain = 0) {
+    check(lcs_channelize_u8(h_, d_wide, fmt, n_in, fs_in, up, down, f_shift.empty() ? 0 : &f_shift[0], (int)f_shift.size(), d_out, n_out, d_gain));
+  }
   static std::vector<double> channelizer_proto(int down) {
     std::vector<double> g(down >= 2 && down <= 128 ? 16 * down : 0);
     if (lcs_channelizer_proto(down, g.empty() ? 0 : &g[0]) != LCS_OK) throw error("lcs_channelizer_proto: down outside 2..128");

@@ -492,8 +492,25 @@ class Searcher:
         self._chk(self._lib.lcs_channelize_rational(self._h, C.c_void_p(d_wide_ptr), int(fmt), int(n_in), float(fs_in), int(up), int(down), _dp(f),
                                                     int(f.size), C.c_void_p(d_out_ptr), int(n_out)), "lcs_channelize_rational")
 
+    def channelize_u8(self, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, up: int, down: int, f_shift, d_out_ptr: int, n_out: int,
+                      want_gain: bool = False):
+        """channelize (up == 1, down in 2..16) or channelize_rational (any other rate) with 8-bit carriers (lcs_channelize_u8): the
+        buffers at d_out_ptr are [n_ch][n_out][2] uint8, the FMT_IQ_U8 batch layout, each carrier scaled by a power of two 2^e
+        that puts its component rms in (16, 32] codes and rounded to 127 + rint(.), clamped to 0..255.  Queued and ordered like
+        channelize: a batch_enqueue(d_out_ptr, FMT_IQ_U8, n_ch, n_out, ...) behind it takes the int8 correlation kernel.
+        want_gain: returns the gains 2^e as a float32 torch tensor [n_ch] on the device (written by the same stream)."""
+        f = np.ascontiguousarray(np.atleast_1d(f_shift), np.float64)
+        gain = None
+        if want_gain:
+            import torch
+            gain = torch.empty(int(f.size), dtype=torch.float32, device=torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+        self._chk(self._lib.lcs_channelize_u8(self._h, C.c_void_p(d_wide_ptr), int(fmt), int(n_in), float(fs_in), int(up), int(down), _dp(f), int(f.size),
+                                              C.c_void_p(d_out_ptr), int(n_out), C.c_void_p(gain.data_ptr() if gain is not None else None)),
+                  "lcs_channelize_u8")
+        return gain
+
     def last_channelize_ms(self) -> float:
-        """HIP-event time (ms) of the last channelize / channelize_rational call of this context (lcs_last_channelize_ms)."""
+        """HIP-event time (ms) of the last channelize / channelize_rational / channelize_u8 call of this context (lcs_last_channelize_ms)."""
         ms = C.c_float(0)
         self._chk(self._lib.lcs_last_channelize_ms(self._h, C.byref(ms)), "lcs_last_channelize_ms")
         return ms.value

@@ -70,7 +70,7 @@ EXPORTS = [
     "lcs_foe_partial", "lcs_foe_finish", "lcs_foe_contend", "lcs_foe_resolve", "lcs_track_block", "lcs_track_stats", "lcs_track_stream_block", "lcs_track_stream_reset", "lcs_track_cut", "lcs_stream_open", "lcs_stream_push", "lcs_stream_collect", "lcs_stream_close",
     "lcs_last_xcorr_ms", "lcs_last_xcorr_info", "lcs_last_frq_repairs", "lcs_last_frq_repair_stats", "lcs_frq_tie_eps", "lcs_last_batch_stats", "lcs_last_collect_host_us", "lcs_stream", "lcs_sync", "lcs_table_pss_td", "lcs_table_pss_fd", "lcs_table_sss_fd",
     "lcs_table_lte_pn", "lcs_chi2cdf_inv", "lcs_channelizer_taps", "lcs_channelize", "lcs_last_channelize_ms",
-    "lcs_channelizer_proto", "lcs_channelize_rational",
+    "lcs_channelizer_proto", "lcs_channelize_rational", "lcs_channelize_u8",
 ]
 
 _lib = None
@@ -167,6 +167,7 @@ def load() -> C.CDLL:
     L.lcs_last_channelize_ms.argtypes = [vp, fp]
     L.lcs_channelizer_proto.argtypes = [C.c_int, dp]
     L.lcs_channelize_rational.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.c_int, dp, C.c_int, vp, C.c_uint32]
+    L.lcs_channelize_u8.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.c_int, dp, C.c_int, vp, C.c_uint32, vp]
     L.lcs_stream.argtypes = [vp]
     L.lcs_stream.restype = vp
     L.lcs_sync.argtypes = [vp]

@@ -1,17 +1,42 @@
-// channelizer.h -- the wideband channelizer's launchers (channelizer.hip: integer decimation; channelizer_rate.hip: rational
-// rate change up / down).  Its per-context state (parameter and filter-bank buffers, page-locked slots, events) are the
-// chan_* / ev_chan* members of the context, shared by both forms.
+// channelizer.h -- the wideband channelizer's launchers (channelizer.hip: integer decimation and the 8-bit output stage;
+// channelizer_rate.hip: rational rate change up / down).  Its per-context state (parameter and filter-bank buffers, page-locked
+// slots, events, the float scratch of the 8-bit form) are the chan_* / ev_chan* members of the context, shared by all forms.
 #pragma once
 #include "lcs_internal.h"
+#include <cmath>
 
 void lcs_chan_taps(int decim, double *taps /*[16*decim]*/);      // any decim >= 2
 unsigned long long lcs_chan_step(double f_shift, double fs_in);
 int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot);          // the next page-locked parameter slot, free to be written
+// d_part == nullptr: the float forms.  Otherwise [n_ch][workgroups along the outputs] floats: every workgroup leaves the sum of
+// |y|^2 of its outputs per carrier there (lcs_chan_blocks / lcs_chan_rate_blocks say how many there are per carrier).
 int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
-                          int n_ch, void *d_out, uint32_t n_out);
+                          int n_ch, void *d_out, uint32_t n_out, float *d_part = nullptr);
 int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
-                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out);
-int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context's last channelizer launch (either form)
+                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out, float *d_part = nullptr);
+unsigned lcs_chan_blocks(uint32_t n_out);
+unsigned lcs_chan_rate_blocks(uint32_t n_out, int up, int down);
+// lcs_channelize_u8: the float form into the context's scratch with the power partials, then k_chan_quant_u8 (channelizer.hip)
+int lcs_launch_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift,
+                             int n_ch, void *d_out, uint32_t n_out, float *d_gain);
+int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context's last channelizer launch (any form)
+
+// ---- the 8-bit output's rule (include/lcs.h, lcs_channelize_u8): k_chan_quant_u8 and tests/host/chan_u8_host.cpp call these two.
+// The exponent e of a carrier of mean power P = mean |y|^2: the integer with 16^2 < 4^e P / 2 <= 32^2, i.e. 2^9 < 4^e P <= 2^11;
+// 0 for a power that is zero or not finite.  P = m 2^x, 1/2 <= m < 1: 2 e is the even number in [10 - x, 11 - x], and in
+// (10 - x, 12 - x] when m is 1/2 exactly (a power of two sits on the closed end).
+__host__ __device__ __forceinline__ int chan_u8_exponent(double P) {
+  if (!(P > 0.0) || !std::isfinite(P)) return 0;
+  int x;
+  const double m = frexp(P, &x);
+  const int t = 11 - x + (m == 0.5 ? 1 : 0);
+  return (t - (t & 1)) / 2;      // floor(t / 2): t - (t & 1) is even for either sign
+}
+// The code of a scaled component z = 2^e * component: clamp(127 + rint(z), 0, 255), ties to even; 127 for a z that is not finite
+__host__ __device__ __forceinline__ unsigned chan_u8_code(float z) {
+  if (!std::isfinite(z)) return 127u;
+  return (unsigned)fminf(fmaxf(127.f + rintf(z), 0.f), 255.f);
+}
 
 // sample n of a capture of format FMT as (re, im) floats
 template <int FMT>

@@ -86,10 +86,13 @@ __global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *_
   }
 }
 
-template <int FMT>
+// POW (the 8-bit form, lcs_channelize_u8): the workgroup also leaves, per carrier, the sum of |y|^2 over the outputs it stored in
+// part[carrier][blockIdx.x] -- per lane over its two tiles, over the 32 columns by a butterfly of lane exchanges, over the four
+// waves through LDS in wave order: one fixed order, no atomics, so two runs give the same bits.
+template <int FMT, bool POW>
 __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, unsigned long long n_in, int D,
                                                     const float *__restrict__ tab, const unsigned long long *__restrict__ step,
-                                                    int n_ch, float2 *__restrict__ out, unsigned n_out) {
+                                                    int n_ch, float2 *__restrict__ out, unsigned n_out, float *__restrict__ part) {
   __shared__ float xs[CH_XROWS * CH_SMAX];
   const int S = 2 * D + 1, T = 16 * D;
   const unsigned m0 = blockIdx.x * CH_NT;
@@ -126,6 +129,11 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
   }
   // register v of a lane: row (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of the tile, column lane & 31; row = 2 carrier + (re | im)
   const int h = lane >> 5;
+  float pw[8];      // POW: |y|^2 of the lane's column per carrier 4 a + 2 h + bb, index 2 a + bb
+  if constexpr (POW) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pw[i] = 0.f;
+  }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const unsigned m = m0 + wave * 64 + t * 32 + (lane & 31);
@@ -142,8 +150,73 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
         const float sn = sinpif(ht), cs = cospif(ht);
         const float re = t ? acc1[4 * a + 2 * bb] : acc0[4 * a + 2 * bb];
         const float im = t ? acc1[4 * a + 2 * bb + 1] : acc0[4 * a + 2 * bb + 1];
-        out[(size_t)ch * n_out + m] = make_float2(re * cs + im * sn, im * cs - re * sn);
+        const float2 y = make_float2(re * cs + im * sn, im * cs - re * sn);
+        out[(size_t)ch * n_out + m] = y;
+        if constexpr (POW) pw[2 * a + bb] += y.x * y.x + y.y * y.y;
       }
+    }
+  }
+  if constexpr (POW) {
+    __shared__ float red[4][CH_CARRIERS];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float v = pw[i];
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);      // within the lane's half: the 32 columns of its carriers
+      if ((lane & 31) == 0) red[wave][4 * (i >> 1) + 2 * h + (i & 1)] = v;
+    }
+    __syncthreads();
+    const int ch = rb * CH_CARRIERS + tid;
+    if (tid < CH_CARRIERS && ch < n_ch) part[(size_t)ch * gridDim.x + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  }
+}
+
+// The 8-bit output (include/lcs.h, lcs_channelize_u8): carrier ch's floats y[ch][n_out] -> bytes out[ch][n_out][2].  Every workgroup
+// sums its carrier's power partials in double in index order (one lane; the same bits in every workgroup of the carrier), takes the
+// exponent and hands the gain 2^e round through LDS.  A row of bytes starts 2 n_out bytes behind the last, at any even address: its
+// interior is cut into groups of 8 samples from the first 16-byte boundary on -- a lane reads a group as four 16-byte loads (the
+// floats are 8-byte aligned) and stores it as one 16-byte store -- and the up to 7 samples in front of the first and behind the last
+// whole group go out as 2-byte stores from the row's first workgroup.  Memory-bound: 8 bytes in, 2 out per sample.
+#define CQ_GROUPS 2048                 // groups of 8 samples per workgroup: 8 per lane
+typedef float cq_f32x4 __attribute__((ext_vector_type(4), aligned(8)));
+
+__global__ __launch_bounds__(256) void k_chan_quant_u8(const float2 *__restrict__ y, const float *__restrict__ part, int n_blocks, unsigned n_out,
+                                                       unsigned n_xb, uint8_t *__restrict__ out, float *__restrict__ gain) {
+  __shared__ float s_gain;
+  const unsigned ch = blockIdx.x / n_xb, xb = blockIdx.x - ch * n_xb;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    const float *p = part + (size_t)ch * n_blocks;
+    double P = 0.0;
+    for (int i = 0; i < n_blocks; ++i) P += (double)p[i];
+    const float g = ldexpf(1.f, chan_u8_exponent(P / (double)n_out));
+    s_gain = g;
+    if (gain && xb == 0) gain[ch] = g;
+  }
+  __syncthreads();
+  const float g = s_gain;
+  const float2 *row = y + (size_t)ch * n_out;
+  uint8_t *orow = out + (size_t)ch * n_out * 2;
+  const unsigned to_16 = (unsigned)((16u - (unsigned)(reinterpret_cast<uintptr_t>(orow) & 15u)) & 15u) >> 1;      // samples up to the boundary
+  const unsigned head = to_16 < n_out ? to_16 : n_out;
+  const unsigned n_g = (n_out - head) >> 3, tail = head + 8u * n_g;
+  const unsigned g_end = (xb + 1u) * CQ_GROUPS < n_g ? (xb + 1u) * CQ_GROUPS : n_g;
+  for (unsigned gi = xb * CQ_GROUPS + tid; gi < g_end; gi += 256) {
+    const unsigned s0 = head + 8u * gi;      // s0 + 7 < tail <= n_out
+    const cq_f32x4 *src = reinterpret_cast<const cq_f32x4 *>(row + s0);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const cq_f32x4 f = src[j];
+      w[j] = chan_u8_code(g * f[0]) | (chan_u8_code(g * f[1]) << 8) | (chan_u8_code(g * f[2]) << 16) | (chan_u8_code(g * f[3]) << 24);
+    }
+    *reinterpret_cast<uint4 *>(orow + 2 * (size_t)s0) = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  if (xb == 0 && tid < 16) {      // lanes 0..7: the samples in front of the first group; 8..15: those behind the last
+    const unsigned s = tid < 8 ? (unsigned)tid : tail + (unsigned)(tid - 8);
+    if (tid < 8 ? s < head : s < n_out) {
+      const float2 f = row[s];
+      *reinterpret_cast<uint16_t *>(orow + 2 * (size_t)s) = (uint16_t)(chan_u8_code(g * f.x) | (chan_u8_code(g * f.y) << 8));
     }
   }
 }
@@ -158,8 +231,21 @@ int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
   return c->chan_hpin[k].reserve(c, bytes);
 }
 
+unsigned lcs_chan_blocks(uint32_t n_out) { return (n_out + CH_NT - 1) / CH_NT; }
+
+template <int FMT>
+static void chan_launch(lcs_ctx *c, dim3 grid, const void *d_wide, unsigned long long n_in, int decim, const unsigned long long *d_step, int n_ch,
+                        void *d_out, unsigned n_out, float *d_part) {
+  if (d_part)
+    hipLaunchKernelGGL((k_channelize<FMT, true>), grid, dim3(256), 0, c->stream, d_wide, n_in, decim, (const float *)c->chan_tab, d_step, n_ch,
+                       (float2 *)d_out, n_out, d_part);
+  else
+    hipLaunchKernelGGL((k_channelize<FMT, false>), grid, dim3(256), 0, c->stream, d_wide, n_in, decim, (const float *)c->chan_tab, d_step, n_ch,
+                       (float2 *)d_out, n_out, d_part);
+}
+
 int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
-                          int n_ch, void *d_out, uint32_t n_out) {
+                          int n_ch, void *d_out, uint32_t n_out, float *d_part) {
   const int T = 16 * decim, n_rb = (n_ch + CH_CARRIERS - 1) / CH_CARRIERS;
   const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 256 * sizeof(float);
   const size_t tab_floats = (size_t)n_rb * 64 * T;
@@ -186,19 +272,34 @@ int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in
   HIPCHK(c, hipEventRecord(c->ev_chan0, c->stream));
   const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
   hipLaunchKernelGGL(k_chan_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, decim, n_rb, c->chan_tab);
-  const dim3 grid((n_out + CH_NT - 1) / CH_NT, n_rb);
-  if (fmt == LCS_FMT_C64)
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_C64>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
-                       d_step, n_ch, (float2 *)d_out, n_out);
-  else if (fmt == LCS_FMT_IQ_S16)
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S16>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
-                       d_step, n_ch, (float2 *)d_out, n_out);
-  else
-    hipLaunchKernelGGL(k_channelize<LCS_FMT_IQ_S8>, grid, dim3(256), 0, c->stream, d_wide, (unsigned long long)n_in, decim, (const float *)c->chan_tab,
-                       d_step, n_ch, (float2 *)d_out, n_out);
+  const dim3 grid(lcs_chan_blocks(n_out), n_rb);
+  if (fmt == LCS_FMT_C64) chan_launch<LCS_FMT_C64>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
+  else if (fmt == LCS_FMT_IQ_S16) chan_launch<LCS_FMT_IQ_S16>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
+  else chan_launch<LCS_FMT_IQ_S8>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));
   c->chan_timed = true;
+  return LCS_OK;
+}
+
+// The 8-bit form: the float form (integer for up == 1, else rational) writes the context's scratch and the power partials, and
+// k_chan_quant_u8 turns the scratch into the caller's bytes.  The scratch grows on demand like the filter bank: one stream
+// synchronisation, because an earlier call's kernels may still read the old block.
+int lcs_launch_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift,
+                             int n_ch, void *d_out, uint32_t n_out, float *d_gain) {
+  const unsigned n_blocks = up == 1 ? lcs_chan_blocks(n_out) : lcs_chan_rate_blocks(n_out, up, down);
+  const size_t y_elems = (size_t)n_ch * n_out, part_elems = (size_t)n_ch * n_blocks;
+  int rc;
+  if (y_elems > c->chan_y.capacity() || part_elems > c->chan_part.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = c->chan_y.reserve(c, y_elems)) || (rc = c->chan_part.reserve(c, part_elems))) return rc;
+  if (up == 1) rc = lcs_launch_channelize(c, d_wide, fmt, n_in, fs_in, down, f_shift, n_ch, c->chan_y, n_out, c->chan_part);
+  else rc = lcs_launch_channelize_rational(c, d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, c->chan_y, n_out, c->chan_part);
+  if (rc) return rc;
+  const unsigned n_xb = std::max(1u, (n_out / 8 + CQ_GROUPS - 1) / CQ_GROUPS);
+  hipLaunchKernelGGL(k_chan_quant_u8, dim3((unsigned)n_ch * n_xb), dim3(256), 0, c->stream, (const float2 *)c->chan_y, (const float *)c->chan_part,
+                     (int)n_blocks, n_out, n_xb, (uint8_t *)d_out, d_gain);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));      // the call's time runs through its last kernel
   return LCS_OK;
 }
 

@@ -35,11 +35,14 @@ __global__ __launch_bounds__(256) void k_chan_rate_tables(const unsigned long lo
     tab[e] = cr_table_value(e, step, taps, n_ch, U, D, G);
 }
 
-template <int FMT>
+// POW (the 8-bit form): as k_channelize<FMT, true> -- the sum of |y|^2 per carrier over the outputs the workgroup stored goes to
+// part[carrier][blockIdx.x]: per lane over its wave's tiles in tile order, over the 32 columns by lane exchanges, over the waves
+// through LDS in wave order.
+template <int FMT, bool POW>
 __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict__ x, unsigned long long n_in, int U, int D, int G, int NI,
                                                          int xrows, const float *__restrict__ tab,
                                                          const unsigned long long *__restrict__ step, int n_ch,
-                                                         float2 *__restrict__ out, unsigned n_out) {
+                                                         float2 *__restrict__ out, unsigned n_out, float *__restrict__ part) {
   extern __shared__ float xs[];      // xrows rows of D samples, row stride 2 D + 1
   const unsigned long long i0 = (unsigned long long)blockIdx.x * (32u * NI);
   const int rb = blockIdx.y;
@@ -54,6 +57,11 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
     xs[o + 1] = v.y;
   }
   __syncthreads();
+  float pw[8];      // POW: |y|^2 of the lane's columns per carrier, index v / 2
+  if constexpr (POW) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pw[i] = 0.f;
+  }
   for (int t = wave; t < U * NI; t += 4) {      // uniform per wave
     const cr_tile tl = cr_tile_of(t, U, D);
     cr_f32x16 acc;
@@ -78,16 +86,44 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
     for (int v = 0; v < 16; v += 2) {      // registers v, v + 1: (re, im) of one carrier (cr_acc_row)
       const int ch = cr_acc_carrier(rb, v, lane);
       if (ch >= n_ch) continue;
-      out[(size_t)ch * n_out + col.m] = cr_rotate(acc[v], acc[v + 1], step[ch], col.nd);
+      const float2 y = cr_rotate(acc[v], acc[v + 1], step[ch], col.nd);
+      out[(size_t)ch * n_out + col.m] = y;
+      if constexpr (POW) pw[v >> 1] += y.x * y.x + y.y * y.y;
     }
+  }
+  if constexpr (POW) {
+    __shared__ float red[4][CR_CARRIERS];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float v = pw[i];
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);      // within the lane's half: the 32 columns of its carriers
+      if ((lane & 31) == 0) red[wave][cr_acc_row(2 * i, lane) >> 1] = v;
+    }
+    __syncthreads();
+    const int ch = rb * CR_CARRIERS + tid;
+    if (tid < CR_CARRIERS && ch < n_ch) part[(size_t)ch * gridDim.x + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
   }
 }
 
+unsigned lcs_chan_rate_blocks(uint32_t n_out, int up, int down) { return cr_grid_x(n_out, up, cr_geometry(up, down).NI); }
+
+template <int FMT>
+static void chan_rate_launch(lcs_ctx *c, dim3 grid, size_t lds_bytes, const void *d_wide, unsigned long long n_in, int up, int down, const cr_geom &geo,
+                             const unsigned long long *d_step, int n_ch, void *d_out, unsigned n_out, float *d_part) {
+  if (d_part)
+    hipLaunchKernelGGL((k_channelize_rate<FMT, true>), grid, dim3(256), lds_bytes, c->stream, d_wide, n_in, up, down, geo.G, geo.NI, geo.xrows,
+                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out, d_part);
+  else
+    hipLaunchKernelGGL((k_channelize_rate<FMT, false>), grid, dim3(256), lds_bytes, c->stream, d_wide, n_in, up, down, geo.G, geo.NI, geo.xrows,
+                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out, d_part);
+}
+
 int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
-                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out) {
+                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out, float *d_part) {
   const int Tg = 16 * down, n_rb = (n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
   const cr_geom geo = cr_geometry(up, down);
-  const int G = geo.G, ni = geo.NI, xrows = geo.xrows;
+  const int G = geo.G, ni = geo.NI;
   const size_t lds_bytes = geo.lds_bytes;
   const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 16 * 128 * sizeof(float);
   const size_t tab_floats = (size_t)n_rb * up * G * 256;
@@ -115,15 +151,9 @@ int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint
   const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
   hipLaunchKernelGGL(k_chan_rate_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, up, down, G, n_rb, c->chan_tab);
   const dim3 grid(cr_grid_x(n_out, up, ni), n_rb);
-  if (fmt == LCS_FMT_C64)
-    hipLaunchKernelGGL(k_channelize_rate<LCS_FMT_C64>, grid, dim3(256), lds_bytes, c->stream, d_wide, (unsigned long long)n_in, up, down, G, ni, xrows,
-                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out);
-  else if (fmt == LCS_FMT_IQ_S16)
-    hipLaunchKernelGGL(k_channelize_rate<LCS_FMT_IQ_S16>, grid, dim3(256), lds_bytes, c->stream, d_wide, (unsigned long long)n_in, up, down, G, ni, xrows,
-                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out);
-  else
-    hipLaunchKernelGGL(k_channelize_rate<LCS_FMT_IQ_S8>, grid, dim3(256), lds_bytes, c->stream, d_wide, (unsigned long long)n_in, up, down, G, ni, xrows,
-                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out);
+  if (fmt == LCS_FMT_C64) chan_rate_launch<LCS_FMT_C64>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
+  else if (fmt == LCS_FMT_IQ_S16) chan_rate_launch<LCS_FMT_IQ_S16>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
+  else chan_rate_launch<LCS_FMT_IQ_S8>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));
   c->chan_timed = true;

@@ -360,6 +360,8 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<char> chan_par;            // [n_ch] phase steps, then the taps
   DevBuf<float> chan_tab;           // the filter bank in A-operand order
   PinnedBuf<char> chan_hpin[2];     // page-locked parameter slots, used in turn
+  DevBuf<float2> chan_y;            // lcs_channelize_u8: the float outputs [n_ch][n_out] its bytes are made from
+  DevBuf<float> chan_part;          // lcs_channelize_u8: [n_ch][workgroups along the outputs] sums of |y|^2
   int chan_slot = 0;
   bool chan_timed = false;
   // results of a batch, compacted on the device (k_pack_results): [8 ints header][n_buf counts][records]; h_res = its page-locked mirror

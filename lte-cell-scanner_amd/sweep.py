@@ -75,7 +75,7 @@ def dedup(detected: Sequence[Sequence[dict]]) -> List[dict]:
 
 
 def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, fc_centre: float, carriers, f_search_set,
-                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None):
+                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64"):
     """A band search from ONE wideband capture resident in HBM (n_in samples of fmt at fs_in, centred on fc_centre): the
     carriers (absolute Hz, e.g. fc_search_set(...)) are channelized `chunk` at a time (Searcher.channelize: mix, low-pass,
     decimate by decim) into a torch buffer this function owns, and every chunk goes through the full chain as a
@@ -84,7 +84,10 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     batch needs an even n_cap); 153584 = the most an 80 ms capture gives, rounded down: 15 combining windows as for a
     dongle buffer.  rate = (up, down) takes a capture at any rate with fs_in * up / down = 1.92 Msps (20 Msps: (12, 125))
     through Searcher.channelize_rational instead: decim is ignored, fs_programmed = fs_in * up / down, and n_out -- unless
-    given -- is the largest even count the capture holds (without rate it is 153584).  Returns one list of cells (LcsCell)
+    given -- is the largest even count the capture holds (without rate it is 153584).  out = "u8" channelizes into bytes
+    (Searcher.channelize_u8: every carrier scaled by a power of two of its own, component rms 16..32 codes) and hands the
+    chunks over as FMT_IQ_U8 batches, which take the int8 correlation kernel and a quarter of the memory; a byte batch takes
+    any n_cap, so with a rate n_out is then all the capture holds, odd or even.  Returns one list of cells (LcsCell)
     per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's."""
     import torch
     from . import capi
@@ -93,24 +96,39 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
         up, down = int(rate[0]), int(rate[1])
         fs_out = float(fs_in) * up / down
         if n_out is None:      # what the capture holds: (n_out - 1) * down + 16 * down <= n_in * up
-            n_out = ((int(n_in) * up - 16 * down) // down + 1) & ~1
+            n_out = (int(n_in) * up - 16 * down) // down + 1
+            if out != "u8":
+                n_out &= ~1
     else:
         fs_out = float(fs_in) / int(decim)
         if n_out is None:
             n_out = 153584
+    if out not in ("c64", "u8"):
+        raise ValueError(f"search_wideband: out must be 'c64' or 'u8', not {out!r}")
     chunk = max(1, min(int(chunk), carriers.size))
     dev = getattr(searcher, "device", -1)
-    buf = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device()))
-    out = []
+    tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
+    if out == "u8":
+        buf = torch.empty((chunk, int(n_out), 2), dtype=torch.uint8, device=tdev)
+        up8, down8 = (up, down) if rate is not None else (1, int(decim))
+        cells = []
+        for a in range(0, carriers.size, chunk):
+            fc = carriers[a:a + chunk]
+            searcher.channelize_u8(d_wide_ptr, fmt, n_in, fs_in, up8, down8, fc - float(fc_centre), buf.data_ptr(), n_out)
+            cells += searcher.search_batch(buf.data_ptr(), capi.FMT_IQ_U8, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
+                                           max_cells_per_buf)
+        return cells
+    buf = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=tdev)
+    cells = []
     for a in range(0, carriers.size, chunk):
         fc = carriers[a:a + chunk]
         if rate is not None:
             searcher.channelize_rational(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
         else:
             searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, decim, fc - float(fc_centre), buf.data_ptr(), n_out)
-        out += searcher.search_batch(buf.data_ptr(), capi.FMT_C64, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
-                                     max_cells_per_buf)
-    return out
+        cells += searcher.search_batch(buf.data_ptr(), capi.FMT_C64, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
+                                       max_cells_per_buf)
+    return cells
 
 
 def _all_gather_bytes(arr: np.ndarray, dist, device, world: int) -> List[np.ndarray]:

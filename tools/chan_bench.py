@@ -13,8 +13,15 @@ rate; the target is a <= 0.25 b.  Writes one JSON document (--out) and prints it
 on those buffers as batches of at most 128.  Its record goes under the key "rational" of the same document; the integer
 record at the top level stays as it is (and a plain run keeps the "rational" record).
 
+--u8 compares the two pipelines of a band search on the integer record's carriers (256 carriers, decim 16, s16, n_f = 31), both
+in this one process on one box, medians as above: (a) lcs_channelize_u8, then search_batch on the bytes (LCS_FMT_IQ_U8: the int8
+correlation kernel); (b) lcs_channelize, then search_batch on the floats.  Each pipeline is timed by HIP events from in front of
+the channelizer to behind the second batch's collect.  Its record -- both times, their ratio, the channelizer's share of (a)
+against the search behind it, the new kernels' resources -- goes under the key "u8"; everything else in the document stays.
+
     python tools/chan_bench.py --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --rate 12/125 --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --u8 --out profiles/channelizer/chan_bench.json
 """
 import argparse
 import importlib.util
@@ -51,7 +58,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cells", type=int, default=8, help="cells planted across the band (every 32nd carrier)")
     ap.add_argument("--rate", default=None, metavar="UP/DOWN", help="measure lcs_channelize_rational at this rate change, e.g. 12/125")
+    ap.add_argument("--u8", action="store_true", help="time lcs_channelize_u8 + search on bytes against lcs_channelize + search on floats")
     args = ap.parse_args()
+    if args.u8 and args.rate:
+        ap.error("--u8 runs on the integer record's carriers: it takes no --rate")
     rate = tuple(int(v) for v in args.rate.split("/")) if args.rate else None
     import torch
     from __graft_entry__ import load_package
@@ -79,6 +89,8 @@ def main():
     torch.cuda.synchronize(dev)
     samples, stop = [], threading.Event()
     th = threading.Thread(target=sclk_sampler, args=(args.device, samples, stop), daemon=True)
+    if args.u8:
+        return bench_u8(args, pkg, torch, dev, d_wide, d_out, carriers - FC0, carriers, f, n_in, fs_in, D, N_CH, N_OUT, samples, stop, th)
     with pkg.Searcher(args.device) as s:
         stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
         th.start()
@@ -134,6 +146,64 @@ def main():
         doc = dict(res, **({"rational": old["rational"]} if "rational" in old else {}))
     with open(args.out, "w") as fh:
         json.dump(doc, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+def bench_u8(args, pkg, torch, dev, d_wide, d_c64, shifts, carriers, f, n_in, fs_in, D, N_CH, N_OUT, samples, stop, th):
+    d_u8 = torch.empty((N_CH, N_OUT, 2), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    t = {"u8": dict(total=[], chan=[]), "c64": dict(total=[], chan=[])}
+    cells = {}
+    with pkg.Searcher(args.device) as s:
+        stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
+        th.start()
+        for i in range(args.warmup + args.reps):
+            for mode in ("u8", "c64"):      # interleaved: both pipelines see the same clocks
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                if mode == "u8":
+                    s.channelize_u8(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, 1, D, shifts, d_u8.data_ptr(), N_OUT)
+                    buf, fmt = d_u8, pkg.FMT_IQ_U8
+                else:
+                    s.channelize(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, D, shifts, d_c64.data_ptr(), N_OUT)
+                    buf, fmt = d_c64, pkg.FMT_C64
+                n = 0
+                for h in range(N_CH // 128):
+                    sl = slice(128 * h, 128 * h + 128)
+                    n += sum(len(c) for c in s.search_batch(buf[128 * h].data_ptr(), fmt, 128, N_OUT, f, carriers[sl], carriers[sl], 1.92e6, pkg.STAGE_FULL))
+                e1.record(stream)
+                e1.synchronize()
+                t[mode]["total"].append(e0.elapsed_time(e1))
+                t[mode]["chan"].append(s.last_channelize_ms())
+                cells[mode] = n
+        stop.set()
+        th.join(timeout=10)
+    med = lambda v: float(np.median(v[args.warmup:]))
+    a, b, a_chan, b_chan = med(t["u8"]["total"]), med(t["c64"]["total"]), med(t["u8"]["chan"]), med(t["c64"]["chan"])
+    spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "tools", "code_objects.py"))
+    co = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(co)
+    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items()
+          if "k_chan_quant_u8" in k or ("k_channelize" in k and "Lb1E" in k)}
+    res = {"a_u8_pipeline_ms": a, "b_c64_pipeline_ms": b, "ratio_a_over_b": a / b, "u8_is_faster": bool(a < b),
+           "a_channelize_u8_ms": a_chan, "a_search_ms": a - a_chan, "a_channelizer_share_of_search": a_chan / (a - a_chan), "target_share": 0.25,
+           "meets_target": bool(a_chan <= 0.25 * (a - a_chan)), "b_channelize_ms": b_chan, "b_search_ms": b - b_chan,
+           "config": {"decim": D, "fmt": "s16", "n_ch": N_CH, "n_in": n_in, "n_out": N_OUT, "raster_hz": 100e3, "n_f": int(f.size), "batches": "2 x 128",
+                      "stage": "full", "reps": args.reps, "warmup": args.warmup, "cells_planted": args.cells, "cells_decoded_u8": cells["u8"],
+                      "cells_decoded_c64": cells["c64"]},
+           "a_ms_min_max": [float(min(t["u8"]["total"][args.warmup:])), float(max(t["u8"]["total"][args.warmup:]))],
+           "b_ms_min_max": [float(min(t["c64"]["total"][args.warmup:])), float(max(t["c64"]["total"][args.warmup:]))],
+           "sclk_mhz_median": (sorted(samples)[len(samples) // 2] if samples else None), "sclk_samples": len(samples),
+           "device": torch.cuda.get_device_name(dev), "kernels": ks}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    try:
+        with open(args.out) as fh:
+            old = json.load(fh)
+    except (OSError, ValueError):
+        old = {}
+    with open(args.out, "w") as fh:
+        json.dump(dict(old, u8=res), fh, indent=1)
         fh.write("\n")
     print(json.dumps(res))
 
