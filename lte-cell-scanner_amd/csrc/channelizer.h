@@ -1,25 +1,82 @@
-// channelizer.h -- the wideband channelizer's launchers (channelizer.hip: integer decimation and the 8-bit output stage;
-// channelizer_rate.hip: rational rate change up / down).  Its per-context state (parameter and filter-bank buffers, page-locked
-// slots, events, the float scratch of the 8-bit form) are the chan_* / ev_chan* members of the context, shared by all forms.
+// channelizer.h -- the wideband channelizer: what its entry points (lcs_api.hip) hand down as one ChanCall, the rules a call
+// is refused by, the one launcher (channelizer.hip: the integer form up == 1, the 8-bit output stage; channelizer_rate.hip: the
+// rational form's kernels) and the index arithmetic both forms' kernels share with the host twins under tests/host.  The
+// per-context state (parameter and filter-bank buffers, page-locked slots, events, the float scratch of the 8-bit form) are the
+// chan_* / ev_chan* members of the context, shared by all forms.
 #pragma once
 #include "lcs_internal.h"
 #include <cmath>
 
+// One call as every layer below the entry points sees it: fs_out = fs_in * up / down, and lcs_channelize is up = 1, down = decim
+struct ChanCall {
+  const void *d_wide;
+  int fmt;
+  uint64_t n_in;
+  double fs_in;
+  int up, down;
+  const double *f_shift;
+  int n_ch;
+  void *d_out;
+  uint32_t n_out;
+};
+
+// What the entry points refuse, in the order they look: the text of the first rule a call breaks, nullptr for a call that may be
+// launched.  CHAN_DECIM: the rate rule of lcs_channelize; CHAN_RATE: those of lcs_channelize_rational and lcs_channelize_u8;
+// CHAN_RATE_ONLY stops behind them (lcs_channelize_rational hands a call with up == 1 to lcs_channelize there).
+enum ChanRules { CHAN_DECIM, CHAN_RATE, CHAN_RATE_ONLY };
+static inline const char *chan_refusal(const ChanCall &a, ChanRules rules) {
+  if (!a.d_wide || !a.f_shift || !a.d_out) return "null pointer";
+  if (rules == CHAN_DECIM) {
+    if (a.down < 2 || a.down > 16) return "decim outside 2..16";
+  } else {
+    if (a.down < 2 || a.down > 128) return "down outside 2..128";
+    if (a.up < 1 || a.up > 127) return "up outside 1..127";
+    if (a.up >= a.down) return "up >= down: interpolation is not supported";
+    if (a.down > 16 * a.up) return "down / up > 16";
+    for (int p = a.up, q = a.down; q;) {
+      const int r = p % q;
+      p = q, q = r;
+      if (!q && p != 1) return "up and down have a common factor";
+    }
+    if (rules == CHAN_RATE_ONLY) return nullptr;
+  }
+  if (a.n_ch < 1) return "n_ch < 1";
+  if (a.n_out < 1) return "n_out < 1";
+  if (!(a.fs_in > 0) || !std::isfinite(a.fs_in)) return "fs_in is not a positive rate";
+  // the last output's window ends at sample floor(((n_out-1) down + 16 down - 1) / up): at up == 1 the bound is (n_out-1) decim + 16 decim
+  if (a.n_in < (((uint64_t)a.n_out - 1) * a.down + 16ull * a.down - 1) / a.up + 1)
+    return a.up == 1 ? "n_in < (n_out-1)*decim + 16*decim: the capture is too short for n_out outputs"
+                     : "n_in < floor(((n_out-1)*down + 16*down - 1) / up) + 1: the capture is too short for n_out outputs";
+  if (a.fmt != LCS_FMT_C64 && a.fmt != LCS_FMT_IQ_S8 && a.fmt != LCS_FMT_IQ_S16) return "unknown sample format";
+  for (int k = 0; k < a.n_ch; ++k)
+    if (!(std::fabs(a.f_shift[k]) <= 0.5 * a.fs_in)) return "|f_shift| > fs_in/2";
+  if (reinterpret_cast<uintptr_t>(a.d_out) & 15) return "d_out is not 16-byte aligned";
+  const uintptr_t in_align = a.fmt == LCS_FMT_C64 ? 7 : a.fmt == LCS_FMT_IQ_S16 ? 3 : 1;
+  if (reinterpret_cast<uintptr_t>(a.d_wide) & in_align) return "d_wide is not aligned to its sample size";
+  return nullptr;
+}
+
 void lcs_chan_taps(int decim, double *taps /*[16*decim]*/);      // any decim >= 2
 unsigned long long lcs_chan_step(double f_shift, double fs_in);
-int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot);          // the next page-locked parameter slot, free to be written
-// d_part == nullptr: the float forms.  Otherwise [n_ch][workgroups along the outputs] floats: every workgroup leaves the sum of
-// |y|^2 of its outputs per carrier there (lcs_chan_blocks / lcs_chan_rate_blocks say how many there are per carrier).
-int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
-                          int n_ch, void *d_out, uint32_t n_out, float *d_part = nullptr);
-int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
-                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out, float *d_part = nullptr);
-unsigned lcs_chan_blocks(uint32_t n_out);
-unsigned lcs_chan_rate_blocks(uint32_t n_out, int up, int down);
+// d_part == nullptr: the float forms.  Otherwise [n_ch][lcs_chan_blocks(call)] floats: every workgroup along the outputs leaves
+// the sum of |y|^2 of its outputs per carrier there.
+int lcs_launch_channelize(lcs_ctx *c, const ChanCall &a, float *d_part);
+unsigned lcs_chan_blocks(const ChanCall &a);
 // lcs_channelize_u8: the float form into the context's scratch with the power partials, then k_chan_quant_u8 (channelizer.hip)
-int lcs_launch_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift,
-                             int n_ch, void *d_out, uint32_t n_out, float *d_gain);
+int lcs_launch_channelize_u8(lcs_ctx *c, const ChanCall &a, float *d_gain);
 int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context's last channelizer launch (any form)
+
+// The kernels are templates over the capture's format and POW (the power partials of the 8-bit form):
+// chan_by_form(fmt, pow, [&](auto fmt, auto pow) { launch k<decltype(fmt)::value, decltype(pow)::value> }) picks the instantiation.
+template <class F> inline void chan_by_form(int fmt, bool pow, F &&launch) {
+  auto by_pow = [&](auto f) {
+    if (pow) launch(f, std::true_type{});
+    else launch(f, std::false_type{});
+  };
+  if (fmt == LCS_FMT_C64) by_pow(std::integral_constant<int, LCS_FMT_C64>{});
+  else if (fmt == LCS_FMT_IQ_S16) by_pow(std::integral_constant<int, LCS_FMT_IQ_S16>{});
+  else by_pow(std::integral_constant<int, LCS_FMT_IQ_S8>{});
+}
 
 // ---- the 8-bit output's rule (include/lcs.h, lcs_channelize_u8): k_chan_quant_u8 and tests/host/chan_u8_host.cpp call these two.
 // The exponent e of a carrier of mean power P = mean |y|^2: the integer with 16^2 < 4^e P / 2 <= 32^2, i.e. 2^9 < 4^e P <= 2^11;
@@ -50,9 +107,10 @@ __host__ __device__ __forceinline__ float2 chan_sample(const void *x, unsigned l
   return make_float2((float)(int)(int8_t)(p & 255u) * (1.f / 128.f), (float)(int)(int8_t)(p >> 8) * (1.f / 128.f));
 }
 
-// ---- the rational form's bookkeeping (channelizer_rate.hip): where every tap, sample and output goes for a rate U / D.  The
-// kernels and the launcher decide by these, and tests/host/chan_rate_host.cpp walks a workgroup on the CPU with the same ones
-// (a host build supplies sinpi / cospi / sinpif / cospif itself where its libm has none).
+// ---- the kernels' bookkeeping: where every tap, sample and output goes for a rate U / D.  The kernels and the launcher decide by
+// these -- the rational form by all of them, k_channelize (U = 1, two tiles per wave) by its staging offset, its accumulator map,
+// its rotation and its power partials -- and tests/host/chan_rate_host.cpp walks a workgroup on the CPU with the same ones (a
+// host build supplies sinpi / cospi / sinpif / cospif itself where its libm has none).
 #define CR_CARRIERS 16                 // carriers per A tile (32 rows)
 #define CR_LDS_MAX (48 * 1024)         // NI grows only while the staged samples stay below this
 
@@ -154,4 +212,21 @@ __host__ __device__ __forceinline__ float2 cr_rotate(float re, float im, unsigne
   const float ht = (float)(int)(unsigned)(ph >> 32) * 0x1p-31f;      // half-turns of the carrier phase at sample s_q + i D
   const float sn = sinpif(ht), cs = cospif(ht);
   return make_float2(re * cs + im * sn, im * cs - re * sn);
+}
+// POW (the 8-bit form): pw[i] is the lane's sum of |y|^2 over the outputs it stored for the carrier of its registers 2 i, 2 i + 1.
+// The workgroup's sum per carrier goes to part[carrier][blockIdx.x]: over the 32 columns by a butterfly of lane exchanges, over
+// the four waves through LDS in wave order -- one fixed order, no atomics, so two runs give the same bits.
+__device__ __forceinline__ void cr_power_partials(const float (&pw)[8], int rb, int n_ch, float *__restrict__ part) {
+  __shared__ float red[4][CR_CARRIERS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float v = pw[i];
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);      // within the lane's half: the 32 columns of its carriers
+    if ((lane & 31) == 0) red[wave][cr_acc_row(2 * i, lane) >> 1] = v;
+  }
+  __syncthreads();
+  const int ch = rb * CR_CARRIERS + tid;
+  if (tid < CR_CARRIERS && ch < n_ch) part[(size_t)ch * gridDim.x + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }

@@ -25,7 +25,6 @@
 typedef float ch_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ch_f32x4 __attribute__((ext_vector_type(4)));
 
-#define CH_CARRIERS 16                 // carriers per A tile (32 rows)
 #define CH_NT 256                      // outputs per workgroup: 4 waves x 2 tiles x 32 columns
 #define CH_XROWS (CH_NT + 15)          // LDS rows of D samples: the windows of CH_NT outputs span (CH_NT + 15) D samples
 #define CH_SMAX (2 * 16 + 1)           // row stride in floats at D = 16
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *_
     const size_t rest = e >> 8;
     const int s4 = (int)(rest % q4), rb = (int)(rest / q4);
     const int s = 4 * s4 + i, r = l & 31, c = l >> 5;
-    const int ch = rb * CH_CARRIERS + (r >> 1), ri = r & 1;
+    const int ch = rb * CR_CARRIERS + (r >> 1), ri = r & 1;
     float v = 0.f;
     if (ch < n_ch) {
       const unsigned long long ph = step[ch] * (unsigned long long)s;
@@ -87,8 +86,7 @@ __global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *_
 }
 
 // POW (the 8-bit form, lcs_channelize_u8): the workgroup also leaves, per carrier, the sum of |y|^2 over the outputs it stored in
-// part[carrier][blockIdx.x] -- per lane over its two tiles, over the 32 columns by a butterfly of lane exchanges, over the four
-// waves through LDS in wave order: one fixed order, no atomics, so two runs give the same bits.
+// part[carrier][blockIdx.x] -- per lane over its two tiles, then cr_power_partials.
 template <int FMT, bool POW>
 __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, unsigned long long n_in, int D,
                                                     const float *__restrict__ tab, const unsigned long long *__restrict__ step,
@@ -101,11 +99,11 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
   // the samples [m0 D, (m0 + CH_XROWS) D) as floats; beyond the capture's end zeros (only outputs >= n_out read them)
   const unsigned long long n0 = (unsigned long long)m0 * D;
   for (int idx = tid; idx < CH_XROWS * D; idx += 256) {
-    const int row = idx / D, p = idx - row * D;
+    const int o = cr_stage_offset(idx, D);
     const unsigned long long n = n0 + (unsigned)idx;
     const float2 v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
-    xs[row * S + 2 * p] = v.x;
-    xs[row * S + 2 * p + 1] = v.y;
+    xs[o] = v.x;
+    xs[o + 1] = v.y;
   }
   __syncthreads();
   ch_f32x16 acc0, acc1;
@@ -127,9 +125,7 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
       if (++p == D) { p = 0; ++q; }
     }
   }
-  // register v of a lane: row (v & 3) + 8 (v >> 2) + 4 (lane >> 5) of the tile, column lane & 31; row = 2 carrier + (re | im)
-  const int h = lane >> 5;
-  float pw[8];      // POW: |y|^2 of the lane's column per carrier 4 a + 2 h + bb, index 2 a + bb
+  float pw[8];      // POW: |y|^2 of the lane's columns per carrier, index v / 2
   if constexpr (POW) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) pw[i] = 0.f;
@@ -140,35 +136,15 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
     if (m >= n_out) continue;
     const unsigned long long nd = (unsigned long long)m * (unsigned)D;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-#pragma unroll
-      for (int bb = 0; bb < 2; ++bb) {
-        const int ch = rb * CH_CARRIERS + 4 * a + 2 * h + bb;
-        if (ch >= n_ch) continue;
-        const unsigned long long ph = step[ch] * nd;
-        const float ht = (float)(int)(unsigned)(ph >> 32) * 0x1p-31f;      // half-turns of the carrier phase at sample m D
-        const float sn = sinpif(ht), cs = cospif(ht);
-        const float re = t ? acc1[4 * a + 2 * bb] : acc0[4 * a + 2 * bb];
-        const float im = t ? acc1[4 * a + 2 * bb + 1] : acc0[4 * a + 2 * bb + 1];
-        const float2 y = make_float2(re * cs + im * sn, im * cs - re * sn);
-        out[(size_t)ch * n_out + m] = y;
-        if constexpr (POW) pw[2 * a + bb] += y.x * y.x + y.y * y.y;
-      }
+    for (int v = 0; v < 16; v += 2) {      // registers v, v + 1: (re, im) of one carrier (cr_acc_row)
+      const int ch = cr_acc_carrier(rb, v, lane);
+      if (ch >= n_ch) continue;
+      const float2 y = cr_rotate(t ? acc1[v] : acc0[v], t ? acc1[v + 1] : acc0[v + 1], step[ch], nd);
+      out[(size_t)ch * n_out + m] = y;
+      if constexpr (POW) pw[v >> 1] += y.x * y.x + y.y * y.y;
     }
   }
-  if constexpr (POW) {
-    __shared__ float red[4][CH_CARRIERS];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = pw[i];
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);      // within the lane's half: the 32 columns of its carriers
-      if ((lane & 31) == 0) red[wave][4 * (i >> 1) + 2 * h + (i & 1)] = v;
-    }
-    __syncthreads();
-    const int ch = rb * CH_CARRIERS + tid;
-    if (tid < CH_CARRIERS && ch < n_ch) part[(size_t)ch * gridDim.x + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-  }
+  if constexpr (POW) cr_power_partials(pw, rb, n_ch, part);
 }
 
 // The 8-bit output (include/lcs.h, lcs_channelize_u8): carrier ch's floats y[ch][n_out] -> bytes out[ch][n_out][2].  Every workgroup
@@ -231,24 +207,21 @@ int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
   return c->chan_hpin[k].reserve(c, bytes);
 }
 
-unsigned lcs_chan_blocks(uint32_t n_out) { return (n_out + CH_NT - 1) / CH_NT; }
-
-template <int FMT>
-static void chan_launch(lcs_ctx *c, dim3 grid, const void *d_wide, unsigned long long n_in, int decim, const unsigned long long *d_step, int n_ch,
-                        void *d_out, unsigned n_out, float *d_part) {
-  if (d_part)
-    hipLaunchKernelGGL((k_channelize<FMT, true>), grid, dim3(256), 0, c->stream, d_wide, n_in, decim, (const float *)c->chan_tab, d_step, n_ch,
-                       (float2 *)d_out, n_out, d_part);
-  else
-    hipLaunchKernelGGL((k_channelize<FMT, false>), grid, dim3(256), 0, c->stream, d_wide, n_in, decim, (const float *)c->chan_tab, d_step, n_ch,
-                       (float2 *)d_out, n_out, d_part);
+// workgroups along the outputs
+unsigned lcs_chan_blocks(const ChanCall &a) {
+  return a.up == 1 ? (a.n_out + CH_NT - 1) / CH_NT : cr_grid_x(a.n_out, a.up, cr_geometry(a.up, a.down).NI);
 }
 
-int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift,
-                          int n_ch, void *d_out, uint32_t n_out, float *d_part) {
-  const int T = 16 * decim, n_rb = (n_ch + CH_CARRIERS - 1) / CH_CARRIERS;
-  const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 256 * sizeof(float);
-  const size_t tab_floats = (size_t)n_rb * 64 * T;
+void lcs_chan_rate_enqueue(lcs_ctx *c, const ChanCall &a, const cr_geom &geo, dim3 tab_grid, dim3 grid, const unsigned long long *d_step,
+                           const float *d_taps, float *d_part);      // channelizer_rate.hip
+
+// Every form's launch: parameters up, the form's table kernel, its main kernel, the two events the call's time is taken between.
+// The filter bank has 256 up G floats per row block in both forms (G = 4 down at up == 1: the 16 down taps).
+int lcs_launch_channelize(lcs_ctx *c, const ChanCall &a, float *d_part) {
+  const int T = 16 * a.down, n_ch = a.n_ch, n_rb = (n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
+  const cr_geom geo = cr_geometry(a.up, a.down);
+  const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 16 * 128 * sizeof(float);
+  const size_t tab_floats = (size_t)n_rb * a.up * geo.G * 256;
   int k = 0, rc;
   if (par_bytes > c->chan_par.capacity() || tab_floats > c->chan_tab.capacity())      // grown on demand (earlier calls may still read the old ones)
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -260,44 +233,47 @@ int lcs_launch_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in
   if ((rc = lcs_chan_slot(c, par_bytes, &k))) return rc;
   unsigned long long *h_step = reinterpret_cast<unsigned long long *>(c->chan_hpin[k].get());
   float *h_taps = (float *)(h_step + n_ch);
-  for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);
-  double taps[256];
-  lcs_chan_taps(decim, taps);
+  for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(a.f_shift[i], a.fs_in);
+  double taps[16 * 128];
+  lcs_chan_taps(a.down, taps);
   for (int t = 0; t < T; ++t) h_taps[t] = (float)taps[t];
-  const size_t up = (size_t)n_ch * sizeof(unsigned long long) + T * sizeof(float);
-  HIPCHK(c, hipMemcpyAsync(c->chan_par, h_step, up, hipMemcpyHostToDevice, c->stream));
+  const size_t upl = (size_t)n_ch * sizeof(unsigned long long) + T * sizeof(float);
+  HIPCHK(c, hipMemcpyAsync(c->chan_par, h_step, upl, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_chan_slot[k], c->stream));
   const unsigned long long *d_step = reinterpret_cast<const unsigned long long *>(c->chan_par.get());
   const float *d_taps = (const float *)(d_step + n_ch);
   HIPCHK(c, hipEventRecord(c->ev_chan0, c->stream));
-  const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_chan_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, decim, n_rb, c->chan_tab);
-  const dim3 grid(lcs_chan_blocks(n_out), n_rb);
-  if (fmt == LCS_FMT_C64) chan_launch<LCS_FMT_C64>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
-  else if (fmt == LCS_FMT_IQ_S16) chan_launch<LCS_FMT_IQ_S16>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
-  else chan_launch<LCS_FMT_IQ_S8>(c, grid, d_wide, n_in, decim, d_step, n_ch, d_out, n_out, d_part);
+  const dim3 tab_grid((unsigned)std::min<size_t>((tab_floats + 255) / 256, 2048)), grid(lcs_chan_blocks(a), n_rb);
+  if (a.up == 1) {
+    hipLaunchKernelGGL(k_chan_tables, tab_grid, dim3(256), 0, c->stream, d_step, d_taps, n_ch, a.down, n_rb, c->chan_tab);
+    chan_by_form(a.fmt, d_part != nullptr, [&](auto fmt, auto pow) {
+      hipLaunchKernelGGL((k_channelize<decltype(fmt)::value, decltype(pow)::value>), grid, dim3(256), 0, c->stream, a.d_wide,
+                         (unsigned long long)a.n_in, a.down, (const float *)c->chan_tab, d_step, n_ch, (float2 *)a.d_out, (unsigned)a.n_out, d_part);
+    });
+  } else {
+    lcs_chan_rate_enqueue(c, a, geo, tab_grid, grid, d_step, d_taps, d_part);
+  }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));
   c->chan_timed = true;
   return LCS_OK;
 }
 
-// The 8-bit form: the float form (integer for up == 1, else rational) writes the context's scratch and the power partials, and
-// k_chan_quant_u8 turns the scratch into the caller's bytes.  The scratch grows on demand like the filter bank: one stream
-// synchronisation, because an earlier call's kernels may still read the old block.
-int lcs_launch_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift,
-                             int n_ch, void *d_out, uint32_t n_out, float *d_gain) {
-  const unsigned n_blocks = up == 1 ? lcs_chan_blocks(n_out) : lcs_chan_rate_blocks(n_out, up, down);
-  const size_t y_elems = (size_t)n_ch * n_out, part_elems = (size_t)n_ch * n_blocks;
+// The 8-bit form: the float form writes the context's scratch and the power partials, and k_chan_quant_u8 turns the scratch into
+// the caller's bytes.  The scratch grows on demand like the filter bank: one stream synchronisation, because an earlier call's
+// kernels may still read the old block.
+int lcs_launch_channelize_u8(lcs_ctx *c, const ChanCall &a, float *d_gain) {
+  const unsigned n_blocks = lcs_chan_blocks(a), n_out = a.n_out;
+  const size_t y_elems = (size_t)a.n_ch * n_out, part_elems = (size_t)a.n_ch * n_blocks;
   int rc;
   if (y_elems > c->chan_y.capacity() || part_elems > c->chan_part.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
   if ((rc = c->chan_y.reserve(c, y_elems)) || (rc = c->chan_part.reserve(c, part_elems))) return rc;
-  if (up == 1) rc = lcs_launch_channelize(c, d_wide, fmt, n_in, fs_in, down, f_shift, n_ch, c->chan_y, n_out, c->chan_part);
-  else rc = lcs_launch_channelize_rational(c, d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, c->chan_y, n_out, c->chan_part);
-  if (rc) return rc;
+  ChanCall y = a;
+  y.d_out = c->chan_y;
+  if ((rc = lcs_launch_channelize(c, y, c->chan_part))) return rc;
   const unsigned n_xb = std::max(1u, (n_out / 8 + CQ_GROUPS - 1) / CQ_GROUPS);
-  hipLaunchKernelGGL(k_chan_quant_u8, dim3((unsigned)n_ch * n_xb), dim3(256), 0, c->stream, (const float2 *)c->chan_y, (const float *)c->chan_part,
-                     (int)n_blocks, n_out, n_xb, (uint8_t *)d_out, d_gain);
+  hipLaunchKernelGGL(k_chan_quant_u8, dim3((unsigned)a.n_ch * n_xb), dim3(256), 0, c->stream, (const float2 *)c->chan_y, (const float *)c->chan_part,
+                     (int)n_blocks, n_out, n_xb, (uint8_t *)a.d_out, d_gain);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));      // the call's time runs through its last kernel
   return LCS_OK;

@@ -36,8 +36,7 @@ __global__ __launch_bounds__(256) void k_chan_rate_tables(const unsigned long lo
 }
 
 // POW (the 8-bit form): as k_channelize<FMT, true> -- the sum of |y|^2 per carrier over the outputs the workgroup stored goes to
-// part[carrier][blockIdx.x]: per lane over its wave's tiles in tile order, over the 32 columns by lane exchanges, over the waves
-// through LDS in wave order.
+// part[carrier][blockIdx.x]: per lane over its wave's tiles in tile order, then cr_power_partials.
 template <int FMT, bool POW>
 __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict__ x, unsigned long long n_in, int U, int D, int G, int NI,
                                                          int xrows, const float *__restrict__ tab,
@@ -91,71 +90,16 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
       if constexpr (POW) pw[v >> 1] += y.x * y.x + y.y * y.y;
     }
   }
-  if constexpr (POW) {
-    __shared__ float red[4][CR_CARRIERS];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float v = pw[i];
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o);      // within the lane's half: the 32 columns of its carriers
-      if ((lane & 31) == 0) red[wave][cr_acc_row(2 * i, lane) >> 1] = v;
-    }
-    __syncthreads();
-    const int ch = rb * CR_CARRIERS + tid;
-    if (tid < CR_CARRIERS && ch < n_ch) part[(size_t)ch * gridDim.x + blockIdx.x] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-  }
+  if constexpr (POW) cr_power_partials(pw, rb, n_ch, part);
 }
 
-unsigned lcs_chan_rate_blocks(uint32_t n_out, int up, int down) { return cr_grid_x(n_out, up, cr_geometry(up, down).NI); }
-
-template <int FMT>
-static void chan_rate_launch(lcs_ctx *c, dim3 grid, size_t lds_bytes, const void *d_wide, unsigned long long n_in, int up, int down, const cr_geom &geo,
-                             const unsigned long long *d_step, int n_ch, void *d_out, unsigned n_out, float *d_part) {
-  if (d_part)
-    hipLaunchKernelGGL((k_channelize_rate<FMT, true>), grid, dim3(256), lds_bytes, c->stream, d_wide, n_in, up, down, geo.G, geo.NI, geo.xrows,
-                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out, d_part);
-  else
-    hipLaunchKernelGGL((k_channelize_rate<FMT, false>), grid, dim3(256), lds_bytes, c->stream, d_wide, n_in, up, down, geo.G, geo.NI, geo.xrows,
-                       (const float *)c->chan_tab, d_step, n_ch, (float2 *)d_out, n_out, d_part);
-}
-
-int lcs_launch_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
-                                   const double *f_shift, int n_ch, void *d_out, uint32_t n_out, float *d_part) {
-  const int Tg = 16 * down, n_rb = (n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
-  const cr_geom geo = cr_geometry(up, down);
-  const int G = geo.G, ni = geo.NI;
-  const size_t lds_bytes = geo.lds_bytes;
-  const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + 16 * 128 * sizeof(float);
-  const size_t tab_floats = (size_t)n_rb * up * G * 256;
-  int k = 0, rc;
-  if (par_bytes > c->chan_par.capacity() || tab_floats > c->chan_tab.capacity())      // grown on demand (earlier calls may still read the old ones)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  if ((rc = c->chan_par.reserve(c, par_bytes)) || (rc = c->chan_tab.reserve(c, tab_floats))) return rc;
-  if (!c->ev_chan0) {
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan0, LCS_EVENT_NOFENCE));
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_chan1, LCS_EVENT_NOFENCE));
-  }
-  if ((rc = lcs_chan_slot(c, par_bytes, &k))) return rc;
-  unsigned long long *h_step = reinterpret_cast<unsigned long long *>(c->chan_hpin[k].get());
-  float *h_taps = (float *)(h_step + n_ch);
-  for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);
-  double taps[16 * 128];
-  lcs_chan_taps(down, taps);
-  for (int t = 0; t < Tg; ++t) h_taps[t] = (float)taps[t];
-  const size_t upl = (size_t)n_ch * sizeof(unsigned long long) + Tg * sizeof(float);
-  HIPCHK(c, hipMemcpyAsync(c->chan_par, h_step, upl, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev_chan_slot[k], c->stream));
-  const unsigned long long *d_step = reinterpret_cast<const unsigned long long *>(c->chan_par.get());
-  const float *d_taps = (const float *)(d_step + n_ch);
-  HIPCHK(c, hipEventRecord(c->ev_chan0, c->stream));
-  const int tab_grid = (int)std::min<size_t>((tab_floats + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_chan_rate_tables, dim3(tab_grid), dim3(256), 0, c->stream, d_step, d_taps, n_ch, up, down, G, n_rb, c->chan_tab);
-  const dim3 grid(cr_grid_x(n_out, up, ni), n_rb);
-  if (fmt == LCS_FMT_C64) chan_rate_launch<LCS_FMT_C64>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
-  else if (fmt == LCS_FMT_IQ_S16) chan_rate_launch<LCS_FMT_IQ_S16>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
-  else chan_rate_launch<LCS_FMT_IQ_S8>(c, grid, lds_bytes, d_wide, n_in, up, down, geo, d_step, n_ch, d_out, n_out, d_part);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));
-  c->chan_timed = true;
-  return LCS_OK;
+// The rational form's part of lcs_launch_channelize (channelizer.hip): a kernel is launched from the file that holds it
+void lcs_chan_rate_enqueue(lcs_ctx *c, const ChanCall &a, const cr_geom &geo, dim3 tab_grid, dim3 grid, const unsigned long long *d_step,
+                           const float *d_taps, float *d_part) {
+  hipLaunchKernelGGL(k_chan_rate_tables, tab_grid, dim3(256), 0, c->stream, d_step, d_taps, a.n_ch, a.up, a.down, geo.G, (int)grid.y, c->chan_tab);
+  chan_by_form(a.fmt, d_part != nullptr, [&](auto fmt, auto pow) {
+    hipLaunchKernelGGL((k_channelize_rate<decltype(fmt)::value, decltype(pow)::value>), grid, dim3(256), geo.lds_bytes, c->stream, a.d_wide,
+                       (unsigned long long)a.n_in, a.up, a.down, geo.G, geo.NI, geo.xrows, (const float *)c->chan_tab, d_step, a.n_ch, (float2 *)a.d_out,
+                       (unsigned)a.n_out, d_part);
+  });
 }

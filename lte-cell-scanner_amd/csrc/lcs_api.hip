@@ -1279,35 +1279,20 @@ int lcs_channelizer_taps(int decim, double *taps) {
   return LCS_OK;
 }
 
-// What the channelizer's entry points refuse, in the order they look: the text of the first rule a call breaks, nullptr for a call
-// that may be launched.  chan_refusal: the integer form's rules; chan_rate_refusal: the rate's own; chan_rest_refusal: what the
-// rational form asks of everything else.  lcs_channelize_u8 goes by the same three, so it refuses what the call it extends refuses.
-static const char *chan_refusal(const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift, int n_ch, const void *d_out,
-                                uint32_t n_out) {
-  if (!d_wide || !f_shift || !d_out) return "null pointer";
-  if (decim < 2 || decim > 16) return "decim outside 2..16";
-  if (n_ch < 1) return "n_ch < 1";
-  if (n_out < 1) return "n_out < 1";
-  if (!(fs_in > 0) || !std::isfinite(fs_in)) return "fs_in is not a positive rate";
-  if (n_in < ((uint64_t)n_out - 1) * decim + 16ull * decim) return "n_in < (n_out-1)*decim + 16*decim: the capture is too short for n_out outputs";
-  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_S8 && fmt != LCS_FMT_IQ_S16) return "unknown sample format";
-  for (int k = 0; k < n_ch; ++k)
-    if (!(std::fabs(f_shift[k]) <= 0.5 * fs_in)) return "|f_shift| > fs_in/2";
-  if (reinterpret_cast<uintptr_t>(d_out) & 15) return "d_out is not 16-byte aligned";
-  const uintptr_t in_align = fmt == LCS_FMT_C64 ? 7 : fmt == LCS_FMT_IQ_S16 ? 3 : 1;
-  if (reinterpret_cast<uintptr_t>(d_wide) & in_align) return "d_wide is not aligned to its sample size";
-  return nullptr;
+// The entry points fill one ChanCall and refuse by chan_refusal (channelizer.h); lcs_channelize_u8 refuses what the call it
+// extends refuses, then looks at d_gain.
+static int chan_refused(lcs_ctx *c, const char *entry, const char *what) {
+  c->err = std::string(entry) + ": " + what;
+  return LCS_ERR_BAD_ARG;
 }
 
 int lcs_channelize(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int decim, const double *f_shift, int n_ch,
                    void *d_out, uint32_t n_out) {
   if (!c) return LCS_ERR_BAD_ARG;
-  if (const char *what = chan_refusal(d_wide, fmt, n_in, fs_in, decim, f_shift, n_ch, d_out, n_out)) {
-    c->err = std::string("lcs_channelize: ") + what;
-    return LCS_ERR_BAD_ARG;
-  }
+  const ChanCall a = {d_wide, fmt, n_in, fs_in, 1, decim, f_shift, n_ch, d_out, n_out};
+  if (const char *what = chan_refusal(a, CHAN_DECIM)) return chan_refused(c, "lcs_channelize", what);
   HIPCHK(c, hipSetDevice(c->device));
-  return lcs_launch_channelize(c, d_wide, fmt, n_in, fs_in, decim, f_shift, n_ch, d_out, n_out);
+  return lcs_launch_channelize(c, a, nullptr);
 }
 
 int lcs_channelizer_proto(int down, double *taps) {
@@ -1316,57 +1301,26 @@ int lcs_channelizer_proto(int down, double *taps) {
   return LCS_OK;
 }
 
-static const char *chan_rate_refusal(const void *d_wide, int up, int down, const double *f_shift, const void *d_out) {
-  if (!d_wide || !f_shift || !d_out) return "null pointer";
-  if (down < 2 || down > 128) return "down outside 2..128";
-  if (up < 1 || up > 127) return "up outside 1..127";
-  if (up >= down) return "up >= down: interpolation is not supported";
-  if (down > 16 * up) return "down / up > 16";
-  for (int a = up, b = down; b;) {
-    const int r = a % b;
-    a = b, b = r;
-    if (!b && a != 1) return "up and down have a common factor";
-  }
-  return nullptr;
-}
-static const char *chan_rest_refusal(const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift, int n_ch,
-                                     const void *d_out, uint32_t n_out) {
-  if (n_ch < 1) return "n_ch < 1";
-  if (n_out < 1) return "n_out < 1";
-  if (!(fs_in > 0) || !std::isfinite(fs_in)) return "fs_in is not a positive rate";
-  if (n_in < (((uint64_t)n_out - 1) * down + 16ull * down - 1) / up + 1)
-    return "n_in < floor(((n_out-1)*down + 16*down - 1) / up) + 1: the capture is too short for n_out outputs";
-  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_S8 && fmt != LCS_FMT_IQ_S16) return "unknown sample format";
-  for (int k = 0; k < n_ch; ++k)
-    if (!(std::fabs(f_shift[k]) <= 0.5 * fs_in)) return "|f_shift| > fs_in/2";
-  if (reinterpret_cast<uintptr_t>(d_out) & 15) return "d_out is not 16-byte aligned";
-  const uintptr_t in_align = fmt == LCS_FMT_C64 ? 7 : fmt == LCS_FMT_IQ_S16 ? 3 : 1;
-  if (reinterpret_cast<uintptr_t>(d_wide) & in_align) return "d_wide is not aligned to its sample size";
-  return nullptr;
-}
-
 int lcs_channelize_rational(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift,
                             int n_ch, void *d_out, uint32_t n_out) {
   if (!c) return LCS_ERR_BAD_ARG;
-  auto bad = [&](const char *what) { c->err = std::string("lcs_channelize_rational: ") + what; return LCS_ERR_BAD_ARG; };
-  if (const char *what = chan_rate_refusal(d_wide, up, down, f_shift, d_out)) return bad(what);
+  const ChanCall a = {d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out};
+  if (const char *what = chan_refusal(a, CHAN_RATE_ONLY)) return chan_refused(c, "lcs_channelize_rational", what);
   if (up == 1) return lcs_channelize(c, d_wide, fmt, n_in, fs_in, down, f_shift, n_ch, d_out, n_out);      // the integer path, bit for bit
-  if (const char *what = chan_rest_refusal(d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out)) return bad(what);
+  if (const char *what = chan_refusal(a, CHAN_RATE)) return chan_refused(c, "lcs_channelize_rational", what);
   HIPCHK(c, hipSetDevice(c->device));
-  return lcs_launch_channelize_rational(c, d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out);
+  return lcs_launch_channelize(c, a, nullptr);
 }
 
 int lcs_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down, const double *f_shift, int n_ch,
                       void *d_out, uint32_t n_out, float *d_gain) {
   if (!c) return LCS_ERR_BAD_ARG;
-  auto bad = [&](const char *what) { c->err = std::string("lcs_channelize_u8: ") + what; return LCS_ERR_BAD_ARG; };
-  if (const char *what = chan_rate_refusal(d_wide, up, down, f_shift, d_out)) return bad(what);
-  if (const char *what = up == 1 ? chan_refusal(d_wide, fmt, n_in, fs_in, down, f_shift, n_ch, d_out, n_out)
-                                 : chan_rest_refusal(d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out))
-    return bad(what);
-  if (reinterpret_cast<uintptr_t>(d_gain) & 3) return bad("d_gain is not aligned to a float");
+  const ChanCall a = {d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out};
+  const char *what = chan_refusal(a, CHAN_RATE);
+  if (!what && (reinterpret_cast<uintptr_t>(d_gain) & 3)) what = "d_gain is not aligned to a float";
+  if (what) return chan_refused(c, "lcs_channelize_u8", what);
   HIPCHK(c, hipSetDevice(c->device));
-  return lcs_launch_channelize_u8(c, d_wide, fmt, n_in, fs_in, up, down, f_shift, n_ch, d_out, n_out, d_gain);
+  return lcs_launch_channelize_u8(c, a, d_gain);
 }
 
 int lcs_last_channelize_ms(lcs_ctx *c, float *ms) {

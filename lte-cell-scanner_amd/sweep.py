@@ -92,42 +92,28 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     import torch
     from . import capi
     carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
-    if rate is not None:
-        up, down = int(rate[0]), int(rate[1])
-        fs_out = float(fs_in) * up / down
-        if n_out is None:      # what the capture holds: (n_out - 1) * down + 16 * down <= n_in * up
-            n_out = (int(n_in) * up - 16 * down) // down + 1
-            if out != "u8":
-                n_out &= ~1
-    else:
-        fs_out = float(fs_in) / int(decim)
-        if n_out is None:
-            n_out = 153584
     if out not in ("c64", "u8"):
         raise ValueError(f"search_wideband: out must be 'c64' or 'u8', not {out!r}")
+    up, down = (int(rate[0]), int(rate[1])) if rate is not None else (1, int(decim))      # up == 1 is the integer path, bit for bit
+    fs_out = float(fs_in) * up / down
+    if n_out is None and rate is None:
+        n_out = 153584
+    elif n_out is None:      # what the capture holds: (n_out - 1) * down + 16 * down <= n_in * up
+        n_out = (int(n_in) * up - 16 * down) // down + 1
+        if out != "u8":
+            n_out &= ~1
     chunk = max(1, min(int(chunk), carriers.size))
     dev = getattr(searcher, "device", -1)
     tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
     if out == "u8":
-        buf = torch.empty((chunk, int(n_out), 2), dtype=torch.uint8, device=tdev)
-        up8, down8 = (up, down) if rate is not None else (1, int(decim))
-        cells = []
-        for a in range(0, carriers.size, chunk):
-            fc = carriers[a:a + chunk]
-            searcher.channelize_u8(d_wide_ptr, fmt, n_in, fs_in, up8, down8, fc - float(fc_centre), buf.data_ptr(), n_out)
-            cells += searcher.search_batch(buf.data_ptr(), capi.FMT_IQ_U8, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
-                                           max_cells_per_buf)
-        return cells
-    buf = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=tdev)
+        buf, batch_fmt, channelize = torch.empty((chunk, int(n_out), 2), dtype=torch.uint8, device=tdev), capi.FMT_IQ_U8, searcher.channelize_u8
+    else:
+        buf, batch_fmt, channelize = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=tdev), capi.FMT_C64, searcher.channelize_rational
     cells = []
     for a in range(0, carriers.size, chunk):
         fc = carriers[a:a + chunk]
-        if rate is not None:
-            searcher.channelize_rational(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
-        else:
-            searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, decim, fc - float(fc_centre), buf.data_ptr(), n_out)
-        cells += searcher.search_batch(buf.data_ptr(), capi.FMT_C64, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL,
-                                       max_cells_per_buf)
+        channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
+        cells += searcher.search_batch(buf.data_ptr(), batch_fmt, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL, max_cells_per_buf)
     return cells
 
 

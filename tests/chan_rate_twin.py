@@ -1,6 +1,7 @@
 """The host twin of the rational channelizer (tests/host/chan_rate_host.cpp: a workgroup of channelizer_rate.hip walked on the CPU
 with the kernel's own index helpers of channelizer.h), built on demand and wrapped for numpy; the rate domain and its corners.
-Shared by tests/test_channelizer_rate_twin_host.py and tests/test_gpu_channelizer_rate.py."""
+Shared by tests/test_channelizer_rate_twin_host.py and tests/test_gpu_channelizer_rate.py; host_lib builds and loads the other
+host twins of channelizer.h the same way (tests/test_channelizer_u8_host.py, tests/test_channelizer_args_host.py)."""
 import ctypes as C
 import math
 import os
@@ -9,8 +10,6 @@ import subprocess
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "host", "chan_rate_host.cpp")
-LIB = os.path.join(ROOT, "tests", "host", "libchan_rate_host.so")
 CSRC = os.path.join(ROOT, "lte-cell-scanner_amd", "csrc")
 FMT = {"c64": 0, "s8": 3, "s16": 4}          # LCS_FMT_C64, LCS_FMT_IQ_S8, LCS_FMT_IQ_S16 (include/lcs.h)
 CR_LDS_MAX = 48 * 1024
@@ -43,15 +42,21 @@ def shifts17(fs_in):
                     + [(-0.41 + 0.097 * k) * fs_in for k in range(9)])
 
 
+def host_lib(name):
+    """tests/host/lib<name>.so of tests/host/<name>.cpp, a host twin of channelizer.h, rebuilt when a file it is compiled from is newer"""
+    src, lib_path = os.path.join(ROOT, "tests", "host", name + ".cpp"), os.path.join(ROOT, "tests", "host", "lib" + name + ".so")
+    dep = [src, os.path.join(CSRC, "channelizer.h"), os.path.join(CSRC, "lcs_internal.h"), os.path.join(ROOT, "include", "lcs.h")]
+    if not os.path.exists(lib_path) or any(os.path.getmtime(d) > os.path.getmtime(lib_path) for d in dep):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
+                               "-shared", "-I" + os.path.join(ROOT, "include"), "-o", lib_path, src])
+    return C.CDLL(lib_path)
+
+
 def lib():
-    """the twin, rebuilt when a file it is compiled from is newer"""
+    """the twin of the rational kernel"""
     global _lib
     if _lib is None:
-        dep = [SRC, os.path.join(CSRC, "channelizer.h"), os.path.join(CSRC, "lcs_internal.h"), os.path.join(ROOT, "include", "lcs.h")]
-        if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in dep):
-            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
-                                   "-shared", "-I" + os.path.join(ROOT, "include"), "-o", LIB, SRC])
-        h = C.CDLL(LIB)
+        h = host_lib("chan_rate_host")
         ip, fp, up = C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)
         h.cr_host_geometry.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_longlong)]
         h.cr_host_geometry.restype = None

@@ -161,7 +161,7 @@ static long long run(const void *x, unsigned long long n_in, int U, int D, const
   return outside;
 }
 
-// the launch of lcs_launch_channelize_rational on the CPU; out[n_ch][n_out] (re, im) floats.  Returns the number of stores that
+// the rational form's launch (lcs_launch_channelize, up > 1) on the CPU; out[n_ch][n_out] (re, im) floats.  Returns the number of stores that
 // fell outside out (none were made), -1 for an unknown format.
 extern "C" long long cr_host_run(int fmt, const void *x, unsigned long long n_in, int U, int D, const unsigned long long *step, const float *taps,
                                  int n_ch, float *out, unsigned n_out) {

@@ -15,9 +15,7 @@ from conftest import ROOT, load_pkg
 
 @pytest.fixture(scope="module")
 def host():
-    path = os.path.join(ROOT, "tests", "host", "libchan_u8_host.so")
-    assert os.path.exists(path), "tests/host/libchan_u8_host.so is missing: run __graft_entry__.build()"
-    L = C.CDLL(path)
+    L = T.host_lib("chan_u8_host")      # built here when build() has not left it, as the other twins' tests do
     L.chan_u8_host_exponents.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
     L.chan_u8_host_codes.argtypes = [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_ubyte)]
     return L
