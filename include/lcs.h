@@ -526,6 +526,49 @@ int lcs_channelize_rational(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t 
 int lcs_channelize_u8(lcs_ctx *ctx, const void *d_wide, int fmt, uint64_t n_in, double fs_in, int up, int down,
                       const double *f_shift, int n_ch, void *d_out /*DEVICE [n_ch][n_out][2] u8*/, uint32_t n_out,
                       float *d_gain /*DEVICE [n_ch] or NULL*/);
+/* Continuous form of lcs_channelize / lcs_channelize_rational for front ends that deliver a wideband stream in transfer buffers of
+ * any size (HackRF, Airspy, USRP): the carrier phase runs on over the cuts and no sample at a buffer's end is lost.  A context holds
+ * one such stream, as it holds one lcs_stream_open stream.  With N the samples pushed since open and Tg = 16 * down,
+ *
+ *   M(N) = 0 when N * up < Tg, otherwise (N * up - Tg) / down + 1 in integer division
+ *
+ * is the largest n_out for which the one-shot call accepts n_in = N (its rule is (n_out - 1) * down + Tg - 1 < N * up).  After a push
+ * exactly the outputs m < M(N) of every carrier have been handed out, each once, by the first push that can compute it: a push
+ * writes the outputs m_first .. m_first + n_emit - 1, m_first = the previous M, n_emit = M(N) - m_first, output m_first + j of
+ * carrier k to d_out[k * row_stride + j], and touches nothing else of d_out.  Every output is, bit for bit, output m of ONE
+ * lcs_channelize_rational call (lcs_channelize when up == 1, down in 2..16) on all N samples with n_out = M(N), for finite samples:
+ * a column of the matrix product has the same filter rows, the same samples and the same order of summation wherever a launch
+ * places it, and the carrier phase is step * n mod 2^64 of the stream's own sample index n, so a stream has no length limit.
+ *   open   fmt, fs_in, up, down, f_shift (HOST [n_ch]) and n_ch as the one-shot forms take and refuse them, with their texts; up = 1
+ *          is the integer form.  The filter taps, the phase steps and the filter bank are built here, once, into memory of the
+ *          stream's own: lcs_channelize, lcs_channelize_rational and lcs_channelize_u8 on the same context stay legal while the
+ *          stream is open and give what they give without it.
+ *   count  n_emit of a push of n_chunk samples now; nothing is queued.
+ *   push   d_chunk: DEVICE, n_chunk samples of fmt, aligned to one sample, n_chunk <= 2^31; NULL only with n_chunk == 0.  It must
+ *          stay valid and unchanged until the work the push queued has run (everything is queued on the context's stream).
+ *          d_out: DEVICE complex<float>, 8-byte aligned -- a caller advances it by 8 bytes per output it has taken; rows are
+ *          row_stride samples apart, row_stride >= out_cap, and out_cap is the room per row.  n_emit and m_first (either may be
+ *          NULL) are known in closed form and returned without waiting for the GPU.  A push may hand out nothing (a chunk shorter
+ *          than the filter, n_chunk == 0): the samples are kept.  A push with n_emit > out_cap is refused: counts grow by at most one
+ *          per sample (up < down), so count finds the chunk length of any exact split.
+ *   close  waits for the queued pushes and frees the stream's memory; lcs_destroy closes an open stream.
+ * Between pushes the context keeps the samples from the first one of the output column that holds output M(N) on (a column = the
+ * `up` outputs whose windows start in one stretch of `down` samples): fewer than 16 * down / up + down, at most 365, in the input's
+ * own format.  A push therefore costs two kernels (one when it hands out nothing) and recomputes at most up - 1 outputs.
+ * Non-finite samples (LCS_FMT_C64): the caveat of lcs_channelize_rational holds with one more clause.  The up to 4 samples behind an
+ * output's window that the one-shot call multiplies by zero taps may not have arrived yet when the stream computes the output, and
+ * count as zeros then: an output whose window holds no non-finite sample may be finite here where the one-shot call makes it
+ * non-finite, never the reverse.
+ * LCS_ERR_BAD_ARG (an lcs_last_error text, nothing launched, the stream where it was): open with a stream already open; count, push
+ * or close with none; n_chunk above 2^31; a null chunk with n_chunk > 0; a misaligned chunk or d_out; a null d_out with outputs to
+ * hand out; row_stride < out_cap; out_cap < n_emit.  lcs_last_channelize_ms is not set by a push: it keeps the time of the last
+ * one-shot call. */
+int lcs_chan_stream_open(lcs_ctx *ctx, int fmt, double fs_in, int up, int down, const double *f_shift /*host [n_ch]*/, int n_ch);
+int lcs_chan_stream_count(lcs_ctx *ctx, uint64_t n_chunk, uint32_t *n_emit);
+int lcs_chan_stream_push(lcs_ctx *ctx, const void *d_chunk /*DEVICE, n_chunk samples of fmt*/, uint64_t n_chunk,
+                         void *d_out /*DEVICE complex<float>*/, uint32_t row_stride /*samples between carrier rows*/, uint32_t out_cap,
+                         uint32_t *n_emit, uint64_t *m_first);
+int lcs_chan_stream_close(lcs_ctx *ctx);
 /* HIP-event time (ms) of the last lcs_channelize, lcs_channelize_rational or lcs_channelize_u8 of the context (filter-bank build
  * through the call's last kernel), as lcs_last_xcorr_ms */
 int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);

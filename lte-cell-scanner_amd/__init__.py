@@ -509,6 +509,32 @@ class Searcher:
                   "lcs_channelize_u8")
         return gain
 
+    # ---- the channelizer's continuous form (lcs_chan_stream_open, include/lcs.h) -----------
+    def chan_stream_open(self, fmt: int, fs_in: float, up: int, down: int, f_shift):
+        """Open the context's channelizer stream: samples of fmt at fs_in, pushed in chunks of any size, come out as len(f_shift)
+        carriers at fs_in * up / down -- after any pushes bit for bit what ONE channelize_rational call on all the samples gives
+        ((1, decim): channelize).  Steps, taps and the filter bank are built here, once."""
+        f = np.ascontiguousarray(np.atleast_1d(f_shift), np.float64)
+        self._chk(self._lib.lcs_chan_stream_open(self._h, int(fmt), float(fs_in), int(up), int(down), _dp(f), int(f.size)), "lcs_chan_stream_open")
+
+    def chan_stream_count(self, n_chunk: int) -> int:
+        """Outputs per carrier a push of n_chunk samples would hand out now (lcs_chan_stream_count)."""
+        n = C.c_uint32(0)
+        self._chk(self._lib.lcs_chan_stream_count(self._h, int(n_chunk), C.byref(n)), "lcs_chan_stream_count")
+        return n.value
+
+    def chan_stream_push(self, d_chunk_ptr: int, n_chunk: int, d_out_ptr: int, row_stride: int, out_cap: int):
+        """Push n_chunk samples at d_chunk_ptr (device).  Output m_first + j of carrier k goes to complex64 element k * row_stride + j
+        behind d_out_ptr (device, 8-byte aligned), j < n_emit <= out_cap.  Queued on the context's stream; the chunk must stay
+        unchanged until that work has run.  Returns (n_emit, m_first), known without waiting for the GPU."""
+        n, m = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self._lib.lcs_chan_stream_push(self._h, C.c_void_p(d_chunk_ptr), int(n_chunk), C.c_void_p(d_out_ptr), int(row_stride), int(out_cap),
+                                                 C.byref(n), C.byref(m)), "lcs_chan_stream_push")
+        return n.value, m.value
+
+    def chan_stream_close(self):
+        self._chk(self._lib.lcs_chan_stream_close(self._h), "lcs_chan_stream_close")
+
     def last_channelize_ms(self) -> float:
         """HIP-event time (ms) of the last channelize / channelize_rational / channelize_u8 call of this context (lcs_last_channelize_ms)."""
         ms = C.c_float(0)

@@ -71,6 +71,7 @@ EXPORTS = [
     "lcs_last_xcorr_ms", "lcs_last_xcorr_info", "lcs_last_frq_repairs", "lcs_last_frq_repair_stats", "lcs_frq_tie_eps", "lcs_last_batch_stats", "lcs_last_collect_host_us", "lcs_stream", "lcs_sync", "lcs_table_pss_td", "lcs_table_pss_fd", "lcs_table_sss_fd",
     "lcs_table_lte_pn", "lcs_chi2cdf_inv", "lcs_channelizer_taps", "lcs_channelize", "lcs_last_channelize_ms",
     "lcs_channelizer_proto", "lcs_channelize_rational", "lcs_channelize_u8",
+    "lcs_chan_stream_open", "lcs_chan_stream_count", "lcs_chan_stream_push", "lcs_chan_stream_close",
 ]
 
 _lib = None
@@ -168,6 +169,10 @@ def load() -> C.CDLL:
     L.lcs_channelizer_proto.argtypes = [C.c_int, dp]
     L.lcs_channelize_rational.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.c_int, dp, C.c_int, vp, C.c_uint32]
     L.lcs_channelize_u8.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_double, C.c_int, C.c_int, dp, C.c_int, vp, C.c_uint32, vp]
+    L.lcs_chan_stream_open.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, dp, C.c_int]
+    L.lcs_chan_stream_count.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32)]
+    L.lcs_chan_stream_push.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.lcs_chan_stream_close.argtypes = [vp]
     L.lcs_stream.argtypes = [vp]
     L.lcs_stream.restype = vp
     L.lcs_sync.argtypes = [vp]

@@ -56,6 +56,35 @@ static inline const char *chan_refusal(const ChanCall &a, ChanRules rules) {
   return nullptr;
 }
 
+// The continuous form (include/lcs.h, lcs_chan_stream_open): what its four entry points refuse beyond chan_refusal, in the order they
+// look.  open hands its rate, format, shifts and n_ch to chan_refusal first (CHAN_RATE; the rules for n_in, n_out and d_out have
+// nothing to look at there) and then asks here; count looks at the first two rules, close at the first.
+enum ChanStreamEntry { CHAN_STREAM_OPEN, CHAN_STREAM_COUNT, CHAN_STREAM_PUSH, CHAN_STREAM_CLOSE };
+struct ChanPush {
+  bool is_open;              // the context has a stream
+  int fmt;                   // the stream's format
+  const void *d_chunk;
+  uint64_t n_chunk;
+  void *d_out;
+  uint32_t row_stride, out_cap;
+  uint64_t n_emit;           // what the push would hand out (cs_count)
+};
+static inline const char *chan_stream_refusal(const ChanPush &a, ChanStreamEntry entry) {
+  if (entry == CHAN_STREAM_OPEN) return a.is_open ? "a channelizer stream is already open on this context" : nullptr;
+  if (!a.is_open) return "no channelizer stream is open on this context";
+  if (entry == CHAN_STREAM_CLOSE) return nullptr;
+  if (a.n_chunk > (1ull << 31)) return "n_chunk > 2^31";
+  if (entry == CHAN_STREAM_COUNT) return nullptr;
+  if (!a.d_chunk && a.n_chunk) return "null chunk with n_chunk > 0";
+  const uintptr_t in_align = a.fmt == LCS_FMT_C64 ? 7 : a.fmt == LCS_FMT_IQ_S16 ? 3 : 1;
+  if (reinterpret_cast<uintptr_t>(a.d_chunk) & in_align) return "d_chunk is not aligned to its sample size";
+  if (!a.d_out && a.n_emit) return "null d_out with outputs to hand out";
+  if (reinterpret_cast<uintptr_t>(a.d_out) & 7) return "d_out is not 8-byte aligned";
+  if (a.row_stride < a.out_cap) return "row_stride < out_cap";
+  if (a.out_cap < a.n_emit) return "out_cap < n_emit: size or split the chunk by lcs_chan_stream_count";
+  return nullptr;
+}
+
 void lcs_chan_taps(int decim, double *taps /*[16*decim]*/);      // any decim >= 2
 unsigned long long lcs_chan_step(double f_shift, double fs_in);
 // d_part == nullptr: the float forms.  Otherwise [n_ch][lcs_chan_blocks(call)] floats: every workgroup along the outputs leaves
@@ -65,6 +94,10 @@ unsigned lcs_chan_blocks(const ChanCall &a);
 // lcs_channelize_u8: the float form into the context's scratch with the power partials, then k_chan_quant_u8 (channelizer.hip)
 int lcs_launch_channelize_u8(lcs_ctx *c, const ChanCall &a, float *d_gain);
 int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context's last channelizer launch (any form)
+// the continuous form: the stream's own steps, taps, table and history (ChanStream, lcs_internal.h); channelizer.hip
+int lcs_chan_stream_start(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch);
+int lcs_chan_stream_enqueue(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, uint32_t row_stride);
+int lcs_chan_stream_end(lcs_ctx *c);
 
 // The kernels are templates over the capture's format and POW (the power partials of the 8-bit form):
 // chan_by_form(fmt, pow, [&](auto fmt, auto pow) { launch k<decltype(fmt)::value, decltype(pow)::value> }) picks the instantiation.
@@ -107,12 +140,78 @@ __host__ __device__ __forceinline__ float2 chan_sample(const void *x, unsigned l
   return make_float2((float)(int)(int8_t)(p & 255u) * (1.f / 128.f), (float)(int)(int8_t)(p >> 8) * (1.f / 128.f));
 }
 
+// ---- the continuous form's bookkeeping (include/lcs.h, lcs_chan_stream_push).  N samples pushed so far, Tg = 16 D.  Everything is
+// an ABSOLUTE index of the whole stream.  The launcher and the kernels go by these, and tests/host/chan_stream_host.cpp walks them.
+// M(N): the outputs N samples give -- the largest n_out chan_refusal takes for n_in = N: (n_out - 1) D + Tg - 1 < N U
+static inline unsigned long long cs_count(unsigned long long N, int U, int D) {
+  const unsigned __int128 fine = (unsigned __int128)N * (unsigned)U;      // no limit on N below 2^64
+  const unsigned Tg = 16u * (unsigned)D;
+  return fine < Tg ? 0ull : (unsigned long long)((fine - Tg) / (unsigned)D) + 1ull;
+}
+// The aligned base behind M outputs: the first sample of column floor(M / U), the column (outputs i U .. i U + U - 1) that holds
+// output M.  Output M's own window starts at ceil(M D / U) >= floor(M / U) D, and every later window starts later still.
+static inline unsigned long long cs_base(unsigned long long M, int U, int D) { return M / (unsigned)U * (unsigned)D; }
+// Samples kept behind a push: kept = N - cs_base(M(N)).  M > (N U - Tg) / D gives N < (M D + Tg) / U, and floor(M / U) >=
+// (M - U + 1) / U, so kept < (Tg + (U - 1) D) / U = 16 D / U + D - D / U (with M = 0: kept = N < Tg / U).  kept is an integer:
+// kept <= ceil((Tg + (U - 1) D) / U) - 1 = floor((Tg + (U - 1) D - 1) / U), the size of a history slot in samples (365 at 8/127)
+static inline unsigned cs_keep_max(int U, int D) { return (unsigned)((16 * D + (U - 1) * D - 1) / U); }
+// One push: N_prev samples before it, n_chunk new ones
+struct cs_plan {
+  unsigned long long m_first, m_end;      // the outputs handed out: m_first <= m < m_end
+  unsigned long long i_base;              // the first column launched, floor(m_first / U); the history starts at sample i_base D
+  unsigned long long n_base_next;         // where the history behind the push starts: cs_base(m_end)
+  unsigned n_keep;                        // ... and how many samples it holds: N_prev + n_chunk - n_base_next
+  unsigned cols, grid_x;                  // columns i_base .. floor((m_end - 1) / U) and the workgroups along them (0: nothing to hand out)
+};
+static inline cs_plan cs_plan_push(unsigned long long N_prev, unsigned long long n_chunk, int U, int D, int cols_per_block) {
+  cs_plan p;
+  p.m_first = cs_count(N_prev, U, D);
+  p.m_end = cs_count(N_prev + n_chunk, U, D);
+  p.i_base = p.m_first / (unsigned)U;
+  p.n_base_next = cs_base(p.m_end, U, D);
+  p.n_keep = (unsigned)(N_prev + n_chunk - p.n_base_next);
+  p.cols = p.m_end > p.m_first ? (unsigned)((p.m_end - 1) / (unsigned)U - p.i_base) + 1u : 0u;
+  p.grid_x = (p.cols + (unsigned)cols_per_block - 1) / (unsigned)cols_per_block;
+  return p;
+}
+// What a push's kernels know of the stream.  Sample n >= n_base of the stream is one of: history (samples [n_base, n_base + n_hist)
+// in the input's format), the chunk behind it, or -- behind the chunk's end -- a zero
+struct cs_args {
+  const void *hist;
+  unsigned long long i_base;              // n_base = i_base D
+  unsigned n_hist;
+  unsigned long long m_first, m_end;
+  unsigned row_stride;
+};
+enum { CS_HIST = 0, CS_CHUNK = 1, CS_ZERO = 2 };
+struct cs_where { int part; unsigned long long off; };
+__host__ __device__ __forceinline__ cs_where cs_source(unsigned long long n, unsigned long long n_base, unsigned n_hist, unsigned long long n_chunk) {
+  cs_where w;
+  w.off = n - n_base;                     // n >= n_base: no workgroup of a push starts in front of column i_base
+  w.part = CS_HIST;
+  if (w.off >= n_hist) {
+    w.off -= n_hist;
+    w.part = w.off < n_chunk ? CS_CHUNK : CS_ZERO;
+  }
+  return w;
+}
+template <int FMT>
+__host__ __device__ __forceinline__ float2 cs_sample(const void *hist, const void *chunk, const cs_where &w) {
+  if (w.part == CS_ZERO) return make_float2(0.f, 0.f);
+  return chan_sample<FMT>(w.part == CS_HIST ? hist : chunk, w.off);
+}
+// bytes of one sample of a format
+__host__ __device__ __forceinline__ unsigned chan_sample_bytes(int fmt) { return fmt == LCS_FMT_C64 ? 8u : fmt == LCS_FMT_IQ_S16 ? 4u : 2u; }
+
 // ---- the kernels' bookkeeping: where every tap, sample and output goes for a rate U / D.  The kernels and the launcher decide by
 // these -- the rational form by all of them, k_channelize (U = 1, two tiles per wave) by its staging offset, its accumulator map,
 // its rotation and its power partials -- and tests/host/chan_rate_host.cpp walks a workgroup on the CPU with the same ones (a
 // host build supplies sinpi / cospi / sinpif / cospif itself where its libm has none).
 #define CR_CARRIERS 16                 // carriers per A tile (32 rows)
 #define CR_LDS_MAX (48 * 1024)         // NI grows only while the staged samples stay below this
+// k_channelize (up == 1)
+#define CH_NT 256                      // outputs per workgroup: 4 waves x 2 tiles x 32 columns
+#define CH_XROWS (CH_NT + 15)          // LDS rows of D samples: the windows of CH_NT outputs span (CH_NT + 15) D samples
 
 struct cr_geom { int G, NI, xrows; size_t lds_bytes; };
 struct cr_tile { int q, it, sq; };                 // residue, column block of the workgroup, s_q = ceil(q D / U)

@@ -21,12 +21,12 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
+#include <vector>
 
 typedef float ch_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ch_f32x4 __attribute__((ext_vector_type(4)));
 
-#define CH_NT 256                      // outputs per workgroup: 4 waves x 2 tiles x 32 columns
-#define CH_XROWS (CH_NT + 15)          // LDS rows of D samples: the windows of CH_NT outputs span (CH_NT + 15) D samples
 #define CH_SMAX (2 * 16 + 1)           // row stride in floats at D = 16
 
 // Kaiser window's I0 by its power series (x <= 7.75: 40 terms reach 1e-17 relative)
@@ -87,13 +87,20 @@ __global__ __launch_bounds__(256) void k_chan_tables(const unsigned long long *_
 
 // POW (the 8-bit form, lcs_channelize_u8): the workgroup also leaves, per carrier, the sum of |y|^2 over the outputs it stored in
 // part[carrier][blockIdx.x] -- per lane over its two tiles, then cr_power_partials.
-template <int FMT, bool POW>
+// STREAM (the continuous form, lcs_chan_stream_push): a push's launch.  Every index is one of the whole stream: the workgroups start
+// at output sa.i_base (the stream's m_first at up == 1), the staged samples come from the stream's history and the chunk behind it
+// (x, n_in: the chunk and its length; cs_source), and only the outputs sa.m_first <= m < sa.m_end are stored, at column
+// m - sa.m_first of rows sa.row_stride apart.  A column's A rows, its samples and its k order are those of the one-shot launch,
+// wherever in a workgroup it sits.  The one-shot instantiations read nothing of sa.
+template <int FMT, bool POW, bool STREAM = false>
 __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, unsigned long long n_in, int D,
                                                     const float *__restrict__ tab, const unsigned long long *__restrict__ step,
-                                                    int n_ch, float2 *__restrict__ out, unsigned n_out, float *__restrict__ part) {
+                                                    int n_ch, float2 *__restrict__ out, unsigned n_out, float *__restrict__ part, cs_args sa) {
   __shared__ float xs[CH_XROWS * CH_SMAX];
   const int S = 2 * D + 1, T = 16 * D;
-  const unsigned m0 = blockIdx.x * CH_NT;
+  using index_t = std::conditional_t<STREAM, unsigned long long, unsigned>;
+  index_t m0 = blockIdx.x * CH_NT;
+  if constexpr (STREAM) m0 += sa.i_base;
   const int rb = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the samples [m0 D, (m0 + CH_XROWS) D) as floats; beyond the capture's end zeros (only outputs >= n_out read them)
@@ -101,7 +108,9 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
   for (int idx = tid; idx < CH_XROWS * D; idx += 256) {
     const int o = cr_stage_offset(idx, D);
     const unsigned long long n = n0 + (unsigned)idx;
-    const float2 v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
+    float2 v;
+    if constexpr (STREAM) v = cs_sample<FMT>(sa.hist, x, cs_source(n, sa.i_base * (unsigned)D, sa.n_hist, n_in));
+    else v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
     xs[o] = v.x;
     xs[o + 1] = v.y;
   }
@@ -132,19 +141,35 @@ __global__ __launch_bounds__(256) void k_channelize(const void *__restrict__ x, 
   }
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const unsigned m = m0 + wave * 64 + t * 32 + (lane & 31);
-    if (m >= n_out) continue;
+    const index_t m = m0 + wave * 64 + t * 32 + (lane & 31);
+    if constexpr (STREAM) {
+      if (m < sa.m_first || m >= sa.m_end) continue;
+    } else if (m >= n_out) continue;
     const unsigned long long nd = (unsigned long long)m * (unsigned)D;
 #pragma unroll
     for (int v = 0; v < 16; v += 2) {      // registers v, v + 1: (re, im) of one carrier (cr_acc_row)
       const int ch = cr_acc_carrier(rb, v, lane);
       if (ch >= n_ch) continue;
       const float2 y = cr_rotate(t ? acc1[v] : acc0[v], t ? acc1[v + 1] : acc0[v + 1], step[ch], nd);
-      out[(size_t)ch * n_out + m] = y;
+      if constexpr (STREAM) out[(size_t)ch * sa.row_stride + (m - sa.m_first)] = y;
+      else out[(size_t)ch * n_out + m] = y;
       if constexpr (POW) pw[v >> 1] += y.x * y.x + y.y * y.y;
     }
   }
   if constexpr (POW) cr_power_partials(pw, rb, n_ch, part);
+}
+
+// The continuous form's history: behind a push's main kernel, the n_keep samples from the next aligned base on (sample `skip` of
+// [history ++ chunk]) go into the OTHER history slot -- a short chunk leaves part of the old history needed, so the two never
+// alias.  Samples travel as the w 16-bit units they are made of (1, 2, 4: s8, s16, c64); one workgroup, at most cs_keep_max samples.
+__global__ __launch_bounds__(256) void k_chan_keep(const uint16_t *__restrict__ hist, const uint16_t *__restrict__ chunk, unsigned n_hist,
+                                                   unsigned long long n_chunk, unsigned long long skip, unsigned n_keep, unsigned w,
+                                                   uint16_t *__restrict__ dst) {
+  for (unsigned e = threadIdx.x; e < n_keep * w; e += 256) {
+    const unsigned s = e / w, u = e - s * w;
+    const cs_where from = cs_source(skip + s, 0, n_hist, n_chunk);
+    dst[e] = from.part == CS_ZERO ? (uint16_t)0 : (from.part == CS_HIST ? hist : chunk)[from.off * w + u];
+  }
 }
 
 // The 8-bit output (include/lcs.h, lcs_channelize_u8): carrier ch's floats y[ch][n_out] -> bytes out[ch][n_out][2].  Every workgroup
@@ -248,7 +273,8 @@ int lcs_launch_channelize(lcs_ctx *c, const ChanCall &a, float *d_part) {
     hipLaunchKernelGGL(k_chan_tables, tab_grid, dim3(256), 0, c->stream, d_step, d_taps, n_ch, a.down, n_rb, c->chan_tab);
     chan_by_form(a.fmt, d_part != nullptr, [&](auto fmt, auto pow) {
       hipLaunchKernelGGL((k_channelize<decltype(fmt)::value, decltype(pow)::value>), grid, dim3(256), 0, c->stream, a.d_wide,
-                         (unsigned long long)a.n_in, a.down, (const float *)c->chan_tab, d_step, n_ch, (float2 *)a.d_out, (unsigned)a.n_out, d_part);
+                         (unsigned long long)a.n_in, a.down, (const float *)c->chan_tab, d_step, n_ch, (float2 *)a.d_out, (unsigned)a.n_out, d_part,
+                         cs_args{});
     });
   } else {
     lcs_chan_rate_enqueue(c, a, geo, tab_grid, grid, d_step, d_taps, d_part);
@@ -276,6 +302,98 @@ int lcs_launch_channelize_u8(lcs_ctx *c, const ChanCall &a, float *d_gain) {
                      (int)n_blocks, n_out, n_xb, (uint8_t *)a.d_out, d_gain);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));      // the call's time runs through its last kernel
+  return LCS_OK;
+}
+
+// ---- the continuous form (include/lcs.h, lcs_chan_stream_open).  open builds what depends on the carriers and the rate only --
+// steps, taps, the A-operand table -- once, into buffers of the stream's own; a push launches its main kernel over the columns
+// that hold its outputs and the history append, and carries its scalars as kernel arguments.
+void lcs_chan_rate_tables_enqueue(lcs_ctx *c, int n_ch, int up, int down, const cr_geom &geo, dim3 tab_grid, int n_rb, const unsigned long long *d_step,
+                                  const float *d_taps, float *d_tab);      // channelizer_rate.hip
+void lcs_chan_rate_stream_enqueue(lcs_ctx *c, int fmt, const void *d_chunk, uint64_t n_chunk, int up, int down, const cr_geom &geo, dim3 grid,
+                                  const float *d_tab, const unsigned long long *d_step, int n_ch, float2 *d_out, const cs_args &sa);
+
+static void chan_stream_drop(lcs_ctx *c) {
+  lcs_ctx::ChanStream &st = c->chan_stream;
+  st.par.reset(), st.tab.reset(), st.hist[0].reset(), st.hist[1].reset();
+  st.open = false;
+}
+
+int lcs_chan_stream_start(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch) {
+  lcs_ctx::ChanStream &st = c->chan_stream;
+  const int T = 16 * down, n_rb = (n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
+  const cr_geom geo = cr_geometry(up, down);
+  const size_t par_bytes = (size_t)n_ch * sizeof(unsigned long long) + (size_t)T * sizeof(float);
+  const size_t tab_floats = (size_t)n_rb * up * geo.G * 256, hist_bytes = (size_t)cs_keep_max(up, down) * chan_sample_bytes(fmt);
+  int rc;
+  if ((rc = st.par.alloc(c, par_bytes)) || (rc = st.tab.alloc(c, tab_floats)) || (rc = st.hist[0].alloc(c, hist_bytes)) ||
+      (rc = st.hist[1].alloc(c, hist_bytes))) {
+    chan_stream_drop(c);
+    return rc;
+  }
+  std::vector<char> h(par_bytes);
+  unsigned long long *h_step = reinterpret_cast<unsigned long long *>(h.data());
+  float *h_taps = reinterpret_cast<float *>(h_step + n_ch);
+  for (int i = 0; i < n_ch; ++i) h_step[i] = lcs_chan_step(f_shift[i], fs_in);
+  double taps[16 * 128];
+  lcs_chan_taps(down, taps);
+  for (int t = 0; t < T; ++t) h_taps[t] = (float)taps[t];
+  const unsigned long long *d_step = reinterpret_cast<const unsigned long long *>(st.par.get());
+  const float *d_taps = reinterpret_cast<const float *>(d_step + n_ch);
+  const dim3 tab_grid((unsigned)std::min<size_t>((tab_floats + 255) / 256, 2048));
+  hipError_t e = hipMemcpyAsync(st.par, h.data(), par_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    if (up == 1) hipLaunchKernelGGL(k_chan_tables, tab_grid, dim3(256), 0, c->stream, d_step, d_taps, n_ch, down, n_rb, st.tab.get());
+    else lcs_chan_rate_tables_enqueue(c, n_ch, up, down, geo, tab_grid, n_rb, d_step, d_taps, st.tab);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // h is ordinary memory that goes with this call; once per stream
+  if (e != hipSuccess) {
+    chan_stream_drop(c);
+    return lcs_hip_error(c, "lcs_chan_stream_open", e);
+  }
+  st.fmt = fmt, st.up = up, st.down = down, st.n_ch = n_ch;
+  st.cur = 0, st.n_hist = 0, st.n_total = 0;
+  st.open = true;
+  return LCS_OK;
+}
+
+// One push, already found acceptable: nothing here can refuse.  The stream moves on only when both launches were taken.
+int lcs_chan_stream_enqueue(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, uint32_t row_stride) {
+  lcs_ctx::ChanStream &st = c->chan_stream;
+  if (!n_chunk) return LCS_OK;      // nothing new: the outputs, the base and the history stay what they are
+  const cr_geom geo = cr_geometry(st.up, st.down);
+  const cs_plan p = cs_plan_push(st.n_total, n_chunk, st.up, st.down, st.up == 1 ? CH_NT : 32 * geo.NI);
+  const int n_rb = (st.n_ch + CR_CARRIERS - 1) / CR_CARRIERS;
+  const unsigned long long *d_step = reinterpret_cast<const unsigned long long *>(st.par.get());
+  const void *hist = st.hist[st.cur].get();
+  if (p.grid_x) {
+    const cs_args sa = {hist, p.i_base, st.n_hist, p.m_first, p.m_end, row_stride};
+    const dim3 grid(p.grid_x, n_rb);
+    if (st.up == 1) {
+      chan_by_form(st.fmt, false, [&](auto fmt, auto) {
+        hipLaunchKernelGGL((k_channelize<decltype(fmt)::value, false, true>), grid, dim3(256), 0, c->stream, d_chunk, (unsigned long long)n_chunk,
+                           st.down, (const float *)st.tab, d_step, st.n_ch, (float2 *)d_out, 0u, (float *)nullptr, sa);
+      });
+    } else {
+      lcs_chan_rate_stream_enqueue(c, st.fmt, d_chunk, n_chunk, st.up, st.down, geo, grid, st.tab, d_step, st.n_ch, (float2 *)d_out, sa);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  const unsigned long long n_base = p.i_base * (unsigned)st.down;      // == st.n_total - st.n_hist
+  hipLaunchKernelGGL(k_chan_keep, dim3(1), dim3(256), 0, c->stream, (const uint16_t *)hist, (const uint16_t *)d_chunk, st.n_hist,
+                     (unsigned long long)n_chunk, p.n_base_next - n_base, p.n_keep, chan_sample_bytes(st.fmt) / 2u, (uint16_t *)st.hist[st.cur ^ 1].get());
+  HIPCHK(c, hipGetLastError());
+  st.cur ^= 1;
+  st.n_hist = p.n_keep;
+  st.n_total += n_chunk;
+  return LCS_OK;
+}
+
+// the queued pushes may still read the stream's buffers
+int lcs_chan_stream_end(lcs_ctx *c) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  chan_stream_drop(c);
   return LCS_OK;
 }
 

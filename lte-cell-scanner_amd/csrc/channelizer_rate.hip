@@ -37,13 +37,17 @@ __global__ __launch_bounds__(256) void k_chan_rate_tables(const unsigned long lo
 
 // POW (the 8-bit form): as k_channelize<FMT, true> -- the sum of |y|^2 per carrier over the outputs the workgroup stored goes to
 // part[carrier][blockIdx.x]: per lane over its wave's tiles in tile order, then cr_power_partials.
-template <int FMT, bool POW>
+// STREAM (the continuous form): as k_channelize<FMT, POW, true> -- the workgroups start at column sa.i_base of the whole stream, the
+// samples come from the history and the chunk (x, n_in), the outputs sa.m_first <= m < sa.m_end are stored at column m - sa.m_first
+// of rows sa.row_stride apart; the up to U - 1 outputs of column i_base in front of m_first are computed and dropped.
+template <int FMT, bool POW, bool STREAM = false>
 __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict__ x, unsigned long long n_in, int U, int D, int G, int NI,
                                                          int xrows, const float *__restrict__ tab,
                                                          const unsigned long long *__restrict__ step, int n_ch,
-                                                         float2 *__restrict__ out, unsigned n_out, float *__restrict__ part) {
+                                                         float2 *__restrict__ out, unsigned n_out, float *__restrict__ part, cs_args sa) {
   extern __shared__ float xs[];      // xrows rows of D samples, row stride 2 D + 1
-  const unsigned long long i0 = (unsigned long long)blockIdx.x * (32u * NI);
+  unsigned long long i0 = (unsigned long long)blockIdx.x * (32u * NI);
+  if constexpr (STREAM) i0 += sa.i_base;
   const int rb = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the samples [i0 D, (i0 + xrows) D) as floats; beyond the capture's end zeros (only zero taps and outputs >= n_out read them)
@@ -51,7 +55,9 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
   for (int idx = tid; idx < xrows * D; idx += 256) {
     const int o = cr_stage_offset(idx, D);
     const unsigned long long n = n0 + (unsigned)idx;
-    const float2 v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
+    float2 v;
+    if constexpr (STREAM) v = cs_sample<FMT>(sa.hist, x, cs_source(n, sa.i_base * (unsigned)D, sa.n_hist, n_in));
+    else v = n < n_in ? chan_sample<FMT>(x, n) : make_float2(0.f, 0.f);
     xs[o] = v.x;
     xs[o + 1] = v.y;
   }
@@ -80,13 +86,16 @@ __global__ __launch_bounds__(256) void k_channelize_rate(const void *__restrict_
       }
     }
     const cr_col col = cr_col_of(i0, tl, lane, U, D);
-    if (col.m >= n_out) continue;
+    if constexpr (STREAM) {
+      if (col.m < sa.m_first || col.m >= sa.m_end) continue;
+    } else if (col.m >= n_out) continue;
 #pragma unroll
     for (int v = 0; v < 16; v += 2) {      // registers v, v + 1: (re, im) of one carrier (cr_acc_row)
       const int ch = cr_acc_carrier(rb, v, lane);
       if (ch >= n_ch) continue;
       const float2 y = cr_rotate(acc[v], acc[v + 1], step[ch], col.nd);
-      out[(size_t)ch * n_out + col.m] = y;
+      if constexpr (STREAM) out[(size_t)ch * sa.row_stride + (col.m - sa.m_first)] = y;
+      else out[(size_t)ch * n_out + col.m] = y;
       if constexpr (POW) pw[v >> 1] += y.x * y.x + y.y * y.y;
     }
   }
@@ -100,6 +109,19 @@ void lcs_chan_rate_enqueue(lcs_ctx *c, const ChanCall &a, const cr_geom &geo, di
   chan_by_form(a.fmt, d_part != nullptr, [&](auto fmt, auto pow) {
     hipLaunchKernelGGL((k_channelize_rate<decltype(fmt)::value, decltype(pow)::value>), grid, dim3(256), geo.lds_bytes, c->stream, a.d_wide,
                        (unsigned long long)a.n_in, a.up, a.down, geo.G, geo.NI, geo.xrows, (const float *)c->chan_tab, d_step, a.n_ch, (float2 *)a.d_out,
-                       (unsigned)a.n_out, d_part);
+                       (unsigned)a.n_out, d_part, cs_args{});
+  });
+}
+
+// The continuous form's two launches of this file's kernels (channelizer.hip: lcs_chan_stream_start, lcs_chan_stream_enqueue)
+void lcs_chan_rate_tables_enqueue(lcs_ctx *c, int n_ch, int up, int down, const cr_geom &geo, dim3 tab_grid, int n_rb, const unsigned long long *d_step,
+                                  const float *d_taps, float *d_tab) {
+  hipLaunchKernelGGL(k_chan_rate_tables, tab_grid, dim3(256), 0, c->stream, d_step, d_taps, n_ch, up, down, geo.G, n_rb, d_tab);
+}
+void lcs_chan_rate_stream_enqueue(lcs_ctx *c, int fmt, const void *d_chunk, uint64_t n_chunk, int up, int down, const cr_geom &geo, dim3 grid,
+                                  const float *d_tab, const unsigned long long *d_step, int n_ch, float2 *d_out, const cs_args &sa) {
+  chan_by_form(fmt, false, [&](auto f, auto) {
+    hipLaunchKernelGGL((k_channelize_rate<decltype(f)::value, false, true>), grid, dim3(256), geo.lds_bytes, c->stream, d_chunk,
+                       (unsigned long long)n_chunk, up, down, geo.G, geo.NI, geo.xrows, d_tab, d_step, n_ch, d_out, 0u, (float *)nullptr, sa);
   });
 }

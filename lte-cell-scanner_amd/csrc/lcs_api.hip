@@ -1323,6 +1323,58 @@ int lcs_channelize_u8(lcs_ctx *c, const void *d_wide, int fmt, uint64_t n_in, do
   return lcs_launch_channelize_u8(c, a, d_gain);
 }
 
+// The continuous form.  open refuses what the one-shot forms refuse of a rate, a format, the shifts and n_ch -- chan_refusal on a
+// call whose capture and outputs break no rule -- and everything else by chan_stream_refusal; a refused call launches nothing and
+// leaves the stream where it was.
+int lcs_chan_stream_open(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  alignas(16) static char any[16];      // stands for d_wide and d_out: never null, never misaligned, never read
+  const ChanCall a = {any, fmt, ~0ull, fs_in, up, down, f_shift, n_ch, any, 1};
+  const char *what = chan_refusal(a, CHAN_RATE);
+  if (!what) what = chan_stream_refusal(ChanPush{c->chan_stream.open}, CHAN_STREAM_OPEN);
+  if (what) return chan_refused(c, "lcs_chan_stream_open", what);
+  HIPCHK(c, hipSetDevice(c->device));
+  return lcs_chan_stream_start(c, fmt, fs_in, up, down, f_shift, n_ch);
+}
+
+static uint64_t chan_stream_emit(const lcs_ctx *c, uint64_t n_chunk, uint64_t *m_first) {
+  const lcs_ctx::ChanStream &st = c->chan_stream;
+  const unsigned long long m0 = cs_count(st.n_total, st.up, st.down);
+  if (m_first) *m_first = m0;
+  return cs_count(st.n_total + n_chunk, st.up, st.down) - m0;
+}
+
+int lcs_chan_stream_count(lcs_ctx *c, uint64_t n_chunk, uint32_t *n_emit) {
+  if (!c || !n_emit) return LCS_ERR_BAD_ARG;
+  ChanPush a = {c->chan_stream.open};
+  a.n_chunk = n_chunk;
+  if (const char *what = chan_stream_refusal(a, CHAN_STREAM_COUNT)) return chan_refused(c, "lcs_chan_stream_count", what);
+  *n_emit = (uint32_t)chan_stream_emit(c, n_chunk, nullptr);      // < n_chunk <= 2^31
+  return LCS_OK;
+}
+
+int lcs_chan_stream_push(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, uint32_t row_stride, uint32_t out_cap, uint32_t *n_emit,
+                         uint64_t *m_first) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  const bool open = c->chan_stream.open;
+  uint64_t m0 = 0;
+  ChanPush a = {open, c->chan_stream.fmt, d_chunk, n_chunk, d_out, row_stride, out_cap, 0};
+  if (open && n_chunk <= (1ull << 31)) a.n_emit = chan_stream_emit(c, n_chunk, &m0);
+  if (const char *what = chan_stream_refusal(a, CHAN_STREAM_PUSH)) return chan_refused(c, "lcs_chan_stream_push", what);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = lcs_chan_stream_enqueue(c, d_chunk, n_chunk, d_out, row_stride)) return rc;
+  if (n_emit) *n_emit = (uint32_t)a.n_emit;
+  if (m_first) *m_first = m0;
+  return LCS_OK;
+}
+
+int lcs_chan_stream_close(lcs_ctx *c) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (const char *what = chan_stream_refusal(ChanPush{c->chan_stream.open}, CHAN_STREAM_CLOSE)) return chan_refused(c, "lcs_chan_stream_close", what);
+  HIPCHK(c, hipSetDevice(c->device));
+  return lcs_chan_stream_end(c);
+}
+
 int lcs_last_channelize_ms(lcs_ctx *c, float *ms) {
   if (!c || !ms) return LCS_ERR_BAD_ARG;
   return lcs_chan_last_ms(c, ms);

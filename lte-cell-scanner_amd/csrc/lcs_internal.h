@@ -364,6 +364,18 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<float> chan_part;          // lcs_channelize_u8: [n_ch][workgroups along the outputs] sums of |y|^2
   int chan_slot = 0;
   bool chan_timed = false;
+  // the continuous form (lcs_chan_stream_*): one stream per context, with its own parameters, table and history -- the one-shot
+  // calls above stay legal while it is open and touch none of this
+  struct ChanStream {
+    bool open = false;
+    int fmt = 0, up = 0, down = 0, n_ch = 0;
+    DevBuf<char> par;               // [n_ch] phase steps, then the taps
+    DevBuf<float> tab;              // the filter bank in A-operand order, built once by open
+    DevBuf<char> hist[2];           // two history slots of cs_keep_max samples, written in turn
+    int cur = 0;                    // the slot that holds samples [n_total - n_hist, n_total)
+    unsigned n_hist = 0;
+    unsigned long long n_total = 0; // samples pushed since open
+  } chan_stream;
   // results of a batch, compacted on the device (k_pack_results): [8 ints header][n_buf counts][records]; h_res = its page-locked mirror
   DevBuf<char> res_pack;
   PinnedBuf<char> h_res;

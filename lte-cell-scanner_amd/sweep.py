@@ -117,6 +117,80 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     return cells
 
 
+class WidebandFeed:
+    """A band search from a wideband STREAM: push() takes the front end's transfer buffers as they come (n_samples of fmt at fs_in,
+    centred on fc_centre, resident in HBM), the searcher's channelizer stream (Searcher.chan_stream_open, rate = (up, down),
+    (1, decim) for the integer form) continues every carrier over the cuts, and whenever n_cap outputs per carrier are complete
+    they go through the full chain as one FMT_C64 capture per carrier -- fc_requested = fc_programmed = the carrier, fs_programmed =
+    fs_in * up / down, batches of at most 128 carriers, as search_wideband does.  Two [n_ch][n_cap] complex64 buffers are filled in
+    turn; a transfer buffer that straddles a capture's end is split there (chan_stream_count, bisected on the chunk length: counts
+    grow by at most one per sample, so the split is exact).  The searcher's one channelizer stream is this object's until close()."""
+
+    def __init__(self, searcher, fmt: int, fs_in: float, rate, fc_centre: float, carriers, f_search_set, n_cap: int = 153600,
+                 max_cells_per_buf: int = 16):
+        import torch
+        from . import capi
+        self.searcher, self.fmt, self.n_cap, self.max_cells_per_buf = searcher, int(fmt), int(n_cap), int(max_cells_per_buf)
+        self.carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
+        self.f_search_set = f_search_set
+        up, down = int(rate[0]), int(rate[1])
+        self.fs_out = float(fs_in) * up / down
+        self._sample_bytes = {capi.FMT_C64: 8, capi.FMT_IQ_S16: 4, capi.FMT_IQ_S8: 2}.get(self.fmt, 1)
+        dev = getattr(searcher, "device", -1)
+        tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
+        self.bufs = [torch.empty((self.carriers.size, self.n_cap), dtype=torch.complex64, device=tdev) for _ in range(2)]
+        self.cur, self.filled = 0, 0
+        searcher.chan_stream_open(self.fmt, fs_in, up, down, self.carriers - float(fc_centre))
+        self._open = True
+
+    def _longest(self, n: int, room: int) -> int:
+        """the longest chunk of at most n samples that hands out at most `room` outputs"""
+        count = self.searcher.chan_stream_count
+        if count(n) <= room:
+            return n
+        lo, hi = 0, n                  # count(lo) <= room < count(hi)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if count(mid) <= room else (lo, mid)
+        return lo
+
+    def _search(self, buf):
+        from . import capi
+        cells = []
+        for a in range(0, self.carriers.size, 128):
+            fc = self.carriers[a:a + 128]
+            cells += self.searcher.search_batch(buf[a].data_ptr(), capi.FMT_C64, fc.size, self.n_cap, self.f_search_set, fc, fc, self.fs_out,
+                                                capi.STAGE_FULL, self.max_cells_per_buf)
+        return cells
+
+    def push(self, d_ptr: int, n_samples: int):
+        """Feed n_samples at d_ptr (device; they must stay unchanged until the searcher's stream has run the work queued here).
+        Returns the per-carrier cell lists of every capture this push completed: usually []."""
+        done, off, n_samples = [], 0, int(n_samples)
+        while off < n_samples:
+            room = self.n_cap - self.filled
+            n = self._longest(n_samples - off, room)
+            buf = self.bufs[self.cur]
+            n_emit, _ = self.searcher.chan_stream_push(d_ptr + off * self._sample_bytes, n, buf.data_ptr() + 8 * self.filled, self.n_cap, room)
+            off += n
+            self.filled += n_emit
+            if self.filled == self.n_cap:
+                done.append(self._search(buf))
+                self.cur, self.filled = self.cur ^ 1, 0
+        return done
+
+    def close(self):
+        if self._open:
+            self._open = False
+            self.searcher.chan_stream_close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def _all_gather_bytes(arr: np.ndarray, dist, device, world: int) -> List[np.ndarray]:
     """One all-gather of a fixed-size numpy array (viewed as bytes) -> the array of every rank."""
     import torch

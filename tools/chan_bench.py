@@ -19,9 +19,18 @@ correlation kernel); (b) lcs_channelize, then search_batch on the floats.  Each 
 the channelizer to behind the second batch's collect.  Its record -- both times, their ratio, the channelizer's share of (a)
 against the search behind it, the new kernels' resources -- goes under the key "u8"; everything else in the document stays.
 
+--stream compares the continuous form (lcs_chan_stream_push) with the one-shot call on the same samples, in this one process, HIP
+events on the context's stream around each, medians as above: (a) the one-shot call (lcs_channelize on the integer record's
+workload; with --rate 12/125 lcs_channelize_rational on the rational record's); (b) the same capture as 8 equal pushes of a stream
+opened before the clock starts; (c) as 64 pushes; (z) one push that hands out nothing (one sample into a fresh stream: the history
+append alone).  The condition is relative: b <= 1.10 a + 7 z -- seven more launches than one call, and 10 % (twice the +-4 % box
+spread of README, and the recomputed columns).  (c) has no bar.  The record goes under "stream" / "<up>/<down>"; the rest stays.
+
     python tools/chan_bench.py --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --rate 12/125 --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --u8 --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --stream --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --stream --rate 12/125 --out profiles/channelizer/chan_bench.json
 """
 import argparse
 import importlib.util
@@ -59,7 +68,10 @@ def main():
     ap.add_argument("--cells", type=int, default=8, help="cells planted across the band (every 32nd carrier)")
     ap.add_argument("--rate", default=None, metavar="UP/DOWN", help="measure lcs_channelize_rational at this rate change, e.g. 12/125")
     ap.add_argument("--u8", action="store_true", help="time lcs_channelize_u8 + search on bytes against lcs_channelize + search on floats")
+    ap.add_argument("--stream", action="store_true", help="time the continuous form (8 and 64 pushes) against the one-shot call on the same samples")
     args = ap.parse_args()
+    if args.u8 and args.stream:
+        ap.error("--u8 and --stream are two measurements")
     if args.u8 and args.rate:
         ap.error("--u8 runs on the integer record's carriers: it takes no --rate")
     rate = tuple(int(v) for v in args.rate.split("/")) if args.rate else None
@@ -91,6 +103,8 @@ def main():
     th = threading.Thread(target=sclk_sampler, args=(args.device, samples, stop), daemon=True)
     if args.u8:
         return bench_u8(args, pkg, torch, dev, d_wide, d_out, carriers - FC0, carriers, f, n_in, fs_in, D, N_CH, N_OUT, samples, stop, th)
+    if args.stream:
+        return bench_stream(args, pkg, torch, dev, d_wide, carriers - FC0, n_in, fs_in, rate or (1, D), samples, stop, th)
     with pkg.Searcher(args.device) as s:
         stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
         th.start()
@@ -150,6 +164,71 @@ def main():
     print(json.dumps(res))
 
 
+def bench_stream(args, pkg, torch, dev, d_wide, shifts, n_in, fs_in, rate, samples, stop, th):
+    up, down = rate
+    n_ch = len(shifts)
+    n_out = (n_in * up - 16 * down) // down + 1          # M(n_in): all the capture gives
+    d_out = torch.empty((n_ch, n_out), dtype=torch.complex64, device=dev)
+    torch.cuda.synchronize(dev)
+    t = {"a": [], "b": [], "c": [], "z": []}
+    emitted = {}
+    with pkg.Searcher(args.device) as s:
+        stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        def pushes(n_push):
+            edges = [n_in * k // n_push for k in range(n_push + 1)]
+            filled = 0
+            for a, b in zip(edges[:-1], edges[1:]):
+                n_emit, _ = s.chan_stream_push(d_wide.data_ptr() + 4 * a, b - a, d_out.data_ptr() + 8 * filled, n_out, n_out - filled)
+                filled += n_emit
+            emitted[n_push] = filled
+
+        th.start()
+        for i in range(args.warmup + args.reps):      # interleaved: every form sees the same clocks
+            t["a"].append(timed(lambda: s.channelize_rational(d_wide.data_ptr(), pkg.FMT_IQ_S16, n_in, fs_in, up, down, shifts, d_out.data_ptr(), n_out)))
+            for key, n_push in (("b", 8), ("c", 64)):
+                s.chan_stream_open(pkg.FMT_IQ_S16, fs_in, up, down, shifts)
+                t[key].append(timed(lambda: pushes(n_push)))
+                s.chan_stream_close()
+            s.chan_stream_open(pkg.FMT_IQ_S16, fs_in, up, down, shifts)
+            t["z"].append(timed(lambda: s.chan_stream_push(d_wide.data_ptr(), 1, d_out.data_ptr(), n_out, n_out)))
+            s.chan_stream_close()
+        stop.set()
+        th.join(timeout=10)
+    assert emitted == {8: n_out, 64: n_out}, emitted
+    med = lambda v: float(np.median(v[args.warmup:]))
+    a, b, c, z = med(t["a"]), med(t["b"]), med(t["c"]), med(t["z"])
+    spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "tools", "code_objects.py"))
+    co = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(co)
+    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items()
+          if "k_chan_keep" in k or ("k_channelize" in k and "Lb0ELb1E" in k)}
+    res = {"a_one_shot_ms": a, "b_8_pushes_ms": b, "c_64_pushes_ms": c, "z_push_without_output_ms": z, "bound_ms": 1.10 * a + 7.0 * z,
+           "meets_condition": bool(b <= 1.10 * a + 7.0 * z), "ratio_b_over_a": b / a, "ratio_c_over_a": c / a,
+           "config": {"up": up, "down": down, "fs_in": fs_in, "fmt": "s16", "n_ch": n_ch, "n_in": n_in, "n_out": n_out, "reps": args.reps, "warmup": args.warmup},
+           "ms_min_max": {k: [float(min(v[args.warmup:])), float(max(v[args.warmup:]))] for k, v in t.items()},
+           "sclk_mhz_median": (sorted(samples)[len(samples) // 2] if samples else None), "sclk_samples": len(samples),
+           "device": torch.cuda.get_device_name(dev), "kernels": ks}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    try:
+        with open(args.out) as fh:
+            old = json.load(fh)
+    except (OSError, ValueError):
+        old = {}
+    with open(args.out, "w") as fh:
+        json.dump(dict(old, stream=dict(old.get("stream", {}), **{"%d/%d" % (up, down): res})), fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
 def bench_u8(args, pkg, torch, dev, d_wide, d_c64, shifts, carriers, f, n_in, fs_in, D, N_CH, N_OUT, samples, stop, th):
     d_u8 = torch.empty((N_CH, N_OUT, 2), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
@@ -185,7 +264,7 @@ def bench_u8(args, pkg, torch, dev, d_wide, d_c64, shifts, carriers, f, n_in, fs
     co = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(co)
     ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items()
-          if "k_chan_quant_u8" in k or ("k_channelize" in k and "Lb1E" in k)}
+          if "k_chan_quant_u8" in k or ("k_channelize" in k and "Lb1ELb0E" in k)}
     res = {"a_u8_pipeline_ms": a, "b_c64_pipeline_ms": b, "ratio_a_over_b": a / b, "u8_is_faster": bool(a < b),
            "a_channelize_u8_ms": a_chan, "a_search_ms": a - a_chan, "a_channelizer_share_of_search": a_chan / (a - a_chan), "target_share": 0.25,
            "meets_target": bool(a_chan <= 0.25 * (a - a_chan)), "b_channelize_ms": b_chan, "b_search_ms": b - b_chan,
