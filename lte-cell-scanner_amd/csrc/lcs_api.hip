@@ -10,22 +10,9 @@
 #include "lcs_internal.h"
 #include "channelizer.h"
 #include "lte_device.h"
+#include "pss_ref.h"
 
 namespace {
-
-XcGeom make_geo(uint32_t n_cap, int n_f, int ds, int cpg = LCS_TG) {
-  XcGeom g;
-  g.n_cap = n_cap;
-  g.n_f = n_f;
-  g.n_tmpl = 3 * n_f;
-  g.cpg = cpg;
-  g.G = (g.n_tmpl + cpg - 1) / cpg;
-  g.n_comb = (int)((n_cap - 136 - 100) / 9600);   // ref src/searcher.cpp:276
-  g.ds = ds;
-  g.foi0 = 0;
-  g.n_narrow = (n_f == 1 || cpg == 3) ? g.n_comb : 0;     // one hypothesis per group: no spread at all; otherwise pack_grid looks at the grid
-  return g;
-}
 
 // Grow the workspace so that n_slots buffers of n_cap samples with n_f hypotheses fit.
 int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int G_need = 0) {
@@ -144,50 +131,7 @@ int ensure_res_pack(lcs_ctx *c, int n_buf) {
   return LCS_OK;
 }
 
-// One walk over the (window, group) pairs of a frequency grid packed `cpg` template columns per group: the largest spread of the
-// window starts inside one template group (see k_prep_tables; the correlation kernels hold 137 taps + that spread), and the number
-// of leading combining windows in which every group's spread stays within LCS_NARROW_SPREAD samples (the spread grows with the
-// window index; the count stops at the first window that exceeds it).
-struct GridSpread { int worst, n_narrow; };
-GridSpread grid_spread(const XcGeom &geo, const double *fset, double fc_req, double fc_prog, double fs_prog) {
-  GridSpread r{0, geo.n_comb};
-  for (int w = 0; w < geo.n_comb; ++w)
-    for (int g = 0; g < geo.G; ++g) {
-      const int c_hi = std::min(g * geo.cpg + geo.cpg - 1, geo.n_tmpl - 1);
-      const int f_lo = (g * geo.cpg) / 3, f_hi = c_hi / 3;
-      int mn = 0, mx = 0;
-      for (int f = f_lo; f <= f_hi; ++f) {
-        const double kf = (fc_req - fset[f]) / fc_prog;
-        const int s = (int)std::rint((((double)w * .005) * kf) * fs_prog);
-        if (f == f_lo) { mn = mx = s; } else { mn = std::min(mn, s); mx = std::max(mx, s); }
-      }
-      r.worst = std::max(r.worst, mx - mn);
-      if (mx - mn > LCS_NARROW_SPREAD) r.n_narrow = std::min(r.n_narrow, w);
-    }
-  return r;
-}
-
-// Choose how the 3 n_f templates are packed into 16-column groups: densely when the window starts of a group's
-// hypotheses stay within `max_taps` - 137 samples of each other over the whole buffer (every grid the CLI builds), else
-// with fewer whole hypotheses per group -- one per group always fits (its three templates share a window start).
-XcGeom pack_grid(uint32_t n_cap, int n_f, int ds, const double *fset, const double *fc_req, const double *fc_prog, int n_buf,
-                 double fs_prog, int max_taps) {
-  static const int packings[] = {LCS_TG, 15, 12, 9, 6, 3};
-  for (int cpg : packings) {
-    XcGeom geo = make_geo(n_cap, n_f, ds, cpg);
-    GridSpread all{0, geo.n_comb};
-    for (int i = 0; i < n_buf && (cpg == 3 || 137 + all.worst <= max_taps); ++i)      // (a packing that does not fit is left at once)
-      if (i == 0 || fc_req[i] != fc_req[i - 1] || fc_prog[i] != fc_prog[i - 1]) {
-        const GridSpread s = grid_spread(geo, fset, fc_req[i], fc_prog[i], fs_prog);
-        all = GridSpread{std::max(all.worst, s.worst), std::min(all.n_narrow, s.n_narrow)};
-      }
-    if (137 + all.worst <= max_taps || cpg == 3) {
-      geo.n_narrow = all.n_narrow;
-      return geo;
-    }
-  }
-  return make_geo(n_cap, n_f, ds, 3);
-}
+const double kPeakThresh = std::pow(10.0, -12.0 / 10.0);                  // peak_search: udb10(-12.0), what lies below this fraction of a found peak is cleared (ref src/searcher.cpp:501)
 constexpr int kMaxTapsI8 = LCS_I8_MAX_TAPS;                               // int8 kernel: 137 taps + delays below LCS_I8_OFF (the fp16 kernel holds 160)
 constexpr int kMaxTapsF32 = 2 * (LCS_KP2_MAX - LCS_KP2_UNROLL);          // fp32 kernel: 124 tap pairs
 
@@ -492,7 +436,7 @@ int lcs_peak_search(lcs_ctx *c, const double *pow_, const int32_t *frq, const do
   Launch L = make_launch(c, 1, 153600, CapSrc{});
   L.geo = make_geo(153600, n_f, ds_comb_arm);
   if ((rc = lcs_launch_single_layout(c, L, 0, c->sref, 0))) return rc;
-  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), false))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, false))) return rc;
   std::vector<lcs_cell> tmp;
   int n = 0;
   if ((rc = read_peak_table(c, tmp, &n))) return rc;
@@ -560,7 +504,7 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   L.needed_rows_only = true;
   L.tfoec_parts = 2;
   if ((rc = lcs_launch_xcorr(c, L, false, true))) return rc;
-  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, true))) return rc;
   int rounds = 0;
   if (stage_mask & 2) {
     // The per-cell stages hold max_work cells at a time, in rounds.  Round 4: the batch before is the predictor for how many
@@ -977,7 +921,7 @@ int lcs_search_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const do
   L.repair = FrqRepair::peaks_only;      // no array leaves this call: the peak list is what has to be exact
   L.needed_rows_only = true;
   if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
-  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, true))) return rc;
   if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
   return read_cells_and_peaks(c, cells, nullptr, max_cells, n_cells, peaks, max_peaks, n_peaks);
 }
@@ -1061,7 +1005,7 @@ int lcs_foe_finish(lcs_ctx *c, const void *d_words, const double *d_meta, const 
   // peak_search names the winning hypothesis by its GLOBAL index: the whole grid now, not this rank's share
   HIPCHK(c, hipMemcpyAsync(c->fset_ws, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   if ((rc = lcs_launch_foe_unpack(c, L, static_cast<const long long *>(d_words), d_meta))) return rc;
-  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, true))) return rc;
   if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
   return read_cells_and_peaks(c, cells, order, max_cells, n_cells, peaks, max_peaks, n_peaks);
 }
@@ -1092,7 +1036,7 @@ int stream_chain(lcs_ctx *c, int k) {
   L.xc = c->st_fmt == LCS_FMT_IQ_U8 ? XcKernel::i8 : XcKernel::fp32;      // one hypothesis: no window-start spread, the int8 kernel always fits
   L.needed_rows_only = true;
   if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
-  if ((rc = lcs_launch_peak_search(c, L, std::pow(10.0, -12.0 / 10.0), true))) return rc;
+  if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, true))) return rc;
   if ((rc = launch_per_peak(c, L, 0, 1))) return rc;
   HIPCHK(c, hipMemcpyAsync(h->res, c->peaks, sizeof(h->res), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&h->n_peaks, c->npeaks, sizeof(int), hipMemcpyDeviceToHost, c->stream));

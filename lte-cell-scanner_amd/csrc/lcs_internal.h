@@ -5,7 +5,7 @@
 //   cap32   [S][n_cap]            float2   capture buffer, fp32 (PSS correlation input)
 //   cap64   [1][n_cap]            double2  fp64 copy, only when a host entry point hands over complex<double>
 //   tmpl    [S][n_f][3][137]      float2   conj(fshift(pss_td))/137   (searcher.cpp:146-151)
-//   start   [S][NW][n_f]          int      round_i(m*.005*k_factor*fs) (searcher.cpp:298)
+//   start   [S][NW][n_f]          int      window starts (pss_ref.h: lcs_win_start)
 //   smin/kp2[S][NW][G]            int      per (window, 16-template group): first lag offset, tap pairs
 //   btab    [S][NW][G][KP2][64]   float    MFMA B operands: delay-shifted templates (fp32 kernel)
 //   brow8   [S][G][LCS_I8_IMG]    uint32   int8 kernel: three-digit operand rows of a group, as they sit in LDS
@@ -24,6 +24,7 @@
 #include "../../include/lcs.h"
 #include "lcs_mem.h"
 
+#define FS_LTE 30720000.0    // LTE sampling rate at 2048 subcarriers; the searcher works at FS_LTE / 16
 #define LCS_NW_MAX 16        // incoherent-combining windows (15 for a 153600-sample buffer)
 // Frequency hypotheses per call: the reference loops over whatever f_search_set holds (src/searcher.cpp:113-174; CellSearch builds
 // n_f = 2 floor((fc ppm / 1e6 + 2500) / 5000) + 1, src/CellSearch.cpp:463-465: 125 at 2.6 GHz, 289 at 6 GHz for the default 120 ppm).
@@ -125,21 +126,39 @@ __device__ __forceinline__ void lcs_wave_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// What the kind of source decides, in one place: the raw sample type, where a slot starts, and the sample as the fp64 stages see it.
+template <int KIND> struct CapKind;
+template <> struct CapKind<0> {
+  typedef uint16_t T;
+  static __host__ __device__ __forceinline__ const T *slot(const CapSrc &s, int slot) { return s.c8 + (size_t)slot * lcs_cap8_stride(s.n_cap); }
+  static __host__ __device__ __forceinline__ const T *of(const CapView &v) { return v.c8; }
+  static __host__ __device__ __forceinline__ double2 cvt(T p) {      // (u8 - 127) / 128 of the int8 pair 127 - u8
+    return make_double2(-(double)(int)(int8_t)(p & 255u) / 128.0, -(double)(int)(int8_t)(p >> 8) / 128.0);
+  }
+};
+template <> struct CapKind<1> {
+  typedef float2 T;
+  static __host__ __device__ __forceinline__ const T *slot(const CapSrc &s, int slot) { return s.c32 + (size_t)slot * s.n_cap; }
+  static __host__ __device__ __forceinline__ const T *of(const CapView &v) { return v.c32; }
+  static __host__ __device__ __forceinline__ double2 cvt(T f) { return make_double2((double)f.x, (double)f.y); }
+};
+template <> struct CapKind<2> {
+  typedef double2 T;
+  static __host__ __device__ __forceinline__ const T *slot(const CapSrc &s, int slot) { return s.c64 + (size_t)slot * s.n_cap; }
+  static __host__ __device__ __forceinline__ const T *of(const CapView &v) { return v.c64; }
+  static __host__ __device__ __forceinline__ double2 cvt(T d) { return d; }
+};
 __device__ __forceinline__ CapView cap_view(const CapSrc &s, int slot) {
   CapView v;
-  v.c32 = s.c32 ? s.c32 + (size_t)slot * s.n_cap : nullptr;
-  v.c64 = s.c64 ? s.c64 + (size_t)slot * s.n_cap : nullptr;
-  v.c8 = s.c8 ? s.c8 + (size_t)slot * lcs_cap8_stride(s.n_cap) : nullptr;
+  v.c32 = s.c32 ? CapKind<1>::slot(s, slot) : nullptr;
+  v.c64 = s.c64 ? CapKind<2>::slot(s, slot) : nullptr;
+  v.c8 = s.c8 ? CapKind<0>::slot(s, slot) : nullptr;
   return v;
 }
 __device__ __forceinline__ double2 cap_at(const CapView &v, size_t i) {
-  if (v.c64) return v.c64[i];
-  if (v.c8) {
-    const uint32_t p = v.c8[i];
-    return make_double2(-(double)(int)(int8_t)(p & 255u) / 128.0, -(double)(int)(int8_t)(p >> 8) / 128.0);
-  }
-  const float2 f = v.c32[i];
-  return make_double2((double)f.x, (double)f.y);
+  if (v.c64) return CapKind<2>::cvt(v.c64[i]);
+  if (v.c8) return CapKind<0>::cvt(v.c8[i]);
+  return CapKind<1>::cvt(v.c32[i]);
 }
 #endif
 

@@ -32,6 +32,28 @@ __host__ __device__ __forceinline__ cd2 cis_small(double x) {
   c_ = fma(c_, z, 1.0);
   return mk(c_, x * s_);
 }
+// Sixteen samples of a capture buffer for the register-resident 128-point transform (fft128_x8): x[j] = sample IDX::at(loc, l, j),
+// zero where that lies outside the buffer (the reference's mid() would read out of bounds) or !valid.  Sixteen loads in flight in
+// the source's own width, no branch between them; converted afterwards (conversions between the loads needed every register the
+// callers' waves can have).  Returns the mask of slots that lie inside the buffer.
+template <int KIND, class IDX>
+__device__ __forceinline__ unsigned cap_load16(const CapView &cap, long loc, int l, uint32_t n_cap, bool valid, cd2 (&x)[16]) {
+  typename CapKind<KIND>::T raw[16];
+  unsigned in_mask = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const long sidx = IDX::at(loc, l, j);
+    const bool in = valid && sidx >= 0 && (uint64_t)sidx < n_cap;
+    in_mask |= (in ? 1u : 0u) << j;
+    raw[j] = CapKind<KIND>::of(cap)[in ? (size_t)sidx : 0];
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const double2 v = CapKind<KIND>::cvt(raw[j]);
+    x[j] = ((in_mask >> j) & 1u) ? mk(v.x, v.y) : mk(0, 0);
+  }
+  return in_mask;
+}
 // Is one component of a capture a dongle sample, (b - 127) / 128 for a byte b (ref src/capbuf.cpp:172-181)?  Accepted iff it
 // COMPARES EQUAL to one of those 256 values (-0.0 as 0.0 -> b = 127); *byte = b only then (127 otherwise).  The decision is made
 // on k = x * 128: a power-of-two scale is exact in either type (a subnormal only grows), where x * 128 + 127 rounds -- in fp32
@@ -78,7 +100,7 @@ __host__ __device__ __forceinline__ TrkCutCell trk_cut_cell(int cp_type, double 
                                                             double ts0, long k0, long pos0) {
   TrkCutCell r;
   const double k_factor = (fc_req - freq_off) / fc_prog;
-  r.step = (30720000.0 / 16) / (fs_prog * k_factor);
+  r.step = (FS_LTE / 16) / (fs_prog * k_factor);
   r.ft = frame_timing;
   r.ts0 = ts0;
   r.normal = cp_type == LCS_CP_NORMAL;
@@ -360,6 +382,77 @@ __device__ __forceinline__ void qpsk_llr(cd2 sym, double np, double &l0, double 
   }
   l0 = trunc_log(metric[0] + metric[1]) - trunc_log(metric[2] + metric[3]);
   l1 = trunc_log(metric[0] + metric[2]) - trunc_log(metric[1] + metric[3]);
+}
+
+// ---- PBCH symbols of one attempt (four frames): extraction, equalisation, LLRs (ref src/searcher.cpp:1503-1520, :1571-1612;
+// src/tracker_thread.cpp:494-529, :555-705).  The searcher's and the tracker's kernels differ in how a row of the grid is addressed
+// and where the noise powers come from; the rest is here.
+// Symbol idx of the attempt sits in frame `fr`, PBCH OFDM symbol `sym` (0 .. 3 of slot 1), subcarrier `scx` of the 72: the symbols
+// that carry reference signals leave out every third subcarrier, the one congruent to n_id_cell mod 3
+struct PbchRe { int fr, sym, scx; };
+__device__ __forceinline__ PbchRe pbch_re(int idx, int per_frame, int n_symb, int id) {
+  const int v3 = d_imod(id, 3);
+  const int r0 = (v3 == 0) ? 1 : 0, r1 = (v3 == 2) ? 1 : 2;     // the two residues != v3, ascending
+  PbchRe r;
+  r.fr = idx / per_frame;
+  int rem = idx % per_frame;
+  if (rem < 48) r.sym = 0; else if (rem < 96) { r.sym = 1; rem -= 48; } else if (rem < 168) { r.sym = 2; rem -= 96; } else { r.sym = 3; rem -= 168; }
+  const bool has_rs = (r.sym == 0) || (r.sym == 1) || (r.sym == 3 && n_symb == 6);
+  r.scx = has_rs ? (3 * (rem / 2) + ((rem & 1) ? r1 : r0)) : rem;
+  return r;
+}
+// the two antenna ports the pair starting at symbol t is equalised with (ref :1582-1611): port 0 (and 1) for one / two ports; with
+// four, pairs alternate between ports (0, 2) and (1, 3)
+__device__ __forceinline__ void pbch_pair_ports(int n_ports, int t, int &pa, int &pb) {
+  pa = (n_ports == 4 && (t & 3) != 0) ? 1 : 0;
+  pb = (n_ports == 2) ? 1 : (n_ports == 4 ? pa + 2 : 0);
+}
+// One symbol pair x through the channels ha, hb of its two ports with noise powers npa, npb -> symbols and their noise powers.
+// POW_SQ: |h|^2 from pow(., 2) as the reference writes it (the tracker's kernel; this device's pow is not a product to the last
+// bit) or from products (the searcher's kernel) -- each kernel keeps the bits it has always produced.
+template <bool POW_SQ> __device__ __forceinline__ double pbch_sq(double x) { return POW_SQ ? pow(x, 2) : x * x; }
+template <bool POW_SQ>
+__device__ __forceinline__ void pbch_equalise_pair(int n_ports, const cd2 (&x)[2], const cd2 (&ha)[2], const cd2 (&hb)[2], double npa, double npb,
+                                                   cd2 (&syms)[2], double (&npv)[2]) {
+  if (n_ports == 1) {
+    for (int q = 0; q < 2; ++q) {
+      const cd2 gain = cconj(cdiv(ha[q], mk(cabs2(ha[q]), 0)));
+      syms[q] = cmul(x[q], gain);
+      npv[q] = npa * cabs2(gain);
+    }
+  } else {
+    const cd2 h1 = cdivr(cadd(ha[0], ha[1]), 2), h2 = cdivr(cadd(hb[0], hb[1]), 2);
+    const double np_temp = (npa + npb) / 2;
+    const double scale = pbch_sq<POW_SQ>(h1.re) + pbch_sq<POW_SQ>(h1.im) + pbch_sq<POW_SQ>(h2.re) + pbch_sq<POW_SQ>(h2.im);
+    const cd2 s0 = cdivr(cadd(cmul(cconj(h1), x[0]), cmul(h2, cconj(x[1]))), scale);
+    const cd2 s1 = cconj(cdivr(cadd(cmul(mk(-h2.re, h2.im), x[0]), cmul(h1, cconj(x[1]))), scale));
+    const double a1 = hypot(h1.re, h1.im) / scale, a2 = hypot(h2.re, h2.im) / scale;
+    const double s2 = pow(2.0, 0.5);
+    syms[0] = cscale(s0, s2); syms[1] = cscale(s1, s2);
+    npv[0] = npv[1] = (a1 * a1 + a2 * a2) * np_temp;
+  }
+}
+// soft demodulation (exact log-MAP, qpsk_llr) and descrambling of the pair starting at symbol t: four LLRs into e_est
+__device__ __forceinline__ void pbch_llr_store(const cd2 (&syms)[2], const double (&npv)[2], const uint8_t *__restrict__ scr, int t, double *__restrict__ e_est) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int l = t + q;
+    double l0, l1;
+    qpsk_llr(syms[q], npv[q], l0, l1);
+    if (scr[2 * l]) l0 = -l0;
+    if (scr[2 * l + 1]) l1 = -l1;
+    e_est[2 * l] = l0; e_est[2 * l + 1] = l1;
+  }
+}
+// the first six bits of the MIB (ref :1640-1667); n_rb_dl = 0 for a reserved bandwidth code
+struct MibFields { int n_rb_dl, phich_duration, phich_resource; };
+__host__ __device__ __forceinline__ MibFields mib_fields(unsigned bits) {
+  const int b0 = bits & 1u, b1 = (bits >> 1) & 1u, b2 = (bits >> 2) & 1u, bw = b0 * 4 + b1 * 2 + b2;
+  MibFields f;
+  f.n_rb_dl = bw == 0 ? 6 : (bw == 1 ? 15 : (bw == 2 ? 25 : (bw == 3 ? 50 : (bw == 4 ? 75 : (bw == 5 ? 100 : 0)))));
+  f.phich_duration = ((bits >> 3) & 1u) ? 2 : 1;
+  f.phich_resource = 1 + (int)((bits >> 4) & 1u) * 2 + (int)((bits >> 5) & 1u);
+  return f;
 }
 
 // ---- tail-biting Viterbi of the PBCH decoder (K = 7, G = (133,171,165)o, 40 steps; ref src/lte_lib.cpp:538-551 -> itpp

@@ -9,6 +9,7 @@
 // peak_ind < ds_comb_arm (quirk Q2), +-274 cancellation in the peak's own row, the no-op
 // "other PSS" loop (quirk Q1, omitted because it has no effect), the -12 dB floor.
 #include "lcs_internal.h"
+#include "pss_ref.h"
 
 #define PS_THREADS 1024
 #define PS_MAX_ITER 4096
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(256) void k_foe_pack(const float *__restrict__ pow3
 }
 __global__ __launch_bounds__(256) void k_foe_unpack(const long long *__restrict__ words, const double *__restrict__ meta, double *__restrict__ pow_,
                                                     float *__restrict__ pow32, int *__restrict__ frq, double *__restrict__ spinc, double *__restrict__ zth,
-                                                    double R_th1, double rx_cutoff, int ds) {
+                                                    SpArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < 3 * LCS_N_IDX) {
     const long long w = words[i];
@@ -283,7 +284,8 @@ __global__ __launch_bounds__(256) void k_foe_unpack(const long long *__restrict_
   if (i < LCS_N_IDX) {
     const double v = meta[i];
     spinc[i] = v;
-    zth[i] = R_th1 * v / rx_cutoff / 137 / 2 / (int)meta[LCS_N_IDX] / (2 * ds + 1);      // src/CellSearch.cpp:500-503, as k_sp_fold
+    a.n_comb_xc = (int)meta[LCS_N_IDX];      // the sending ranks' count
+    zth[i] = lcs_z_th1(a, v);
   }
 }
 int lcs_launch_foe_pack(lcs_ctx *c, const Launch &L, long long *d_words, double *d_meta) {
@@ -294,11 +296,8 @@ int lcs_launch_foe_pack(lcs_ctx *c, const Launch &L, long long *d_words, double 
   return LCS_OK;
 }
 int lcs_launch_foe_unpack(lcs_ctx *c, const Launch &L, const long long *d_words, const double *d_meta) {
-  const XcGeom &geo = L.geo;
-  const double R_th1 = lcs_tables::chi2cdf_inv(1 - pow(10.0, -12), 2.0 * geo.n_comb * (2 * geo.ds + 1));
-  const double rx_cutoff = (6 * 12 * 15e3 / 2 + 4 * 15e3) / (30720000.0 / 16 / 2);
   hipLaunchKernelGGL(k_foe_unpack, dim3((3 * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, d_words, d_meta, c->pow_, reinterpret_cast<float *>(c->work.get()),
-                     c->frq, c->spinc, c->zth, R_th1, rx_cutoff, geo.ds);
+                     c->frq, c->spinc, c->zth, make_sp_args(L.geo));
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

@@ -9,7 +9,7 @@
 // (a "group" of consecutive (foi, pss) pairs) and walks the 15 windows; per window it stages
 // 64+K' capture samples in LDS (planar, conflict-free), correlates them against the group's
 // templates and accumulates |xc|^2 in registers.  The per-foi window start
-// round_i(m*.005*k_factor*fs) differs between the templates of a group by a few samples; that
+// (lcs_win_start, pss_ref.h) differs between the templates of a group by a few samples; that
 // delay is folded into the template ("B") table, which therefore holds zero-padded, shifted
 // copies of conj(fshift(pss_td))/137.  Raw xc never touches HBM.
 //
@@ -21,6 +21,7 @@
 // operands (template rows) stream through LDS.
 #include "lcs_internal.h"
 #include "lte_device.h"
+#include "pss_ref.h"
 #include <algorithm>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -148,32 +149,19 @@ __global__ __launch_bounds__(256) void k_prep_tables(const SlotParams *__restric
   // starts and per-group offsets are few: workgroup y = 0 does them
   for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < geo.n_f * 3 * 137; i += gridDim.y * blockDim.x) {
     const int m = i % 137, t = (i / 137) % 3, foi = i / (137 * 3);
-    const double f_off = fset[foi];
-    const double kf = (p.fc_req - f_off) / p.fc_prog;
-    const double fs = p.fs_prog * kf;
-    const double k = M_PI * f_off / (fs / 2);
-    const double ang = k * (double)m;
-    const double cs = cos(ang), sn = sin(ang);
-    const double2 s = pss_td[t * 137 + m];
-    const double rr = s.x * cs - s.y * sn, ri = s.x * sn + s.y * cs;   // seq*coeff
-    tmpl[(((size_t)slot * NFM + foi) * 3 + t) * 137 + m] = make_float2((float)(rr / 137), (float)(-ri / 137));
+    tmpl[(((size_t)slot * NFM + foi) * 3 + t) * 137 + m] = pss_xc_round(pss_tmpl_tap(p, fset[foi], pss_td[t * 137 + m], m));
   }
   if (blockIdx.y != 0) return;
-  // round_i(m*.005*k_factor*fs_programmed), evaluated left to right (ref :298)
-  auto win_start = [&](int w, int foi) { return (int)rint((((double)w * .005) * ((p.fc_req - fset[foi]) / p.fc_prog)) * p.fs_prog); };
   for (int i = threadIdx.x; i < geo.n_f * geo.n_comb; i += blockDim.x) {
     const int w = i / geo.n_f, foi = i - w * geo.n_f;
-    start[((size_t)slot * NW + w) * NFM + foi] = win_start(w, foi);
+    start[((size_t)slot * NW + w) * NFM + foi] = lcs_win_start(p, fset[foi], w);
   }
   for (int i = threadIdx.x; i < geo.n_comb * geo.G; i += blockDim.x) {
     const int w = i / geo.G, g = i % geo.G;
-    const int c_hi = min(g * geo.cpg + geo.cpg - 1, geo.n_tmpl - 1);
-    const int f_lo = (g * geo.cpg) / 3, f_hi = c_hi / 3;
-    int mn = win_start(w, f_lo), mx = mn;       // (any grid size: recomputed, a group spans at most 7 hypotheses)
-    for (int f = f_lo + 1; f <= f_hi; ++f) { const int s = win_start(w, f); mn = min(mn, s); mx = max(mx, s); }
-    int k2 = (137 + (mx - mn) + 1) / 2;
+    const WinSpan sp = lcs_group_span(geo, p, fset, g, w);       // (any grid size: recomputed, a group spans at most 7 hypotheses)
+    int k2 = (137 + (sp.mx - sp.mn) + 1) / 2;
     if (k2 > LCS_KP2_MAX - LCS_KP2_UNROLL) k2 = LCS_KP2_MAX - LCS_KP2_UNROLL;   // rejected on the host before launch (lcs_api.hip)
-    smin[((size_t)slot * NW + w) * GM + g] = mn;
+    smin[((size_t)slot * NW + w) * GM + g] = sp.mn;
     kp2[((size_t)slot * NW + w) * GM + g] = k2;
   }
 }
@@ -356,11 +344,6 @@ __global__ __launch_bounds__(NWV * 64, WPS) void k_xcorr_mfma_blk(const float2 *
 // and the detection threshold of the main loop (ref src/CellSearch.cpp:500-503).  The reference
 // updates sp with a serial recurrence; here every window sum is formed directly in fp64 (differs
 // from the recurrence at the 1e-14 relative level).
-struct SpArgs {
-  int n_comb_sp;
-  double R_th1, rx_cutoff;
-  int n_comb_xc, ds;
-};
 // grid (tiles of 1024 positions, windows, slots): sp_all[slot][m][i].  Each lane owns 16
 // consecutive positions: the 274-sample sum of its first position is formed from 17 sixteen-sample
 // segment sums (shared through LDS) plus two samples, then 15 sliding updates (the reference's own
@@ -432,7 +415,7 @@ __global__ __launch_bounds__(256) void k_sp_fold(const double *__restrict__ sp_a
     const double v = acc / a.n_comb_sp;
     const int o = (i + 137) % 9600;
     spinc[(size_t)slot * 9600 + o] = v;
-    zth[(size_t)slot * 9600 + o] = a.R_th1 * v / a.rx_cutoff / 137 / 2 / a.n_comb_xc / (2 * a.ds + 1);
+    zth[(size_t)slot * 9600 + o] = lcs_z_th1(a, v);
   }
 }
 
@@ -493,7 +476,7 @@ __global__ __launch_bounds__(256) void k_sp_i8(const uint16_t *__restrict__ cap8
       const double vv = acc[r] / a.n_comb_sp;
       const int o = (i + 137) % 9600;
       spinc[(size_t)slot * 9600 + o] = vv;
-      zth[(size_t)slot * 9600 + o] = a.R_th1 * vv / a.rx_cutoff / 137 / 2 / a.n_comb_xc / (2 * a.ds + 1);
+      zth[(size_t)slot * 9600 + o] = lcs_z_th1(a, vv);
     }
   }
 }
@@ -750,24 +733,14 @@ __global__ __launch_bounds__(256) void k_xc_debug(const double2 *__restrict__ ca
   const SlotParams p = params[0];
   if (threadIdx.x < 137) {
     const int m = threadIdx.x;
-    const double f_off = fset[foi];
-    const double kf = (p.fc_req - f_off) / p.fc_prog;
-    const double fs = p.fs_prog * kf;
-    const double k = M_PI * f_off / (fs / 2);
-    const double cs = cos(k * (double)m), sn = sin(k * (double)m);
-    const double2 s = pss_td[t * 137 + m];
-    temp[m] = make_double2((s.x * cs - s.y * sn) / 137, -(s.x * sn + s.y * cs) / 137);
+    temp[m] = pss_tmpl_tap(p, fset[foi], pss_td[t * 137 + m], m);
   }
   __syncthreads();
   const uint32_t n_k = geo.n_cap - 136;
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n_k; k += gridDim.x * blockDim.x) {
-    double ar = 0, ai = 0;
-    for (int m = 0; m < 137; ++m) {
-      const double2 a = temp[m], b = cap64[k + m];
-      ar += a.x * b.x - a.y * b.y;
-      ai += a.x * b.y + a.y * b.x;
-    }
-    xc[((size_t)t * n_k + k) * geo.n_f + foi] = make_float2((float)ar, (float)ai);
+    double2 acc = make_double2(0.0, 0.0);      // pss_tap_sum's loop with the 32-bit index it had here (as a pointer walk: 47 registers for 32)
+    for (int m = 0; m < 137; ++m) pss_tap<2>(acc, temp[m], cap64[k + m]);
+    xc[((size_t)t * n_k + k) * geo.n_f + foi] = pss_xc_round(acc);
   }
 }
 
@@ -802,10 +775,6 @@ __device__ __forceinline__ float repair_gpu_value(const float *__restrict__ sgs,
 #define REPAIR_THREADS 256
 #define REPAIR_CROWDED 32          // listed positions per workgroup beyond which the work is bounded (see k_frq_repair)
 #define REPAIR_WG_BUDGET 256       // candidates a workgroup recomputes at most once the list is crowded
-template <int KIND> struct RepairSample;
-template <> struct RepairSample<0> { typedef uint16_t T; static __device__ __forceinline__ double2 cvt(uint16_t p) { return make_double2(-(double)(int)(int8_t)(p & 255u) / 128.0, -(double)(int)(int8_t)(p >> 8) / 128.0); } };
-template <> struct RepairSample<1> { typedef float2 T; static __device__ __forceinline__ double2 cvt(float2 f) { return make_double2((double)f.x, (double)f.y); } };
-template <> struct RepairSample<2> { typedef double2 T; static __device__ __forceinline__ double2 cvt(double2 d) { return d; } };
 // SPLIT (lcs_foe_contend: one buffer's hypotheses split over GPUs): the candidates are this rank's hypotheses within the distance
 // of the GLOBAL maximum (from the all-reduced words) plus the global winner itself, whoever owns it -- every rank holds the whole
 // buffer and the whole grid (fset = the GLOBAL grid here, this rank's hypotheses sit at foi0 ..) -- and the result goes into a
@@ -819,14 +788,12 @@ __global__ __launch_bounds__(REPAIR_THREADS) void k_frq_repair(const float *__re
                                                                const long long *__restrict__ words, long long *__restrict__ words2,
                                                                const double *__restrict__ zth, int *__restrict__ n_skipped, XcGeom geo) {
   LCS_TAIL_PRIO();
-  typedef typename RepairSample<KIND>::T ST;
+  typedef typename CapKind<KIND>::T ST;
   __shared__ double2 s_tmpl[137];
   __shared__ ST s_smp[LCS_NW_MAX][REPAIR_SPAN + 1];
   __shared__ double s_sq[REPAIR_MAX_LAGS * LCS_NW_MAX];
   __shared__ float s_lag[REPAIR_MAX_LAGS];
   const int tid = threadIdx.x, lane = tid & 63;
-  const ST *capbase = KIND == 0 ? reinterpret_cast<const ST *>(src.c8) : (KIND == 1 ? reinterpret_cast<const ST *>(src.c32) : reinterpret_cast<const ST *>(src.c64));
-  const size_t cap_stride = KIND == 0 ? lcs_cap8_stride(src.n_cap) : (size_t)src.n_cap;
   const int n = *n_fix;
   const int n_lag = 2 * geo.ds + 1, span = 137 + n_lag - 1;
   // Bounded work.  Real data list ~2 positions per buffer.  A degenerate input -- duplicated entries of f_search_set
@@ -846,7 +813,7 @@ __global__ __launch_bounds__(REPAIR_THREADS) void k_frq_repair(const float *__re
     }
     const float *sgs = sg + (size_t)slot * geo.G * LCS_N_IDX * LCS_TG;
     const SlotParams p = params[slot];
-    const ST *cap = capbase + (size_t)slot * cap_stride;
+    const ST *cap = CapKind<KIND>::slot(src, slot);
     // the values the collapse kernel compared (same expression, same rounding), 64 hypotheses per pass; every wave computes the
     // same candidate masks (no exchange needed)
     const int n_ch = (geo.n_f + 63) >> 6;
@@ -879,20 +846,12 @@ __global__ __launch_bounds__(REPAIR_THREADS) void k_frq_repair(const float *__re
         m &= m - 1;
         const int f = SPLIT ? (f_loc < 0 ? g_win : geo.foi0 + f_loc) : f_loc;      // index into fset
         ++spent;
-        // conj(fshift(pss_td, f_off, fs_programmed * k_factor)) / 137 in double (ref :146-151, dsp.h:40-53)
         const double f_off = fset[f];
-        const double kf = (p.fc_req - f_off) / p.fc_prog;
-        const double k = M_PI * f_off / ((p.fs_prog * kf) / 2);
-        if (tid < 137) {
-          double sn, cs;
-          sincos(k * (double)tid, &sn, &cs);
-          const double2 s = pss_td[t * 137 + tid];
-          s_tmpl[tid] = make_double2((s.x * cs - s.y * sn) / 137, -(s.x * sn + s.y * cs) / 137);
-        }
-        // window starts: from the table (this rank's own hypotheses) or, for a hypothesis of another rank, by k_prep_tables' expression
+        if (tid < 137) s_tmpl[tid] = pss_tmpl_tap(p, f_off, pss_td[t * 137 + tid], tid);
+        // window starts: from the table (this rank's own hypotheses) or, for a hypothesis of another rank, by k_prep_tables' function
         const int *st = start + ((size_t)slot * LCS_NW_MAX) * NFM + (SPLIT ? max(f_loc, 0) : f);
         __shared__ int s_st[LCS_NW_MAX];
-        if (tid < LCS_NW_MAX) s_st[tid] = (SPLIT && f_loc < 0) ? (int)rint((((double)tid * .005) * kf) * p.fs_prog) : (tid < geo.n_comb ? st[(size_t)tid * NFM] : 0);
+        if (tid < LCS_NW_MAX) s_st[tid] = (SPLIT && f_loc < 0) ? lcs_win_start(p, f_off, tid) : (tid < geo.n_comb ? st[(size_t)tid * NFM] : 0);
         __syncthreads();
         {
           // thread -> sample o of window w, all of a thread's loads in flight together.  Sample o of window w is what the positions
@@ -917,28 +876,15 @@ __global__ __launch_bounds__(REPAIR_THREADS) void k_frq_repair(const float *__re
         __syncthreads();
         for (int it = tid; it < n_lag * geo.n_comb; it += REPAIR_THREADS) {      // (lag, window): one 137-tap correlation each
           const int l = it / geo.n_comb, w = it - l * geo.n_comb;
-          double ar = 0, ai = 0;
           const int ii = idx + l - geo.ds;                               // this lag's position before the circular wrap
           const bool staged = (idx - geo.ds < 0) ? (ii < 0) : (ii < LCS_N_IDX);
-          if (staged) {
-            const ST *x = &s_smp[w][l];
-#pragma unroll 8
-            for (int mm = 0; mm < 137; ++mm) {           // (the LDS reads of eight taps in flight; the sums stay in tap order)
-              const double2 a = s_tmpl[mm], b = RepairSample<KIND>::cvt(x[mm]);
-              ar += a.x * b.x - a.y * b.y;
-              ai += a.x * b.y + a.y * b.x;
-            }
-          } else {                                       // the few lags on the other side of the wrap: straight from memory
+          double2 xc;
+          if (staged) xc = pss_tap_sum<KIND, true>(s_tmpl, &s_smp[w][l]);     // (the LDS reads of eight taps in flight)
+          else {                                         // the few lags on the other side of the wrap: straight from memory
             const int iw = ii < 0 ? ii + LCS_N_IDX : (ii >= LCS_N_IDX ? ii - LCS_N_IDX : ii);
-            const size_t k0 = (size_t)iw + (size_t)s_st[w];
-            for (int mm = 0; mm < 137; ++mm) {
-              const double2 a = s_tmpl[mm], b = RepairSample<KIND>::cvt(cap[k0 + mm]);
-              ar += a.x * b.x - a.y * b.y;
-              ai += a.x * b.y + a.y * b.x;
-            }
+            xc = pss_tap_sum<KIND, false>(s_tmpl, cap + (size_t)iw + (size_t)s_st[w]);
           }
-          const float fr = (float)ar, fi = (float)ai;                    // xc is complex<float>
-          s_sq[it] = (double)fr * (double)fr + (double)fi * (double)fi;
+          s_sq[it] = pss_xc_sq(xc);
         }
         __syncthreads();
         if (tid < n_lag) {                                               // the float running sum over the windows, in window order
@@ -983,28 +929,18 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_single_exact(const CapSrc src, const SlotParams *__restrict__ params, const double *__restrict__ fset,
                                                        const double2 *__restrict__ pss_td, const int *__restrict__ start,
                                                        float *__restrict__ single, XcGeom geo) {
-  typedef typename RepairSample<KIND>::T ST;
+  typedef typename CapKind<KIND>::T ST;
   __shared__ double2 s_tmpl[LCS_TG][137];
   __shared__ int s_st[LCS_TG][LCS_NW_MAX];
   const int tid = threadIdx.x, j = tid & (LCS_TG - 1), pp = tid / LCS_TG;
   const int g = blockIdx.y, slot = blockIdx.z;
-  const ST *capbase = KIND == 0 ? reinterpret_cast<const ST *>(src.c8) : (KIND == 1 ? reinterpret_cast<const ST *>(src.c32) : reinterpret_cast<const ST *>(src.c64));
-  const ST *cap = capbase + (size_t)slot * (KIND == 0 ? lcs_cap8_stride(src.n_cap) : (size_t)src.n_cap);
+  const ST *cap = CapKind<KIND>::slot(src, slot);
   const SlotParams p = params[slot];
   for (int e = tid; e < LCS_TG * 137; e += 256) {
     const int jj = e / 137, m = e - jj * 137;
     const int c = lcs_col_tmpl(geo, g, jj);
     double2 v = make_double2(0.0, 0.0);
-    if (c >= 0) {
-      const int foi = c / 3, t = c - 3 * foi;
-      const double f_off = fset[foi];
-      const double kf = (p.fc_req - f_off) / p.fc_prog;
-      const double k = M_PI * f_off / ((p.fs_prog * kf) / 2);
-      double sn, cs;
-      sincos(k * (double)m, &sn, &cs);
-      const double2 s = pss_td[t * 137 + m];
-      v = make_double2((s.x * cs - s.y * sn) / 137, -(s.x * sn + s.y * cs) / 137);
-    }
+    if (c >= 0) v = pss_tmpl_tap(p, fset[c / 3], pss_td[(c % 3) * 137 + m], m);
     s_tmpl[jj][m] = v;
   }
   for (int e = tid; e < LCS_TG * LCS_NW_MAX; e += 256) {
@@ -1021,16 +957,7 @@ __global__ __launch_bounds__(256) void k_single_exact(const CapSrc src, const Sl
     float o = 0.f;
     if (live) {
       for (int w = 0; w < geo.n_comb; ++w) {
-        const ST *x = cap + (size_t)idx + (size_t)s_st[j][w];
-        double ar = 0, ai = 0;
-#pragma unroll 8
-        for (int m = 0; m < 137; ++m) {
-          const double2 a = s_tmpl[j][m], b = RepairSample<KIND>::cvt(x[m]);
-          ar += a.x * b.x - a.y * b.y;
-          ai += a.x * b.y + a.y * b.x;
-        }
-        const float fr = (float)ar, fi = (float)ai;                      // xc is complex<float>
-        o = (float)((double)o + ((double)fr * (double)fr + (double)fi * (double)fi));
+        o = (float)((double)o + pss_xc_sq(pss_tap_sum<KIND, true>(s_tmpl[j], cap + (size_t)idx + (size_t)s_st[j][w])));
       }
       o = __fdiv_rn(o, (float)geo.n_comb);
     }
@@ -1133,12 +1060,7 @@ int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it)
   // them in front of it: the correlation of a single buffer waited 26 us for them; lcs_search_capbuf 0.377 -> 0.337 ms same-box).
   // The streaming mode's captured chain keeps everything on one stream: as a parallel branch of the graph (fork to stream_xc, join
   // before the collapse) a replay took 0.315 instead of 0.273 ms -- the runtime replays a forked graph over several streams.
-  SpArgs a;
-  a.n_comb_sp = (int)((geo.n_cap - 136 - 137) / 9600);
-  a.n_comb_xc = geo.n_comb;
-  a.ds = geo.ds;
-  a.R_th1 = lcs_tables::chi2cdf_inv(1 - pow(10.0, -12), 2.0 * geo.n_comb * (2 * geo.ds + 1));
-  a.rx_cutoff = (6 * 12 * 15e3 / 2 + 4 * 15e3) / (30720000.0 / 16 / 2);
+  const SpArgs a = make_sp_args(geo);
   auto launch_sp = [&](hipStream_t st) {
     if (cs.c8) {
       hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, st, c->i8.cap8, geo.n_cap, c->spinc, c->zth, a);

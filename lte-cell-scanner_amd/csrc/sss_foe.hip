@@ -22,7 +22,6 @@
 
 #define SF_THREADS 256
 #define MAX_HF 20
-#define FS_LTE 30720000.0
 
 #include "lte_device.h"
 
@@ -50,28 +49,7 @@ __device__ __forceinline__ int d_range_len(double first, double incr, double las
 // t = (l + 2 + 8 j) & 127: cis(k t) = cis(k (l + 2)) cis(8 k j) -- one factor per lane and sixteen per window, which the
 // window's eight lanes compute two each and share through LDS -- except where t wraps (j = 15, l >= 6: t = l - 6).  Four
 // sincos per lane and 8 windows instead of sixteen (rounds 1-4: one per sample).
-template <int KIND>
-__device__ __forceinline__ void win_load16(const CapView &cap, long loc, int l, uint32_t n_cap, bool valid, cd2 (&x)[16]) {
-  uint16_t r8[16];
-  float2 r32[16];
-  unsigned in_mask = 0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const long sidx = loc + ((l + 2 + 8 * j) & 127);
-    const bool in = valid && sidx >= 0 && (uint64_t)sidx < n_cap;
-    const size_t ci = in ? (size_t)sidx : 0;
-    in_mask |= (in ? 1u : 0u) << j;
-    if (KIND == 0) r8[j] = cap.c8[ci];
-    else if (KIND == 1) r32[j] = cap.c32[ci];
-    else { const double2 v = cap.c64[ci]; x[j] = mk(v.x, v.y); }
-  }
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if (KIND == 0) { const uint32_t pr = r8[j]; x[j] = mk(-(double)(int)(int8_t)(pr & 255u) / 128.0, -(double)(int)(int8_t)(pr >> 8) / 128.0); }
-    else if (KIND == 1) x[j] = mk((double)r32[j].x, (double)r32[j].y);
-    if (!((in_mask >> j) & 1u)) x[j] = mk(0, 0);      // beyond the buffer: zeros (the reference's mid() would read out of bounds)
-  }
-}
+struct WinIdx { static __device__ __forceinline__ long at(long loc, int l, int j) { return loc + ((l + 2 + 8 * j) & 127); } };
 // trot: this wave's [8][16] table in LDS.  The factors are computed BEFORE the samples are loaded (four sincos expansions with
 // sixteen samples live beside them needed every register the wave can have).
 // (cis_call is a real call, not inlined, lte_device.h: four inlined sincos expansions pushed k_sss_win to 256 + 26 registers -- 288 as allocated, more than the
@@ -108,7 +86,7 @@ template <int KIND>
 __device__ __forceinline__ void win_fft8(const CapView &cap, long loc, bool valid, const WinRot &r, uint32_t n_cap, int lane, cd2 *tb, const cd2 *tw,
                                          const cd2 *trot, cd2 (&x)[16]) {
   const int l = lane & 7;
-  win_load16<KIND>(cap, loc, l, n_cap, valid, x);
+  cap_load16<KIND, WinIdx>(cap, loc, l, n_cap, valid, x);
   win_rotate16(x, r, lane, trot);
   fft128_x8(x, tb, tw, lane);
 }

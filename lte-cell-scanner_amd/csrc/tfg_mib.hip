@@ -10,7 +10,6 @@
 // grid that strides over that device-side list, so the chain needs no host round trip.
 #include "lcs_internal.h"
 
-#define FS_LTE 30720000.0
 #define N_RB_MAXDL 110
 #define NSC 72
 #define ROWS LCS_TFG_ROWS
@@ -272,30 +271,7 @@ __device__ __forceinline__ bool tfg_row_needed(int t, int n_symb) {
                              // correlation workgroup (4 waves, one per SIMD) retired -- as one-wave workgroups spread over the chip every
                              // one of them kept a whole correlation slot empty for the sake of one SIMD (measured: step - 9 %)
 #define TFG_THREADS (64 * TFG_WAVES)
-template <int KIND>      // which copy of the capture buffer: 0 = int8 pairs (dongle bytes), 1 = complex<float>, 2 = complex<double>
-__device__ __forceinline__ void tfg_load16(const CapView &cap, long loc, int l, uint32_t n_cap, cd2 (&x)[16], bool &oob) {
-  // sixteen loads in flight in the source's own width, no branch between them; converted afterwards
-  uint16_t r8[16];
-  float2 r32[16];
-  unsigned in_mask = 0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const long sidx = loc + l + 8 * j;
-    const bool in = sidx >= 0 && (uint64_t)sidx < n_cap;
-    const size_t ci = in ? (size_t)sidx : 0;
-    in_mask |= (in ? 1u : 0u) << j;
-    if (KIND == 0) r8[j] = cap.c8[ci];
-    else if (KIND == 1) r32[j] = cap.c32[ci];
-    else { const double2 v = cap.c64[ci]; x[j] = mk(v.x, v.y); }
-  }
-  oob |= in_mask != 0xffffu;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if (KIND == 0) { const uint32_t pr = r8[j]; x[j] = mk(-(double)(int)(int8_t)(pr & 255u) / 128.0, -(double)(int)(int8_t)(pr >> 8) / 128.0); }
-    else if (KIND == 1) x[j] = mk((double)r32[j].x, (double)r32[j].y);
-    if (!((in_mask >> j) & 1u)) x[j] = mk(0, 0);
-  }
-}
+struct TfgIdx { static __device__ __forceinline__ long at(long loc, int l, int j) { return loc + l + 8 * j; } };
 // (one instantiation per source format: with the three formats' load paths in one kernel the register allocation is the widest one's)
 template <int KIND>
 __global__ __launch_bounds__(TFG_THREADS) void k_tfg(const WorkItem *__restrict__ items, const int *__restrict__ n_work,
@@ -321,9 +297,8 @@ __global__ __launch_bounds__(TFG_THREADS) void k_tfg(const WorkItem *__restrict_
     PH(30);
     const int row = d.row;
     cd2 x[16];
-    bool oob = false;
     const long loc = (long)d_round_i(d.ideal);
-    tfg_load16<KIND>(cap, loc, l, n_cap, x, oob);
+    const bool oob = cap_load16<KIND, TfgIdx>(cap, loc, l, n_cap, true, x) != 0xffffu;
     if (row >= 0) {
       // sample n = l + 8 j of the window is rotated by cis(pi kk (loc + n)): [window factor x position factor l] x position
       // factor 8 j, the latter as P(8 (j & 3)) P(32 (j >> 2)) -- six table values (uniform: scalar loads) instead of sixteen
@@ -892,57 +867,24 @@ static __device__ __forceinline__ void pbch_llr_wave(const lcs_cell &c, const do
   const int n_symb = cell_n_symb(c), id = cell_id(c);
   const int m_bit = (c.cp_type == LCS_CP_NORMAL) ? 1920 : 1728;
   const int n_sym = m_bit / 2, per_frame = n_sym / 4;
-  const int v3 = d_imod(id, 3);
-  const int r0 = (v3 == 0) ? 1 : 0, r1 = (v3 == 2) ? 1 : 2;     // the two residues != v3, ascending
   const double np0 = np_from_partials(sc, 0), np1 = np_from_partials(sc, 1), np2 = np_from_partials(sc, 2), np3 = np_from_partials(sc, 3);
   const int start = guess * 10 * 2 * n_symb;
   for (int pr = tid; pr < n_sym / 2; pr += PB_THREADS) {         // one symbol pair per lane and round
     cd2 x[2], ha[2], hb[2], syms[2];
     double npv[2];
     const int t = 2 * pr;
-    // the two antenna ports this pair is equalised with (ref :1582-1611): port 0 (and 1) for one / two ports; with four, pairs
-    // alternate between ports (0, 2) and (1, 3)
-    const int pa = (n_ports == 4 && (t & 3) != 0) ? 1 : 0, pb = (n_ports == 2) ? 1 : (n_ports == 4 ? pa + 2 : 0);
+    int pa, pb;
+    pbch_pair_ports(n_ports, t, pa, pb);
     for (int q = 0; q < 2; ++q) {
-      const int idx = t + q;
-      const int fr = idx / per_frame;
-      int rem = idx % per_frame, sym;
-      if (rem < 48) sym = 0; else if (rem < 96) { sym = 1; rem -= 48; } else if (rem < 168) { sym = 2; rem -= 96; } else { sym = 3; rem -= 168; }
-      const bool has_rs = (sym == 0) || (sym == 1) || (sym == 3 && n_symb == 6);
-      const int scx = has_rs ? (3 * (rem / 2) + ((rem & 1) ? r1 : r0)) : rem;
-      const int row = start + fr * 10 * 2 * n_symb + n_symb + sym;
-      x[q] = ld(&g[(size_t)row * NSC + scx]);
-      ha[q] = ld(&cep[((size_t)pa * ROWS + row) * NSC + scx]);
-      hb[q] = ld(&cep[((size_t)pb * ROWS + row) * NSC + scx]);
+      const PbchRe re = pbch_re(t + q, per_frame, n_symb, id);
+      const int row = start + re.fr * 10 * 2 * n_symb + n_symb + re.sym;
+      x[q] = ld(&g[(size_t)row * NSC + re.scx]);
+      ha[q] = ld(&cep[((size_t)pa * ROWS + row) * NSC + re.scx]);
+      hb[q] = ld(&cep[((size_t)pb * ROWS + row) * NSC + re.scx]);
     }
-    if (n_ports == 1) {
-      for (int q = 0; q < 2; ++q) {
-        const cd2 gain = cconj(cdiv(ha[q], mk(cabs2(ha[q]), 0)));
-        syms[q] = cmul(x[q], gain);
-        npv[q] = np0 * cabs2(gain);
-      }
-    } else {
-      const cd2 h1 = cdivr(cadd(ha[0], ha[1]), 2), h2 = cdivr(cadd(hb[0], hb[1]), 2);
-      const double np_temp = (n_ports == 2) ? (np0 + np1) / 2 : (pa == 0 ? (np0 + np2) / 2 : (np1 + np3) / 2);
-      const double scale = h1.re * h1.re + h1.im * h1.im + h2.re * h2.re + h2.im * h2.im;
-      const cd2 s0 = cdivr(cadd(cmul(cconj(h1), x[0]), cmul(h2, cconj(x[1]))), scale);
-      const cd2 s1 = cconj(cdivr(cadd(cmul(mk(-h2.re, h2.im), x[0]), cmul(h1, cconj(x[1]))), scale));
-      const double a1 = hypot(h1.re, h1.im) / scale, a2 = hypot(h2.re, h2.im) / scale;
-      const double npp = (a1 * a1 + a2 * a2) * np_temp;
-      const double s2 = pow(2.0, 0.5);
-      syms[0] = cscale(s0, s2); syms[1] = cscale(s1, s2);
-      npv[0] = npp; npv[1] = npp;
-    }
-    // soft demodulation (exact log-MAP, lte_device.h) and descrambling
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int l = t + q;
-      double l0, l1;
-      qpsk_llr(syms[q], npv[q], l0, l1);
-      if (scr[2 * l]) l0 = -l0;
-      if (scr[2 * l + 1]) l1 = -l1;
-      e_est[2 * l] = l0; e_est[2 * l + 1] = l1;
-    }
+    // sigpower(filtered - raw) of the pair's two ports
+    pbch_equalise_pair<false>(n_ports, x, ha, hb, pa ? np1 : np0, n_ports == 2 ? np1 : (pa ? np3 : np2), syms, npv);
+    pbch_llr_store(syms, npv, scr, t, e_est);
   }
 }
 __global__ __launch_bounds__(PB_THREADS * PB_CANDS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_pbch(const lcs_cell *__restrict__ cells, int *__restrict__ n_work,
@@ -998,12 +940,11 @@ __global__ __launch_bounds__(64) void k_mib_select(lcs_cell *__restrict__ cells,
       const int guess = cand / 3, n_ports = (cand % 3 == 2) ? 4 : (cand % 3) + 1;
       lcs_cell c = cells[it];
       auto bit = [&](int i) { return (int)((bits >> i) & 1u); };
+      const MibFields f = mib_fields(bits);
       c.n_ports = n_ports;
-      const int bw = bit(0) * 4 + bit(1) * 2 + bit(2);
-      const int bwt[6] = {6, 15, 25, 50, 75, 100};
-      if (bw < 6) c.n_rb_dl = bwt[bw];
-      c.phich_duration = bit(3) ? 2 : 1;
-      c.phich_resource = 1 + bit(4) * 2 + bit(5);
+      if (f.n_rb_dl) c.n_rb_dl = f.n_rb_dl;      // (a reserved bandwidth code leaves the field as it was)
+      c.phich_duration = f.phich_duration;
+      c.phich_resource = f.phich_resource;
       const signed char sfn_temp = (signed char)(128 * bit(6) + 64 * bit(7) + 32 * bit(8) + 16 * bit(9) + 8 * bit(10) + 4 * bit(11) + 2 * bit(12) + bit(13));   // quirk Q10
       c.sfn = d_imod((int)sfn_temp * 4 - guess, 1024);
       cells[it] = c;

@@ -17,7 +17,6 @@
 #include <cstring>
 #include <vector>
 
-#define FS_LTE 30720000.0
 #define TRK_MEAS 9
 
 // (trk_wrap, trk_wrap_certain_interval: lte_device.h)
@@ -455,67 +454,33 @@ __global__ __launch_bounds__(TRK_PB_THREADS) void k_trk_mib(const lcs_track_cell
   }
   const int m_bit = (c.cp_type == LCS_CP_NORMAL) ? 1920 : 1728;
   const int n_syms = m_bit / 2, per_fr = n_syms / 4;
-  const int v3 = d_imod(id, 3);
-  const int r0 = (v3 == 0) ? 1 : 0, r1 = (v3 == 2) ? 1 : 2;       // the two residues != v3, ascending
   const uint8_t *scr = pbch_scr + (size_t)id * 1920;
   for (int pr = tid; pr < n_syms / 2; pr += TRK_PB_THREADS) {
     cd2 x[2], ha[2], hb[2], sy[2];
     double npa = 0, npb = 0, npv[2];
     const int t = 2 * pr;
-    // the two antenna ports this pair is equalised with: port 0 (and 1) for one / two ports; with four, pairs alternate between
-    // ports (0, 2) and (1, 3) (the array form h[port][q] indexed by a run-time port lived in scratch memory)
-    const int pa = (c.n_ports == 4 && (t & 3) != 0) ? 1 : 0, pb = (c.n_ports == 2) ? 1 : (c.n_ports == 4 ? pa + 2 : 0);
+    int pa, pb;      // (the array form h[port][q] indexed by a run-time port lived in scratch memory)
+    pbch_pair_ports(c.n_ports, t, pa, pb);
     for (int q = 0; q < 2; ++q) {
-      const int ix = t + q, fr = ix / per_fr;
-      int rem = ix % per_fr, symn;
-      if (rem < 48) symn = 0; else if (rem < 96) { symn = 1; rem -= 48; } else if (rem < 168) { symn = 2; rem -= 96; } else { symn = 3; rem -= 168; }
-      const bool has_rs = (symn == 0) || (symn == 1) || (symn == 3 && n_symb == 6);
-      const int scx = has_rs ? (3 * (rem / 2) + ((rem & 1) ? r1 : r0)) : rem;
-      const int i = (off + fr) * per_frame + n_symb + symn;
-      x[q] = ld(&syms[((size_t)cell * n_sym + i) * 72 + scx]);
-      ha[q] = ld(&ce[(((size_t)cell * 4 + pa) * n_sym + i) * 72 + scx]);
-      hb[q] = ld(&ce[(((size_t)cell * 4 + pb) * n_sym + i) * 72 + scx]);
+      const PbchRe re = pbch_re(t + q, per_fr, n_symb, id);
+      const int i = (off + re.fr) * per_frame + n_symb + re.sym;
+      x[q] = ld(&syms[((size_t)cell * n_sym + i) * 72 + re.scx]);
+      ha[q] = ld(&ce[(((size_t)cell * 4 + pa) * n_sym + i) * 72 + re.scx]);
+      hb[q] = ld(&ce[(((size_t)cell * 4 + pb) * n_sym + i) * 72 + re.scx]);
       if (q == 0) {                                                  // np_pre(port, t): the symbol pair shares an OFDM symbol
         npa = ce_pw[(((size_t)cell * 4 + pa) * n_sym + i) * 4 + 3];
         npb = ce_pw[(((size_t)cell * 4 + pb) * n_sym + i) * 4 + 3];
       }
     }
-    if (c.n_ports == 1) {
-      for (int q = 0; q < 2; ++q) {
-        const cd2 gain = cconj(cdiv(ha[q], mk(cabs2(ha[q]), 0)));
-        sy[q] = cmul(x[q], gain);
-        npv[q] = npa * cabs2(gain);
-      }
-    } else {
-      const cd2 h1 = cdivr(cadd(ha[0], ha[1]), 2), h2 = cdivr(cadd(hb[0], hb[1]), 2);
-      const double np_temp = (npa + npb) / 2;
-      const double scale = pow(h1.re, 2) + pow(h1.im, 2) + pow(h2.re, 2) + pow(h2.im, 2);
-      const cd2 s0 = cdivr(cadd(cmul(cconj(h1), x[0]), cmul(h2, cconj(x[1]))), scale);
-      const cd2 s1 = cconj(cdivr(cadd(cmul(mk(-h2.re, h2.im), x[0]), cmul(h1, cconj(x[1]))), scale));
-      const double a1 = hypot(h1.re, h1.im) / scale, a2 = hypot(h2.re, h2.im) / scale;
-      const double s2 = pow(2.0, 0.5);
-      sy[0] = cscale(s0, s2); sy[1] = cscale(s1, s2);
-      npv[0] = npv[1] = (a1 * a1 + a2 * a2) * np_temp;
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int l = t + q;
-      double l0, l1;
-      qpsk_llr(sy[q], npv[q], l0, l1);
-      if (scr[2 * l]) l0 = -l0;
-      if (scr[2 * l + 1]) l1 = -l1;
-      e_est[2 * l] = l0; e_est[2 * l + 1] = l1;
-    }
+    pbch_equalise_pair<true>(c.n_ports, x, ha, hb, npa, npb, sy, npv);
+    pbch_llr_store(sy, npv, scr, t, e_est);
   }
   int ok = 0;
   unsigned long long bits40 = 0;
   pbch_decode_wave(e_est, d_est, derm_inv, m_bit, c.n_ports, tid, ok, bits40);
   if (tid == 0) {
-    const int bw[8] = {6, 15, 25, 50, 75, 100, 0, 0};
-    const int b0 = (int)(bits40 & 1), b1 = (int)((bits40 >> 1) & 1), b2 = (int)((bits40 >> 2) & 1);
-    const int n_rb = bw[b0 * 4 + b1 * 2 + b2];
-    const int dur = ((bits40 >> 3) & 1) ? 2 : 1, res = 1 + (int)((bits40 >> 4) & 1) * 2 + (int)((bits40 >> 5) & 1);
-    const int fields = (n_rb == c.n_rb_dl) && (dur == c.phich_duration) && (res == c.phich_resource);
+    const MibFields f = mib_fields((unsigned)bits40);      // (a reserved bandwidth code gives 0: no match)
+    const int fields = (f.n_rb_dl == c.n_rb_dl) && (f.phich_duration == c.phich_duration) && (f.phich_resource == c.phich_resource);
     mib_ok[(size_t)cell * n_off + off] = (ok ? 1 : 0) | (fields ? 2 : 0);
     mib_bits[(size_t)cell * n_off + off] = bits40;
   }

@@ -195,3 +195,74 @@ def test_dense_raster_split_over_two_contexts(pkg, cases, step):
     finally:
         for S_ in ctxs:
             S_.close()
+
+
+# ---- the repair at the circular edge of the 9600 positions, and the remote winner's window starts ----------------------------
+# k_frq_repair stages the samples of the lags on one side of the wrap and reads the others straight from memory; on the split
+# path a rank recomputes a winner it does not own from window starts it forms itself (lcs_win_start).  The dense rasters above
+# list no position within the arm of 0 or 9599 (checked on the oracle's output), so one crafted buffer does: two cells whose PSS
+# correlation peaks sit on positions 0 (PSS 0) and 9599 (PSS 1), three hypotheses of which the last two are the same frequency --
+# an exact tie at every position they win, the peaks and their +- arm neighbours far above Z_th1 (the list is crowded, so only
+# such positions are recomputed).
+EDGE_F = np.array([30e3, 35e3, 35e3])
+EDGE_AT = ((0, 0), (1, 9599))      # (PSS, position of its peak)
+
+
+@pytest.fixture(scope="module")
+def edge_case(pkg):
+    fc = 739e6
+    iq, _ = pkg.synth.make_capbuf(4242, fc, [dict(n_id_1=25, n_id_2=0, f_off=35e3, t0=823.0), dict(n_id_1=101, n_id_2=1, f_off=35e3, t0=10424.0)])
+    cap = iq_u8_to_capbuf(iq)
+    ro = O.xcorr_pss(cap, EDGE_F, 2, fc, fc, FS)
+    z = O.z_th1(ro["sp_incoherent"], ro["n_comb_xc"])
+    where = []
+    for t, p in EDGE_AT:
+        assert int(np.argmax(ro["single"][t, :, 1])) == p, "the crafted peak moved"
+        for d in range(-2, 3):
+            i = (p + d) % 9600
+            # the position is an exact tie of the duplicated hypotheses, won by the first, and can become a peak: it is listed AND repaired
+            assert ro["incoherent"][t, i, 1] == ro["incoherent"][t, i, 2] > ro["incoherent"][t, i, 0] and ro["frq"][t, i] == 1
+            assert ro["pow"][t, i] > 2 * z[i]
+            where.append((t, i))
+    return fc, cap, ro, where
+
+
+def _assert_edge(pw, fq, ro, where, tag):
+    for t, i in where:
+        assert fq[t, i] == ro["frq"][t, i], f"{tag}: frq[{t}][{i}] = {fq[t, i]}, the oracle's {ro['frq'][t, i]}"
+        assert pw[t, i] == ro["pow"][t, i], f"{tag}: pow[{t}][{i}] = {pw[t, i]!r} is not the oracle's float {ro['pow'][t, i]!r}"
+
+
+def test_repair_at_the_circular_edge(S, edge_case):
+    fc, cap, ro, where = edge_case
+    r = S.xcorr_pss(cap, EDGE_F, 2, fc, fc, FS)
+    assert S.last_xcorr_info()[0] == "k_xcorr_i8x3"
+    listed, left = S.last_frq_repair_stats()
+    assert listed > 32 * 64 and 0 < left < listed, (listed, left)      # crowded: bounded work, yet some positions were recomputed
+    _assert_edge(r["pow"], r["frq"], ro, where, "edge")
+
+
+def test_remote_winner_at_the_circular_edge(pkg, edge_case):
+    """The same buffer with the hypotheses split 2 + 1 over two contexts: the second rank owns only the duplicate, so wherever it
+    contends the global winner (hypothesis 1) is remote and its window starts are formed by the contending rank."""
+    import torch
+    fc, cap, ro, where = edge_case
+    shares = [(0, 2), (2, 1)]
+    ctxs = [pkg.Searcher(0) for _ in shares]
+    try:
+        words = [torch.empty(3 * 9600, dtype=torch.int64, device="cuda") for _ in ctxs]
+        meta = [torch.empty(9601, dtype=torch.float64, device="cuda") for _ in ctxs]
+        for S_, (a, n), w, m in zip(ctxs, shares, words, meta):
+            S_.foe_partial(cap, EDGE_F, a, n, fc, fc, FS, w.data_ptr(), m.data_ptr())
+        red = torch.stack(words).max(dim=0).values
+        w2 = [torch.empty(3 * 9600, dtype=torch.int64, device="cuda") for _ in ctxs]
+        for S_, x in zip(ctxs, w2):
+            S_.foe_contend(EDGE_F, red.data_ptr(), x.data_ptr())
+        assert ctxs[1].last_frq_repair_stats()[0] > 0, "the rank that owns only the duplicate contends"
+        red2 = torch.stack(w2).max(dim=0).values
+        ctxs[0].foe_resolve(red.data_ptr(), red2.data_ptr())
+        pw, fq = pkg.sweep.unpack_pow_frq(red.cpu().numpy().reshape(3, 9600))
+        _assert_edge(pw, fq, ro, where, "edge, split 2 + 1")
+    finally:
+        for S_ in ctxs:
+            S_.close()
