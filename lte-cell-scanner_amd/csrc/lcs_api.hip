@@ -30,9 +30,7 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
   const size_t S = n_slots, NE = 3 * LCS_N_IDX;
   const int G = std::max(std::max(G_need, c->cap_G), (3 * n_f + LCS_TG - 1) / LCS_TG);
   int rc;
-  c->btab.reset();          // fp32 kernel's operand tables (0.5 MB per slot and group): allocated by its first launch (lcs_launch_xcorr)
-  c->i8 = I8Set();          // the int8 and fp16 sets were sized for the old workspace: gone, allocated again on first use
-  c->f16 = F16Set();
+  c->xcb = XcBufs();        // the correlation kernels' sets were sized for the old workspace: gone, allocated again on first use (lcs_ensure_xc)
   // the per-hypothesis / per-group tables (fset .. kp2, single, sref) are sized for the largest grid seen; every call lays its
   // own grid out with its own strides n_f and G (k_prep_tables rebuilds them per call)
   if ((rc = c->cap32.alloc(c, S * n_cap)) || (rc = c->cap64.alloc(c, (size_t)n_cap)) || (rc = c->params_ws.alloc(c, S)) ||
@@ -51,36 +49,6 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
   c->cap_n_f = n_f;
   c->cap_G = G;
   c->cap_debug = debug;
-  return LCS_OK;
-}
-
-// Buffers of the int8 correlation path (u8 sources), sized like the current workspace.
-int ensure_i8(lcs_ctx *c) {
-  if (c->i8.ready) return LCS_OK;
-  if (c->st_open) { c->err = "int8 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
-  const size_t S = (size_t)c->cap_slots;
-  const int G = c->cap_G;
-  int rc;
-  const size_t n8 = S * lcs_cap8_stride(c->cap_n_cap);
-  if ((rc = c->i8.cap8.alloc(c, n8)) || (rc = c->i8.cap8s.alloc(c, n8)) || (rc = c->i8.brow8.alloc(c, S * G * (size_t)LCS_I8_IMG)) ||
-      (rc = c->i8.tq.alloc(c, S * G * LCS_TG)) || (rc = c->i8.tsc.alloc(c, S * G * LCS_TG)))
-    return rc;
-  c->i8.ready = true;
-  return LCS_OK;
-}
-
-// Buffers of the fp16 three-product correlation path (complex<float> sources of the batch entry points).
-int ensure_f16(lcs_ctx *c) {
-  if (c->f16.ready) return LCS_OK;
-  if (c->st_open) { c->err = "fp16 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
-  const size_t S = (size_t)c->cap_slots;
-  int rc;
-  const size_t n16 = S * lcs_cap8_stride(c->cap_n_cap);
-  if ((rc = c->f16.cap16h.alloc(c, n16)) || (rc = c->f16.cap16l.alloc(c, n16)) || (rc = c->f16.brow16.alloc(c, S * c->cap_G * (size_t)LCS_F16_IMG)) ||
-      (rc = c->f16.texp16.alloc(c, S * c->cap_G * LCS_TG)) || (rc = c->f16.tsc16.alloc(c, S * c->cap_G * LCS_TG)) ||
-      (rc = c->f16.xmax16.alloc(c, S)) || (rc = c->f16.xpart16.alloc(c, S * 128)))
-    return rc;
-  c->f16.ready = true;
   return LCS_OK;
 }
 
@@ -132,8 +100,6 @@ int ensure_res_pack(lcs_ctx *c, int n_buf) {
 }
 
 const double kPeakThresh = std::pow(10.0, -12.0 / 10.0);                  // peak_search: udb10(-12.0), what lies below this fraction of a found peak is cleared (ref src/searcher.cpp:501)
-constexpr int kMaxTapsI8 = LCS_I8_MAX_TAPS;                               // int8 kernel: 137 taps + delays below LCS_I8_OFF (the fp16 kernel holds 160)
-constexpr int kMaxTapsF32 = 2 * (LCS_KP2_MAX - LCS_KP2_UNROLL);          // fp32 kernel: 124 tap pairs
 
 // lcs_set_float_batch_probe: is a batch of complex<float> buffers dongle data -- every component exactly (u8 - 127) / 128 (ref
 // src/capbuf.cpp:172-181)?  One pass: per component dongle_component_f32 (lte_device.h) decides on the exact product x * 128 and
@@ -153,6 +119,24 @@ __global__ __launch_bounds__(256) void k_c64_probe_u8(const float *__restrict__ 
   }
   if (__any(!ok) && (threadIdx.x & 63) == 0) atomicAnd(flag, 0);
 }
+// The probe of one batch: one pass + one small read-back -- the host waits for it, while the other contexts' kernels keep the GPU busy,
+// before it knows which kernels to queue.  c->last_c64_routed: the batch is dongle data and takes the u8 route with the bytes in c->c64_u8.
+int probe_c64_batch(lcs_ctx *c, bool may_probe, const void *d_capbufs, size_t n_comp) {
+  c->last_c64_routed = false;
+  if (!may_probe) return LCS_OK;
+  if (c->c64_skip > 0) { --c->c64_skip; return LCS_OK; }
+  if (n_comp > c->c64_u8.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = c->c64_u8.reserve(c, n_comp);
+  if (rc) return rc;
+  int flag = 1;
+  HIPCHK(c, hipMemcpyAsync(c->d_flag, &flag, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_c64_probe_u8, dim3(2048), dim3(256), 0, c->stream, (const float *)d_capbufs, n_comp, c->c64_u8, c->d_flag);
+  HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (flag) c->last_c64_routed = true;
+  else c->c64_skip = 15;      // a float front end: the next batches are not probed (one in sixteen is)
+  return LCS_OK;
+}
 
 // The one place a Launch is built: n_buf buffers of n_cap samples that the fp64 stages read from `src`, parameters and hypotheses in
 // the workspace's arrays, 64 workgroups per work-list axis.  The entry point then sets what differs for its call.  Two things a
@@ -171,30 +155,36 @@ Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &sr
   return L;
 }
 
-// complex<double> host buffer -> device (cap64, slot 0) and the choice of the correlation kernel: a buffer whose every
-// component is exactly (u8 - 127) / 128 -- any dongle capture -- takes the int8 kernel, anything else the fp32 one.
-// *out: the launch to correlate with (geometry, kernel, source).
+// What xc_route (xcorr_route.h) asks about a context; the caller adds what it knows of its call.
+XcFacts route_facts(const lcs_ctx *c, XcCaller caller, bool u8, int n_comb) {
+  return XcFacts{caller, u8, c->st_open, c->xcb.i8.ready, c->xcb.f16.ready, n_comb, XcVerdict::unknown, c->c64_probe, false};
+}
+
+// complex<double> host buffer -> device (cap64, slot 0) and xc_route's choice of the correlation kernel, once the ingest has
+// said whether the buffer is dongle data.  *out: the launch to correlate with (geometry, kernel, source).
 int upload_host_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double *f_search_set, int n_f, int ds, double fc_req,
                        double fc_prog, double fs_prog, bool debug, Launch *out) {
-  const XcGeom geo32 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, kMaxTapsF32);
-  const XcGeom geo8 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, kMaxTapsI8);
+  const XcGeom geo32 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, xc_max_taps(XcKernel::fp32));
+  const XcGeom geo8 = pack_grid(n_cap, n_f, ds, f_search_set, &fc_req, &fc_prog, 1, fs_prog, xc_max_taps(XcKernel::i8));
   int rc;
   c->foe_ready = false;      // slot 0 is overwritten: a pending lcs_foe_partial result is gone (lcs_foe_partial sets it again)
   if ((rc = ensure_ws(c, 1, n_cap, n_f, debug, std::max(geo32.G, geo8.G)))) return rc;
-  // the int8 copies cannot be (re)allocated under an open stream's graph: such a context keeps the fp32 kernel
-  const bool can_i8 = c->i8.ready || !c->st_open;
-  if (can_i8 && (rc = ensure_i8(c))) return rc;
+  XcFacts facts = route_facts(c, XcCaller::host, false, geo8.n_comb);
+  const unsigned sets = xc_route(facts).sets;
+  if ((rc = lcs_ensure_xc(c, sets))) return rc;
   c->h_params = SlotParams{fc_req, fc_prog, fs_prog};
   HIPCHK(c, hipMemcpyAsync(c->cap64, capbuf, sizeof(double2) * n_cap, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->fset_ws, f_search_set, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->params_ws, &c->h_params, sizeof(SlotParams), hipMemcpyHostToDevice, c->stream));
   bool exact = false;
   CapSrc src;
-  if (can_i8) { if ((rc = lcs_launch_ingest_c128(c, n_cap, &exact, &src))) return rc; }
+  if (sets & XC_SET_I8) { if ((rc = lcs_launch_ingest_c128(c, n_cap, &exact, &src))) return rc; }
   else if ((rc = lcs_launch_ingest(c, nullptr, LCS_FMT_C128, 1, n_cap, &src))) return rc;
+  facts.verdict = exact ? XcVerdict::dongle : XcVerdict::other;
+  const XcRoute r = xc_route(facts);
   *out = make_launch(c, 1, n_cap, src);
-  out->geo = exact ? geo8 : geo32;
-  out->xc = exact ? XcKernel::i8 : XcKernel::fp32;
+  out->geo = r.pack_taps == xc_max_taps(XcKernel::i8) ? geo8 : geo32;
+  out->xc = r.kernel;
   return LCS_OK;
 }
 
@@ -457,11 +447,10 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   c->foe_ready = false;      // the batch overwrites the buffers a pending lcs_foe_partial left for lcs_foe_finish
-  // u8 I/Q is exact in int8: the int8 three-digit kernel (pss_xcorr_i8.hip), 137 taps + window-start spread <= 152 inside
-  // every template group; every other source takes the fp32 kernel (spread <= 111); pack_grid thins the groups of a grid
-  // that is too sparse for that
+  // pack: 137 taps + window-start spread <= 152 inside every template group, the int8 kernel's limit, whatever kernel follows (the
+  // fp16 kernel holds 160 taps, the fp32 kernel more); pack_grid thins the groups of a grid that is too sparse for that
   const XcGeom geo = pack_grid(n_cap, n_f, 2 /* DS_COMB_ARM, ref src/CellSearch.cpp:484 */, f_search_set, fc_requested, fc_programmed,
-                               n_buf, fs_programmed, kMaxTapsI8);      // the fp16 kernel holds 160 taps per group and shares the int8 kernel's packing
+                               n_buf, fs_programmed, xc_max_taps(XcKernel::i8));
   if ((rc = ensure_ws(c, n_buf, n_cap, n_f, false, geo.G))) return rc;
   if ((rc = ensure_res_pack(c, n_buf))) return rc;
   if ((rc = c->h_pinned.reserve(c, sizeof(SlotParams) * n_buf + sizeof(double) * n_f))) return rc;
@@ -471,36 +460,21 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   std::memcpy(hf, f_search_set, sizeof(double) * n_f);
   HIPCHK(c, hipMemcpyAsync(c->params_ws, hp, sizeof(SlotParams) * n_buf, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->fset_ws, hf, sizeof(double) * n_f, hipMemcpyHostToDevice, c->stream));
-  // lcs_set_float_batch_probe: a complex<float> batch that is dongle data becomes the u8 batch it came from (one pass + one small
-  // read-back: the host waits for it -- while the other contexts' kernels keep the GPU busy -- before it knows which kernels to queue)
-  c->last_c64_routed = false;
-  if (fmt == LCS_FMT_C64 && c->c64_probe && (c->i8.ready || !c->st_open) && ((size_t)n_buf * n_cap) % 2 == 0 && (reinterpret_cast<uintptr_t>(d_capbufs) & 15) == 0) {
-    if (c->c64_skip > 0) --c->c64_skip;
-    else {
-      const size_t n_comp = (size_t)2 * n_cap * n_buf;
-      if (n_comp > c->c64_u8.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
-      if ((rc = c->c64_u8.reserve(c, n_comp))) return rc;
-      int flag = 1;
-      HIPCHK(c, hipMemcpyAsync(c->d_flag, &flag, sizeof(int), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(k_c64_probe_u8, dim3(2048), dim3(256), 0, c->stream, (const float *)d_capbufs, n_comp, c->c64_u8, c->d_flag);
-      HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (flag) { d_capbufs = c->c64_u8; fmt = LCS_FMT_IQ_U8; c->last_c64_routed = true; }
-      else c->c64_skip = 15;      // a float front end: the next batches are not probed (one in sixteen is)
-    }
-  }
-  const int fmt_in = c->last_c64_routed ? LCS_FMT_C64 : fmt;      // what the caller handed over: the hint bookkeeping goes by it
-  // complex<float> sources: fp16 hi / lo operands, three products (pss_xcorr_f16.hip) -- unless its buffers would have to be
-  // allocated under an open stream's graph: such a context keeps the fp32 kernel for them (160 taps per group fit it too)
-  const bool use_f16 = fmt == LCS_FMT_C64 && (c->f16.ready || !c->st_open);
-  if (fmt == LCS_FMT_IQ_U8 && (rc = ensure_i8(c))) return rc;      // int8 copies: every u8 source (the fp64 stages read them)
-  if (use_f16 && (rc = ensure_f16(c))) return rc;
+  // route: a complex<float> batch that the probe finds to be dongle data becomes the u8 batch it came from
+  XcFacts facts = route_facts(c, XcCaller::batch, fmt == LCS_FMT_IQ_U8, geo.n_comb);
+  facts.probe_fits = xc_probe_fits((size_t)n_buf * n_cap, reinterpret_cast<uintptr_t>(d_capbufs));
+  if ((rc = probe_c64_batch(c, xc_route(facts).may_probe, d_capbufs, (size_t)2 * n_cap * n_buf))) return rc;
+  const int fmt_in = fmt;      // what the caller handed over: the hint bookkeeping goes by it
+  if (c->last_c64_routed) { d_capbufs = c->c64_u8; fmt = LCS_FMT_IQ_U8; facts.u8 = true; }
+  const XcRoute r = xc_route(facts);
+  if ((rc = lcs_ensure_xc(c, r.sets))) return rc;
+  // ingest: int8 copies of a u8 source (the fp64 stages read them), fp16 hi / lo pairs of a complex<float> one that holds the fp16 set
   CapSrc src;
-  if (use_f16) { if ((rc = lcs_launch_ingest_f16(c, d_capbufs, n_buf, n_cap, &src))) return rc; }
+  if (r.sets & XC_SET_F16) { if ((rc = lcs_launch_ingest_f16(c, d_capbufs, n_buf, n_cap, &src))) return rc; }
   else if ((rc = lcs_launch_ingest(c, d_capbufs, fmt, n_buf, n_cap, &src))) return rc;
   Launch L = make_launch(c, n_buf, n_cap, src);
   L.geo = geo;
-  L.xc = fmt == LCS_FMT_IQ_U8 ? XcKernel::i8 : use_f16 ? XcKernel::f16 : XcKernel::fp32;
+  L.xc = r.kernel;
   L.needed_rows_only = true;
   L.tfoec_parts = 2;
   if ((rc = lcs_launch_xcorr(c, L, false, true))) return rc;
@@ -1018,6 +992,8 @@ int lcs_foe_finish(lcs_ctx *c, const void *d_words, const double *d_meta, const 
 // pushes (samples, frequency offset, tracked identities) travels through fixed pinned host buffers
 // that the graph's copy nodes read at execution time.
 namespace {
+// xc_route for the stream: the sets its open allocates, the kernel its chain runs
+XcRoute stream_route(const lcs_ctx *c, int fmt, const XcGeom &geo) { return xc_route(route_facts(c, XcCaller::stream, fmt == LCS_FMT_IQ_U8, geo.n_comb)); }
 // the chain as slot k sees it: its own pinned input buffer and parameter / result block, the shared device workspace.  Its kernels
 // take the slot parameters and the hypothesis from the stream's device mirror (one copy per push), not from the workspace arrays the
 // other entry points fill.
@@ -1030,10 +1006,10 @@ int stream_chain(lcs_ctx *c, int k) {
   CapSrc src;
   if ((rc = lcs_launch_ingest(c, c->st_din, c->st_fmt, 1, c->st_n_cap, &src))) return rc;
   Launch L = make_launch(c, 1, c->st_n_cap, src);
-  L.geo = make_geo(c->st_n_cap, 1, 2);
+  L.geo = make_geo(c->st_n_cap, 1, 2);      // one hypothesis: no window-start spread, every kernel's image holds it
   L.params = reinterpret_cast<const SlotParams *>(c->st_dmirror + offsetof(StreamHost, p));
   L.fset = reinterpret_cast<const double *>(c->st_dmirror + offsetof(StreamHost, f));
-  L.xc = c->st_fmt == LCS_FMT_IQ_U8 ? XcKernel::i8 : XcKernel::fp32;      // one hypothesis: no window-start spread, the int8 kernel always fits
+  L.xc = stream_route(c, c->st_fmt, L.geo).kernel;
   L.needed_rows_only = true;
   if ((rc = lcs_launch_xcorr(c, L, false, false))) return rc;
   if ((rc = lcs_launch_peak_search(c, L, kPeakThresh, true))) return rc;
@@ -1078,8 +1054,7 @@ int stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, double
   int rc;
   if ((rc = ensure_ws(c, 1, n_cap, 1, false))) return rc;
   if ((rc = ensure_percell(c))) return rc;
-  if (fmt == LCS_FMT_IQ_U8 && (rc = ensure_i8(c))) return rc;
-  if ((rc = lcs_ensure_btab(c))) return rc;      // host buffers that are not dongle data take the fp32 kernel, also while the stream is open
+  if ((rc = lcs_ensure_xc(c, stream_route(c, fmt, make_geo(n_cap, 1, 2)).sets))) return rc;
   c->st_fmt = fmt;
   c->st_n_cap = n_cap;
   c->st_in_bytes = (size_t)n_cap * (fmt == LCS_FMT_IQ_U8 ? 2 : sizeof(float2));

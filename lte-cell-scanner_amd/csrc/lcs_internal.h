@@ -23,6 +23,7 @@
 #include <vector>
 #include "../../include/lcs.h"
 #include "lcs_mem.h"
+#include "xcorr_route.h"   // XcKernel, and what a template group holds: LCS_KP2_MAX, LCS_KP2_UNROLL, LCS_I8_OFF, LCS_I8_MAX_TAPS
 
 #define FS_LTE 30720000.0    // LTE sampling rate at 2048 subcarriers; the searcher works at FS_LTE / 16
 #define LCS_NW_MAX 16        // incoherent-combining windows (15 for a 153600-sample buffer)
@@ -36,8 +37,6 @@
 // arbiter issue these few waves ahead of the MFMA stream instead of round-robin behind 4-5 of them.
 #define LCS_TAIL_PRIO() __builtin_amdgcn_s_setprio(3)
 #define LCS_TG 16            // templates per MFMA column group
-#define LCS_KP2_MAX 128      // tap pairs per (window, group): 137 taps + up to 119 samples of spread
-#define LCS_KP2_UNROLL 4
 #define LCS_LAG_TILE 64      // lags per wave
 #define LCS_PS 336           // LDS plane stride in floats: >= 64 + 2*KP2_MAX, == 16 (mod 32)
 #define LCS_MAXP LCS_MAX_PEAKS   // peaks kept per capture buffer: the most peak_search can return (lcs.h)
@@ -47,8 +46,6 @@
 // compares (worst measured 1.8e-6: the int8 kernel on a two-window buffer).  lcs_frq_tie_eps() hands it out.
 #define LCS_FRQ_TIE_EPS 4e-6f
 #define LCS_I8_KB 5          // 32-tap blocks of the int8 correlation kernel
-#define LCS_I8_OFF 16        // int8 kernel: a template column's delay inside its group (window-start spread) stays below this
-#define LCS_I8_MAX_TAPS (137 + LCS_I8_OFF - 1)
 #define LCS_I8_IMG 17024     // dwords of the int8 kernel's operand image per (buffer, group) (pss_xcorr_i8.hip)
 #define LCS_F16_IMG 11840    // the same for the fp16 kernel (pss_xcorr_f16.hip)
 #define LCS_MAX_WORK 1024    // most cells carried into the TFG/MIB stages per round (~6 MB each)
@@ -170,7 +167,6 @@ struct WorkItem {
 
 // Everything a launcher needs to know about the call it serves, apart from the context's memory: built by the entry point
 // (lcs_api.hip: make_launch) and handed to every lcs_launch_* function.  No launcher reads a mode from lcs_ctx.
-enum class XcKernel { fp32, i8, f16 };      // k_xcorr_mfma_blk / k_xcorr_i8x3 (u8 sources) / k_xcorr_f16x3 (complex<float> batches)
 enum class FrqRepair {
   all,            // every near-tie of the arg-max is recomputed in the reference's arithmetic (the arrays leave the call)
   peaks_only,     // only the near-ties at or above their position's Z_th1: the peak list is what has to be exact (lcs_search_capbuf)
@@ -182,7 +178,7 @@ struct Launch {
   XcGeom geo{};
   const SlotParams *params = nullptr;   // per-slot parameter records and the hypotheses: the workspace's arrays (params_ws / fset_ws),
   const double *fset = nullptr;         // or the device mirror of the streaming mode's pinned block
-  XcKernel xc = XcKernel::fp32;
+  XcKernel xc = XcKernel::fp32;         // xc_route's choice (xcorr_route.h)
   CapSrc src{};                         // what the fp64 stages read: decided where the data is ingested (lcs_launch_ingest*)
   FrqRepair repair = FrqRepair::all;
   bool single_stream = false;           // everything on `stream`, no hand-over to stream_xc (a context with an open stream)
@@ -241,7 +237,8 @@ struct TrkStream {
 
 // Buffers of the int8 correlation path (u8 sources) and of the fp16 three-product path (complex<float> sources of the batch
 // entry points): each set is sized like the workspace, exists as a whole or not at all (`ready`), and goes with the workspace
-// it was sized for (ensure_ws assigns an empty set).
+// it was sized for.  With the fp32 kernel's operand tables they are the XcBufs of a context: lcs_ensure_xc (pss_xcorr.hip) is the one
+// place any of them is allocated, ensure_ws drops them all by assigning an empty XcBufs.
 struct I8Set {
   DevBuf<uint16_t> cap8;             // capture buffers as (re, im) int8 pairs 127 - u8, slot stride lcs_cap8_stride (pss_xcorr_i8.hip)
   DevBuf<uint16_t> cap8s;            // the same shifted down by one sample: cap8s[i] = cap8[i + 1]
@@ -258,6 +255,11 @@ struct F16Set {
   DevBuf<unsigned> xmax16;           // per slot: bits of the largest |component|
   DevBuf<unsigned> xpart16;          // per slot: 128 partial maxima (one per workgroup of the read-only maximum pass)
   bool ready = false;
+};
+struct XcBufs {
+  I8Set i8;
+  F16Set f16;
+  DevBuf<float> btab;                // fp32 kernel only: sized for the workspace's slots and groups (0.5 MB per slot, window and group)
 };
 
 // The streams and events of a context (the streaming mode's own events and graphs: lcs_stream_close).  A BASE of lcs_ctx,
@@ -278,8 +280,8 @@ struct lcs_ctx_queues {
 // that is one, and nothing else frees it; a plain pointer member is a VIEW of memory owned elsewhere and says so.  What a launch
 // depends on beyond memory travels in a Launch, not in fields of this struct; the two records kept here (`batch`, `foe`) are saved
 // copies of the Launch of a call whose work a later call continues, and a saved copy's pointers end with what they point into:
-// ensure_ws drops both records when it replaces the workspace, lcs_stream_close takes the stream's tracked list out of them,
-// lcs_batch_collect the caller's complex<float> buffers.  lcs_destroy
+// ensure_ws drops both records when it replaces the workspace (and `xcb`, the correlation kernels' buffer sets, sized for it),
+// lcs_stream_close takes the stream's tracked list out of them, lcs_batch_collect the caller's complex<float> buffers.  lcs_destroy
 // is `delete`: ~lcs_ctx makes the context's device current, closes an open stream (graphs first) and synchronises both
 // streams; then the members go, the owners freeing their memory; the base goes last, with the events and then the streams --
 // the order the hand-written tear-down had.
@@ -296,14 +298,12 @@ struct lcs_ctx : lcs_ctx_queues {
 
   // device buffers
   DevBuf<float2> cap32;
-  I8Set i8;
-  F16Set f16;
+  XcBufs xcb;                        // what the correlation kernels read beyond the workspace: lcs_ensure_xc
   DevBuf<double2> cap64;             // slot 0 only: fp64 copy for the host (complex<double>) entry points
   DevBuf<SlotParams> params_ws;      // the workspace's parameter records and hypotheses (ensure_ws): what every entry point but the
   DevBuf<double> fset_ws;            // streaming chain uploads to and hands to its launches (Launch::params / fset)
   DevBuf<float2> tmpl;
   DevBuf<int> start, smin, kp2;
-  DevBuf<float> btab;                // fp32 kernel only: allocated by its first launch for the workspace's slots and groups
   DevBuf<float> single, incoh, sref;
   DevBuf<double> pow_, work, spinc, zth, sp;
   DevBuf<int> frq;
@@ -452,7 +452,7 @@ void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.c
 int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap, CapSrc *src);
 int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src);   // cap64 -> cap32 + int8 copies; exact: every component is (u8 - 127) / 128
 int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it);
-int lcs_ensure_btab(lcs_ctx *c);   // fp32 kernel's operand tables for the current workspace (allocated on first use)
+int lcs_ensure_xc(lcs_ctx *c, unsigned sets);   // XcSet bits: the sets a call needs, allocated for the current workspace on first use
 int lcs_launch_single_layout(lcs_ctx *c, const Launch &L, int slot, float *ref_layout, int to_ref);   // group-major <-> [t][idx][foi]
 int lcs_launch_foe_contend(lcs_ctx *c, const Launch &L, const double *fset_g, const long long *d_words, long long *d_words2);
 int lcs_launch_foe_resolve(lcs_ctx *c, long long *d_words, const long long *d_words2);

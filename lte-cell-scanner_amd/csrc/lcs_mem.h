@@ -2,7 +2,7 @@
 // lcs_internal.h).  A Buf is move-only, frees its block exactly once (reset(), a later alloc(), or its destructor) and
 // carries its capacity in elements: the capacity is non-zero only while the block it describes exists, so a failed
 // alloc() / reserve() leaves an empty owner that the next call allocates again.  It converts to T * by itself, so that
-// kernel arguments, copy operands, pointer arithmetic and `if (c->btab)` read as they do with a raw pointer.
+// kernel arguments, copy operands, pointer arithmetic and `if (c->xcb.btab)` read as they do with a raw pointer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>

@@ -987,12 +987,12 @@ __global__ __launch_bounds__(256) void k_foe_resolve(long long *__restrict__ wor
 
 // ------------------------------------------------------------------------------ launch
 // complex<double> in cap64 (slot 0): fp32 copy + int8 copies + exactness verdict (one small readback: the caller picks
-// the correlation kernel from it).  Needs the int8 buffers (ensure_i8 in lcs_api.hip).  The fp64 stages read cap64 itself.
+// the correlation kernel from it).  Needs the int8 set (lcs_ensure_xc).  The fp64 stages read cap64 itself.
 int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src) {
   *src = CapSrc{nullptr, c->cap64, nullptr, n_cap};
   HIPCHK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
-  hipLaunchKernelGGL(k_ingest_c128, dim3(nb), dim3(256), 0, c->stream, c->cap64, n_cap, c->cap32, c->i8.cap8, c->i8.cap8s, c->d_flag);
+  hipLaunchKernelGGL(k_ingest_c128, dim3(nb), dim3(256), 0, c->stream, c->cap64, n_cap, c->cap32, c->xcb.i8.cap8, c->xcb.i8.cap8s, c->d_flag);
   HIPCHK(c, hipGetLastError());
   int flag = 1;
   HIPCHK(c, hipMemcpyAsync(&flag, c->d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1004,17 +1004,89 @@ int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src)
 // fmt LCS_FMT_C128: cap64 (slot 0, uploaded by the caller) -> cap32
 int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap, CapSrc *src) {
   *src = CapSrc{nullptr, nullptr, nullptr, n_cap};
-  if (fmt == LCS_FMT_IQ_U8) src->c8 = c->i8.cap8;
+  if (fmt == LCS_FMT_IQ_U8) src->c8 = c->xcb.i8.cap8;
   else if (fmt == LCS_FMT_C128) src->c64 = c->cap64;
   else src->c32 = c->cap32;
   if (fmt == LCS_FMT_IQ_U8) {
     const unsigned nb = (unsigned)((lcs_cap8_stride(n_cap) / 8 + 255) / 256);
-    hipLaunchKernelGGL(k_ingest_u8, dim3(nb, n_buf), dim3(256), 0, c->stream, (const uint8_t *)d_src, n_cap, c->i8.cap8, c->i8.cap8s);
+    hipLaunchKernelGGL(k_ingest_u8, dim3(nb, n_buf), dim3(256), 0, c->stream, (const uint8_t *)d_src, n_cap, c->xcb.i8.cap8, c->xcb.i8.cap8s);
   } else {
     hipLaunchKernelGGL(k_ingest, dim3(128, n_buf), dim3(256), 0, c->stream, d_src, fmt, n_cap, c->cap32, c->cap64);
   }
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
+}
+
+// The correlation kernels' buffer sets (XcBufs), each sized like the current workspace and allocated as a whole on first use; the fp32
+// kernel's tables are 0.5 MB per (slot, window, group): only contexts that take it pay for them.  Under an open stream a missing set is refused.
+int lcs_ensure_xc(lcs_ctx *c, unsigned sets) {
+  XcBufs &b = c->xcb;
+  const size_t S = (size_t)c->cap_slots, G = (size_t)c->cap_G, n_cap8 = S * lcs_cap8_stride(c->cap_n_cap), n_btab = S * LCS_NW_MAX * G * LCS_KP2_MAX * 64;
+  int rc = LCS_OK;
+  auto missing = [&](unsigned set, bool ready, const char *refusal) {      // wanted and not there: refused, or to be allocated now
+    if (rc || !(sets & set) || ready) return false;
+    if (c->st_open) { c->err = refusal; rc = LCS_ERR_BAD_ARG; }
+    return rc == LCS_OK;
+  };
+  if (missing(XC_SET_I8, b.i8.ready, "int8 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"))
+    b.i8.ready = !((rc = b.i8.cap8.alloc(c, n_cap8)) || (rc = b.i8.cap8s.alloc(c, n_cap8)) || (rc = b.i8.brow8.alloc(c, S * G * LCS_I8_IMG)) ||
+                   (rc = b.i8.tq.alloc(c, S * G * LCS_TG)) || (rc = b.i8.tsc.alloc(c, S * G * LCS_TG)));
+  if (missing(XC_SET_F16, b.f16.ready, "fp16 buffers cannot be (re)allocated while a stream is open: lcs_stream_close first"))
+    b.f16.ready = !((rc = b.f16.cap16h.alloc(c, n_cap8)) || (rc = b.f16.cap16l.alloc(c, n_cap8)) || (rc = b.f16.brow16.alloc(c, S * G * LCS_F16_IMG)) ||
+                    (rc = b.f16.texp16.alloc(c, S * G * LCS_TG)) || (rc = b.f16.tsc16.alloc(c, S * G * LCS_TG)) ||
+                    (rc = b.f16.xmax16.alloc(c, S)) || (rc = b.f16.xpart16.alloc(c, S * 128)));
+  if (missing(XC_SET_BTAB, n_btab <= b.btab.capacity(), "the fp32 correlation tables cannot be allocated while a stream is open: lcs_stream_close first")) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rc = b.btab.reserve(c, n_btab);
+  }
+  return rc;
+}
+
+// one combining window: every element in the reference's own arithmetic, for every slot of the call at once
+static int lcs_launch_single_exact(lcs_ctx *c, hipStream_t sxc, const Launch &L) {
+  lcs_by_cap_kind(L.src, [&](auto kind) {
+    hipLaunchKernelGGL(k_single_exact<decltype(kind)::value>, dim3(EXS_CHUNKS, L.geo.G, L.n_buf), dim3(256), 0, sxc, L.src, L.params, L.fset, c->d_pss_td, c->start, c->single, L.geo);
+  });
+  c->last_xc_kernel = "k_single_exact";
+  return LCS_OK;
+}
+// The fp32 kernel's launchers, as those of the other two (pss_xcorr_i8.hip, pss_xcorr_f16.hip); its tables are allocated by its first
+// fill, and it reports no executed operations (last_xc_ops stays 0).
+static int lcs_launch_fill_btab(lcs_ctx *c, const Launch &L) {
+  if (int rc = lcs_ensure_xc(c, XC_SET_BTAB)) return rc;
+  hipLaunchKernelGGL(k_fill_btab, dim3(L.geo.n_comb * L.geo.G * L.n_buf), dim3(256), 0, c->stream, c->tmpl, c->start, c->smin, c->kp2, c->xcb.btab, L.geo, L.n_buf);
+  HIPCHK(c, hipGetLastError());
+  return LCS_OK;
+}
+static int lcs_launch_xcorr_f32(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map) {
+  const XcGeom &geo = L.geo;
+  constexpr int NWV = 4;                                                      // 4-wave workgroups, B through LDS
+  hipLaunchKernelGGL((k_xcorr_mfma_blk<4, NWV, 32>), dim3((unsigned)(((LCS_N_IDX + NWV * 64 - 1) / (NWV * 64)) * geo.G * n_slots)),
+                     dim3(NWV * 64), 0, sxc, c->cap32, c->smin, c->kp2, c->xcb.btab, c->single, geo, slot0, n_slots, xcd_map);
+  HIPCHK(c, hipGetLastError());
+  c->last_xc_kernel = "k_xcorr_mfma_blk<4,4,32>";
+  return LCS_OK;
+}
+// ---- lcs_launch_xcorr, step by step.  Two of the steps dispatch on the kernel: its operands, one part of its launches. ----
+// templates, window starts and per-group tables of the call, then the kernel's operands
+static int xc_tables_and_operands(lcs_ctx *c, const Launch &L) {
+  hipLaunchKernelGGL(k_prep_tables, dim3(L.n_buf, 4), dim3(256), 0, c->stream, L.params, L.fset, c->d_pss_td, c->tmpl, c->start, c->smin, c->kp2, c->n_fix, L.geo);
+  switch (L.xc) {
+    case XcKernel::i8: return lcs_launch_fill_brow_i8(c, L);
+    case XcKernel::f16: return lcs_launch_fill_brow_f16(c, L);
+    case XcKernel::fp32: return lcs_launch_fill_btab(c, L);
+    case XcKernel::single_exact: break;      // no operand tables
+  }
+  return LCS_OK;
+}
+static int xc_launch_part(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map) {
+  switch (L.xc) {
+    case XcKernel::i8: return lcs_launch_xcorr_i8(c, sxc, L, slot0, n_slots, xcd_map);
+    case XcKernel::f16: return lcs_launch_xcorr_f16(c, sxc, L, slot0, n_slots, xcd_map);
+    case XcKernel::fp32: return lcs_launch_xcorr_f32(c, sxc, L, slot0, n_slots, xcd_map);
+    case XcKernel::single_exact: break;      // its one part is the whole call (xc_correlate)
+  }
+  return lcs_launch_single_exact(c, sxc, L);
 }
 
 // The correlation kernel saturates the matrix pipes on its own; two of them from different
@@ -1026,127 +1098,102 @@ int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_
 static std::mutex g_xc_mutex;
 static hipEvent_t g_xc_done[64] = {};
 
-// The fp32 kernel's operand tables: one per (slot, window, group), 0.5 MB each -- only contexts that take this kernel pay for them.
-int lcs_ensure_btab(lcs_ctx *c) {
-  const size_t need = (size_t)c->cap_slots * LCS_NW_MAX * c->cap_G * LCS_KP2_MAX * 64;
-  if (need <= c->btab.capacity()) return LCS_OK;
-  if (c->st_open) { c->err = "the fp32 correlation tables cannot be allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return c->btab.reserve(c, need);
+// main stream -> correlation stream (tables and capture buffer are ready), behind the device's previous correlation
+static int xc_hand_over(lcs_ctx *c, hipStream_t sxc) {
+  HIPCHK(c, hipEventRecord(c->ev_pre, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(sxc, c->ev_pre, 0));
+  std::lock_guard<std::mutex> lk(g_xc_mutex);
+  hipEvent_t &ev = g_xc_done[c->device & 63];
+  if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming | LCS_EVENT_NOFENCE));
+  else HIPCHK(c, hipStreamWaitEvent(sxc, ev, 0));
+  return LCS_OK;
+}
+// ... and back: the device's next correlation and this context's main stream wait for this one
+static int xc_hand_back(lcs_ctx *c, hipStream_t sxc) {
+  {
+    std::lock_guard<std::mutex> lk(g_xc_mutex);
+    HIPCHK(c, hipEventRecord(g_xc_done[c->device & 63], sxc));
+  }
+  HIPCHK(c, hipEventRecord(c->ev_post, sxc));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_post, 0));
+  return LCS_OK;
 }
 
-int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it) {
-  const int n_buf = L.n_buf;
+// The signal-power estimate and the threshold need the capture buffer only, not the correlation: in the batch / single-buffer chains
+// the correlation sits on stream_xc and they run BESIDE it on the main stream, behind the hand-over event (rounds 1-5 enqueued
+// them in front of it: the correlation of a single buffer waited 26 us for them; lcs_search_capbuf 0.377 -> 0.337 ms same-box).
+// The streaming mode's captured chain keeps everything on one stream: as a parallel branch of the graph (fork to stream_xc, join
+// before the collapse) a replay took 0.315 instead of 0.273 ms -- the runtime replays a forked graph over several streams.
+static void xc_signal_power(lcs_ctx *c, const Launch &L) {
   const XcGeom &geo = L.geo;
-  const CapSrc &cs = L.src;
-  hipLaunchKernelGGL(k_prep_tables, dim3(n_buf, 4), dim3(256), 0, c->stream, L.params, L.fset, c->d_pss_td, c->tmpl,
-                     c->start, c->smin, c->kp2, c->n_fix, geo);
-  // one combining window: every element in the reference's own arithmetic (k_single_exact); no operand tables needed
-  const bool exact_single = geo.n_comb == 1;
-  if (exact_single) ;
-  else if (L.xc == XcKernel::i8) {
-    int rc_ = lcs_launch_fill_brow_i8(c, L);
-    if (rc_) return rc_;
-  } else if (L.xc == XcKernel::f16) {
-    int rc_ = lcs_launch_fill_brow_f16(c, L);
-    if (rc_) return rc_;
-  } else {
-    { int rc_ = lcs_ensure_btab(c); if (rc_) return rc_; }
-    hipLaunchKernelGGL(k_fill_btab, dim3(geo.n_comb * geo.G * n_buf), dim3(256), 0, c->stream, c->tmpl,
-                       c->start, c->smin, c->kp2, c->btab, geo, n_buf);
-  }
-  // The signal-power estimate and the threshold need the capture buffer only, not the correlation: in the batch / single-buffer chains
-  // the correlation sits on stream_xc and they run BESIDE it on the main stream, behind the hand-over event (rounds 1-5 enqueued
-  // them in front of it: the correlation of a single buffer waited 26 us for them; lcs_search_capbuf 0.377 -> 0.337 ms same-box).
-  // The streaming mode's captured chain keeps everything on one stream: as a parallel branch of the graph (fork to stream_xc, join
-  // before the collapse) a replay took 0.315 instead of 0.273 ms -- the runtime replays a forked graph over several streams.
+  const int n_buf = L.n_buf;
   const SpArgs a = make_sp_args(geo);
-  auto launch_sp = [&](hipStream_t st) {
-    if (cs.c8) {
-      hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, st, c->i8.cap8, geo.n_cap, c->spinc, c->zth, a);
-    } else {
-      hipLaunchKernelGGL(k_sp_sums, dim3(((LCS_N_IDX + SP_TILE - 1) / SP_TILE) * a.n_comb_sp * n_buf), dim3(64), 0,
-                         st, cs, c->sp, geo.n_cap, a.n_comb_sp, n_buf);       // one-wave workgroups
-      hipLaunchKernelGGL(k_sp_fold, dim3((n_buf * LCS_N_IDX + 255) / 256), dim3(256), 0, st, c->sp, c->spinc, c->zth, a, n_buf);
-    }
-  };
+  if (L.src.c8) {
+    hipLaunchKernelGGL(k_sp_i8, dim3(LCS_N_IDX / SPI_TILE, n_buf), dim3(256), 0, c->stream, c->xcb.i8.cap8, geo.n_cap, c->spinc, c->zth, a);
+  } else {
+    hipLaunchKernelGGL(k_sp_sums, dim3(((LCS_N_IDX + SP_TILE - 1) / SP_TILE) * a.n_comb_sp * n_buf), dim3(64), 0,
+                       c->stream, L.src, c->sp, geo.n_cap, a.n_comb_sp, n_buf);       // one-wave workgroups
+    hipLaunchKernelGGL(k_sp_fold, dim3((n_buf * LCS_N_IDX + 255) / 256), dim3(256), 0, c->stream, c->sp, c->spinc, c->zth, a, n_buf);
+  }
+}
 
-  // slots [0, n8) with the XCD-aware mapping, the remainder with the plain one
-  const int n8 = (n_buf >= 8) ? (n_buf & ~7) : 0;
-  // main stream -> correlation stream hand-off (tables and capture buffer are ready)
-  const bool single_stream = L.single_stream;
-  hipStream_t sxc = single_stream ? c->stream : c->stream_xc;
-  if (!single_stream) {
-    HIPCHK(c, hipEventRecord(c->ev_pre, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(sxc, c->ev_pre, 0));
-    {
-      std::lock_guard<std::mutex> lk(g_xc_mutex);
-      hipEvent_t &ev = g_xc_done[c->device & 63];
-      if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming | LCS_EVENT_NOFENCE));
-      else HIPCHK(c, hipStreamWaitEvent(sxc, ev, 0));
-    }
-    launch_sp(c->stream);
-  } else
-    launch_sp(c->stream);
+// the correlation launches: slots [0, n8) with the XCD-aware mapping, the remainder with the plain one (k_single_exact has none: one launch)
+static int xc_correlate(lcs_ctx *c, hipStream_t sxc, const Launch &L, bool time_it) {
+  const int n_buf = L.n_buf;
+  const int n8 = (n_buf >= 8 && L.xc != XcKernel::single_exact) ? (n_buf & ~7) : 0;
   if (time_it) HIPCHK(c, hipEventRecord(c->ev_xc0, sxc));
   int launches = 0;
   c->last_xc_ops = 0;
-  c->last_xc_kernel = "k_xcorr_mfma_blk<4,4,32>";
-  if (exact_single) {
-    const dim3 grid(EXS_CHUNKS, geo.G, n_buf);
-    lcs_by_cap_kind(cs, [&](auto kind) {
-      hipLaunchKernelGGL(k_single_exact<decltype(kind)::value>, grid, dim3(256), 0, sxc, cs, L.params, L.fset, c->d_pss_td, c->start, c->single, geo);
-    });
-    c->last_xc_kernel = "k_single_exact";
-    launches = 1;
-  }
-  for (int part = 0; part < 2 && !exact_single; ++part) {
+  for (int part = 0; part < 2; ++part) {
     const int s0 = part ? n8 : 0, ns = part ? n_buf - n8 : n8;
     if (ns <= 0) continue;
-    if (L.xc == XcKernel::i8) {                                                 // u8 sources: int8 three-digit kernel
-      int rc_ = lcs_launch_xcorr_i8(c, sxc, L, s0, ns, part ? 0 : 1);
-      if (rc_) return rc_;
-    } else if (L.xc == XcKernel::f16) {                                         // complex<float> batches: fp16 three-product kernel
-      int rc_ = lcs_launch_xcorr_f16(c, sxc, L, s0, ns, part ? 0 : 1);
-      if (rc_) return rc_;
-    } else {                                                                    // fp32: 4-wave workgroups, B through LDS
-      constexpr int NWV = 4;
-      hipLaunchKernelGGL((k_xcorr_mfma_blk<4, NWV, 32>), dim3((unsigned)(((LCS_N_IDX + NWV * 64 - 1) / (NWV * 64)) * geo.G * ns)),
-                         dim3(NWV * 64), 0, sxc, c->cap32, c->smin, c->kp2, c->btab, c->single, geo, s0, ns, part ? 0 : 1);
-    }
+    if (int rc = xc_launch_part(c, sxc, L, s0, ns, part ? 0 : 1)) return rc;
     ++launches;
   }
   if (time_it) { HIPCHK(c, hipEventRecord(c->ev_xc1, sxc)); c->last_xc_launches = launches; }
-  if (!single_stream) {
-    {
-      std::lock_guard<std::mutex> lk(g_xc_mutex);
-      HIPCHK(c, hipEventRecord(g_xc_done[c->device & 63], sxc));
-    }
-    HIPCHK(c, hipEventRecord(c->ev_post, sxc));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_post, 0));
-  }
-  {
-    const dim3 grid((LCS_N_IDX / 64) * n_buf), block(256);
-    float *incoh = want_incoh ? c->incoh : nullptr;
-    float *pow32 = reinterpret_cast<float *>(c->work.get());
-    const double *zf = L.repair == FrqRepair::peaks_only ? c->zth : nullptr;         // only near-ties that can become a peak
-    float *s2 = L.repair == FrqRepair::none_keep_2nd ? c->second32 : nullptr;        // the runner-up values for lcs_foe_contend
-    if (geo.ds == 2 && !incoh && geo.cpg == LCS_TG)
-      hipLaunchKernelGGL(k_collapse_arm2, dim3((LCS_N_IDX / (4 * COLLAPSE_OUT)) * n_buf), block, 0, c->stream, c->single, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
-    else if (geo.ds == 2 && !incoh) hipLaunchKernelGGL((k_collapse<2, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
-    else if (!incoh) hipLaunchKernelGGL((k_collapse<-1, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);   // any arm, no debug copy
-    else hipLaunchKernelGGL((k_collapse<-1, true>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
-    // near-ties of the arg-max, recomputed in the reference's arithmetic (a few positions per buffer; the kernel loops over the list)
-    if (L.repair != FrqRepair::none_keep_2nd && geo.n_f > 1) {      // (one hypothesis -- the streaming mode -- has no arg-max to repair: one graph node less)
-      // at least 64 workgroups: a single buffer on a dense raster lists a few hundred genuine near-ties (tests/test_gpu_frq_ties.py:
-      // 336 on a one-window buffer), which 8 workgroups (crowded beyond 256) would have left to the bound meant for degenerate grids
-      const int ng = std::min(512, std::max(64, 8 * n_buf));
-      lcs_by_cap_kind(cs, [&](auto kind) {
-        hipLaunchKernelGGL((k_frq_repair<decltype(kind)::value, false>), dim3(ng), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, cs,
-                           L.params, L.fset, c->d_pss_td, c->start, c->pow_, pow32, c->frq, nullptr, nullptr, c->zth, c->n_fix + 1, geo);
-      });
-    }
-  }
+  return LCS_OK;
+}
+
+// xc_incoherent_single -> collapsed power, arg-max and the list of its near-ties
+static void xc_collapse(lcs_ctx *c, const Launch &L, bool want_incoh) {
+  const XcGeom &geo = L.geo;
+  const int n_buf = L.n_buf;
+  const dim3 grid((LCS_N_IDX / 64) * n_buf), block(256);
+  float *incoh = want_incoh ? c->incoh : nullptr;
+  float *pow32 = reinterpret_cast<float *>(c->work.get());
+  const double *zf = L.repair == FrqRepair::peaks_only ? c->zth : nullptr;         // only near-ties that can become a peak
+  float *s2 = L.repair == FrqRepair::none_keep_2nd ? c->second32 : nullptr;        // the runner-up values for lcs_foe_contend
+  if (geo.ds == 2 && !incoh && geo.cpg == LCS_TG)
+    hipLaunchKernelGGL(k_collapse_arm2, dim3((LCS_N_IDX / (4 * COLLAPSE_OUT)) * n_buf), block, 0, c->stream, c->single, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
+  else if (geo.ds == 2 && !incoh) hipLaunchKernelGGL((k_collapse<2, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
+  else if (!incoh) hipLaunchKernelGGL((k_collapse<-1, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);   // any arm, no debug copy
+  else hipLaunchKernelGGL((k_collapse<-1, true>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
+}
+
+// near-ties of the arg-max, recomputed in the reference's arithmetic (a few positions per buffer; the kernel loops over the list)
+static void xc_tie_repair(lcs_ctx *c, const Launch &L) {
+  const XcGeom &geo = L.geo;
+  if (L.repair == FrqRepair::none_keep_2nd || geo.n_f <= 1) return;      // (one hypothesis -- the streaming mode -- has no arg-max to repair: one graph node less)
+  // at least 64 workgroups: a single buffer on a dense raster lists a few hundred genuine near-ties (tests/test_gpu_frq_ties.py:
+  // 336 on a one-window buffer), which 8 workgroups (crowded beyond 256) would have left to the bound meant for degenerate grids
+  const int ng = std::min(512, std::max(64, 8 * L.n_buf));
+  float *pow32 = reinterpret_cast<float *>(c->work.get());
+  lcs_by_cap_kind(L.src, [&](auto kind) {
+    hipLaunchKernelGGL((k_frq_repair<decltype(kind)::value, false>), dim3(ng), dim3(REPAIR_THREADS), 0, c->stream, c->single, c->fix_list, c->n_fix, L.src,
+                       L.params, L.fset, c->d_pss_td, c->start, c->pow_, pow32, c->frq, nullptr, nullptr, c->zth, c->n_fix + 1, geo);
+  });
+}
+
+int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it) {
+  hipStream_t sxc = L.single_stream ? c->stream : c->stream_xc;      // a context with an open stream keeps everything on its main stream: no hand-over
+  int rc;
+  if ((rc = xc_tables_and_operands(c, L))) return rc;
+  if (!L.single_stream && (rc = xc_hand_over(c, sxc))) return rc;
+  xc_signal_power(c, L);
+  if ((rc = xc_correlate(c, sxc, L, time_it))) return rc;
+  if (!L.single_stream && (rc = xc_hand_back(c, sxc))) return rc;
+  xc_collapse(c, L, want_incoh);
+  xc_tie_repair(c, L);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

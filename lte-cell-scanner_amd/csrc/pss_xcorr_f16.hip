@@ -365,22 +365,22 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_f16x3(const uint32_t *__restri
 // ---- launchers -----------------------------------------------------------------------------------------------------
 // d_src: the caller's complex<float> buffers (LCS_FMT_C64, device memory); replaces lcs_launch_ingest for these batches
 int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap, CapSrc *src) {
-  HIPCHK(c, hipMemsetAsync(c->f16.xmax16, 0, sizeof(unsigned) * n_buf, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->xcb.f16.xmax16, 0, sizeof(unsigned) * n_buf, c->stream));
   if ((n_cap & 1u) == 0 && (reinterpret_cast<uintptr_t>(d_src) & 15u) == 0) {
     // read in place: no copy into cap32; the fp64 stages read the caller's buffers (they stay valid until the batch is
     // collected, include/lcs.h), the maximum is a read-only pass
     *src = CapSrc{static_cast<const float2 *>(d_src), nullptr, nullptr, n_cap};
     const unsigned per_wg = 256 * F16_MAX_ILP, n_part = (n_cap / 2 + per_wg - 1) / per_wg;
     if (n_part > F16_MAXP) { c->err = "capture buffer too long for the fp16 path's partial maxima"; return LCS_ERR_BAD_ARG; }     // > 262144 samples: check_common refuses those
-    hipLaunchKernelGGL(k_f16_max4, dim3(n_part, n_buf), dim3(256), 0, c->stream, static_cast<const float4 *>(d_src), n_cap, c->f16.xpart16);
-    hipLaunchKernelGGL(k_f16_max_fold, dim3(n_buf), dim3(128), 0, c->stream, c->f16.xpart16, (int)n_part, c->f16.xmax16);
+    hipLaunchKernelGGL(k_f16_max4, dim3(n_part, n_buf), dim3(256), 0, c->stream, static_cast<const float4 *>(d_src), n_cap, c->xcb.f16.xpart16);
+    hipLaunchKernelGGL(k_f16_max_fold, dim3(n_buf), dim3(128), 0, c->stream, c->xcb.f16.xpart16, (int)n_part, c->xcb.f16.xmax16);
     hipLaunchKernelGGL((k_f16_ingest<true>), dim3((unsigned)((lcs_cap8_stride(n_cap) / 2 + per_wg - 1) / per_wg), n_buf), dim3(256), 0, c->stream, src->c32,
-                       n_cap, c->f16.xmax16, c->f16.cap16h, c->f16.cap16l);
+                       n_cap, c->xcb.f16.xmax16, c->xcb.f16.cap16h, c->xcb.f16.cap16l);
   } else {
     int rc = lcs_launch_ingest(c, d_src, LCS_FMT_C64, n_buf, n_cap, src);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_f16_max, dim3(32, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->f16.xmax16);
-    hipLaunchKernelGGL((k_f16_ingest<false>), dim3(64, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->f16.xmax16, c->f16.cap16h, c->f16.cap16l);
+    hipLaunchKernelGGL(k_f16_max, dim3(32, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->xcb.f16.xmax16);
+    hipLaunchKernelGGL((k_f16_ingest<false>), dim3(64, n_buf), dim3(256), 0, c->stream, c->cap32, n_cap, c->xcb.f16.xmax16, c->xcb.f16.cap16h, c->xcb.f16.cap16l);
   }
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
@@ -388,8 +388,8 @@ int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_c
 int lcs_launch_fill_brow_f16(lcs_ctx *c, const Launch &L) {
   const int n_buf = L.n_buf;
   const XcGeom &geo = L.geo;
-  hipLaunchKernelGGL(k_f16_scales, dim3(n_buf), dim3(256), 0, c->stream, c->tmpl, c->f16.xmax16, c->f16.texp16, c->f16.tsc16, geo);
-  hipLaunchKernelGGL(k_fill_brow_f16, dim3((LCS_TG * F16R_RLEN + 255) / 256, geo.G, n_buf), dim3(256), 0, c->stream, c->tmpl, c->f16.texp16, c->f16.brow16, geo);
+  hipLaunchKernelGGL(k_f16_scales, dim3(n_buf), dim3(256), 0, c->stream, c->tmpl, c->xcb.f16.xmax16, c->xcb.f16.texp16, c->xcb.f16.tsc16, geo);
+  hipLaunchKernelGGL(k_fill_brow_f16, dim3((LCS_TG * F16R_RLEN + 255) / 256, geo.G, n_buf), dim3(256), 0, c->stream, c->tmpl, c->xcb.f16.texp16, c->xcb.f16.brow16, geo);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
@@ -398,10 +398,10 @@ int lcs_launch_xcorr_f16(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0
   const unsigned grid = (unsigned)(F16_TILES * geo.G * n_slots);
   const bool narrow = geo.n_narrow >= geo.n_comb;
   if (narrow)
-    hipLaunchKernelGGL(k_xcorr_f16x3<true>, dim3(grid), dim3(256), 0, sxc, c->f16.cap16h, c->f16.cap16l, c->smin, c->start, c->f16.brow16, c->f16.tsc16, c->single, geo,
+    hipLaunchKernelGGL(k_xcorr_f16x3<true>, dim3(grid), dim3(256), 0, sxc, c->xcb.f16.cap16h, c->xcb.f16.cap16l, c->smin, c->start, c->xcb.f16.brow16, c->xcb.f16.tsc16, c->single, geo,
                        slot0, n_slots, xcd_map);
   else
-    hipLaunchKernelGGL(k_xcorr_f16x3<false>, dim3(grid), dim3(256), 0, sxc, c->f16.cap16h, c->f16.cap16l, c->smin, c->start, c->f16.brow16, c->f16.tsc16, c->single, geo,
+    hipLaunchKernelGGL(k_xcorr_f16x3<false>, dim3(grid), dim3(256), 0, sxc, c->xcb.f16.cap16h, c->xcb.f16.cap16l, c->smin, c->start, c->xcb.f16.brow16, c->xcb.f16.tsc16, c->single, geo,
                        slot0, n_slots, xcd_map);
   HIPCHK(c, hipGetLastError());
   // executed work: per wave and window 3 products x F16_NKB tap blocks x F16_MT sub-tiles x (re, im) MFMAs of 16x16x32 MACs

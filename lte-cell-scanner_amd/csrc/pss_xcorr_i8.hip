@@ -346,15 +346,15 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
 int lcs_launch_fill_brow_i8(lcs_ctx *c, const Launch &L) {
   const int n_buf = L.n_buf;
   const XcGeom &geo = L.geo;
-  hipLaunchKernelGGL(k_i8_scales, dim3(n_buf), dim3(256), 0, c->stream, c->tmpl, c->i8.tq, c->i8.tsc, geo);
-  hipLaunchKernelGGL(k_fill_brow_i8, dim3((LCS_TG * 2 * I8R_RLEN + 255) / 256, geo.G, n_buf), dim3(256), 0, c->stream, c->tmpl, c->i8.tq, c->i8.brow8, geo);
+  hipLaunchKernelGGL(k_i8_scales, dim3(n_buf), dim3(256), 0, c->stream, c->tmpl, c->xcb.i8.tq, c->xcb.i8.tsc, geo);
+  hipLaunchKernelGGL(k_fill_brow_i8, dim3((LCS_TG * 2 * I8R_RLEN + 255) / 256, geo.G, n_buf), dim3(256), 0, c->stream, c->tmpl, c->xcb.i8.tq, c->xcb.i8.brow8, geo);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
 int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map) {
   const XcGeom &geo = L.geo;
   const unsigned grid = (unsigned)(I8_TILES * geo.G * n_slots);
-  hipLaunchKernelGGL(k_xcorr_i8x3, dim3(grid), dim3(256), 0, sxc, c->i8.cap8, c->i8.cap8s, c->smin, c->start, c->i8.brow8, c->i8.tsc, c->single, geo, slot0,
+  hipLaunchKernelGGL(k_xcorr_i8x3, dim3(grid), dim3(256), 0, sxc, c->xcb.i8.cap8, c->xcb.i8.cap8s, c->smin, c->start, c->xcb.i8.brow8, c->xcb.i8.tsc, c->single, geo, slot0,
                      n_slots, xcd_map);
   HIPCHK(c, hipGetLastError());
   // executed work: per wave and window 3 digits x I8_NKB tap blocks x I8_MT sub-tiles x (re, im) MFMAs of 16x16x64 MACs

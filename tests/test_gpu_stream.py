@@ -144,3 +144,43 @@ def test_complex64_batch_on_a_context_with_an_open_stream(pkg):
         cells, _, _ = S.stream_collect()
         assert [c.n_id_cell() for c in cells] == [277, 271]
         S.stream_close()
+
+
+def test_routes_of_a_context_whose_open_stream_forbids_the_int8_set(pkg):
+    """The three rows of the routing rule (csrc/xcorr_route.h) that only a context with an open complex<float> stream and no int8
+    set reaches, on the shortest capture with two combining windows (one hypothesis, one buffer: what the stream's workspace
+    holds; k_single_exact does not take over): (a) a dongle host buffer keeps the fp32 kernel and finds what a fresh context's
+    int8 kernel finds; (b) a u8 batch is refused; (c) a complex<float> batch is not probed, let alone routed, and the stream lives on."""
+    import torch
+    n = 2 * 9600 + 136 + 100
+    g = np.ascontiguousarray(golden("capbuf_0000")["iq_u8"][:2 * n])
+    cap = iq_u8_to_capbuf(g)
+    c64 = cap.astype(np.complex64)
+    d8, d32 = torch.from_numpy(g[None, :]).cuda(), torch.from_numpy(c64[None, :]).cuda()
+    f, fc = np.array([35e3]), np.array([FC])
+    pk_key = lambda p: (p.n_id_2, p.ind, p.freq)
+    with pkg.Searcher(0) as S, pkg.Searcher(0) as F:
+        S.stream_open(pkg.FMT_C64, n, FC, FC, FS)
+        S.stream_push(c64, 35e3)
+        before = S.stream_collect()[:2]
+        # (a)
+        cells, peaks = S.search_capbuf(cap, f, FC, FC, FS)
+        assert S.last_xcorr_info()[0].startswith("k_xcorr_mfma_blk"), S.last_xcorr_info()
+        ref_cells, ref_peaks = F.search_capbuf(cap, f, FC, FC, FS)
+        assert F.last_xcorr_info()[0] == "k_xcorr_i8x3"
+        assert [_key(c) for c in cells] == [_key(c) for c in ref_cells]
+        assert [pk_key(p) for p in peaks] == [pk_key(p) for p in ref_peaks] and len(peaks) >= 1
+        for x, y in zip(peaks, ref_peaks):
+            assert abs(x.pss_pow - y.pss_pow) <= 1e-5 * y.pss_pow
+        # (b)
+        with pytest.raises(pkg.SearcherError, match=r"int8 buffers cannot be \(re\)allocated while a stream is open: lcs_stream_close first"):
+            S.batch_enqueue(d8.data_ptr(), pkg.FMT_IQ_U8, 1, n, f, fc, fc, FS, pkg.STAGE_FULL)
+        # (c)
+        S.set_float_batch_probe(True)
+        got = S.search_batch(d32.data_ptr(), pkg.FMT_C64, 1, n, f, fc, fc, FS, pkg.STAGE_FULL)[0]
+        assert S.last_xcorr_info()[0].startswith("k_xcorr_mfma_blk"), S.last_xcorr_info()
+        assert [_key(c) for c in got] == [_key(c) for c in ref_cells]
+        S.stream_push(c64, 35e3)
+        after = S.stream_collect()[:2]
+        assert [_key(c) for c in after[0]] == [_key(c) for c in before[0]] and after[1] == before[1]
+        S.stream_close()

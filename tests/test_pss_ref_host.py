@@ -33,7 +33,7 @@ _dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
 
 @pytest.fixture(scope="module")
 def H():
-    dep = [SRC] + [os.path.join(CSRC, h) for h in ("pss_ref.h", "lcs_internal.h")]
+    dep = [SRC] + [os.path.join(CSRC, h) for h in ("pss_ref.h", "lcs_internal.h", "xcorr_route.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in dep):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC",
                                "-shared", "-I" + os.path.join(ROOT, "include"), "-o", LIB, SRC])
