@@ -569,6 +569,39 @@ int lcs_chan_stream_push(lcs_ctx *ctx, const void *d_chunk /*DEVICE, n_chunk sam
                          void *d_out /*DEVICE complex<float>*/, uint32_t row_stride /*samples between carrier rows*/, uint32_t out_cap,
                          uint32_t *n_emit, uint64_t *m_first);
 int lcs_chan_stream_close(lcs_ctx *ctx);
+/* The continuous form with 8-bit carriers: the stream hands out whole CAPTURES of n_cap outputs per carrier as bytes, the
+ * LCS_FMT_IQ_U8 batch layout, each capture of each carrier scaled by a power of two of its own -- what a live band search feeds the
+ * int8 correlation kernel.  M(N), the formats, the rates, the chunk's alignment, the stream ordering and the non-finite clause are
+ * lcs_chan_stream_open's.  Capture c is the outputs m = c * n_cap .. (c + 1) * n_cap - 1 of every carrier.  After a push exactly the
+ * captures c < M(N) / n_cap (integer division) have been handed out, each once: a push writes the captures cap_first .. cap_first +
+ * n_done - 1, capture cap_first + j to slot j of d_out and of d_gain, and touches nothing else of either; slots >= n_done stay as
+ * they were.  n_done and cap_first (either may be NULL) are closed forms of N and are returned without waiting for the GPU.
+ *   Bytes.   With y_k[m] the floats lcs_chan_stream_push hands out for the same samples (bit for bit those of one
+ *            lcs_channelize_rational call), capture c of carrier k is lcs_channelize_u8's rule on y_k[c * n_cap ..]: P = the mean of
+ *            |y|^2 over the capture; e the integer with 16^2 < 4^e * P / 2 <= 32^2, 0 for a P that is zero or not finite; code =
+ *            clamp(127 + rint(2^e * component), 0, 255), ties to even, 127 for a component that is not finite; d_gain = 2^e.
+ *   Chunking.  A gain is constant inside a capture and free between captures: every threshold of the search chain is relative to the
+ *            buffer's own power.  It is known when the capture is complete, so the stream keeps the capture in hand as floats
+ *            ([n_ch][n_cap] complex<float>, allocated by open_u8, freed by close) and sums P from those floats in ONE order that
+ *            depends on n_cap only (fp32 over fixed blocks of a row, double across the blocks): any two ways of cutting the same
+ *            samples into pushes, and any two runs, give the same bytes and the same gains, bit for bit.
+ *   Layout.  A capture is [n_ch][n_cap][2] bytes, I then Q: rows lie 2 * n_cap bytes apart (at any even address when n_cap is odd),
+ *            captures 2 * n_ch * n_cap bytes apart.  d_out: DEVICE [cap_room][n_ch][n_cap][2], 16-byte aligned; d_gain: DEVICE
+ *            [cap_room][n_ch] floats, or NULL.
+ *   open_u8  as open, plus n_cap >= 1.  A context holds ONE channelizer stream of either kind; close closes either.
+ *   count_u8 n_done of a push of n_chunk samples now; nothing is queued.  lcs_chan_stream_count works on either kind of stream.
+ *   push_u8  d_chunk as push takes it.  A push may complete no capture (it writes nothing then) or many.
+ * LCS_ERR_BAD_ARG (an lcs_last_error text, nothing launched, the stream where it was; all decided before the first launch): everything
+ * open refuses; n_cap < 1; a stream already open; count_u8 or push_u8 with no stream or on a stream opened by lcs_chan_stream_open;
+ * lcs_chan_stream_push on a stream opened here; n_chunk above 2^31; a null chunk with n_chunk > 0; a misaligned chunk; a null d_out
+ * with captures to hand out; d_out not 16-byte aligned; d_gain not aligned to a float; cap_room < n_done.  lcs_last_channelize_ms is
+ * not set by a push. */
+int lcs_chan_stream_open_u8(lcs_ctx *ctx, int fmt, double fs_in, int up, int down, const double *f_shift /*host [n_ch]*/, int n_ch,
+                            uint32_t n_cap);
+int lcs_chan_stream_count_u8(lcs_ctx *ctx, uint64_t n_chunk, uint32_t *n_done);
+int lcs_chan_stream_push_u8(lcs_ctx *ctx, const void *d_chunk /*DEVICE, n_chunk samples of fmt*/, uint64_t n_chunk,
+                            void *d_out /*DEVICE [cap_room][n_ch][n_cap][2] u8, 16-byte aligned*/,
+                            float *d_gain /*DEVICE [cap_room][n_ch] or NULL*/, uint32_t cap_room, uint32_t *n_done, uint64_t *cap_first);
 /* HIP-event time (ms) of the last lcs_channelize, lcs_channelize_rational or lcs_channelize_u8 of the context (filter-bank build
  * through the call's last kernel), as lcs_last_xcorr_ms */
 int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);

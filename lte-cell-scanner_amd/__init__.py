@@ -535,6 +535,30 @@ class Searcher:
     def chan_stream_close(self):
         self._chk(self._lib.lcs_chan_stream_close(self._h), "lcs_chan_stream_close")
 
+    def chan_stream_open_u8(self, fmt: int, fs_in: float, up: int, down: int, f_shift, n_cap: int):
+        """Open the context's channelizer stream for 8-bit captures (lcs_chan_stream_open_u8): as chan_stream_open, but the stream
+        hands out whole captures of n_cap outputs per carrier as bytes, the FMT_IQ_U8 batch layout, each capture of each carrier
+        scaled by channelize_u8's rule with a gain of its own -- the same bytes and gains however the samples are cut into pushes."""
+        f = np.ascontiguousarray(np.atleast_1d(f_shift), np.float64)
+        self._chk(self._lib.lcs_chan_stream_open_u8(self._h, int(fmt), float(fs_in), int(up), int(down), _dp(f), int(f.size), int(n_cap)),
+                  "lcs_chan_stream_open_u8")
+
+    def chan_stream_count_u8(self, n_chunk: int) -> int:
+        """Captures a push_u8 of n_chunk samples would complete now (lcs_chan_stream_count_u8)."""
+        n = C.c_uint32(0)
+        self._chk(self._lib.lcs_chan_stream_count_u8(self._h, int(n_chunk), C.byref(n)), "lcs_chan_stream_count_u8")
+        return n.value
+
+    def chan_stream_push_u8(self, d_chunk_ptr: int, n_chunk: int, d_out_ptr: int, d_gain_ptr: int, cap_room: int):
+        """Push n_chunk samples at d_chunk_ptr (device).  Capture cap_first + j goes to slot j of d_out_ptr (device, uint8
+        [cap_room][n_ch][n_cap][2], 16-byte aligned) and its gains to slot j of d_gain_ptr (device, float32 [cap_room][n_ch]; 0 or
+        None for no gains), j < n_done <= cap_room.  Queued on the context's stream.  Returns (n_done, cap_first), known without
+        waiting for the GPU."""
+        n, m = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self._lib.lcs_chan_stream_push_u8(self._h, C.c_void_p(d_chunk_ptr), int(n_chunk), C.c_void_p(d_out_ptr), C.c_void_p(d_gain_ptr or None),
+                                                    int(cap_room), C.byref(n), C.byref(m)), "lcs_chan_stream_push_u8")
+        return n.value, m.value
+
     def last_channelize_ms(self) -> float:
         """HIP-event time (ms) of the last channelize / channelize_rational / channelize_u8 call of this context (lcs_last_channelize_ms)."""
         ms = C.c_float(0)

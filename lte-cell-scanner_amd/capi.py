@@ -72,6 +72,7 @@ EXPORTS = [
     "lcs_table_lte_pn", "lcs_chi2cdf_inv", "lcs_channelizer_taps", "lcs_channelize", "lcs_last_channelize_ms",
     "lcs_channelizer_proto", "lcs_channelize_rational", "lcs_channelize_u8",
     "lcs_chan_stream_open", "lcs_chan_stream_count", "lcs_chan_stream_push", "lcs_chan_stream_close",
+    "lcs_chan_stream_open_u8", "lcs_chan_stream_count_u8", "lcs_chan_stream_push_u8",
 ]
 
 _lib = None
@@ -173,6 +174,9 @@ def load() -> C.CDLL:
     L.lcs_chan_stream_count.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32)]
     L.lcs_chan_stream_push.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.lcs_chan_stream_close.argtypes = [vp]
+    L.lcs_chan_stream_open_u8.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, dp, C.c_int, C.c_uint32]
+    L.lcs_chan_stream_count_u8.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint32)]
+    L.lcs_chan_stream_push_u8.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.lcs_stream.argtypes = [vp]
     L.lcs_stream.restype = vp
     L.lcs_sync.argtypes = [vp]

@@ -58,7 +58,8 @@ static inline const char *chan_refusal(const ChanCall &a, ChanRules rules) {
 
 // The continuous form (include/lcs.h, lcs_chan_stream_open): what its four entry points refuse beyond chan_refusal, in the order they
 // look.  open hands its rate, format, shifts and n_ch to chan_refusal first (CHAN_RATE; the rules for n_in, n_out and d_out have
-// nothing to look at there) and then asks here; count looks at the first two rules, close at the first.
+// nothing to look at there) and then asks here; count looks at the first two rules, close at the first.  count and close take either
+// kind of stream; a push on a stream of 8-bit captures is refused behind the first rule.
 enum ChanStreamEntry { CHAN_STREAM_OPEN, CHAN_STREAM_COUNT, CHAN_STREAM_PUSH, CHAN_STREAM_CLOSE };
 struct ChanPush {
   bool is_open;              // the context has a stream
@@ -68,11 +69,13 @@ struct ChanPush {
   void *d_out;
   uint32_t row_stride, out_cap;
   uint64_t n_emit;           // what the push would hand out (cs_count)
+  bool is_u8 = false;        // the stream hands out 8-bit captures (lcs_chan_stream_open_u8): its pushes are lcs_chan_stream_push_u8's
 };
 static inline const char *chan_stream_refusal(const ChanPush &a, ChanStreamEntry entry) {
   if (entry == CHAN_STREAM_OPEN) return a.is_open ? "a channelizer stream is already open on this context" : nullptr;
   if (!a.is_open) return "no channelizer stream is open on this context";
   if (entry == CHAN_STREAM_CLOSE) return nullptr;
+  if (entry == CHAN_STREAM_PUSH && a.is_u8) return "the stream hands out 8-bit captures: push with lcs_chan_stream_push_u8";
   if (a.n_chunk > (1ull << 31)) return "n_chunk > 2^31";
   if (entry == CHAN_STREAM_COUNT) return nullptr;
   if (!a.d_chunk && a.n_chunk) return "null chunk with n_chunk > 0";
@@ -82,6 +85,38 @@ static inline const char *chan_stream_refusal(const ChanPush &a, ChanStreamEntry
   if (reinterpret_cast<uintptr_t>(a.d_out) & 7) return "d_out is not 8-byte aligned";
   if (a.row_stride < a.out_cap) return "row_stride < out_cap";
   if (a.out_cap < a.n_emit) return "out_cap < n_emit: size or split the chunk by lcs_chan_stream_count";
+  return nullptr;
+}
+
+// The stream of 8-bit captures (include/lcs.h, lcs_chan_stream_open_u8): what open_u8 (behind chan_refusal, as open), count_u8 and
+// push_u8 refuse, in the order they look; count_u8 stops behind the chunk's length.  Where a rule is one of chan_stream_refusal's it
+// has that rule's text.
+struct ChanPushU8 {
+  bool is_open, is_u8;       // the context has a stream; it hands out 8-bit captures
+  int fmt;
+  const void *d_chunk;
+  uint64_t n_chunk;
+  void *d_out;
+  const float *d_gain;
+  uint32_t cap_room, n_cap;  // capture slots behind d_out; open_u8: the capture's length
+  uint64_t n_done;           // the captures the push would hand out (cs_cap_done)
+};
+static inline const char *chan_stream_u8_refusal(const ChanPushU8 &a, ChanStreamEntry entry) {
+  if (entry == CHAN_STREAM_OPEN) {
+    if (a.n_cap < 1) return "n_cap < 1";
+    return a.is_open ? "a channelizer stream is already open on this context" : nullptr;
+  }
+  if (!a.is_open) return "no channelizer stream is open on this context";
+  if (!a.is_u8) return "the stream hands out floats: 8-bit captures need lcs_chan_stream_open_u8";
+  if (a.n_chunk > (1ull << 31)) return "n_chunk > 2^31";
+  if (entry == CHAN_STREAM_COUNT) return nullptr;
+  if (!a.d_chunk && a.n_chunk) return "null chunk with n_chunk > 0";
+  const uintptr_t in_align = a.fmt == LCS_FMT_C64 ? 7 : a.fmt == LCS_FMT_IQ_S16 ? 3 : 1;
+  if (reinterpret_cast<uintptr_t>(a.d_chunk) & in_align) return "d_chunk is not aligned to its sample size";
+  if (!a.d_out && a.n_done) return "null d_out with captures to hand out";
+  if (reinterpret_cast<uintptr_t>(a.d_out) & 15) return "d_out is not 16-byte aligned";
+  if (reinterpret_cast<uintptr_t>(a.d_gain) & 3) return "d_gain is not aligned to a float";
+  if (a.cap_room < a.n_done) return "cap_room < n_done: size d_out or split the chunk by lcs_chan_stream_count_u8";
   return nullptr;
 }
 
@@ -98,6 +133,11 @@ int lcs_chan_last_ms(lcs_ctx *c, float *ms);   // HIP-event time of the context'
 int lcs_chan_stream_start(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch);
 int lcs_chan_stream_enqueue(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, uint32_t row_stride);
 int lcs_chan_stream_end(lcs_ctx *c);
+// the stream of 8-bit captures: start as above plus the float capture [n_ch][n_cap] and its power partials; a push is cut where
+// captures fill (cs_cap_segment), every piece is enqueued as above into the float capture, and a full capture goes through
+// k_chan_cap_power and k_chan_quant_u8 into its slot of d_out / d_gain
+int lcs_chan_stream_start_u8(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch, uint32_t n_cap);
+int lcs_chan_stream_enqueue_u8(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, float *d_gain);
 
 // The kernels are templates over the capture's format and POW (the power partials of the 8-bit form):
 // chan_by_form(fmt, pow, [&](auto fmt, auto pow) { launch k<decltype(fmt)::value, decltype(pow)::value> }) picks the instantiation.
@@ -173,6 +213,44 @@ static inline cs_plan cs_plan_push(unsigned long long N_prev, unsigned long long
   p.cols = p.m_end > p.m_first ? (unsigned)((p.m_end - 1) / (unsigned)U - p.i_base) + 1u : 0u;
   p.grid_x = (p.cols + (unsigned)cols_per_block - 1) / (unsigned)cols_per_block;
   return p;
+}
+// ---- captures of n_cap outputs from the stream (include/lcs.h, lcs_chan_stream_push_u8): capture c is the outputs c n_cap ..
+// (c + 1) n_cap - 1 of every carrier.  The launcher cuts a push by these, and tests/host/chan_stream_u8_host.cpp walks them.
+// The inverse of cs_count: the smallest N with M(N) >= t, t >= 1: N U >= (t - 1) D + Tg.  M grows by at most one per sample
+// (U < D), so M(cs_need(t)) == t and M(cs_need(t) - 1) == t - 1.
+static inline unsigned long long cs_need(unsigned long long t, int U, int D) {
+  const unsigned __int128 fine = (unsigned __int128)(t - 1) * (unsigned)D + 16u * (unsigned)D;
+  return (unsigned long long)((fine + (unsigned)U - 1) / (unsigned)U);
+}
+// the captures complete behind N samples, and those a push of n_chunk samples completes
+static inline unsigned long long cs_cap_count(unsigned long long N, unsigned n_cap, int U, int D) { return cs_count(N, U, D) / n_cap; }
+static inline unsigned long long cs_cap_done(unsigned long long N_prev, unsigned long long n_chunk, unsigned n_cap, int U, int D) {
+  return cs_cap_count(N_prev + n_chunk, n_cap, U, D) - cs_cap_count(N_prev, n_cap, U, D);
+}
+// One piece of a push: the next n samples hand out n_emit outputs, all of the capture being filled, and `fills` says that they
+// complete it.  N_prev samples before the piece, n_left > 0 in the push from it on, `filled` outputs of the capture in hand
+// (filled == M(N_prev) mod n_cap): the piece ends with the sample that completes the capture, cs_need of the capture's end, or with
+// the push.
+struct cs_seg { unsigned long long n; unsigned n_emit; bool fills; };
+static inline cs_seg cs_cap_segment(unsigned long long N_prev, unsigned long long n_left, unsigned filled, unsigned n_cap, int U, int D) {
+  const unsigned long long m = cs_count(N_prev, U, D), t = m - filled + n_cap;      // the capture's end
+  const unsigned long long to_fill = cs_need(t, U, D) - N_prev;                      // > 0: M(N_prev) < t
+  cs_seg s;
+  s.fills = to_fill <= n_left;
+  s.n = s.fills ? to_fill : n_left;
+  s.n_emit = (unsigned)(cs_count(N_prev + s.n, U, D) - m);
+  return s;
+}
+// A push as its pieces, in order: each(piece) -> 0 to go on; returns the first other value.  The pieces add up to n_chunk; nothing for n_chunk == 0.
+template <class F>
+static inline int cs_cap_plan(unsigned long long N_prev, unsigned long long n_chunk, unsigned filled, unsigned n_cap, int U, int D, F &&each) {
+  for (unsigned long long done = 0; done < n_chunk;) {
+    const cs_seg s = cs_cap_segment(N_prev + done, n_chunk - done, filled, n_cap, U, D);
+    if (const int rc = each(s)) return rc;
+    done += s.n;
+    filled = s.fills ? 0u : filled + s.n_emit;
+  }
+  return 0;
 }
 // What a push's kernels know of the stream.  Sample n >= n_base of the stream is one of: history (samples [n_base, n_base + n_hist)
 // in the input's format), the chunk behind it, or -- behind the chunk's end -- a zero

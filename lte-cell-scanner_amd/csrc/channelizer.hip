@@ -222,6 +222,49 @@ __global__ __launch_bounds__(256) void k_chan_quant_u8(const float2 *__restrict_
   }
 }
 
+// floats y[n_ch][n_out] and their power partials part[n_ch][n_blocks] -> bytes and gains
+static int chan_quant_enqueue(lcs_ctx *c, const float2 *y, const float *part, unsigned n_blocks, int n_ch, unsigned n_out, void *d_out, float *d_gain) {
+  const unsigned n_xb = std::max(1u, (n_out / 8 + CQ_GROUPS - 1) / CQ_GROUPS);
+  hipLaunchKernelGGL(k_chan_quant_u8, dim3((unsigned)n_ch * n_xb), dim3(256), 0, c->stream, y, part, (int)n_blocks, n_out, n_xb, (uint8_t *)d_out, d_gain);
+  HIPCHK(c, hipGetLastError());
+  return LCS_OK;
+}
+
+// The power of a finished capture of the stream (include/lcs.h, lcs_chan_stream_push_u8): part[ch][block] = the sum of |y|^2 over block
+// `block` of row ch of y[n_ch][n_out], for k_chan_quant_u8 to add up.  A block is CP_PAIRS pairs of samples from the row's start on,
+// whatever launch computed them, so the sum's order depends on n_out alone: lane t takes the pairs t, t + 256, t + 512, t + 768 of its
+// block -- four 16-byte loads in flight (a row starts at any 8-byte address) -- squares and adds them in that order in fp32, the wave
+// adds its lanes by a butterfly of lane exchanges, the four waves meet in LDS in wave order.  The odd last sample of a row counts as
+// the pair behind the last whole one.  No atomics; 8 bytes in per sample.  y holds one more sample than its rows (see the loads).
+#define CP_ILP 4
+#define CP_PAIRS (256 * CP_ILP)
+static unsigned cap_power_blocks(unsigned n_out) { return ((n_out + 1) / 2 + CP_PAIRS - 1) / CP_PAIRS; }
+
+__global__ __launch_bounds__(256) void k_chan_cap_power(const float2 *__restrict__ y, unsigned n_out, float *__restrict__ part) {
+  __shared__ float red[4];
+  const float2 *row = y + (size_t)blockIdx.y * n_out;
+  const cq_f32x4 *row4 = reinterpret_cast<const cq_f32x4 *>(row);
+  const unsigned n2 = n_out >> 1, i0 = blockIdx.x * CP_PAIRS + threadIdx.x, last = n2 ? n2 - 1 : 0;
+  cq_f32x4 v[CP_ILP];
+#pragma unroll
+  for (int k = 0; k < CP_ILP; ++k) v[k] = row4[std::min(i0 + 256u * k, last)];      // unconditional (a branch per load would serialise them): the
+  // tail reads the last pair again, and a row of ONE sample reads 8 bytes behind itself -- y has one sample of padding behind its last row
+  const float2 f = row[n_out - 1];
+  const float tail = (n_out & 1u) ? f.x * f.x + f.y * f.y : 0.f;      // the odd last sample: pair n2
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < CP_ILP; ++k) {
+    const unsigned i = i0 + 256u * k;
+    const float pair = (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
+    s += i < n2 ? pair : (i == n2 ? tail : 0.f);      // selected, not multiplied: what a lane beyond the row's end loaded may be anything
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // One call's parameters on their way to the device: [n_ch] phase steps, then T taps as float.  Two page-locked slots used in
 // turn, each guarded by the event behind its copy, so a call never waits for the GPU unless three calls are in flight.
 int lcs_chan_slot(lcs_ctx *c, size_t bytes, int *slot) {
@@ -297,10 +340,7 @@ int lcs_launch_channelize_u8(lcs_ctx *c, const ChanCall &a, float *d_gain) {
   ChanCall y = a;
   y.d_out = c->chan_y;
   if ((rc = lcs_launch_channelize(c, y, c->chan_part))) return rc;
-  const unsigned n_xb = std::max(1u, (n_out / 8 + CQ_GROUPS - 1) / CQ_GROUPS);
-  hipLaunchKernelGGL(k_chan_quant_u8, dim3((unsigned)a.n_ch * n_xb), dim3(256), 0, c->stream, (const float2 *)c->chan_y, (const float *)c->chan_part,
-                     (int)n_blocks, n_out, n_xb, (uint8_t *)a.d_out, d_gain);
-  HIPCHK(c, hipGetLastError());
+  if ((rc = chan_quant_enqueue(c, c->chan_y, c->chan_part, n_blocks, a.n_ch, n_out, a.d_out, d_gain))) return rc;
   HIPCHK(c, hipEventRecord(c->ev_chan1, c->stream));      // the call's time runs through its last kernel
   return LCS_OK;
 }
@@ -315,8 +355,8 @@ void lcs_chan_rate_stream_enqueue(lcs_ctx *c, int fmt, const void *d_chunk, uint
 
 static void chan_stream_drop(lcs_ctx *c) {
   lcs_ctx::ChanStream &st = c->chan_stream;
-  st.par.reset(), st.tab.reset(), st.hist[0].reset(), st.hist[1].reset();
-  st.open = false;
+  st.par.reset(), st.tab.reset(), st.hist[0].reset(), st.hist[1].reset(), st.cap.reset(), st.cap_part.reset();
+  st.open = st.u8 = false;
 }
 
 int lcs_chan_stream_start(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch) {
@@ -354,7 +394,21 @@ int lcs_chan_stream_start(lcs_ctx *c, int fmt, double fs_in, int up, int down, c
   }
   st.fmt = fmt, st.up = up, st.down = down, st.n_ch = n_ch;
   st.cur = 0, st.n_hist = 0, st.n_total = 0;
+  st.u8 = false, st.n_cap = 0, st.filled = 0;
   st.open = true;
+  return LCS_OK;
+}
+
+// The stream of 8-bit captures: the float stream plus the capture in hand.  A failed allocation drops the whole stream.
+int lcs_chan_stream_start_u8(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch, uint32_t n_cap) {
+  lcs_ctx::ChanStream &st = c->chan_stream;
+  int rc;
+  if ((rc = lcs_chan_stream_start(c, fmt, fs_in, up, down, f_shift, n_ch))) return rc;
+  if ((rc = st.cap.alloc(c, (size_t)n_ch * n_cap + 1)) || (rc = st.cap_part.alloc(c, (size_t)n_ch * cap_power_blocks(n_cap)))) {
+    chan_stream_drop(c);
+    return rc;
+  }
+  st.u8 = true, st.n_cap = n_cap;
   return LCS_OK;
 }
 
@@ -388,6 +442,29 @@ int lcs_chan_stream_enqueue(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, v
   st.n_hist = p.n_keep;
   st.n_total += n_chunk;
   return LCS_OK;
+}
+
+// One push of the stream of 8-bit captures, already found acceptable.  A push cut in two is bit for bit the push uncut, so it is cut
+// where captures fill: every piece goes into the float capture at column `filled`, and a capture that fills leaves for its slot of
+// d_out / d_gain before the next piece overwrites it -- everything in order on the context's stream, so one float capture is enough.
+int lcs_chan_stream_enqueue_u8(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, float *d_gain) {
+  lcs_ctx::ChanStream &st = c->chan_stream;
+  const size_t sample = chan_sample_bytes(st.fmt), cap_bytes = 2 * (size_t)st.n_ch * st.n_cap;
+  const unsigned n_pb = cap_power_blocks(st.n_cap);
+  const char *chunk = static_cast<const char *>(d_chunk);
+  unsigned slot = 0;
+  return cs_cap_plan(st.n_total, n_chunk, st.filled, st.n_cap, st.up, st.down, [&](const cs_seg &s) -> int {
+    if (int rc = lcs_chan_stream_enqueue(c, chunk, s.n, st.cap.get() + st.filled, st.n_cap)) return rc;
+    chunk += s.n * sample;
+    st.filled += s.n_emit;
+    if (!s.fills) return LCS_OK;
+    st.filled = 0;
+    hipLaunchKernelGGL(k_chan_cap_power, dim3(n_pb, (unsigned)st.n_ch), dim3(256), 0, c->stream, (const float2 *)st.cap, st.n_cap, st.cap_part.get());
+    HIPCHK(c, hipGetLastError());
+    const unsigned k = slot++;
+    return chan_quant_enqueue(c, st.cap, st.cap_part, n_pb, st.n_ch, st.n_cap, static_cast<char *>(d_out) + k * cap_bytes,
+                              d_gain ? d_gain + (size_t)k * st.n_ch : nullptr);
+  });
 }
 
 // the queued pushes may still read the stream's buffers

@@ -1277,13 +1277,57 @@ int lcs_chan_stream_push(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void
   if (!c) return LCS_ERR_BAD_ARG;
   const bool open = c->chan_stream.open;
   uint64_t m0 = 0;
-  ChanPush a = {open, c->chan_stream.fmt, d_chunk, n_chunk, d_out, row_stride, out_cap, 0};
+  ChanPush a = {open, c->chan_stream.fmt, d_chunk, n_chunk, d_out, row_stride, out_cap, 0, c->chan_stream.u8};
   if (open && n_chunk <= (1ull << 31)) a.n_emit = chan_stream_emit(c, n_chunk, &m0);
   if (const char *what = chan_stream_refusal(a, CHAN_STREAM_PUSH)) return chan_refused(c, "lcs_chan_stream_push", what);
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = lcs_chan_stream_enqueue(c, d_chunk, n_chunk, d_out, row_stride)) return rc;
   if (n_emit) *n_emit = (uint32_t)a.n_emit;
   if (m_first) *m_first = m0;
+  return LCS_OK;
+}
+
+// The stream of 8-bit captures: open_u8 refuses what open refuses and then by chan_stream_u8_refusal, as count_u8 and push_u8 do.
+int lcs_chan_stream_open_u8(lcs_ctx *c, int fmt, double fs_in, int up, int down, const double *f_shift, int n_ch, uint32_t n_cap) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  alignas(16) static char any[16];
+  const ChanCall a = {any, fmt, ~0ull, fs_in, up, down, f_shift, n_ch, any, 1};
+  const char *what = chan_refusal(a, CHAN_RATE);
+  ChanPushU8 u = {c->chan_stream.open};
+  u.n_cap = n_cap;
+  if (!what) what = chan_stream_u8_refusal(u, CHAN_STREAM_OPEN);
+  if (what) return chan_refused(c, "lcs_chan_stream_open_u8", what);
+  HIPCHK(c, hipSetDevice(c->device));
+  return lcs_chan_stream_start_u8(c, fmt, fs_in, up, down, f_shift, n_ch, n_cap);
+}
+
+// a push as chan_stream_u8_refusal sees it; n_done only where the rules in front of it let it be computed
+static ChanPushU8 chan_stream_u8_call(const lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, const float *d_gain, uint32_t cap_room) {
+  const lcs_ctx::ChanStream &st = c->chan_stream;
+  ChanPushU8 a = {st.open, st.u8, st.fmt, d_chunk, n_chunk, d_out, d_gain, cap_room, st.n_cap, 0};
+  if (st.open && st.u8 && n_chunk <= (1ull << 31)) a.n_done = cs_cap_done(st.n_total, n_chunk, st.n_cap, st.up, st.down);
+  return a;
+}
+
+int lcs_chan_stream_count_u8(lcs_ctx *c, uint64_t n_chunk, uint32_t *n_done) {
+  if (!c || !n_done) return LCS_ERR_BAD_ARG;
+  const ChanPushU8 a = chan_stream_u8_call(c, nullptr, n_chunk, nullptr, nullptr, 0);
+  if (const char *what = chan_stream_u8_refusal(a, CHAN_STREAM_COUNT)) return chan_refused(c, "lcs_chan_stream_count_u8", what);
+  *n_done = (uint32_t)a.n_done;      // <= outputs < n_chunk <= 2^31
+  return LCS_OK;
+}
+
+int lcs_chan_stream_push_u8(lcs_ctx *c, const void *d_chunk, uint64_t n_chunk, void *d_out, float *d_gain, uint32_t cap_room, uint32_t *n_done,
+                            uint64_t *cap_first) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  const ChanPushU8 a = chan_stream_u8_call(c, d_chunk, n_chunk, d_out, d_gain, cap_room);
+  if (const char *what = chan_stream_u8_refusal(a, CHAN_STREAM_PUSH)) return chan_refused(c, "lcs_chan_stream_push_u8", what);
+  const lcs_ctx::ChanStream &st = c->chan_stream;
+  const uint64_t first = cs_cap_count(st.n_total, st.n_cap, st.up, st.down);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = lcs_chan_stream_enqueue_u8(c, d_chunk, n_chunk, d_out, d_gain)) return rc;
+  if (n_done) *n_done = (uint32_t)a.n_done;
+  if (cap_first) *cap_first = first;
   return LCS_OK;
 }
 

@@ -394,6 +394,11 @@ struct lcs_ctx : lcs_ctx_queues {
     int cur = 0;                    // the slot that holds samples [n_total - n_hist, n_total)
     unsigned n_hist = 0;
     unsigned long long n_total = 0; // samples pushed since open
+    // the stream of 8-bit captures (lcs_chan_stream_open_u8): the capture in hand as floats until it is full and its gain is known
+    bool u8 = false;
+    uint32_t n_cap = 0, filled = 0; // outputs per capture, and how many of the capture in hand have been computed
+    DevBuf<float2> cap;             // [n_ch][n_cap], and one sample of padding (k_chan_cap_power)
+    DevBuf<float> cap_part;         // [n_ch][cap_power_blocks(n_cap)] sums of |y|^2 (k_chan_cap_power)
   } chan_stream;
   // results of a batch, compacted on the device (k_pack_results): [8 ints header][n_buf counts][records]; h_res = its page-locked mirror
   DevBuf<char> res_pack;

@@ -74,6 +74,23 @@ def dedup(detected: Sequence[Sequence[dict]]) -> List[dict]:
     return final
 
 
+def records_with_gain(cells_per_carrier, gain) -> List[List[dict]]:
+    """The per-carrier cell lists of a band search on 8-bit carriers (search_wideband(out="u8"), WidebandFeed(out="u8")) as
+    record_to_dict dicts on ONE power scale: carrier k's bytes are its floats times gain[k] (Searcher.channelize_u8's gains, or
+    WidebandFeed.gains), and a correlation power scales with the square of the buffer's amplitude, so pss_pow is divided by
+    gain[k]**2 -- exactly, the gain being a power of two.  dedup() on the result compares carriers as it does for float buffers."""
+    gain = np.asarray(gain.detach().cpu().numpy() if hasattr(gain, "detach") else gain, np.float64).reshape(-1)
+    if len(cells_per_carrier) != gain.size:
+        raise ValueError(f"records_with_gain: {len(cells_per_carrier)} carriers, {gain.size} gains")
+    out = []
+    for cells, g in zip(cells_per_carrier, gain):
+        recs = [record_to_dict(r) for r in cells_to_records(cells)]
+        for d in recs:
+            d["pss_pow"] /= g * g
+        out.append(recs)
+    return out
+
+
 def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, fc_centre: float, carriers, f_search_set,
                     n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64"):
     """A band search from ONE wideband capture resident in HBM (n_in samples of fmt at fs_in, centred on fc_centre): the
@@ -124,12 +141,19 @@ class WidebandFeed:
     they go through the full chain as one FMT_C64 capture per carrier -- fc_requested = fc_programmed = the carrier, fs_programmed =
     fs_in * up / down, batches of at most 128 carriers, as search_wideband does.  Two [n_ch][n_cap] complex64 buffers are filled in
     turn; a transfer buffer that straddles a capture's end is split there (chan_stream_count, bisected on the chunk length: counts
-    grow by at most one per sample, so the split is exact).  The searcher's one channelizer stream is this object's until close()."""
+    grow by at most one per sample, so the split is exact).  The searcher's one channelizer stream is this object's until close().
+    out = "u8": the stream hands out 8-bit captures (Searcher.chan_stream_open_u8), searched as FMT_IQ_U8 batches on the int8
+    correlation kernel.  bufs are then two [n_ch][n_cap][2] uint8 buffers, written in turn one whole capture at a time (cur: the one
+    the next capture goes to; filled stays 0, the capture in hand lives in the library), and `gains` is the float32 [n_ch] device
+    tensor of the last finished capture's gains (None before the first), read without synchronising: records_with_gain(cells, feed.gains)
+    puts the cells of its carriers on one power scale."""
 
     def __init__(self, searcher, fmt: int, fs_in: float, rate, fc_centre: float, carriers, f_search_set, n_cap: int = 153600,
-                 max_cells_per_buf: int = 16):
+                 max_cells_per_buf: int = 16, out: str = "c64"):
         import torch
         from . import capi
+        if out not in ("c64", "u8"):
+            raise ValueError(f"WidebandFeed: out must be 'c64' or 'u8', not {out!r}")
         self.searcher, self.fmt, self.n_cap, self.max_cells_per_buf = searcher, int(fmt), int(n_cap), int(max_cells_per_buf)
         self.carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
         self.f_search_set = f_search_set
@@ -138,14 +162,20 @@ class WidebandFeed:
         self._sample_bytes = {capi.FMT_C64: 8, capi.FMT_IQ_S16: 4, capi.FMT_IQ_S8: 2}.get(self.fmt, 1)
         dev = getattr(searcher, "device", -1)
         tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
-        self.bufs = [torch.empty((self.carriers.size, self.n_cap), dtype=torch.complex64, device=tdev) for _ in range(2)]
-        self.cur, self.filled = 0, 0
-        searcher.chan_stream_open(self.fmt, fs_in, up, down, self.carriers - float(fc_centre))
+        self.cur, self.filled, self._u8 = 0, 0, out == "u8"
+        if self._u8:
+            self.bufs = [torch.empty((self.carriers.size, self.n_cap, 2), dtype=torch.uint8, device=tdev) for _ in range(2)]
+            self._gains = [torch.empty(self.carriers.size, dtype=torch.float32, device=tdev) for _ in range(2)]
+            self.gains = None
+            searcher.chan_stream_open_u8(self.fmt, fs_in, up, down, self.carriers - float(fc_centre), self.n_cap)
+        else:
+            self.bufs = [torch.empty((self.carriers.size, self.n_cap), dtype=torch.complex64, device=tdev) for _ in range(2)]
+            searcher.chan_stream_open(self.fmt, fs_in, up, down, self.carriers - float(fc_centre))
         self._open = True
 
     def _longest(self, n: int, room: int) -> int:
-        """the longest chunk of at most n samples that hands out at most `room` outputs"""
-        count = self.searcher.chan_stream_count
+        """the longest chunk of at most n samples that hands out at most `room` outputs (out = "u8": completes at most `room` captures)"""
+        count = self.searcher.chan_stream_count_u8 if self._u8 else self.searcher.chan_stream_count
         if count(n) <= room:
             return n
         lo, hi = 0, n                  # count(lo) <= room < count(hi)
@@ -159,14 +189,30 @@ class WidebandFeed:
         cells = []
         for a in range(0, self.carriers.size, 128):
             fc = self.carriers[a:a + 128]
-            cells += self.searcher.search_batch(buf[a].data_ptr(), capi.FMT_C64, fc.size, self.n_cap, self.f_search_set, fc, fc, self.fs_out,
-                                                capi.STAGE_FULL, self.max_cells_per_buf)
+            cells += self.searcher.search_batch(buf[a].data_ptr(), capi.FMT_IQ_U8 if self._u8 else capi.FMT_C64, fc.size, self.n_cap, self.f_search_set,
+                                                fc, fc, self.fs_out, capi.STAGE_FULL, self.max_cells_per_buf)
         return cells
+
+    def _push_u8(self, d_ptr: int, n_samples: int):
+        """every library push completes at most one capture, into the buffer and the gain tensor whose turn it is"""
+        done, off = [], 0
+        while off < n_samples:
+            n = self._longest(n_samples - off, 1)      # >= 1: one sample hands out at most one output
+            buf, gain = self.bufs[self.cur], self._gains[self.cur]
+            n_done, _ = self.searcher.chan_stream_push_u8(d_ptr + off * self._sample_bytes, n, buf.data_ptr(), gain.data_ptr(), 1)
+            off += n
+            if n_done:
+                self.gains = gain
+                done.append(self._search(buf))
+                self.cur ^= 1
+        return done
 
     def push(self, d_ptr: int, n_samples: int):
         """Feed n_samples at d_ptr (device; they must stay unchanged until the searcher's stream has run the work queued here).
         Returns the per-carrier cell lists of every capture this push completed: usually []."""
         done, off, n_samples = [], 0, int(n_samples)
+        if self._u8:
+            return self._push_u8(d_ptr, n_samples)
         while off < n_samples:
             room = self.n_cap - self.filled
             n = self._longest(n_samples - off, room)

@@ -26,11 +26,20 @@ opened before the clock starts; (c) as 64 pushes; (z) one push that hands out no
 append alone).  The condition is relative: b <= 1.10 a + 7 z -- seven more launches than one call, and 10 % (twice the +-4 % box
 spread of README, and the recomputed columns).  (c) has no bar.  The record goes under "stream" / "<up>/<down>"; the rest stays.
 
+--stream --u8 compares the two pipelines of a LIVE band search, one capture of n_cap = 153600 outputs per carrier arriving as 8 equal
+pushes (the integer record's carriers at 30.72 Msps; with --rate 12/125 the rational record's 181), both in this one process, streams
+opened before the clock starts, HIP events on the context's stream, medians as above: (a) the float stream's pushes
+(lcs_chan_stream_push), then search_batch on the floats; (b) lcs_chan_stream_push_u8, then search_batch on the bytes (the int8
+correlation kernel); (p) the pushes of (b) alone and (s) the search of (b) alone, from an event between the two.  The conditions are
+relative: p <= 0.25 s (the channelizer stage's standing condition) and b <= 0.90 a.  The record goes under "stream_u8" / "<up>/<down>".
+
     python tools/chan_bench.py --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --rate 12/125 --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --u8 --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --stream --out profiles/channelizer/chan_bench.json
     python tools/chan_bench.py --stream --rate 12/125 --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --stream --u8 --out profiles/channelizer/chan_bench.json
+    python tools/chan_bench.py --stream --u8 --rate 12/125 --out profiles/channelizer/chan_bench.json
 """
 import argparse
 import importlib.util
@@ -44,6 +53,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+STREAM_N_CAP = 153600      # --stream --u8: outputs per capture
 
 
 def sclk_sampler(device, samples, stop):
@@ -70,9 +82,7 @@ def main():
     ap.add_argument("--u8", action="store_true", help="time lcs_channelize_u8 + search on bytes against lcs_channelize + search on floats")
     ap.add_argument("--stream", action="store_true", help="time the continuous form (8 and 64 pushes) against the one-shot call on the same samples")
     args = ap.parse_args()
-    if args.u8 and args.stream:
-        ap.error("--u8 and --stream are two measurements")
-    if args.u8 and args.rate:
+    if args.u8 and args.rate and not args.stream:
         ap.error("--u8 runs on the integer record's carriers: it takes no --rate")
     rate = tuple(int(v) for v in args.rate.split("/")) if args.rate else None
     import torch
@@ -84,6 +94,9 @@ def main():
         up, down = rate
         fs_in, n_in = 1.92e6 * down / up, -(-153600 // up) * down
         N_CH = 2 * int(0.45 * fs_in / 100e3) + 1
+    if args.u8 and args.stream:      # one capture of STREAM_N_CAP outputs and not a sample more
+        u, d = rate or (1, D)
+        n_in = -(-((STREAM_N_CAP - 1) * d + 16 * d) // u)
     carriers = FC0 + 100e3 * (np.arange(N_CH) - N_CH // 2)
     args.cells = min(args.cells, (N_CH - 17) // 32 + 1)
     rng = np.random.default_rng(5)
@@ -93,7 +106,7 @@ def main():
     if rate:
         iq, _ = pkg.synth.make_wideband_rate(77, FC0, up, down, placed, 10.0, pkg.FMT_IQ_S16, n_in=n_in)
     else:
-        iq, _ = pkg.synth.make_wideband(77, FC0, D, placed, 10.0, pkg.FMT_IQ_S16)
+        iq, _ = pkg.synth.make_wideband(77, FC0, D, placed, 10.0, pkg.FMT_IQ_S16, n_in=n_in)
     dev = torch.device("cuda", args.device)
     d_wide = torch.from_numpy(iq).to(dev)
     d_out = torch.empty((N_CH, N_OUT), dtype=torch.complex64, device=dev)
@@ -101,6 +114,8 @@ def main():
     torch.cuda.synchronize(dev)
     samples, stop = [], threading.Event()
     th = threading.Thread(target=sclk_sampler, args=(args.device, samples, stop), daemon=True)
+    if args.u8 and args.stream:
+        return bench_stream_u8(args, pkg, torch, dev, d_wide, carriers - FC0, carriers, f, n_in, fs_in, rate or (1, D), samples, stop, th)
     if args.u8:
         return bench_u8(args, pkg, torch, dev, d_wide, d_out, carriers - FC0, carriers, f, n_in, fs_in, D, N_CH, N_OUT, samples, stop, th)
     if args.stream:
@@ -225,6 +240,93 @@ def bench_stream(args, pkg, torch, dev, d_wide, shifts, n_in, fs_in, rate, sampl
         old = {}
     with open(args.out, "w") as fh:
         json.dump(dict(old, stream=dict(old.get("stream", {}), **{"%d/%d" % (up, down): res})), fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res))
+
+
+def bench_stream_u8(args, pkg, torch, dev, d_wide, shifts, carriers, f, n_in, fs_in, rate, samples, stop, th):
+    up, down = rate
+    n_ch, n_cap, n_push = len(shifts), STREAM_N_CAP, 8
+    assert (n_in * up - 16 * down) // down + 1 == n_cap
+    d_c64 = torch.empty((n_ch, n_cap), dtype=torch.complex64, device=dev)
+    d_u8 = torch.empty((n_ch, n_cap, 2), dtype=torch.uint8, device=dev)
+    d_gain = torch.empty(n_ch, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    edges = [n_in * k // n_push for k in range(n_push + 1)]
+    t = {"a": [], "b": [], "p": [], "s": []}
+    cells, kernel = {}, {}
+    with pkg.Searcher(args.device) as s:
+        stream = torch.cuda.ExternalStream(pkg.capi.load().lcs_stream(s._h), device=dev)
+
+        def search(buf, fmt):
+            n = 0
+            for h in range(-(-n_ch // 128)):
+                sl = slice(128 * h, min(128 * h + 128, n_ch))
+                n += sum(len(c) for c in s.search_batch(buf[128 * h].data_ptr(), fmt, sl.stop - sl.start, n_cap, f, carriers[sl], carriers[sl], 1.92e6, pkg.STAGE_FULL))
+            return n
+
+        def events(k):
+            return [torch.cuda.Event(enable_timing=True) for _ in range(k)]
+
+        th.start()
+        for i in range(args.warmup + args.reps):      # interleaved: both pipelines see the same clocks
+            s.chan_stream_open(pkg.FMT_IQ_S16, fs_in, up, down, shifts)
+            e = events(2)
+            e[0].record(stream)
+            filled = 0
+            for a, b in zip(edges[:-1], edges[1:]):
+                n_emit, _ = s.chan_stream_push(d_wide.data_ptr() + 4 * a, b - a, d_c64.data_ptr() + 8 * filled, n_cap, n_cap - filled)
+                filled += n_emit
+            cells["c64"] = search(d_c64, pkg.FMT_C64)
+            e[1].record(stream)
+            e[1].synchronize()
+            t["a"].append(e[0].elapsed_time(e[1]))
+            kernel["c64"] = s.last_xcorr_info()[0]
+            s.chan_stream_close()
+            assert filled == n_cap
+            s.chan_stream_open_u8(pkg.FMT_IQ_S16, fs_in, up, down, shifts, n_cap)
+            e = events(3)
+            e[0].record(stream)
+            done = 0
+            for a, b in zip(edges[:-1], edges[1:]):
+                done += s.chan_stream_push_u8(d_wide.data_ptr() + 4 * a, b - a, d_u8.data_ptr(), d_gain.data_ptr(), 1)[0]
+            e[1].record(stream)
+            cells["u8"] = search(d_u8, pkg.FMT_IQ_U8)
+            e[2].record(stream)
+            e[2].synchronize()
+            t["b"].append(e[0].elapsed_time(e[2]))
+            t["p"].append(e[0].elapsed_time(e[1]))
+            t["s"].append(e[1].elapsed_time(e[2]))
+            kernel["u8"] = s.last_xcorr_info()[0]
+            s.chan_stream_close()
+            assert done == 1
+        stop.set()
+        th.join(timeout=10)
+    med = lambda v: float(np.median(v[args.warmup:]))
+    a, b, p, sr = med(t["a"]), med(t["b"]), med(t["p"]), med(t["s"])
+    spec = importlib.util.spec_from_file_location("code_objects", os.path.join(ROOT, "tools", "code_objects.py"))
+    co = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(co)
+    ks = {k: v for k, v in co.kernels_of(os.path.join(ROOT, "lte-cell-scanner_amd", "liblcs_amd.so")).items()
+          if "k_chan_cap_power" in k or "k_chan_quant_u8" in k or "k_chan_keep" in k}
+    res = {"a_float_stream_and_search_ms": a, "b_u8_stream_and_search_ms": b, "p_u8_pushes_ms": p, "s_u8_search_ms": sr,
+           "ratio_p_over_s": p / sr, "target_p_over_s": 0.25, "meets_p_target": bool(p <= 0.25 * sr),
+           "ratio_b_over_a": b / a, "target_b_over_a": 0.90, "meets_b_target": bool(b <= 0.90 * a),
+           "config": {"up": up, "down": down, "fs_in": fs_in, "fmt": "s16", "n_ch": n_ch, "n_in": n_in, "n_cap": n_cap, "pushes": n_push, "n_f": int(f.size),
+                      "batches": " + ".join(str(min(128, n_ch - 128 * h)) for h in range(-(-n_ch // 128))), "stage": "full", "reps": args.reps,
+                      "warmup": args.warmup, "cells_planted": args.cells, "cells_decoded_u8": cells["u8"], "cells_decoded_c64": cells["c64"],
+                      "xcorr_kernel_u8": kernel["u8"], "xcorr_kernel_c64": kernel["c64"]},
+           "ms_min_max": {k: [float(min(v[args.warmup:])), float(max(v[args.warmup:]))] for k, v in t.items()},
+           "sclk_mhz_median": (sorted(samples)[len(samples) // 2] if samples else None), "sclk_samples": len(samples),
+           "device": torch.cuda.get_device_name(dev), "kernels": ks}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    try:
+        with open(args.out) as fh:
+            old = json.load(fh)
+    except (OSError, ValueError):
+        old = {}
+    with open(args.out, "w") as fh:
+        json.dump(dict(old, stream_u8=dict(old.get("stream_u8", {}), **{"%d/%d" % (up, down): res})), fh, indent=1)
         fh.write("\n")
     print(json.dumps(res))
 
