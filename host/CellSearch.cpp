@@ -61,6 +61,7 @@ struct Options {
   bool gpu_all = false;          // -g all: shard the carriers over every visible GPU
   std::vector<long> gpu_list;    // -g a,b,...: one device thread per entry (an index may repeat: "0,0" = two threads on GPU 0)
   long batch = 64;               // carriers per GPU batch (one correlation launch)
+  int duplex = LCS_DUPLEX_FDD;   // -x: the band's duplex mode, set on every context
   int verbosity = 1;
 };
 
@@ -79,6 +80,7 @@ const OptSpec kSpecs[] = {
     {'i', "device-index", INDEX, "device index", {"(accepted for compatibility; there is no RTLSDR dongle on a GPU node)", 0}},
     {'g', "gpu", INDEX, "gpu index", {"GPU to run the searcher on (default: current device); 'all' shards the carriers over every GPU, 'a,b,..' over the listed ones", 0}},
     {'B', "batch", INDEX, "batch size", {"carriers searched per GPU batch (default 64)", 0}},
+    {'x', "duplex", TEXT, 0, {"duplex mode of the band, fdd (default) or tdd (bands 33-53: SSS three symbols before the PSS; the frequency grid is then 2.5 kHz)", 0}},
     {'s', "freq-start", REAL, "start frequency", {"frequency where cell search should start", 0}},
     {'e', "freq-end", REAL, "end frequency", {"frequency where cell search should end", 0}},
     {'p', "ppm", REAL, "ppm value", {"crystal remaining PPM error", 0}},
@@ -87,13 +89,13 @@ const OptSpec kSpecs[] = {
     {'l', "load", FLAG, 0, {"used data in capbuf_XXXX.it files instead of live data", 0}},
     {'d', "data-dir", TEXT, 0, {"directory where capbuf_XXXX.it files are located", 0}},
 };
-const char *arg_name(const OptSpec &s) { return s.kind == FLAG ? "" : (s.letter == 's' ? " fs" : s.letter == 'e' ? " fe" : s.letter == 'p' ? " ppm" : s.letter == 'c' ? " c" : s.letter == 'd' ? " dir" : " N"); }
+const char *arg_name(const OptSpec &s) { return s.kind == FLAG ? "" : (s.letter == 's' ? " fs" : s.letter == 'e' ? " fe" : s.letter == 'p' ? " ppm" : s.letter == 'c' ? " c" : s.letter == 'd' ? " dir" : s.letter == 'x' ? " fdd|tdd" : " N"); }
 
 void usage() {
   std::cout << "LTE CellSearch v" << VERSION_STRING << " (MI355X) help screen\n\n"
             << "CellSearch -s start_frequency [optional_parameters]\n";
   const struct { const char *title; const char *letters; } sections[] = {
-      {"Basic options", "hvbigB"}, {"Frequency search options:", "se"}, {"Dongle LO correction options:", "pc"},
+      {"Basic options", "hvbigB"}, {"Frequency search options:", "sex"}, {"Dongle LO correction options:", "pc"},
       {"Capture buffer save/ load options:", "rld"}};
   for (const auto &sec : sections) {
     std::cout << "  " << sec.title << "\n";
@@ -122,7 +124,15 @@ void store(Options &o, const OptSpec &s, const char *value) {
       else if (s.letter == 'r') o.record = true;
       else o.load = true;
       return;
-    case TEXT: o.data_dir = value; return;
+    case TEXT:
+      if (s.letter == 'x') {
+        if (std::strcmp(value, "fdd") == 0) o.duplex = LCS_DUPLEX_FDD;
+        else if (std::strcmp(value, "tdd") == 0) o.duplex = LCS_DUPLEX_TDD;
+        else die("duplex mode must be fdd or tdd");
+        return;
+      }
+      o.data_dir = value;
+      return;
     case REAL: {
       const double v = std::strtod(value, &end);
       if (end == value || *end) die(std::string("could not parse ") + s.what);
@@ -328,7 +338,7 @@ struct InFlight {
 void device_thread(Sweep *sw, int device, int first_batch, int stride) {
   try {
     std::unique_ptr<lcs::Searcher> ctx[2];
-    for (int k = 0; k < 2; ++k) ctx[k].reset(new lcs::Searcher(device));
+    for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); ctx[k]->set_duplex(sw->opt.duplex); }
     std::unique_ptr<lcs::Searcher> one;                     // for captures that are not raw dongle bytes
     unsigned char *pinned[2] = {0, 0};
     size_t pinned_bytes[2] = {0, 0};
@@ -343,7 +353,7 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
         for (size_t j = 0; j < f.carriers.size(); ++j) sw->detected[f.carriers[j]].swap(found[j]);
       }
       for (size_t j = 0; j < f.singles.size(); ++j) {
-        if (!one) one.reset(new lcs::Searcher(device));
+        if (!one) { one.reset(new lcs::Searcher(device)); one->set_duplex(sw->opt.duplex); }
         const double fc = sw->opt.freq_start + 100e3 * f.single_carriers[j];
         lcsc::cvec capbuf((int)f.singles[j].samples.size());
         std::memcpy(capbuf._data(), f.singles[j].samples.data(), f.singles[j].samples.size() * sizeof(std::complex<double>));
@@ -431,9 +441,12 @@ int main(int argc, char *const argv[]) {
   sw.fs_programmed = 1.92e6 * opt.correction;   // recorded-data convention, src/LTE-Tracker.cpp:791
 
   // frequency-offset hypotheses and carrier raster (src/CellSearch.cpp:463-465; n_extra uses freq_start only)
-  const int n_extra = (int)std::floor((opt.freq_start * opt.ppm / 1e6 + 2.5e3) / 5e3);
+  // A TDD search takes half the step: the PSS/SSS frequency estimate is unambiguous within +- 2330 Hz (normal CP) / +- 2000 Hz
+  // (extended) of the hypothesis there, and the residual on a 5 kHz grid reaches +- 2500 Hz (include/lcs.h: lcs_set_duplex)
+  const double f_step = opt.duplex == LCS_DUPLEX_TDD ? 2.5e3 : 5e3;
+  const int n_extra = (int)std::floor((opt.freq_start * opt.ppm / 1e6 + f_step / 2) / f_step);
   sw.f_search_set.set_size(2 * n_extra + 1);
-  for (int i = 0; i <= 2 * n_extra; ++i) sw.f_search_set(i) = 5000.0 * (i - n_extra);
+  for (int i = 0; i <= 2 * n_extra; ++i) sw.f_search_set(i) = f_step * (i - n_extra);
   sw.n_fc = (int)std::floor((opt.freq_end - opt.freq_start) / 100e3) + 1;
   sw.kBatch = (int)opt.batch;
   sw.n_batches = (sw.n_fc + sw.kBatch - 1) / sw.kBatch;

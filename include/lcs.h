@@ -115,6 +115,40 @@ int lcs_set_max_cells_in_flight(lcs_ctx *ctx, int n);
  * the caller's buffer is not read again after the call returns; anything else takes the fp16 kernel as before (and the next fifteen
  * batches of the context are not checked).  Off by default.  Results do not depend on it. */
 int lcs_set_float_batch_probe(lcs_ctx *ctx, int on);
+/* Duplex mode of the band a context searches: where the SSS lies relative to the PSS.  LCS_DUPLEX_FDD (the default, and the
+ * reference's only mode: frame structure type 1, PSS in the last symbol of slots 0 / 10, SSS directly before it) or
+ * LCS_DUPLEX_TDD (36.211 frame structure type 2, bands 33-53: PSS in symbol 2 of slots 2 / 12, SSS in the last symbol of slots
+ * 1 / 11, three symbols earlier).  Under FDD every record and every array is what it was before the mode existed, bit for bit.  The mode
+ * is context-wide -- one wideband capture covers one band, and a band has one duplex -- and reaches every entry point that runs
+ * sss_detect or pss_sss_foe: lcs_sss_detect, lcs_pss_sss_foe, lcs_search_capbuf, the batch entry points (device and host, enqueue
+ * and collect: a batch keeps the mode it was enqueued with), the streaming mode and lcs_foe_finish.  Everything behind those two
+ * stages (lcs_extract_tfg, lcs_tfoec, lcs_decode_mib) takes the frame timing from the cell record and needs no mode.  In samples at
+ * 1.92 Msps, sc = 16 / FS_LTE * fs_programmed * k_factor:
+ *                                                FDD                              TDD
+ *   SSS DFT window, normal / extended CP         pss_dft - 137 / - 160            pss_dft - 412 / - 480
+ *   peak moved right by 9600 k_factor when       peak_loc + 9 < 162               peak_loc + 9 < 482
+ *   PSS DFT start inside the frame (P)           832                              2204 normal CP, 2272 extended CP
+ *   frame_start before half-frame step and wrap  cell.ind + (9 - 2 - P) sc        peak_loc + (9 - 2 - P) sc
+ *   pss_sss_dist, normal / extended CP           round(137 sc) / round(160 k)     round(412 sc) / round(480 k)
+ *   first SSS DFT start minus frame_start        695 sc / 672 sc                  1792 sc
+ * (TDD's frame_start reads the peak position BEHIND the room rule, as the reference's Matlab original does; FDD keeps the C++
+ * reference's cell.ind, which is half a frame off for the peaks the rule moved -- the first 153 samples there, the first 473 here.)
+ * lcs_set_duplex refuses (LCS_ERR_BAD_ARG, an lcs_last_error text) any other value, and a change while an lcs_stream_open stream
+ * is open: the captured graph holds the mode it was opened with.
+ * NO AUTOMATIC DECISION between the two is made: trying both would double the SSS windows per occurrence (the window kernel has two
+ * idle window slots per pair of occurrences and would need four) and would change the population the second threshold
+ * (thresh2_n_sigma) is taken over, i.e. the decision itself, for FDD cells too.
+ * RANGE OF THE FREQUENCY ESTIMATE.  pss_sss_foe measures a phase over pss_sss_dist samples and is unambiguous within
+ * +- fs k / (2 pss_sss_dist) of the hypothesis the peak was found at: FDD +- 7.0 kHz (normal CP) / +- 6.0 kHz (extended), TDD
+ * +- 2330 Hz / +- 2000 Hz.  On the reference's 5 kHz hypothesis grid the residual reaches +- 2500 Hz: a TDD search needs a grid step
+ * of at most 4 kHz (host/CellSearch -x tdd and the Python helper f_search_set_for(..., step=2.5e3) use 2.5 kHz).  The library does
+ * not touch the caller's f_search_set.
+ * The tracker entry points (lcs_track_*) stay FDD whatever the mode: lcs_track_cut and lcs_track_block take symbol positions from
+ * the caller, and the PSS / SSS positions of lcs_track_stats are frame structure type 1's. */
+#define LCS_DUPLEX_FDD 0
+#define LCS_DUPLEX_TDD 1
+int lcs_set_duplex(lcs_ctx *ctx, int duplex);
+int lcs_get_duplex(const lcs_ctx *ctx, int *duplex);
 
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 

@@ -61,6 +61,10 @@ class Searcher {
   // context settings (include/lcs.h): the per-cell stages' footprint limit; device-resident complex<float> batches checked for dongle data
   void set_max_cells_in_flight(int n) { check(lcs_set_max_cells_in_flight(h_, n)); }
   void set_float_batch_probe(bool on) { check(lcs_set_float_batch_probe(h_, on ? 1 : 0)); }
+  // LCS_DUPLEX_FDD (default) / LCS_DUPLEX_TDD: where sss_detect and pss_sss_foe look for the SSS, for every call on this context
+  // (lcs_set_duplex).  A context setting: the reference's signatures (host/searcher_shim) have no duplex.
+  void set_duplex(int duplex) { check(lcs_set_duplex(h_, duplex)); }
+  int duplex() { int d = LCS_DUPLEX_FDD; check(lcs_get_duplex(h_, &d)); return d; }
 
   // include/searcher.h:22-41
   void xcorr_pss(const cn::cvec &capbuf, const cn::vec &f_search_set, unsigned char ds_comb_arm, double fc_requested,

@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS
+from .capi import LcsCell, LcsTrackCell, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -51,10 +51,12 @@ def new_cell(**kw) -> LcsCell:
     return c
 
 
-def f_search_set_for(freq_start: float, ppm: float) -> np.ndarray:
-    """Frequency-offset grid of the CLI (src/CellSearch.cpp:463-464)."""
-    n_extra = int(np.floor((freq_start * ppm / 1e6 + 2.5e3) / 5e3))
-    return np.arange(-n_extra, n_extra + 1) * 5000.0
+def f_search_set_for(freq_start: float, ppm: float, step: float = 5e3) -> np.ndarray:
+    """Frequency-offset grid of the CLI (src/CellSearch.cpp:463-464); step = 5e3 is the reference's grid exactly.
+    A TDD search (Searcher.set_duplex) needs step <= 4e3: its PSS/SSS frequency estimate is unambiguous within +- 2330 Hz
+    (normal CP) / +- 2000 Hz (extended) of the hypothesis only (include/lcs.h: lcs_set_duplex); host/CellSearch -x tdd uses 2.5e3."""
+    n_extra = int(np.floor((freq_start * ppm / 1e6 + step / 2) / step))
+    return np.arange(-n_extra, n_extra + 1) * float(step)
 
 
 class Searcher:
@@ -358,6 +360,17 @@ class Searcher:
         out["bpo"] = np.array([tc[i].bulk_phase_offset for i in range(n_cells)])
         out["gpu_ms"] = ms.value
         return out
+
+    def set_duplex(self, duplex: int):
+        """DUPLEX_FDD (default) or DUPLEX_TDD: where sss_detect and pss_sss_foe look for the SSS relative to the PSS, for every call
+        on this searcher (lcs_set_duplex, include/lcs.h).  Refused for any other value and while a stream is open."""
+        self._chk(self._lib.lcs_set_duplex(self._h, int(duplex)), "lcs_set_duplex")
+
+    @property
+    def duplex(self) -> int:
+        d = C.c_int(-1)
+        self._chk(self._lib.lcs_get_duplex(self._h, C.byref(d)), "lcs_get_duplex")
+        return d.value
 
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route

@@ -16,6 +16,7 @@ FMT_C64, FMT_IQ_U8, FMT_C128 = 0, 1, 2      # FMT_C128: lcs_track_cut only
 FMT_IQ_S8, FMT_IQ_S16 = 3, 4                # wideband captures of lcs_channelize: interleaved signed 8 / 16 bit
 STAGE_PSS, STAGE_FULL = 1, 3
 MAX_PEAKS = 104            # LCS_MAX_PEAKS: the longest list peak_search can return (include/lcs.h)
+DUPLEX_FDD, DUPLEX_TDD = 0, 1      # LCS_DUPLEX_*: where the SSS lies relative to the PSS (include/lcs.h: lcs_set_duplex)
 ERRORS = {-1: "LCS_ERR_NO_DEVICE", -2: "LCS_ERR_BAD_ARG", -3: "LCS_ERR_HIP", -4: "LCS_ERR_OVERFLOW", -5: "LCS_ERR_NOMEM"}
 
 
@@ -63,7 +64,7 @@ class LcsTrackCell(C.Structure):
 
 
 EXPORTS = [
-    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe",
+    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -105,6 +106,9 @@ def load() -> C.CDLL:
     L.lcs_cell_init.argtypes = [cp]
     L.lcs_cell_init.restype = None
     L.lcs_set_max_cells_in_flight.argtypes = [vp, C.c_int]
+    if hasattr(L, "lcs_set_duplex"):      # (absent from older developer builds loaded through bench.py --lib)
+        L.lcs_set_duplex.argtypes = [vp, C.c_int]
+        L.lcs_get_duplex.argtypes = [vp, C.POINTER(C.c_int)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

@@ -151,6 +151,7 @@ Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &sr
   L.fset = c->fset_ws;
   L.round_cells = std::min(c->max_work, c->percell_cap);
   L.single_stream = c->st_open;
+  L.duplex = c->duplex;
   if (c->st_open) { L.tracked = c->st_dtracked; L.n_tracked = c->st_dntracked; }
   return L;
 }
@@ -352,6 +353,22 @@ int lcs_set_float_batch_probe(lcs_ctx *c, int on) {
   if (!c) return LCS_ERR_BAD_ARG;
   c->c64_probe = on != 0;
   c->c64_skip = 0;
+  return LCS_OK;
+}
+
+int lcs_set_duplex(lcs_ctx *c, int duplex) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (duplex != LCS_DUPLEX_FDD && duplex != LCS_DUPLEX_TDD) { c->err = "duplex is neither LCS_DUPLEX_FDD nor LCS_DUPLEX_TDD"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open && duplex != c->duplex) {
+    c->err = "the open stream's captured graph holds the duplex mode it was opened with: lcs_stream_close first";
+    return LCS_ERR_BAD_ARG;
+  }
+  c->duplex = duplex;
+  return LCS_OK;
+}
+int lcs_get_duplex(const lcs_ctx *c, int *duplex) {
+  if (!c || !duplex) return LCS_ERR_BAD_ARG;
+  *duplex = c->duplex;
   return LCS_OK;
 }
 

@@ -188,6 +188,7 @@ struct Launch {
   int tfoec_parts = 4;                  // workgroups per cell for the timing estimate: 2 in batches
   const int16_t *tracked = nullptr;     // identities k_gather_work leaves out (the streaming mode's tracked list), null: no filter
   const int *n_tracked = nullptr;
+  int duplex = LCS_DUPLEX_FDD;          // lcs_set_duplex: where the SSS lies relative to the PSS (sss_foe.hip: the Dx table)
 };
 // The last enqueued batch: lcs_batch_collect (its late per-cell rounds), lcs_batch_readback and lcs_last_batch_stats read it.
 struct BatchRecord {
@@ -338,6 +339,7 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<int16_t> d_derm_inv;       // [2][120][16]: for every coded bit (stream*40+col) the rate-matched PBCH bit positions carrying it (ascending, -1 padded)
   DevBuf<double> d_dbg;             // debug outputs of the single-cell stage entry points
   DevBuf<int> d_flag;               // exactness verdict of k_ingest_c128
+  int duplex = LCS_DUPLEX_FDD;      // lcs_set_duplex: copied into every Launch by make_launch, read by nothing else
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)

@@ -159,13 +159,38 @@ __device__ __forceinline__ WorkItem peak_lookup(const int *__restrict__ npeaks, 
   return w;
 }
 
+// ------------------------------------------------------------------ where the synchronisation signals lie (lcs_set_duplex)
+// Samples at 1.92 Msps.  Frame structure type 1 (FDD) carries the PSS in the last symbol of slots 0 / 10 and the SSS in the symbol
+// before it; type 2 (TDD, 36.211 4.2) carries the PSS in symbol 2 of slots 2 / 12 and the SSS in the last symbol of slots 1 / 11,
+// three symbols earlier.  The FDD column is the reference's (src/searcher.cpp:533-850), the TDD column the same expressions with the
+// type 2 positions.  The mode is an argument of every kernel below (Launch::duplex, wave-uniform), and all of them read their
+// geometry here and nowhere else.
+struct Dx {
+  // PSS DFT window start minus SSS DFT window start: 128 + 9 | 128 + 32; 3 * 128 + 10 + 9 + 9 | 3 * 160
+  static __host__ __device__ constexpr int sss_back(int duplex, bool ext) {
+    return duplex == LCS_DUPLEX_TDD ? (ext ? 480 : 412) : (ext ? 128 + 32 : 128 + 9);
+  }
+  // the room rule (ref :556-558): a peak whose extended-CP SSS window would start before the buffer moves one half frame right
+  static __host__ __device__ constexpr int room(int duplex) { return 2 + sss_back(duplex, true); }
+  // PSS DFT window start inside the frame: 960 - 128 | 1920 + 138 + 137 + 9, 1920 + 2 * 160 + 32 (in TDD it depends on the CP)
+  static __host__ __device__ constexpr int pss_in_frame(int duplex, bool ext) {
+    return duplex == LCS_DUPLEX_TDD ? (ext ? 2272 : 2204) : 960 - 128;
+  }
+  // first SSS DFT window start inside the frame: in front of the PSS | the last symbol of slot 1 whatever the CP
+  static __host__ __device__ constexpr int sss_in_frame(int duplex, bool ext) {
+    return duplex == LCS_DUPLEX_TDD ? 1920 - 128 : (ext ? 960 - 128 - 32 - 128 : 960 - 128 - 9 - 128);
+  }
+};
+static_assert(Dx::room(LCS_DUPLEX_FDD) == 162 && Dx::room(LCS_DUPLEX_TDD) == 482, "the room rule's bound");
+static_assert(9 - 2 - Dx::pss_in_frame(LCS_DUPLEX_FDD, false) == 128 + 9 - 960 - 2, "the reference's frame_start offset");
+
 // ------------------------------------------------------------------ sss_detect geometry
 struct SssGeo { double peak_loc, k_factor, kph; int n_pss; };
-__device__ __forceinline__ SssGeo sss_geometry(const lcs_cell &cell, const SlotParams &p, uint32_t n_cap) {
+__device__ __forceinline__ SssGeo sss_geometry(const lcs_cell &cell, const SlotParams &p, uint32_t n_cap, int duplex) {
   SssGeo g;
   g.peak_loc = cell.ind;
   g.k_factor = (p.fc_req - cell.freq) / p.fc_prog;
-  if (g.peak_loc + 9 < 162) g.peak_loc += 9600 * g.k_factor;
+  if (g.peak_loc + 9 < Dx::room(duplex)) g.peak_loc += 9600 * g.k_factor;
   g.n_pss = d_range_len(g.peak_loc, g.k_factor * 9600, (double)n_cap - 125 - 9);
   if (g.n_pss > MAX_HF) g.n_pss = MAX_HF;
   const double fs = p.fs_prog * g.k_factor;
@@ -182,7 +207,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sss_win(const lcs_cell *__restri
                                                         WorkItem *__restrict__ items, int *__restrict__ n_items,
                                                         const CapSrc src,
                                                         uint32_t n_cap, const SlotParams *__restrict__ params,
-                                                        const double2 *__restrict__ pss_fd, double *__restrict__ ws) {
+                                                        const double2 *__restrict__ pss_fd, double *__restrict__ ws, int duplex) {
   LCS_TAIL_PRIO();
   __shared__ cd2 tw[128];
   __shared__ cd2 tb_all[SW_WAVES][8 * FFT128_WSTRIDE];
@@ -208,7 +233,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sss_win(const lcs_cell *__restri
     const int slot = __builtin_amdgcn_readfirstlane(wi.slot), pk = __builtin_amdgcn_readfirstlane(wi.peak);
     const lcs_cell cell = peaks[(size_t)slot * LCS_MAXP + pk];
     const SlotParams p = params[slot];
-    const SssGeo g = sss_geometry(cell, p, n_cap);
+    const SssGeo g = sss_geometry(cell, p, n_cap, duplex);
     const CapView cap = cap_view(src, slot);
     const WinRot rot = win_rot_prepare(g.kph, lane, trot);
     const int occ = w / 3, kind = w - 3 * occ;
@@ -218,7 +243,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sss_win(const lcs_cell *__restri
       const bool valid = w < 6 && k < g.n_pss;
       const uint32_t pss_loc = (uint32_t)d_round_i(g.peak_loc + k * (g.k_factor * 9600));
       const long pss_dft = (long)(pss_loc + 9 - 2);
-      const long loc = (kind == 0) ? pss_dft : (kind == 1 ? pss_dft - 128 - 32 : pss_dft - 128 - 9);
+      const long loc = (kind == 0) ? pss_dft : pss_dft - Dx::sss_back(duplex, kind == 1);
       cd2 x[16];
       win_fft8<KIND>(cap, loc, valid, rot, n_cap, lane, tb, tw, trot, x);
       double *rec = ws + (size_t)it * SW_ITEM + (size_t)k * SW_REC;
@@ -264,7 +289,7 @@ __global__ __launch_bounds__(SF_THREADS) void k_sss_ml(lcs_cell *__restrict__ pe
                                                        const int *__restrict__ n_items, uint32_t n_cap,
                                                        const SlotParams *__restrict__ params, double thresh2,
                                                        const int8_t *__restrict__ sss_fd, const double *__restrict__ ws,
-                                                       double *dbg) {
+                                                       double *dbg, int duplex) {
   LCS_TAIL_PRIO();
   __shared__ MlShared S;
   const int tid = threadIdx.x;
@@ -273,7 +298,7 @@ __global__ __launch_bounds__(SF_THREADS) void k_sss_ml(lcs_cell *__restrict__ pe
     lcs_cell *cell_p = peaks + (size_t)slot * LCS_MAXP + items[it].peak;
     const lcs_cell cell = *cell_p;
     const SlotParams p = params[slot];
-    const SssGeo g = sss_geometry(cell, p, n_cap);
+    const SssGeo g = sss_geometry(cell, p, n_cap, duplex);
     if (g.n_pss < 1) continue;
     const int n_id_2 = cell.n_id_2;
     const double *wsi = ws + (size_t)it * SW_ITEM;
@@ -344,7 +369,10 @@ __global__ __launch_bounds__(SF_THREADS) void k_sss_ml(lcs_cell *__restrict__ pe
       const int cp_type = e ? LCS_CP_EXTENDED : LCS_CP_NORMAL;
       const double mx0 = S.dec[2 * e][0], mx1 = S.dec[2 * e + 1][0];
       const double k_factor = g.k_factor;
-      double frame_start = cell.ind + (128 + 9 - 960 - 2) * 16 / FS_LTE * p.fs_prog * k_factor;
+      // FDD: the reference's cell.ind (:737), so a peak the room rule moved comes out half a frame off as it does there; TDD: peak_loc,
+      // the value behind the room rule, as the Matlab original has it (sss_detect.m) -- the rule moves 5 % of all timings there
+      const double pss_at = (duplex == LCS_DUPLEX_TDD) ? g.peak_loc : (double)cell.ind;
+      double frame_start = pss_at + (9 - 2 - Dx::pss_in_frame(duplex, e != 0)) * 16 / FS_LTE * p.fs_prog * k_factor;
       int col;
       if (mx0 > mx1) col = 0;
       else { col = 1; frame_start = frame_start + 9600 * k_factor * 16 / FS_LTE * p.fs_prog * k_factor; }   // k_factor^2: quirk Q3
@@ -380,7 +408,7 @@ __global__ __launch_bounds__(SF_THREADS) void k_sss_ml(lcs_cell *__restrict__ pe
 
 // ------------------------------------------------------------------ pss_sss_foe
 struct FoeGeo { int pss_sss_dist, sn_init, n_sss; double first_sss, step, k_factor, kph; bool ok; };
-__device__ __forceinline__ FoeGeo foe_geometry(const lcs_cell &cell, const SlotParams &p, uint32_t n_cap) {
+__device__ __forceinline__ FoeGeo foe_geometry(const lcs_cell &cell, const SlotParams &p, uint32_t n_cap, int duplex) {
   FoeGeo g;
   g.ok = false;
   g.n_sss = 0;
@@ -388,11 +416,11 @@ __device__ __forceinline__ FoeGeo foe_geometry(const lcs_cell &cell, const SlotP
   const double k_factor = (p.fc_req - cell.freq) / p.fc_prog;
   g.k_factor = k_factor;
   if (cell.cp_type == LCS_CP_NORMAL) {
-    g.pss_sss_dist = (int)(uint16_t)d_round_i((128 + 9) * 16 / FS_LTE * p.fs_prog * k_factor);
-    g.first_sss = cell.frame_start + (960 - 128 - 9 - 128) * 16 / FS_LTE * p.fs_prog * k_factor;
+    g.pss_sss_dist = (int)(uint16_t)d_round_i(Dx::sss_back(duplex, false) * 16 / FS_LTE * p.fs_prog * k_factor);
+    g.first_sss = cell.frame_start + Dx::sss_in_frame(duplex, false) * 16 / FS_LTE * p.fs_prog * k_factor;
   } else if (cell.cp_type == LCS_CP_EXTENDED) {
-    g.pss_sss_dist = (int)(uint16_t)d_round_i((128 + 32) * k_factor);   // quirk Q4
-    g.first_sss = cell.frame_start + (960 - 128 - 32 - 128) * 16 / FS_LTE * p.fs_prog * k_factor;
+    g.pss_sss_dist = (int)(uint16_t)d_round_i(Dx::sss_back(duplex, true) * k_factor);   // quirk Q4
+    g.first_sss = cell.frame_start + Dx::sss_in_frame(duplex, true) * 16 / FS_LTE * p.fs_prog * k_factor;
   } else return g;
   g.first_sss = d_wrap(g.first_sss, -0.5, 9600 * 2 - 0.5);
   if (g.first_sss - 9600 * k_factor > -0.5) { g.first_sss -= 9600 * k_factor; g.sn_init = 10; } else g.sn_init = 0;
@@ -416,7 +444,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_foe_win(const lcs_cell *__restri
                                                         const CapSrc src,
                                                         uint32_t n_cap, const SlotParams *__restrict__ params,
                                                         const double2 *__restrict__ pss_fd, const int8_t *__restrict__ sss_fd,
-                                                        double *__restrict__ ws) {
+                                                        double *__restrict__ ws, int duplex) {
   LCS_TAIL_PRIO();
   __shared__ cd2 tw[128];
   __shared__ cd2 tb_all[FW_WAVES][8 * FFT128_WSTRIDE];
@@ -438,7 +466,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_foe_win(const lcs_cell *__restri
     const int slot = items[it].slot;
     const lcs_cell cell = peaks[(size_t)slot * LCS_MAXP + items[it].peak];
     const SlotParams p = params[slot];
-    const FoeGeo g = foe_geometry(cell, p, n_cap);
+    const FoeGeo g = foe_geometry(cell, p, n_cap, duplex);
     if (!g.ok || k0 >= g.n_sss) continue;
     const CapView cap = cap_view(src, slot);
     const WinRot rot = win_rot_prepare(g.kph, lane, trot);
@@ -493,7 +521,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_foe_win(const lcs_cell *__restri
 
 __global__ __launch_bounds__(64) void k_foe_fin(lcs_cell *__restrict__ peaks, const WorkItem *__restrict__ items,
                                                 const int *__restrict__ n_items, uint32_t n_cap,
-                                                const SlotParams *__restrict__ params, const double *__restrict__ ws) {
+                                                const SlotParams *__restrict__ params, const double *__restrict__ ws, int duplex) {
   LCS_TAIL_PRIO();
   const int it = blockIdx.x * blockDim.x + threadIdx.x;
   if (it >= *n_items) return;
@@ -501,7 +529,7 @@ __global__ __launch_bounds__(64) void k_foe_fin(lcs_cell *__restrict__ peaks, co
   lcs_cell *cell_p = peaks + (size_t)slot * LCS_MAXP + items[it].peak;
   const lcs_cell cell = *cell_p;
   const SlotParams p = params[slot];
-  const FoeGeo g = foe_geometry(cell, p, n_cap);
+  const FoeGeo g = foe_geometry(cell, p, n_cap, duplex);
   if (!g.ok) return;
   cd2 M = mk(0, 0);
   for (int k = 0; k < g.n_sss; ++k) {
@@ -533,18 +561,18 @@ static int run_sss_foe(lcs_ctx *c, const Launch &L, double thresh2, int mode, do
   if (mode & 1) {
     lcs_by_cap_kind(src, [&](auto kind) {
       hipLaunchKernelGGL(k_sss_win<decltype(kind)::value>, dim3(win_grid), dim3(SW_THREADS), 0, c->stream, c->peaks, c->npeaks, n_buf, c->pk_items, c->n_pk, src,
-                         n_cap, L.params, c->d_pss_fd, c->sss_ws);
+                         n_cap, L.params, c->d_pss_fd, c->sss_ws, L.duplex);
     });
     hipLaunchKernelGGL(k_sss_ml, dim3(item_grid), dim3(SF_THREADS), 0, c->stream, c->peaks, c->pk_items, c->n_pk, n_cap,
-                       L.params, thresh2, c->d_sss_fd, c->sss_ws, dbg);
+                       L.params, thresh2, c->d_sss_fd, c->sss_ws, dbg, L.duplex);
   }
   if (mode & 2) {
     lcs_by_cap_kind(src, [&](auto kind) {
       hipLaunchKernelGGL(k_foe_win<decltype(kind)::value>, dim3((int)std::min<size_t>((cap_items * FW_QUADS + 3) / 4, LCS_WIN_GRID)), dim3(FW_THREADS), 0, c->stream,
-                         c->peaks, c->pk_items, c->n_pk, src, n_cap, L.params, c->d_pss_fd, c->d_sss_fd, c->sss_ws);
+                         c->peaks, c->pk_items, c->n_pk, src, n_cap, L.params, c->d_pss_fd, c->d_sss_fd, c->sss_ws, L.duplex);
     });
     hipLaunchKernelGGL(k_foe_fin, dim3((unsigned)((cap_items + 63) / 64)), dim3(64), 0, c->stream, c->peaks, c->pk_items,
-                       c->n_pk, n_cap, L.params, c->sss_ws);
+                       c->n_pk, n_cap, L.params, c->sss_ws, L.duplex);
   }
   HIPCHK(c, hipGetLastError());
   return LCS_OK;

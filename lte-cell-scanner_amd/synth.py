@@ -124,11 +124,20 @@ def _crs(n_id_cell, slot, sym, cp_normal):
     return ((1 - 2 * c[2 * m]) + 1j * (1 - 2 * c[2 * m + 1])) / np.sqrt(2.0)
 
 
+# 36.211 table 4.2-2: the kind of each subframe (Downlink, Special, Uplink) per uplink-downlink configuration 0..6
+TDD_SUBFRAMES = ("DSUUUDSUUU", "DSUUDDSUUD", "DSUDDDSUDD", "DSUUUDDDDD", "DSUUDDDDDD", "DSUDDDDDDD", "DSUUUDSUUD")
+
+
 def cell_waveform(n_frames, n_id_1, n_id_2, cp_normal=True, n_ports=2, n_rb_dl=50, phich_duration_ext=0,
-                  phich_res=2, sfn0=0, load=0.5, rng=None, port_gains=None, per_port=False):
+                  phich_res=2, sfn0=0, load=0.5, rng=None, port_gains=None, per_port=False, tdd=None):
     """Baseband samples at the nominal 1.92 Msps, n_frames*19200 long, starting at the boundary of frame sfn0.
     per_port: the antenna ports' waveforms separately, [n_ports, n] each scaled by 1/sqrt(n_ports) and without the flat
-    per-port gains -- what a channel model per (cell, port) starts from (fading_channel)."""
+    per-port gains -- what a channel model per (cell, port) starts from (fading_channel).
+    tdd: None = frame structure type 1 (FDD), or (ul_dl_config 0..6, dwpts_symbols) = frame structure type 2 (36.211 4.2): the
+    PSS in symbol 2 of slots 2 and 12 (subframe 6 carries it in configurations 3-5 too, where it is an ordinary downlink subframe),
+    the SSS in the last symbol of slots 1 and 11 with the sequences of slots 0 and 10, PBCH, CRS and load as in FDD in downlink
+    subframes and in the first dwpts_symbols symbols (>= 3) of a special subframe; the rest of a special subframe and the uplink
+    subframes are silent (exactly zero, and nothing is drawn from rng for them).  tdd=None draws from rng in the order it always did."""
     rng = rng or np.random.default_rng(0)
     n_id_cell = n_id_2 + 3 * n_id_1
     n_symb = 7 if cp_normal else 6
@@ -141,6 +150,10 @@ def cell_waveform(n_frames, n_id_1, n_id_2, cp_normal=True, n_ports=2, n_rb_dl=5
     pss = _pss_fd(n_id_2)
     crs_cache = {}
     out = np.zeros((n_ports, n_frames * 19200) if per_port else n_frames * 19200, np.complex128)
+    if tdd is not None:
+        kinds, dwpts = TDD_SUBFRAMES[int(tdd[0])], int(tdd[1])
+        if not 3 <= dwpts <= 2 * n_symb:
+            raise ValueError("dwpts_symbols must hold the PSS (>= 3) and fit the subframe")
     pos = 0
     pbch = None
     for fr in range(n_frames):
@@ -151,6 +164,12 @@ def cell_waveform(n_frames, n_id_1, n_id_2, cp_normal=True, n_ports=2, n_rb_dl=5
         pb_i = 0
         for slot in range(20):
             for sym in range(n_symb):
+                cp = (10 if sym == 0 else 9) if cp_normal else 32
+                if tdd is not None:
+                    kind = kinds[slot >> 1]
+                    if kind == "U" or (kind == "S" and (slot & 1) * n_symb + sym >= dwpts):
+                        pos += cp + 128
+                        continue
                 grid = np.zeros((n_ports, 72), np.complex128)
                 reserved = np.zeros(72, bool)
                 # cell-specific reference signals
@@ -170,10 +189,15 @@ def cell_waveform(n_frames, n_id_1, n_id_2, cp_normal=True, n_ports=2, n_rb_dl=5
                         reserved[idx] = True
                         if port < n_ports:
                             grid[port, idx] = crs_cache[key]
-                is_sync = (slot % 10 == 0) and sym >= n_symb - 2
+                if tdd is None:
+                    is_sync = (slot % 10 == 0) and sym >= n_symb - 2
+                    is_pss = sym == n_symb - 1
+                else:
+                    is_pss = (slot % 10 == 2) and sym == 2
+                    is_sync = is_pss or ((slot % 10 == 1) and sym == n_symb - 1)
                 is_pbch = (slot == 1) and sym <= 3
                 if is_sync:
-                    seq = pss if sym == n_symb - 1 else _sss_fd(n_id_1, n_id_2, slot)
+                    seq = pss if is_pss else _sss_fd(n_id_1, n_id_2, slot - (slot % 10))
                     grid[:, :] = 0
                     grid[0, 5:67] = seq * np.sqrt(n_ports)      # sync signals go out on port 0
                 elif is_pbch:
@@ -207,7 +231,6 @@ def cell_waveform(n_frames, n_id_1, n_id_2, cp_normal=True, n_ports=2, n_rb_dl=5
                 X[..., 92:128] = mix[..., :36]
                 X[..., 1:37] = mix[..., 36:]
                 td = np.fft.ifft(X, axis=-1) * np.sqrt(128.0)
-                cp = (10 if sym == 0 else 9) if cp_normal else 32
                 out[..., pos:pos + cp] = td[..., -cp:]
                 out[..., pos + cp:pos + cp + 128] = td
                 pos += cp + 128
@@ -285,7 +308,7 @@ def make_signal(rng, fc, cells=(), n_cap=N_CAP, fc_programmed=None, fs_programme
         chan = cd.get("channel")
         w = cell_waveform(n_frames, cd["n_id_1"], cd["n_id_2"], cd.get("cp_normal", True), cd.get("n_ports", 2),
                           cd.get("n_rb_dl", 50), cd.get("phich_duration_ext", 0), cd.get("phich_res", 2),
-                          cd.get("sfn0", int(rng.integers(0, 1024))), cd.get("load", 0.5), rng, cd.get("port_gains"), per_port=chan is not None)
+                          cd.get("sfn0", int(rng.integers(0, 1024))), cd.get("load", 0.5), rng, cd.get("port_gains"), per_port=chan is not None, tdd=cd.get("tdd"))
         if chan is not None:      # an independent fading multipath channel per (cell, antenna port), 36.101 B.2
             w = sum(fading_channel(rng, wp, chan, float(cd.get("doppler_hz", 0.0))) for wp in w)
         # receiver sample n is taken at transmitter time (t0 + n / rate) nominal samples
@@ -330,7 +353,7 @@ def make_capbuf(seed, fc, cells=(), snr_db=10.0, n_cap=N_CAP, rms=0.15, quantise
     fc_programmed and the true sample rate fs_programmed * k_factor (src/searcher.cpp:147).
 
     cells: dicts with n_id_1, n_id_2 and optionally cp_normal, n_ports, n_rb_dl, phich_duration_ext,
-    phich_res, sfn0, load, f_off (Hz, the dongle's LO error: +f_off means the cell appears f_off
+    phich_res, sfn0, load, tdd ((ul_dl_config, dwpts_symbols): a frame structure type 2 cell, cell_waveform), f_off (Hz, the dongle's LO error: +f_off means the cell appears f_off
     above DC), t0 (samples into the first frame), gain_db, channel ("EPA" / "EVA" / "ETU" or (delays_ns, powers_db): an
     independent Rayleigh tapped delay line per antenna port, fading_channel) with doppler_hz.  front_end: see
     add_noise_and_quantise.  Returns (iq_u8 or complex128, truth)."""
@@ -345,19 +368,22 @@ def iq_u8_to_complex(iq):
     return ((f[0::2] - 127.0) / 128.0) + 1j * ((f[1::2] - 127.0) / 128.0)
 
 
-def make_batch_u8(n_buf, seed, fc_list, occupied_every=4, n_distinct=8, cells_cycle=(1, 2)):
+def make_batch_u8(n_buf, seed, fc_list, occupied_every=4, n_distinct=8, cells_cycle=(1, 2), tdd=False, f_off_max=60e3):
     """Synthetic sweep: every `occupied_every`-th carrier holds 1-2 cells (SNR 0..10 dB, LO error within
     +-60 kHz), the others are noise only -- like a band scan where most raster points are empty.
     To keep host-side generation quick, `n_distinct` different occupied buffers are generated and
     re-used cyclically with an independent circular time shift.  cells_cycle: cells planted in the i-th distinct
-    occupied buffer, cyclically."""
+    occupied buffer, cyclically.  tdd=True plants frame structure type 2 cells (uplink-downlink configurations 0..6 in turn, a
+    9-symbol DwPTS) with the same draws, i.e. the same occupancy, identities and timings; f_off_max bounds the LO error (a TDD
+    search wants a 2.5 kHz grid: 37.5e3 keeps it at the 31 hypotheses the default 60e3 has on a 5 kHz grid)."""
     rng = np.random.default_rng(seed)
     occ = []
     for i in range(min(n_distinct, max(1, n_buf // occupied_every + 1))):
         n_cells = int(cells_cycle[i % len(cells_cycle)])
         cells = [dict(n_id_1=int(rng.integers(0, 168)), n_id_2=int(rng.integers(0, 3)), cp_normal=bool(i % 5 != 4),
                       n_ports=int((1, 2, 2, 4)[i % 4]), n_rb_dl=int((6, 15, 25, 50, 75, 100)[i % 6]),
-                      f_off=float(rng.uniform(-60e3, 60e3)), gain_db=-3.0 * j) for j in range(n_cells)]
+                      f_off=float(rng.uniform(-f_off_max, f_off_max)), gain_db=-3.0 * j, tdd=((i + j) % 7, 9) if tdd else None)
+                 for j in range(n_cells)]
         occ.append(make_capbuf(seed * 1000 + i, float(fc_list[0]), cells, snr_db=float(rng.uniform(0, 10)))[0])
     out = np.empty((n_buf, 2 * N_CAP), np.uint8)
     k = 0

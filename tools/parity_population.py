@@ -26,6 +26,13 @@ The buffers:
              noise realisations, 1-2 cells through the fading channels of the `channels` group, LO errors out to 0.9 of the
              grid's edge (up to 380 kHz), the stage arrays of every decoded cell compared as there.
 
+  tdd        128 buffers of frame structure type 2 cells (36.211 4.2), searched with the context set to LCS_DUPLEX_TDD: 16 scenes x 8
+             noise realisations -- 0-3 cells, every uplink-downlink configuration, DwPTS of 3..12 symbols, both CP types, 1 / 2 / 4
+             ports, SNR -6 .. +10 dB, bands 38 / 39 / 40 on the 2.5 kHz grids a TDD search needs (n_f = 25 / 31 / 31).  The oracle has
+             no TDD: the reference side runs sss_detect and pss_sss_foe from the numpy restatement with the TDD geometry
+             (tests/sss_duplex_ref.py, pinned to the oracle in FDD) and everything else from the oracle; the same records per buffer
+             are compared, and the worst |GPU - reference| of frame_start / freq_fine / freq_superfine is kept per group.
+
 Per buffer, GPU (lcs_batch_enqueue / lcs_batch_collect / lcs_batch_readback) against oracle (oracle/lcs_oracle.c, one
 process per host core):
   xc_incoherent_collapsed_frq   every one of the 3 x 9600 indices EQUAL
@@ -144,6 +151,38 @@ def highband_scene(synth, s, seed_offset=0):
     return dict(sig=sig, ref_pow=ref_pow, f=f, fc_req=fc_req, fc_prog=fc_prog, fs_prog=fs_prog, planted=cells, front_end=fe)
 
 
+TDD_GRIDS = ((1.9e9, 20.0), (2.35e9, 16.0), (2.6e9, 12.0))      # bands 39, 40, 38: n_f = 31, 31, 25 at the 2.5 kHz step a TDD search needs
+TDD_SNRS = (-6.0, -3.0, 0.0, 5.0, 10.0, -3.0, 0.0, 5.0)
+
+
+def f_grid_step(freq_start, ppm, step):
+    n_extra = int(np.floor((freq_start * ppm / 1e6 + step / 2) / step))
+    return np.arange(-n_extra, n_extra + 1) * float(step)
+
+
+def tdd_scene(synth, s, seed_offset=0):
+    """Scene s of 16 of the `tdd` group: 0-3 frame structure type 2 cells (every uplink-downlink configuration, DwPTS 3..12
+    symbols, both CP types, 1 / 2 / 4 ports) on a 2.5 kHz hypothesis grid; searched with the context set to LCS_DUPLEX_TDD."""
+    rng = np.random.default_rng(60_000 + s + 1000 * seed_offset)
+    fc, ppm = TDD_GRIDS[s % 3]
+    f = f_grid_step(fc, ppm, 2.5e3)
+    fc_req = fc + 100e3 * (s % 7)
+    dongle = (s % 3 == 1)
+    fc_prog = fc_req * (1 + 17e-6) if dongle else fc_req
+    fs_prog = FS * (1 - 23e-6) if dongle else FS
+    n_cells = (1, 2, 1, 3, 0, 2, 1, 1)[s % 8]
+    cells = []
+    for j in range(n_cells):
+        cp_normal = bool((s + j) % 3 != 0)
+        cells.append(dict(n_id_1=int(rng.integers(0, 168)), n_id_2=int(rng.integers(0, 3)), cp_normal=cp_normal,
+                          n_ports=int((1, 2, 4)[(s + j) % 3]), n_rb_dl=int((6, 15, 25, 50, 75, 100)[(s + 2 * j) % 6]),
+                          phich_duration_ext=int((s + j) % 2), phich_res=int((s + j) % 4),
+                          tdd=(int((s + 3 * j) % 7), int(3 + (s + 5 * j) % (10 if cp_normal else 8))),
+                          f_off=float(rng.uniform(-0.9, 0.9) * f[-1]), gain_db=-3.0 * j))
+    sig, ref_pow, _ = synth.make_signal(rng, fc_req, cells, N_CAP, fc_prog, fs_prog)
+    return dict(sig=sig, ref_pow=ref_pow, f=f, fc_req=fc_req, fc_prog=fc_prog, fs_prog=fs_prog, planted=cells)
+
+
 def _highband_scene_job(args):
     import __graft_entry__ as ge
     s, seed_offset = args
@@ -198,6 +237,17 @@ def build_population(pkg, groups, limit=None, dense_limit=None, seed_offset=0, p
                 items.append(dict(name=f"highband/scene{s:02d}/nf{sc['f'].size}/snr{CH_SNRS[v]:+.0f}dB/v{v}", group="highband", iq=iq, f=sc["f"],
                                   fc_req=sc["fc_req"], fc_prog=sc["fc_prog"], fs_prog=sc["fs_prog"], n_planted=len(sc["planted"]),
                                   snr_db=CH_SNRS[v], arrays=True))
+    if "tdd" in groups:
+        n_scenes = 16 if limit is None else max(1, min(16, limit // 8))
+        for s in range(n_scenes):
+            sc = tdd_scene(synth, s, seed_offset)
+            for v in range(8):
+                rng = np.random.default_rng(92_000 + 8 * s + v + 10_000 * seed_offset)
+                sig = np.roll(sc["sig"], int(rng.integers(0, N_CAP))) if v else sc["sig"]
+                iq = synth.add_noise_and_quantise(rng, sig, sc["ref_pow"], TDD_SNRS[v], rms=float(rng.uniform(0.08, 0.22)))
+                items.append(dict(name=f"tdd/scene{s:02d}/snr{TDD_SNRS[v]:+.0f}dB/v{v}", group="tdd", iq=iq, f=sc["f"],
+                                  fc_req=sc["fc_req"], fc_prog=sc["fc_prog"], fs_prog=sc["fs_prog"], n_planted=len(sc["planted"]),
+                                  snr_db=TDD_SNRS[v], duplex="tdd"))
     fcs = FC + 100e3 * np.arange(128)
     f31 = f_grid(FC, 100.0)
     if "bench" in groups:
@@ -232,6 +282,16 @@ def oracle_job(it):
     import oracle as O
     O.set_legacy(False)
     O.set_threads(1)
+    # the oracle is FDD only: for a TDD buffer the two stages that depend on the duplex mode come from the numpy restatement
+    # (tests/sss_duplex_ref.py, pinned to the oracle in FDD by tests/test_sss_duplex_ref.py), the rest from the oracle
+    if it.get("duplex") == "tdd":
+        if os.path.join(ROOT, "tests") not in sys.path:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import sss_duplex_ref as R
+        sss_detect = lambda c, *a: R.sss_detect(c, *a, geo=R.GEO["tdd"])
+        pss_sss_foe = lambda c, *a: R.pss_sss_foe(c, *a, geo=R.GEO["tdd"])
+    else:
+        sss_detect, pss_sss_foe = O.sss_detect, O.pss_sss_foe
     t0 = time.perf_counter()
     x = it["iq"].astype(np.float64)
     cap = ((x[0::2] - 127.0) / 128.0) + 1j * ((x[1::2] - 127.0) / 128.0)
@@ -254,7 +314,7 @@ def oracle_job(it):
     out_peaks = []
     for p, zr in zip(peaks, z_ratio):
         rec = dict(peak=cell_to_dict(p), z_ratio=zr)
-        c1, dbg = O.sss_detect(p, cap, 3.0, fr, fp, fs)
+        c1, dbg = sss_detect(p, cap, 3.0, fr, fp, fs)
         L = np.concatenate([dbg["ll_nrm"].T.reshape(-1), dbg["ll_ext"].T.reshape(-1)])
         mean, sd = float(L.mean()), float(np.sqrt(L.var(ddof=1)))
         ll = dbg["ll_nrm"] if dbg["ll_nrm"].max() > dbg["ll_ext"].max() else dbg["ll_ext"]
@@ -263,7 +323,7 @@ def oracle_job(it):
         rec["sss_found"] = bool(c1.n_id_1 != -1)
         rec["mib_found"] = False
         if rec["sss_found"]:
-            c2 = O.pss_sss_foe(c1, cap, fr, fp, fs)
+            c2 = pss_sss_foe(c1, cap, fr, fp, fs)
             tfg, ts = O.extract_tfg(c2, cap, fr, fp, fs)
             c3, tfgc, _ = O.tfoec(c2, tfg, ts, fr, fp)
             c4 = O.decode_mib(c3, tfgc)
@@ -299,14 +359,15 @@ def gpu_pass(pkg, items, batch=128, input_fmt="u8"):
     out = [None] * len(items)
     keys = {}
     for i, it in enumerate(items):
-        keys.setdefault((it["group"], it["f"].tobytes(), it["fs_prog"]), []).append(i)
+        keys.setdefault((it["group"], it["f"].tobytes(), it["fs_prog"], it.get("duplex", "fdd")), []).append(i)
     n_repairs = 0
     ties = {}          # group -> [positions listed as near-ties, listed positions left unrepaired], summed over its batches
     t_gpu = 0.0
     kernels = set()
     with pkg.Searcher(0) as S:
-        for (group, _, fs), idx in keys.items():
+        for (group, _, fs, duplex), idx in keys.items():
             f = items[idx[0]]["f"]
+            S.set_duplex(pkg.DUPLEX_TDD if duplex == "tdd" else pkg.DUPLEX_FDD)
             for a in range(0, len(idx), batch):
                 ids = idx[a:a + batch]
                 host = np.stack([items[i]["iq"] for i in ids])
@@ -378,6 +439,7 @@ def compare_arrays(pkg, S, it, o):
 def compare(it, g, o):
     """-> (list of disagreements, counters)"""
     dis = []
+    worst = dict(frame_start=0.0, freq_fine=0.0, freq_superfine=0.0)      # largest |GPU - reference| over the cells both decoded
     name = it["name"]
     bad = np.argwhere(g["frq"] != o["frq"])
     for t, i in bad:
@@ -425,11 +487,13 @@ def compare(it, g, o):
     else:
         for a, p in zip(gc, oc):
             b = p["cell"]
+            for fld in ("frame_start", "freq_fine", "freq_superfine"):
+                worst[fld] = max(worst[fld], abs(a[fld] - b[fld]))
             for fld, tol, rel_ in (("pss_pow", 1e-5, True), ("frame_start", 1e-6, False), ("freq_fine", 1e-4, False), ("freq_superfine", 1e-3, False)):
                 d = abs(a[fld] - b[fld]) / (abs(b[fld]) if rel_ else 1.0)
                 if not d <= tol:
                     dis.append(dict(buffer=name, stage="continuous", what=f"{fld}: {a[fld]!r} vs {b[fld]!r}", margin=None, threshold=str(tol)))
-    return dis, dict(peaks=len(op), sss_found=sum(p["sss_found"] for p in o["peaks"]), cells=len(oc),
+    return dis, dict(worst=worst, peaks=len(op), sss_found=sum(p["sss_found"] for p in o["peaks"]), cells=len(oc),
                      min_sss_margin=min([abs(p["sss_sigma"] - 3.0) for p in o["peaks"]], default=None),
                      min_z_ratio=min([abs(p["z_ratio"] - 1.0) for p in o["peaks"]] + [abs(o["z_rejected"] - 1.0)]),
                      frq_near_ties_1e_5=int(np.count_nonzero(o["frq_margin"] < 1e-5)), frq_near_ties_4e_6=int(np.count_nonzero(o["frq_margin"] < 4e-6)),
@@ -473,7 +537,9 @@ def run(groups=("synthetic", "bench", "dense"), limit=None, workers=None, out_pa
     for it, g, o in zip(items, gpu, orc):
         dis, cnt = compare(it, g, o)
         all_dis += dis
-        pg = per_group.setdefault(it["group"], dict(buffers=0, peaks=0, sss_found=0, cells=0, disagreements=0))
+        pg = per_group.setdefault(it["group"], dict(buffers=0, peaks=0, sss_found=0, cells=0, disagreements=0,
+                                                    worst_abs_deviation=dict(frame_start=0.0, freq_fine=0.0, freq_superfine=0.0)))
+        pg["worst_abs_deviation"] = {k: max(v, cnt["worst"][k]) for k, v in pg["worst_abs_deviation"].items()}
         pg["buffers"] += 1
         pg["disagreements"] += len(dis)
         for k in ("peaks", "sss_found", "cells"):
@@ -523,7 +589,7 @@ def run(groups=("synthetic", "bench", "dense"), limit=None, workers=None, out_pa
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--groups", default="synthetic,bench,dense", help="any of synthetic, bench, dense, channels, highband")
+    ap.add_argument("--groups", default="synthetic,bench,dense", help="any of synthetic, bench, dense, channels, highband, tdd")
     ap.add_argument("--limit", type=int, default=None, help="quick runs: at most this many buffers per group (synthetic: whole scenes of 8; bench: a quarter of it from each of the four batches)")
     ap.add_argument("--dense-limit", type=int, default=None)
     ap.add_argument("--workers", type=int, default=None)
