@@ -62,6 +62,7 @@ struct Options {
   std::vector<long> gpu_list;    // -g a,b,...: one device thread per entry (an index may repeat: "0,0" = two threads on GPU 0)
   long batch = 64;               // carriers per GPU batch (one correlation launch)
   int duplex = LCS_DUPLEX_FDD;   // -x: the band's duplex mode, set on every context
+  bool foe_unwrap = false;       // -u: pss_sss_foe unwrapped by the PSS-only coarse estimate (lcs_set_foe_unwrap), set on every context
   int verbosity = 1;
 };
 
@@ -81,6 +82,7 @@ const OptSpec kSpecs[] = {
     {'g', "gpu", INDEX, "gpu index", {"GPU to run the searcher on (default: current device); 'all' shards the carriers over every GPU, 'a,b,..' over the listed ones", 0}},
     {'B', "batch", INDEX, "batch size", {"carriers searched per GPU batch (default 64)", 0}},
     {'x', "duplex", TEXT, 0, {"duplex mode of the band, fdd (default) or tdd (bands 33-53: SSS three symbols before the PSS; the frequency grid is then 2.5 kHz)", 0}},
+    {'u', "foe-unwrap", FLAG, 0, {"unwrap the PSS/SSS frequency estimate with a PSS-only one: a tdd search then keeps the 5 kHz frequency grid (half the hypotheses)", 0}},
     {'s', "freq-start", REAL, "start frequency", {"frequency where cell search should start", 0}},
     {'e', "freq-end", REAL, "end frequency", {"frequency where cell search should end", 0}},
     {'p', "ppm", REAL, "ppm value", {"crystal remaining PPM error", 0}},
@@ -95,7 +97,7 @@ void usage() {
   std::cout << "LTE CellSearch v" << VERSION_STRING << " (MI355X) help screen\n\n"
             << "CellSearch -s start_frequency [optional_parameters]\n";
   const struct { const char *title; const char *letters; } sections[] = {
-      {"Basic options", "hvbigB"}, {"Frequency search options:", "sex"}, {"Dongle LO correction options:", "pc"},
+      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexu"}, {"Dongle LO correction options:", "pc"},
       {"Capture buffer save/ load options:", "rld"}};
   for (const auto &sec : sections) {
     std::cout << "  " << sec.title << "\n";
@@ -122,6 +124,7 @@ void store(Options &o, const OptSpec &s, const char *value) {
       else if (s.letter == 'v') o.verbosity = 2;
       else if (s.letter == 'b') o.verbosity = 0;
       else if (s.letter == 'r') o.record = true;
+      else if (s.letter == 'u') o.foe_unwrap = true;
       else o.load = true;
       return;
     case TEXT:
@@ -338,7 +341,7 @@ struct InFlight {
 void device_thread(Sweep *sw, int device, int first_batch, int stride) {
   try {
     std::unique_ptr<lcs::Searcher> ctx[2];
-    for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); ctx[k]->set_duplex(sw->opt.duplex); }
+    for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); ctx[k]->set_duplex(sw->opt.duplex); ctx[k]->set_foe_unwrap(sw->opt.foe_unwrap); }
     std::unique_ptr<lcs::Searcher> one;                     // for captures that are not raw dongle bytes
     unsigned char *pinned[2] = {0, 0};
     size_t pinned_bytes[2] = {0, 0};
@@ -353,7 +356,7 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
         for (size_t j = 0; j < f.carriers.size(); ++j) sw->detected[f.carriers[j]].swap(found[j]);
       }
       for (size_t j = 0; j < f.singles.size(); ++j) {
-        if (!one) { one.reset(new lcs::Searcher(device)); one->set_duplex(sw->opt.duplex); }
+        if (!one) { one.reset(new lcs::Searcher(device)); one->set_duplex(sw->opt.duplex); one->set_foe_unwrap(sw->opt.foe_unwrap); }
         const double fc = sw->opt.freq_start + 100e3 * f.single_carriers[j];
         lcsc::cvec capbuf((int)f.singles[j].samples.size());
         std::memcpy(capbuf._data(), f.singles[j].samples.data(), f.singles[j].samples.size() * sizeof(std::complex<double>));
@@ -442,8 +445,9 @@ int main(int argc, char *const argv[]) {
 
   // frequency-offset hypotheses and carrier raster (src/CellSearch.cpp:463-465; n_extra uses freq_start only)
   // A TDD search takes half the step: the PSS/SSS frequency estimate is unambiguous within +- 2330 Hz (normal CP) / +- 2000 Hz
-  // (extended) of the hypothesis there, and the residual on a 5 kHz grid reaches +- 2500 Hz (include/lcs.h: lcs_set_duplex)
-  const double f_step = opt.duplex == LCS_DUPLEX_TDD ? 2.5e3 : 5e3;
+  // (extended) of the hypothesis there, and the residual on a 5 kHz grid reaches +- 2500 Hz (include/lcs.h: lcs_set_duplex) -- unless
+  // the estimate is unwrapped (--foe-unwrap, lcs_set_foe_unwrap): then TDD keeps the reference's grid too
+  const double f_step = (opt.duplex == LCS_DUPLEX_TDD && !opt.foe_unwrap) ? 2.5e3 : 5e3;
   const int n_extra = (int)std::floor((opt.freq_start * opt.ppm / 1e6 + f_step / 2) / f_step);
   sw.f_search_set.set_size(2 * n_extra + 1);
   for (int i = 0; i <= 2 * n_extra; ++i) sw.f_search_set(i) = f_step * (i - n_extra);

@@ -138,17 +138,37 @@ int lcs_set_float_batch_probe(lcs_ctx *ctx, int on);
  * NO AUTOMATIC DECISION between the two is made: trying both would double the SSS windows per occurrence (the window kernel has two
  * idle window slots per pair of occurrences and would need four) and would change the population the second threshold
  * (thresh2_n_sigma) is taken over, i.e. the decision itself, for FDD cells too.
- * RANGE OF THE FREQUENCY ESTIMATE.  pss_sss_foe measures a phase over pss_sss_dist samples and is unambiguous within
+ * RANGE OF THE FREQUENCY ESTIMATE.  pss_sss_foe measures a phase over pss_sss_dist samples and is by itself unambiguous within
  * +- fs k / (2 pss_sss_dist) of the hypothesis the peak was found at: FDD +- 7.0 kHz (normal CP) / +- 6.0 kHz (extended), TDD
  * +- 2330 Hz / +- 2000 Hz.  On the reference's 5 kHz hypothesis grid the residual reaches +- 2500 Hz: a TDD search needs a grid step
- * of at most 4 kHz (host/CellSearch -x tdd and the Python helper f_search_set_for(..., step=2.5e3) use 2.5 kHz).  The library does
- * not touch the caller's f_search_set.
+ * of at most 4 kHz (host/CellSearch -x tdd and the Python helper f_search_set_for(..., step=2.5e3) use 2.5 kHz) unless
+ * lcs_set_foe_unwrap is on, which gives TDD +- 1.5 periods (+- 6990 Hz / +- 6000 Hz) and with them the 5 kHz grid.  The library
+ * does not touch the caller's f_search_set.
  * The tracker entry points (lcs_track_*) stay FDD whatever the mode: lcs_track_cut and lcs_track_block take symbol positions from
  * the caller, and the PSS / SSS positions of lcs_track_stats are frame structure type 1's. */
 #define LCS_DUPLEX_FDD 0
 #define LCS_DUPLEX_TDD 1
 int lcs_set_duplex(lcs_ctx *ctx, int duplex);
 int lcs_get_duplex(const lcs_ctx *ctx, int *duplex);
+/* A second mode of the frequency estimate: pss_sss_foe unwrapped by a PSS-only coarse estimate.  The native estimate aliases by
+ * whole periods fs / pss_sss_dist (see above); nothing else in the chain minds a residual of +- 2.5 kHz -- the PSS correlation and
+ * the peak search do not, and sss_detect removes the common PSS -> SSS phase before its likelihood.  With on = 1 every call that
+ * runs pss_sss_foe also computes, per cell and on the device, the phase between the two halves of the PSS's time-domain symbol,
+ * 64 samples apart (range +- 15 kHz): with fs = fs_programmed k_factor, dist = pss_sss_dist, and first_sss, step, n_sss as
+ * pss_sss_foe forms them in the context's duplex mode,
+ *   P_k      = round(first_sss + k step) + dist + 2                       first sample of the PSS's useful part, k = 0 .. n_sss - 1
+ *   z_k[t]   = capbuf[P_k + t] cis(-2 pi cell.freq / fs t) conj(p[t])     t = 0 .. 127, p[t] = entry 9 + t of lcs_table_pss_td(n_id_2)
+ *   A_k, B_k = the sums of z_k over t < 64 and t >= 64;  C = sum_k conj(A_k) B_k, in occurrence order, unweighted
+ *   f_coarse = atan2(C.im, C.re) / (2 pi) fs / 64                         relative to cell.freq
+ *   n        = clamp(rint((f_coarse - (native - cell.freq)) / (fs / dist)), -1, +1);  0 if n_sss = 0 or C is zero or not finite
+ *   freq_fine = native if n = 0 (the same double), native + n fs / dist otherwise
+ * where native is the reference's freq_fine.  One rule for both duplex modes (in FDD n is 0 on any sane grid).  Off by default, and
+ * then every record and every array is what it was before the mode existed, bit for bit.  Context-wide like the duplex mode, and it
+ * reaches the same entry points: lcs_pss_sss_foe, lcs_search_capbuf, the batch entry points (device and host, enqueue and collect:
+ * a batch keeps the mode it was enqueued with), the streaming mode and lcs_foe_finish.  lcs_set_foe_unwrap refuses
+ * (LCS_ERR_BAD_ARG, an lcs_last_error text) any value other than 0 / 1, and a change while an lcs_stream_open stream is open. */
+int lcs_set_foe_unwrap(lcs_ctx *ctx, int on);
+int lcs_get_foe_unwrap(const lcs_ctx *ctx, int *on);
 
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
@@ -190,6 +210,13 @@ int lcs_sss_detect(lcs_ctx *ctx, const lcs_cell *cell, const double *capbuf_re_i
 int lcs_pss_sss_foe(lcs_ctx *ctx, const lcs_cell *cell_in, const double *capbuf_re_im,
                     uint32_t n_cap, double fc_requested, double fc_programmed,
                     double fs_programmed, lcs_cell *cell_out);
+
+/* The PSS-only coarse estimate of lcs_set_foe_unwrap as a stage of its own, in the context's duplex mode and whatever the unwrap
+ * setting: *f_coarse in Hz relative to cell->freq, c_re_im = C (2 doubles, or NULL), *n_occ = the occurrences summed (or NULL).
+ * Refuses a cell without n_id_1 / n_id_2 / CP type, as lcs_pss_sss_foe does. */
+int lcs_pss_foe_coarse(lcs_ctx *ctx, const lcs_cell *cell, const double *capbuf_re_im, uint32_t n_cap,
+                       double fc_requested, double fc_programmed, double fs_programmed,
+                       double *f_coarse, double *c_re_im /*2, or NULL*/, int *n_occ /*or NULL*/);
 
 /* Replaces extract_tfg -- include/searcher.h:88-98, src/searcher.cpp:857-935.
  * tfg is [n_ofdm][72] row-major; *n_ofdm = 854 (normal CP) or 732 (extended). */

@@ -65,6 +65,18 @@ class Searcher {
   // (lcs_set_duplex).  A context setting: the reference's signatures (host/searcher_shim) have no duplex.
   void set_duplex(int duplex) { check(lcs_set_duplex(h_, duplex)); }
   int duplex() { int d = LCS_DUPLEX_FDD; check(lcs_get_duplex(h_, &d)); return d; }
+  // pss_sss_foe unwrapped by the PSS-only coarse estimate (lcs_set_foe_unwrap): a TDD band is then searched on the 5 kHz grid
+  void set_foe_unwrap(bool on) { check(lcs_set_foe_unwrap(h_, on ? 1 : 0)); }
+  bool foe_unwrap() { int on = 0; check(lcs_get_foe_unwrap(h_, &on)); return on != 0; }
+  // ... and the coarse estimate as a stage of its own (lcs_pss_foe_coarse): Hz relative to cell.freq; C and the occurrences summed if asked
+  double pss_foe_coarse(const Cell &cell, const cn::cvec &capbuf, double fc_requested, double fc_programmed, double fs_programmed,
+                        std::complex<double> *C = 0, int *n_occ = 0) {
+    double f = 0, c2[2] = {0, 0};
+    check(lcs_pss_foe_coarse(h_, &cell, reinterpret_cast<const double *>(capbuf._data()), (uint32_t)capbuf.length(), fc_requested,
+                             fc_programmed, fs_programmed, &f, c2, n_occ));
+    if (C) *C = std::complex<double>(c2[0], c2[1]);
+    return f;
+  }
 
   // include/searcher.h:22-41
   void xcorr_pss(const cn::cvec &capbuf, const cn::vec &f_search_set, unsigned char ds_comb_arm, double fc_requested,

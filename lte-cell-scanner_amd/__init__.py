@@ -53,8 +53,10 @@ def new_cell(**kw) -> LcsCell:
 
 def f_search_set_for(freq_start: float, ppm: float, step: float = 5e3) -> np.ndarray:
     """Frequency-offset grid of the CLI (src/CellSearch.cpp:463-464); step = 5e3 is the reference's grid exactly.
-    A TDD search (Searcher.set_duplex) needs step <= 4e3: its PSS/SSS frequency estimate is unambiguous within +- 2330 Hz
-    (normal CP) / +- 2000 Hz (extended) of the hypothesis only (include/lcs.h: lcs_set_duplex); host/CellSearch -x tdd uses 2.5e3."""
+    A TDD search (Searcher.set_duplex) needs step <= 4e3: its PSS/SSS frequency estimate is by itself unambiguous within +- 2330 Hz
+    (normal CP) / +- 2000 Hz (extended) of the hypothesis only (include/lcs.h: lcs_set_duplex); host/CellSearch -x tdd uses 2.5e3.
+    With Searcher.set_foe_unwrap(True) the estimate is unwrapped by a PSS-only one and TDD takes step = 5e3 as well: half the
+    hypotheses for the same coverage (host/CellSearch -x tdd --foe-unwrap)."""
     n_extra = int(np.floor((freq_start * ppm / 1e6 + step / 2) / step))
     return np.arange(-n_extra, n_extra + 1) * float(step)
 
@@ -371,6 +373,29 @@ class Searcher:
         d = C.c_int(-1)
         self._chk(self._lib.lcs_get_duplex(self._h, C.byref(d)), "lcs_get_duplex")
         return d.value
+
+    def set_foe_unwrap(self, on: bool):
+        """pss_sss_foe unwrapped by a PSS-only coarse estimate, for every call on this searcher (lcs_set_foe_unwrap, include/lcs.h):
+        the native estimate aliases by whole periods fs / pss_sss_dist -- 4660 / 4000 Hz in TDD --, and the phase between the two
+        halves of the PSS picks the period.  With it a TDD band is searched on the reference's 5 kHz grid.  Off by default (every
+        record is then what it was, bit for bit); refused while a stream is open."""
+        self._chk(self._lib.lcs_set_foe_unwrap(self._h, 1 if on else 0), "lcs_set_foe_unwrap")
+
+    @property
+    def foe_unwrap(self) -> bool:
+        d = C.c_int(-1)
+        self._chk(self._lib.lcs_get_foe_unwrap(self._h, C.byref(d)), "lcs_get_foe_unwrap")
+        return d.value != 0
+
+    def pss_foe_coarse(self, cell, capbuf, fc_requested, fc_programmed, fs_programmed):
+        """The coarse estimate as a stage of its own (lcs_pss_foe_coarse), in the searcher's duplex mode and whatever the unwrap
+        setting -> (f_coarse in Hz relative to cell.freq, C, occurrences summed)"""
+        cap = np.ascontiguousarray(capbuf, np.complex128)
+        f, c2, n = C.c_double(0.0), (C.c_double * 2)(), C.c_int(0)
+        rc = self._lib.lcs_pss_foe_coarse(self._h, C.byref(cell), _dp(cap), cap.size, fc_requested, fc_programmed, fs_programmed,
+                                          C.byref(f), c2, C.byref(n))
+        self._chk(rc, "lcs_pss_foe_coarse")
+        return f.value, complex(c2[0], c2[1]), n.value
 
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route

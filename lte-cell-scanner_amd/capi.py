@@ -64,7 +64,7 @@ class LcsTrackCell(C.Structure):
 
 
 EXPORTS = [
-    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex",
+    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -109,6 +109,11 @@ def load() -> C.CDLL:
     if hasattr(L, "lcs_set_duplex"):      # (absent from older developer builds loaded through bench.py --lib)
         L.lcs_set_duplex.argtypes = [vp, C.c_int]
         L.lcs_get_duplex.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, "lcs_set_foe_unwrap"):      # (likewise)
+        L.lcs_set_foe_unwrap.argtypes = [vp, C.c_int]
+        L.lcs_get_foe_unwrap.argtypes = [vp, C.POINTER(C.c_int)]
+        L.lcs_pss_foe_coarse.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_double,
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

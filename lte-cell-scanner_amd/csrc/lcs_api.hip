@@ -152,6 +152,7 @@ Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &sr
   L.round_cells = std::min(c->max_work, c->percell_cap);
   L.single_stream = c->st_open;
   L.duplex = c->duplex;
+  L.foe_unwrap = c->foe_unwrap;
   if (c->st_open) { L.tracked = c->st_dtracked; L.n_tracked = c->st_dntracked; }
   return L;
 }
@@ -369,6 +370,22 @@ int lcs_set_duplex(lcs_ctx *c, int duplex) {
 int lcs_get_duplex(const lcs_ctx *c, int *duplex) {
   if (!c || !duplex) return LCS_ERR_BAD_ARG;
   *duplex = c->duplex;
+  return LCS_OK;
+}
+
+int lcs_set_foe_unwrap(lcs_ctx *c, int on) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (on != 0 && on != 1) { c->err = "foe_unwrap is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open && on != c->foe_unwrap) {
+    c->err = "the open stream's captured graph holds the foe_unwrap mode it was opened with: lcs_stream_close first";
+    return LCS_ERR_BAD_ARG;
+  }
+  c->foe_unwrap = on;
+  return LCS_OK;
+}
+int lcs_get_foe_unwrap(const lcs_ctx *c, int *on) {
+  if (!c || !on) return LCS_ERR_BAD_ARG;
+  *on = c->foe_unwrap;
   return LCS_OK;
 }
 
@@ -799,6 +816,31 @@ int lcs_pss_sss_foe(lcs_ctx *c, const lcs_cell *cell_in, const double *capbuf, u
   if ((rc = lcs_launch_foe_only(c, L))) return rc;
   HIPCHK(c, hipMemcpyAsync(cell_out, c->peaks, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+// The coarse estimate alone: the work list and k_foe_fin_unwrap in its read-back form -- no native estimate, no write to the record.
+int lcs_pss_foe_coarse(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint32_t n_cap, double fc_req, double fc_prog,
+                       double fs_prog, double *f_coarse, double *c_re_im, int *n_occ) {
+  if (!c || !cell || !f_coarse) return LCS_ERR_BAD_ARG;
+  if (n_ofdm_for(cell) < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
+    c->err = "pss_foe_coarse needs a cell with n_id_1, n_id_2 and a known cp_type";      // as lcs_pss_sss_foe: it shares its geometry
+    return LCS_ERR_BAD_ARG;
+  }
+  int rc;
+  Launch L;
+  if ((rc = upload_cap_and_params(c, capbuf, n_cap, fc_req, fc_prog, fs_prog, &L))) return rc;
+  if ((rc = c->foe_coarse.reserve(c, 4))) return rc;
+  const int one = 1;
+  double out[4] = {0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(c->peaks, cell, sizeof(lcs_cell), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->npeaks, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = lcs_launch_foe_coarse(c, L, c->foe_coarse))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->foe_coarse, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *f_coarse = out[0];
+  if (c_re_im) { c_re_im[0] = out[1]; c_re_im[1] = out[2]; }
+  if (n_occ) *n_occ = (int)out[3];
   return LCS_OK;
 }
 

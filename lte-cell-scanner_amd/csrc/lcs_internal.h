@@ -189,6 +189,7 @@ struct Launch {
   const int16_t *tracked = nullptr;     // identities k_gather_work leaves out (the streaming mode's tracked list), null: no filter
   const int *n_tracked = nullptr;
   int duplex = LCS_DUPLEX_FDD;          // lcs_set_duplex: where the SSS lies relative to the PSS (sss_foe.hip: the Dx table)
+  int foe_unwrap = 0;                   // lcs_set_foe_unwrap: pss_sss_foe unwrapped by the PSS-only coarse estimate (foe_coarse.h)
 };
 // The last enqueued batch: lcs_batch_collect (its late per-cell rounds), lcs_batch_readback and lcs_last_batch_stats read it.
 struct BatchRecord {
@@ -340,6 +341,8 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<double> d_dbg;             // debug outputs of the single-cell stage entry points
   DevBuf<int> d_flag;               // exactness verdict of k_ingest_c128
   int duplex = LCS_DUPLEX_FDD;      // lcs_set_duplex: copied into every Launch by make_launch, read by nothing else
+  int foe_unwrap = 0;               // lcs_set_foe_unwrap: likewise
+  DevBuf<double> foe_coarse;        // [4]: what lcs_pss_foe_coarse reads back (k_foe_fin_unwrap)
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -480,6 +483,7 @@ int lcs_launch_foe_unpack(lcs_ctx *c, const Launch &L, const long long *d_words,
 int lcs_launch_sss_foe(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg /*device, nullable*/);
 int lcs_launch_sss_only(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, double *dbg);
 int lcs_launch_foe_only(lcs_ctx *c, const Launch &L);
+int lcs_launch_foe_coarse(lcs_ctx *c, const Launch &L, double *coarse /*device, 4: f_coarse, C.re, C.im, occurrences*/);
 // tfg_mib.hip
 int lcs_launch_gather_work(lcs_ctx *c, const Launch &L, int skip /* cells already handled by earlier rounds */);
 __host__ __device__ static inline size_t lcs_pack_rec_offset(int n_buf) { return ((size_t)(8 + n_buf) * sizeof(int) + 63) & ~(size_t)63; }

@@ -15,7 +15,9 @@
 //   k_sss_ml     one workgroup per peak: even/odd combining in the reference's k order, the
 //                168 x 2 x 2 ML search and the decision;
 //   k_foe_win    one workgroup per (peak, occurrence): PSS and SSS windows, per-occurrence FOE term;
-//   k_foe_fin    one thread per peak: sum the terms in occurrence order -> freq_fine.
+//   k_foe_fin    one thread per peak: sum the terms in occurrence order -> freq_fine;
+//   k_foe_fin_unwrap  in its place with lcs_set_foe_unwrap: one workgroup per peak, the PSS-only coarse estimate (foe_coarse.h)
+//                and freq_fine unwrapped by it.
 // Every workgroup needs < 8 KB of LDS (k_sss_ml 17 KB) and at most 4 waves, so they can also be
 // placed next to resident correlation workgroups of the following batch.
 #include "lcs_internal.h"
@@ -24,6 +26,7 @@
 #define MAX_HF 20
 
 #include "lte_device.h"
+#include "foe_coarse.h"
 
 __device__ __forceinline__ int d_floor_i(double x) { return (int)floor(x); }
 __device__ __forceinline__ double d_matlab_mod(double k, double n) { return (n == 0) ? k : (k - n * d_floor_i(k / n)); }
@@ -539,9 +542,89 @@ __global__ __launch_bounds__(64) void k_foe_fin(lcs_cell *__restrict__ peaks, co
   cell_p->freq_fine = cell.freq + atan2(M.im, M.re) / (2 * M_PI) / (1 / (p.fs_prog * g.k_factor) * g.pss_sss_dist);
 }
 
+// ------------------------------------------------------------------ pss_sss_foe unwrapped (lcs_set_foe_unwrap; foe_coarse.h)
+// Takes k_foe_fin's place when the mode is on, so the per-peak tail has as many launches as without it: one workgroup per peak, one
+// wave per occurrence (k = wave, wave + 4, ...).  A wave holds the 128 samples of the PSS's useful part two per lane (t = lane and
+// lane + 64), rotates them to the hypothesis -- one cis per lane and PEAK: the factor depends on t alone, and the second half's is the
+// first's times the square of lane 32's --, multiplies by the conjugate template and reduces each half across the lanes in the fixed
+// order of foe_half_sum_wave (the host twin runs the same tree, foe_half_sum); conj(A) B goes to LDS.  Thread 0 then sums both kinds
+// of terms in occurrence order and decides.  A wave's loads are all issued before the first reduction.  Nothing is written outside
+// the cell's freq_fine (or `coarse`), no workspace record is touched.
+// coarse != null: the stage entry point of the coarse estimate alone (item 0: f_coarse, C.re, C.im, occurrences); the native terms
+// are not read (k_foe_win has not run) and the cell record is left alone.
+#define FU_WAVES 4
+#define FU_THREADS (64 * FU_WAVES)
+#define FU_PER_WAVE ((MAX_HF + FU_WAVES - 1) / FU_WAVES)
+template <int KIND>
+__global__ __launch_bounds__(FU_THREADS) void k_foe_fin_unwrap(lcs_cell *__restrict__ peaks, const WorkItem *__restrict__ items,
+                                                               const int *__restrict__ n_items, const CapSrc src, uint32_t n_cap,
+                                                               const SlotParams *__restrict__ params, const double2 *__restrict__ pss_td,
+                                                               const double *__restrict__ ws, int duplex, double *__restrict__ coarse) {
+  LCS_TAIL_PRIO();
+  __shared__ cd2 term[MAX_HF];
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (int it = blockIdx.x; it < *n_items; it += gridDim.x) {      // workgroup-uniform, and so is everything that leaves the loop early
+    const int slot = items[it].slot;
+    lcs_cell *cell_p = peaks + (size_t)slot * LCS_MAXP + items[it].peak;
+    const lcs_cell cell = *cell_p;
+    const SlotParams p = params[slot];
+    const FoeGeo g = foe_geometry(cell, p, n_cap, duplex);
+    if (!g.ok) continue;
+    const CapView cap = cap_view(src, slot);
+    typename CapKind<KIND>::T raw0[FU_PER_WAVE], raw1[FU_PER_WAVE];
+    bool in0[FU_PER_WAVE], in1[FU_PER_WAVE];
+#pragma unroll
+    for (int j = 0; j < FU_PER_WAVE; ++j) {
+      const int k = wv + FU_WAVES * j;
+      // the PSS DFT window of k_foe_win starts 2 samples earlier, inside the cyclic prefix; n_sss's range rule keeps pss + 127 <= n_cap - 98
+      const long pss = (long)(uint32_t)d_round_i(g.first_sss + k * g.step) + g.pss_sss_dist + 2;
+      const long i0 = pss + lane, i1 = pss + FOE_HALF + lane;
+      in0[j] = k < g.n_sss && i0 >= 0 && (uint64_t)i0 < n_cap;
+      in1[j] = k < g.n_sss && i1 >= 0 && (uint64_t)i1 < n_cap;
+      raw0[j] = CapKind<KIND>::of(cap)[in0[j] ? (size_t)i0 : 0];
+      raw1[j] = CapKind<KIND>::of(cap)[in1[j] ? (size_t)i1 : 0];
+    }
+    const double2 *tp = pss_td + cell.n_id_2 * 137 + 9;             // the template behind its 9-sample cyclic prefix
+    const double2 p0 = tp[lane], p1 = tp[FOE_HALF + lane];
+    const cd2 r0 = cis_call(g.kph * (double)lane);
+    const cd2 r32 = mk(__shfl(r0.re, 32), __shfl(r0.im, 32));
+    const cd2 r1 = cmul(r0, cmul(r32, r32));
+#pragma unroll
+    for (int j = 0; j < FU_PER_WAVE; ++j) {
+      const int k = wv + FU_WAVES * j;
+      if (k >= g.n_sss) break;                                       // wave-uniform
+      const double2 v0 = CapKind<KIND>::cvt(raw0[j]), v1 = CapKind<KIND>::cvt(raw1[j]);
+      const cd2 a = foe_half_sum_wave(foe_halves_z(in0[j] ? mk(v0.x, v0.y) : mk(0, 0), r0, mk(p0.x, p0.y)));
+      const cd2 b = foe_half_sum_wave(foe_halves_z(in1[j] ? mk(v1.x, v1.y) : mk(0, 0), r1, mk(p1.x, p1.y)));
+      if (lane == 0) term[k] = foe_halves_term(a, b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      cd2 C = mk(0, 0);
+      for (int k = 0; k < g.n_sss; ++k) C = cadd(C, term[k]);         // occurrence order, unweighted
+      const double fs = p.fs_prog * g.k_factor;
+      const double f_coarse = foe_coarse_hz(C, fs);
+      if (coarse) {
+        if (it == 0) { coarse[0] = f_coarse; coarse[1] = C.re; coarse[2] = C.im; coarse[3] = (double)g.n_sss; }
+      } else {
+        cd2 M = mk(0, 0);
+        for (int k = 0; k < g.n_sss; ++k) {
+          const double *rec = ws + (size_t)it * SW_ITEM + (size_t)k * SW_REC;
+          M = cadd(M, mk(rec[SW_ACC], rec[SW_ACC + 1]));
+        }
+        const double native = cell.freq + atan2(M.im, M.re) / (2 * M_PI) / (1 / (p.fs_prog * g.k_factor) * g.pss_sss_dist);      // k_foe_fin's expression
+        cell_p->freq_fine = foe_unwrap(native, cell.freq, f_coarse, fs, g.pss_sss_dist, foe_coarse_usable(C, g.n_sss));
+      }
+    }
+    __syncthreads();                                                 // the terms are rewritten by the workgroup's next peak
+  }
+}
+
 // ------------------------------------------------------------------ launchers
-// mode bit 0: run sss_detect, bit 1: run pss_sss_foe (only for cells whose SSS was found)
-static int run_sss_foe(lcs_ctx *c, const Launch &L, double thresh2, int mode, double *dbg) {
+// mode bit 0: run sss_detect, bit 1: run pss_sss_foe (only for cells whose SSS was found); coarse: the stage entry point of the
+// PSS-only estimate -- that estimate alone, whatever the launch's mode, read back through `coarse`
+static int run_sss_foe(lcs_ctx *c, const Launch &L, double thresh2, int mode, double *dbg, double *coarse = nullptr) {
   const int n_buf = L.n_buf;
   const uint32_t n_cap = L.n_cap;
   const size_t cap_items = (size_t)n_buf * LCS_MAXP;
@@ -567,12 +650,19 @@ static int run_sss_foe(lcs_ctx *c, const Launch &L, double thresh2, int mode, do
                        L.params, thresh2, c->d_sss_fd, c->sss_ws, dbg, L.duplex);
   }
   if (mode & 2) {
-    lcs_by_cap_kind(src, [&](auto kind) {
-      hipLaunchKernelGGL(k_foe_win<decltype(kind)::value>, dim3((int)std::min<size_t>((cap_items * FW_QUADS + 3) / 4, LCS_WIN_GRID)), dim3(FW_THREADS), 0, c->stream,
-                         c->peaks, c->pk_items, c->n_pk, src, n_cap, L.params, c->d_pss_fd, c->d_sss_fd, c->sss_ws, L.duplex);
-    });
-    hipLaunchKernelGGL(k_foe_fin, dim3((unsigned)((cap_items + 63) / 64)), dim3(64), 0, c->stream, c->peaks, c->pk_items,
-                       c->n_pk, n_cap, L.params, c->sss_ws, L.duplex);
+    if (!coarse)
+      lcs_by_cap_kind(src, [&](auto kind) {
+        hipLaunchKernelGGL(k_foe_win<decltype(kind)::value>, dim3((int)std::min<size_t>((cap_items * FW_QUADS + 3) / 4, LCS_WIN_GRID)), dim3(FW_THREADS), 0, c->stream,
+                           c->peaks, c->pk_items, c->n_pk, src, n_cap, L.params, c->d_pss_fd, c->d_sss_fd, c->sss_ws, L.duplex);
+      });
+    if (L.foe_unwrap || coarse)
+      lcs_by_cap_kind(src, [&](auto kind) {
+        hipLaunchKernelGGL(k_foe_fin_unwrap<decltype(kind)::value>, dim3(item_grid), dim3(FU_THREADS), 0, c->stream, c->peaks, c->pk_items, c->n_pk, src,
+                           n_cap, L.params, c->d_pss_td, c->sss_ws, L.duplex, coarse);
+      });
+    else
+      hipLaunchKernelGGL(k_foe_fin, dim3((unsigned)((cap_items + 63) / 64)), dim3(64), 0, c->stream, c->peaks, c->pk_items,
+                         c->n_pk, n_cap, L.params, c->sss_ws, L.duplex);
   }
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
@@ -586,3 +676,4 @@ int lcs_launch_sss_only(lcs_ctx *c, const Launch &L, double thresh2_n_sigma, dou
   return run_sss_foe(c, L, thresh2_n_sigma, 1, dbg);
 }
 int lcs_launch_foe_only(lcs_ctx *c, const Launch &L) { return run_sss_foe(c, L, 0.0, 2, nullptr); }
+int lcs_launch_foe_coarse(lcs_ctx *c, const Launch &L, double *coarse) { return run_sss_foe(c, L, 0.0, 2, nullptr, coarse); }

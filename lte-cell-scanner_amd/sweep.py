@@ -105,7 +105,8 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     (Searcher.channelize_u8: every carrier scaled by a power of two of its own, component rms 16..32 codes) and hands the
     chunks over as FMT_IQ_U8 batches, which take the int8 correlation kernel and a quarter of the memory; a byte batch takes
     any n_cap, so with a rate n_out is then all the capture holds, odd or even.  The search runs in the searcher's duplex mode
-    (Searcher.set_duplex: one capture covers one band, and a band has one duplex; a TDD band wants f_search_set in 2.5 kHz steps).
+    (Searcher.set_duplex: one capture covers one band, and a band has one duplex; a TDD band wants f_search_set in 2.5 kHz steps,
+    or Searcher.set_foe_unwrap(True) and the usual 5 kHz).
     Returns one list of cells (LcsCell)
     per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's."""
     import torch
@@ -149,7 +150,8 @@ class WidebandFeed:
     the next capture goes to; filled stays 0, the capture in hand lives in the library), and `gains` is the float32 [n_ch] device
     tensor of the last finished capture's gains (None before the first), read without synchronising: records_with_gain(cells, feed.gains)
     puts the cells of its carriers on one power scale.
-    The captures are searched in the searcher's duplex mode (Searcher.set_duplex), as search_wideband's are."""
+    The captures are searched in the searcher's duplex and frequency-estimate modes (Searcher.set_duplex, set_foe_unwrap), as
+    search_wideband's are."""
 
     def __init__(self, searcher, fmt: int, fs_in: float, rate, fc_centre: float, carriers, f_search_set, n_cap: int = 153600,
                  max_cells_per_buf: int = 16, out: str = "c64"):
