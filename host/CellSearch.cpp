@@ -63,6 +63,7 @@ struct Options {
   long batch = 64;               // carriers per GPU batch (one correlation launch)
   int duplex = LCS_DUPLEX_FDD;   // -x: the band's duplex mode, set on every context
   bool foe_unwrap = false;       // -u: pss_sss_foe unwrapped by the PSS-only coarse estimate (lcs_set_foe_unwrap), set on every context
+  bool tdd_config = false;       // -T: estimate every TDD cell's uplink-downlink configuration (lcs_set_tdd_config) and add it to the report
   int verbosity = 1;
 };
 
@@ -83,6 +84,7 @@ const OptSpec kSpecs[] = {
     {'B', "batch", INDEX, "batch size", {"carriers searched per GPU batch (default 64)", 0}},
     {'x', "duplex", TEXT, 0, {"duplex mode of the band, fdd (default) or tdd (bands 33-53: SSS three symbols before the PSS; the frequency grid is then 2.5 kHz)", 0}},
     {'u', "foe-unwrap", FLAG, 0, {"unwrap the PSS/SSS frequency estimate with a PSS-only one: a tdd search then keeps the 5 kHz frequency grid (half the hypotheses)", 0}},
+    {'T', "tdd-config", FLAG, 0, {"with -x tdd: estimate each cell's uplink-downlink configuration and DwPTS class from its reference signals; two more columns in the report", 0}},
     {'s', "freq-start", REAL, "start frequency", {"frequency where cell search should start", 0}},
     {'e', "freq-end", REAL, "end frequency", {"frequency where cell search should end", 0}},
     {'p', "ppm", REAL, "ppm value", {"crystal remaining PPM error", 0}},
@@ -97,7 +99,7 @@ void usage() {
   std::cout << "LTE CellSearch v" << VERSION_STRING << " (MI355X) help screen\n\n"
             << "CellSearch -s start_frequency [optional_parameters]\n";
   const struct { const char *title; const char *letters; } sections[] = {
-      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexu"}, {"Dongle LO correction options:", "pc"},
+      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexuT"}, {"Dongle LO correction options:", "pc"},
       {"Capture buffer save/ load options:", "rld"}};
   for (const auto &sec : sections) {
     std::cout << "  " << sec.title << "\n";
@@ -125,6 +127,7 @@ void store(Options &o, const OptSpec &s, const char *value) {
       else if (s.letter == 'b') o.verbosity = 0;
       else if (s.letter == 'r') o.record = true;
       else if (s.letter == 'u') o.foe_unwrap = true;
+      else if (s.letter == 'T') o.tdd_config = true;
       else o.load = true;
       return;
     case TEXT:
@@ -254,11 +257,15 @@ Capture read_capture(const std::string &path, double fc_expected) {
 // The reference's rule (src/CellSearch.cpp:285-319): walk the carriers in order; a cell is the same as an earlier one
 // when the identity matches and the two true centre frequencies lie within 1 MHz; of the two, the stronger PSS
 // stays, in the earlier one's place in the list.
-std::vector<Cell> merge_duplicates(const std::vector<std::list<Cell> > &per_carrier) {
+// origin (if asked): for every kept cell the carrier it was found on and its place in that carrier's list
+std::vector<Cell> merge_duplicates(const std::vector<std::list<Cell> > &per_carrier, std::vector<std::pair<int, int> > *origin = 0) {
   std::vector<Cell> kept;
   std::multimap<int, size_t> by_identity;                    // n_id_cell -> positions in `kept`, in insertion order
-  for (const std::list<Cell> &found : per_carrier)
+  for (size_t fci = 0; fci < per_carrier.size(); ++fci) {
+    const std::list<Cell> &found = per_carrier[fci];
+    int pos = -1;
     for (const Cell &c : found) {
+      ++pos;
       const double f_true = c.fc_requested + c.freq_superfine;
       size_t twin = kept.size();
       const auto range = by_identity.equal_range(c.n_id_cell());
@@ -267,10 +274,13 @@ std::vector<Cell> merge_duplicates(const std::vector<std::list<Cell> > &per_carr
       if (twin == kept.size()) {
         by_identity.insert(std::make_pair(c.n_id_cell(), kept.size()));
         kept.push_back(c);
+        if (origin) origin->push_back(std::make_pair((int)fci, pos));
       } else if (c.pss_pow > kept[twin].pss_pow) {
         kept[twin] = c;
+        if (origin) (*origin)[twin] = std::make_pair((int)fci, pos);
       }
     }
+  }
   return kept;
 }
 
@@ -294,6 +304,12 @@ std::string table_row(const Cell &c, double correction) {
          (c.phich_resource >= 0 && c.phich_resource <= 4 ? pr[c.phich_resource] : "") + " " + num(correction_new, 20);
 }
 
+// --tdd-config: the uplink-downlink configuration (0..6) and the DwPTS class (1..4 reference rows), "-" where there is no estimate
+std::string tdd_columns(const lcs_tdd_info &t) {
+  auto col = [](int v) { return v >= 0 ? fmt(" %2d", v) : std::string("  -"); };
+  return col(t.ul_dl_config) + col(t.dwpts_rs_rows);
+}
+
 void announce(const std::list<Cell> &cells) {
   for (const Cell &c : cells)
     std::cout << "  Detected a cell!\n    cell ID: " << c.n_id_cell() << "\n    RX power level: " << num(db10(c.pss_pow))
@@ -312,6 +328,7 @@ struct Sweep {
   double fs_programmed;
   int n_fc, n_batches;
   std::vector<std::list<Cell> > detected;
+  std::vector<std::vector<lcs_tdd_info> > tdd;       // --tdd-config: per carrier, one record per detected cell
   std::vector<char> fc_matches, batched;
   std::vector<char> batch_done;
   std::string failure;
@@ -341,7 +358,8 @@ struct InFlight {
 void device_thread(Sweep *sw, int device, int first_batch, int stride) {
   try {
     std::unique_ptr<lcs::Searcher> ctx[2];
-    for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); ctx[k]->set_duplex(sw->opt.duplex); ctx[k]->set_foe_unwrap(sw->opt.foe_unwrap); }
+    auto configure = [&](lcs::Searcher &s) { s.set_duplex(sw->opt.duplex); s.set_foe_unwrap(sw->opt.foe_unwrap); if (sw->opt.tdd_config) s.set_tdd_config(true); };
+    for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); configure(*ctx[k]); }
     std::unique_ptr<lcs::Searcher> one;                     // for captures that are not raw dongle bytes
     unsigned char *pinned[2] = {0, 0};
     size_t pinned_bytes[2] = {0, 0};
@@ -353,14 +371,23 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
         std::vector<std::list<Cell> > found;
         ctx[slot]->collect_batch(found);
         if (ctx[slot]->last_batch_overflowed()) std::cerr << "Warning: more cells than the result arrays hold; list truncated" << std::endl;
+        if (sw->opt.tdd_config) {
+          const std::vector<lcs_tdd_info> info = ctx[slot]->last_tdd_info((int)f.carriers.size(), LCS_MAX_PEAKS);
+          for (size_t j = 0; j < f.carriers.size(); ++j)
+            sw->tdd[f.carriers[j]].assign(info.begin() + j * LCS_MAX_PEAKS, info.begin() + j * LCS_MAX_PEAKS + found[j].size());
+        }
         for (size_t j = 0; j < f.carriers.size(); ++j) sw->detected[f.carriers[j]].swap(found[j]);
       }
       for (size_t j = 0; j < f.singles.size(); ++j) {
-        if (!one) { one.reset(new lcs::Searcher(device)); one->set_duplex(sw->opt.duplex); one->set_foe_unwrap(sw->opt.foe_unwrap); }
+        if (!one) { one.reset(new lcs::Searcher(device)); configure(*one); }
         const double fc = sw->opt.freq_start + 100e3 * f.single_carriers[j];
         lcsc::cvec capbuf((int)f.singles[j].samples.size());
         std::memcpy(capbuf._data(), f.singles[j].samples.data(), f.singles[j].samples.size() * sizeof(std::complex<double>));
         one->search_capbuf(capbuf, sw->f_search_set, fc, fc, sw->fs_programmed, sw->detected[f.single_carriers[j]]);
+        if (sw->opt.tdd_config) {
+          const std::vector<lcs_tdd_info> info = one->last_tdd_info(1, LCS_MAX_PEAKS);
+          sw->tdd[f.single_carriers[j]].assign(info.begin(), info.begin() + sw->detected[f.single_carriers[j]].size());
+        }
       }
       sw->finish(f.batch);
       f = InFlight();
@@ -455,6 +482,7 @@ int main(int argc, char *const argv[]) {
   sw.kBatch = (int)opt.batch;
   sw.n_batches = (sw.n_fc + sw.kBatch - 1) / sw.kBatch;
   sw.detected.resize(sw.n_fc);
+  sw.tdd.resize(sw.n_fc);
   sw.fc_matches.assign(sw.n_fc, 1);
   sw.batched.assign(sw.n_fc, 0);
   sw.batch_done.assign(sw.n_batches, 0);
@@ -505,14 +533,17 @@ int main(int argc, char *const argv[]) {
     return 2;
   }
 
-  const std::vector<Cell> cells = merge_duplicates(sw.detected);
+  std::vector<std::pair<int, int> > origin;
+  const std::vector<Cell> cells = merge_duplicates(sw.detected, &origin);
   if (cells.empty()) {
     std::cout << "No LTE cells were found..." << std::endl;
   } else {
     std::cout << "Detected the following cells:\n"
               << "A: #antenna ports C: CP type ; P: PHICH duration ; PR: PHICH resource type\n"
-              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor\n";
-    for (const Cell &c : cells) std::cout << table_row(c, opt.correction) << "\n";
+              << (opt.tdd_config ? "UD: uplink-downlink configuration ; DW: DwPTS class (port-0 reference rows in the special subframe)\n" : "")
+              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor" << (opt.tdd_config ? " UD DW" : "") << "\n";
+    for (size_t i = 0; i < cells.size(); ++i)
+      std::cout << table_row(cells[i], opt.correction) << (opt.tdd_config ? tdd_columns(sw.tdd[origin[i].first][origin[i].second]) : std::string()) << "\n";
     std::cout.flush();
   }
   return 0;

@@ -169,6 +169,52 @@ int lcs_get_duplex(const lcs_ctx *ctx, int *duplex);
  * (LCS_ERR_BAD_ARG, an lcs_last_error text) any value other than 0 / 1, and a change while an lcs_stream_open stream is open. */
 int lcs_set_foe_unwrap(lcs_ctx *ctx, int on);
 int lcs_get_foe_unwrap(const lcs_ctx *ctx, int *on);
+/* The uplink-downlink configuration of a TDD cell (36.211 table 4.2-2), estimated from its cell-specific reference signals.  The
+ * configuration is broadcast in SIB1, which a 1.92 Msps searcher cannot read for a cell wider than 6 RB; but CRS are sent in every
+ * downlink subframe and in the DwPTS and never in an uplink subframe, and the chain holds 61 subframes of the grid of every cell
+ * that decoded a MIB.  THE RULE (lte-cell-scanner_amd/csrc/tdd_config.h, host and device), for a cell with n_id_1, n_id_2, cp_type
+ * and a grid tfg[n_ofdm][72] whose row 0 is slot 0 symbol 0 of a frame -- what lcs_extract_tfg delivers for a record behind
+ * lcs_decode_mib.  No frequency or timing correction is applied: a row's frequency correction is a common phase and drops out of
+ * the products below, the timing correction turns every product by one angle and drops out in the projection on ref; the rule
+ * gives the same answer on the raw grid (which the fused chain holds) and on the compensated one.  With n_symb = 7 / 6:
+ *   rows used   r with sym = r mod n_symb in {0, n_symb - 3}: port 0's reference symbols.  slot = (r / n_symb) mod 20, s = slot / 2,
+ *               j = 2 (slot & 1) + (sym != 0)
+ *   per row     h_m = tfg[r][shift + 6 m] conj(rs[m]), m = 0 .. 11 (shift, rs: RS_DL of (slot, sym, port 0));
+ *               c_r = sum_{m = 0 .. 10} h_m conj(h_{m+1})
+ *   per bin     C[s][j] = sum of c_r in row order, N[s][j] = rows;  C[s] = sum_j C[s][j], N[s] = sum_j N[s][j]
+ *   statistic   ref = C[0] + C[5], n_ref = N[0] + N[5] (subframes 0 and 5 are downlink in every configuration);
+ *               T[s] = Re(C[s] conj(ref)) / |ref|^2  n_ref / N[s]      ~ 1 with CRS, ~ 0 without, whatever the uplink carries
+ *   decision    subframe s is downlink iff T[s] > 1/2.  The pattern over s = (3, 4, 7, 8, 9) names the configuration:
+ *               UUUUU 0, UDUUD 1, DDUDD 2, UUDDD 3, UDDDD 4, DDDDD 5, UUUUD 6; any other pattern gives -1, and so does a subframe 2
+ *               that reads downlink (it is uplink in every configuration: a grid that is no TDD frame gets no number)
+ *   margin      min |T[s] - 1/2| over s = 2, 3, 4, 7, 8, 9
+ *   DwPTS       R[j] = Re((C[1][j] (+ C[6][j])) conj(ref)) / |ref|^2  n_ref / (N[1][j] (+ N[6][j])), subframe 6 joining only where
+ *               the configuration found has it special (0, 1, 2, 6); row j is present iff R[j] > 1/2; dwpts_rs_rows = the number of
+ *               rows present if they are a prefix that starts with row 0, else -1 (and -1 without a configuration):
+ *                 1: DwPTS of 3 symbols (either CP)   2: 6 (normal CP) / 5 (extended)   3: 9-11 / 8-9   4: 12 / 10
+ *   no decision when ref is zero or not finite, a subframe has no row, or a T is not finite: configuration -1, margin 0.
+ * WHAT IT CANNOT SEE: the special-subframe configuration beyond these four DwPTS classes (GP and UpPTS carry no CRS), and anything
+ * at all for a cell that decodes no MIB -- its records read LCS_TDD_NOT_ESTIMATED in both integer fields.
+ * lcs_set_tdd_config(ctx, 1) makes every fused call of a context in LCS_DUPLEX_TDD run the rule, once per per-cell round behind
+ * the MIB decode, on the device (one kernel, k_tdd_config): lcs_search_capbuf and the batch entry points (device and host, enqueue
+ * and collect: a batch keeps the mode it was enqueued with).  After any of them lcs_last_tdd_info hands out one record
+ * per cell: info[b * max_cells_per_buf + k] belongs to cells[b][k] of that call (b = 0 for lcs_search_capbuf); entries beyond a
+ * buffer's cells, and every entry after a call with the mode off or in FDD, read LCS_TDD_NOT_ESTIMATED.  It waits for the context's
+ * stream.  lcs_cell does not change.  Off by default, context-wide; with the mode off, or in FDD, every record and every array is
+ * what it was before the mode existed, bit for bit, and no additional kernel is launched.  The streaming mode does not carry the
+ * estimate yet: lcs_stream_open refuses (LCS_ERR_BAD_ARG, an lcs_last_error text) a context with the mode on, and
+ * lcs_set_tdd_config refuses a change while a stream is open, and any value other than 0 / 1. */
+typedef struct lcs_tdd_info {
+  int32_t ul_dl_config;   /* 0 .. 6, -1: no configuration fits, LCS_TDD_NOT_ESTIMATED */
+  int32_t dwpts_rs_rows;  /* 1 .. 4, -1, LCS_TDD_NOT_ESTIMATED */
+  double margin;
+  double T[10];
+  double R[4];
+} lcs_tdd_info;           /* 128 bytes */
+#define LCS_TDD_NOT_ESTIMATED (-2)
+int lcs_set_tdd_config(lcs_ctx *ctx, int on);
+int lcs_get_tdd_config(const lcs_ctx *ctx, int *on);
+int lcs_last_tdd_info(lcs_ctx *ctx, lcs_tdd_info *info, int max_cells_per_buf);
 
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
@@ -241,6 +287,13 @@ int lcs_decode_mib(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, 
  * reference's searcher.cpp (not in searcher.h); exported so that it can be tested directly. */
 int lcs_chan_est(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, int n_ofdm, int port,
                  double *ce_tfg_re_im /*[n_ofdm][72]*/, double *np);
+
+/* The uplink-downlink configuration of a TDD cell as a stage of its own (the rule: lcs_set_tdd_config above), whatever the
+ * context's modes: the grid of lcs_extract_tfg, raw or compensated, of a cell with n_id_1, n_id_2 and a CP type.  n_ofdm may be
+ * any number of rows from two frames (280 normal CP / 240 extended) to LCS_TFG_MAX_OFDM; a partial last slot counts with the
+ * rows it has.  Refuses (LCS_ERR_BAD_ARG, an lcs_last_error text) a cell without identity or CP type and an n_ofdm outside that
+ * range. */
+int lcs_tdd_config(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, int n_ofdm, lcs_tdd_info *out);
 
 /* ---- fused chain ------------------------------------------------------------------- */
 

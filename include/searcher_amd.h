@@ -78,6 +78,26 @@ class Searcher {
     return f;
   }
 
+  // The uplink-downlink configuration of the TDD cells a fused call decodes, from their reference signals (lcs_set_tdd_config: it
+  // takes effect in LCS_DUPLEX_TDD only); last_tdd_info: the records of the last search_capbuf (n_buf = 1) or batch,
+  // [n_buf][max_cells_per_buf], entry k of a buffer belonging to its k-th cell, LCS_TDD_NOT_ESTIMATED where nothing was estimated
+  void set_tdd_config(bool on) { check(lcs_set_tdd_config(h_, on ? 1 : 0)); }
+  bool tdd_config_mode() { int on = 0; check(lcs_get_tdd_config(h_, &on)); return on != 0; }
+  std::vector<lcs_tdd_info> last_tdd_info(int n_buf = 1, int max_cells_per_buf = 16) {
+    std::vector<lcs_tdd_info> info((size_t)n_buf * max_cells_per_buf);
+    const int rc = lcs_last_tdd_info(h_, info.data(), max_cells_per_buf);
+    if (rc != LCS_ERR_OVERFLOW) check(rc);
+    return info;
+  }
+  // ... and the estimate as a stage of its own (lcs_tdd_config): a cell with identity and CP type, its grid from extract_tfg
+  lcs_tdd_info tdd_config(const Cell &cell, const cn::cmat &tfg) {
+    std::vector<double> g;
+    to_rows(tfg, g);
+    lcs_tdd_info out;
+    check(lcs_tdd_config(h_, &cell, g.data(), tfg.rows(), &out));
+    return out;
+  }
+
   // include/searcher.h:22-41
   void xcorr_pss(const cn::cvec &capbuf, const cn::vec &f_search_set, unsigned char ds_comb_arm, double fc_requested,
                  double fc_programmed, double fs_programmed, cn::mat &xc_incoherent_collapsed_pow,

@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD
+from .capi import LcsCell, LcsTrackCell, TddInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -64,8 +64,8 @@ def f_search_set_for(freq_start: float, ppm: float, step: float = 5e3) -> np.nda
 class Searcher:
     """One context = one GPU + stream + workspace (lcs_create / lcs_destroy)."""
 
-    def __init__(self, device: int = -1):
-        self._lib = capi.load()
+    def __init__(self, device: int = -1, lib=None):
+        self._lib = lib if lib is not None else capi.load()      # lib: another build from capi.load_other (developer A/B runs)
         h = C.c_void_p()
         rc = self._lib.lcs_create(device, C.byref(h))
         if rc != 0:
@@ -396,6 +396,36 @@ class Searcher:
                                           C.byref(f), c2, C.byref(n))
         self._chk(rc, "lcs_pss_foe_coarse")
         return f.value, complex(c2[0], c2[1]), n.value
+
+    def set_tdd_config(self, on: bool):
+        """Estimate the uplink-downlink configuration (36.211 table 4.2-2) and the DwPTS class of every cell a fused call decodes,
+        from its reference signals on the device (lcs_set_tdd_config, include/lcs.h); last_tdd_info() reads the records.  It takes
+        effect in DUPLEX_TDD only.  Off by default (every record is then what it was, bit for bit); refused while a stream is open,
+        and stream_open is refused while it is on."""
+        self._chk(self._lib.lcs_set_tdd_config(self._h, 1 if on else 0), "lcs_set_tdd_config")
+
+    @property
+    def tdd_config_mode(self) -> bool:
+        d = C.c_int(-1)
+        self._chk(self._lib.lcs_get_tdd_config(self._h, C.byref(d)), "lcs_get_tdd_config")
+        return d.value != 0
+
+    def tdd_config(self, cell, tfg):
+        """The estimate as a stage of its own (lcs_tdd_config): a cell with identity and CP type and its grid from extract_tfg, raw
+        or compensated, two frames to 854 rows -> TddInfo"""
+        tfg = np.ascontiguousarray(tfg, np.complex128)
+        out = capi.TddInfo()
+        self._chk(self._lib.lcs_tdd_config(self._h, C.byref(cell), _dp(tfg), tfg.shape[0], C.byref(out)), "lcs_tdd_config")
+        return out
+
+    def last_tdd_info(self, n_buf: int = 1, max_cells_per_buf: int = 16):
+        """The records of the last search_capbuf (n_buf = 1) or batch: per buffer a list of max_cells_per_buf TddInfo, entry k
+        belonging to cell k of that buffer; the entries behind a buffer's cells, and all of them without the mode, read
+        TDD_NOT_ESTIMATED (lcs_last_tdd_info)."""
+        info = (capi.TddInfo * (n_buf * max_cells_per_buf))()
+        rc = self._lib.lcs_last_tdd_info(self._h, info, max_cells_per_buf)
+        self._note_overflow(self._chk(rc, "lcs_last_tdd_info", allow_overflow=True), "lcs_last_tdd_info")
+        return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
 
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route

@@ -17,6 +17,7 @@ FMT_IQ_S8, FMT_IQ_S16 = 3, 4                # wideband captures of lcs_channeliz
 STAGE_PSS, STAGE_FULL = 1, 3
 MAX_PEAKS = 104            # LCS_MAX_PEAKS: the longest list peak_search can return (include/lcs.h)
 DUPLEX_FDD, DUPLEX_TDD = 0, 1      # LCS_DUPLEX_*: where the SSS lies relative to the PSS (include/lcs.h: lcs_set_duplex)
+TDD_NOT_ESTIMATED = -2     # LCS_TDD_NOT_ESTIMATED: a record of lcs_last_tdd_info that belongs to no decoded cell, or to a call without the mode
 ERRORS = {-1: "LCS_ERR_NO_DEVICE", -2: "LCS_ERR_BAD_ARG", -3: "LCS_ERR_HIP", -4: "LCS_ERR_OVERFLOW", -5: "LCS_ERR_NOMEM"}
 
 
@@ -63,8 +64,29 @@ class LcsTrackCell(C.Structure):
                 ("bulk_phase_offset", C.c_double)]
 
 
+class TddInfo(C.Structure):
+    """lcs_tdd_info: the uplink-downlink configuration of a TDD cell as its reference signals show it (include/lcs.h:
+    lcs_set_tdd_config).  ul_dl_config 0..6 or -1, dwpts_rs_rows 1..4 or -1 (both TDD_NOT_ESTIMATED where nothing was estimated),
+    margin = the smallest distance of a deciding T from 1/2, T per subframe, R per reference row of the special subframe."""
+    _fields_ = [("ul_dl_config", C.c_int32), ("dwpts_rs_rows", C.c_int32), ("margin", C.c_double), ("T", C.c_double * 10), ("R", C.c_double * 4)]
+
+    def copy(self) -> "TddInfo":
+        o = TddInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(TddInfo))
+        return o
+
+    def as_dict(self) -> dict:
+        return dict(ul_dl_config=self.ul_dl_config, dwpts_rs_rows=self.dwpts_rs_rows, margin=self.margin, T=list(self.T), R=list(self.R))
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"TddInfo(ul_dl_config={self.ul_dl_config}, dwpts_rs_rows={self.dwpts_rs_rows}, margin={self.margin:.3f})"
+
+
+assert C.sizeof(TddInfo) == 128
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
+    "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -94,7 +116,19 @@ def load() -> C.CDLL:
         import torch  # noqa: F401
     except Exception:  # torch is optional plumbing, not a dependency of the C ABI
         pass
-    L = C.CDLL(LIB_PATH)
+    _lib = _declare(C.CDLL(LIB_PATH))
+    return _lib
+
+
+def load_other(path: str) -> C.CDLL:
+    """Another build of liblcs_amd.so beside the in-tree one, in the same process and with the same prototypes (developer A/B runs:
+    tools/bench_tdd_config.py times the parent commit's library call by call against this tree's).  Not cached; hand it to
+    Searcher(device, lib=...)."""
+    load()      # torch's HIP runtime first, as for the in-tree library
+    return _declare(C.CDLL(os.path.abspath(path)))
+
+
+def _declare(L: C.CDLL) -> C.CDLL:
     vp, dp, ip, fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float)
     cp, u16p = C.POINTER(LcsCell), C.POINTER(C.c_uint16)
     L.lcs_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -114,6 +148,11 @@ def load() -> C.CDLL:
         L.lcs_get_foe_unwrap.argtypes = [vp, C.POINTER(C.c_int)]
         L.lcs_pss_foe_coarse.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_double,
                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    if hasattr(L, "lcs_set_tdd_config"):      # (likewise)
+        L.lcs_set_tdd_config.argtypes = [vp, C.c_int]
+        L.lcs_get_tdd_config.argtypes = [vp, C.POINTER(C.c_int)]
+        L.lcs_tdd_config.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_int, C.POINTER(TddInfo)]
+        L.lcs_last_tdd_info.argtypes = [vp, C.POINTER(TddInfo), C.c_int]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,
@@ -195,5 +234,4 @@ def load() -> C.CDLL:
     L.lcs_table_lte_pn.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8)]
     L.lcs_chi2cdf_inv.argtypes = [C.c_double, C.c_double]
     L.lcs_chi2cdf_inv.restype = C.c_double
-    _lib = L
     return L

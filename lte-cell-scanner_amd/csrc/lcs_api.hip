@@ -10,6 +10,7 @@
 #include "lcs_internal.h"
 #include "channelizer.h"
 #include "lte_device.h"
+#include "tdd_config.h"
 #include "pss_ref.h"
 
 namespace {
@@ -153,6 +154,7 @@ Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &sr
   L.single_stream = c->st_open;
   L.duplex = c->duplex;
   L.foe_unwrap = c->foe_unwrap;
+  L.tdd_config = (c->tdd_config && c->duplex == LCS_DUPLEX_TDD) ? 1 : 0;
   if (c->st_open) { L.tracked = c->st_dtracked; L.n_tracked = c->st_dntracked; }
   return L;
 }
@@ -195,12 +197,26 @@ int ensure_stage_ws(lcs_ctx *c, int n_f = 1) { return ensure_ws(c, 1, std::max<u
 
 // The per-peak chain of a launch: sss_detect + pss_sss_foe on every peak (with the first round), then per round of L.round_cells
 // cells the work list, the grids, the frequency / timing correction and the MIB.  Rounds [r0, r1).
+// With L.tdd_config (lcs_set_tdd_config in LCS_DUPLEX_TDD) every round also estimates the uplink-downlink configuration of its cells
+// (k_tdd_config, on the raw grid) into c->tdd_info, a table laid out like the peak table: the first round's call sets every record of
+// it to LCS_TDD_NOT_ESTIMATED (all 32-bit words -2: lcs_last_tdd_info reads the integer fields only of such a record), later rounds
+// -- lcs_batch_collect's among them -- fill in their own cells.
 int launch_per_peak(lcs_ctx *c, const Launch &L, int r0, int r1) {
   int rc;
+  if (r0 == 0) {
+    c->tdd_n_buf = L.n_buf;
+    c->tdd_made = L.tdd_config != 0;
+    if (L.tdd_config) {
+      const size_t n = (size_t)L.n_buf * LCS_MAXP;
+      if (n > c->tdd_info.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+      if ((rc = c->tdd_info.reserve(c, n))) return rc;
+      HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->tdd_info.get()), LCS_TDD_NOT_ESTIMATED, n * (sizeof(lcs_tdd_info) / 4), c->stream));
+    }
+  }
   if (r0 == 0 && (rc = lcs_launch_sss_foe(c, L, 3.0 /* THRESH2_N_SIGMA, ref src/CellSearch.cpp:528 */, nullptr))) return rc;
   for (int r = r0; r < r1; ++r)
     if ((rc = lcs_launch_gather_work(c, L, r * L.round_cells)) || (rc = lcs_launch_tfg(c, L, true)) || (rc = lcs_launch_tfoec(c, L, false)) ||
-        (rc = lcs_launch_mib(c, L, true)))
+        (rc = lcs_launch_mib(c, L, true)) || (L.tdd_config && (rc = lcs_launch_tdd_config(c, L, c->tdd_info, false))))
       return rc;
   return LCS_OK;
 }
@@ -389,6 +405,50 @@ int lcs_get_foe_unwrap(const lcs_ctx *c, int *on) {
   return LCS_OK;
 }
 
+int lcs_set_tdd_config(lcs_ctx *c, int on) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (on != 0 && on != 1) { c->err = "tdd_config is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open && on != c->tdd_config) {
+    c->err = "the streaming mode does not carry the uplink-downlink estimate: the tdd_config mode cannot change under an open stream, lcs_stream_close first";
+    return LCS_ERR_BAD_ARG;
+  }
+  c->tdd_config = on;
+  return LCS_OK;
+}
+int lcs_get_tdd_config(const lcs_ctx *c, int *on) {
+  if (!c || !on) return LCS_ERR_BAD_ARG;
+  *on = c->tdd_config;
+  return LCS_OK;
+}
+
+// The table of the last fused call, in the order of the records that call handed out: those are the peaks with SSS and MIB in peak
+// order (k_pack_results, read_cells_and_peaks), and they are the ones k_tdd_config gave an estimate.
+int lcs_last_tdd_info(lcs_ctx *c, lcs_tdd_info *info, int max_cells_per_buf) {
+  if (!c || max_cells_per_buf < 0 || (!info && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
+  if (c->tdd_n_buf <= 0) { c->err = "lcs_last_tdd_info needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
+  const int nb = c->tdd_n_buf;
+  lcs_tdd_info none;
+  tdd_info_clear(&none, LCS_TDD_NOT_ESTIMATED);
+  for (size_t i = 0; i < (size_t)nb * max_cells_per_buf; ++i) info[i] = none;
+  if (!c->tdd_made) return LCS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<lcs_tdd_info> tab((size_t)nb * LCS_MAXP);
+  HIPCHK(c, hipMemcpyAsync(tab.data(), c->tdd_info, tab.size() * sizeof(lcs_tdd_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = LCS_OK;
+  for (int b = 0; b < nb; ++b) {
+    int k = 0;
+    for (int p = 0; p < LCS_MAXP; ++p) {
+      const lcs_tdd_info &t = tab[(size_t)b * LCS_MAXP + p];
+      if (t.ul_dl_config == LCS_TDD_NOT_ESTIMATED) continue;
+      if (k < max_cells_per_buf) info[(size_t)b * max_cells_per_buf + k] = t; else rc = LCS_ERR_OVERFLOW;
+      ++k;
+    }
+  }
+  if (rc) c->err = "more results than the output array holds";
+  return rc;
+}
+
 int lcs_set_max_cells_in_flight(lcs_ctx *c, int n) {
   if (!c || n < 1) return LCS_ERR_BAD_ARG;
   c->max_work = std::min(n, (int)LCS_MAX_WORK);
@@ -481,6 +541,8 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   c->foe_ready = false;      // the batch overwrites the buffers a pending lcs_foe_partial left for lcs_foe_finish
+  c->tdd_n_buf = n_buf;      // lcs_last_tdd_info: this batch's table (launch_per_peak makes it, if the batch gets that far and the mode is on)
+  c->tdd_made = false;
   // pack: 137 taps + window-start spread <= 152 inside every template group, the int8 kernel's limit, whatever kernel follows (the
   // fp16 kernel holds 160 taps, the fp32 kernel more); pack_grid thins the groups of a grid that is too sparse for that
   const XcGeom geo = pack_grid(n_cap, n_f, 2 /* DS_COMB_ARM, ref src/CellSearch.cpp:484 */, f_search_set, fc_requested, fc_programmed,
@@ -910,6 +972,33 @@ int lcs_decode_mib(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
   return LCS_OK;
 }
 
+// The uplink-downlink configuration as a stage (tdd_config.h): the caller's grid takes the place of the chain's raw one, k_cell_prep
+// builds RS_DL, k_tdd_config writes its record into the debug block (the fused calls' table stays what it is).
+int lcs_tdd_config(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, lcs_tdd_info *out) {
+  if (!c || !cell || !tfg || !out) return LCS_ERR_BAD_ARG;
+  const int full = n_ofdm_for(cell);
+  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
+    c->err = "tdd_config needs a cell with n_id_1, n_id_2 and a known cp_type";
+    return LCS_ERR_BAD_ARG;
+  }
+  const int n_symb = full == 854 ? 7 : 6;
+  if (n_ofdm < 2 * 20 * n_symb) { c->err = "tdd_config needs at least two frames of the grid (280 OFDM symbols with the normal CP, 240 with the extended)"; return LCS_ERR_BAD_ARG; }
+  if (n_ofdm > LCS_TFG_MAX_OFDM) { c->err = "tdd_config takes at most LCS_TFG_MAX_OFDM (854) OFDM symbols"; return LCS_ERR_BAD_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_stage_ws(c))) return rc;
+  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->tfg, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
+  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  static_assert(sizeof(lcs_tdd_info) <= 2048 * sizeof(double), "the debug block holds a record");
+  lcs_tdd_info *d_out = reinterpret_cast<lcs_tdd_info *>(c->d_dbg.get());
+  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  if ((rc = lcs_launch_tdd_config(c, L, d_out, true))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(lcs_tdd_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
 // chan_est of decode_mib as a stage of its own (ref src/searcher.cpp:1369-1477, ce_interp_hex :1223-1362): the channel
 // estimate of one antenna port on the whole grid and its noise power -- an internal function of the reference, exported
 // so that the tests can pin it to the oracle directly rather than through the decoded MIB.
@@ -1153,6 +1242,10 @@ int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, do
   int rc = check_common(c, n_cap, 1);
   if (rc) return rc;
   if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
+  if (c->tdd_config) {
+    c->err = "the streaming mode does not carry the uplink-downlink estimate: lcs_set_tdd_config(ctx, 0) first";
+    return LCS_ERR_BAD_ARG;
+  }
   if (c->st_open) lcs_stream_close(c);
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = stream_open(c, fmt, n_cap, fc_requested, fc_programmed, fs_programmed))) lcs_stream_close(c);      // whatever a failed open got hold of goes again

@@ -37,6 +37,7 @@ extern "C" int lcs_debug_phase_ts(unsigned long long *out) { return (int)hipMemc
 #define CS_SIZE LCS_CELL_SCRATCH
 
 #include "lte_device.h"
+#include "tdd_config.h"
 
 // block-wide sum of a complex value (any order; the reference sums sequentially, the
 // difference is at the 1e-16 relative level)
@@ -954,6 +955,78 @@ __global__ __launch_bounds__(64) void k_mib_select(lcs_cell *__restrict__ cells,
   if (peaks) peaks[(size_t)items[it].slot * LCS_MAXP + items[it].peak] = cells[it];
 }
 
+// ------------------------------------------------------------------ the uplink-downlink configuration of a TDD cell (tdd_config.h)
+// One workgroup per cell, eight waves over port 0's reference rows: 16 lanes hold one row -- twelve of them its reference
+// subcarriers --, the neighbour product h_m conj(h_{m+1}) takes h_{m+1} from the next lane and the row's sum is the header's
+// butterfly over the 16 lanes.  A thread's rows are q = group + 32 pass: the shifts of all of them are loaded first, then all grid
+// and RS_DL values, and only then the first product is formed -- two memory round trips per cell, whatever the number of rows.
+// The row sums meet in LDS; 40 threads add up their bin in row order, one thread decides (tdd_decide) and sixteen copy the record
+// out.  It reads the RAW grid (rows 0 and n_symb - 3 of every slot are among the rows k_tfg computes under needed_only:
+// tfg_needed_row) and the RS_DL table k_cell_prep left in the cell's scratch.  `force`: the stage entry point -- the record goes
+// to out[it] and is estimated whatever the cell carries; in the fused chain it goes to the cell's place in a table laid out like
+// the peak table, and a cell without a MIB gets LCS_TDD_NOT_ESTIMATED.
+#define TC_THREADS 512
+#define TC_GROUPS (TC_THREADS / TDD_ROW_LANES)             // rows per pass
+#define TC_MAX_Q 288                                        // reference rows of 854 symbols with the extended CP: 285
+#define TC_PASSES (TC_MAX_Q / TC_GROUPS)
+static_assert(TC_PASSES * TC_GROUPS == TC_MAX_Q && TC_GROUPS % 2 == 0 && sizeof(lcs_tdd_info) == 128, "k_tdd_config's row split");
+__global__ __launch_bounds__(TC_THREADS) void k_tdd_config(const lcs_cell *__restrict__ cells, const WorkItem *__restrict__ items,
+                                                           const int *__restrict__ n_work, const double *__restrict__ scratch,
+                                                           const double2 *__restrict__ tfg, lcs_tdd_info *__restrict__ out, int force) {
+  LCS_TAIL_PRIO();
+  __shared__ cd2 s_c[TC_MAX_Q];
+  __shared__ cd2 s_C[TDD_BINS];
+  __shared__ int s_N[TDD_BINS];
+  __shared__ lcs_tdd_info s_info;
+  const int tid = threadIdx.x, grp = tid / TDD_ROW_LANES, m = tid % TDD_ROW_LANES;
+  for (int it = blockIdx.x; it < *n_work; it += gridDim.x) {
+    const lcs_cell c = cells[it];
+    const double *sc = scratch + (size_t)it * CS_SIZE;
+    const int n_symb = cell_n_symb(c);
+    lcs_tdd_info *dst = out + (force ? (size_t)it : (size_t)items[it].slot * LCS_MAXP + items[it].peak);
+    const bool estimate = n_symb > 0 && cell_id(c) >= 0 && (force || c.n_rb_dl != -1);      // the same for the whole workgroup
+    if (estimate) {
+      const int n_ofdm = min(max((int)sc[CS_N_OFDM], 0), ROWS);
+      const int n_q = min(tdd_n_ref_rows(n_ofdm, n_symb), TC_MAX_Q);
+      const double2 *g = tfg + (size_t)it * ROWS * NSC;
+      int sh[TC_PASSES];
+      double2 x[TC_PASSES], r[TC_PASSES];
+#pragma unroll
+      for (int p = 0; p < TC_PASSES; ++p) {
+        const int q = grp + TC_GROUPS * p;
+        const int row20 = d_imod(q >> 1, 20) * n_symb + ((q & 1) ? n_symb - 3 : 0);
+        sh[p] = (q < n_q && m < 12) ? (int)sc[CS_SHIFT + row20 * 4] : -1;
+      }
+#pragma unroll
+      for (int p = 0; p < TC_PASSES; ++p) {
+        const int q = grp + TC_GROUPS * p;
+        const int row20 = d_imod(q >> 1, 20) * n_symb + ((q & 1) ? n_symb - 3 : 0);
+        const bool live = sh[p] >= 0 && sh[p] <= 5;      // (a table without port 0 on this row: the row counts as zeros)
+        x[p] = live ? g[(size_t)tdd_grid_row(q, n_symb) * NSC + sh[p] + 6 * m] : make_double2(0, 0);
+        r[p] = live ? *reinterpret_cast<const double2 *>(&sc[CS_RS + (row20 * 12 + m) * 2]) : make_double2(0, 0);
+      }
+#pragma unroll
+      for (int p = 0; p < TC_PASSES; ++p) {
+        const int q = grp + TC_GROUPS * p;
+        const cd2 h = tdd_h(mk(x[p].x, x[p].y), mk(r[p].x, r[p].y));
+        const cd2 hn = mk(__shfl_down(h.re, 1, TDD_ROW_LANES), __shfl_down(h.im, 1, TDD_ROW_LANES));
+        const cd2 pr = tdd_pair(h, hn);
+        const cd2 s = tdd_row_sum_lanes(m < 11 ? pr : mk(0, 0));
+        if (m == 0 && q < n_q) s_c[q] = s;
+      }
+      __syncthreads();
+      if (tid < TDD_BINS) { s_C[tid] = tdd_bin_sum(s_c, tid, n_q); s_N[tid] = tdd_bin_count(tid, n_q); }
+      __syncthreads();
+      if (tid == 0) tdd_decide(s_C, s_N, &s_info);
+    } else if (tid == 0) {
+      tdd_info_clear(&s_info, LCS_TDD_NOT_ESTIMATED);
+    }
+    __syncthreads();
+    if (tid < 16) reinterpret_cast<double *>(dst)[tid] = reinterpret_cast<const double *>(&s_info)[tid];
+    __syncthreads();                                     // the next cell rewrites the shared arrays
+  }
+}
+
 // ------------------------------------------------------------------------------ launch
 // workgroups loop over the work list; L.grid_items of them per list axis (64: a typical 64-buffer batch in one round)
 int lcs_launch_gather_work(lcs_ctx *c, const Launch &L, int skip) {
@@ -1016,6 +1089,13 @@ int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused) {
                      c->ce, c->cell_scratch, c->d_pbch_scr, c->d_derm_inv);
   hipLaunchKernelGGL(k_mib_select, dim3((LCS_MAX_WORK + 63) / 64), dim3(64), 0, c->stream, c->cells_out, c->n_work,
                      c->cell_scratch, scatter_back ? c->peaks : nullptr, c->work_items);
+  HIPCHK(c, hipGetLastError());
+  return LCS_OK;
+}
+// the uplink-downlink configuration of every cell on the work list (lcs_set_tdd_config, lcs_tdd_config): behind k_mib_select, on the raw grid
+int lcs_launch_tdd_config(lcs_ctx *c, const Launch &L, lcs_tdd_info *out, bool force) {
+  hipLaunchKernelGGL(k_tdd_config, dim3(L.grid_items), dim3(TC_THREADS), 0, c->stream, c->cells_out, c->work_items, c->n_work,
+                     c->cell_scratch, (const double2 *)c->tfg, out, force ? 1 : 0);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }
