@@ -64,6 +64,7 @@ struct Options {
   int duplex = LCS_DUPLEX_FDD;   // -x: the band's duplex mode, set on every context
   bool foe_unwrap = false;       // -u: pss_sss_foe unwrapped by the PSS-only coarse estimate (lcs_set_foe_unwrap), set on every context
   bool tdd_config = false;       // -T: estimate every TDD cell's uplink-downlink configuration (lcs_set_tdd_config) and add it to the report
+  bool meas = false;             // -M: measure every cell's RSRP, RSRQ and CRS SINR (lcs_set_cell_meas) and add them to the report
   int verbosity = 1;
 };
 
@@ -85,6 +86,7 @@ const OptSpec kSpecs[] = {
     {'x', "duplex", TEXT, 0, {"duplex mode of the band, fdd (default) or tdd (bands 33-53: SSS three symbols before the PSS; the frequency grid is then 2.5 kHz)", 0}},
     {'u', "foe-unwrap", FLAG, 0, {"unwrap the PSS/SSS frequency estimate with a PSS-only one: a tdd search then keeps the 5 kHz frequency grid (half the hypotheses)", 0}},
     {'T', "tdd-config", FLAG, 0, {"with -x tdd: estimate each cell's uplink-downlink configuration and DwPTS class from its reference signals; two more columns in the report", 0}},
+    {'M', "meas", FLAG, 0, {"measure each cell's RSRP, RSRQ and SINR on its reference signals (with -x tdd on subframes 0 and 5, with --tdd-config on the downlink subframes found); three more columns in the report", 0}},
     {'s', "freq-start", REAL, "start frequency", {"frequency where cell search should start", 0}},
     {'e', "freq-end", REAL, "end frequency", {"frequency where cell search should end", 0}},
     {'p', "ppm", REAL, "ppm value", {"crystal remaining PPM error", 0}},
@@ -99,7 +101,7 @@ void usage() {
   std::cout << "LTE CellSearch v" << VERSION_STRING << " (MI355X) help screen\n\n"
             << "CellSearch -s start_frequency [optional_parameters]\n";
   const struct { const char *title; const char *letters; } sections[] = {
-      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexuT"}, {"Dongle LO correction options:", "pc"},
+      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexuTM"}, {"Dongle LO correction options:", "pc"},
       {"Capture buffer save/ load options:", "rld"}};
   for (const auto &sec : sections) {
     std::cout << "  " << sec.title << "\n";
@@ -128,6 +130,7 @@ void store(Options &o, const OptSpec &s, const char *value) {
       else if (s.letter == 'r') o.record = true;
       else if (s.letter == 'u') o.foe_unwrap = true;
       else if (s.letter == 'T') o.tdd_config = true;
+      else if (s.letter == 'M') o.meas = true;
       else o.load = true;
       return;
     case TEXT:
@@ -310,6 +313,13 @@ std::string tdd_columns(const lcs_tdd_info &t) {
   return col(t.ul_dl_config) + col(t.dwpts_rs_rows);
 }
 
+// --meas: RSRP of port 0, RSRQ and port 0's SINR in dB to one decimal, "-" where there is no record, "inf" for an SINR without noise
+std::string meas_columns(const lcs_meas_info &m) {
+  if (m.status != 0) return "     -     -     -";
+  auto dbcol = [](double v) { return v > 0 ? fmt(" %5.1f", 10.0 * std::log10(v)) : std::string("     -"); };
+  return dbcol(m.rsrp[0]) + dbcol(m.rsrq) + (m.noise[0] > 0 ? dbcol(m.rsrp[0] / m.noise[0]) : std::string("   inf"));
+}
+
 void announce(const std::list<Cell> &cells) {
   for (const Cell &c : cells)
     std::cout << "  Detected a cell!\n    cell ID: " << c.n_id_cell() << "\n    RX power level: " << num(db10(c.pss_pow))
@@ -329,6 +339,7 @@ struct Sweep {
   int n_fc, n_batches;
   std::vector<std::list<Cell> > detected;
   std::vector<std::vector<lcs_tdd_info> > tdd;       // --tdd-config: per carrier, one record per detected cell
+  std::vector<std::vector<lcs_meas_info> > meas;     // --meas: likewise
   std::vector<char> fc_matches, batched;
   std::vector<char> batch_done;
   std::string failure;
@@ -358,7 +369,7 @@ struct InFlight {
 void device_thread(Sweep *sw, int device, int first_batch, int stride) {
   try {
     std::unique_ptr<lcs::Searcher> ctx[2];
-    auto configure = [&](lcs::Searcher &s) { s.set_duplex(sw->opt.duplex); s.set_foe_unwrap(sw->opt.foe_unwrap); if (sw->opt.tdd_config) s.set_tdd_config(true); };
+    auto configure = [&](lcs::Searcher &s) { s.set_duplex(sw->opt.duplex); s.set_foe_unwrap(sw->opt.foe_unwrap); if (sw->opt.tdd_config) s.set_tdd_config(true); if (sw->opt.meas) s.set_cell_meas(true); };
     for (int k = 0; k < 2; ++k) { ctx[k].reset(new lcs::Searcher(device)); configure(*ctx[k]); }
     std::unique_ptr<lcs::Searcher> one;                     // for captures that are not raw dongle bytes
     unsigned char *pinned[2] = {0, 0};
@@ -376,6 +387,11 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
           for (size_t j = 0; j < f.carriers.size(); ++j)
             sw->tdd[f.carriers[j]].assign(info.begin() + j * LCS_MAX_PEAKS, info.begin() + j * LCS_MAX_PEAKS + found[j].size());
         }
+        if (sw->opt.meas) {
+          const std::vector<lcs_meas_info> info = ctx[slot]->last_cell_meas((int)f.carriers.size(), LCS_MAX_PEAKS);
+          for (size_t j = 0; j < f.carriers.size(); ++j)
+            sw->meas[f.carriers[j]].assign(info.begin() + j * LCS_MAX_PEAKS, info.begin() + j * LCS_MAX_PEAKS + found[j].size());
+        }
         for (size_t j = 0; j < f.carriers.size(); ++j) sw->detected[f.carriers[j]].swap(found[j]);
       }
       for (size_t j = 0; j < f.singles.size(); ++j) {
@@ -387,6 +403,10 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
         if (sw->opt.tdd_config) {
           const std::vector<lcs_tdd_info> info = one->last_tdd_info(1, LCS_MAX_PEAKS);
           sw->tdd[f.single_carriers[j]].assign(info.begin(), info.begin() + sw->detected[f.single_carriers[j]].size());
+        }
+        if (sw->opt.meas) {
+          const std::vector<lcs_meas_info> info = one->last_cell_meas(1, LCS_MAX_PEAKS);
+          sw->meas[f.single_carriers[j]].assign(info.begin(), info.begin() + sw->detected[f.single_carriers[j]].size());
         }
       }
       sw->finish(f.batch);
@@ -483,6 +503,7 @@ int main(int argc, char *const argv[]) {
   sw.n_batches = (sw.n_fc + sw.kBatch - 1) / sw.kBatch;
   sw.detected.resize(sw.n_fc);
   sw.tdd.resize(sw.n_fc);
+  sw.meas.resize(sw.n_fc);
   sw.fc_matches.assign(sw.n_fc, 1);
   sw.batched.assign(sw.n_fc, 0);
   sw.batch_done.assign(sw.n_batches, 0);
@@ -541,9 +562,11 @@ int main(int argc, char *const argv[]) {
     std::cout << "Detected the following cells:\n"
               << "A: #antenna ports C: CP type ; P: PHICH duration ; PR: PHICH resource type\n"
               << (opt.tdd_config ? "UD: uplink-downlink configuration ; DW: DwPTS class (port-0 reference rows in the special subframe)\n" : "")
-              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor" << (opt.tdd_config ? " UD DW" : "") << "\n";
+              << (opt.meas ? "RSRP: power per reference resource element of port 0, dB re full scale ; RSRQ: 6 RSRP / RSSI, dB ; SINR: RSRP / noise on port 0's reference signals, dB\n" : "")
+              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor" << (opt.tdd_config ? " UD DW" : "") << (opt.meas ? "  RSRP  RSRQ  SINR" : "") << "\n";
     for (size_t i = 0; i < cells.size(); ++i)
-      std::cout << table_row(cells[i], opt.correction) << (opt.tdd_config ? tdd_columns(sw.tdd[origin[i].first][origin[i].second]) : std::string()) << "\n";
+      std::cout << table_row(cells[i], opt.correction) << (opt.tdd_config ? tdd_columns(sw.tdd[origin[i].first][origin[i].second]) : std::string())
+                << (opt.meas ? meas_columns(sw.meas[origin[i].first][origin[i].second]) : std::string()) << "\n";
     std::cout.flush();
   }
   return 0;

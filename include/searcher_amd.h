@@ -16,6 +16,7 @@
 #ifndef SEARCHER_AMD_H
 #define SEARCHER_AMD_H
 
+#include <limits>
 #include <cmath>
 #include <complex>
 #include <list>
@@ -97,6 +98,30 @@ class Searcher {
     check(lcs_tdd_config(h_, &cell, g.data(), tfg.rows(), &out));
     return out;
   }
+
+  // RSRP, RSSI, RSRQ and the noise power of the cells a fused call decodes, from their reference signals (lcs_set_cell_meas);
+  // last_cell_meas: the records of the last search_capbuf (n_buf = 1) or batch, [n_buf][max_cells_per_buf], entry k of a buffer
+  // belonging to its k-th cell, status LCS_MEAS_NOT_MEASURED where nothing was measured
+  void set_cell_meas(bool on) { check(lcs_set_cell_meas(h_, on ? 1 : 0)); }
+  bool cell_meas_mode() { int on = 0; check(lcs_get_cell_meas(h_, &on)); return on != 0; }
+  std::vector<lcs_meas_info> last_cell_meas(int n_buf = 1, int max_cells_per_buf = 16) {
+    std::vector<lcs_meas_info> info((size_t)n_buf * max_cells_per_buf);
+    const int rc = lcs_last_cell_meas(h_, info.data(), max_cells_per_buf);
+    if (rc != LCS_ERR_OVERFLOW) check(rc);
+    return info;
+  }
+  // ... and the measurement as a stage of its own (lcs_cell_meas): a cell with identity and CP type, its grid from extract_tfg, the
+  // subframes to measure (bit s of dl_mask = subframe s; tdd_dl_mask(configuration) for a TDD cell)
+  lcs_meas_info cell_meas(const Cell &cell, const cn::cmat &tfg, int dl_mask = 0x3ff) {
+    std::vector<double> g;
+    to_rows(tfg, g);
+    lcs_meas_info out;
+    check(lcs_cell_meas(h_, &cell, g.data(), tfg.rows(), dl_mask, &out));
+    return out;
+  }
+  static int tdd_dl_mask(int ul_dl_config) { return lcs_tdd_dl_mask(ul_dl_config); }
+  // the SINR of port p of a record: rsrp / noise, infinite where noise <= 0
+  static double sinr(const lcs_meas_info &m, int p = 0) { return m.noise[p] > 0 ? m.rsrp[p] / m.noise[p] : std::numeric_limits<double>::infinity(); }
 
   // include/searcher.h:22-41
   void xcorr_pss(const cn::cvec &capbuf, const cn::vec &f_search_set, unsigned char ds_comb_arm, double fc_requested,

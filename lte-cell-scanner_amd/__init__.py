@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -427,6 +427,36 @@ class Searcher:
         self._note_overflow(self._chk(rc, "lcs_last_tdd_info", allow_overflow=True), "lcs_last_tdd_info")
         return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
 
+    def set_cell_meas(self, on: bool):
+        """Measure RSRP, RSSI, RSRQ and the noise power of every cell a fused call decodes, from its reference signals on the device
+        (lcs_set_cell_meas, include/lcs.h); last_cell_meas() reads the records.  Off by default (every record is then what it was,
+        bit for bit, and no kernel is added); refused while a stream is open, and stream_open is refused while it is on."""
+        self._chk(self._lib.lcs_set_cell_meas(self._h, 1 if on else 0), "lcs_set_cell_meas")
+
+    @property
+    def cell_meas_mode(self) -> bool:
+        d = C.c_int(-1)
+        self._chk(self._lib.lcs_get_cell_meas(self._h, C.byref(d)), "lcs_get_cell_meas")
+        return d.value != 0
+
+    def cell_meas(self, cell, tfg, dl_mask: int = 0x3FF):
+        """The measurement as a stage of its own (lcs_cell_meas): a cell with identity and CP type (n_ports 0 / unknown: port 0 alone)
+        and its grid from extract_tfg, raw or compensated, two frames to 854 rows; dl_mask: bit s set = subframe s is measured
+        (tdd_dl_mask(configuration) for a TDD cell) -> CellMeas"""
+        tfg = np.ascontiguousarray(tfg, np.complex128)
+        out = capi.CellMeas()
+        self._chk(self._lib.lcs_cell_meas(self._h, C.byref(cell), _dp(tfg), tfg.shape[0], int(dl_mask), C.byref(out)), "lcs_cell_meas")
+        return out
+
+    def last_cell_meas(self, n_buf: int = 1, max_cells_per_buf: int = 16):
+        """The records of the last search_capbuf (n_buf = 1) or batch: per buffer a list of max_cells_per_buf CellMeas, entry k
+        belonging to cell k of that buffer; the entries behind a buffer's cells, and all of them without the mode, read
+        MEAS_NOT_MEASURED (lcs_last_cell_meas)."""
+        info = (capi.CellMeas * (n_buf * max_cells_per_buf))()
+        rc = self._lib.lcs_last_cell_meas(self._h, info, max_cells_per_buf)
+        self._note_overflow(self._chk(rc, "lcs_last_cell_meas", allow_overflow=True), "lcs_last_cell_meas")
+        return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
+
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route
         (lcs_set_float_batch_probe, include/lcs.h); off by default."""
@@ -687,6 +717,12 @@ class Searcher:
 
     def sync(self):
         self._chk(self._lib.lcs_sync(self._h), "lcs_sync")
+
+
+def tdd_dl_mask(ul_dl_config: int) -> int:
+    """The downlink subframes of uplink-downlink configuration 0..6 (36.211 table 4.2-2) as a dl_mask for Searcher.cell_meas, special
+    subframes excluded; -1 for anything else (lcs_tdd_dl_mask)."""
+    return int(capi.load().lcs_tdd_dl_mask(int(ul_dl_config)))
 
 
 def frq_tie_eps() -> float:

@@ -6,6 +6,7 @@ There is no fallback: if the library is missing or no MI355X is visible, calls r
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,6 +19,7 @@ STAGE_PSS, STAGE_FULL = 1, 3
 MAX_PEAKS = 104            # LCS_MAX_PEAKS: the longest list peak_search can return (include/lcs.h)
 DUPLEX_FDD, DUPLEX_TDD = 0, 1      # LCS_DUPLEX_*: where the SSS lies relative to the PSS (include/lcs.h: lcs_set_duplex)
 TDD_NOT_ESTIMATED = -2     # LCS_TDD_NOT_ESTIMATED: a record of lcs_last_tdd_info that belongs to no decoded cell, or to a call without the mode
+MEAS_NOT_MEASURED = -2     # LCS_MEAS_NOT_MEASURED: a record of lcs_last_cell_meas that belongs to no decoded cell, or to a call without the mode
 ERRORS = {-1: "LCS_ERR_NO_DEVICE", -2: "LCS_ERR_BAD_ARG", -3: "LCS_ERR_HIP", -4: "LCS_ERR_OVERFLOW", -5: "LCS_ERR_NOMEM"}
 
 
@@ -84,9 +86,59 @@ class TddInfo(C.Structure):
 
 assert C.sizeof(TddInfo) == 128
 
+
+class CellMeas(C.Structure):
+    """lcs_meas_info: RSRP, RSSI, RSRQ and the noise power of a cell from its cell-specific reference signals (include/lcs.h:
+    lcs_set_cell_meas).  status 0 measured, -1 no number, MEAS_NOT_MEASURED never written; n_rows reference rows of the subframes in
+    dl_mask, n_ports ports measured (1 or 2); rsrp and noise per port and rssi in the grid's power units, rsrq = 6 rsrp[0] / rssi,
+    a_re_im = the neighbour-product sums A_0, A_1.  The SINR is the caller's division: the properties below do it."""
+    _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_ports", C.c_int32), ("dl_mask", C.c_int32), ("rsrp", C.c_double * 2),
+                ("noise", C.c_double * 2), ("rssi", C.c_double), ("rsrq", C.c_double), ("a_re_im", C.c_double * 4), ("reserved", C.c_double * 4)]
+
+    def copy(self) -> "CellMeas":
+        o = CellMeas()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(CellMeas))
+        return o
+
+    @property
+    def measured(self) -> bool:
+        return self.status == 0
+
+    @property
+    def sinr(self) -> tuple:
+        """rsrp[p] / noise[p] of the ports measured, inf where noise <= 0"""
+        return tuple((self.rsrp[p] / self.noise[p]) if self.noise[p] > 0 else math.inf for p in range(max(self.n_ports, 0)))
+
+    @property
+    def rsrp_db(self) -> tuple:
+        return tuple(_db10(self.rsrp[p]) for p in range(max(self.n_ports, 0)))
+
+    @property
+    def rsrq_db(self) -> float:
+        return _db10(self.rsrq)
+
+    @property
+    def sinr_db(self) -> tuple:
+        return tuple(_db10(v) for v in self.sinr)
+
+    def as_dict(self) -> dict:
+        return dict(status=self.status, n_rows=self.n_rows, n_ports=self.n_ports, dl_mask=self.dl_mask, rsrp=list(self.rsrp), noise=list(self.noise),
+                    rssi=self.rssi, rsrq=self.rsrq, a_re_im=list(self.a_re_im))
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"CellMeas(status={self.status}, n_rows={self.n_rows}, dl_mask={self.dl_mask:#x}, rsrp={list(self.rsrp)}, rsrq={self.rsrq:.4f})"
+
+
+def _db10(x: float) -> float:
+    return math.inf if x == math.inf else (10.0 * math.log10(x) if x > 0 else -math.inf)
+
+
+assert C.sizeof(CellMeas) == 128
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
+    "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -153,6 +205,12 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_get_tdd_config.argtypes = [vp, C.POINTER(C.c_int)]
         L.lcs_tdd_config.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_int, C.POINTER(TddInfo)]
         L.lcs_last_tdd_info.argtypes = [vp, C.POINTER(TddInfo), C.c_int]
+    if hasattr(L, "lcs_set_cell_meas"):      # (likewise)
+        L.lcs_set_cell_meas.argtypes = [vp, C.c_int]
+        L.lcs_get_cell_meas.argtypes = [vp, C.POINTER(C.c_int)]
+        L.lcs_cell_meas.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(CellMeas)]
+        L.lcs_last_cell_meas.argtypes = [vp, C.POINTER(CellMeas), C.c_int]
+        L.lcs_tdd_dl_mask.argtypes = [C.c_int]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

@@ -11,6 +11,7 @@
 #include "channelizer.h"
 #include "lte_device.h"
 #include "tdd_config.h"
+#include "cell_meas.h"
 #include "pss_ref.h"
 
 namespace {
@@ -155,6 +156,7 @@ Launch make_launch(const lcs_ctx *c, int n_buf, uint32_t n_cap, const CapSrc &sr
   L.duplex = c->duplex;
   L.foe_unwrap = c->foe_unwrap;
   L.tdd_config = (c->tdd_config && c->duplex == LCS_DUPLEX_TDD) ? 1 : 0;
+  L.cell_meas = c->cell_meas;
   if (c->st_open) { L.tracked = c->st_dtracked; L.n_tracked = c->st_dntracked; }
   return L;
 }
@@ -201,6 +203,8 @@ int ensure_stage_ws(lcs_ctx *c, int n_f = 1) { return ensure_ws(c, 1, std::max<u
 // (k_tdd_config, on the raw grid) into c->tdd_info, a table laid out like the peak table: the first round's call sets every record of
 // it to LCS_TDD_NOT_ESTIMATED (all 32-bit words -2: lcs_last_tdd_info reads the integer fields only of such a record), later rounds
 // -- lcs_batch_collect's among them -- fill in their own cells.
+// With L.cell_meas (lcs_set_cell_meas) every round measures its cells as well (k_cell_meas, behind k_tdd_config, whose record of the
+// cell names the subframes to measure where there is one) into c->cell_meas_tab, a table made and kept in the same way.
 int launch_per_peak(lcs_ctx *c, const Launch &L, int r0, int r1) {
   int rc;
   if (r0 == 0) {
@@ -212,11 +216,20 @@ int launch_per_peak(lcs_ctx *c, const Launch &L, int r0, int r1) {
       if ((rc = c->tdd_info.reserve(c, n))) return rc;
       HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->tdd_info.get()), LCS_TDD_NOT_ESTIMATED, n * (sizeof(lcs_tdd_info) / 4), c->stream));
     }
+    c->meas_made = L.cell_meas != 0;
+    if (L.cell_meas) {
+      const size_t n = (size_t)L.n_buf * LCS_MAXP;
+      if (n > c->cell_meas_tab.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+      if ((rc = c->cell_meas_tab.reserve(c, n))) return rc;
+      HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->cell_meas_tab.get()), LCS_MEAS_NOT_MEASURED, n * (sizeof(lcs_meas_info) / 4), c->stream));
+    }
   }
+  const int meas_mask = L.duplex == LCS_DUPLEX_TDD ? 0x021 : 0x3ff;      // TDD: subframes 0 and 5 are downlink in every configuration
   if (r0 == 0 && (rc = lcs_launch_sss_foe(c, L, 3.0 /* THRESH2_N_SIGMA, ref src/CellSearch.cpp:528 */, nullptr))) return rc;
   for (int r = r0; r < r1; ++r)
     if ((rc = lcs_launch_gather_work(c, L, r * L.round_cells)) || (rc = lcs_launch_tfg(c, L, true)) || (rc = lcs_launch_tfoec(c, L, false)) ||
-        (rc = lcs_launch_mib(c, L, true)) || (L.tdd_config && (rc = lcs_launch_tdd_config(c, L, c->tdd_info, false))))
+        (rc = lcs_launch_mib(c, L, true)) || (L.tdd_config && (rc = lcs_launch_tdd_config(c, L, c->tdd_info, false))) ||
+        (L.cell_meas && (rc = lcs_launch_cell_meas(c, L, L.tdd_config ? c->tdd_info.get() : nullptr, c->cell_meas_tab, meas_mask, false))))
       return rc;
   return LCS_OK;
 }
@@ -449,6 +462,50 @@ int lcs_last_tdd_info(lcs_ctx *c, lcs_tdd_info *info, int max_cells_per_buf) {
   return rc;
 }
 
+int lcs_set_cell_meas(lcs_ctx *c, int on) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (on != 0 && on != 1) { c->err = "cell_meas is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open && on != c->cell_meas) {
+    c->err = "the streaming mode does not carry the cell measurement: the cell_meas mode cannot change under an open stream, lcs_stream_close first";
+    return LCS_ERR_BAD_ARG;
+  }
+  c->cell_meas = on;
+  return LCS_OK;
+}
+int lcs_get_cell_meas(const lcs_ctx *c, int *on) {
+  if (!c || !on) return LCS_ERR_BAD_ARG;
+  *on = c->cell_meas;
+  return LCS_OK;
+}
+int lcs_tdd_dl_mask(int ul_dl_config) { return meas_tdd_dl_mask(ul_dl_config); }
+
+// The measurement table of the last fused call, in the order of the records that call handed out (as lcs_last_tdd_info).
+int lcs_last_cell_meas(lcs_ctx *c, lcs_meas_info *info, int max_cells_per_buf) {
+  if (!c || max_cells_per_buf < 0 || (!info && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
+  if (c->tdd_n_buf <= 0) { c->err = "lcs_last_cell_meas needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
+  const int nb = c->tdd_n_buf;
+  lcs_meas_info none;
+  meas_clear(&none, LCS_MEAS_NOT_MEASURED);
+  for (size_t i = 0; i < (size_t)nb * max_cells_per_buf; ++i) info[i] = none;
+  if (!c->meas_made) return LCS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<lcs_meas_info> tab((size_t)nb * LCS_MAXP);
+  HIPCHK(c, hipMemcpyAsync(tab.data(), c->cell_meas_tab, tab.size() * sizeof(lcs_meas_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = LCS_OK;
+  for (int b = 0; b < nb; ++b) {
+    int k = 0;
+    for (int p = 0; p < LCS_MAXP; ++p) {
+      const lcs_meas_info &t = tab[(size_t)b * LCS_MAXP + p];
+      if (t.status == LCS_MEAS_NOT_MEASURED) continue;
+      if (k < max_cells_per_buf) info[(size_t)b * max_cells_per_buf + k] = t; else rc = LCS_ERR_OVERFLOW;
+      ++k;
+    }
+  }
+  if (rc) c->err = "more results than the output array holds";
+  return rc;
+}
+
 int lcs_set_max_cells_in_flight(lcs_ctx *c, int n) {
   if (!c || n < 1) return LCS_ERR_BAD_ARG;
   c->max_work = std::min(n, (int)LCS_MAX_WORK);
@@ -543,6 +600,7 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   c->foe_ready = false;      // the batch overwrites the buffers a pending lcs_foe_partial left for lcs_foe_finish
   c->tdd_n_buf = n_buf;      // lcs_last_tdd_info: this batch's table (launch_per_peak makes it, if the batch gets that far and the mode is on)
   c->tdd_made = false;
+  c->meas_made = false;
   // pack: 137 taps + window-start spread <= 152 inside every template group, the int8 kernel's limit, whatever kernel follows (the
   // fp16 kernel holds 160 taps, the fp32 kernel more); pack_grid thins the groups of a grid that is too sparse for that
   const XcGeom geo = pack_grid(n_cap, n_f, 2 /* DS_COMB_ARM, ref src/CellSearch.cpp:484 */, f_search_set, fc_requested, fc_programmed,
@@ -999,6 +1057,34 @@ int lcs_tdd_config(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
   return LCS_OK;
 }
 
+// RSRP, RSSI, RSRQ and the noise power as a stage (cell_meas.h), as lcs_tdd_config: the caller's grid in the chain's place, the
+// record through the debug block.
+int lcs_cell_meas(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int dl_mask, lcs_meas_info *out) {
+  if (!c || !cell || !tfg || !out) return LCS_ERR_BAD_ARG;
+  const int full = n_ofdm_for(cell);
+  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
+    c->err = "cell_meas needs a cell with n_id_1, n_id_2 and a known cp_type";
+    return LCS_ERR_BAD_ARG;
+  }
+  const int n_symb = full == 854 ? 7 : 6;
+  if (n_ofdm < 2 * 20 * n_symb) { c->err = "cell_meas needs at least two frames of the grid (280 OFDM symbols with the normal CP, 240 with the extended)"; return LCS_ERR_BAD_ARG; }
+  if (n_ofdm > LCS_TFG_MAX_OFDM) { c->err = "cell_meas takes at most LCS_TFG_MAX_OFDM (854) OFDM symbols"; return LCS_ERR_BAD_ARG; }
+  if (!meas_mask_ok(dl_mask)) { c->err = "cell_meas needs a dl_mask with at least one of the bits 0 .. 9 and none above"; return LCS_ERR_BAD_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_stage_ws(c))) return rc;
+  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->tfg, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
+  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  static_assert(sizeof(lcs_meas_info) <= 2048 * sizeof(double), "the debug block holds a record");
+  lcs_meas_info *d_out = reinterpret_cast<lcs_meas_info *>(c->d_dbg.get());
+  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  if ((rc = lcs_launch_cell_meas(c, L, nullptr, d_out, dl_mask, true))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(lcs_meas_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
 // chan_est of decode_mib as a stage of its own (ref src/searcher.cpp:1369-1477, ce_interp_hex :1223-1362): the channel
 // estimate of one antenna port on the whole grid and its noise power -- an internal function of the reference, exported
 // so that the tests can pin it to the oracle directly rather than through the decoded MIB.
@@ -1244,6 +1330,10 @@ int lcs_stream_open(lcs_ctx *c, int fmt, uint32_t n_cap, double fc_requested, do
   if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
   if (c->tdd_config) {
     c->err = "the streaming mode does not carry the uplink-downlink estimate: lcs_set_tdd_config(ctx, 0) first";
+    return LCS_ERR_BAD_ARG;
+  }
+  if (c->cell_meas) {
+    c->err = "the streaming mode does not carry the cell measurement: lcs_set_cell_meas(ctx, 0) first";
     return LCS_ERR_BAD_ARG;
   }
   if (c->st_open) lcs_stream_close(c);

@@ -191,6 +191,7 @@ struct Launch {
   int duplex = LCS_DUPLEX_FDD;          // lcs_set_duplex: where the SSS lies relative to the PSS (sss_foe.hip: the Dx table)
   int foe_unwrap = 0;                   // lcs_set_foe_unwrap: pss_sss_foe unwrapped by the PSS-only coarse estimate (foe_coarse.h)
   int tdd_config = 0;                   // lcs_set_tdd_config AND duplex == LCS_DUPLEX_TDD: k_tdd_config behind k_mib_select (tdd_config.h)
+  int cell_meas = 0;                    // lcs_set_cell_meas: k_cell_meas behind k_mib_select and k_tdd_config (cell_meas.h)
 };
 // The last enqueued batch: lcs_batch_collect (its late per-cell rounds), lcs_batch_readback and lcs_last_batch_stats read it.
 struct BatchRecord {
@@ -348,6 +349,9 @@ struct lcs_ctx : lcs_ctx_queues {
   DevBuf<lcs_tdd_info> tdd_info;    // [n_buf][LCS_MAXP], laid out like `peaks`: what k_tdd_config writes in the fused chain, [0] for lcs_tdd_config
   int tdd_n_buf = 0;                // buffers of the last fused call (lcs_last_tdd_info), 0: none yet
   bool tdd_made = false;            // ... and whether that call ran k_tdd_config: otherwise its table is LCS_TDD_NOT_ESTIMATED throughout
+  int cell_meas = 0;                // lcs_set_cell_meas: likewise
+  DevBuf<lcs_meas_info> cell_meas_tab;   // [n_buf][LCS_MAXP], laid out like `peaks`: what k_cell_meas writes in the fused chain
+  bool meas_made = false;           // whether the last fused call (tdd_n_buf buffers) ran k_cell_meas: otherwise its table is LCS_MEAS_NOT_MEASURED throughout
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -499,4 +503,7 @@ int lcs_launch_tfoec(lcs_ctx *c, const Launch &L, bool apply_grid);
 int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused);   // chan_est + PBCH candidates + selection (+ record back into the peak table)
 int lcs_launch_chan_est(lcs_ctx *c, const Launch &L);
 int lcs_launch_tdd_config(lcs_ctx *c, const Launch &L, lcs_tdd_info *out /*device*/, bool force /* the stage: out[item], whatever the record carries */);
+// cell_meas.hip
+int lcs_launch_cell_meas(lcs_ctx *c, const Launch &L, const lcs_tdd_info *tdd /*device: this launch's k_tdd_config table, or null*/, lcs_meas_info *out /*device*/,
+                         int dl_mask, bool force /* the stage: out[item] with dl_mask, whatever the record carries */);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

@@ -11,8 +11,7 @@
 #include "lcs_internal.h"
 
 #define N_RB_MAXDL 110
-#define NSC 72
-#define ROWS LCS_TFG_ROWS
+#include "tfg_layout.h"      // NSC, ROWS, the cell_scratch layout CS_*, the reference-row split TC_*
 
 // cell_scratch layout (doubles, per work item)
 // Phase timestamps of workgroup (0,0,0) for tuning runs (-DLCS_PHASE_TS); compiled out otherwise.
@@ -23,19 +22,6 @@ extern "C" int lcs_debug_phase_ts(unsigned long long *out) { return (int)hipMemc
 #else
 #define PH(i) do { } while (0)
 #endif
-#define CS_N_OFDM 0
-#define CS_KFACTOR 1
-#define CS_OOB 2
-#define CS_NRS 8         // 4 values: RS rows per port
-#define CS_NPP 640       // [4 ports][CE_NCHUNK <= 8] partial sums of |filtered - raw|^2
-#define CS_TF_RES 680    // tfoec: residual_f, k_factor_residual, delay
-#define CS_TF_KRES 681
-#define CS_TF_TOE 684     // 4 complex partial sums of the timing estimate (k_tfoec_est parts), summed in part order
-#define CS_CAND 16       // 12 candidates x 4: ok, bits lo (24 bits as double), unused
-#define CS_SHIFT 64      // [140][4] (-1 = no RS)
-#define CS_RS 1024       // [140][12] complex
-#define CS_SIZE LCS_CELL_SCRATCH
-
 #include "lte_device.h"
 #include "tdd_config.h"
 
@@ -965,11 +951,7 @@ __global__ __launch_bounds__(64) void k_mib_select(lcs_cell *__restrict__ cells,
 // tfg_needed_row) and the RS_DL table k_cell_prep left in the cell's scratch.  `force`: the stage entry point -- the record goes
 // to out[it] and is estimated whatever the cell carries; in the fused chain it goes to the cell's place in a table laid out like
 // the peak table, and a cell without a MIB gets LCS_TDD_NOT_ESTIMATED.
-#define TC_THREADS 512
-#define TC_GROUPS (TC_THREADS / TDD_ROW_LANES)             // rows per pass
-#define TC_MAX_Q 288                                        // reference rows of 854 symbols with the extended CP: 285
-#define TC_PASSES (TC_MAX_Q / TC_GROUPS)
-static_assert(TC_PASSES * TC_GROUPS == TC_MAX_Q && TC_GROUPS % 2 == 0 && sizeof(lcs_tdd_info) == 128, "k_tdd_config's row split");
+static_assert(TC_PASSES * TC_GROUPS == TC_MAX_Q && TC_GROUPS % 2 == 0 && TC_GROUPS * TDD_ROW_LANES == TC_THREADS && sizeof(lcs_tdd_info) == 128, "k_tdd_config's row split");
 __global__ __launch_bounds__(TC_THREADS) void k_tdd_config(const lcs_cell *__restrict__ cells, const WorkItem *__restrict__ items,
                                                            const int *__restrict__ n_work, const double *__restrict__ scratch,
                                                            const double2 *__restrict__ tfg, lcs_tdd_info *__restrict__ out, int force) {

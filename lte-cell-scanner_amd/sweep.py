@@ -91,8 +91,34 @@ def records_with_gain(cells_per_carrier, gain) -> List[List[dict]]:
     return out
 
 
+def meas_with_gain(meas_per_carrier, gain) -> list:
+    """The per-carrier measurement lists (Searcher.last_cell_meas) of a band search on 8-bit carriers on ONE power scale, as
+    records_with_gain does for pss_pow: carrier k's bytes are its floats times gain[k], and rsrp, noise, rssi and the sums a_re_im are
+    powers of the buffer, so they are divided by gain[k]**2 -- exactly, the gain being a power of two; rsrq and the SINR are ratios
+    and stay what they are.  Returns copies (capi.CellMeas); records that hold no measurement pass unchanged."""
+    gain = np.asarray(gain.detach().cpu().numpy() if hasattr(gain, "detach") else gain, np.float64).reshape(-1)
+    if len(meas_per_carrier) != gain.size:
+        raise ValueError(f"meas_with_gain: {len(meas_per_carrier)} carriers, {gain.size} gains")
+    out = []
+    for recs, g in zip(meas_per_carrier, gain):
+        row = []
+        for m in recs:
+            m = m.copy()
+            if m.status == 0:
+                g2 = g * g
+                for p in range(2):
+                    m.rsrp[p] /= g2
+                    m.noise[p] /= g2
+                for i in range(4):
+                    m.a_re_im[i] /= g2
+                m.rssi /= g2
+            row.append(m)
+        out.append(row)
+    return out
+
+
 def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, fc_centre: float, carriers, f_search_set,
-                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64"):
+                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64", meas: bool = False):
     """A band search from ONE wideband capture resident in HBM (n_in samples of fmt at fs_in, centred on fc_centre): the
     carriers (absolute Hz, e.g. fc_search_set(...)) are channelized `chunk` at a time (Searcher.channelize: mix, low-pass,
     decimate by decim) into a torch buffer this function owns, and every chunk goes through the full chain as a
@@ -108,7 +134,10 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     (Searcher.set_duplex: one capture covers one band, and a band has one duplex; a TDD band wants f_search_set in 2.5 kHz steps,
     or Searcher.set_foe_unwrap(True) and the usual 5 kHz).
     Returns one list of cells (LcsCell)
-    per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's."""
+    per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's.
+    meas=True turns Searcher.set_cell_meas on for these batches (and puts the mode back afterwards) and returns the cells as
+    record_to_dict dicts instead, each with its measurement (capi.CellMeas) as cell["meas"]; with out="u8" the measurement and
+    pss_pow are already on one power scale over the carriers (meas_with_gain, records_with_gain)."""
     import torch
     from . import capi
     carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
@@ -130,10 +159,31 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     else:
         buf, batch_fmt, channelize = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=tdev), capi.FMT_C64, searcher.channelize_rational
     cells = []
-    for a in range(0, carriers.size, chunk):
-        fc = carriers[a:a + chunk]
-        channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
-        cells += searcher.search_batch(buf.data_ptr(), batch_fmt, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL, max_cells_per_buf)
+    if not meas:
+        for a in range(0, carriers.size, chunk):
+            fc = carriers[a:a + chunk]
+            channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
+            cells += searcher.search_batch(buf.data_ptr(), batch_fmt, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL, max_cells_per_buf)
+        return cells
+    was_on = searcher.cell_meas_mode
+    searcher.set_cell_meas(True)
+    try:
+        for a in range(0, carriers.size, chunk):
+            fc = carriers[a:a + chunk]
+            if out == "u8":
+                gain = channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out, want_gain=True)
+            else:
+                channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
+                gain = np.ones(fc.size)
+            found = searcher.search_batch(buf.data_ptr(), batch_fmt, fc.size, int(n_out), f_search_set, fc, fc, fs_out, capi.STAGE_FULL, max_cells_per_buf)
+            recs = records_with_gain(found, gain)
+            info = meas_with_gain(searcher.last_cell_meas(fc.size, max_cells_per_buf), gain)
+            for rs_, ms_ in zip(recs, info):
+                for d, m in zip(rs_, ms_):
+                    d["meas"] = m
+            cells += recs
+    finally:
+        searcher.set_cell_meas(was_on)
     return cells
 
 
