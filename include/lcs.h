@@ -265,6 +265,38 @@ int lcs_last_cell_meas(lcs_ctx *ctx, lcs_meas_info *info, int max_cells_per_buf)
 /* the downlink subframes of uplink-downlink configuration 0 .. 6 (36.211 table 4.2-2) as a dl_mask, special subframes excluded; -1
  * for anything else */
 int lcs_tdd_dl_mask(int ul_dl_config);
+/* The same measurement over the cell's whole bandwidth, from wide samples that are resident on the device (lcs_cell_meas_wide,
+ * lcs_extract_tfg_wide below; a stage of its own, not part of the fused chain).  THE RULE (lte-cell-scanner_amd/csrc/cell_meas_wide.h,
+ * host and device), for a cell with n_id_1, n_id_2, cp_type, n_ports, frame_start and freq_fine, a DEVICE buffer of n_cap
+ * complex<float> samples at fs_programmed ~ 1.92e6 R centred on the cell's carrier (frame_start counts in that buffer's samples),
+ * n_fft = 128 R with R in {1, 2, 4, 8, 16}, n_rb resource blocks with 6 <= n_rb <= {6, 15, 25, 50, 100}[log2 R] (fewer than the
+ * cell has is fine), n_ofdm rows with 2 n_symb <= n_ofdm <= 122 n_symb, and a dl_mask as above:
+ *   positions   extract_tfg's with the caller's rate (src/searcher.cpp:875-934): k_factor = (fc_requested - freq_fine) / fc_programmed;
+ *               the first DFT starts at frame_start + {10 | 32} 16 / FS_LTE fs_programmed k_factor, moved 10 ms back where that stays
+ *               > -0.5; the steps are (128 + 9 | 10 | 32) 16 / FS_LTE fs_programmed k_factor; every DFT is taken at round_i of its location
+ *   correction  sample i of the buffer is turned by fshift(-freq_fine, fs_programmed k_factor), i.e. by exp(j pi kk i) with
+ *               kk = -freq_fine / (fs_programmed k_factor / 2), the phase kk i formed in double and reduced exactly (sincospi)
+ *   grid row    concat(dft.right(6 n_rb), dft.mid(1, 6 n_rb)) of the n_fft samples, dft = fft / sqrt(n_fft) as the reference's, times
+ *               exp(-j 2 pi late / n_fft cn), late = round_i(location) - location, cn = -6 n_rb .. -1, 1 .. 6 n_rb: 12 n_rb columns
+ *   rs          36.211 6.10.1.1 for N_RB = n_rb: r(m'), m' = m + 110 - n_rb, m = 0 .. 2 n_rb - 1 (at n_rb = 6 RS_DL's twelve); the
+ *               shifts of ports 0 and 1 as above
+ *   per row, port   h_m = tfg[row][shift_p + 6 m] conj(rs[m]);  a_p = sum_{m < 2 n_rb - 1} h_m conj(h_{m+1});  e_p = sum_m |h_m|^2
+ *   per row     w = sum_k |tfg[row][k]|^2;  per resource block i: b_p[i] = h_{2i} conj(h_{2i+1}), w[i] = the power of its 12 columns
+ *   rsrp[p]     |A_p| / ((2 n_rb - 1) n_rows);  noise[p] = E_p / (2 n_rb n_rows) - rsrp[p];  rssi = W / n_rows;  rsrq = n_rb rsrp[0] / rssi
+ *   rsrp_rb[p][i]   |B_p[i]| / n_rows;  rssi_rb[i] = W[i] / n_rows;  entries i >= n_rb are zero
+ * over port 0's reference rows under the mask, as above; status and the conditions for "no number" are lcs_meas_info's (the per-RB
+ * arrays are then zero as well).  Resource block 0 is the lowest in frequency (columns 0 .. 11 of a grid row).  UNITS are the
+ * buffer's power per sample, as above; the same cell fills 1 / R of the bins of a buffer at 1.92e6 R, so its rsrp, noise and rssi
+ * read R times (10 log10 R dB above) what they read at 1.92 Msps.  rsrq and the SINR are ratios. */
+#define LCS_MEAS_WIDE_MAX_RB 100
+typedef struct lcs_meas_wide_info {
+  int32_t status, n_rows, n_ports, dl_mask;
+  int32_t n_rb, n_fft, reserved_i[2];
+  double rsrp[2], noise[2], rssi, rsrq, a_re_im[4];
+  double reserved[2];
+  double rsrp_rb[2][LCS_MEAS_WIDE_MAX_RB];
+  double rssi_rb[LCS_MEAS_WIDE_MAX_RB];
+} lcs_meas_wide_info;     /* 2528 bytes */
 
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
@@ -351,6 +383,22 @@ int lcs_tdd_config(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, 
  * lcs_last_error text) a cell without identity or CP type, an n_ofdm outside the range, and a dl_mask that is 0 or has a bit
  * above bit 9. */
 int lcs_cell_meas(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, int n_ofdm, int dl_mask, lcs_meas_info *out);
+
+/* The full-bandwidth grid and measurement (the rule: lcs_meas_wide_info above) on wide samples that are already on the device:
+ * d_capbuf holds n_cap complex<float> samples at fs_programmed, 8-byte aligned -- a channel of lcs_channelize at decim = K / R of a
+ * K x 1.92 Msps capture, centred on the cell.  lcs_extract_tfg_wide hands out all n_ofdm rows, [n_ofdm][12 n_rb] (re, im) pairs, and
+ * their ideal locations (timestamp_out, or NULL); lcs_cell_meas_wide transforms port 0's reference rows only.  Both wait for the
+ * context's stream, work whatever the context's modes are and with a stream open, and leave the modes and the last fused call's
+ * tables alone; their device buffers are allocated on first use.  They refuse (LCS_ERR_BAD_ARG, an lcs_last_error text), launching
+ * nothing: a null pointer or a misaligned buffer; an n_fft that is not 128 {1, 2, 4, 8, 16}; |fs_programmed / (15000 n_fft) - 1| >=
+ * 1e-3; an n_rb or n_ofdm outside its range; a dl_mask that is 0 or has a bit above bit 9; a cell without n_id_1, n_id_2 or CP
+ * type; and a capture that does not hold every requested row (one starts before sample 0, or round_i(location) + n_fft > n_cap). */
+int lcs_extract_tfg_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                         double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                         double *tfg_out_re_im /*host [n_ofdm][12 n_rb][2]*/, double *timestamp_out /*host [n_ofdm] or NULL*/);
+int lcs_cell_meas_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                       double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                       int dl_mask, lcs_meas_wide_info *out);
 
 /* ---- fused chain ------------------------------------------------------------------- */
 

@@ -119,6 +119,27 @@ class Searcher {
     check(lcs_cell_meas(h_, &cell, g.data(), tfg.rows(), dl_mask, &out));
     return out;
   }
+  // ... and over the cell's whole bandwidth, from complex<float> samples at 15 kHz x n_fft that are on the device, centred on the
+  // cell (lcs_cell_meas_wide / lcs_extract_tfg_wide: n_fft = 128 R, R in 1, 2, 4, 8, 16; cell.frame_start counts in those samples).
+  // The grid comes as [n_ofdm][12 n_rb]; timestamps: the rows' ideal locations
+  lcs_meas_wide_info cell_meas_wide(const Cell &cell, const void *d_capbuf, uint32_t n_cap, double fc_requested, double fc_programmed,
+                                    double fs_programmed, int n_fft, int n_rb, int n_ofdm, int dl_mask = 0x3ff) {
+    lcs_meas_wide_info out;
+    check(lcs_cell_meas_wide(h_, &cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm, dl_mask, &out));
+    return out;
+  }
+  void extract_tfg_wide(const Cell &cell, const void *d_capbuf, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed,
+                        int n_fft, int n_rb, int n_ofdm, cn::cmat &tfg, cn::vec &tfg_timestamp) {
+    const int nc = 12 * (n_rb > 0 ? n_rb : 0), n = n_ofdm > 0 ? n_ofdm : 0;
+    std::vector<double> g((size_t)n * nc * 2);
+    tfg_timestamp.set_size(n);
+    check(lcs_extract_tfg_wide(h_, &cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm, g.data(),
+                               tfg_timestamp._data()));
+    tfg.set_size(n, nc);
+    for (int r = 0; r < n; ++r)
+      for (int c = 0; c < nc; ++c) tfg(r, c) = std::complex<double>(g[((size_t)r * nc + c) * 2], g[((size_t)r * nc + c) * 2 + 1]);
+  }
+  static double sinr(const lcs_meas_wide_info &m, int p = 0) { return m.noise[p] > 0 ? m.rsrp[p] / m.noise[p] : std::numeric_limits<double>::infinity(); }
   static int tdd_dl_mask(int ul_dl_config) { return lcs_tdd_dl_mask(ul_dl_config); }
   // the SINR of port p of a record: rsrp / noise, infinite where noise <= 0
   static double sinr(const lcs_meas_info &m, int p = 0) { return m.noise[p] > 0 ? m.rsrp[p] / m.noise[p] : std::numeric_limits<double>::infinity(); }

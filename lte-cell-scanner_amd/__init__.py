@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -456,6 +456,40 @@ class Searcher:
         rc = self._lib.lcs_last_cell_meas(self._h, info, max_cells_per_buf)
         self._note_overflow(self._chk(rc, "lcs_last_cell_meas", allow_overflow=True), "lcs_last_cell_meas")
         return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
+
+    # ---- the full-bandwidth grid and measurement (lcs_extract_tfg_wide, lcs_cell_meas_wide) ---
+    @staticmethod
+    def _wide_samples(d_capbuf, n_cap):
+        """a device pointer with its sample count, or a torch tensor of complex64 on the device (its whole length unless n_cap says less)"""
+        if hasattr(d_capbuf, "data_ptr"):
+            t = d_capbuf
+            if str(t.dtype) != "torch.complex64" or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("the wide samples are a contiguous complex64 tensor on the device, or a device pointer and n_cap")
+            return int(t.data_ptr()), int(t.numel() if n_cap is None else n_cap)
+        if n_cap is None:
+            raise ValueError("a device pointer needs n_cap")
+        return int(d_capbuf), int(n_cap)
+
+    def extract_tfg_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, n_cap=None):
+        """The grid of a cell over n_rb resource blocks from complex64 samples at fs_programmed = 15 kHz x n_fft that are on the
+        device, centred on the cell (a channel of channelize at decim = K / R): n_fft = 128 R, R in 1, 2, 4, 8, 16; cell.frame_start
+        counts in those samples.  -> (tfg [n_ofdm][12 n_rb] complex128, the rows' ideal locations [n_ofdm])."""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        tfg = np.empty((max(int(n_ofdm), 0), 12 * max(int(n_rb), 0)), np.complex128)
+        ts = np.empty(max(int(n_ofdm), 0))
+        self._chk(self._lib.lcs_extract_tfg_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                                 float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), _dp(tfg), _dp(ts)), "lcs_extract_tfg_wide")
+        return tfg, ts
+
+    def cell_meas_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                       n_cap=None):
+        """RSRP, RSSI, RSRQ and the noise power over n_rb resource blocks, with the per-RB profile, from the same samples
+        (lcs_cell_meas_wide: only port 0's reference rows are transformed) -> CellMeasWide"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        out = capi.CellMeasWide()
+        self._chk(self._lib.lcs_cell_meas_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                               float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(out)), "lcs_cell_meas_wide")
+        return out
 
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route

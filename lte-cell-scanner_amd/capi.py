@@ -135,10 +135,58 @@ def _db10(x: float) -> float:
 
 assert C.sizeof(CellMeas) == 128
 
+MEAS_WIDE_MAX_RB = 100
+
+
+class CellMeasWide(C.Structure):
+    """lcs_meas_wide_info: the measurement of CellMeas over n_rb resource blocks of an n_fft-point grid taken from wide samples
+    (include/lcs.h: lcs_cell_meas_wide), with a per-RB profile: rsrq = n_rb rsrp[0] / rssi; rsrp_rb[p][i] and rssi_rb[i] per resource
+    block, lowest frequency first (numpy views of the record, cut to n_rb; the record's arrays hold 100 entries, zero beyond n_rb)."""
+    _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_ports", C.c_int32), ("dl_mask", C.c_int32), ("n_rb", C.c_int32), ("n_fft", C.c_int32),
+                ("reserved_i", C.c_int32 * 2), ("rsrp", C.c_double * 2), ("noise", C.c_double * 2), ("rssi", C.c_double), ("rsrq", C.c_double),
+                ("a_re_im", C.c_double * 4), ("reserved", C.c_double * 2), ("_rsrp_rb", (C.c_double * MEAS_WIDE_MAX_RB) * 2), ("_rssi_rb", C.c_double * MEAS_WIDE_MAX_RB)]
+
+    def copy(self) -> "CellMeasWide":
+        o = CellMeasWide()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(CellMeasWide))
+        return o
+
+    def _n(self) -> int:
+        return min(max(int(self.n_rb), 0), MEAS_WIDE_MAX_RB)
+
+    @property
+    def rsrp_rb(self):
+        """[2][n_rb] view: |B_p[i]| / n_rows per port and resource block"""
+        import numpy as np
+        return np.ctypeslib.as_array(self._rsrp_rb)[:, :self._n()]
+
+    @property
+    def rssi_rb(self):
+        """[n_rb] view: the power of each resource block's 12 columns per reference row"""
+        import numpy as np
+        return np.ctypeslib.as_array(self._rssi_rb)[:self._n()]
+
+    measured = CellMeas.measured
+    sinr = CellMeas.sinr
+    rsrp_db = CellMeas.rsrp_db
+    rsrq_db = CellMeas.rsrq_db
+    sinr_db = CellMeas.sinr_db
+
+    def as_dict(self) -> dict:
+        return dict(status=self.status, n_rows=self.n_rows, n_ports=self.n_ports, dl_mask=self.dl_mask, n_rb=self.n_rb, n_fft=self.n_fft, rsrp=list(self.rsrp),
+                    noise=list(self.noise), rssi=self.rssi, rsrq=self.rsrq, a_re_im=list(self.a_re_im), rsrp_rb=self.rsrp_rb.tolist(), rssi_rb=self.rssi_rb.tolist())
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"CellMeasWide(status={self.status}, n_rb={self.n_rb}, n_fft={self.n_fft}, n_rows={self.n_rows}, rsrp={list(self.rsrp)}, rsrq={self.rsrq:.4f})"
+
+
+assert C.sizeof(CellMeasWide) == 2528
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -211,6 +259,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_cell_meas.argtypes = [vp, C.POINTER(LcsCell), C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(CellMeas)]
         L.lcs_last_cell_meas.argtypes = [vp, C.POINTER(CellMeas), C.c_int]
         L.lcs_tdd_dl_mask.argtypes = [C.c_int]
+    if hasattr(L, "lcs_cell_meas_wide"):      # (likewise)
+        L.lcs_extract_tfg_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, dp]
+        L.lcs_cell_meas_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(CellMeasWide)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

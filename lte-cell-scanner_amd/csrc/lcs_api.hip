@@ -12,6 +12,8 @@
 #include "lte_device.h"
 #include "tdd_config.h"
 #include "cell_meas.h"
+#include "cell_meas_wide.h"
+#include "tfg_layout.h"
 #include "pss_ref.h"
 
 namespace {
@@ -1081,6 +1083,98 @@ int lcs_cell_meas(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofd
   if ((rc = lcs_launch_rs_build(c, L))) return rc;
   if ((rc = lcs_launch_cell_meas(c, L, nullptr, d_out, dl_mask, true))) return rc;
   HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(lcs_meas_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+// ---- the full-bandwidth grid and measurement (tfg_wide.hip, cell_meas_wide.h).  They touch the context's stream and the blocks of
+// c->meas_wide and nothing else: no workspace, no mode, no table of a fused call -- so they run beside an open stream as well.
+namespace {
+int wide_refused(lcs_ctx *c, const char *who, const char *what) {
+  c->err = std::string(who) + ": " + what;
+  return LCS_ERR_BAD_ARG;
+}
+// What the two entry points refuse alike, then extract_tfg's walk (ref src/searcher.cpp:875-920) with the caller's rate: ts[t] = the
+// ideal location of row t; *kk = the frequency correction's phase step in half turns per sample (fshift, ref dsp.h:40-53)
+int wide_rows(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_cap, double fc_req, double fc_prog, double fs_prog, int n_fft,
+              int n_rb, int n_ofdm, std::vector<double> *ts, double *kk) {
+  if (!cell || !d_cap) return wide_refused(c, who, "a null pointer");
+  if (reinterpret_cast<uintptr_t>(d_cap) & 7) return wide_refused(c, who, "d_capbuf is not aligned to a complex<float>");
+  if (measw_log2r(n_fft) < 0) return wide_refused(c, who, "n_fft is not 128, 256, 512, 1024 or 2048");
+  if (!(fabs(fs_prog / (15000.0 * n_fft) - 1.0) < 1e-3)) return wide_refused(c, who, "fs_programmed is not 15 kHz x n_fft to within 1e-3");
+  if (!measw_rb_ok(n_fft, n_rb)) return wide_refused(c, who, "n_rb is outside 6 .. {6, 15, 25, 50, 100} for n_fft = 128 {1, 2, 4, 8, 16}");
+  const int full = n_ofdm_for(cell);
+  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2)
+    return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  const int n_symb = full == 854 ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  const double k_factor = (fc_req - cell->freq_fine) / fc_prog;
+  double loc;
+  if (cell->cp_type == LCS_CP_NORMAL) loc = cell->frame_start + 10 * 16 / FS_LTE * fs_prog * k_factor;
+  else loc = cell->frame_start + 32 * 16 / FS_LTE * fs_prog * k_factor;
+  if (loc - .01 * fs_prog * k_factor > -0.5) loc = loc - .01 * fs_prog * k_factor;
+  const double inc_ext = (128 + 32) * 16 / FS_LTE * fs_prog * k_factor;
+  const double inc_10 = (128 + 10) * 16 / FS_LTE * fs_prog * k_factor;
+  const double inc_9 = (128 + 9) * 16 / FS_LTE * fs_prog * k_factor;
+  ts->resize((size_t)n_ofdm);
+  int sym_num = 0;
+  for (int t = 0; t < n_ofdm; ++t) {
+    (*ts)[t] = loc;
+    if (n_symb == 6) loc += inc_ext;
+    else { loc += (sym_num == 6) ? inc_10 : inc_9; sym_num = (sym_num + 1) % 7; }
+  }
+  *kk = (-cell->freq_fine) / ((fs_prog * k_factor) / 2);
+  if (!std::isfinite((*ts)[0]) || !std::isfinite((*ts)[(size_t)n_ofdm - 1]) || !std::isfinite(*kk))
+    return wide_refused(c, who, "the cell's frame_start / freq_fine and the frequencies give no finite positions");
+  return LCS_OK;
+}
+// every requested row inside the capture: the locations grow, so the first and the last decide
+int wide_rows_fit(lcs_ctx *c, const char *who, const std::vector<double> &ideal, int n_fft, uint32_t n_cap) {
+  const double first = rint(ideal.front()), last = rint(ideal.back());
+  if (first < 0.0) return wide_refused(c, who, "the first requested row starts before sample 0 of the capture");
+  if (last + (double)n_fft > (double)n_cap) return wide_refused(c, who, "the capture does not hold the last requested row (round_i(location) + n_fft > n_cap)");
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_extract_tfg_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                         int n_fft, int n_rb, int n_ofdm, double *tfg, double *timestamp) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_extract_tfg_wide";
+  if (!tfg) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if ((rc = wide_rows_fit(c, who, ts, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ts.data(), n_ofdm, kk, n_fft, n_rb))) return rc;
+  HIPCHK(c, hipMemcpyAsync(tfg, c->meas_wide.grid, sizeof(double2) * (size_t)n_ofdm * 12 * n_rb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (timestamp) std::memcpy(timestamp, ts.data(), sizeof(double) * (size_t)n_ofdm);
+  return LCS_OK;
+}
+
+int lcs_cell_meas_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                       int n_fft, int n_rb, int n_ofdm, int dl_mask, lcs_meas_wide_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_cell_meas_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  // port 0's reference rows only: reference row q is row q of the device's grid
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_q = tdd_n_ref_rows(n_ofdm, n_symb);
+  static_assert(2 * 122 <= TC_MAX_Q, "the reference rows of 122 slots fit the per-row table");
+  std::vector<double> ideal((size_t)n_q);
+  for (int q = 0; q < n_q; ++q) ideal[q] = ts[(size_t)tdd_grid_row(q, n_symb)];
+  if ((rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), n_q, kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_cell_meas_wide(c, *cell, n_q, n_fft, n_rb, dl_mask))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->meas_wide.rec, sizeof(lcs_meas_wide_info), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
 }

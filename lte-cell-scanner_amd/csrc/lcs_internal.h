@@ -352,6 +352,18 @@ struct lcs_ctx : lcs_ctx_queues {
   int cell_meas = 0;                // lcs_set_cell_meas: likewise
   DevBuf<lcs_meas_info> cell_meas_tab;   // [n_buf][LCS_MAXP], laid out like `peaks`: what k_cell_meas writes in the fused chain
   bool meas_made = false;           // whether the last fused call (tdd_n_buf buffers) ran k_cell_meas: otherwise its table is LCS_MEAS_NOT_MEASURED throughout
+  // the full-bandwidth grid and measurement (tfg_wide.hip: lcs_extract_tfg_wide, lcs_cell_meas_wide): every block is allocated by
+  // the first call that needs it and grown on demand; a context that never calls the stage holds none of them
+  struct MeasWide {
+    DevBuf<double2> tw[5];          // [n_fft / 2] per n_fft = 128 << i: the transform's twiddles W^t, built in double on the host by the first call at that length
+    DevBuf<double2> grid;           // [rows][12 n_rb]: the rows of the last call
+    DevBuf<double> ideal;           // [rows]: the ideal location of every requested row
+    DevBuf<double> rowv;            // [MEAS_NV][TC_MAX_Q]: the seven values of every reference row
+    DevBuf<double> binrb;           // [40][MEASW_NRB][100]: the per-RB values of every bin
+    DevBuf<uint32_t> pn_jump;       // [32]: Gold-sequence jump-ahead to c(2 (110 - n_rb)) of the call's n_rb
+    uint32_t h_pn_jump[32] = {};    // ... and the host block it is uploaded from (it outlives the launcher's frame)
+    DevBuf<lcs_meas_wide_info> rec; // [1]
+  } meas_wide;
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -506,4 +518,10 @@ int lcs_launch_tdd_config(lcs_ctx *c, const Launch &L, lcs_tdd_info *out /*devic
 // cell_meas.hip
 int lcs_launch_cell_meas(lcs_ctx *c, const Launch &L, const lcs_tdd_info *tdd /*device: this launch's k_tdd_config table, or null*/, lcs_meas_info *out /*device*/,
                          int dl_mask, bool force /* the stage: out[item] with dl_mask, whatever the record carries */);
+// tfg_wide.hip
+// rows of an n_fft-point grid from complex<float> samples on the device: row i is taken at round_i(h_ideal[i]) and lands in
+// c->meas_wide.grid[i][12 n_rb].  kk: the frequency correction's phase step in half turns per sample
+int lcs_launch_tfg_wide(lcs_ctx *c, const float2 *d_cap, uint32_t n_cap, const double *h_ideal, int n_rows, double kk, int n_fft, int n_rb);
+// the measurement on the n_q reference rows that call left in c->meas_wide.grid -> c->meas_wide.rec
+int lcs_launch_cell_meas_wide(lcs_ctx *c, const lcs_cell &cell, int n_q, int n_fft, int n_rb, int dl_mask);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

@@ -349,6 +349,48 @@ __device__ __forceinline__ void rs_dl_row(int slot, int t, int id, int cp_type, 
   }
 }
 
+// ---- the same row for N_RB = n_rb resource blocks (36.211 6.10.1.1: r(m'), m' = m + 110 - n_rb, m = 0 .. 2 n_rb - 1; the twelve
+// centre values of every n_rb are rs_dl_row's).  The sequence comes as BITS -- bit 2 m of the word array is c(2 m'), bit 2 m + 1 is
+// c(2 m' + 1), (4 n_rb + 31) / 32 words -- and rs_dl_wide_value turns entry m into its value; the shifts as rs_dl_row.
+// pn_jump: the jump-ahead table for 1600 + 2 * (110 - n_rb) clocks (lcs_tables::pn_jump_table)
+#define RS_DL_WIDE_WORDS 13                           // 4 * 100 bits
+__host__ __device__ __forceinline__ void rs_dl_row_wide(int slot, int t, int id, int cp_type, int n_symb, int n_rb, const uint32_t *__restrict__ pn_jump,
+                                                        uint32_t *bits /*[(4 n_rb + 31) / 32]*/, double *shift4) {
+  const int sym = (t == 2) ? (n_symb - 3) : t;
+  const uint32_t n_cp = (cp_type == LCS_CP_NORMAL);
+  const uint32_t c_init = (1u << 10) * (7 * (slot + 1) + sym + 1) * (2 * id + 1) + 2 * id + n_cp;
+  uint32_t x1 = pn_jump[31], x2 = 0;
+  for (int b = 0; b < 31; ++b) if ((c_init >> b) & 1u) x2 ^= pn_jump[b];
+  const int n_bits = 4 * n_rb;
+  for (int i0 = 0; i0 < n_bits; i0 += 32) {
+    uint32_t word = 0;
+    for (int i = 0; i < 32 && i0 + i < n_bits; ++i) {
+      word |= ((x1 ^ x2) & 1u) << i;
+      const uint32_t n1 = ((x1 >> 3) ^ x1) & 1u;
+      const uint32_t n2 = ((x2 >> 3) ^ (x2 >> 2) ^ (x2 >> 1) ^ x2) & 1u;
+      x1 = (x1 >> 1) | (n1 << 30);
+      x2 = (x2 >> 1) | (n2 << 30);
+    }
+    bits[i0 >> 5] = word;
+  }
+  for (int port = 0; port < 4; ++port) {
+    int v = -1;
+    if (port == 0 && sym == 0) v = 0;
+    else if (port == 0 && sym == n_symb - 3) v = 3;
+    else if (port == 1 && sym == 0) v = 3;
+    else if (port == 1 && sym == n_symb - 3) v = 0;
+    else if (port == 2 && sym == 1) v = 3 * (slot & 1);
+    else if (port == 3 && sym == 1) v = 3 + 3 * (slot & 1);
+    const bool want = (t == 0 || t == 2) ? (port <= 1) : (port >= 2);
+    if (want && v >= 0) shift4[port] = (double)((v + id) % 6);
+  }
+}
+__host__ __device__ __forceinline__ cd2 rs_dl_wide_value(const uint32_t *bits, int m) {
+  const double isq = 1 / sqrt(2.0);
+  const uint32_t two = (bits[m >> 4] >> (2 * (m & 15))) & 3u;
+  return mk(isq * (1 - 2 * (int)(two & 1u)), isq * (1 - 2 * (int)(two >> 1)));
+}
+
 // ---- soft demodulation of one QPSK symbol: exact log-MAP as itpp::Modulator::demodulate_soft_bits (LOGMAP) with
 // rx = sym/sqrt(np), channel = 1/sqrt(np), N0 = 1 (ref src/lte_lib.cpp:612-634)
 __device__ __forceinline__ double trunc_log(double x) {     // itpp::trunc_log

@@ -187,6 +187,116 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     return cells
 
 
+MEAS_MAX_RB = {1: 6, 2: 15, 4: 25, 8: 50, 16: 100}      # the resource blocks a 128 R-point grid holds (lcs_cell_meas_wide)
+
+
+def meas_rate(n_rb: int) -> int:
+    """R of the narrowest measurement rate 1.92e6 R whose grid holds n_rb resource blocks"""
+    for R, most in MEAS_MAX_RB.items():
+        if 6 <= n_rb <= most:
+            return R
+    raise ValueError(f"measure_wideband: no measurement rate holds n_rb = {n_rb} (6 .. 100)")
+
+
+def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> float:
+    """A position in the outputs of channelize(decim_search) as a position in the outputs of channelize(decim_meas) of the same
+    capture.  Output m of a decimation D is the filter centred on wide sample m D + (16 D - 1) / 2 (include/lcs.h: lcs_channelize),
+    so the wide sample of the one is read back through the other; decim_meas = 1 is the capture itself (no filter, no delay)."""
+    wide = frame_start * decim_search + (16 * decim_search - 1) / 2
+    return (wide - ((16 * decim_meas - 1) / 2 if decim_meas > 1 else 0.0)) / decim_meas
+
+
+def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
+                     carriers, n_rb: int = None, dl_mask: int = None):
+    """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
+    cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
+    For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
+    carrier with decim_meas = K / R (K = fs_in / 1.92e6; the integer path only, decim_meas >= 2) into complex64 at 1.92e6 R, the
+    cell's frame_start is mapped into that buffer (map_frame_start; a negative position is advanced by whole frames), and the stage
+    measures as many whole slots as the buffer holds, 122 at the most.  K == R is accepted only for a complex64 capture already
+    centred on the carrier, which is measured in place.  dl_mask: None takes the narrow record's where the cell carries one
+    (meas=True), else 0x3FF (FDD) / 0x021 (TDD, the searcher's duplex mode).
+    Returns one list per carrier, entry k belonging to cell k: a capi.CellMeasWide, or None for a cell without a MIB; a dict cell
+    also gets it as cell["meas_wide"].  The wide records come from float carriers and need no gain, whatever `out` the search used.
+    Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
+    carrier or in an integer format, and for a capture too short for two slots of the cell."""
+    import ctypes as C
+    import torch
+    from . import capi
+    carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
+    if len(cells_per_carrier) != carriers.size:
+        raise ValueError(f"measure_wideband: {len(cells_per_carrier)} cell lists, {carriers.size} carriers")
+    K = float(fs_in) / 1.92e6
+    if abs(K - round(K)) > 1e-9 * K or round(K) < 1:
+        raise ValueError(f"measure_wideband: fs_in = {fs_in} is no integer multiple of 1.92 Msps; rational-rate captures are not measured")
+    K, D_s = int(round(K)), int(decim_search)
+    dev = getattr(searcher, "device", -1)
+    tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
+    bufs = {}                                             # decim_meas -> (buffer, the carrier it holds)
+    out = []
+    for fc, cells in zip(carriers, cells_per_carrier):
+        row = []
+        for cell in cells:
+            d = cell if isinstance(cell, dict) else None
+            get = (lambda k: d[k]) if d is not None else (lambda k: getattr(cell, k))
+            if get("n_rb_dl") not in (6, 15, 25, 50, 75, 100) or get("cp_type") not in (1, 2):
+                row.append(None)
+                continue
+            rb = int(n_rb) if n_rb is not None else int(get("n_rb_dl"))
+            R = meas_rate(rb)
+            if K % R or K < R:
+                raise ValueError(f"measure_wideband: {rb} resource blocks need 1.92e6 x {R} samples per second, which fs_in = {fs_in} (K = {K}) does not give by an integer decimation")
+            D_m = K // R
+            if D_m == 1:
+                if fmt != capi.FMT_C64 or float(fc) != float(fc_centre):
+                    raise ValueError("measure_wideband: K / R < 2 -- the capture is used in place, which takes a complex64 capture centred on the cell's carrier")
+                ptr, n_cap = int(d_wide_ptr), int(n_in)
+            else:
+                if not 2 <= D_m <= 16:
+                    raise ValueError(f"measure_wideband: decim_meas = {D_m} is outside the channelizer's 2 .. 16")
+                n_cap = (int(n_in) - 16 * D_m) // D_m + 1
+                if D_m not in bufs:
+                    bufs[D_m] = [torch.empty(max(n_cap, 1), dtype=torch.complex64, device=tdev), None]
+                if bufs[D_m][1] != float(fc):
+                    searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, D_m, [float(fc) - float(fc_centre)], bufs[D_m][0].data_ptr(), n_cap)
+                    bufs[D_m][1] = float(fc)
+                ptr = bufs[D_m][0].data_ptr()
+            fs_m = float(fs_in) / D_m
+            n_symb = 7 if get("cp_type") == 1 else 6      # LCS_CP_NORMAL / LCS_CP_EXTENDED
+            k_factor = (float(fc) - get("freq_fine")) / float(fc)
+            frame = 0.01 * fs_m * k_factor
+            start = map_frame_start(get("frame_start"), D_s, D_m)
+            while start < 0:
+                start += frame
+            # whole slots between the first DFT the stage takes (it moves 10 ms back where it can) and the buffer's end
+            first = start + (10 if n_symb == 7 else 32) * R * k_factor
+            if first - frame > -0.5:
+                first -= frame
+            n_slots = int((n_cap - 128 * R - first) / (frame / 20)) - 1
+            if n_slots < 2:
+                raise ValueError("measure_wideband: the capture holds less than two slots of the cell at the measurement rate")
+            if d is None:
+                mc = capi.LcsCell.from_buffer_copy(bytes(cell))
+            else:
+                mc = capi.LcsCell()
+                searcher._lib.lcs_cell_init(C.byref(mc))
+                for f in FIELDS:
+                    setattr(mc, f, d[f])
+            mc.frame_start = start
+            if dl_mask is not None:
+                mask = int(dl_mask)
+            elif d is not None and getattr(d.get("meas"), "status", -1) == 0:
+                mask = int(d["meas"].dl_mask)
+            else:
+                mask = 0x3FF if searcher.duplex == capi.DUPLEX_FDD else 0x021
+            rec = searcher.cell_meas_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
+            if d is not None:
+                d["meas_wide"] = rec
+            row.append(rec)
+        out.append(row)
+    return out
+
+
 class WidebandFeed:
     """A band search from a wideband STREAM: push() takes the front end's transfer buffers as they come (n_samples of fmt at fs_in,
     centred on fc_centre, resident in HBM), the searcher's channelizer stream (Searcher.chan_stream_open, rate = (up, down),

@@ -489,3 +489,203 @@ def wideband_to_complex(iq, fmt):
     sc = 128.0 if fmt == capi.FMT_IQ_S8 else 32768.0
     a = np.asarray(iq, np.int8 if fmt == capi.FMT_IQ_S8 else np.int16).astype(np.float64)
     return (a[0::2] + 1j * a[1::2]) / sc
+
+
+# ---- cells wider than the 6 centre resource blocks: what lcs_cell_meas_wide measures ------------------------------------------
+def _crs_wide(n_id_cell, slot, sym, cp_normal, n_rb):
+    """2 n_rb CRS values of an n_rb-RB carrier (36.211 6.10.1.1: r(m'), m' = m + 110 - n_rb); the twelve centre ones are _crs's."""
+    c_init = (1 << 10) * (7 * (slot + 1) + sym + 1) * (2 * n_id_cell + 1) + 2 * n_id_cell + (1 if cp_normal else 0)
+    c = _pn(c_init, 440).astype(np.float64)
+    m = np.arange(2 * n_rb) + 110 - n_rb
+    return ((1 - 2 * c[2 * m]) + 1j * (1 - 2 * c[2 * m + 1])) / np.sqrt(2.0)
+
+
+def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
+                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0):
+    """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,
+    CP lengths R * {10, 9, 32}), n_frames * 19200 * R samples from the boundary of frame sfn0.  The 72 centre subcarriers carry what
+    cell_waveform puts there -- PSS, SSS, PBCH (the MIB says n_rb_dl: n_rb where that is an LTE bandwidth, else 50), CRS and load --
+    and the other 12 n_rb - 72 carry the CRS of the n_rb sequence and load in every symbol that is sent.  Unit power per resource
+    element before port_gains / sqrt(n_ports), so a reference element of port p has power |port_gains[p]|^2 / n_ports.  per_port and
+    tdd as for cell_waveform.  A function of its own: its draws from rng are not cell_waveform's."""
+    rng = rng or np.random.default_rng(0)
+    R, n_rb = int(R), int(n_rb)
+    n_fft, nc, c0 = 128 * R, 12 * n_rb, 6 * n_rb - 36          # c0: the first of the 72 centre columns
+    if R not in (1, 2, 4, 8, 16) or not 6 <= n_rb or 12 * n_rb >= n_fft:
+        raise ValueError("cell_waveform_wide: R in 1, 2, 4, 8, 16 and 6 <= n_rb with 12 n_rb < 128 R")
+    if n_rb_dl is None:
+        n_rb_dl = n_rb if n_rb in _BW_IDX else 50
+    n_id_cell = n_id_2 + 3 * n_id_1
+    n_symb = 7 if cp_normal else 6
+    v_shift = n_id_cell % 6
+    if per_port:
+        port_gains = np.eye(n_ports)
+    elif port_gains is None:
+        port_gains = np.exp(2j * np.pi * rng.random(n_ports)) * (0.8 + 0.4 * rng.random(n_ports))
+    port_gains = np.asarray(port_gains, np.complex128) / np.sqrt(n_ports)
+    pss = _pss_fd(n_id_2)
+    crs_cache = {}
+    n_frame = 19200 * R
+    out = np.zeros((n_ports, n_frames * n_frame) if per_port else n_frames * n_frame, np.complex128)
+    if tdd is not None:
+        kinds, dwpts = TDD_SUBFRAMES[int(tdd[0])], int(tdd[1])
+        if not 3 <= dwpts <= 2 * n_symb:
+            raise ValueError("dwpts_symbols must hold the PSS (>= 3) and fit the subframe")
+    centre = np.zeros(nc, bool)
+    centre[c0:c0 + 72] = True
+    pos = 0
+    pbch = None
+    for fr in range(n_frames):
+        sfn = (sfn0 + fr) % 1024
+        if pbch is None or sfn % 4 == 0:
+            pbch = pbch_symbols(n_id_cell, n_ports, n_rb_dl, phich_duration_ext, phich_res, sfn - (sfn % 4), cp_normal)
+        quarter = pbch.reshape(4, -1)[sfn % 4]
+        pb_i = 0
+        for slot in range(20):
+            for sym in range(n_symb):
+                cp = R * ((10 if sym == 0 else 9) if cp_normal else 32)
+                if tdd is not None:
+                    kind = kinds[slot >> 1]
+                    if kind == "U" or (kind == "S" and (slot & 1) * n_symb + sym >= dwpts):
+                        pos += cp + n_fft
+                        continue
+                grid = np.zeros((n_ports, nc), np.complex128)
+                reserved = np.zeros(nc, bool)
+                rs_here = {}
+                if sym == 0:
+                    rs_here = {0: 0, 1: 3}
+                elif sym == n_symb - 3:
+                    rs_here = {0: 3, 1: 0}
+                elif sym == 1:
+                    rs_here = {2: 3 * (slot & 1), 3: 3 + 3 * (slot & 1)}
+                if rs_here:
+                    key = (slot, sym)
+                    if key not in crs_cache:
+                        crs_cache[key] = _crs_wide(n_id_cell, slot, sym, cp_normal, n_rb)
+                    for port, v in rs_here.items():
+                        idx = (v + v_shift) % 6 + 6 * np.arange(2 * n_rb)
+                        reserved[idx] = True
+                        if port < n_ports:
+                            grid[port, idx] = crs_cache[key]
+                if tdd is None:
+                    is_sync = (slot % 10 == 0) and sym >= n_symb - 2
+                    is_pss = sym == n_symb - 1
+                else:
+                    is_pss = (slot % 10 == 2) and sym == 2
+                    is_sync = is_pss or ((slot % 10 == 1) and sym == n_symb - 1)
+                is_pbch = (slot == 1) and sym <= 3
+                if is_sync:
+                    seq = pss if is_pss else _sss_fd(n_id_1, n_id_2, slot - (slot % 10))
+                    grid[:, c0:c0 + 72] = 0
+                    grid[0, c0 + 5:c0 + 67] = seq * np.sqrt(n_ports)      # sync signals go out on port 0
+                    reserved |= centre
+                elif is_pbch:
+                    skip = (sym in (0, 1)) or (sym == 3 and not cp_normal)
+                    sc = c0 + np.array([k for k in range(72) if not (skip and k % 3 == v_shift % 3)])
+                    s = quarter[pb_i:pb_i + len(sc)]
+                    pb_i += len(sc)
+                    if n_ports == 1:
+                        grid[0, sc] = s
+                    else:
+                        s0, s1 = s[0::2], s[1::2]
+                        a = np.empty((2, len(sc)), np.complex128)
+                        a[0, 0::2], a[0, 1::2] = s0, s1
+                        a[1, 0::2], a[1, 1::2] = -np.conj(s1), np.conj(s0)
+                        a /= np.sqrt(2.0)
+                        if n_ports == 2:
+                            grid[0, sc], grid[1, sc] = a[0], a[1]
+                        else:   # SFBC-FSTD: pairs alternate between ports (0,2) and (1,3)
+                            pair = (np.arange(len(sc)) // 2) & 1
+                            for q, (p0, p1) in enumerate(((0, 2), (1, 3))):
+                                m = pair == q
+                                grid[p0, sc[m]] = a[0, m]
+                                grid[p1, sc[m]] = a[1, m]
+                    reserved |= centre
+                free = np.flatnonzero(~reserved)
+                on = free[rng.random(free.size) < load]
+                d = ((1 - 2.0 * rng.integers(0, 2, on.size)) + 1j * (1 - 2.0 * rng.integers(0, 2, on.size))) / np.sqrt(2.0)
+                grid[0, on] = d * np.sqrt(n_ports)     # single-layer data through port 0
+                mix = port_gains @ grid
+                X = np.zeros(mix.shape[:-1] + (n_fft,), np.complex128)
+                X[..., n_fft - 6 * n_rb:] = mix[..., :6 * n_rb]
+                X[..., 1:6 * n_rb + 1] = mix[..., 6 * n_rb:]
+                td = np.fft.ifft(X, axis=-1) * np.sqrt(float(n_fft))
+                out[..., pos:pos + cp] = td[..., -cp:]
+                out[..., pos + cp:pos + cp + n_fft] = td
+                pos += cp + n_fft
+    assert pos == out.shape[-1]
+    return out
+
+
+def make_signal_wide(rng, fc, cd, R, n_rb, n_cap):
+    """make_signal for ONE cell of cell_waveform_wide at 1.92e6 * R: the noise-free samples as a receiver at that rate takes them.
+    cd as for make_capbuf (t0 counts nominal 1.92 Msps samples into the first frame; no channel model).  -> (signal [n_cap], truth)"""
+    R = int(R)
+    n = np.arange(n_cap, dtype=np.float64)
+    f_off = float(cd.get("f_off", 0.0))
+    k_factor = (fc - f_off) / fc
+    t0 = float(cd.get("t0", rng.uniform(0, 19200)))
+    n_frames = int(np.ceil((n_cap / (R * k_factor) + t0) / 19200)) + 1
+    w = cell_waveform_wide(n_frames, cd["n_id_1"], cd["n_id_2"], R, n_rb, cd.get("cp_normal", True), cd.get("n_ports", 2), cd.get("load", 0.5), rng,
+                           cd.get("port_gains"), tdd=cd.get("tdd"), n_rb_dl=cd.get("n_rb_dl"), phich_duration_ext=cd.get("phich_duration_ext", 0),
+                           phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))))
+    y = frac_resample(w, t0 * R + n / k_factor)
+    y = y * np.exp(2j * np.pi * f_off * n / (FS * R * k_factor))
+    g = 10 ** (cd.get("gain_db", 0.0) / 20)
+    return g * y, dict(cd, t0=t0, n_id_cell=cd["n_id_2"] + 3 * cd["n_id_1"], k_factor=k_factor, R=R, n_rb=n_rb)
+
+
+def make_wideband_cell(seed, fc_centre, decim, wide_cells, placed=(), snr_db=10.0, fmt=capi.FMT_C64, n_in=None, rms=0.15):
+    """make_wideband with cells of cell_waveform_wide in it: one capture at decim x 1.92 Msps centred on fc_centre.
+    wide_cells: list of (carrier_hz, R, n_rb, cell) -- the cell's signal at 1.92e6 * R (make_signal_wide; R divides decim) is band-
+    limited-interpolated by decim / R and shifted by carrier_hz - fc_centre.  placed: narrow carriers as for make_wideband.  One AWGN
+    at the wide rate, snr_db below the PSS/SSS sample power of a gain_db = 0 cell inside a 1.92 MHz channel; AGC to rms; fmt as
+    make_wideband.  Returns (capture, truth, scale): truth is a list of (carrier_hz, [cell truth]) -- wide cells first --, scale the
+    factor the AGC applied (a reference element of port p then has power scale^2 |port_gains[p]|^2 / n_ports 10^(gain_db / 10))."""
+    decim = int(decim)
+    n_in = N_CAP * decim if n_in is None else int(n_in)
+    n_nb = -(-n_in // decim)
+    n_nb += n_nb & 1
+    n_w = n_nb * decim
+    rng = np.random.default_rng(seed)
+    n = np.arange(n_w, dtype=np.float64)
+    fs_in = FS * decim
+    wide = np.zeros(n_w, np.complex128)
+    truth = []
+
+    def place(sig, up, carrier):
+        n_s = sig.size
+        if up == 1:
+            y = sig
+        else:
+            X = np.fft.fft(sig)
+            Xw = np.zeros(n_w, np.complex128)
+            Xw[:n_s // 2] = X[:n_s // 2]
+            Xw[-(n_s // 2) + 1:] = X[n_s // 2 + 1:]      # (the Nyquist bin of the narrower signal is dropped)
+            y = np.fft.ifft(Xw) * up
+        return y * np.exp(2j * np.pi * ((float(carrier) - float(fc_centre)) / fs_in) * n)
+
+    for carrier, R, n_rb, cd in wide_cells:
+        R = int(R)
+        if decim % R:
+            raise ValueError("make_wideband_cell: R divides decim")
+        sig, tr = make_signal_wide(rng, float(carrier), cd, R, n_rb, n_nb * R)
+        wide += place(sig, decim // R, carrier)
+        truth.append((float(carrier), [tr]))
+    for carrier, cells in placed:
+        sig, _, tr = make_signal(rng, float(carrier), cells, n_nb)
+        wide += place(sig, decim, carrier)
+        truth.append((float(carrier), tr))
+    noise_pow = decim * (62.0 / 128.0) / 10 ** (snr_db / 10) if snr_db is not None else 0.0
+    x = (wide + np.sqrt(noise_pow / 2) * (rng.standard_normal(n_w) + 1j * rng.standard_normal(n_w)))[:n_in]
+    scale = rms / np.sqrt(np.mean(np.abs(x) ** 2))
+    x *= scale
+    if fmt == capi.FMT_C64:
+        return x.astype(np.complex64), truth, float(scale)
+    if fmt not in (capi.FMT_IQ_S8, capi.FMT_IQ_S16):
+        raise ValueError("make_wideband_cell: fmt is FMT_IQ_S8, FMT_IQ_S16 or FMT_C64")
+    dt, sc = (np.int8, 128.0) if fmt == capi.FMT_IQ_S8 else (np.int16, 32768.0)
+    iq = np.empty(2 * n_in, dt)
+    iq[0::2] = np.clip(np.rint(sc * x.real), -sc, sc - 1).astype(dt)
+    iq[1::2] = np.clip(np.rint(sc * x.imag), -sc, sc - 1).astype(dt)
+    return iq, truth, float(scale)
