@@ -84,12 +84,7 @@ class Searcher {
   // [n_buf][max_cells_per_buf], entry k of a buffer belonging to its k-th cell, LCS_TDD_NOT_ESTIMATED where nothing was estimated
   void set_tdd_config(bool on) { check(lcs_set_tdd_config(h_, on ? 1 : 0)); }
   bool tdd_config_mode() { int on = 0; check(lcs_get_tdd_config(h_, &on)); return on != 0; }
-  std::vector<lcs_tdd_info> last_tdd_info(int n_buf = 1, int max_cells_per_buf = 16) {
-    std::vector<lcs_tdd_info> info((size_t)n_buf * max_cells_per_buf);
-    const int rc = lcs_last_tdd_info(h_, info.data(), max_cells_per_buf);
-    if (rc != LCS_ERR_OVERFLOW) check(rc);
-    return info;
-  }
+  std::vector<lcs_tdd_info> last_tdd_info(int n_buf = 1, int max_cells_per_buf = 16) { return last_records(lcs_last_tdd_info, n_buf, max_cells_per_buf); }
   // ... and the estimate as a stage of its own (lcs_tdd_config): a cell with identity and CP type, its grid from extract_tfg
   lcs_tdd_info tdd_config(const Cell &cell, const cn::cmat &tfg) {
     std::vector<double> g;
@@ -104,12 +99,7 @@ class Searcher {
   // belonging to its k-th cell, status LCS_MEAS_NOT_MEASURED where nothing was measured
   void set_cell_meas(bool on) { check(lcs_set_cell_meas(h_, on ? 1 : 0)); }
   bool cell_meas_mode() { int on = 0; check(lcs_get_cell_meas(h_, &on)); return on != 0; }
-  std::vector<lcs_meas_info> last_cell_meas(int n_buf = 1, int max_cells_per_buf = 16) {
-    std::vector<lcs_meas_info> info((size_t)n_buf * max_cells_per_buf);
-    const int rc = lcs_last_cell_meas(h_, info.data(), max_cells_per_buf);
-    if (rc != LCS_ERR_OVERFLOW) check(rc);
-    return info;
-  }
+  std::vector<lcs_meas_info> last_cell_meas(int n_buf = 1, int max_cells_per_buf = 16) { return last_records(lcs_last_cell_meas, n_buf, max_cells_per_buf); }
   // ... and the measurement as a stage of its own (lcs_cell_meas): a cell with identity and CP type, its grid from extract_tfg, the
   // subframes to measure (bit s of dl_mask = subframe s; tdd_dl_mask(configuration) for a TDD cell)
   lcs_meas_info cell_meas(const Cell &cell, const cn::cmat &tfg, int dl_mask = 0x3ff) {
@@ -449,6 +439,13 @@ class Searcher {
   enum { LCS_MAX_CELLS_STREAM = 64 };
   void check(int rc) {
     if (rc != LCS_OK) throw error(std::string("liblcs_amd: ") + lcs_last_error(h_));
+  }
+  // a side table of the last fused call (lcs_last_tdd_info, lcs_last_cell_meas): LCS_ERR_OVERFLOW leaves what the array holds
+  template <class Rec> std::vector<Rec> last_records(int (*last)(lcs_ctx *, Rec *, int), int n_buf, int max_cells_per_buf) {
+    std::vector<Rec> info((size_t)n_buf * max_cells_per_buf);
+    const int rc = last(h_, info.data(), max_cells_per_buf);
+    if (rc != LCS_ERR_OVERFLOW) check(rc);
+    return info;
   }
   static void to3d(const std::vector<float> &flat, int n_f, vf3d &out) {
     out.assign(3, std::vector<std::vector<float> >(9600, std::vector<float>(n_f)));

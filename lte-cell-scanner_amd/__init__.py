@@ -256,12 +256,12 @@ class Searcher:
         return [[cells[b * max_cells_per_buf + i].copy() for i in range(min(cnt[b], max_cells_per_buf))]
                 for b in range(n_buf)]
 
-    def _note_overflow(self, rc, what):
+    def _note_overflow(self, rc, what, stacklevel=3):
         self.last_overflow = rc == -4
         if self.last_overflow:
             import warnings
             warnings.warn(f"{what}: LCS_ERR_OVERFLOW: {self._lib.lcs_last_error(self._h).decode()} (results truncated)",
-                          RuntimeWarning, stacklevel=3)
+                          RuntimeWarning, stacklevel=stacklevel)
 
     def batch_readback(self, buf: int, n_f: int):
         """xcorr_pss outputs of buffer `buf` of the last batch in the reference's layouts (debug)."""
@@ -363,6 +363,19 @@ class Searcher:
         out["gpu_ms"] = ms.value
         return out
 
+    def _mode(self, getter: str) -> int:
+        """a context setting through its lcs_get_* function"""
+        d = C.c_int(-1)
+        self._chk(getattr(self._lib, getter)(self._h, C.byref(d)), getter)
+        return d.value
+
+    def _last_records(self, what: str, rec, n_buf: int, max_cells_per_buf: int):
+        """a side table of the last fused call (lcs_last_tdd_info, lcs_last_cell_meas) -> [n_buf][max_cells_per_buf] records"""
+        info = (rec * (n_buf * max_cells_per_buf))()
+        rc = getattr(self._lib, what)(self._h, info, max_cells_per_buf)
+        self._note_overflow(self._chk(rc, what, allow_overflow=True), what, stacklevel=4)      # the warning names the public method's caller
+        return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
+
     def set_duplex(self, duplex: int):
         """DUPLEX_FDD (default) or DUPLEX_TDD: where sss_detect and pss_sss_foe look for the SSS relative to the PSS, for every call
         on this searcher (lcs_set_duplex, include/lcs.h).  Refused for any other value and while a stream is open."""
@@ -370,9 +383,7 @@ class Searcher:
 
     @property
     def duplex(self) -> int:
-        d = C.c_int(-1)
-        self._chk(self._lib.lcs_get_duplex(self._h, C.byref(d)), "lcs_get_duplex")
-        return d.value
+        return self._mode("lcs_get_duplex")
 
     def set_foe_unwrap(self, on: bool):
         """pss_sss_foe unwrapped by a PSS-only coarse estimate, for every call on this searcher (lcs_set_foe_unwrap, include/lcs.h):
@@ -383,9 +394,7 @@ class Searcher:
 
     @property
     def foe_unwrap(self) -> bool:
-        d = C.c_int(-1)
-        self._chk(self._lib.lcs_get_foe_unwrap(self._h, C.byref(d)), "lcs_get_foe_unwrap")
-        return d.value != 0
+        return self._mode("lcs_get_foe_unwrap") != 0
 
     def pss_foe_coarse(self, cell, capbuf, fc_requested, fc_programmed, fs_programmed):
         """The coarse estimate as a stage of its own (lcs_pss_foe_coarse), in the searcher's duplex mode and whatever the unwrap
@@ -406,9 +415,7 @@ class Searcher:
 
     @property
     def tdd_config_mode(self) -> bool:
-        d = C.c_int(-1)
-        self._chk(self._lib.lcs_get_tdd_config(self._h, C.byref(d)), "lcs_get_tdd_config")
-        return d.value != 0
+        return self._mode("lcs_get_tdd_config") != 0
 
     def tdd_config(self, cell, tfg):
         """The estimate as a stage of its own (lcs_tdd_config): a cell with identity and CP type and its grid from extract_tfg, raw
@@ -422,10 +429,7 @@ class Searcher:
         """The records of the last search_capbuf (n_buf = 1) or batch: per buffer a list of max_cells_per_buf TddInfo, entry k
         belonging to cell k of that buffer; the entries behind a buffer's cells, and all of them without the mode, read
         TDD_NOT_ESTIMATED (lcs_last_tdd_info)."""
-        info = (capi.TddInfo * (n_buf * max_cells_per_buf))()
-        rc = self._lib.lcs_last_tdd_info(self._h, info, max_cells_per_buf)
-        self._note_overflow(self._chk(rc, "lcs_last_tdd_info", allow_overflow=True), "lcs_last_tdd_info")
-        return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
+        return self._last_records("lcs_last_tdd_info", capi.TddInfo, n_buf, max_cells_per_buf)
 
     def set_cell_meas(self, on: bool):
         """Measure RSRP, RSSI, RSRQ and the noise power of every cell a fused call decodes, from its reference signals on the device
@@ -435,9 +439,7 @@ class Searcher:
 
     @property
     def cell_meas_mode(self) -> bool:
-        d = C.c_int(-1)
-        self._chk(self._lib.lcs_get_cell_meas(self._h, C.byref(d)), "lcs_get_cell_meas")
-        return d.value != 0
+        return self._mode("lcs_get_cell_meas") != 0
 
     def cell_meas(self, cell, tfg, dl_mask: int = 0x3FF):
         """The measurement as a stage of its own (lcs_cell_meas): a cell with identity and CP type (n_ports 0 / unknown: port 0 alone)
@@ -452,10 +454,7 @@ class Searcher:
         """The records of the last search_capbuf (n_buf = 1) or batch: per buffer a list of max_cells_per_buf CellMeas, entry k
         belonging to cell k of that buffer; the entries behind a buffer's cells, and all of them without the mode, read
         MEAS_NOT_MEASURED (lcs_last_cell_meas)."""
-        info = (capi.CellMeas * (n_buf * max_cells_per_buf))()
-        rc = self._lib.lcs_last_cell_meas(self._h, info, max_cells_per_buf)
-        self._note_overflow(self._chk(rc, "lcs_last_cell_meas", allow_overflow=True), "lcs_last_cell_meas")
-        return [[info[b * max_cells_per_buf + i].copy() for i in range(max_cells_per_buf)] for b in range(n_buf)]
+        return self._last_records("lcs_last_cell_meas", capi.CellMeas, n_buf, max_cells_per_buf)
 
     # ---- the full-bandwidth grid and measurement (lcs_extract_tfg_wide, lcs_cell_meas_wide) ---
     @staticmethod

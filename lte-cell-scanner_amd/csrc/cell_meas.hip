@@ -82,10 +82,10 @@ __global__ __launch_bounds__(TC_THREADS) void k_cell_meas(const lcs_cell *__rest
           const cd2 h0n = mk(__shfl_down(h0.re, 1, TDD_ROW_LANES), __shfl_down(h0.im, 1, TDD_ROW_LANES));
           const cd2 h1n = mk(__shfl_down(h1.re, 1, TDD_ROW_LANES), __shfl_down(h1.im, 1, TDD_ROW_LANES));
           double v[MEAS_NV];
-          meas_entry(xs, m, ports, h0, h0n, h1, h1n, v);
+          meas_entry(xs, m, ports, h0, h0n, h1, h1n, v, 12);
 #pragma unroll
           for (int i = 0; i < MEAS_NV; ++i) {
-            const double s = meas_row_sum_lanes(m < 12 ? v[i] : 0.0);
+            const double s = meas_row_sum_lanes<TDD_ROW_LANES>(m < 12 ? v[i] : 0.0);
             if (m == 0 && q < n_q) s_row[i][q] = s;
           }
         }

@@ -202,36 +202,22 @@ int ensure_stage_ws(lcs_ctx *c, int n_f = 1) { return ensure_ws(c, 1, std::max<u
 // The per-peak chain of a launch: sss_detect + pss_sss_foe on every peak (with the first round), then per round of L.round_cells
 // cells the work list, the grids, the frequency / timing correction and the MIB.  Rounds [r0, r1).
 // With L.tdd_config (lcs_set_tdd_config in LCS_DUPLEX_TDD) every round also estimates the uplink-downlink configuration of its cells
-// (k_tdd_config, on the raw grid) into c->tdd_info, a table laid out like the peak table: the first round's call sets every record of
-// it to LCS_TDD_NOT_ESTIMATED (all 32-bit words -2: lcs_last_tdd_info reads the integer fields only of such a record), later rounds
-// -- lcs_batch_collect's among them -- fill in their own cells.
+// (k_tdd_config, on the raw grid) into c->tdd_info, a table beside the peak table (SideTable: the first round's call sets every
+// record of it to LCS_TDD_NOT_ESTIMATED, all 32-bit words -2: lcs_last_tdd_info reads the integer fields only of such a record).
 // With L.cell_meas (lcs_set_cell_meas) every round measures its cells as well (k_cell_meas, behind k_tdd_config, whose record of the
 // cell names the subframes to measure where there is one) into c->cell_meas_tab, a table made and kept in the same way.
 int launch_per_peak(lcs_ctx *c, const Launch &L, int r0, int r1) {
   int rc;
   if (r0 == 0) {
-    c->tdd_n_buf = L.n_buf;
-    c->tdd_made = L.tdd_config != 0;
-    if (L.tdd_config) {
-      const size_t n = (size_t)L.n_buf * LCS_MAXP;
-      if (n > c->tdd_info.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
-      if ((rc = c->tdd_info.reserve(c, n))) return rc;
-      HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->tdd_info.get()), LCS_TDD_NOT_ESTIMATED, n * (sizeof(lcs_tdd_info) / 4), c->stream));
-    }
-    c->meas_made = L.cell_meas != 0;
-    if (L.cell_meas) {
-      const size_t n = (size_t)L.n_buf * LCS_MAXP;
-      if (n > c->cell_meas_tab.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
-      if ((rc = c->cell_meas_tab.reserve(c, n))) return rc;
-      HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->cell_meas_tab.get()), LCS_MEAS_NOT_MEASURED, n * (sizeof(lcs_meas_info) / 4), c->stream));
-    }
+    c->fused_n_buf = L.n_buf;
+    if ((rc = c->tdd_info.begin(c, L.n_buf, L.tdd_config != 0)) || (rc = c->cell_meas_tab.begin(c, L.n_buf, L.cell_meas != 0))) return rc;
   }
   const int meas_mask = L.duplex == LCS_DUPLEX_TDD ? 0x021 : 0x3ff;      // TDD: subframes 0 and 5 are downlink in every configuration
   if (r0 == 0 && (rc = lcs_launch_sss_foe(c, L, 3.0 /* THRESH2_N_SIGMA, ref src/CellSearch.cpp:528 */, nullptr))) return rc;
   for (int r = r0; r < r1; ++r)
     if ((rc = lcs_launch_gather_work(c, L, r * L.round_cells)) || (rc = lcs_launch_tfg(c, L, true)) || (rc = lcs_launch_tfoec(c, L, false)) ||
-        (rc = lcs_launch_mib(c, L, true)) || (L.tdd_config && (rc = lcs_launch_tdd_config(c, L, c->tdd_info, false))) ||
-        (L.cell_meas && (rc = lcs_launch_cell_meas(c, L, L.tdd_config ? c->tdd_info.get() : nullptr, c->cell_meas_tab, meas_mask, false))))
+        (rc = lcs_launch_mib(c, L, true)) || (L.tdd_config && (rc = lcs_launch_tdd_config(c, L, c->tdd_info.get(), false))) ||
+        (L.cell_meas && (rc = lcs_launch_cell_meas(c, L, L.tdd_config ? c->tdd_info.get() : nullptr, c->cell_meas_tab.get(), meas_mask, false))))
       return rc;
   return LCS_OK;
 }
@@ -272,6 +258,21 @@ int read_cells_and_peaks(lcs_ctx *c, lcs_cell *cells, int32_t *order, int max_ce
   *n_cells = n;
   if (rc) c->err = "more results than the output arrays hold";
   return rc;
+}
+
+// A mode of a context that is 0 or 1 and that an open stream holds (lcs_set_foe_unwrap, lcs_set_tdd_config, lcs_set_cell_meas);
+// `held`: the refusal of a change under an open stream
+int set_mode(lcs_ctx *c, int lcs_ctx::*mode, int on, const char *name, const char *held) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (on != 0 && on != 1) { c->err = std::string(name) + " is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
+  if (c->st_open && on != c->*mode) { c->err = held; return LCS_ERR_BAD_ARG; }
+  c->*mode = on;
+  return LCS_OK;
+}
+int get_mode(const lcs_ctx *c, int lcs_ctx::*mode, int *on) {
+  if (!c || !on) return LCS_ERR_BAD_ARG;
+  *on = c->*mode;
+  return LCS_OK;
 }
 
 int check_common(lcs_ctx *c, uint32_t n_cap, int n_f) {
@@ -398,114 +399,41 @@ int lcs_set_duplex(lcs_ctx *c, int duplex) {
   c->duplex = duplex;
   return LCS_OK;
 }
-int lcs_get_duplex(const lcs_ctx *c, int *duplex) {
-  if (!c || !duplex) return LCS_ERR_BAD_ARG;
-  *duplex = c->duplex;
-  return LCS_OK;
-}
+int lcs_get_duplex(const lcs_ctx *c, int *duplex) { return get_mode(c, &lcs_ctx::duplex, duplex); }
 
 int lcs_set_foe_unwrap(lcs_ctx *c, int on) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  if (on != 0 && on != 1) { c->err = "foe_unwrap is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
-  if (c->st_open && on != c->foe_unwrap) {
-    c->err = "the open stream's captured graph holds the foe_unwrap mode it was opened with: lcs_stream_close first";
-    return LCS_ERR_BAD_ARG;
-  }
-  c->foe_unwrap = on;
-  return LCS_OK;
+  return set_mode(c, &lcs_ctx::foe_unwrap, on, "foe_unwrap",
+                  "the open stream's captured graph holds the foe_unwrap mode it was opened with: lcs_stream_close first");
 }
-int lcs_get_foe_unwrap(const lcs_ctx *c, int *on) {
-  if (!c || !on) return LCS_ERR_BAD_ARG;
-  *on = c->foe_unwrap;
-  return LCS_OK;
-}
+int lcs_get_foe_unwrap(const lcs_ctx *c, int *on) { return get_mode(c, &lcs_ctx::foe_unwrap, on); }
 
 int lcs_set_tdd_config(lcs_ctx *c, int on) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  if (on != 0 && on != 1) { c->err = "tdd_config is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
-  if (c->st_open && on != c->tdd_config) {
-    c->err = "the streaming mode does not carry the uplink-downlink estimate: the tdd_config mode cannot change under an open stream, lcs_stream_close first";
-    return LCS_ERR_BAD_ARG;
-  }
-  c->tdd_config = on;
-  return LCS_OK;
+  return set_mode(c, &lcs_ctx::tdd_config, on, "tdd_config",
+                  "the streaming mode does not carry the uplink-downlink estimate: the tdd_config mode cannot change under an open stream, lcs_stream_close first");
 }
-int lcs_get_tdd_config(const lcs_ctx *c, int *on) {
-  if (!c || !on) return LCS_ERR_BAD_ARG;
-  *on = c->tdd_config;
-  return LCS_OK;
-}
-
-// The table of the last fused call, in the order of the records that call handed out: those are the peaks with SSS and MIB in peak
-// order (k_pack_results, read_cells_and_peaks), and they are the ones k_tdd_config gave an estimate.
-int lcs_last_tdd_info(lcs_ctx *c, lcs_tdd_info *info, int max_cells_per_buf) {
-  if (!c || max_cells_per_buf < 0 || (!info && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
-  if (c->tdd_n_buf <= 0) { c->err = "lcs_last_tdd_info needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
-  const int nb = c->tdd_n_buf;
-  lcs_tdd_info none;
-  tdd_info_clear(&none, LCS_TDD_NOT_ESTIMATED);
-  for (size_t i = 0; i < (size_t)nb * max_cells_per_buf; ++i) info[i] = none;
-  if (!c->tdd_made) return LCS_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  std::vector<lcs_tdd_info> tab((size_t)nb * LCS_MAXP);
-  HIPCHK(c, hipMemcpyAsync(tab.data(), c->tdd_info, tab.size() * sizeof(lcs_tdd_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int rc = LCS_OK;
-  for (int b = 0; b < nb; ++b) {
-    int k = 0;
-    for (int p = 0; p < LCS_MAXP; ++p) {
-      const lcs_tdd_info &t = tab[(size_t)b * LCS_MAXP + p];
-      if (t.ul_dl_config == LCS_TDD_NOT_ESTIMATED) continue;
-      if (k < max_cells_per_buf) info[(size_t)b * max_cells_per_buf + k] = t; else rc = LCS_ERR_OVERFLOW;
-      ++k;
-    }
-  }
-  if (rc) c->err = "more results than the output array holds";
-  return rc;
-}
+int lcs_get_tdd_config(const lcs_ctx *c, int *on) { return get_mode(c, &lcs_ctx::tdd_config, on); }
 
 int lcs_set_cell_meas(lcs_ctx *c, int on) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  if (on != 0 && on != 1) { c->err = "cell_meas is neither 0 nor 1"; return LCS_ERR_BAD_ARG; }
-  if (c->st_open && on != c->cell_meas) {
-    c->err = "the streaming mode does not carry the cell measurement: the cell_meas mode cannot change under an open stream, lcs_stream_close first";
-    return LCS_ERR_BAD_ARG;
-  }
-  c->cell_meas = on;
-  return LCS_OK;
+  return set_mode(c, &lcs_ctx::cell_meas, on, "cell_meas",
+                  "the streaming mode does not carry the cell measurement: the cell_meas mode cannot change under an open stream, lcs_stream_close first");
 }
-int lcs_get_cell_meas(const lcs_ctx *c, int *on) {
-  if (!c || !on) return LCS_ERR_BAD_ARG;
-  *on = c->cell_meas;
-  return LCS_OK;
-}
+int lcs_get_cell_meas(const lcs_ctx *c, int *on) { return get_mode(c, &lcs_ctx::cell_meas, on); }
 int lcs_tdd_dl_mask(int ul_dl_config) { return meas_tdd_dl_mask(ul_dl_config); }
 
-// The measurement table of the last fused call, in the order of the records that call handed out (as lcs_last_tdd_info).
+// The side tables of the last fused call (SideTable::read_last): k_tdd_config's estimates and k_cell_meas's measurements
+int lcs_last_tdd_info(lcs_ctx *c, lcs_tdd_info *info, int max_cells_per_buf) {
+  if (!c || max_cells_per_buf < 0 || (!info && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
+  if (c->fused_n_buf <= 0) { c->err = "lcs_last_tdd_info needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
+  lcs_tdd_info none;
+  tdd_info_clear(&none, LCS_TDD_NOT_ESTIMATED);
+  return c->tdd_info.read_last(c, c->fused_n_buf, none, &lcs_tdd_info::ul_dl_config, info, max_cells_per_buf);
+}
 int lcs_last_cell_meas(lcs_ctx *c, lcs_meas_info *info, int max_cells_per_buf) {
   if (!c || max_cells_per_buf < 0 || (!info && max_cells_per_buf > 0)) return LCS_ERR_BAD_ARG;
-  if (c->tdd_n_buf <= 0) { c->err = "lcs_last_cell_meas needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
-  const int nb = c->tdd_n_buf;
+  if (c->fused_n_buf <= 0) { c->err = "lcs_last_cell_meas needs lcs_search_capbuf or a batch on this context first"; return LCS_ERR_BAD_ARG; }
   lcs_meas_info none;
   meas_clear(&none, LCS_MEAS_NOT_MEASURED);
-  for (size_t i = 0; i < (size_t)nb * max_cells_per_buf; ++i) info[i] = none;
-  if (!c->meas_made) return LCS_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  std::vector<lcs_meas_info> tab((size_t)nb * LCS_MAXP);
-  HIPCHK(c, hipMemcpyAsync(tab.data(), c->cell_meas_tab, tab.size() * sizeof(lcs_meas_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int rc = LCS_OK;
-  for (int b = 0; b < nb; ++b) {
-    int k = 0;
-    for (int p = 0; p < LCS_MAXP; ++p) {
-      const lcs_meas_info &t = tab[(size_t)b * LCS_MAXP + p];
-      if (t.status == LCS_MEAS_NOT_MEASURED) continue;
-      if (k < max_cells_per_buf) info[(size_t)b * max_cells_per_buf + k] = t; else rc = LCS_ERR_OVERFLOW;
-      ++k;
-    }
-  }
-  if (rc) c->err = "more results than the output array holds";
-  return rc;
+  return c->cell_meas_tab.read_last(c, c->fused_n_buf, none, &lcs_meas_info::status, info, max_cells_per_buf);
 }
 
 int lcs_set_max_cells_in_flight(lcs_ctx *c, int n) {
@@ -600,9 +528,9 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "unknown capture format"; return LCS_ERR_BAD_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   c->foe_ready = false;      // the batch overwrites the buffers a pending lcs_foe_partial left for lcs_foe_finish
-  c->tdd_n_buf = n_buf;      // lcs_last_tdd_info: this batch's table (launch_per_peak makes it, if the batch gets that far and the mode is on)
-  c->tdd_made = false;
-  c->meas_made = false;
+  c->fused_n_buf = n_buf;      // lcs_last_tdd_info, lcs_last_cell_meas: this batch's tables (launch_per_peak makes them, if the batch gets that far and the mode is on)
+  (void)c->tdd_info.begin(c, n_buf, false);
+  (void)c->cell_meas_tab.begin(c, n_buf, false);
   // pack: 137 taps + window-start spread <= 152 inside every template group, the int8 kernel's limit, whatever kernel follows (the
   // fp16 kernel holds 160 taps, the fp32 kernel more); pack_grid thins the groups of a grid that is too sparse for that
   const XcGeom geo = pack_grid(n_cap, n_f, 2 /* DS_COMB_ARM, ref src/CellSearch.cpp:484 */, f_search_set, fc_requested, fc_programmed,
@@ -891,6 +819,39 @@ int put_single_work_item(lcs_ctx *c, const lcs_cell *cell, int n_ofdm) {
 int n_ofdm_for(const lcs_cell *cell) {
   return cell->cp_type == LCS_CP_NORMAL ? 854 : (cell->cp_type == LCS_CP_EXTENDED ? 732 : -1);
 }
+// a cell with n_id_1 in 0 .. 167, n_id_2 in 0 .. 2 and a known cp_type
+bool cell_identified(const lcs_cell *cell) {
+  return n_ofdm_for(cell) >= 0 && cell->n_id_1 >= 0 && cell->n_id_1 <= 167 && cell->n_id_2 >= 0 && cell->n_id_2 <= 2;
+}
+// What the stages that take the caller's grid share: the workspace, the one-cell work list, the grid in `dst` (c->tfg: in the
+// chain's raw grid's place, c->tfg_comp: in the compensated one's) and the cell's RS_DL table (k_cell_prep).  *L: the launch of
+// the stage's own kernels.
+int stage_grid(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, DevBuf<double2> lcs_ctx::*dst, Launch *L) {
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ensure_stage_ws(c))) return rc;
+  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->*dst, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
+  *L = make_launch(c, 1, 0, CapSrc{});
+  return lcs_launch_rs_build(c, *L);
+}
+// lcs_tdd_config and lcs_cell_meas, which take a raw grid of two frames .. LCS_TFG_MAX_OFDM rows and leave one record: what they
+// refuse alike, under the stage's own name ...
+int record_stage_check(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_ofdm) {
+  const char *what = nullptr;
+  if (!cell_identified(cell)) what = " needs a cell with n_id_1, n_id_2 and a known cp_type";
+  else if (n_ofdm < 2 * 20 * (n_ofdm_for(cell) == 854 ? 7 : 6)) what = " needs at least two frames of the grid (280 OFDM symbols with the normal CP, 240 with the extended)";
+  else if (n_ofdm > LCS_TFG_MAX_OFDM) what = " takes at most LCS_TFG_MAX_OFDM (854) OFDM symbols";
+  if (!what) return LCS_OK;
+  c->err = std::string(who) + what;
+  return LCS_ERR_BAD_ARG;
+}
+// ... and how their record comes back: the kernel writes it into the debug block (the fused calls' tables stay what they are)
+int read_dbg_record(lcs_ctx *c, void *out, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(out, c->d_dbg, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
 }  // namespace
 
 int lcs_sss_detect(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint32_t n_cap, double thresh2_n_sigma,
@@ -925,7 +886,7 @@ int lcs_sss_detect(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint3
 int lcs_pss_sss_foe(lcs_ctx *c, const lcs_cell *cell_in, const double *capbuf, uint32_t n_cap, double fc_req,
                     double fc_prog, double fs_prog, lcs_cell *cell_out) {
   if (!c || !cell_in || !cell_out) return LCS_ERR_BAD_ARG;
-  if (n_ofdm_for(cell_in) < 0 || cell_in->n_id_1 < 0 || cell_in->n_id_1 > 167 || cell_in->n_id_2 < 0 || cell_in->n_id_2 > 2) {
+  if (!cell_identified(cell_in)) {
     c->err = "pss_sss_foe needs a cell with n_id_1, n_id_2 and a known cp_type";   // the reference throws (src/searcher.cpp:786)
     return LCS_ERR_BAD_ARG;
   }
@@ -945,7 +906,7 @@ int lcs_pss_sss_foe(lcs_ctx *c, const lcs_cell *cell_in, const double *capbuf, u
 int lcs_pss_foe_coarse(lcs_ctx *c, const lcs_cell *cell, const double *capbuf, uint32_t n_cap, double fc_req, double fc_prog,
                        double fs_prog, double *f_coarse, double *c_re_im, int *n_occ) {
   if (!c || !cell || !f_coarse) return LCS_ERR_BAD_ARG;
-  if (n_ofdm_for(cell) < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
+  if (!cell_identified(cell)) {
     c->err = "pss_foe_coarse needs a cell with n_id_1, n_id_2 and a known cp_type";      // as lcs_pss_sss_foe: it shares its geometry
     return LCS_ERR_BAD_ARG;
   }
@@ -1018,14 +979,10 @@ int lcs_decode_mib(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
     c->err = "decode_mib needs a detected cell and its full 854/732-symbol grid";
     return LCS_ERR_BAD_ARG;
   }
-  HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_stage_ws(c))) return rc;
-  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->tfg_comp, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  Launch L = make_launch(c, 1, 0, CapSrc{});
+  Launch L;
+  if ((rc = stage_grid(c, cell, tfg, n_ofdm, &lcs_ctx::tfg_comp, &L))) return rc;
   L.needed_rows_only = true;      // decode_mib reads the channel estimate on PBCH rows only
-  if ((rc = lcs_launch_rs_build(c, L))) return rc;
   if ((rc = lcs_launch_mib(c, L, false))) return rc;
   HIPCHK(c, hipMemcpyAsync(cell_out, c->cells_out, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1033,58 +990,28 @@ int lcs_decode_mib(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
 }
 
 // The uplink-downlink configuration as a stage (tdd_config.h): the caller's grid takes the place of the chain's raw one, k_cell_prep
-// builds RS_DL, k_tdd_config writes its record into the debug block (the fused calls' table stays what it is).
+// builds RS_DL, k_tdd_config writes its record into the debug block.
 int lcs_tdd_config(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, lcs_tdd_info *out) {
   if (!c || !cell || !tfg || !out) return LCS_ERR_BAD_ARG;
-  const int full = n_ofdm_for(cell);
-  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
-    c->err = "tdd_config needs a cell with n_id_1, n_id_2 and a known cp_type";
-    return LCS_ERR_BAD_ARG;
-  }
-  const int n_symb = full == 854 ? 7 : 6;
-  if (n_ofdm < 2 * 20 * n_symb) { c->err = "tdd_config needs at least two frames of the grid (280 OFDM symbols with the normal CP, 240 with the extended)"; return LCS_ERR_BAD_ARG; }
-  if (n_ofdm > LCS_TFG_MAX_OFDM) { c->err = "tdd_config takes at most LCS_TFG_MAX_OFDM (854) OFDM symbols"; return LCS_ERR_BAD_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_stage_ws(c))) return rc;
-  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->tfg, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  Launch L;
+  if ((rc = record_stage_check(c, "tdd_config", cell, n_ofdm)) || (rc = stage_grid(c, cell, tfg, n_ofdm, &lcs_ctx::tfg, &L))) return rc;
   static_assert(sizeof(lcs_tdd_info) <= 2048 * sizeof(double), "the debug block holds a record");
-  lcs_tdd_info *d_out = reinterpret_cast<lcs_tdd_info *>(c->d_dbg.get());
-  if ((rc = lcs_launch_rs_build(c, L))) return rc;
-  if ((rc = lcs_launch_tdd_config(c, L, d_out, true))) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(lcs_tdd_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
+  if ((rc = lcs_launch_tdd_config(c, L, reinterpret_cast<lcs_tdd_info *>(c->d_dbg.get()), true))) return rc;
+  return read_dbg_record(c, out, sizeof(*out));
 }
 
-// RSRP, RSSI, RSRQ and the noise power as a stage (cell_meas.h), as lcs_tdd_config: the caller's grid in the chain's place, the
-// record through the debug block.
+// RSRP, RSSI, RSRQ and the noise power as a stage (cell_meas.h), as lcs_tdd_config
 int lcs_cell_meas(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int dl_mask, lcs_meas_info *out) {
   if (!c || !cell || !tfg || !out) return LCS_ERR_BAD_ARG;
-  const int full = n_ofdm_for(cell);
-  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2) {
-    c->err = "cell_meas needs a cell with n_id_1, n_id_2 and a known cp_type";
-    return LCS_ERR_BAD_ARG;
-  }
-  const int n_symb = full == 854 ? 7 : 6;
-  if (n_ofdm < 2 * 20 * n_symb) { c->err = "cell_meas needs at least two frames of the grid (280 OFDM symbols with the normal CP, 240 with the extended)"; return LCS_ERR_BAD_ARG; }
-  if (n_ofdm > LCS_TFG_MAX_OFDM) { c->err = "cell_meas takes at most LCS_TFG_MAX_OFDM (854) OFDM symbols"; return LCS_ERR_BAD_ARG; }
-  if (!meas_mask_ok(dl_mask)) { c->err = "cell_meas needs a dl_mask with at least one of the bits 0 .. 9 and none above"; return LCS_ERR_BAD_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_stage_ws(c))) return rc;
-  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->tfg, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  const Launch L = make_launch(c, 1, 0, CapSrc{});
+  Launch L;
+  if ((rc = record_stage_check(c, "cell_meas", cell, n_ofdm))) return rc;
+  if (!meas_mask_ok(dl_mask)) { c->err = "cell_meas needs a dl_mask with at least one of the bits 0 .. 9 and none above"; return LCS_ERR_BAD_ARG; }
+  if ((rc = stage_grid(c, cell, tfg, n_ofdm, &lcs_ctx::tfg, &L))) return rc;
   static_assert(sizeof(lcs_meas_info) <= 2048 * sizeof(double), "the debug block holds a record");
-  lcs_meas_info *d_out = reinterpret_cast<lcs_meas_info *>(c->d_dbg.get());
-  if ((rc = lcs_launch_rs_build(c, L))) return rc;
-  if ((rc = lcs_launch_cell_meas(c, L, nullptr, d_out, dl_mask, true))) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(lcs_meas_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
+  if ((rc = lcs_launch_cell_meas(c, L, nullptr, reinterpret_cast<lcs_meas_info *>(c->d_dbg.get()), dl_mask, true))) return rc;
+  return read_dbg_record(c, out, sizeof(*out));
 }
 
 // ---- the full-bandwidth grid and measurement (tfg_wide.hip, cell_meas_wide.h).  They touch the context's stream and the blocks of
@@ -1103,10 +1030,8 @@ int wide_rows(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_c
   if (measw_log2r(n_fft) < 0) return wide_refused(c, who, "n_fft is not 128, 256, 512, 1024 or 2048");
   if (!(fabs(fs_prog / (15000.0 * n_fft) - 1.0) < 1e-3)) return wide_refused(c, who, "fs_programmed is not 15 kHz x n_fft to within 1e-3");
   if (!measw_rb_ok(n_fft, n_rb)) return wide_refused(c, who, "n_rb is outside 6 .. {6, 15, 25, 50, 100} for n_fft = 128 {1, 2, 4, 8, 16}");
-  const int full = n_ofdm_for(cell);
-  if (full < 0 || cell->n_id_1 < 0 || cell->n_id_1 > 167 || cell->n_id_2 < 0 || cell->n_id_2 > 2)
-    return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  const int n_symb = full == 854 ? 7 : 6;
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
   if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
   const double k_factor = (fc_req - cell->freq_fine) / fc_prog;
   double loc;
@@ -1189,13 +1114,9 @@ int lcs_chan_est(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm
     c->err = "chan_est needs a detected cell, its full 854/732-symbol grid and a port 0..3";
     return LCS_ERR_BAD_ARG;
   }
-  HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ensure_stage_ws(c))) return rc;
-  if ((rc = put_single_work_item(c, cell, n_ofdm))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->tfg_comp, tfg, sizeof(double2) * n_ofdm * LCS_TFG_NSC, hipMemcpyHostToDevice, c->stream));
-  const Launch L = make_launch(c, 1, 0, CapSrc{});
-  if ((rc = lcs_launch_rs_build(c, L))) return rc;
+  Launch L;
+  if ((rc = stage_grid(c, cell, tfg, n_ofdm, &lcs_ctx::tfg_comp, &L))) return rc;
   if ((rc = lcs_launch_chan_est(c, L))) return rc;
   int first, per_port, n_rs_at;
   lcs_chan_est_np_layout(&first, &per_port, &n_rs_at);

@@ -266,6 +266,25 @@ struct XcBufs {
   DevBuf<float> btab;                // fp32 kernel only: sized for the workspace's slots and groups (0.5 MB per slot, window and group)
 };
 
+// A table beside the peak table and laid out like it, [n_buf][LCS_MAXP], that a fused call fills when its mode is on (k_tdd_config's,
+// k_cell_meas's): the block, whether the last fused call made it, and the 32-bit word a record that belongs to no decoded cell is
+// made of.  The bodies follow lcs_ctx.
+struct lcs_ctx;
+template <class Rec> struct SideTable {
+  explicit SideTable(int sentinel_word) : sentinel(sentinel_word) {}
+  DevBuf<Rec> tab;
+  bool made = false;       // whether the last fused call ran the kernel that fills it: otherwise it reads the sentinel throughout
+  const int sentinel;
+  Rec *get() const { return tab.get(); }
+  // launch_per_peak's first round: `on`, the table of n_buf buffers exists and every word of it is the sentinel (it synchronises the
+  // stream only when the block has to grow); later rounds -- lcs_batch_collect's among them -- fill in their own cells
+  int begin(lcs_ctx *c, int n_buf, bool on);
+  // The table of the last fused call (n_buf buffers) in the order of the records that call handed out -- the peaks with SSS and MIB
+  // in peak order (k_pack_results, read_cells_and_peaks): out[b * max_cells_per_buf + k] belongs to cell k of buffer b, `none`
+  // everywhere else and throughout when the table was not made.  A record whose field `key` reads the sentinel belongs to no cell.
+  int read_last(lcs_ctx *c, int n_buf, const Rec &none, int32_t Rec::*key, Rec *out, int max_cells_per_buf);
+};
+
 // The streams and events of a context (the streaming mode's own events and graphs: lcs_stream_close).  A BASE of lcs_ctx,
 // because a base is destroyed after every member of the struct derived from it: see the note on ownership at lcs_ctx.
 struct lcs_ctx_queues {
@@ -346,12 +365,10 @@ struct lcs_ctx : lcs_ctx_queues {
   int foe_unwrap = 0;               // lcs_set_foe_unwrap: likewise
   DevBuf<double> foe_coarse;        // [4]: what lcs_pss_foe_coarse reads back (k_foe_fin_unwrap)
   int tdd_config = 0;               // lcs_set_tdd_config: likewise (it reaches a Launch only in LCS_DUPLEX_TDD)
-  DevBuf<lcs_tdd_info> tdd_info;    // [n_buf][LCS_MAXP], laid out like `peaks`: what k_tdd_config writes in the fused chain, [0] for lcs_tdd_config
-  int tdd_n_buf = 0;                // buffers of the last fused call (lcs_last_tdd_info), 0: none yet
-  bool tdd_made = false;            // ... and whether that call ran k_tdd_config: otherwise its table is LCS_TDD_NOT_ESTIMATED throughout
   int cell_meas = 0;                // lcs_set_cell_meas: likewise
-  DevBuf<lcs_meas_info> cell_meas_tab;   // [n_buf][LCS_MAXP], laid out like `peaks`: what k_cell_meas writes in the fused chain
-  bool meas_made = false;           // whether the last fused call (tdd_n_buf buffers) ran k_cell_meas: otherwise its table is LCS_MEAS_NOT_MEASURED throughout
+  int fused_n_buf = 0;              // buffers of the last fused call (lcs_last_tdd_info, lcs_last_cell_meas), 0: none yet
+  SideTable<lcs_tdd_info> tdd_info{LCS_TDD_NOT_ESTIMATED};        // what k_tdd_config writes in the fused chain
+  SideTable<lcs_meas_info> cell_meas_tab{LCS_MEAS_NOT_MEASURED};  // what k_cell_meas writes in the fused chain
   // the full-bandwidth grid and measurement (tfg_wide.hip: lcs_extract_tfg_wide, lcs_cell_meas_wide): every block is allocated by
   // the first call that needs it and grown on demand; a context that never calls the stage holds none of them
   struct MeasWide {
@@ -464,6 +481,37 @@ inline int lcs_hip_error(lcs_ctx *c, const char *call, hipError_t e) {
     hipError_t e_ = (call);                                                      \
     if (e_ != hipSuccess) return lcs_hip_error((ctx), #call, e_);                \
   } while (0)
+
+template <class Rec> int SideTable<Rec>::begin(lcs_ctx *c, int n_buf, bool on) {
+  made = on;
+  if (!on) return LCS_OK;
+  const size_t n = (size_t)n_buf * LCS_MAXP;
+  if (n > tab.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc;
+  if ((rc = tab.reserve(c, n))) return rc;
+  HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tab.get()), sentinel, n * (sizeof(Rec) / 4), c->stream));
+  return LCS_OK;
+}
+template <class Rec> int SideTable<Rec>::read_last(lcs_ctx *c, int n_buf, const Rec &none, int32_t Rec::*key, Rec *out, int max_cells_per_buf) {
+  for (size_t i = 0; i < (size_t)n_buf * max_cells_per_buf; ++i) out[i] = none;
+  if (!made) return LCS_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<Rec> t((size_t)n_buf * LCS_MAXP);
+  HIPCHK(c, hipMemcpyAsync(t.data(), tab.get(), t.size() * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int rc = LCS_OK;
+  for (int b = 0; b < n_buf; ++b) {
+    int k = 0;
+    for (int p = 0; p < LCS_MAXP; ++p) {
+      const Rec &r = t[(size_t)b * LCS_MAXP + p];
+      if (r.*key == sentinel) continue;
+      if (k < max_cells_per_buf) out[(size_t)b * max_cells_per_buf + k] = r; else rc = LCS_ERR_OVERFLOW;
+      ++k;
+    }
+  }
+  if (rc) c->err = "more results than the output array holds";
+  return rc;
+}
 
 // ---- host tables (lte_tables.cpp) --------------------------------------------------
 namespace lcs_tables {

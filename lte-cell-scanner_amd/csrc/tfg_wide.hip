@@ -127,7 +127,7 @@ __global__ __launch_bounds__(MEASW_LANES) void k_cell_meas_wide(const double2 *_
       const cd2 h0 = meas_h(xs, shift0, rs), h1 = meas_h(xs, shift1, rs);
       const cd2 h0n = tdd_h(mk(y0.x, y0.y), rsn), h1n = tdd_h(mk(y1.x, y1.y), rsn);
       double v[MEAS_NV];
-      measw_entry(xs, m, n_ent, ports, h0, h0n, h1, h1n, v);
+      meas_entry(xs, m, ports, h0, h0n, h1, h1n, v, n_ent);
 #pragma unroll
       for (int i = 0; i < MEAS_NV; ++i) {
         v[i] = live ? v[i] : 0.0;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(MEASW_LANES) void k_cell_meas_wide(const double2 *_
     }
 #pragma unroll
     for (int i = 0; i < MEAS_NV; ++i) {
-      const double sum = measw_row_sum_lanes(lv[i]);
+      const double sum = meas_row_sum_lanes<MEASW_LANES>(lv[i]);
       if (lane == 0) rowv[(size_t)i * TC_MAX_Q + q] = sum;
     }
     first = false;

@@ -9,10 +9,11 @@ Two workloads of 128 raw u8 buffers resident in HBM, bench.py's own (synth.make_
 carrier holds 1-2 cells) and the dense band (2-3 cells in every buffer); 31 hypotheses on the 5 kHz grid, one context per line:
   p    the parent's library
   p2   the parent's library on a context of its own: p against p2 is the parent's spread against itself in this run
+  pon  the parent's library with lcs_set_cell_meas(1), where the parent has the mode: what `on` is held against
   off  this tree, mode off
   on   this tree, lcs_set_cell_meas(1): k_cell_meas once per per-cell round
 `warmup` calls per line, then `steps` timed search_batch calls per line, interleaved call by call; the medians decide.  Also: the
-records of all four lines are byte-identical, and what the measurement says about the cells.  Writes one JSON file and prints it.
+records of all lines are byte-identical, and what the measurement says about the cells.  Writes one JSON file and prints it.
 
     rocprofv3 --kernel-trace --stats -d DIR -o meas -- python tools/bench_cell_meas.py --trace-run && python tools/kernel_times.py DIR/.../meas_results.db k_cell_meas k_tdd_config k_chan_est
 
@@ -60,11 +61,11 @@ def main():
     if not a.parent_lib:
         ap.error("--parent-lib is required (unless --trace-run)")
     parent = pkg.capi.load_other(a.parent_lib)
-    assert not hasattr(parent, "lcs_set_cell_meas"), "--parent-lib already has the mode: not the parent commit's library"
+    parent_has_mode = hasattr(parent, "lcs_set_cell_meas")
     n_buf, fs = 128, 1.92e6
     fcs = 739e6 + 100e3 * np.arange(n_buf)
     f = np.arange(-15, 16) * 5e3
-    lines = [("p", parent, None), ("p2", parent, None), ("off", None, False), ("on", None, True)]
+    lines = [("p", parent, None), ("p2", parent, None)] + ([("pon", parent, True)] if parent_has_mode else []) + [("off", None, False), ("on", None, True)]
     out = dict(n_buf=n_buf, n_f=int(f.size), steps=a.steps, warmup=a.warmup)
     for name, kw in (("band_scan", dict(seed=1234)), ("dense_band", dict(seed=4321, occupied_every=1, n_distinct=8, cells_cycle=(2, 3)))):
         seed = kw.pop("seed")
@@ -96,11 +97,15 @@ def main():
                                  sinr_db_min_median_max=[float(sinr.min()), float(np.median(sinr)), float(sinr.max())] if sinr.size else None,
                                  rsrq_db_median=float(np.median([t.rsrq_db for t in m if t.status == 0])) if sinr.size else None)
         rec = {k: [[bytes(c) for c in x] for x in cells[k]] for k, _, _ in lines}
-        w["records_identical"] = bool(rec["p"] == rec["p2"] == rec["off"] == rec["on"])
+        w["records_identical"] = all(rec[k] == rec["p"] for k, _, _ in lines)
         w["parent_spread"] = abs(w["p"]["ms_median"] / w["p2"]["ms_median"] - 1.0)
         w["on_over_parent"] = w["on"]["ms_median"] / w["p"]["ms_median"]
         w["off_over_parent"] = w["off"]["ms_median"] / w["p"]["ms_median"]
         w["on_over_off"] = w["on"]["ms_median"] / w["off"]["ms_median"]
+        if parent_has_mode:
+            w["on_over_parent_on"] = w["on"]["ms_median"] / w["pon"]["ms_median"]
+            pm = ctx["pon"].last_cell_meas(n_buf, 16)
+            w["measurements_identical_to_parent"] = all(bytes(x) == bytes(y) for a_, b_ in zip(info, pm) for x, y in zip(a_, b_))
         out[name] = w
         for k in ctx:
             ctx[k].close()
