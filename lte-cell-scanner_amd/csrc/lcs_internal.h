@@ -14,6 +14,7 @@
 //   pow/frq [S][3][9600]          double/int
 //   spinc/zth [S][9600]           double
 //   peaks   [S][MAXP] lcs_cell, npeaks [S]
+// The tracker's buffers (lcs_ctx::trk) are not in this workspace: trk_layout.h holds the one table of their arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +24,7 @@
 #include <vector>
 #include "../../include/lcs.h"
 #include "lcs_mem.h"
+#include "trk_layout.h"
 #include "xcorr_route.h"   // XcKernel, and what a template group holds: LCS_KP2_MAX, LCS_KP2_UNROLL, LCS_I8_OFF, LCS_I8_MAX_TAPS
 
 #define FS_LTE 30720000.0    // LTE sampling rate at 2048 subcarriers; the searcher works at FS_LTE / 16
@@ -238,6 +240,17 @@ struct TrkStream {
   // before the two change places at the commit (no allocation or release -- a device-wide synchronisation -- per call)
   DevBuf<double2> d_tail[3], d_spare[3];
 };
+// The device buffers FIRST .. FIRST + N - 1 of trk_layout.h's table and the capacity they were allocated for
+struct TrkCutCap { size_t n_cells = 0, n = 0; };   // the most cells, and the most cells x symbols, of any call
+template <int FIRST, int N, class Cap> struct TrkPart {
+  DevBuf<char> buf[N];
+  Cap cap;
+  template <class T> T *at(const TrkLay &l, int a) const { return l.at<T>(buf[TRK_ROWS[a].buf - FIRST].get(), a); }
+  // Every buffer anew, as `l` sizes it for `want`, once the stream has drained (the body follows lcs_ctx).  The capacity describes a
+  // complete set or nothing: if an allocation fails, later calls must not take the half-replaced buffers for the old shape.
+  int regrow(lcs_ctx *c, const TrkLay &l, const Cap &want);
+  int reserve(lcs_ctx *c, TrkShape s) { return trk_fits(cap, s) ? LCS_OK : regrow(c, trk_layout(trk_grow(cap, s)), trk_grow(cap, s)); }   // grow only
+};
 
 // Buffers of the int8 correlation path (u8 sources) and of the fp16 three-product path (complex<float> sources of the batch
 // entry points): each set is sized like the workspace, exists as a whole or not at all (`ready`), and goes with the workspace
@@ -402,22 +415,15 @@ struct lcs_ctx : lcs_ctx_queues {
   hipGraph_t st_graph[2] = {nullptr, nullptr};
   hipGraphExec_t st_exec[2] = {nullptr, nullptr};
   hipEvent_t st_ev0[2] = {nullptr, nullptr}, st_ev1[2] = {nullptr, nullptr};
-  // tracker block pipeline (tracker.hip): workspace laid out for one (n_cells, n_sym) block shape
-  DevBuf<double2> trk_td, trk_syms, trk_raw, trk_ce;
-  DevBuf<double> trk_meta, trk_rs, trk_fmeta, trk_pw;
-  DevBuf<int> trk_idx, trk_small;
-  DevBuf<lcs_track_cell> trk_cells;
-  int trk_cells_cap = 0, trk_sym_cap = 0;     // the workspace holds any block of up to this many cells x symbols
-  int trk_last_cells = 0, trk_last_sym = 0;   // shape of the block the last lcs_track_block call processed (lcs_track_stats reads it)
-  DevBuf<double2> trk_acfd, trk_actd, trk_syncce;   // lcs_track_stats outputs
-  DevBuf<double> trk_sync;
-  int trk_stat_cells = 0, trk_stat_sym = 0;   // capacity of the statistics buffers
-  TrkStream trk_stream;              // carried state of lcs_track_stream_block (tracker.hip)
-  Buf<char, LcsPageableMem> trk_hpin;   // reusable host staging block of lcs_track_block (pageable): metadata up, measurement tables down
-  DevBuf<int> trk_cut_hit;          // lcs_track_cut: first sample of every symbol [cells][symbols], per-cell flag / count behind it
-  DevBuf<double> trk_cut_meta;      // lcs_track_cut: late [cells][symbols], then frame_timing, freq_off [cells]
-  size_t trk_cut_cap = 0;           // the SHAPE the two are laid out for (as trk_cells_cap / trk_sym_cap): symbols x cells ...
-  int trk_cut_cells_cap = 0;        // ... and cells
+  // the tracker (tracker.hip): trk_layout.h says which arrays every buffer holds and where
+  struct Tracker {
+    TrkPart<TB_TD, TRK_BLOCK_BUFS, TrkShape> block;                // lcs_track_block's workspace: any block of up to cap cells x symbols ...
+    TrkShape last;                                                 // ... and the block the last call processed (lcs_track_stats reads it)
+    TrkPart<TB_ACFD, TRK_STAT_BUFS, TrkShape> stats;               // lcs_track_stats' outputs
+    TrkPart<TB_CUT_HIT, TRK_CUT_BUFS, TrkCutCap> cut;              // lcs_track_cut: laid out by the capacity, not by the call
+    TrkStream stream;                                              // carried state of lcs_track_stream_block
+    Buf<char, LcsPageableMem> stage;                               // reusable host staging block of a block (pageable): metadata up, measurement tables down
+  } trk;
   // wideband channelizer (channelizer.hip)
   DevBuf<char> chan_par;            // [n_ch] phase steps, then the taps
   DevBuf<float> chan_tab;           // the filter bank in A-operand order
@@ -482,6 +488,13 @@ inline int lcs_hip_error(lcs_ctx *c, const char *call, hipError_t e) {
     if (e_ != hipSuccess) return lcs_hip_error((ctx), #call, e_);                \
   } while (0)
 
+template <int FIRST, int N, class Cap> int TrkPart<FIRST, N, Cap>::regrow(lcs_ctx *c, const TrkLay &l, const Cap &want) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  cap = Cap();
+  for (int b = 0, rc; b < N; ++b) if ((rc = buf[b].alloc(c, l.bytes[FIRST + b]))) return rc;
+  cap = want;
+  return LCS_OK;
+}
 template <class Rec> int SideTable<Rec>::begin(lcs_ctx *c, int n_buf, bool on) {
   made = on;
   if (!on) return LCS_OK;

@@ -17,8 +17,6 @@
 #include <cstring>
 #include <vector>
 
-#define TRK_MEAS 9
-
 // (trk_wrap, trk_wrap_certain_interval: lte_device.h)
 __device__ __forceinline__ int trk_n_symb(const lcs_track_cell &c) { return c.cp_type == LCS_CP_NORMAL ? 7 : 6; }
 __device__ __forceinline__ double trk_sym_len(int cp_type, int sym) {            // samples from the previous DFT to this one's
@@ -245,7 +243,7 @@ __global__ __launch_bounds__(TRK_CE_THREADS) void k_trk_ce(const lcs_track_cell 
   const double *sh = shift + (size_t)cell * 140 * 4;
   const double *fo = freq_off + (size_t)cell * n_sym, *ft = frame_timing + (size_t)cell * n_sym;
   double2 *raw_p = raw + cp * max_rs * 12, *filt_p = filt + cp * max_rs * 12;
-  double *fm = fmeta + cp * max_rs * 4, *ms = meas + cp * max_rs * TRK_MEAS;
+  double *fm = fmeta + cp * max_rs * 4, *ms = meas + cp * max_rs * LCS_TRK_MEAS;
   const bool last = f0 + TRK_CE_CH >= nf;                         // the chunk that owns the tail
   const int nfl = min(TRK_CE_CH + 1, nf - f0);                    // filtered rows computed here: f0 .. f0 + nfl - 1 (one row of halo)
   const int f_own = last ? max(nf - f0, 0) : TRK_CE_CH;           // ... of which it writes the first f_own
@@ -364,7 +362,7 @@ __global__ __launch_bounds__(TRK_CE_THREADS) void k_trk_ce(const lcs_track_cell 
       const double residual_f_np = (foe_comb_np / 2 > .001) ? foe_comb_np / 2 : .001;
       const int f = f0 + fl;
       fm[f * 4] = tp; fm[f * 4 + 1] = sp; fm[f * 4 + 2] = sp_raw; fm[f * 4 + 3] = np;
-      double *mrow = ms + (size_t)f * TRK_MEAS;
+      double *mrow = ms + (size_t)f * LCS_TRK_MEAS;
       mrow[0] = ic; mrow[1] = np; mrow[2] = tp; mrow[3] = sp_raw; mrow[4] = sp;
       mrow[5] = frequency_offset + residual_f; mrow[6] = residual_f_np;
     }
@@ -373,7 +371,7 @@ __global__ __launch_bounds__(TRK_CE_THREADS) void k_trk_ce(const lcs_track_cell 
       const cd2 toe1 = cdivr(s_toe[g][0], sqrt(sp)), toe2 = cdivr(s_toe[g][1], sqrt(sp));
       const double delay = -(atan2(toe1.im, toe1.re) + atan2(toe2.im, toe2.re)) / 2 / 3 / (2 * M_PI / 128);
       const double delay_np = (np / sp / 2 / 12 > .001) ? np / sp / 2 / 12 : .001;
-      double *mrow = ms + (size_t)(f0 + fl) * TRK_MEAS;
+      double *mrow = ms + (size_t)(f0 + fl) * LCS_TRK_MEAS;
       mrow[7] = ft[s_idx[fl + 1]] + delay; mrow[8] = delay_np;
     }
   }
@@ -498,7 +496,7 @@ __global__ __launch_bounds__(256) void k_trk_acf(const lcs_track_cell *__restric
   if (port >= cells[cell].n_ports) return;
   const int nf = n_meas[cp];
   const double2 *raw_p = raw + cp * max_rs * 12;
-  const double *ms = meas + cp * max_rs * TRK_MEAS;
+  const double *ms = meas + cp * max_rs * LCS_TRK_MEAS;
   if (ac_fd)
     for (int e = tid; e < nf * 12; e += 256) {
       const int f = e / 12, d = e % 12;
@@ -506,7 +504,7 @@ __global__ __launch_bounds__(256) void k_trk_acf(const lcs_track_cell *__restric
       cd2 a = mk(0, 0);
       for (int t = 0; t < 12 - d; ++t) a = cadd(a, cmul(cconj(ld(&cur[t])), ld(&cur[t + d])));
       a = cdivr(a, (double)(12 - d));
-      st(&ac_fd[(cp * max_rs + f) * 12 + d], cdivr(a, ms[(size_t)f * TRK_MEAS + 4]));
+      st(&ac_fd[(cp * max_rs + f) * 12 + d], cdivr(a, ms[(size_t)f * LCS_TRK_MEAS + 4]));
     }
   if (ac_td)
     for (int e = tid; e < nf * 72; e += 256) {
@@ -516,7 +514,7 @@ __global__ __launch_bounds__(256) void k_trk_acf(const lcs_track_cell *__restric
         const double2 *cur = raw_p + (size_t)(f + 1) * 12, *old = raw_p + (size_t)(f + 1 - t) * 12;
         cd2 a = mk(0, 0);
         for (int k = 0; k < 12; ++k) a = cadd(a, cmul(cconj(ld(&cur[k])), ld(&old[k])));
-        o = cdivr(cdivr(a, 12.0), ms[(size_t)f * TRK_MEAS + 4]);
+        o = cdivr(cdivr(a, 12.0), ms[(size_t)f * LCS_TRK_MEAS + 4]);
       }
       st(&ac_td[(cp * max_rs + f) * 72 + t], o);
     }
@@ -652,146 +650,97 @@ __global__ __launch_bounds__(256) void k_trk_cut_copy(const void *__restrict__ c
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
+// Which arrays a buffer holds, where they start and how long they are: trk_layout.h, for the block workspace, the staging block,
+// the statistics and the cutter alike.  Nothing below computes a size or an offset of its own.
 namespace {
-// Where lcs_track_block leaves its intermediate results in the block workspace (lcs_track_stats reads them back)
-struct TrkLayout {
-  int rs_cap, n_off;
-  size_t N, C4;
-  double *d_fo, *d_ft, *d_late, *d_bpo, *d_rs, *d_shift, *d_fm, *d_meas;
-  int *d_idx, *d_nrs, *d_nmeas, *d_upto, *d_mibok, *d_mibfirst;
-  double2 *d_raw, *d_filt;
-  unsigned long long *d_mibbits;
-  TrkLayout(const lcs_ctx *c, int n_cells, int n_sym) {
-    rs_cap = n_sym / 3 + 4;                               // reference symbols of one port in the block: at most 2 per slot of >= 6 symbols
-    n_off = std::max(0, n_sym / 120 - 3);                 // frame offsets that could hold four frames (120 = extended-CP frame)
-    N = (size_t)n_cells * n_sym; C4 = (size_t)n_cells * 4;
-    d_fo = c->trk_meta; d_ft = d_fo + N; d_late = d_ft + N; d_bpo = d_late + N;
-    d_rs = c->trk_rs; d_shift = d_rs + (size_t)n_cells * 140 * 24;
-    d_idx = c->trk_idx; d_nrs = d_idx + C4 * rs_cap;
-    d_raw = c->trk_raw; d_filt = d_raw + C4 * rs_cap * 12;
-    d_fm = c->trk_fmeta; d_meas = d_fm + C4 * rs_cap * 4;
-    d_nmeas = c->trk_small; d_upto = d_nmeas + C4; d_mibok = d_upto + C4;
-    d_mibbits = reinterpret_cast<unsigned long long *>(d_mibok + (((size_t)n_cells * n_off + 1) & ~(size_t)1));
-    d_mibfirst = c->trk_small + C4 * 2 + (size_t)n_cells * (n_off + 1) * 3;
-  }
-};
-}  // namespace
-
-namespace {
-// What the block workspace already holds when lcs_track_stream_block calls in (continuous tracking)
-struct TrkCarried {
-  int n_tail;              // the first n_tail symbols of every cell have their frequency-domain rows in trk_syms (restored from the previous call)
+enum class TrkTd { host, device, workspace };      // where td lies; workspace: the continuous form has put it into TA_TD already
+struct TrkIn {
+  lcs_track_cell *cells;   // bulk_phase_offset: in before, out after the block
+  TrkShape s;
+  const void *td; TrkTd td_at;      // [n_cells][n_sym][128] (TrkTd::workspace: rows n_tail .. n_sym - 1; the rows before are never read)
+  const double *freq_off, *frame_timing, *late;
+  SlotParams par;
+  // what the workspace already holds when lcs_track_stream_block calls in (continuous tracking; a block that starts from nothing: 0, null)
+  int n_tail;              // the first n_tail symbols of every cell have their frequency-domain rows in TA_SYMS (restored from the previous call)
   const int *mib_first;    // host [n_cells]: frame offsets below were attempted by an earlier call and are not decoded again
 };
+struct TrkOut {            // host arrays as lcs.h documents them for lcs_track_block, null = not wanted
+  double *syms, *ce, *ce_pw; int32_t *ce_upto;
+  double *meas; int max_rs; int32_t *n_meas;
+  int32_t *mib_ok; uint64_t *mib_bits; int max_off;
+  float *gpu_ms;
+};
 
-// The workspace grows to the largest (cells, symbols) shape seen and serves every smaller one: TrkLayout places the arrays
-// by the block's own shape, every array's size is monotone in both.  (Round 3 reallocated all eleven buffers -- eleven
-// device-wide synchronisations -- whenever the shape changed, which the continuous form does with every call whose block is
-// not a whole number of frames.)
-int trk_ensure_ws(lcs_ctx *c, int n_cells, int n_sym) {
-  c->trk_last_cells = c->trk_last_sym = 0;
-  if (n_cells > c->trk_cells_cap || n_sym > c->trk_sym_cap) {
-    const int cc = std::max(n_cells, c->trk_cells_cap), cs = std::max(n_sym + n_sym / 8, c->trk_sym_cap);     // head room for the tail's varying length
-    const int rs_cap = cs / 3 + 4, n_off = std::max(0, cs / 120 - 3);     // as TrkLayout
-    const size_t N = (size_t)cc * cs, C4 = (size_t)cc * 4;
-    int rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // the caps describe a complete workspace or nothing: if an allocation below fails, later calls must not take the
-    // half-replaced buffers for the old shape
-    c->trk_cells_cap = c->trk_sym_cap = 0;
-    if ((rc = c->trk_td.alloc(c, N * 128)) || (rc = c->trk_meta.alloc(c, N * 4)) || (rc = c->trk_cells.alloc(c, (size_t)cc)) ||
-        (rc = c->trk_syms.alloc(c, N * 72)) || (rc = c->trk_rs.alloc(c, (size_t)cc * 140 * 28)) ||
-        (rc = c->trk_idx.alloc(c, C4 * (rs_cap + 1))) || (rc = c->trk_raw.alloc(c, C4 * rs_cap * 24)) ||
-        (rc = c->trk_fmeta.alloc(c, C4 * rs_cap * (4 + TRK_MEAS))) || (rc = c->trk_ce.alloc(c, C4 * cs * 72)) ||
-        (rc = c->trk_pw.alloc(c, C4 * cs * 4)) || (rc = c->trk_small.alloc(c, C4 * 2 + (size_t)cc * (n_off + 1) * 3 + cc)))
-      return rc;
-    c->trk_cells_cap = cc; c->trk_sym_cap = cs;
-  }
-  c->trk_last_cells = n_cells; c->trk_last_sym = n_sym;
-  return LCS_OK;
-}
-
-// td: [n_cells][n_sym][128] on the host (td_on_device 0), on the device (1), or -- td_on_device 2, the continuous form --
-// already in trk_td (rows carry->n_tail .. n_sym - 1; the rows before are never read)
-int trk_block(lcs_ctx *c, lcs_track_cell *cells, int n_cells, int n_sym, const void *td, int td_on_device,
-              const double *freq_off, const double *frame_timing, const double *late, double fc_requested,
-              double fc_programmed, double fs_programmed, double *syms, double *ce, double *ce_pw,
-              int32_t *ce_upto, double *meas, int max_rs, int32_t *n_meas, int32_t *mib_ok, uint64_t *mib_bits,
-              int max_off, float *gpu_ms, const TrkCarried *carry) {
-  const int rs_cap = n_sym / 3 + 4, n_off = std::max(0, n_sym / 120 - 3);     // as TrkLayout
-  int rc;
-  if ((rc = trk_ensure_ws(c, n_cells, n_sym))) return rc;
-  const TrkLayout L(c, n_cells, n_sym);
-  const size_t N = L.N, C4 = L.C4;
-  double *d_fo = L.d_fo, *d_ft = L.d_ft, *d_late = L.d_late, *d_bpo = L.d_bpo, *d_rs = L.d_rs, *d_shift = L.d_shift;
-  int *d_idx = L.d_idx, *d_nrs = L.d_nrs, *d_nmeas = L.d_nmeas, *d_upto = L.d_upto, *d_mibok = L.d_mibok;
-  double2 *d_raw = L.d_raw, *d_filt = L.d_filt;
-  double *d_fm = L.d_fm, *d_meas = L.d_meas;
-  unsigned long long *d_mibbits = L.d_mibbits;
-  const double2 *d_td = (td_on_device == 1) ? (const double2 *)td : c->trk_td;
-  const int sym_first = carry ? carry->n_tail : 0;
-  // One reusable host block for the small traffic of a call (round 4): the three metadata arrays go up as ONE copy (d_fo,
-  // d_ft, d_late are adjacent in trk_meta), the measurement tables come down into the same block -- no per-call vectors
-  // (6 MB zero-filled and 71 k row copies per call before).  Plain pageable memory on purpose: with a PAGE-LOCKED block the
-  // copies become asynchronous stream operations on the copy engines, and blocks of different contexts stopped overlapping
-  // (three contexts in flight: 43 M symbols/s page-locked, 73 M pageable; profiles/r04/experiments/tracker_staging.txt).
-  const size_t n_meas_d = C4 * rs_cap * TRK_MEAS, n_small = C4 * 2 + (size_t)n_cells * n_off, n_bits = (size_t)n_cells * n_off + 1;
-  const size_t up_bytes = sizeof(double) * 3 * N + sizeof(lcs_track_cell) * n_cells;
-  const size_t down_bytes = sizeof(double) * n_meas_d + sizeof(unsigned long long) * n_bits + sizeof(int) * n_small + sizeof(lcs_track_cell) * n_cells;
-  if (c->trk_hpin && up_bytes + down_bytes + 64 > c->trk_hpin.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if ((rc = c->trk_hpin.reserve(c, up_bytes + down_bytes + 64))) return rc;
-  double *h_up = reinterpret_cast<double *>(c->trk_hpin.get());
-  lcs_track_cell *h_cells_up = reinterpret_cast<lcs_track_cell *>(h_up + 3 * N);
-  double *h_meas = reinterpret_cast<double *>(c->trk_hpin + ((up_bytes + 15) & ~(size_t)15));
-  unsigned long long *h_bits = reinterpret_cast<unsigned long long *>(h_meas + n_meas_d);
-  int *h_small = reinterpret_cast<int *>(h_bits + n_bits);
-  lcs_track_cell *h_cells_down = reinterpret_cast<lcs_track_cell *>(h_small + ((n_small + 1) & ~(size_t)1));
-  std::memcpy(h_up, freq_off, sizeof(double) * N);
-  std::memcpy(h_up + N, frame_timing, sizeof(double) * N);
-  std::memcpy(h_up + 2 * N, late, sizeof(double) * N);
-  std::memcpy(h_cells_up, cells, sizeof(lcs_track_cell) * n_cells);
-  if (!td_on_device) HIPCHK(c, hipMemcpyAsync(c->trk_td, td, sizeof(double2) * N * 128, hipMemcpyHostToDevice, c->stream));
-  if (carry && carry->mib_first) HIPCHK(c, hipMemcpyAsync(L.d_mibfirst, carry->mib_first, sizeof(int) * n_cells, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_fo, h_up, sizeof(double) * 3 * N, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->trk_cells, h_cells_up, sizeof(lcs_track_cell) * n_cells, hipMemcpyHostToDevice, c->stream));
+int trk_block(lcs_ctx *c, const TrkIn &in, const TrkOut &out) {
+  const int n_cells = in.s.n_cells, n_sym = in.s.n_sym, rs_cap = trk_rs_cap(n_sym), n_off = trk_n_off(n_sym);
+  // The workspace grows to the largest (cells, symbols) shape seen and serves every smaller one -- the arrays are placed by the block's own
+  // shape, every size and offset is monotone in both --, so the continuous form's ever-changing block lengths cost no reallocation.
+  c->trk.last = TrkShape();
+  int rc = c->trk.block.reserve(c, in.s);
+  if (rc) return rc;
+  c->trk.last = in.s;
+  const auto &B = c->trk.block;
+  const TrkLay L = trk_layout(in.s);
+  auto D = [&](int a) { return B.at<double>(L, a); };
+  auto Z = [&](int a) { return B.at<double2>(L, a); };
+  auto I = [&](int a) { return B.at<int>(L, a); };
+  lcs_track_cell *d_cells = B.at<lcs_track_cell>(L, TA_CELLS);
+  const double2 *d_td = (in.td_at == TrkTd::device) ? (const double2 *)in.td : Z(TA_TD);
+  const int *d_mibfirst = in.mib_first ? I(TA_MIBFIRST) : nullptr;
+  // One reusable host block for the small traffic of a call: the three metadata arrays go up as ONE copy (TA_FO, TA_FT, TA_LATE are
+  // adjacent), the measurement tables come down into the same block.  Plain pageable memory on purpose: with a PAGE-LOCKED block
+  // blocks of different contexts stopped overlapping (43 M against 73 M symbols/s; profiles/r04/experiments/tracker_staging.txt).
+  if (c->trk.stage && L.bytes[TB_STAGE] > c->trk.stage.capacity()) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if ((rc = c->trk.stage.reserve(c, L.bytes[TB_STAGE]))) return rc;
+  char *h = c->trk.stage;
+  std::memcpy(h + L.off[TH_FO], in.freq_off, L.size(TH_FO));
+  std::memcpy(h + L.off[TH_FT], in.frame_timing, L.size(TH_FT));
+  std::memcpy(h + L.off[TH_LATE], in.late, L.size(TH_LATE));
+  std::memcpy(h + L.off[TH_CELLS_UP], in.cells, L.size(TH_CELLS_UP));
+  if (in.td_at == TrkTd::host) HIPCHK(c, hipMemcpyAsync(Z(TA_TD), in.td, L.size(TA_TD), hipMemcpyHostToDevice, c->stream));
+  if (d_mibfirst) HIPCHK(c, hipMemcpyAsync(I(TA_MIBFIRST), in.mib_first, L.size(TA_MIBFIRST), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(D(TA_FO), h + L.off[TH_FO], 3 * L.size(TA_FO), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_cells, h + L.off[TH_CELLS_UP], L.size(TA_CELLS), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_xc0, c->stream));
-  hipLaunchKernelGGL(k_trk_prep, dim3(n_cells), dim3(128), 0, c->stream, c->trk_cells, n_sym, d_fo, c->d_pn_jump, d_rs, d_shift, d_bpo, d_idx,
-                     d_nrs, rs_cap);
-  if (n_sym > sym_first)
-    hipLaunchKernelGGL(k_trk_fd, dim3((n_sym - sym_first + TRK_FD_SYM - 1) / TRK_FD_SYM, n_cells), dim3(64 * TRK_FD_SYM), 0, c->stream, c->trk_cells, n_sym,
-                       sym_first, d_td, d_fo, d_late, d_bpo, fc_requested, fc_programmed, fs_programmed, c->trk_syms);
-  hipLaunchKernelGGL(k_trk_ce, dim3(4, n_cells, std::max(1, (rs_cap - 2 + TRK_CE_CH - 1) / TRK_CE_CH)), dim3(TRK_CE_THREADS), 0, c->stream, c->trk_cells, n_sym, c->trk_syms, d_fo, d_ft, d_rs, d_shift,
-                     d_idx, d_nrs, rs_cap, fc_requested, fc_programmed, fs_programmed, d_raw, d_filt, d_fm, d_meas, d_nmeas, c->trk_ce,
-                     c->trk_pw, d_upto);
+  hipLaunchKernelGGL(k_trk_prep, dim3(n_cells), dim3(128), 0, c->stream, d_cells, n_sym, D(TA_FO), c->d_pn_jump, D(TA_RS), D(TA_SHIFT), D(TA_BPO), I(TA_IDX),
+                     I(TA_NRS), rs_cap);
+  if (n_sym > in.n_tail)
+    hipLaunchKernelGGL(k_trk_fd, dim3((n_sym - in.n_tail + TRK_FD_SYM - 1) / TRK_FD_SYM, n_cells), dim3(64 * TRK_FD_SYM), 0, c->stream, d_cells, n_sym,
+                       in.n_tail, d_td, D(TA_FO), D(TA_LATE), D(TA_BPO), in.par.fc_req, in.par.fc_prog, in.par.fs_prog, Z(TA_SYMS));
+  hipLaunchKernelGGL(k_trk_ce, dim3(4, n_cells, std::max(1, (rs_cap - 2 + TRK_CE_CH - 1) / TRK_CE_CH)), dim3(TRK_CE_THREADS), 0, c->stream, d_cells, n_sym, Z(TA_SYMS), D(TA_FO), D(TA_FT), D(TA_RS), D(TA_SHIFT),
+                     I(TA_IDX), I(TA_NRS), rs_cap, in.par.fc_req, in.par.fc_prog, in.par.fs_prog, Z(TA_RAW), Z(TA_FILT), D(TA_FM), D(TA_MEAS), I(TA_NMEAS), Z(TA_CE),
+                     D(TA_PW), I(TA_UPTO));
   if (n_off > 0)
-    hipLaunchKernelGGL(k_trk_mib, dim3(n_off, n_cells), dim3(TRK_PB_THREADS), 0, c->stream, c->trk_cells, n_sym, n_off, c->trk_syms, c->trk_ce,
-                       c->trk_pw, d_upto, c->d_pbch_scr, c->d_derm_inv, d_mibok, d_mibbits,
-                       (carry && carry->mib_first) ? (const int *)L.d_mibfirst : (const int *)nullptr);
+    hipLaunchKernelGGL(k_trk_mib, dim3(n_off, n_cells), dim3(TRK_PB_THREADS), 0, c->stream, d_cells, n_sym, n_off, Z(TA_SYMS), Z(TA_CE),
+                       D(TA_PW), I(TA_UPTO), c->d_pbch_scr, c->d_derm_inv, I(TA_MIBOK), B.at<unsigned long long>(L, TA_MIBBITS), d_mibfirst);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev_xc1, c->stream));
-  // results
-  HIPCHK(c, hipMemcpyAsync(h_cells_down, c->trk_cells, sizeof(lcs_track_cell) * n_cells, hipMemcpyDeviceToHost, c->stream));
-  if (syms) HIPCHK(c, hipMemcpyAsync(syms, c->trk_syms, sizeof(double2) * N * 72, hipMemcpyDeviceToHost, c->stream));
-  if (ce) HIPCHK(c, hipMemcpyAsync(ce, c->trk_ce, sizeof(double2) * C4 * n_sym * 72, hipMemcpyDeviceToHost, c->stream));
-  if (ce_pw) HIPCHK(c, hipMemcpyAsync(ce_pw, c->trk_pw, sizeof(double) * C4 * n_sym * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_meas, d_meas, sizeof(double) * n_meas_d, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_small, c->trk_small, sizeof(int) * n_small, hipMemcpyDeviceToHost, c->stream));
-  if (n_off > 0) HIPCHK(c, hipMemcpyAsync(h_bits, d_mibbits, sizeof(unsigned long long) * n_cells * n_off, hipMemcpyDeviceToHost, c->stream));
+  // results: TA_NMEAS, TA_UPTO and TA_MIBOK are adjacent, here and in the staging block, and come down as one copy
+  HIPCHK(c, hipMemcpyAsync(h + L.off[TH_CELLS_DOWN], d_cells, L.size(TA_CELLS), hipMemcpyDeviceToHost, c->stream));
+  if (out.syms) HIPCHK(c, hipMemcpyAsync(out.syms, Z(TA_SYMS), L.size(TA_SYMS), hipMemcpyDeviceToHost, c->stream));
+  if (out.ce) HIPCHK(c, hipMemcpyAsync(out.ce, Z(TA_CE), L.size(TA_CE), hipMemcpyDeviceToHost, c->stream));
+  if (out.ce_pw) HIPCHK(c, hipMemcpyAsync(out.ce_pw, D(TA_PW), L.size(TA_PW), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h + L.off[TH_MEAS], D(TA_MEAS), L.size(TA_MEAS), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h + L.off[TH_NMEAS], I(TA_NMEAS), L.size(TA_NMEAS) + L.size(TA_UPTO) + L.size(TA_MIBOK), hipMemcpyDeviceToHost, c->stream));
+  if (n_off > 0) HIPCHK(c, hipMemcpyAsync(h + L.off[TH_BITS], B.at<char>(L, TA_MIBBITS), L.size(TA_MIBBITS), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  std::memcpy(cells, h_cells_down, sizeof(lcs_track_cell) * n_cells);
-  if (gpu_ms) HIPCHK(c, hipEventElapsedTime(gpu_ms, c->ev_xc0, c->ev_xc1));
+  std::memcpy(in.cells, h + L.off[TH_CELLS_DOWN], L.size(TH_CELLS_DOWN));
+  if (out.gpu_ms) HIPCHK(c, hipEventElapsedTime(out.gpu_ms, c->ev_xc0, c->ev_xc1));
+  const int *h_nmeas = L.at<int>(h, TH_NMEAS), *h_upto = L.at<int>(h, TH_UPTO), *h_mibok = L.at<int>(h, TH_MIBOK), max_rs = out.max_rs, max_off = out.max_off;
+  const double *h_meas = L.at<double>(h, TH_MEAS);
+  const uint64_t *h_bits = L.at<uint64_t>(h, TH_BITS);
   rc = LCS_OK;
-  for (size_t q = 0; q < C4; ++q) {
-    int nm = h_small[q];
-    if (n_meas) n_meas[q] = std::min(nm, max_rs);
+  for (size_t q = 0; q < L.n[TA_NMEAS]; ++q) {
+    const int nm = h_nmeas[q];
+    if (out.n_meas) out.n_meas[q] = std::min(nm, max_rs);
     if (nm > max_rs) rc = LCS_ERR_OVERFLOW;
-    if (ce_upto) ce_upto[q] = h_small[C4 + q];
-    if (meas && nm > 0) std::memcpy(meas + q * (size_t)max_rs * TRK_MEAS, h_meas + q * (size_t)rs_cap * TRK_MEAS, sizeof(double) * TRK_MEAS * std::min(nm, max_rs));
+    if (out.ce_upto) out.ce_upto[q] = h_upto[q];
+    if (out.meas && nm > 0) std::memcpy(out.meas + q * (size_t)max_rs * LCS_TRK_MEAS, h_meas + q * (size_t)rs_cap * LCS_TRK_MEAS, sizeof(double) * LCS_TRK_MEAS * std::min(nm, max_rs));
   }
   for (int i = 0; i < n_cells; ++i)
     for (int o = 0; o < max_off; ++o) {
-      if (mib_ok) mib_ok[(size_t)i * max_off + o] = (o < n_off) ? h_small[C4 * 2 + (size_t)i * n_off + o] : -1;
-      if (mib_bits) mib_bits[(size_t)i * max_off + o] = (o < n_off) ? h_bits[(size_t)i * n_off + o] : 0ull;
+      if (out.mib_ok) out.mib_ok[(size_t)i * max_off + o] = (o < n_off) ? h_mibok[(size_t)i * n_off + o] : -1;
+      if (out.mib_bits) out.mib_bits[(size_t)i * max_off + o] = (o < n_off) ? h_bits[(size_t)i * n_off + o] : 0ull;
     }
   if (rc) c->err = "more reference symbols per port than max_rs rows";
   return rc;
@@ -811,8 +760,10 @@ extern "C" int lcs_track_block(lcs_ctx *c, lcs_track_cell *cells, int n_cells, i
         t.n_ports < 1 || t.n_ports > 4) { c->err = "tracked cell needs n_id_1, n_id_2, a known cp_type and 1..4 ports"; return LCS_ERR_BAD_ARG; }
   }
   HIPCHK(c, hipSetDevice(c->device));
-  return trk_block(c, cells, n_cells, n_sym, td, td_on_device ? 1 : 0, freq_off, frame_timing, late, fc_requested, fc_programmed, fs_programmed, syms, ce,
-                   ce_pw, ce_upto, meas, max_rs, n_meas, mib_ok, mib_bits, max_off, gpu_ms, nullptr);
+  const TrkIn in = {cells, TrkShape{n_cells, n_sym}, td, td_on_device ? TrkTd::device : TrkTd::host, freq_off, frame_timing, late,
+                    SlotParams{fc_requested, fc_programmed, fs_programmed}, 0, nullptr};
+  const TrkOut out = {syms, ce, ce_pw, ce_upto, meas, max_rs, n_meas, mib_ok, mib_bits, max_off, gpu_ms};
+  return trk_block(c, in, out);
 }
 
 // The producer thread's symbol extraction (see k_trk_cut_hits): d_capbuf and d_td are DEVICE memory.
@@ -832,21 +783,20 @@ extern "C" int lcs_track_cut(lcs_ctx *c, const void *d_capbuf, int fmt, uint32_t
     }
   }
   HIPCHK(c, hipSetDevice(c->device));
+  auto &K = c->trk.cut;
   const size_t N = (size_t)n_cells * n_sym;
-  if (N > c->trk_cut_cap || n_cells > c->trk_cut_cells_cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t capN = std::max(N, c->trk_cut_cap);
-    const int capC = std::max(n_cells, c->trk_cut_cells_cap);
-    c->trk_cut_cap = 0; c->trk_cut_cells_cap = 0;
-    int rc;
-    if ((rc = c->trk_cut_hit.alloc(c, capN + 4 * (size_t)capC + 2)) || (rc = c->trk_cut_meta.alloc(c, capN + 5 * (size_t)capC))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->trk_cut_hit, 0, sizeof(int) * (capN + 4 * (size_t)capC + 2), c->stream));      // the per-cell flags start at zero
-    c->trk_cut_cap = capN; c->trk_cut_cells_cap = capC;
+  if (N > K.cap.n || (size_t)n_cells > K.cap.n_cells) {
+    const TrkCutCap cap = {std::max((size_t)n_cells, K.cap.n_cells), std::max(N, K.cap.n)};
+    const TrkLay grown = trk_layout(trk_cut_dims(cap.n_cells, cap.n));
+    if (const int rc = K.regrow(c, grown, cap)) return rc;
+    const hipError_t e = hipMemsetAsync(K.at<char>(grown, TA_CUT_HIT), 0, grown.bytes[TB_CUT_HIT], c->stream);      // the per-cell flags start at zero
+    if (e != hipSuccess) { K.cap = TrkCutCap(); return lcs_hip_error(c, "hipMemsetAsync", e); }
   }
-  // hit [cells][symbols], then the per-cell counts, flags and next positions at FIXED offsets (the flags keep their zeros from call to call)
-  int *d_hit = c->trk_cut_hit, *d_ncut = d_hit + c->trk_cut_cap, *d_flags = d_ncut + c->trk_cut_cells_cap;
-  long long *d_pos = reinterpret_cast<long long *>(d_hit + ((c->trk_cut_cap + 2 * (size_t)c->trk_cut_cells_cap + 1) & ~(size_t)1));
-  double *d_late = c->trk_cut_meta, *d_cells = d_late + c->trk_cut_cap;
+  // placed by the CAPACITY, so the per-cell flags keep their place -- and their zeros -- from call to call
+  const TrkLay L = trk_layout(trk_cut_dims(K.cap.n_cells, K.cap.n));
+  int *d_hit = K.at<int>(L, TA_CUT_HIT), *d_ncut = K.at<int>(L, TA_CUT_N), *d_flags = K.at<int>(L, TA_CUT_FLAGS);
+  long long *d_pos = K.at<long long>(L, TA_CUT_POS);
+  double *d_late = K.at<double>(L, TA_CUT_LATE), *d_cells = K.at<double>(L, TA_CUT_CELLS);
   std::vector<double> h_cells((size_t)5 * n_cells);
   for (int i = 0; i < n_cells; ++i) {
     h_cells[5 * i] = (double)cp_type[i]; h_cells[5 * i + 1] = frame_timing[i]; h_cells[5 * i + 2] = freq_off[i];
@@ -873,47 +823,37 @@ extern "C" int lcs_track_cut(lcs_ctx *c, const void *d_capbuf, int fmt, uint32_t
 extern "C" int lcs_track_stats(lcs_ctx *c, int n_cells, int n_sym, double *ac_fd, double *ac_td, int max_rs, double *sync, double *sync_ce,
                                int max_hf, int32_t *n_hf) {
   if (!c) return LCS_ERR_BAD_ARG;
-  if (n_cells < 1 || n_cells != c->trk_last_cells || n_sym != c->trk_last_sym || max_rs < 0 || max_hf < 0) {
+  if (n_cells < 1 || n_cells != c->trk.last.n_cells || n_sym != c->trk.last.n_sym || max_rs < 0 || max_hf < 0) {
     c->err = "lcs_track_stats describes the block of the last lcs_track_block call on this context (same n_cells, n_sym)";
     return LCS_ERR_BAD_ARG;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  const TrkLayout L(c, n_cells, n_sym);
-  const int rs_cap = L.rs_cap;
-  const size_t C4 = L.C4;
-  const int hf_cap = n_sym / 60 + 2;                       // PSS/SSS pairs of the block: two per frame of >= 120 symbols
-  int rc;
-  if (n_cells > c->trk_stat_cells || n_sym > c->trk_stat_sym) {      // grow only, like the block workspace
-    const int cc = std::max(n_cells, c->trk_stat_cells), cs = std::max(n_sym + n_sym / 8, c->trk_stat_sym);
-    const size_t C4c = (size_t)cc * 4, rsc = (size_t)cs / 3 + 4, hfc = (size_t)cs / 60 + 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->trk_stat_cells = c->trk_stat_sym = 0;
-    if ((rc = c->trk_acfd.alloc(c, C4c * rsc * 12)) || (rc = c->trk_actd.alloc(c, C4c * rsc * 72)) ||
-        (rc = c->trk_sync.alloc(c, (size_t)cc * hfc * 4)) || (rc = c->trk_syncce.alloc(c, (size_t)cc * hfc * 72)))
-      return rc;
-    c->trk_stat_cells = cc; c->trk_stat_sym = cs;
-  }
-  const double2 *d_raw = L.d_raw;
-  const double *d_meas = L.d_meas;
-  const int *d_nmeas = L.d_nmeas;
-  std::vector<int> h_nmeas(C4);
-  std::vector<lcs_track_cell> h_cells(n_cells);
+  const auto &B = c->trk.block;
+  auto &S = c->trk.stats;
+  const TrkLay L = trk_layout(c->trk.last);
+  const int rs_cap = trk_rs_cap(n_sym), hf_cap = trk_hf_cap(n_sym);
+  int rc = S.reserve(c, c->trk.last);      // grow only, like the block workspace
+  if (rc) return rc;
+  lcs_track_cell *d_cells = B.at<lcs_track_cell>(L, TA_CELLS);
+  double2 *d_acfd = S.at<double2>(L, TA_ACFD), *d_actd = S.at<double2>(L, TA_ACTD), *d_syncce = S.at<double2>(L, TA_SYNCCE);
+  double *d_sync = S.at<double>(L, TA_SYNC);
+  std::vector<int> h_nmeas(L.n[TA_NMEAS]); std::vector<lcs_track_cell> h_cells(n_cells);
   if (ac_fd || ac_td)
-    hipLaunchKernelGGL(k_trk_acf, dim3(4, n_cells), dim3(256), 0, c->stream, c->trk_cells, d_nmeas, rs_cap, d_raw, d_meas,
-                       ac_fd ? c->trk_acfd : nullptr, ac_td ? c->trk_actd : nullptr);
-  hipLaunchKernelGGL(k_trk_sync, dim3((n_cells * hf_cap + 63) / 64), dim3(64), 0, c->stream, c->trk_cells, n_cells, n_sym, hf_cap, c->trk_syms,
-                     c->d_pss_fd, c->d_sss_fd, c->trk_sync, c->trk_syncce);
+    hipLaunchKernelGGL(k_trk_acf, dim3(4, n_cells), dim3(256), 0, c->stream, d_cells, B.at<int>(L, TA_NMEAS), rs_cap, B.at<double2>(L, TA_RAW), B.at<double>(L, TA_MEAS),
+                       ac_fd ? d_acfd : nullptr, ac_td ? d_actd : nullptr);
+  hipLaunchKernelGGL(k_trk_sync, dim3((n_cells * hf_cap + 63) / 64), dim3(64), 0, c->stream, d_cells, n_cells, n_sym, hf_cap, B.at<double2>(L, TA_SYMS),
+                     c->d_pss_fd, c->d_sss_fd, d_sync, d_syncce);
   HIPCHK(c, hipGetLastError());
-  std::vector<double> h_fd, h_td, h_sync((size_t)n_cells * hf_cap * 4), h_ce;
-  if (ac_fd) { h_fd.resize(C4 * rs_cap * 24); HIPCHK(c, hipMemcpyAsync(h_fd.data(), c->trk_acfd, sizeof(double) * h_fd.size(), hipMemcpyDeviceToHost, c->stream)); }
-  if (ac_td) { h_td.resize(C4 * rs_cap * 144); HIPCHK(c, hipMemcpyAsync(h_td.data(), c->trk_actd, sizeof(double) * h_td.size(), hipMemcpyDeviceToHost, c->stream)); }
-  if (sync_ce) { h_ce.resize((size_t)n_cells * hf_cap * 144); HIPCHK(c, hipMemcpyAsync(h_ce.data(), c->trk_syncce, sizeof(double) * h_ce.size(), hipMemcpyDeviceToHost, c->stream)); }
-  HIPCHK(c, hipMemcpyAsync(h_sync.data(), c->trk_sync, sizeof(double) * h_sync.size(), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_nmeas.data(), d_nmeas, sizeof(int) * C4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_cells.data(), c->trk_cells, sizeof(lcs_track_cell) * n_cells, hipMemcpyDeviceToHost, c->stream));
+  std::vector<double> h_fd, h_td, h_sync(L.n[TA_SYNC]), h_ce;
+  if (ac_fd) { h_fd.resize(2 * L.n[TA_ACFD]); HIPCHK(c, hipMemcpyAsync(h_fd.data(), d_acfd, L.size(TA_ACFD), hipMemcpyDeviceToHost, c->stream)); }
+  if (ac_td) { h_td.resize(2 * L.n[TA_ACTD]); HIPCHK(c, hipMemcpyAsync(h_td.data(), d_actd, L.size(TA_ACTD), hipMemcpyDeviceToHost, c->stream)); }
+  if (sync_ce) { h_ce.resize(2 * L.n[TA_SYNCCE]); HIPCHK(c, hipMemcpyAsync(h_ce.data(), d_syncce, L.size(TA_SYNCCE), hipMemcpyDeviceToHost, c->stream)); }
+  HIPCHK(c, hipMemcpyAsync(h_sync.data(), d_sync, L.size(TA_SYNC), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h_nmeas.data(), B.at<int>(L, TA_NMEAS), L.size(TA_NMEAS), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h_cells.data(), d_cells, L.size(TA_CELLS), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   rc = LCS_OK;
-  for (size_t q = 0; q < C4; ++q) {
+  for (size_t q = 0; q < h_nmeas.size(); ++q) {
     const int rows = std::min(h_nmeas[q], max_rs);
     if (h_nmeas[q] > max_rs) rc = LCS_ERR_OVERFLOW;
     if (ac_fd) std::memcpy(ac_fd + q * max_rs * 24, &h_fd[q * rs_cap * 24], sizeof(double) * 24 * rows);
@@ -934,24 +874,216 @@ extern "C" int lcs_track_stats(lcs_ctx *c, int n_cells, int n_sym, double *ac_fd
 }
 
 // ------------------------------------------------------------------------------------------ continuous tracking
-// The reference's tracker thread never stops: the three-symbol window of filter_ce (ref src/tracker_thread.cpp:176-201),
-// the interpolation between consecutive filtered reference symbols (:383-477), the 72-deep history of do_ac_td (:343-371)
-// and the four-frame fifo of do_mib_decode (:552-745) all reach across any boundary one could cut the symbol stream at.
-// lcs_track_block cuts it: each call starts from nothing.  lcs_track_stream_block removes the cut for a caller that
-// delivers a cell's symbols block after block: the context keeps the last three-to-four frames of every stream -- their
-// frequency-domain rows (get_fd's output) on the device, their metadata and the bulk phase at their first symbol on the
-// host -- and every call processes [carried frames ++ new symbols] as one block that starts at a frame boundary, with the
-// same kernels, so each output row is computed exactly as a single call over the whole stream would compute it (nothing in
-// the pipeline reaches back further than the carried frames), and hands out only the rows no earlier call could: every
-// filtered reference symbol, channel-estimate row, autocorrelation row and MIB attempt exactly once, under its index in the
-// whole stream.  The carried frames are not transformed again (k_trk_fd starts behind them; the rows are the ones the
-// previous call computed, bit for bit) and frame offsets an earlier call attempted are not decoded again (k_trk_mib skips
-// them); the per-port passes of k_trk_ce still run over them (the raw estimates and filter windows they rebuild are cheap).
+// The reference's tracker thread never stops: the three-symbol window of filter_ce (ref src/tracker_thread.cpp:176-201), the interpolation
+// between consecutive filtered reference symbols (:383-477), the 72-deep history of do_ac_td (:343-371) and the four-frame fifo of
+// do_mib_decode (:552-745) all reach across any boundary one could cut the symbol stream at.  lcs_track_block cuts it: each call starts
+// from nothing.  lcs_track_stream_block removes the cut for a caller that delivers a cell's symbols block after block: the context keeps
+// the last three-to-four frames of every stream (trk_layout.h: trk_stream_step) -- their frequency-domain rows on the device, their
+// metadata and the bulk phase at their first symbol on the host -- and every call processes [carried frames ++ new symbols] as one
+// block that starts at a frame boundary, with the same kernels, so each output row is computed exactly as a single call over the whole
+// stream would compute it, and hands out only the rows no earlier call could: every filtered reference symbol, channel-estimate row,
+// autocorrelation row and MIB attempt exactly once, under its index in the whole stream.  The carried frames are not transformed again
+// (k_trk_fd starts behind them) and frame offsets an earlier call attempted are not decoded again (k_trk_mib skips them); the per-port
+// passes of k_trk_ce still run over them (DESIGN.md 3.5 says why).
 extern "C" int lcs_track_stream_reset(lcs_ctx *c) {
   if (!c) return LCS_ERR_BAD_ARG;
-  c->trk_stream = TrkStream();      // (the carried rows on the device go with it)
+  c->trk.stream = TrkStream();      // (the carried rows on the device go with it)
   return LCS_OK;
 }
+
+namespace {
+// What the caller of lcs_track_stream_block handed over (lcs.h documents every array)
+struct TrkStreamCall {
+  lcs_track_cell *cells; int n_cells, n_sym;
+  const double *td, *freq_off, *frame_timing, *late;
+  SlotParams par;
+  double *syms, *ce, *ce_pw; int ce_cap; int64_t *ce_from; int32_t *ce_n;
+  double *meas, *ac_fd, *ac_td; int max_rs; int32_t *n_meas;
+  int32_t *mib_ok; uint64_t *mib_bits; int max_off; int64_t *mib_from; int32_t *n_mib;
+};
+// The cells of ONE CP type in a call -- they carry the same number of frames, so they make one block of [carried tail ++ fresh
+// symbols] per cell --, and what that block gave
+struct TrkGroup {
+  int cp = 0, F = 0; long long T = 0;         // CP type, symbols per frame, stream index of the block's first symbol
+  std::vector<int> idx;                       // the group's cells in the caller's arrays
+  TrkStreamStep s{};
+  TrkShape shape;                             // of the block: the group's cells x s.L symbols
+  TrkLay lay{};                               // ... and where its arrays lie in the workspace
+  std::vector<lcs_track_cell> gc;
+  std::vector<double> fo, ft, late;           // [cell][L]: the carried metadata joined with the caller's
+  std::vector<int> mib_first;
+  std::vector<double> o_syms, o_ce, o_pw, o_meas, o_fd, o_tdc, bpo_at;      // the block's rows as lcs_track_block and lcs_track_stats hand them
+  std::vector<int32_t> o_upto, o_nmeas, o_ok;                               // out; bpo_at: per cell the bulk phase before the next tail's first symbol
+  std::vector<uint64_t> o_bits;
+};
+
+// 1. The first call starts the stream with the cells it names; every later one must name the same cells.
+int trk_stream_start(lcs_ctx *c, const lcs_track_cell *cells, int n_cells) {
+  TrkStream *st = &c->trk.stream;
+  if (st->cells.empty()) {
+    st->cells.resize(n_cells);
+    for (int i = 0; i < n_cells; ++i) {
+      TrkStreamCell &sc = st->cells[i];
+      sc.cp_type = cells[i].cp_type; sc.n_id_1 = cells[i].n_id_1; sc.n_id_2 = cells[i].n_id_2; sc.n_ports = cells[i].n_ports; sc.bpo_before_tail = cells[i].bulk_phase_offset;
+    }
+  }
+  if ((int)st->cells.size() != n_cells) { c->err = "the stream was started with a different number of cells: lcs_track_stream_reset first"; return LCS_ERR_BAD_ARG; }
+  for (int i = 0; i < n_cells; ++i) {
+    const TrkStreamCell &sc = st->cells[i];
+    if (sc.cp_type != cells[i].cp_type || sc.n_id_1 != cells[i].n_id_1 || sc.n_id_2 != cells[i].n_id_2 || sc.n_ports != cells[i].n_ports)
+      { c->err = "a tracked cell changed identity inside a stream: lcs_track_stream_reset first"; return LCS_ERR_BAD_ARG; }
+  }
+  return LCS_OK;
+}
+
+// 2. The block of the group's cells (g.idx; CP type cp) in the workspace and on the host: the carried rows go back to the head of
+// every cell's rows, the new samples behind them, the metadata likewise.
+int trk_stream_assemble(lcs_ctx *c, const TrkStreamCall &a, int cp, TrkGroup &g) {
+  const TrkStream &st = c->trk.stream;
+  const int G = (int)g.idx.size(), n_sym = a.n_sym;
+  g.cp = cp; g.F = (cp == LCS_CP_NORMAL) ? 140 : 120;
+  g.T = st.cells[g.idx[0]].tail_start;
+  g.s = trk_stream_step(st.cells[g.idx[0]].n_seen, g.T, n_sym, g.F);
+  const int n_tail = g.s.n_tail, L = g.s.L;
+  for (int k = 0; k < G; ++k)
+    if (st.cells[g.idx[k]].n_seen - st.cells[g.idx[k]].tail_start != n_tail || st.cells[g.idx[k]].tail_start != g.T) { c->err = "streams out of step"; return LCS_ERR_BAD_ARG; }
+  g.shape.n_cells = G; g.shape.n_sym = L; g.lay = trk_layout(g.shape);
+  g.gc.resize(G); g.mib_first.resize(G); g.fo.resize((size_t)G * L); g.ft.resize((size_t)G * L); g.late.resize((size_t)G * L);
+  c->trk.last = TrkShape();                                         // the workspace stops describing the last block here
+  if (const int rc = c->trk.block.reserve(c, g.shape)) return rc;
+  double2 *d_td = c->trk.block.at<double2>(g.lay, TA_TD), *d_syms = c->trk.block.at<double2>(g.lay, TA_SYMS);
+  if (n_tail > 0)
+    HIPCHK(c, hipMemcpy2DAsync(d_syms, sizeof(double2) * 72 * (size_t)L, st.d_tail[g.cp], sizeof(double2) * 72 * (size_t)n_tail,
+                               sizeof(double2) * 72 * (size_t)n_tail, G, hipMemcpyDeviceToDevice, c->stream));
+  // the new samples: the group's cells are consecutive in td when the stream has one CP type (the usual case) -- then ONE strided
+  // copy places them all behind their carried rows (64 cells: 64 copies of 2 MB each were 0.3-0.5 ms of a call's host and
+  // copy-engine time); cells of a mixed stream go one by one
+  bool one_copy = true;
+  for (int k = 1; k < G; ++k) one_copy = one_copy && g.idx[k] == g.idx[0] + k;
+  if (one_copy)
+    HIPCHK(c, hipMemcpy2DAsync(d_td + (size_t)n_tail * 128, sizeof(double2) * 128 * (size_t)L, a.td + (size_t)g.idx[0] * n_sym * 256,
+                               sizeof(double2) * 128 * (size_t)n_sym, sizeof(double2) * 128 * (size_t)n_sym, G, hipMemcpyDefault, c->stream));
+  for (int k = 0; k < G; ++k) {
+    const int i = g.idx[k];
+    const TrkStreamCell &sc = st.cells[i];
+    g.gc[k] = a.cells[i];
+    g.gc[k].bulk_phase_offset = sc.bpo_before_tail;
+    // (hipMemcpyDefault: td may be pageable host memory, page-locked host memory -- DMA'd in place -- or device memory)
+    if (!one_copy)
+      HIPCHK(c, hipMemcpyAsync(d_td + ((size_t)k * L + n_tail) * 128, a.td + (size_t)i * n_sym * 256, sizeof(double2) * 128 * (size_t)n_sym,
+                               hipMemcpyDefault, c->stream));
+    auto join = [&](const std::vector<double> &tail, const double *fresh, std::vector<double> &out) {
+      std::copy(tail.begin(), tail.end(), out.begin() + (size_t)k * L);
+      std::copy(fresh + (size_t)i * n_sym, fresh + (size_t)(i + 1) * n_sym, out.begin() + (size_t)k * L + n_tail);
+    };
+    join(sc.fo, a.freq_off, g.fo); join(sc.ft, a.frame_timing, g.ft); join(sc.late, a.late, g.late);
+    g.mib_first[k] = trk_mib_first(sc.mib_next, g.T, g.F);
+  }
+  return LCS_OK;
+}
+
+// 3. The block, and its autocorrelation rows when the caller wants them
+int trk_stream_run(lcs_ctx *c, const TrkStreamCall &a, TrkGroup &g) {
+  const size_t G = g.idx.size(), L = (size_t)g.s.L, offs = (size_t)std::max(1, trk_n_off(g.s.L)), rows = G * 4 * trk_rs_cap(g.s.L);
+  g.o_syms.resize(a.syms ? G * L * 144 : 0); g.o_ce.resize(a.ce ? G * 4 * L * 144 : 0); g.o_pw.resize((a.ce_pw || a.ce) ? G * 4 * L * 4 : 0);
+  g.o_meas.resize(rows * LCS_TRK_MEAS); g.o_fd.resize(a.ac_fd ? rows * 24 : 0); g.o_tdc.resize(a.ac_td ? rows * 144 : 0);
+  g.o_upto.resize(G * 4); g.o_nmeas.resize(G * 4); g.o_ok.resize(G * offs); g.o_bits.resize(G * offs);
+  const TrkIn in = {g.gc.data(), g.shape, nullptr, TrkTd::workspace, g.fo.data(), g.ft.data(), g.late.data(), a.par, g.s.n_tail, g.mib_first.data()};
+  const TrkOut out = {a.syms ? g.o_syms.data() : nullptr, a.ce ? g.o_ce.data() : nullptr, (a.ce || a.ce_pw) ? g.o_pw.data() : nullptr, g.o_upto.data(),
+                      g.o_meas.data(), trk_rs_cap(g.s.L), g.o_nmeas.data(), g.o_ok.data(), g.o_bits.data(), (int)offs, nullptr};
+  int rc = trk_block(c, in, out);
+  if (rc != LCS_OK || !(a.ac_fd || a.ac_td)) return rc;
+  rc = lcs_track_stats(c, g.shape.n_cells, g.shape.n_sym, a.ac_fd ? g.o_fd.data() : nullptr, a.ac_td ? g.o_tdc.data() : nullptr, trk_rs_cap(g.s.L), nullptr, nullptr, 0, nullptr);
+  return rc == LCS_ERR_OVERFLOW ? LCS_OK : rc;      // no PSS/SSS rows were asked for: their overflow is of no concern
+}
+
+// 4. The next carried tail: whole frames from T_next on -- its frequency-domain rows into the spare device buffer, the bulk
+// phase before its first symbol (= the value used at the symbol before it) in ONE strided copy
+int trk_stream_carry(lcs_ctx *c, TrkGroup &g) {
+  DevBuf<double2> &spare = c->trk.stream.d_spare[g.cp];
+  const size_t G = g.idx.size(), L = (size_t)g.s.L, n_keep = g.s.n_keep, need = (size_t)72 * n_keep * G;
+  g.bpo_at.assign(G, 0.0);      // (head room below: the tail's length varies by up to a frame from call to call)
+  int rc;
+  if (need > spare.capacity() && (rc = spare.alloc(c, need + need / 4))) return rc;
+  hipError_t e = hipMemcpy2DAsync(spare, sizeof(double2) * 72 * n_keep, c->trk.block.at<double2>(g.lay, TA_SYMS) + g.s.keep_from * 72, sizeof(double2) * 72 * L,
+                                  sizeof(double2) * 72 * n_keep, G, hipMemcpyDeviceToDevice, c->stream);
+  if (e == hipSuccess && g.s.T_next > g.T)
+    e = hipMemcpy2DAsync(g.bpo_at.data(), sizeof(double), c->trk.block.at<double>(g.lay, TA_BPO) + (g.s.keep_from - 1), sizeof(double) * L, sizeof(double), G,
+                         hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { c->err = std::string("carrying the stream's tail: ") + hipGetErrorString(e); return LCS_ERR_HIP; }
+  return LCS_OK;
+}
+
+// 5. The rows of cell k of the group that no earlier call could hand out, under their index in the whole stream, into the
+// caller's arrays; `sc` is the cell's record as it will stand after the call.  LCS_ERR_OVERFLOW: rows beyond the caller's
+// capacities were dropped.
+int trk_stream_emit(const TrkStreamCall &a, const TrkGroup &g, int k, TrkStreamCell &sc) {
+  const int i = g.idx[k], n_sym = a.n_sym, max_rs = a.max_rs, max_off = a.max_off, ce_cap = a.ce_cap, F = g.F, rs_cap = trk_rs_cap(g.s.L), n_off = trk_n_off(g.s.L);
+  const size_t L = (size_t)g.s.L, keep_from = g.s.keep_from, n_keep = g.s.n_keep, offs = (size_t)std::max(1, n_off);
+  const long long T = g.T;
+  int rc = LCS_OK;
+  a.cells[i].bulk_phase_offset = g.gc[k].bulk_phase_offset;
+  if (a.syms) std::memcpy(a.syms + (size_t)i * n_sym * 144, &g.o_syms[((size_t)k * L + g.s.n_tail) * 144], sizeof(double) * n_sym * 144);
+  for (int p = 0; p < 4; ++p) {
+    const size_t q = (size_t)k * 4 + p, Q = (size_t)i * 4 + p;
+    // filtered reference symbols: row r of the block is raw row r + 1 of the block = raw row (rows before T) + r + 1 of the stream
+    const long long rows_before = (T / F) * (p < 2 ? 40 : 20);
+    int emitted = 0;
+    for (int r = 0; r < g.o_nmeas[q]; ++r) {
+      const long long raw = rows_before + r + 1;
+      if (raw < sc.next_raw[p]) continue;
+      if (emitted < max_rs) {
+        if (a.meas) {
+          double *m = a.meas + (Q * max_rs + emitted) * LCS_TRK_MEAS;
+          std::memcpy(m, &g.o_meas[(q * rs_cap + r) * LCS_TRK_MEAS], sizeof(double) * LCS_TRK_MEAS);
+          m[0] += (double)T;                               // symbol index in the stream
+        }
+        if (a.ac_fd) std::memcpy(a.ac_fd + (Q * max_rs + emitted) * 24, &g.o_fd[(q * rs_cap + r) * 24], sizeof(double) * 24);
+        if (a.ac_td) std::memcpy(a.ac_td + (Q * max_rs + emitted) * 144, &g.o_tdc[(q * rs_cap + r) * 144], sizeof(double) * 144);
+      } else rc = LCS_ERR_OVERFLOW;
+      ++emitted;
+      sc.next_raw[p] = raw + 1;
+    }
+    if (a.n_meas) a.n_meas[Q] = std::min(emitted, max_rs);
+    // channel estimates: symbols [ce_upto, T + upto) are new
+    const long long from = sc.ce_upto[p], upto = (g.o_upto[q] > 0) ? T + g.o_upto[q] : from;
+    const int n_new = (int)std::max<long long>(0, upto - from);
+    if (a.ce_from) a.ce_from[Q] = from;
+    if (a.ce_n) a.ce_n[Q] = std::min(n_new, ce_cap);
+    if (n_new > ce_cap && (a.ce || a.ce_pw)) rc = LCS_ERR_OVERFLOW;
+    for (int r = 0; r < std::min(n_new, ce_cap); ++r) {
+      const size_t src = q * L + (size_t)(from - T) + r;
+      if (a.ce) std::memcpy(a.ce + (Q * ce_cap + r) * 144, &g.o_ce[src * 144], sizeof(double) * 144);
+      if (a.ce_pw) std::memcpy(a.ce_pw + (Q * ce_cap + r) * 4, &g.o_pw[src * 4], sizeof(double) * 4);
+    }
+    if (upto > sc.ce_upto[p]) sc.ce_upto[p] = upto;
+  }
+  // MIB attempts: frame offset o of the block is offset T / F + o of the stream; an offset stays pending until it has been tried
+  int em = 0;
+  if (a.mib_from) a.mib_from[i] = sc.mib_next;
+  for (int o = 0; o < n_off; ++o) {
+    const long long og = T / F + o;
+    if (og < sc.mib_next) continue;
+    if (og > sc.mib_next || g.o_ok[(size_t)k * offs + o] == -1) break;
+    if (em < max_off) {
+      if (a.mib_ok) a.mib_ok[(size_t)i * max_off + em] = g.o_ok[(size_t)k * offs + o];
+      if (a.mib_bits) a.mib_bits[(size_t)i * max_off + em] = g.o_bits[(size_t)k * offs + o];
+    } else rc = LCS_ERR_OVERFLOW;
+    ++em;
+    sc.mib_next = og + 1;
+  }
+  if (a.n_mib) a.n_mib[i] = std::min(em, max_off);
+  // the metadata of the carried symbols
+  sc.n_seen = g.s.n_after;
+  sc.fo.assign(g.fo.begin() + (size_t)k * L + keep_from, g.fo.begin() + (size_t)k * L + keep_from + n_keep);
+  sc.ft.assign(g.ft.begin() + (size_t)k * L + keep_from, g.ft.begin() + (size_t)k * L + keep_from + n_keep);
+  sc.late.assign(g.late.begin() + (size_t)k * L + keep_from, g.late.begin() + (size_t)k * L + keep_from + n_keep);
+  if (g.s.T_next > T) sc.bpo_before_tail = g.bpo_at[k];
+  sc.tail_start = g.s.T_next;
+  return rc;
+}
+}  // namespace
 
 extern "C" int lcs_track_stream_block(lcs_ctx *c, lcs_track_cell *cells, int n_cells, int n_sym, const void *td,
                                       const double *freq_off, const double *frame_timing, const double *late, double fc_requested,
@@ -964,176 +1096,27 @@ extern "C" int lcs_track_stream_block(lcs_ctx *c, lcs_track_cell *cells, int n_c
     c->err = "bad argument";
     return LCS_ERR_BAD_ARG;
   }
-  TrkStream *st = &c->trk_stream;
-  if (st->cells.empty()) {
-    st->cells.resize(n_cells);
-    for (int i = 0; i < n_cells; ++i) {
-      TrkStreamCell &sc = st->cells[i];
-      sc.cp_type = cells[i].cp_type; sc.n_id_1 = cells[i].n_id_1; sc.n_id_2 = cells[i].n_id_2; sc.n_ports = cells[i].n_ports;
-      sc.bpo_before_tail = cells[i].bulk_phase_offset;
-    }
-  }
-  if ((int)st->cells.size() != n_cells) { c->err = "the stream was started with a different number of cells: lcs_track_stream_reset first"; return LCS_ERR_BAD_ARG; }
-  for (int i = 0; i < n_cells; ++i) {
-    const TrkStreamCell &sc = st->cells[i];
-    if (sc.cp_type != cells[i].cp_type || sc.n_id_1 != cells[i].n_id_1 || sc.n_id_2 != cells[i].n_id_2 || sc.n_ports != cells[i].n_ports) {
-      c->err = "a tracked cell changed identity inside a stream: lcs_track_stream_reset first";
-      return LCS_ERR_BAD_ARG;
-    }
-  }
-  const double *tdv = static_cast<const double *>(td);
-  int rc_all = LCS_OK;
+  const TrkStreamCall a = {cells, n_cells, n_sym, static_cast<const double *>(td), freq_off, frame_timing, late, SlotParams{fc_requested, fc_programmed, fs_programmed},
+                           syms, ce, ce_pw, ce_cap, ce_from, ce_n, meas, ac_fd, ac_td, max_rs, n_meas, mib_ok, mib_bits, max_off, mib_from, n_mib};
+  int rc, rc_all = LCS_OK;
+  if ((rc = trk_stream_start(c, cells, n_cells))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   // The stream's state is committed only after EVERY group of cells went through (round-3 advisory: a failure in the second
-  // group used to leave the first one advanced): the new per-cell records and device tails are built aside.
+  // group used to leave the first one advanced): the new per-cell records are built aside and the new tails sit in the spare
+  // buffers until then, so a failure has nothing to undo.
+  TrkStream *st = &c->trk.stream;
   std::vector<TrkStreamCell> next = st->cells;
   bool group_done[3] = {false, false, false};
-  auto fail = [&](int rc) { return rc; };              // nothing to undo: the new tails sit in the spare buffers until the commit
-  // cells of one CP type carry the same number of frames: one extended block per CP type
   for (int cp = LCS_CP_NORMAL; cp <= LCS_CP_EXTENDED; ++cp) {
-    std::vector<int> idx;
-    for (int i = 0; i < n_cells; ++i) if (cells[i].cp_type == cp) idx.push_back(i);
-    if (idx.empty()) continue;
-    const int G = (int)idx.size(), F = (cp == LCS_CP_NORMAL) ? 140 : 120;
-    const int n_tail = (int)(st->cells[idx[0]].n_seen - st->cells[idx[0]].tail_start);
-    const int L = n_tail + n_sym;
-    const long long T = st->cells[idx[0]].tail_start;
-    for (int g = 0; g < G; ++g)
-      if (st->cells[idx[g]].n_seen - st->cells[idx[g]].tail_start != n_tail || st->cells[idx[g]].tail_start != T) { c->err = "streams out of step"; return fail(LCS_ERR_BAD_ARG); }
-    std::vector<lcs_track_cell> gc(G);
-    std::vector<double> x_fo((size_t)G * L), x_ft((size_t)G * L), x_late((size_t)G * L);
-    std::vector<int> mib_first(G);
-    int rc = trk_ensure_ws(c, G, L);
-    if (rc != LCS_OK) return fail(rc);
-    // the carried rows go back to the head of every cell's rows, the new samples behind them
-    if (n_tail > 0)
-      HIPCHK(c, hipMemcpy2DAsync(c->trk_syms, sizeof(double2) * 72 * (size_t)L, st->d_tail[cp], sizeof(double2) * 72 * (size_t)n_tail,
-                                 sizeof(double2) * 72 * (size_t)n_tail, G, hipMemcpyDeviceToDevice, c->stream));
-    // the new samples: the group's cells are consecutive in td when the stream has one CP type (the usual case) -- then ONE strided
-    // copy places them all behind their carried rows (64 cells: 64 copies of 2 MB each were 0.3-0.5 ms of a call's host and
-    // copy-engine time); cells of a mixed stream go one by one
-    bool one_copy = true;
-    for (int g = 1; g < G; ++g) one_copy = one_copy && idx[g] == idx[0] + g;
-    if (one_copy)
-      HIPCHK(c, hipMemcpy2DAsync(c->trk_td + (size_t)n_tail * 128, sizeof(double2) * 128 * (size_t)L, tdv + (size_t)idx[0] * n_sym * 256,
-                                 sizeof(double2) * 128 * (size_t)n_sym, sizeof(double2) * 128 * (size_t)n_sym, G, hipMemcpyDefault, c->stream));
-    for (int g = 0; g < G; ++g) {
-      const TrkStreamCell &sc = st->cells[idx[g]];
-      gc[g] = cells[idx[g]];
-      gc[g].bulk_phase_offset = sc.bpo_before_tail;
-      // (hipMemcpyDefault: td may be pageable host memory, page-locked host memory -- DMA'd in place -- or device memory)
-      if (!one_copy)
-        HIPCHK(c, hipMemcpyAsync(c->trk_td + ((size_t)g * L + n_tail) * 128, tdv + (size_t)idx[g] * n_sym * 256, sizeof(double2) * 128 * (size_t)n_sym,
-                                 hipMemcpyDefault, c->stream));
-      auto join = [&](const std::vector<double> &tail, const double *fresh, std::vector<double> &out) {
-        std::copy(tail.begin(), tail.end(), out.begin() + (size_t)g * L);
-        std::copy(fresh + (size_t)idx[g] * n_sym, fresh + (size_t)(idx[g] + 1) * n_sym, out.begin() + (size_t)g * L + n_tail);
-      };
-      join(sc.fo, freq_off, x_fo); join(sc.ft, frame_timing, x_ft); join(sc.late, late, x_late);
-      mib_first[g] = (int)std::max<long long>(0, sc.mib_next - T / F);
-    }
-    const int rs_cap = L / 3 + 4, n_off = std::max(0, L / 120 - 3);
-    std::vector<double> o_syms(syms ? (size_t)G * L * 144 : 0), o_ce(ce ? (size_t)G * 4 * L * 144 : 0), o_pw((ce_pw || ce) ? (size_t)G * 4 * L * 4 : 0);
-    std::vector<double> o_meas((size_t)G * 4 * rs_cap * LCS_TRK_MEAS);
-    std::vector<int32_t> o_upto((size_t)G * 4), o_nmeas((size_t)G * 4), o_ok((size_t)G * std::max(1, n_off));
-    std::vector<uint64_t> o_bits((size_t)G * std::max(1, n_off));
-    const TrkCarried carried = {n_tail, mib_first.data()};
-    rc = trk_block(c, gc.data(), G, L, c->trk_td, 2, x_fo.data(), x_ft.data(), x_late.data(), fc_requested, fc_programmed, fs_programmed,
-                   syms ? o_syms.data() : nullptr, ce ? o_ce.data() : nullptr, (ce || ce_pw) ? o_pw.data() : nullptr, o_upto.data(),
-                   o_meas.data(), rs_cap, o_nmeas.data(), o_ok.data(), o_bits.data(), std::max(1, n_off), nullptr, &carried);
-    if (rc != LCS_OK) return fail(rc);
-    std::vector<double> o_fd, o_tdc;
-    if (ac_fd || ac_td) {
-      if (ac_fd) o_fd.resize((size_t)G * 4 * rs_cap * 24);
-      if (ac_td) o_tdc.resize((size_t)G * 4 * rs_cap * 144);
-      rc = lcs_track_stats(c, G, L, ac_fd ? o_fd.data() : nullptr, ac_td ? o_tdc.data() : nullptr, rs_cap, nullptr, nullptr, 0, nullptr);
-      if (rc != LCS_OK && rc != LCS_ERR_OVERFLOW) return fail(rc);      // no PSS/SSS rows were asked for: their overflow is of no concern
-    }
-    // the next carried tail: whole frames from T_next on -- its frequency-domain rows into a fresh device buffer, the bulk
-    // phase before its first symbol (= the value used at the symbol before it) in ONE strided copy
-    const long long n_after = st->cells[idx[0]].n_seen + n_sym;
-    const long long T_next = std::max<long long>(0, (n_after - 3 * F) / F * F);
-    const size_t keep_from = (size_t)(T_next - T), n_keep = (size_t)(n_after - T_next);
-    std::vector<double> bpo_at(G, 0.0);
-    {
-      const size_t need = (size_t)72 * n_keep * G;
-      // head room: the tail's length varies by up to a frame from call to call
-      if (need > st->d_spare[cp].capacity() && (rc = st->d_spare[cp].alloc(c, need + need / 4))) return fail(rc);
-      const TrkLayout Lay(c, G, L);
-      hipError_t e2 = hipMemcpy2DAsync(st->d_spare[cp], sizeof(double2) * 72 * n_keep, c->trk_syms + keep_from * 72, sizeof(double2) * 72 * (size_t)L,
-                                       sizeof(double2) * 72 * n_keep, G, hipMemcpyDeviceToDevice, c->stream);
-      if (e2 == hipSuccess && T_next > T)
-        e2 = hipMemcpy2DAsync(bpo_at.data(), sizeof(double), Lay.d_bpo + (size_t)(T_next - T - 1), sizeof(double) * (size_t)L, sizeof(double), G,
-                              hipMemcpyDeviceToHost, c->stream);
-      if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
-      if (e2 != hipSuccess) { c->err = std::string("carrying the stream's tail: ") + hipGetErrorString(e2); return fail(LCS_ERR_HIP); }
-    }
+    TrkGroup g;                                         // one extended block per CP type: its cells carry the same number of frames
+    for (int i = 0; i < n_cells; ++i) if (cells[i].cp_type == cp) g.idx.push_back(i);
+    if (g.idx.empty()) continue;
+    if ((rc = trk_stream_assemble(c, a, cp, g)) || (rc = trk_stream_run(c, a, g)) || (rc = trk_stream_carry(c, g))) return rc;
     group_done[cp] = true;
-    for (int g = 0; g < G; ++g) {
-      const int i = idx[g];
-      TrkStreamCell &sc = next[i];
-      cells[i].bulk_phase_offset = gc[g].bulk_phase_offset;
-      if (syms) std::memcpy(syms + (size_t)i * n_sym * 144, &o_syms[((size_t)g * L + n_tail) * 144], sizeof(double) * n_sym * 144);
-      for (int p = 0; p < 4; ++p) {
-        const size_t q = (size_t)g * 4 + p, Q = (size_t)i * 4 + p;
-        // filtered reference symbols: row r of the block is raw row r + 1 of the block = raw row (rows before T) + r + 1 of the stream
-        const long long rows_before = (T / F) * (p < 2 ? 40 : 20);
-        int emitted = 0;
-        for (int r = 0; r < o_nmeas[q]; ++r) {
-          const long long raw = rows_before + r + 1;
-          if (raw < sc.next_raw[p]) continue;
-          if (emitted < max_rs) {
-            if (meas) {
-              double *m = meas + (Q * max_rs + emitted) * LCS_TRK_MEAS;
-              std::memcpy(m, &o_meas[(q * rs_cap + r) * LCS_TRK_MEAS], sizeof(double) * LCS_TRK_MEAS);
-              m[0] += (double)T;                               // symbol index in the stream
-            }
-            if (ac_fd) std::memcpy(ac_fd + (Q * max_rs + emitted) * 24, &o_fd[(q * rs_cap + r) * 24], sizeof(double) * 24);
-            if (ac_td) std::memcpy(ac_td + (Q * max_rs + emitted) * 144, &o_tdc[(q * rs_cap + r) * 144], sizeof(double) * 144);
-          } else rc_all = LCS_ERR_OVERFLOW;
-          ++emitted;
-          sc.next_raw[p] = raw + 1;
-        }
-        if (n_meas) n_meas[Q] = std::min(emitted, max_rs);
-        // channel estimates: symbols [ce_upto, T + upto) are new
-        const long long upto = (o_upto[q] > 0) ? T + o_upto[q] : sc.ce_upto[p];
-        const long long from = sc.ce_upto[p];
-        const int n_new = (int)std::max<long long>(0, upto - from);
-        if (ce_from) ce_from[Q] = from;
-        if (ce_n) ce_n[Q] = std::min(n_new, ce_cap);
-        if (n_new > ce_cap && (ce || ce_pw)) rc_all = LCS_ERR_OVERFLOW;
-        for (int r = 0; r < std::min(n_new, ce_cap); ++r) {
-          const size_t src = q * L + (size_t)(from - T) + r;
-          if (ce) std::memcpy(ce + (Q * ce_cap + r) * 144, &o_ce[src * 144], sizeof(double) * 144);
-          if (ce_pw) std::memcpy(ce_pw + (Q * ce_cap + r) * 4, &o_pw[src * 4], sizeof(double) * 4);
-        }
-        if (upto > sc.ce_upto[p]) sc.ce_upto[p] = upto;
-      }
-      // MIB attempts: frame offset o of the block is offset T / F + o of the stream; an offset stays pending until it has been tried
-      int em = 0;
-      if (mib_from) mib_from[i] = sc.mib_next;
-      for (int o = 0; o < n_off; ++o) {
-        const long long og = T / F + o;
-        if (og < sc.mib_next) continue;
-        if (og > sc.mib_next || o_ok[(size_t)g * std::max(1, n_off) + o] == -1) break;
-        if (em < max_off) {
-          if (mib_ok) mib_ok[(size_t)i * max_off + em] = o_ok[(size_t)g * std::max(1, n_off) + o];
-          if (mib_bits) mib_bits[(size_t)i * max_off + em] = o_bits[(size_t)g * std::max(1, n_off) + o];
-        } else rc_all = LCS_ERR_OVERFLOW;
-        ++em;
-        sc.mib_next = og + 1;
-      }
-      if (n_mib) n_mib[i] = std::min(em, max_off);
-      // the metadata of the carried symbols
-      sc.n_seen = n_after;
-      sc.fo.assign(x_fo.begin() + (size_t)g * L + keep_from, x_fo.begin() + (size_t)g * L + keep_from + n_keep);
-      sc.ft.assign(x_ft.begin() + (size_t)g * L + keep_from, x_ft.begin() + (size_t)g * L + keep_from + n_keep);
-      sc.late.assign(x_late.begin() + (size_t)g * L + keep_from, x_late.begin() + (size_t)g * L + keep_from + n_keep);
-      if (T_next > T) sc.bpo_before_tail = bpo_at[g];
-      sc.tail_start = T_next;
-    }
+    for (int k = 0; k < (int)g.idx.size(); ++k)
+      if (trk_stream_emit(a, g, k, next[g.idx[k]])) rc_all = LCS_ERR_OVERFLOW;
   }
-  // commit
+  // 6. commit
   st->cells.swap(next);
   for (int cp = LCS_CP_NORMAL; cp <= LCS_CP_EXTENDED; ++cp)
     if (group_done[cp]) std::swap(st->d_tail[cp], st->d_spare[cp]);

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from conftest import iq_u8_to_capbuf, load_pkg
+from conftest import golden, iq_u8_to_capbuf, load_pkg
 
 pytestmark = pytest.mark.gpu
 FS, FC = 1.92e6, 739e6
@@ -164,3 +164,117 @@ def test_track_block_of_any_length_with_both_cp_types_in_one_call(pkg, blocks, n
             m = O.trk_mib(b["c"], r["syms"][ii], r["ce"][:b["c"].n_ports][:, ii], r["ce_pw"][:b["c"].n_ports][:, ii, 3])
             assert g["mib_ok"][i, o] == (1 if m[1] else 0) | (2 if m[2] else 0), (tag, o)
             assert [(int(g["mib_bits"][i, o]) >> k) & 1 for k in range(40)] == list(m[0]), (tag, o)
+
+
+def _same(a, b):
+    """bit for bit, NaNs included"""
+    return a.shape == b.shape and a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def _assert_block_and_stats_equal(got, want, gst, wst, cells, tag):
+    """every array lcs_track_block and lcs_track_stats define for the block, over the rows they define"""
+    for key in ("syms", "bpo", "n_meas", "ce_upto", "mib_ok", "n_hf"):
+        a, b = (gst, wst) if key == "n_hf" else (got, want)
+        assert _same(a[key], b[key]), (tag, key)
+    ok = want["mib_ok"] >= 0
+    assert _same(got["mib_bits"][ok], want["mib_bits"][ok]), tag
+    for i, c in enumerate(cells):
+        h = wst["n_hf"][i]
+        assert _same(gst["sync"][i, :h], wst["sync"][i, :h]) and _same(gst["sync_ce"][i, :h], wst["sync_ce"][i, :h]), (tag, i)
+        for p in range(4):
+            n, u = want["n_meas"][i, p], want["ce_upto"][i, p]
+            assert (n == 0 and u == 0) or p < c.n_ports
+            for key, rows in (("meas", n), ("ce", u), ("ce_pw", u)):
+                assert _same(got[key][i, p, :rows], want[key][i, p, :rows]), (tag, key, i, p)
+            for key in ("ac_fd", "ac_td"):
+                assert _same(gst[key][i, p, :n], wst[key][i, p, :n]), (tag, key, i, p)
+
+
+def test_one_context_serves_blocks_that_grow_shrink_and_grow_again(pkg, blocks):
+    """Every tracker test above opens a context per block shape.  Here ONE context runs lcs_track_block + lcs_track_stats on
+    cells x symbols (2, 500), (1, 7), (2, 839), (1, 141), (3, 280) in that order -- its workspace grows, serves smaller blocks
+    placed by their own shape, and grows again; normal- and extended-CP scenes mixed -- and every array of every call equals, bit
+    for bit, the same call on a fresh context.  Likewise lcs_track_cut on (2, 300), (1, 40), (3, 300), the middle call with a cell
+    whose sample rate sends it through the walk (the per-cell flags behind the hits are set and cleared): what it returns -- symbols,
+    `late`, counts, next positions -- is what a fresh context returns."""
+    import torch
+    nominal = [b for b in blocks if b["fcp"] == FC]
+    n0, n1 = [b for b in nominal if b["per_frame"] == 140]
+    e0, e1 = [b for b in nominal if b["per_frame"] == 120]
+    plan = [((n1, e0), 500), ((e0,), 7), ((n0, e1), 839), ((n1,), 141), ((n0, e0, n1), 280)]
+
+    def run(S, grp, n_sym):
+        args = ([b["c"] for b in grp], np.stack([b["td"][:n_sym] for b in grp]), np.stack([b["fov"][:n_sym] for b in grp]),
+                np.stack([b["ftv"][:n_sym] for b in grp]), np.stack([b["late"][:n_sym] for b in grp]), FC, FC, FS)
+        return S.track_block(*args), S.track_stats(len(grp), n_sym)
+
+    with pkg.Searcher(0) as S:
+        for grp, n_sym in plan:
+            got, gst = run(S, grp, n_sym)
+            with pkg.Searcher(0) as fresh:
+                want, wst = run(fresh, grp, n_sym)
+            _assert_block_and_stats_equal(got, want, gst, wst, [b["c"] for b in grp], (len(grp), n_sym))
+
+    cap = iq_u8_to_capbuf(golden("capbuf_0000")["iq_u8"])[:60000]
+    d = torch.from_numpy(cap).cuda()
+    cps, fts, fos = [1, 2, 1], [100.25, 9000.5, 19100.0], [1e3, -2e3, 0.0]
+
+    def cut(S, n_cells, n_sym, fsp):
+        td = torch.full((n_cells, n_sym, 128), float("nan"), dtype=torch.complex128, device="cuda")
+        late, n_cut, pos_next = S.track_cut(d.data_ptr(), pkg.FMT_C128, cap.size, cps[:n_cells], fts[:n_cells], fos[:n_cells], FC, FC, fsp, n_sym, td.data_ptr(),
+                                            want_state=True)
+        return td.cpu().numpy(), late, n_cut, pos_next
+
+    with pkg.Searcher(0) as S:
+        for n_cells, n_sym, fsp in ((2, 300, FS), (1, 40, FS * 0.93), (3, 300, FS)):
+            got = cut(S, n_cells, n_sym, fsp)
+            with pkg.Searcher(0) as fresh:
+                want = cut(fresh, n_cells, n_sym, fsp)
+            assert all(_same(a, b) for a, b in zip(got, want)), (n_cells, n_sym)
+            assert want[2].min() >= 3 and not np.isnan(want[0].real).any()
+
+
+def test_track_stream_of_mixed_cp_types_equals_one_block(pkg, blocks):
+    """lcs_track_stream_block on three cells ordered normal, extended, normal CP: the normal-CP group's cells are not consecutive in
+    the caller's arrays, so their samples go up cell by cell, beside a group of one.  839 symbols delivered from host memory in the
+    cuts (300, 301, 238) give, row for row and bit for bit, what one lcs_track_block call over the 839 symbols gives (compared as
+    tests/test_tracker.py::test_gpu_track_stream_blocks_equal_one_block compares)."""
+    nominal = [b for b in blocks if b["fcp"] == FC]
+    n0, n1 = [b for b in nominal if b["per_frame"] == 140]
+    e0 = [b for b in nominal if b["per_frame"] == 120][0]
+    grp, n_all, cuts = (n0, e0, n1), 839, (300, 301, 238)
+    recs = [b["c"] for b in grp]
+    td, fov, ftv, late = (np.stack([b[k][:n_all] for b in grp]) for k in ("td", "fov", "ftv", "late"))
+    with pkg.Searcher(0) as S:
+        one = S.track_block(recs, td, fov, ftv, late, FC, FC, FS)
+        st = S.track_stats(3, n_all)
+        parts, a = [], 0
+        for n in cuts:
+            parts.append(S.track_stream_block(recs, td[:, a:a + n], fov[:, a:a + n], ftv[:, a:a + n], late[:, a:a + n], FC, FC, FS, want_stats=True))
+            a += n
+    assert a == n_all and np.array_equal(np.concatenate([p["syms"] for p in parts], axis=1), one["syms"])
+    assert np.array_equal(parts[-1]["bpo"], one["bpo"])
+    for i, c in enumerate(recs):
+        for p in range(4):
+            rows = np.concatenate([q["meas"][i, p, :q["n_meas"][i, p]] for q in parts])
+            n = one["n_meas"][i, p]
+            assert rows.shape[0] == n and np.array_equal(rows, one["meas"][i, p, :n]), (i, p)
+            assert (n > 0) == (p < c.n_ports)
+            if n:
+                fd = np.concatenate([q["ac_fd"][i, p, :q["n_meas"][i, p]] for q in parts])
+                tdc = np.concatenate([q["ac_td"][i, p, :q["n_meas"][i, p]] for q in parts])
+                assert np.array_equal(fd, st["ac_fd"][i, p, :n])
+                assert np.array_equal(tdc[71:], st["ac_td"][i, p, 71:n]) and np.isnan(tdc[:71].real).all()
+            # channel estimates: every symbol below ce_upto exactly once, in order
+            pos = 0
+            for q in parts:
+                assert q["ce_from"][i, p] == pos
+                k = q["ce_n"][i, p]
+                assert np.array_equal(q["ce"][i, p, :k], one["ce"][i, p, pos:pos + k]) and np.array_equal(q["ce_pw"][i, p, :k], one["ce_pw"][i, p, pos:pos + k])
+                pos += k
+            assert pos == one["ce_upto"][i, p]
+        ok = np.concatenate([q["mib_ok"][i, :q["n_mib"][i]] for q in parts])
+        bits = np.concatenate([q["mib_bits"][i, :q["n_mib"][i]] for q in parts])
+        tried = one["mib_ok"][i] != -1
+        assert tried.any() and np.array_equal(ok, one["mib_ok"][i][tried]) and np.array_equal(bits, one["mib_bits"][i][tried])
+        assert [q["mib_from"][i] for q in parts] == list(np.cumsum([0] + [q["n_mib"][i] for q in parts[:-1]]))
