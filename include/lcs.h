@@ -298,6 +298,40 @@ typedef struct lcs_meas_wide_info {
   double rssi_rb[LCS_MEAS_WIDE_MAX_RB];
 } lcs_meas_wide_info;     /* 2528 bytes */
 
+/* The PCFICH of a wide cell: the control format indicator of every downlink subframe of a full-bandwidth grid (lcs_pcfich_wide,
+ * lcs_pcfich below; a stage of its own beside the chain).  THE RULE (lte-cell-scanner_amd/csrc/pcfich.h, host and device), on a grid
+ * tfg[n_ofdm][12 n_rb] whose row 0 is symbol 0 of slot 0 of a frame (row r: symbol r mod n_symb of slot (r / n_symb) mod 20), for
+ * n_id_cell, the CP type, n_ports in {1, 2, 4} (anything else counts as 1), n_rb in {6, 15, 25, 50, 75, 100} and a 10-bit dl_mask:
+ *   subframes   grid subframe g = 0, 1, .. starts at row 2 g n_symb and is subframe g mod 10 of its frame; it is decoded iff that bit
+ *               of dl_mask is set, the row lies inside n_ofdm and, with 4 ports, the row after it does too
+ *   elements    36.211 6.7.4: kbar = 6 (n_id_cell mod 2 n_rb); quadruplet i < 4 sits in the resource-element group of symbol 0 that
+ *               starts at column (kbar + 6 floor(i n_rb / 2)) mod 12 n_rb and takes, in increasing order, the four of its six
+ *               columns that are not = n_id_cell (mod 3): both reference positions stay free whatever the port count
+ *   channel     per port p, h_p[m] = tfg[row][shift_p + 6 m] conj(rs[m]) on the port's reference row (symbol 0 for ports 0 and 1,
+ *               symbol 1 of the same slot for ports 2 and 3; shift and rs as for lcs_meas_wide_info), interpolated linearly between
+ *               the two reference elements that bracket the column and, outside the first and the last, extrapolated on the line
+ *               through the nearest two; no smoothing, nothing across time
+ *   combining   1 port: s = conj(h) y.  2 ports, per pair (y0 at k0, y1 at k1) of a quadruplet: s0 = conj(h0(k0)) y0 + h1(k1) conj(y1),
+ *               s1 = conj(h0(k1)) y1 - h1(k0) conj(y0).  4 ports: the same with ports (0, 2) for a quadruplet's first pair and (1, 3)
+ *               for its second
+ *   soft bits   b[2 j] = Re s_j, b[2 j + 1] = Im s_j, 32 of them, times 1 - 2 c(i) of the Gold sequence with
+ *               c_init = (sf + 1) (2 n_id_cell + 1) 2^9 + n_id_cell, sf = g mod 10
+ *   decision    corr[c] = sum_i b_i (1 - 2 w_c[i]) / sum_i |b_i| over the codewords of 36.212 table 5.3.4-1 (w_c[i] = 0 iff i mod 3
+ *               = c, c = cfi - 1); cfi = 1 + argmax (the lowest on a tie), margin = best - second, n_ctrl_sym = cfi + (n_rb <= 10).
+ *               A subframe whose sum of |b_i| is zero or not finite is not decoded.
+ * Per subframe g < n_sf = ceil(n_ofdm / (2 n_symb)): cfi[g] (0: not decoded, its corr and margin are zero), corr[g], margin[g]; the
+ * entries beyond n_sf are zero.  n_decoded and n_cfi count the decoded subframes, mean_n_ctrl_sym and min_margin are taken over
+ * them in subframe order (zero without one).  It does not equalise across time and reads neither PHICH nor PDCCH; the CFI of a
+ * TDD special subframe (one or two symbols at most) is the caller's to mask out. */
+#define LCS_PCFICH_MAX_SF ((LCS_TFG_MAX_OFDM + 11) / 12)
+typedef struct lcs_pcfich_info {
+  int32_t n_sf, n_decoded, n_cfi[3], dl_mask, n_rb, n_ports;   /* n_ports: 1, 2 or 4 as the rule took it */
+  double mean_n_ctrl_sym, min_margin;
+  int32_t cfi[LCS_PCFICH_MAX_SF];
+  double corr[LCS_PCFICH_MAX_SF][3];
+  double margin[LCS_PCFICH_MAX_SF];
+} lcs_pcfich_info;        /* 2640 bytes */
+
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
 /* Replaces xcorr_pss -- include/searcher.h:22-41, src/searcher.cpp:389-419
@@ -399,6 +433,18 @@ int lcs_extract_tfg_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbu
 int lcs_cell_meas_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
                        double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
                        int dl_mask, lcs_meas_wide_info *out);
+
+/* The PCFICH (the rule: lcs_pcfich_info above).  lcs_pcfich_wide takes lcs_cell_meas_wide's arguments with its conventions and its
+ * refusals, and transforms only the rows it reads: symbol 0 of the first slot of every subframe of the mask, and symbol 1 with 4
+ * ports.  lcs_pcfich runs the same stage on a grid from the host, [n_ofdm][12 n_rb] (re, im) pairs, 2 n_symb <= n_ofdm <=
+ * 122 n_symb.  Both also refuse an n_rb that is not 6, 15, 25, 50, 75 or 100 and one that contradicts a known cell->n_rb_dl; n_ofdm
+ * holds at least one whole subframe.  Like the measurement they work in any mode and with a stream open and leave the modes and
+ * the last fused call's tables alone. */
+int lcs_pcfich_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                    double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                    int dl_mask, lcs_pcfich_info *out);
+int lcs_pcfich(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
+               int dl_mask, lcs_pcfich_info *out);
 
 /* ---- fused chain ------------------------------------------------------------------- */
 

@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo,FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -488,6 +488,26 @@ class Searcher:
         out = capi.CellMeasWide()
         self._chk(self._lib.lcs_cell_meas_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
                                                float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(out)), "lcs_cell_meas_wide")
+        return out
+
+    def pcfich_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                    n_cap=None):
+        """The control format indicator of every downlink subframe from the same samples (lcs_pcfich_wide: only symbol 0 of every
+        subframe of the mask is transformed, and symbol 1 for a 4-port cell); n_rb is the cell's bandwidth -> PcfichInfo"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        out = capi.PcfichInfo()
+        self._chk(self._lib.lcs_pcfich_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                            float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(out)), "lcs_pcfich_wide")
+        return out
+
+    def pcfich(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF):
+        """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
+        (extract_tfg_wide's) (lcs_pcfich) -> PcfichInfo"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        out = capi.PcfichInfo()
+        self._chk(self._lib.lcs_pcfich(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(out)), "lcs_pcfich")
         return out
 
     def set_float_batch_probe(self, on: bool):

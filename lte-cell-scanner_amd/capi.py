@@ -182,11 +182,62 @@ class CellMeasWide(C.Structure):
 
 assert C.sizeof(CellMeasWide) == 2528
 
+PCFICH_MAX_SF = (854 + 11) // 12      # LCS_PCFICH_MAX_SF
+
+
+class PcfichInfo(C.Structure):
+    """lcs_pcfich_info: the control format indicator of every subframe of a full-bandwidth grid (include/lcs.h: lcs_pcfich_wide,
+    lcs_pcfich).  cfi[g] in 1 .. 3, or 0 for a subframe that was not decoded; corr[g][c] the normalised correlation with codeword
+    c + 1, margin[g] = best - second.  cfi, corr, margin are numpy views of the record cut to its n_sf subframes; n_ctrl_sym the
+    control region's OFDM symbols per subframe (cfi + 1 up to 10 resource blocks), 0 where not decoded."""
+    _fields_ = [("n_sf", C.c_int32), ("n_decoded", C.c_int32), ("n_cfi", C.c_int32 * 3), ("dl_mask", C.c_int32), ("n_rb", C.c_int32), ("n_ports", C.c_int32),
+                ("mean_n_ctrl_sym", C.c_double), ("min_margin", C.c_double), ("_cfi", C.c_int32 * PCFICH_MAX_SF), ("_corr", (C.c_double * 3) * PCFICH_MAX_SF),
+                ("_margin", C.c_double * PCFICH_MAX_SF)]
+
+    def copy(self) -> "PcfichInfo":
+        o = PcfichInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(PcfichInfo))
+        return o
+
+    def _n(self) -> int:
+        return min(max(int(self.n_sf), 0), PCFICH_MAX_SF)
+
+    @property
+    def cfi(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._cfi)[:self._n()]
+
+    @property
+    def corr(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._corr)[:self._n()]
+
+    @property
+    def margin(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._margin)[:self._n()]
+
+    @property
+    def n_ctrl_sym(self):
+        import numpy as np
+        c = self.cfi
+        return np.where(c > 0, c + (1 if self.n_rb <= 10 else 0), 0)
+
+    def as_dict(self) -> dict:
+        return dict(n_sf=self.n_sf, n_decoded=self.n_decoded, n_cfi=list(self.n_cfi), dl_mask=self.dl_mask, n_rb=self.n_rb, n_ports=self.n_ports,
+                    mean_n_ctrl_sym=self.mean_n_ctrl_sym, min_margin=self.min_margin, cfi=self.cfi.tolist(), corr=self.corr.tolist(), margin=self.margin.tolist())
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"PcfichInfo(n_sf={self.n_sf}, n_decoded={self.n_decoded}, n_cfi={list(self.n_cfi)}, mean_n_ctrl_sym={self.mean_n_ctrl_sym:.3f}, min_margin={self.min_margin:.3f})"
+
+
+assert C.sizeof(PcfichInfo) == 2640
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -263,6 +314,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_extract_tfg_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, dp]
         L.lcs_cell_meas_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(CellMeasWide)]
+    if hasattr(L, "lcs_pcfich_wide"):      # (likewise)
+        L.lcs_pcfich_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(PcfichInfo)]
+        L.lcs_pcfich.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PcfichInfo)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

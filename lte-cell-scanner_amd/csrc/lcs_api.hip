@@ -13,6 +13,7 @@
 #include "tdd_config.h"
 #include "cell_meas.h"
 #include "cell_meas_wide.h"
+#include "pcfich.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
 
@@ -1102,6 +1103,78 @@ int lcs_cell_meas_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, u
   HIPCHK(c, hipMemcpyAsync(out, c->meas_wide.rec, sizeof(lcs_meas_wide_info), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
+}
+
+// ---- the PCFICH on that grid (pcfich.hip, pcfich.h): the same blocks and the same isolation
+namespace {
+// what both entry points refuse about n_rb beyond the measurement's range
+int pcfich_rb_refused(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb) {
+  if (!pcf_rb_ok(n_rb)) return wide_refused(c, who, "n_rb is not an LTE bandwidth (6, 15, 25, 50, 75 or 100)");
+  if (pcf_rb_ok(cell->n_rb_dl) && cell->n_rb_dl != n_rb) return wide_refused(c, who, "n_rb contradicts the cell's n_rb_dl");
+  return LCS_OK;
+}
+// rows[2 g], rows[2 g + 1] for every subframe of the grid: the rows themselves (list == nullptr: the whole grid is there), or their
+// places in *list, the rows a transform is asked for
+int pcfich_plan(const lcs_cell *cell, int n_ofdm, int dl_mask, int *rows, std::vector<int> *list) {
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, ports = pcf_ports(cell->n_ports), n_sf = pcf_n_sf(n_ofdm, n_symb);
+  for (int g = 0; g < n_sf; ++g) {
+    rows[2 * g] = rows[2 * g + 1] = -1;
+    if (!pcf_sf_used(g, n_ofdm, n_symb, ports, dl_mask)) continue;
+    for (int t = 0; t < (ports == 4 ? 2 : 1); ++t) {
+      const int r = 2 * g * n_symb + t;
+      if (list) { rows[2 * g + t] = (int)list->size(); list->push_back(r); }
+      else rows[2 * g + t] = r;
+    }
+  }
+  return n_sf;
+}
+int pcfich_finish(lcs_ctx *c, lcs_pcfich_info *out) {
+  HIPCHK(c, hipMemcpyAsync(out, c->meas_wide.pcf_rec, sizeof(lcs_pcfich_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_pcfich_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                    int n_fft, int n_rb, int n_ofdm, int dl_mask, lcs_pcfich_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pcfich_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  static_assert(122 * 7 <= LCS_TFG_MAX_OFDM && 61 <= PCF_MAX_SF, "the subframes of 122 slots fit the record");
+  int rows[2 * PCF_MAX_SF];
+  std::vector<int> list;
+  const int n_sf = pcfich_plan(cell, n_ofdm, dl_mask, rows, &list);
+  std::vector<double> ideal(list.size());
+  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
+  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_pcfich(c, *cell, rows, n_sf, n_rb, dl_mask))) return rc;
+  return pcfich_finish(c, out);
+}
+
+int lcs_pcfich(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, lcs_pcfich_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pcfich";
+  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  int rc;
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  int rows[2 * PCF_MAX_SF];
+  const int n_sf = pcfich_plan(cell, n_ofdm, dl_mask, rows, nullptr);
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
+  if ((rc = lcs_launch_pcfich(c, *cell, rows, n_sf, n_rb, dl_mask))) return rc;
+  return pcfich_finish(c, out);
 }
 
 // chan_est of decode_mib as a stage of its own (ref src/searcher.cpp:1369-1477, ce_interp_hex :1223-1362): the channel

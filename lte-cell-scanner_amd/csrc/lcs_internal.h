@@ -393,6 +393,13 @@ struct lcs_ctx : lcs_ctx_queues {
     DevBuf<uint32_t> pn_jump;       // [32]: Gold-sequence jump-ahead to c(2 (110 - n_rb)) of the call's n_rb
     uint32_t h_pn_jump[32] = {};    // ... and the host block it is uploaded from (it outlives the launcher's frame)
     DevBuf<lcs_meas_wide_info> rec; // [1]
+    // the PCFICH on the same grid (pcfich.hip: lcs_pcfich_wide, lcs_pcfich), allocated by the first call of that stage
+    DevBuf<int> pcf_rows;           // [LCS_PCFICH_MAX_SF][2]: the grid rows of every subframe's symbols 0 and 1, -1: not read
+    DevBuf<uint32_t> pcf_jump;      // [2][32]: jump-ahead to the call's reference sequence, and by 1600 clocks for the scrambling
+    DevBuf<lcs_pcfich_info> pcf_rec;   // [1]
+    int h_pcf_rows[2 * LCS_PCFICH_MAX_SF] = {};   // the host blocks those two are uploaded from
+    uint32_t h_pcf_jump[64] = {};
+    int pcf_jump_rb = 0;            // the n_rb pcf_jump holds the tables of, 0: none
   } meas_wide;
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
@@ -585,4 +592,10 @@ int lcs_launch_cell_meas(lcs_ctx *c, const Launch &L, const lcs_tdd_info *tdd /*
 int lcs_launch_tfg_wide(lcs_ctx *c, const float2 *d_cap, uint32_t n_cap, const double *h_ideal, int n_rows, double kk, int n_fft, int n_rb);
 // the measurement on the n_q reference rows that call left in c->meas_wide.grid -> c->meas_wide.rec
 int lcs_launch_cell_meas_wide(lcs_ctx *c, const lcs_cell &cell, int n_q, int n_fft, int n_rb, int dl_mask);
+// pcfich.hip
+// a host grid of n_elem (re, im) pairs -> c->meas_wide.grid
+int lcs_pcfich_stage_grid(lcs_ctx *c, const double *h_grid, size_t n_elem);
+// the PCFICH of the n_sf subframes whose rows (rows[2 g], rows[2 g + 1]: symbols 0 and 1, -1: not read) c->meas_wide.grid holds
+// -> c->meas_wide.pcf_rec
+int lcs_launch_pcfich(lcs_ctx *c, const lcs_cell &cell, const int *rows, int n_sf, int n_rb, int dl_mask);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

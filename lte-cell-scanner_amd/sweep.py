@@ -207,7 +207,7 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
-                     carriers, n_rb: int = None, dl_mask: int = None):
+                     carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -218,6 +218,9 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     (meas=True), else 0x3FF (FDD) / 0x021 (TDD, the searcher's duplex mode).
     Returns one list per carrier, entry k belonging to cell k: a capi.CellMeasWide, or None for a cell without a MIB; a dict cell
     also gets it as cell["meas_wide"].  The wide records come from float carriers and need no gain, whatever `out` the search used.
+    pcfich=True also reads the PCFICH (Searcher.pcfich_wide) of every such cell from the same re-channelized buffer, under the same
+    mask and over the same slots: entry k is then the pair (CellMeasWide, PcfichInfo), and a dict cell gets cell["pcfich"] as well.
+    The PCFICH spans the cell's own bandwidth: with an n_rb other than the cell's n_rb_dl its record is None.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -292,6 +295,13 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
             rec = searcher.cell_meas_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
             if d is not None:
                 d["meas_wide"] = rec
+            if pcfich:
+                pc = None
+                if rb == int(get("n_rb_dl")):
+                    pc = searcher.pcfich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
+                if d is not None:
+                    d["pcfich"] = pc
+                rec = (rec, pc)
             row.append(rec)
         out.append(row)
     return out

@@ -500,14 +500,55 @@ def _crs_wide(n_id_cell, slot, sym, cp_normal, n_rb):
     return ((1 - 2 * c[2 * m]) + 1j * (1 - 2 * c[2 * m + 1])) / np.sqrt(2.0)
 
 
+def _tx_diversity(s, n_ports):
+    """[n_ports][len(s)]: the symbols s on their resource elements per antenna port (36.211 6.3.4.1 / 6.3.4.3: one port as they
+    are; two ports SFBC on pairs of elements; four ports SFBC-FSTD, the pairs alternating between ports (0, 2) and (1, 3))"""
+    if n_ports == 1:
+        return np.asarray(s, np.complex128)[None, :]
+    s0, s1 = s[0::2], s[1::2]
+    a = np.empty((2, len(s)), np.complex128)
+    a[0, 0::2], a[0, 1::2] = s0, s1
+    a[1, 0::2], a[1, 1::2] = -np.conj(s1), np.conj(s0)
+    a /= np.sqrt(2.0)
+    if n_ports == 2:
+        return a
+    out = np.zeros((4, len(s)), np.complex128)
+    pair = (np.arange(len(s)) // 2) & 1
+    for q, (p0, p1) in enumerate(((0, 2), (1, 3))):
+        m = pair == q
+        out[p0, m] = a[0, m]
+        out[p1, m] = a[1, m]
+    return out
+
+
+def pcfich_columns(n_id_cell, n_rb):
+    """the 16 columns of symbol 0 that carry the PCFICH, in mapping order (36.211 6.7.4): quadruplet i in the resource-element group
+    at kbar + floor(i n_rb / 2) 6, kbar = 6 (n_id_cell mod 2 n_rb), on the four elements of the group that no port's CRS may take"""
+    cols = []
+    for i in range(4):
+        reg = (6 * (n_id_cell % (2 * n_rb)) + 6 * ((i * n_rb) // 2)) % (12 * n_rb)
+        cols += [reg + o for o in range(6) if (reg + o) % 3 != n_id_cell % 3]
+    return np.array(cols)
+
+
+def pcfich_symbols(n_id_cell, subframe, cfi):
+    """the 16 QPSK symbols of the PCFICH of a subframe: the CFI codeword of 36.212 table 5.3.4-1, scrambled (36.211 6.7.1)"""
+    word = np.array([(0, 1, 1), (1, 0, 1), (1, 1, 0)][int(cfi) - 1] * 11, np.uint8)[:32]
+    b = word ^ _pn((subframe + 1) * (2 * n_id_cell + 1) * 512 + n_id_cell, 32)
+    return ((1 - 2.0 * b[0::2]) + 1j * (1 - 2.0 * b[1::2])) / np.sqrt(2.0)
+
+
 def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
-                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0):
+                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None):
     """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,
     CP lengths R * {10, 9, 32}), n_frames * 19200 * R samples from the boundary of frame sfn0.  The 72 centre subcarriers carry what
     cell_waveform puts there -- PSS, SSS, PBCH (the MIB says n_rb_dl: n_rb where that is an LTE bandwidth, else 50), CRS and load --
     and the other 12 n_rb - 72 carry the CRS of the n_rb sequence and load in every symbol that is sent.  Unit power per resource
     element before port_gains / sqrt(n_ports), so a reference element of port p has power |port_gains[p]|^2 / n_ports.  per_port and
-    tdd as for cell_waveform.  A function of its own: its draws from rng are not cell_waveform's."""
+    tdd as for cell_waveform.  A function of its own: its draws from rng are not cell_waveform's.
+    cfi: None sends no PCFICH (its elements carry load like any other).  An int 1 .. 3, or a callable (frame, subframe) -> 1 .. 3 with
+    frame counting from 0 in this waveform, reserves the 16 PCFICH elements of symbol 0 of every subframe that is sent and puts the
+    scrambled codeword there through the PBCH's precoding."""
     rng = rng or np.random.default_rng(0)
     R, n_rb = int(R), int(n_rb)
     n_fft, nc, c0 = 128 * R, 12 * n_rb, 6 * n_rb - 36          # c0: the first of the 72 centre columns
@@ -533,6 +574,7 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
             raise ValueError("dwpts_symbols must hold the PSS (>= 3) and fit the subframe")
     centre = np.zeros(nc, bool)
     centre[c0:c0 + 72] = True
+    pcfich_cols = pcfich_columns(n_id_cell, n_rb) if cfi is not None else None
     pos = 0
     pbch = None
     for fr in range(n_frames):
@@ -584,23 +626,12 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
                     sc = c0 + np.array([k for k in range(72) if not (skip and k % 3 == v_shift % 3)])
                     s = quarter[pb_i:pb_i + len(sc)]
                     pb_i += len(sc)
-                    if n_ports == 1:
-                        grid[0, sc] = s
-                    else:
-                        s0, s1 = s[0::2], s[1::2]
-                        a = np.empty((2, len(sc)), np.complex128)
-                        a[0, 0::2], a[0, 1::2] = s0, s1
-                        a[1, 0::2], a[1, 1::2] = -np.conj(s1), np.conj(s0)
-                        a /= np.sqrt(2.0)
-                        if n_ports == 2:
-                            grid[0, sc], grid[1, sc] = a[0], a[1]
-                        else:   # SFBC-FSTD: pairs alternate between ports (0,2) and (1,3)
-                            pair = (np.arange(len(sc)) // 2) & 1
-                            for q, (p0, p1) in enumerate(((0, 2), (1, 3))):
-                                m = pair == q
-                                grid[p0, sc[m]] = a[0, m]
-                                grid[p1, sc[m]] = a[1, m]
+                    grid[:, sc] = _tx_diversity(s, n_ports)
                     reserved |= centre
+                if cfi is not None and sym == 0 and not (slot & 1):
+                    value = cfi(fr, slot >> 1) if callable(cfi) else cfi
+                    grid[:, pcfich_cols] = _tx_diversity(pcfich_symbols(n_id_cell, slot >> 1, value), n_ports)
+                    reserved[pcfich_cols] = True
                 free = np.flatnonzero(~reserved)
                 on = free[rng.random(free.size) < load]
                 d = ((1 - 2.0 * rng.integers(0, 2, on.size)) + 1j * (1 - 2.0 * rng.integers(0, 2, on.size))) / np.sqrt(2.0)
@@ -628,20 +659,21 @@ def make_signal_wide(rng, fc, cd, R, n_rb, n_cap):
     n_frames = int(np.ceil((n_cap / (R * k_factor) + t0) / 19200)) + 1
     w = cell_waveform_wide(n_frames, cd["n_id_1"], cd["n_id_2"], R, n_rb, cd.get("cp_normal", True), cd.get("n_ports", 2), cd.get("load", 0.5), rng,
                            cd.get("port_gains"), tdd=cd.get("tdd"), n_rb_dl=cd.get("n_rb_dl"), phich_duration_ext=cd.get("phich_duration_ext", 0),
-                           phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))))
+                           phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))), cfi=cd.get("cfi"))
     y = frac_resample(w, t0 * R + n / k_factor)
     y = y * np.exp(2j * np.pi * f_off * n / (FS * R * k_factor))
     g = 10 ** (cd.get("gain_db", 0.0) / 20)
     return g * y, dict(cd, t0=t0, n_id_cell=cd["n_id_2"] + 3 * cd["n_id_1"], k_factor=k_factor, R=R, n_rb=n_rb)
 
 
-def make_wideband_cell(seed, fc_centre, decim, wide_cells, placed=(), snr_db=10.0, fmt=capi.FMT_C64, n_in=None, rms=0.15):
+def make_wideband_cell(seed, fc_centre, decim, wide_cells, placed=(), snr_db=10.0, fmt=capi.FMT_C64, n_in=None, rms=0.15, cfi=None):
     """make_wideband with cells of cell_waveform_wide in it: one capture at decim x 1.92 Msps centred on fc_centre.
     wide_cells: list of (carrier_hz, R, n_rb, cell) -- the cell's signal at 1.92e6 * R (make_signal_wide; R divides decim) is band-
     limited-interpolated by decim / R and shifted by carrier_hz - fc_centre.  placed: narrow carriers as for make_wideband.  One AWGN
     at the wide rate, snr_db below the PSS/SSS sample power of a gain_db = 0 cell inside a 1.92 MHz channel; AGC to rms; fmt as
     make_wideband.  Returns (capture, truth, scale): truth is a list of (carrier_hz, [cell truth]) -- wide cells first --, scale the
-    factor the AGC applied (a reference element of port p then has power scale^2 |port_gains[p]|^2 / n_ports 10^(gain_db / 10))."""
+    factor the AGC applied (a reference element of port p then has power scale^2 |port_gains[p]|^2 / n_ports 10^(gain_db / 10)).
+    cfi: cell_waveform_wide's, for every wide cell whose dict names none of its own."""
     decim = int(decim)
     n_in = N_CAP * decim if n_in is None else int(n_in)
     n_nb = -(-n_in // decim)
@@ -669,6 +701,8 @@ def make_wideband_cell(seed, fc_centre, decim, wide_cells, placed=(), snr_db=10.
         R = int(R)
         if decim % R:
             raise ValueError("make_wideband_cell: R divides decim")
+        if cfi is not None and "cfi" not in cd:
+            cd = dict(cd, cfi=cfi)
         sig, tr = make_signal_wide(rng, float(carrier), cd, R, n_rb, n_nb * R)
         wide += place(sig, decim // R, carrier)
         truth.append((float(carrier), [tr]))
