@@ -398,6 +398,14 @@ int lcs_tfoec(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im,
 int lcs_decode_mib(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_re_im, int n_ofdm,
                    lcs_cell *cell_out);
 
+/* What lcs_decode_mib computes for ONE of its twelve candidates before it looks at the CRC, exported so that it can be tested
+ * directly: the grid is staged exactly as by lcs_decode_mib, the candidate (frame_timing_guess 0 .. 3, n_ports 1, 2 or 4) is forced.
+ * e_est: the descrambled LLRs (1920 with the normal CP, 1728 with the extended; room for 1920), d_est: the de-rate-matched values
+ * [3][40], bits40: the decoded word (bit t = c_est(t)), crc_ok: whether its CRC passes under the n_ports mask.  Refuses
+ * (LCS_ERR_BAD_ARG, an lcs_last_error text) what lcs_decode_mib refuses, and a candidate outside those values. */
+int lcs_pbch_soft(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_comp_re_im, int n_ofdm, int frame_timing_guess, int n_ports,
+                  double *e_est, double *d_est, uint64_t *bits40, int *crc_ok);
+
 /* chan_est (src/searcher.cpp:1369-1477 with ce_interp_hex :1223-1362), the first half of decode_mib, as a stage of its
  * own: channel estimate of antenna port `port` on the whole compensated grid and the port's noise power.  Internal to the
  * reference's searcher.cpp (not in searcher.h); exported so that it can be tested directly. */

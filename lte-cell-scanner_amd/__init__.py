@@ -188,6 +188,18 @@ class Searcher:
         self._chk(rc, "lcs_decode_mib")
         return out
 
+    # ---- one forced candidate of decode_mib's twelve, before the CRC decides (exported for direct testing) ------
+    def pbch_soft(self, cell, tfg, frame_timing_guess: int, n_ports: int):
+        """-> (e_est [1920 | 1728] descrambled LLRs, d_est [3][40] de-rate-matched, c_est [40] uint8 decoded bits, crc_ok)"""
+        tfg = np.ascontiguousarray(tfg, np.complex128)
+        e, d = np.zeros(1920), np.zeros((3, 40))
+        bits, ok = C.c_uint64(0), C.c_int(0)
+        rc = self._lib.lcs_pbch_soft(self._h, C.byref(cell), _dp(tfg), tfg.shape[0], int(frame_timing_guess), int(n_ports),
+                                     _dp(e), _dp(d), C.byref(bits), C.byref(ok))
+        self._chk(rc, "lcs_pbch_soft")
+        c_est = np.array([(bits.value >> t) & 1 for t in range(40)], np.uint8)
+        return e[:1920 if tfg.shape[0] == 854 else 1728].copy(), d, c_est, bool(ok.value)
+
     # ---- searcher.cpp:1369-1477 (internal to decode_mib; exported for direct testing) ------
     def chan_est(self, cell, tfg, port: int):
         tfg = np.ascontiguousarray(tfg, np.complex128)

@@ -239,7 +239,7 @@ EXPORTS = [
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
     "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
-    "lcs_decode_mib", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
+    "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
     "lcs_foe_partial", "lcs_foe_finish", "lcs_foe_contend", "lcs_foe_resolve", "lcs_track_block", "lcs_track_stats", "lcs_track_stream_block", "lcs_track_stream_reset", "lcs_track_cut", "lcs_stream_open", "lcs_stream_push", "lcs_stream_collect", "lcs_stream_close",
     "lcs_last_xcorr_ms", "lcs_last_xcorr_info", "lcs_last_frq_repairs", "lcs_last_frq_repair_stats", "lcs_frq_tie_eps", "lcs_last_batch_stats", "lcs_last_collect_host_us", "lcs_stream", "lcs_sync", "lcs_table_pss_td", "lcs_table_pss_fd", "lcs_table_sss_fd",
@@ -328,6 +328,8 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.lcs_extract_tfg.argtypes = [vp, cp, dp, C.c_uint32, C.c_double, C.c_double, C.c_double, dp, dp, C.POINTER(C.c_int)]
     L.lcs_tfoec.argtypes = [vp, cp, dp, dp, C.c_int, C.c_double, C.c_double, dp, dp, cp]
     L.lcs_decode_mib.argtypes = [vp, cp, dp, C.c_int, cp]
+    if hasattr(L, "lcs_pbch_soft"):      # (likewise)
+        L.lcs_pbch_soft.argtypes = [vp, cp, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.lcs_chan_est.argtypes = [vp, cp, dp, C.c_int, C.c_int, dp, dp]
     L.lcs_search_capbuf.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_double, C.c_double, C.c_double,
                                     cp, C.c_int, C.POINTER(C.c_int), cp, C.c_int, C.POINTER(C.c_int)]

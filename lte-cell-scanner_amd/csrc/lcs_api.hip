@@ -336,13 +336,8 @@ int lcs_create(int device, lcs_ctx **out) {
   std::vector<uint8_t> scr(504 * 1920);
   for (int id = 0; id < 504; ++id) lcs_tables::lte_pn((uint32_t)id, 1920, &scr[(size_t)id * 1920]);
   std::vector<int16_t> derm(2 * 120 * 16, (int16_t)-1);
-  for (int v = 0; v < 2; ++v) {                            // 0: normal CP (1920 bits), 1: extended CP (1728)
-    const int n_e = v ? 1728 : 1920;
-    std::vector<uint8_t> map(n_e);
-    lcs_tables::pbch_deratematch_map(n_e, map.data());
-    int fill[120] = {0};
-    for (int t = 0; t < n_e; ++t) derm[(v * 120 + map[t]) * 16 + fill[map[t]]++] = (int16_t)t;
-  }
+  for (int v = 0; v < 2; ++v)                              // 0: normal CP (1920 bits), 1: extended CP (1728)
+    if (!lcs_tables::pbch_derm_inv(v ? 1728 : 1920, &derm[(size_t)v * 120 * 16])) { lcs_destroy(c); return LCS_ERR_HIP; }
   uint32_t pn_jump[32];
   lcs_tables::pn_jump_table(1600 + 2 * (110 - 6), pn_jump);
   bool ok = c->d_pss_td.alloc(c, td.size() / 2) == LCS_OK &&
@@ -987,6 +982,37 @@ int lcs_decode_mib(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_of
   if ((rc = lcs_launch_mib(c, L, false))) return rc;
   HIPCHK(c, hipMemcpyAsync(cell_out, c->cells_out, sizeof(lcs_cell), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+// The soft values of one forced PBCH candidate (for tests): staged exactly as lcs_decode_mib, so the channel estimate is the
+// PBCH-rows-only form that decode_mib reads; k_pbch_soft leaves the values in the debug block.
+int lcs_pbch_soft(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int frame_timing_guess, int n_ports,
+                  double *e_est, double *d_est, uint64_t *bits40, int *crc_ok) {
+  if (!c || !cell || !tfg || !e_est || !d_est || !bits40 || !crc_ok) return LCS_ERR_BAD_ARG;
+  const int need = n_ofdm_for(cell);
+  if (need < 0 || n_ofdm != need || cell->n_id_1 < 0 || cell->n_id_2 < 0) {
+    c->err = "pbch_soft needs a detected cell and its full 854/732-symbol grid";
+    return LCS_ERR_BAD_ARG;
+  }
+  if (frame_timing_guess < 0 || frame_timing_guess > 3 || (n_ports != 1 && n_ports != 2 && n_ports != 4)) {
+    c->err = "pbch_soft needs a frame_timing_guess of 0 .. 3 and n_ports of 1, 2 or 4";
+    return LCS_ERR_BAD_ARG;
+  }
+  int rc;
+  Launch L;
+  if ((rc = stage_grid(c, cell, tfg, n_ofdm, &lcs_ctx::tfg_comp, &L))) return rc;
+  L.needed_rows_only = true;      // as lcs_decode_mib
+  if ((rc = lcs_launch_pbch_soft(c, L, frame_timing_guess, n_ports, c->d_dbg))) return rc;
+  std::vector<double> dbg(2048);
+  if ((rc = read_dbg_record(c, dbg.data(), sizeof(double) * dbg.size()))) return rc;
+  int at_d, at_bits, at_ok;
+  lcs_pbch_soft_layout(&at_d, &at_bits, &at_ok);
+  const int m_bit = need == 854 ? 1920 : 1728;
+  std::memcpy(e_est, &dbg[0], sizeof(double) * m_bit);
+  std::memcpy(d_est, &dbg[at_d], sizeof(double) * 120);
+  std::memcpy(bits40, &dbg[at_bits], sizeof(uint64_t));
+  *crc_ok = dbg[at_ok] != 0.0;
   return LCS_OK;
 }
 

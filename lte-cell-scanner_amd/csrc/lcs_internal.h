@@ -542,6 +542,7 @@ void lte_pn(uint32_t c_init, uint32_t len, uint8_t *out);
 void pn_jump_table(uint32_t steps, uint32_t out[32]);
 double chi2cdf_inv(double p, double k);
 void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.cpp:409-463 via :473-478
+bool pbch_derm_inv(int n_e, int16_t *out /*[120][16]*/);    // its inverse: per coded bit the positions carrying it (ascending, -1 padded)
 }  // namespace lcs_tables
 
 // ---- kernel launchers (one per .hip file) -------------------------------------------
@@ -582,6 +583,8 @@ int lcs_launch_tfg(lcs_ctx *c, const Launch &L, bool with_rs /* also build RS_DL
 int lcs_launch_tfoec(lcs_ctx *c, const Launch &L, bool apply_grid);
 int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused);   // chan_est + PBCH candidates + selection (+ record back into the peak table)
 int lcs_launch_chan_est(lcs_ctx *c, const Launch &L);
+int lcs_launch_pbch_soft(lcs_ctx *c, const Launch &L, int guess, int n_ports, double *out /*[2048]*/);   // chan_est + one forced PBCH candidate's soft values
+void lcs_pbch_soft_layout(int *d_est, int *bits, int *ok);                                              // where k_pbch_soft leaves them in `out`
 int lcs_launch_tdd_config(lcs_ctx *c, const Launch &L, lcs_tdd_info *out /*device*/, bool force /* the stage: out[item], whatever the record carries */);
 // cell_meas.hip
 int lcs_launch_cell_meas(lcs_ctx *c, const Launch &L, const lcs_tdd_info *tdd /*device: this launch's k_tdd_config table, or null*/, lcs_meas_info *out /*device*/,

@@ -175,4 +175,18 @@ void pbch_deratematch_map(int n_e, uint8_t *out) {
   }
 }
 
+// The map inverted, as the decoder reads it (lte_device.h pbch_decode_wave): for every coded bit the rate-matched positions that
+// carry it, ascending, padded with -1 to sixteen.  false where a bit would be carried more than sixteen times (n_e > 1920).
+bool pbch_derm_inv(int n_e, int16_t *out /*[120][16]*/) {
+  std::vector<uint8_t> map(n_e);
+  pbch_deratematch_map(n_e, map.data());
+  int fill[120] = {0};
+  for (int i = 0; i < 120 * 16; ++i) out[i] = (int16_t)-1;
+  for (int t = 0; t < n_e; ++t) {
+    if (fill[map[t]] >= 16) return false;
+    out[map[t] * 16 + fill[map[t]]++] = (int16_t)t;
+  }
+  return true;
+}
+
 }  // namespace lcs_tables

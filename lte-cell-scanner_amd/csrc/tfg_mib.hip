@@ -1009,6 +1009,32 @@ __global__ __launch_bounds__(TC_THREADS) void k_tdd_config(const lcs_cell *__res
   }
 }
 
+// The soft values of ONE forced candidate of the work list's first cell (lcs_pbch_soft: a stage for tests): one wave through the
+// same pbch_llr_wave and pbch_decode_wave as a wave of k_pbch, then out[0 .. m_bit) = the descrambled LLRs, out[1920 .. 2040) =
+// the de-rate-matched values [3][40], out[2040] = the 40 decoded bits (as an integer's bit pattern), out[2041] = the CRC flag.
+#define PBS_D_EST 1920
+#define PBS_BITS 2040
+#define PBS_OK 2041
+__global__ __launch_bounds__(PB_THREADS) void k_pbch_soft(const lcs_cell *__restrict__ cells, const double2 *__restrict__ tfg_comp, const double2 *__restrict__ ce,
+                                                          const double *__restrict__ scratch, const uint8_t *__restrict__ pbch_scr,
+                                                          const int16_t *__restrict__ derm_inv, int guess, int n_ports, double *__restrict__ out /*[2048]*/) {
+  __shared__ double e_est[1920];
+  __shared__ double d_est[3][40];
+  const int tid = threadIdx.x;
+  const lcs_cell c = cells[0];
+  const int m_bit = (c.cp_type == LCS_CP_NORMAL) ? 1920 : 1728;
+  pbch_llr_wave(c, scratch, tfg_comp, ce, pbch_scr + (size_t)cell_id(c) * 1920, guess, n_ports, tid, e_est);
+  int ok = 0;
+  unsigned long long bits40 = 0ull;
+  pbch_decode_wave(e_est, d_est, derm_inv, m_bit, n_ports, tid, ok, bits40);
+  for (int i = tid; i < m_bit; i += PB_THREADS) out[i] = e_est[i];
+  for (int i = tid; i < 120; i += PB_THREADS) out[PBS_D_EST + i] = d_est[i / 40][i % 40];
+  if (tid == 0) {
+    reinterpret_cast<unsigned long long *>(out)[PBS_BITS] = bits40;
+    out[PBS_OK] = (double)ok;
+  }
+}
+
 // ------------------------------------------------------------------------------ launch
 // workgroups loop over the work list; L.grid_items of them per list axis (64: a typical 64-buffer batch in one round)
 int lcs_launch_gather_work(lcs_ctx *c, const Launch &L, int skip) {
@@ -1071,6 +1097,16 @@ int lcs_launch_mib(lcs_ctx *c, const Launch &L, bool fused) {
                      c->ce, c->cell_scratch, c->d_pbch_scr, c->d_derm_inv);
   hipLaunchKernelGGL(k_mib_select, dim3((LCS_MAX_WORK + 63) / 64), dim3(64), 0, c->stream, c->cells_out, c->n_work,
                      c->cell_scratch, scatter_back ? c->peaks : nullptr, c->work_items);
+  HIPCHK(c, hipGetLastError());
+  return LCS_OK;
+}
+// lcs_pbch_soft: the channel estimate as lcs_launch_mib's unfused form takes it, then one forced candidate of the first cell
+void lcs_pbch_soft_layout(int *d_est, int *bits, int *ok) { *d_est = PBS_D_EST; *bits = PBS_BITS; *ok = PBS_OK; }
+int lcs_launch_pbch_soft(lcs_ctx *c, const Launch &L, int guess, int n_ports, double *out /*[2048]*/) {
+  hipLaunchKernelGGL(k_chan_est, dim3(L.grid_items, 4, CE_NCHUNK), dim3(CE_THREADS), 0, c->stream, c->cells_out, c->n_work,
+                     c->tfg_comp, (const double2 *)nullptr, (const double *)c->tfg_ts, c->cell_scratch, c->ce, L.needed_rows_only ? 1 : 0);
+  hipLaunchKernelGGL(k_pbch_soft, dim3(1), dim3(PB_THREADS), 0, c->stream, c->cells_out, c->tfg_comp, c->ce, c->cell_scratch,
+                     c->d_pbch_scr, c->d_derm_inv, guess, n_ports, out);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

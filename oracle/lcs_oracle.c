@@ -1204,79 +1204,116 @@ int orc_pbch_crc_ok(const uint8_t *c_est, int n_ports) {
 }
 
 /* ref: src/searcher.cpp:1482-1522 pbch_extract, :1526-1692 decode_mib */
-int orc_decode_mib(const orc_cell *cell, const double *tfg_re_im, int n_ofdm, orc_cell *cell_out) {
-  const cd *tfg = (const cd *)tfg_re_im;
+/* The body of decode_mib's candidate loop up to the CRC comparison, for one (frame_timing_guess, n_ports): pbch_extract,
+ * equalisation, soft demodulation, descrambling, de-rate-matching, decoding.  ce / np_v: chan_est of the four ports.
+ * e_est [m_bit], d_est [3][40], c_est [40]; returns whether the CRC passes under the n_ports mask. */
+static int pbch_soft_ce(const orc_cell *cell, const cd *tfg, cd *const ce[4], const double np_v[4], int frame_timing_guess, int n_ports,
+                        double *e_est, double *d_est, uint8_t *c_est) {
   const int n_symb_dl = cell_n_symb_dl(cell);
-  *cell_out = *cell;
-  if (n_symb_dl < 0) return -1;
-  rs_dl_t *R = (rs_dl_t *)malloc(sizeof(rs_dl_t));
-  rs_dl_build(cell_n_id_cell(cell), cell->cp_type, R);
-  cd *ce[4]; double np_v[4];
-  for (int p = 0; p < 4; p++) { ce[p] = (cd *)malloc(sizeof(cd) * n_ofdm * 72); chan_est(cell, R, tfg, n_ofdm, p, ce[p], &np_v[p]); }
   const int m_bit = (cell->cp_type == ORC_CP_NORMAL) ? 1920 : 1728;
   const int n_sym = m_bit / 2;
   const int v_shift_m3 = imod(cell_n_id_cell(cell), 3);
   cd *pbch_sym = (cd *)malloc(sizeof(cd) * n_sym), *pbch_ce = (cd *)malloc(sizeof(cd) * 4 * n_sym);
   cd *syms = (cd *)malloc(sizeof(cd) * n_sym); double *np = (double *)malloc(sizeof(double) * n_sym);
-  double *e_est = (double *)malloc(sizeof(double) * m_bit); uint8_t *scr = (uint8_t *)malloc(m_bit);
+  uint8_t *scr = (uint8_t *)malloc(m_bit);
+  const int start = frame_timing_guess * 10 * 2 * n_symb_dl;
+  int idx = 0;
+  for (int fr = 0; fr <= 3; fr++) for (int sym = 0; sym <= 3; sym++) for (int sc = 0; sc <= 71; sc++) {
+    if ((imod(sc, 3) == v_shift_m3) && ((sym == 0) || (sym == 1) || ((sym == 3) && (n_symb_dl == 6)))) continue;
+    int sym_num = start + fr * 10 * 2 * n_symb_dl + n_symb_dl + sym;
+    pbch_sym[idx] = tfg[sym_num * 72 + sc];
+    for (int p = 0; p < 4; p++) pbch_ce[p * n_sym + idx] = ce[p][sym_num * 72 + sc];
+    idx++;
+  }
+  if (n_ports == 1) {
+    for (int t = 0; t < n_sym; t++) {
+      cd h = pbch_ce[t];
+      cd gain = cconj(cdiv(h, c_(cabs2(h), 0)));
+      syms[t] = cmul(pbch_sym[t], gain);
+      np[t] = np_v[0] * cabs2(gain);
+    }
+  } else {
+    for (int t = 0; t < n_sym; t += 2) {
+      cd h1, h2; double np_temp;
+      if (n_ports == 2) {
+        h1 = cdivr(cadd(pbch_ce[0 * n_sym + t], pbch_ce[0 * n_sym + t + 1]), 2);
+        h2 = cdivr(cadd(pbch_ce[1 * n_sym + t], pbch_ce[1 * n_sym + t + 1]), 2);
+        np_temp = (np_v[0] + np_v[1]) / 2; /* mean(np_v(0,1)) */
+      } else if (imod(t, 4) == 0) {
+        h1 = cdivr(cadd(pbch_ce[0 * n_sym + t], pbch_ce[0 * n_sym + t + 1]), 2);
+        h2 = cdivr(cadd(pbch_ce[2 * n_sym + t], pbch_ce[2 * n_sym + t + 1]), 2);
+        np_temp = (np_v[0] + np_v[2]) / 2;
+      } else {
+        h1 = cdivr(cadd(pbch_ce[1 * n_sym + t], pbch_ce[1 * n_sym + t + 1]), 2);
+        h2 = cdivr(cadd(pbch_ce[3 * n_sym + t], pbch_ce[3 * n_sym + t + 1]), 2);
+        np_temp = (np_v[1] + np_v[3]) / 2;
+      }
+      cd x1 = pbch_sym[t], x2 = pbch_sym[t + 1];
+      double scale = pow(h1.re, 2) + pow(h1.im, 2) + pow(h2.re, 2) + pow(h2.im, 2);
+      syms[t] = cdivr(cadd(cmul(cconj(h1), x1), cmul(h2, cconj(x2))), scale);
+      cd nh2c = c_(-h2.re, h2.im); /* -conj(h2) */
+      syms[t + 1] = cconj(cdivr(cadd(cmul(nh2c, x1), cmul(h1, cconj(x2))), scale));
+      np[t] = (pow(hypot(h1.re, h1.im) / scale, 2) + pow(hypot(h2.re, h2.im) / scale, 2)) * np_temp;
+      np[t + 1] = np[t];
+    }
+    double s2 = pow(2, 0.5);
+    for (int t = 0; t < n_sym; t++) syms[t] = cscale(syms[t], s2);
+  }
+  lte_demodulate_qpsk(syms, np, n_sym, e_est);
+  orc_lte_pn((uint32_t)cell_n_id_cell(cell), (uint32_t)m_bit, scr);
+  for (int t = 0; t < m_bit; t++) if (scr[t]) e_est[t] = -e_est[t];
+  lte_conv_deratematch(e_est, m_bit, 40, d_est);
+  conv_decode_tailbite(d_est, 40, c_est);
+  free(pbch_sym); free(pbch_ce); free(syms); free(np); free(scr);
+  return orc_pbch_crc_ok(c_est, n_ports);
+}
+
+/* the four ports' channel estimates that decode_mib starts with (ref :1531-1541) */
+static void pbch_chan_est4(const orc_cell *cell, const cd *tfg, int n_ofdm, cd *ce[4], double np_v[4]) {
+  rs_dl_t *R = (rs_dl_t *)malloc(sizeof(rs_dl_t));
+  rs_dl_build(cell_n_id_cell(cell), cell->cp_type, R);
+  for (int p = 0; p < 4; p++) { ce[p] = (cd *)malloc(sizeof(cd) * n_ofdm * 72); chan_est(cell, R, tfg, n_ofdm, p, ce[p], &np_v[p]); }
+  free(R);
+}
+
+/* One candidate of decode_mib, forced: the soft values it forms before the CRC decides (the very code orc_decode_mib runs).
+ * n_cand candidates (guess[i], n_ports[i]) share one channel estimate; e_est [n_cand][1920] (m_bit used), d_est [n_cand][3][40],
+ * c_est [n_cand][40], crc_ok [n_cand]. */
+int orc_pbch_soft_many(const orc_cell *cell, const double *tfg_re_im, int n_ofdm, int n_cand, const int *guess, const int *n_ports,
+                       double *e_est, double *d_est, uint8_t *c_est, int *crc_ok) {
+  const cd *tfg = (const cd *)tfg_re_im;
+  const int n_symb_dl = cell_n_symb_dl(cell);
+  if (n_symb_dl < 0 || n_ofdm != ((n_symb_dl == 7) ? 854 : 732)) return -1;
+  for (int i = 0; i < n_cand; i++)
+    if (guess[i] < 0 || guess[i] > 3 || (n_ports[i] != 1 && n_ports[i] != 2 && n_ports[i] != 4)) return -1;
+  cd *ce[4]; double np_v[4];
+  pbch_chan_est4(cell, tfg, n_ofdm, ce, np_v);
+  for (int i = 0; i < n_cand; i++)
+    crc_ok[i] = pbch_soft_ce(cell, tfg, ce, np_v, guess[i], n_ports[i], e_est + (size_t)i * 1920, d_est + (size_t)i * 120, c_est + (size_t)i * 40);
+  for (int p = 0; p < 4; p++) free(ce[p]);
+  return 0;
+}
+int orc_pbch_soft(const orc_cell *cell, const double *tfg_re_im, int n_ofdm, int guess, int n_ports,
+                  double *e_est, double *d_est, uint8_t *c_est, int *crc_ok) {
+  return orc_pbch_soft_many(cell, tfg_re_im, n_ofdm, 1, &guess, &n_ports, e_est, d_est, c_est, crc_ok);
+}
+void orc_conv_deratematch(const double *e_est, int n_e, double *d_est /*[3][40]*/) { lte_conv_deratematch(e_est, n_e, 40, d_est); }
+
+int orc_decode_mib(const orc_cell *cell, const double *tfg_re_im, int n_ofdm, orc_cell *cell_out) {
+  const cd *tfg = (const cd *)tfg_re_im;
+  const int n_symb_dl = cell_n_symb_dl(cell);
+  *cell_out = *cell;
+  if (n_symb_dl < 0) return -1;
+  cd *ce[4]; double np_v[4];
+  pbch_chan_est4(cell, tfg, n_ofdm, ce, np_v);
+  double *e_est = (double *)malloc(sizeof(double) * 1920);
   int found = 0;
   for (int frame_timing_guess = 0; frame_timing_guess <= 3 && !found; frame_timing_guess++) {
-    const int start = frame_timing_guess * 10 * 2 * n_symb_dl;
-    int idx = 0;
-    for (int fr = 0; fr <= 3; fr++) for (int sym = 0; sym <= 3; sym++) for (int sc = 0; sc <= 71; sc++) {
-      if ((imod(sc, 3) == v_shift_m3) && ((sym == 0) || (sym == 1) || ((sym == 3) && (n_symb_dl == 6)))) continue;
-      int sym_num = start + fr * 10 * 2 * n_symb_dl + n_symb_dl + sym;
-      pbch_sym[idx] = tfg[sym_num * 72 + sc];
-      for (int p = 0; p < 4; p++) pbch_ce[p * n_sym + idx] = ce[p][sym_num * 72 + sc];
-      idx++;
-    }
     for (int n_ports_pre = 1; n_ports_pre <= 3 && !found; n_ports_pre++) {
       const int n_ports = (n_ports_pre == 3) ? 4 : n_ports_pre;
-      if (n_ports == 1) {
-        for (int t = 0; t < n_sym; t++) {
-          cd h = pbch_ce[t];
-          cd gain = cconj(cdiv(h, c_(cabs2(h), 0)));
-          syms[t] = cmul(pbch_sym[t], gain);
-          np[t] = np_v[0] * cabs2(gain);
-        }
-      } else {
-        for (int t = 0; t < n_sym; t += 2) {
-          cd h1, h2; double np_temp;
-          if (n_ports == 2) {
-            h1 = cdivr(cadd(pbch_ce[0 * n_sym + t], pbch_ce[0 * n_sym + t + 1]), 2);
-            h2 = cdivr(cadd(pbch_ce[1 * n_sym + t], pbch_ce[1 * n_sym + t + 1]), 2);
-            np_temp = (np_v[0] + np_v[1]) / 2; /* mean(np_v(0,1)) */
-          } else if (imod(t, 4) == 0) {
-            h1 = cdivr(cadd(pbch_ce[0 * n_sym + t], pbch_ce[0 * n_sym + t + 1]), 2);
-            h2 = cdivr(cadd(pbch_ce[2 * n_sym + t], pbch_ce[2 * n_sym + t + 1]), 2);
-            np_temp = (np_v[0] + np_v[2]) / 2;
-          } else {
-            h1 = cdivr(cadd(pbch_ce[1 * n_sym + t], pbch_ce[1 * n_sym + t + 1]), 2);
-            h2 = cdivr(cadd(pbch_ce[3 * n_sym + t], pbch_ce[3 * n_sym + t + 1]), 2);
-            np_temp = (np_v[1] + np_v[3]) / 2;
-          }
-          cd x1 = pbch_sym[t], x2 = pbch_sym[t + 1];
-          double scale = pow(h1.re, 2) + pow(h1.im, 2) + pow(h2.re, 2) + pow(h2.im, 2);
-          syms[t] = cdivr(cadd(cmul(cconj(h1), x1), cmul(h2, cconj(x2))), scale);
-          cd nh2c = c_(-h2.re, h2.im); /* -conj(h2) */
-          syms[t + 1] = cconj(cdivr(cadd(cmul(nh2c, x1), cmul(h1, cconj(x2))), scale));
-          np[t] = (pow(hypot(h1.re, h1.im) / scale, 2) + pow(hypot(h2.re, h2.im) / scale, 2)) * np_temp;
-          np[t + 1] = np[t];
-        }
-        double s2 = pow(2, 0.5);
-        for (int t = 0; t < n_sym; t++) syms[t] = cscale(syms[t], s2);
-      }
-      lte_demodulate_qpsk(syms, np, n_sym, e_est);
-      orc_lte_pn((uint32_t)cell_n_id_cell(cell), (uint32_t)m_bit, scr);
-      for (int t = 0; t < m_bit; t++) if (scr[t]) e_est[t] = -e_est[t];
       double d_est[3 * 40];
-      lte_conv_deratematch(e_est, m_bit, 40, d_est);
-      uint8_t c_est[40], crc_est[16];
-      conv_decode_tailbite(d_est, 40, c_est);
-      crc16_bits(c_est, 24, crc_est);
-      if (n_ports == 2) for (int t = 0; t < 16; t++) crc_est[t] = 1 - crc_est[t];
-      else if (n_ports == 4) for (int t = 1; t < 16; t += 2) crc_est[t] = 1 - crc_est[t];
-      if (memcmp(crc_est, c_est + 24, 16) == 0) {
+      uint8_t c_est[40];
+      if (pbch_soft_ce(cell, tfg, ce, np_v, frame_timing_guess, n_ports, e_est, d_est, c_est)) {
         cell_out->n_ports = n_ports;
         const int bw_packed = c_est[0] * 4 + c_est[1] * 2 + c_est[2];
         static const int bw[6] = {6, 15, 25, 50, 75, 100};
@@ -1290,7 +1327,7 @@ int orc_decode_mib(const orc_cell *cell, const double *tfg_re_im, int n_ofdm, or
     }
   }
   for (int p = 0; p < 4; p++) free(ce[p]);
-  free(pbch_sym); free(pbch_ce); free(syms); free(np); free(e_est); free(scr); free(R);
+  free(e_est);
   return 0;
 }
 

@@ -307,6 +307,42 @@ def decode_mib(cell, tfg) -> Cell:
     return out
 
 
+CANDIDATES = [(g, p) for g in range(4) for p in (1, 2, 4)]      # decode_mib's loop order
+
+
+def pbch_soft(cell, tfg, frame_timing_guess, n_ports):
+    """One forced candidate of decode_mib -> (e_est [1920|1728], d_est [3][40], c_est [40] uint8, crc_ok)"""
+    e, d, c, ok = pbch_soft_many(cell, tfg, [(frame_timing_guess, n_ports)])
+    return e[0], d[0], c[0], bool(ok[0])
+
+
+def pbch_soft_many(cell, tfg, candidates=None):
+    """The same for a list of (guess, n_ports) on one channel estimate -> (e_est [n][m_bit], d_est [n][3][40], c_est [n][40], crc_ok [n])"""
+    tfg = np.ascontiguousarray(tfg, np.complex128)
+    cand = CANDIDATES if candidates is None else list(candidates)
+    n = len(cand)
+    g, p = np.array([c[0] for c in cand], np.int32), np.array([c[1] for c in cand], np.int32)
+    e, d, c, ok = np.zeros((n, 1920)), np.zeros((n, 3, 40)), np.zeros((n, 40), np.uint8), np.zeros(n, np.int32)
+    L = lib()
+    L.orc_pbch_soft_many.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]
+    rc = L.orc_pbch_soft_many(C.byref(cell), _dp(tfg), tfg.shape[0], n, _ip(g), _ip(p), _dp(e), _dp(d),
+                              c.ctypes.data_as(C.POINTER(C.c_uint8)), _ip(ok))
+    if rc:
+        raise RuntimeError(f"orc_pbch_soft_many rc={rc}")
+    return e[:, :1920 if tfg.shape[0] == 854 else 1728].copy(), d, c, ok.astype(bool)
+
+
+def conv_deratematch(e_est):
+    e = np.ascontiguousarray(e_est, np.float64)
+    d = np.zeros((3, 40))
+    L = lib()
+    L.orc_conv_deratematch.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]
+    L.orc_conv_deratematch.restype = None
+    L.orc_conv_deratematch(_dp(e), e.size, _dp(d))
+    return d
+
+
 def search_capbuf(capbuf, f_search_set, fc_requested, fc_programmed, fs_programmed, max_cells=64):
     """Full per-buffer chain of CellSearch's main loop.  Returns (cells, peaks)."""
     cap = _cap(capbuf)
