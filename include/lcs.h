@@ -332,6 +332,52 @@ typedef struct lcs_pcfich_info {
   double margin[LCS_PCFICH_MAX_SF];
 } lcs_pcfich_info;        /* 2640 bytes */
 
+/* The PDCCH common search space of a wide cell: the DCIs whose CRC is masked with the SI-RNTI, the P-RNTI or an RA-RNTI, in every
+ * downlink subframe of a full-bandwidth grid (lcs_pdcch_wide, lcs_pdcch below; a stage of its own beside the chain).  THE RULE
+ * (lte-cell-scanner_amd/csrc/pdcch.h, host and device; grid, subframes, channel and combining as for lcs_pcfich_info):
+ *   control     symbols 0 .. n_ctrl - 1 of the subframe's first slot, n_ctrl = cfi + (n_rb <= 10); the cfi is the PCFICH's decision
+ *               for that subframe, or cfi_force.  A subframe is read iff its bit of dl_mask is set, the rows of symbols 0 .. 2 (0 .. 3
+ *               for n_rb <= 10) lie inside n_ofdm and its cfi was decoded
+ *   REGs        36.211 6.2.4: symbol 0 has two per resource block (six columns, the four that are not = n_id_cell (mod 3)); symbol 1
+ *               three of four consecutive columns, with 4 ports two as symbol 0; symbol 2 three; symbol 3 three, with the extended
+ *               CP two as symbol 0.  A REG is named (k', l'), k' its lowest column
+ *   PCFICH      its four REGs of symbol 0.   PHICH (36.211 6.9.3): U = m_i ceil(Ng n_rb / 8) units of three REGs; with n_l the REGs
+ *               of symbol l beside the PCFICH numbered by ascending k', REG i = 0, 1, 2 of unit m' is number (floor(n_id_cell n_l /
+ *               n_0) + m' + floor(i n_l / 3)) mod n_l of symbol l = 0 (normal duration) or l = i (extended; needs n_ctrl >= 3)
+ *   order       the N_REG other REGs sorted by (k', l'); N_CCE = floor(N_REG / 9); REG i carries quadruplet w((i + n_id_cell) mod
+ *               N_REG) of the multiplexed stream, w the sub-block interleaver of 36.212 5.1.4.2.1 on quadruplets (32 columns, the
+ *               nulls in front, the PBCH's column permutation); bit j of CCE c is bit 72 c + j of the stream
+ *   soft bits   b[2 e] = Re s_e, b[2 e + 1] = Im s_e for the elements e of quadruplets 0 .. 143, times 1 - 2 c(i) of the Gold
+ *               sequence with c_init = sf 2^9 + n_id_cell; no noise scaling
+ *   candidates  slot s = 0 .. 3: L = 4 from CCE 4 s, while s < min(4, floor(N_CCE / 4)); slot 4, 5: L = 8 from CCE 8 (s - 4), while
+ *               s - 4 < min(2, floor(N_CCE / 8))
+ *   decoding    per candidate and payload size A (K = A + 16): every coded bit is the SUM of its soft bits among the 72 L (36.212
+ *               5.1.4.2 inverted, ascending position); the tail-biting decoder over K steps (the lowest start state among equal
+ *               end metrics); rnti_x = CRC-16 of the first A bits ^ the received sixteen, MSB first
+ *   accepted    rnti_x = 0xFFFF (rnti_mask bit 0, SI), 0xFFFE (bit 1, paging) or 0x0001 .. 0x003C (bit 2, random-access response).
+ *               A silent candidate (every soft bit zero) decodes to all zeros with rnti_x = 0 and is never accepted.
+ * dec[g][s][i]: bits = the A payload bits (bit t = the t-th bit sent); flags 1 = decoded, | 2 = accepted; quality = -(the winning
+ * end metric) / sum |coded bit|: the decoder MINIMISES the sum of -(+-value), so a noise-free codeword gives +1 and noise values
+ * near 0 (0 for a silent candidate).  A slot beyond the subframe's candidates, a subframe that is not read and a candidate with a
+ * value that is not finite leave a zero entry.  cfi, n_reg, n_cce: what the subframe was read with (0: not read).  n_read counts the
+ * subframes read, n_accepted the accepted entries (a DCI found at L = 4 and L = 8 counts twice), n_si / n_paging / n_ra by kind. */
+#define LCS_PDCCH_SLOTS 6
+#define LCS_PDCCH_MAX_SIZES 2
+typedef struct lcs_pdcch_cfg {            /* zero = take from the cell / defaults */
+  int32_t phich_duration, phich_resource; /* 0: the cell's (refused when the cell has none); else as lcs_cell's */
+  int32_t phich_mi[10];                   /* m_i of subframe 0 .. 9: 0, 1 or 2; -1: FDD's 1.  A call with any entry >= 0 is a TDD
+                                             call: with the extended PHICH duration its subframes 1 and 6 are not read */
+  int32_t n_sizes, size[LCS_PDCCH_MAX_SIZES];   /* payload sizes A, 8 .. 48 */
+  int32_t rnti_mask;                      /* bit 0 SI, 1 paging, 2 RA; 0 = all three */
+  int32_t cfi_force;                      /* 0: the PCFICH's decision per subframe */
+} lcs_pdcch_cfg;          /* 68 bytes */
+typedef struct lcs_pdcch_dec { uint64_t bits; uint32_t rnti_x; int32_t flags /*1 decoded, 2 accepted*/; double quality; } lcs_pdcch_dec;
+typedef struct lcs_pdcch_info {
+  int32_t n_sf, n_read, n_accepted, n_si, n_paging, n_ra, dl_mask, n_rb, n_ports, reserved;
+  int32_t cfi[LCS_PCFICH_MAX_SF], n_reg[LCS_PCFICH_MAX_SF], n_cce[LCS_PCFICH_MAX_SF];
+  lcs_pdcch_dec dec[LCS_PCFICH_MAX_SF][LCS_PDCCH_SLOTS][LCS_PDCCH_MAX_SIZES];
+} lcs_pdcch_info;         /* 21640 bytes */
+
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
 /* Replaces xcorr_pss -- include/searcher.h:22-41, src/searcher.cpp:389-419
@@ -453,6 +499,22 @@ int lcs_pcfich_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, ui
                     int dl_mask, lcs_pcfich_info *out);
 int lcs_pcfich(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
                int dl_mask, lcs_pcfich_info *out);
+
+/* The PDCCH common search space (the rule: lcs_pdcch_info above).  The two take lcs_pcfich_wide's and lcs_pcfich's arguments, with
+ * their conventions and refusals, and a configuration (cfg == NULL is refused: the payload sizes have no default in the library).
+ * lcs_pdcch_wide transforms symbols 0 .. 2 (0 .. 3 for n_rb <= 10) of the first slot of every subframe of the mask before the CFI
+ * is known; then both run the PCFICH on those rows (unless cfi_force says the CFI), the soft bits of CCE 0 .. 15 and one decode per
+ * (subframe, candidate, size), all on the device without a host round trip.  Refused beyond the PCFICH's refusals, with
+ * LCS_ERR_BAD_ARG, a text and no launch: a PHICH duration / resource that neither cfg nor the cell says, or outside 1 .. 2 /
+ * 1 .. 4; n_sizes outside 1 .. 2 or a size outside 8 .. 48; cfi_force outside 0 .. 3, or one that the extended PHICH duration does
+ * not fit (n_ctrl < 3); an m_i outside -1 .. 2; an rnti_mask outside 0 .. 7.  The REG map and the de-rate-matching lists are built
+ * on the host once per (n_rb, ports, CP, n_id_cell, PHICH configuration, sizes) and kept in the context.  Isolation as the PCFICH's;
+ * the PCFICH decisions go into a record of this stage's own. */
+int lcs_pdcch_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                   double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                   int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out);
+int lcs_pdcch(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
+              int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out);
 
 /* ---- fused chain ------------------------------------------------------------------- */
 

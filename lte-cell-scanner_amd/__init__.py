@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo,FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -520,6 +520,36 @@ class Searcher:
             raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
         out = capi.PcfichInfo()
         self._chk(self._lib.lcs_pcfich(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(out)), "lcs_pcfich")
+        return out
+
+    @staticmethod
+    def _pdcch_cfg(cfg, n_rb):
+        """a PdcchCfg as it is, or None: FDD, the cell's PHICH configuration, the two sizes of the common search space"""
+        return cfg if cfg is not None else capi.PdcchCfg.make(capi.dci_common_sizes(int(n_rb), False))
+
+    def pdcch_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                   cfg=None, n_cap=None):
+        """The DCIs of the PDCCH common search space (SI, paging, random-access responses) of every downlink subframe from the same
+        samples (lcs_pdcch_wide: symbols 0 .. 2 of every subframe of the mask are transformed, 0 .. 3 up to 10 resource blocks; the
+        CFI is the PCFICH's, decided on the device).  cfg: a capi.PdcchCfg; None = FDD defaults -> PdcchInfo"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out = capi.PdcchInfo()
+        self._chk(self._lib.lcs_pdcch_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_wide")
+        out.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return out
+
+    def pdcch(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
+        """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
+        (extract_tfg_wide's) (lcs_pdcch) -> PdcchInfo"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out = capi.PdcchInfo()
+        self._chk(self._lib.lcs_pdcch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch")
+        out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
 
     def set_float_batch_probe(self, on: bool):

@@ -233,11 +233,171 @@ class PcfichInfo(C.Structure):
 
 assert C.sizeof(PcfichInfo) == 2640
 
+PDCCH_SLOTS, PDCCH_MAX_SIZES = 6, 2      # LCS_PDCCH_SLOTS, LCS_PDCCH_MAX_SIZES
+RNTI_SI, RNTI_PAGING, RNTI_RA = 1, 2, 4   # bits of lcs_pdcch_cfg.rnti_mask
+
+
+class PdcchCfg(C.Structure):
+    """lcs_pdcch_cfg (include/lcs.h).  PdcchCfg.make(sizes, ...) fills it: phich_duration / phich_resource 0 = the cell's; phich_mi
+    None = FDD (every m_i 1), else ten values of 36.211 table 6.9-1 (tdd_phich_mi; None entries, the uplink subframes, count as 0)."""
+    _fields_ = [("phich_duration", C.c_int32), ("phich_resource", C.c_int32), ("phich_mi", C.c_int32 * 10), ("n_sizes", C.c_int32),
+                ("size", C.c_int32 * PDCCH_MAX_SIZES), ("rnti_mask", C.c_int32), ("cfi_force", C.c_int32)]
+
+    @classmethod
+    def make(cls, sizes, phich_duration=0, phich_resource=0, phich_mi=None, rnti_mask=0, cfi_force=0) -> "PdcchCfg":
+        sizes = [int(a) for a in sizes]
+        if not 1 <= len(sizes) <= PDCCH_MAX_SIZES:
+            raise ValueError("PdcchCfg: one or two payload sizes")
+        o = cls()
+        o.phich_duration, o.phich_resource, o.rnti_mask, o.cfi_force, o.n_sizes = int(phich_duration), int(phich_resource), int(rnti_mask), int(cfi_force), len(sizes)
+        for i, a in enumerate(sizes):
+            o.size[i] = a
+        for i in range(10):
+            o.phich_mi[i] = -1 if phich_mi is None else (0 if phich_mi[i] is None else int(phich_mi[i]))
+        return o
+
+
+class PdcchDec(C.Structure):
+    """lcs_pdcch_dec: bits = the payload (bit t = the t-th bit sent), rnti_x, flags (1 decoded, 2 accepted), quality"""
+    _fields_ = [("bits", C.c_uint64), ("rnti_x", C.c_uint32), ("flags", C.c_int32), ("quality", C.c_double)]
+
+
+class PdcchInfo(C.Structure):
+    """lcs_pdcch_info: the decodes of the PDCCH common search space of every subframe of a full-bandwidth grid (include/lcs.h:
+    lcs_pdcch_wide, lcs_pdcch).  cfi / n_reg / n_cce: numpy views cut to n_sf (0: subframe not read); dec[g][slot][size] the entries
+    (slots 0 .. 3: L = 4 from CCE 4 slot; 4, 5: L = 8 from CCE 8 (slot - 4)).  sizes: the payload sizes of the call."""
+    _fields_ = [("n_sf", C.c_int32), ("n_read", C.c_int32), ("n_accepted", C.c_int32), ("n_si", C.c_int32), ("n_paging", C.c_int32), ("n_ra", C.c_int32),
+                ("dl_mask", C.c_int32), ("n_rb", C.c_int32), ("n_ports", C.c_int32), ("reserved", C.c_int32),
+                ("_cfi", C.c_int32 * PCFICH_MAX_SF), ("_n_reg", C.c_int32 * PCFICH_MAX_SF), ("_n_cce", C.c_int32 * PCFICH_MAX_SF),
+                ("dec", ((PdcchDec * PDCCH_MAX_SIZES) * PDCCH_SLOTS) * PCFICH_MAX_SF)]
+    sizes = ()
+
+    def copy(self) -> "PdcchInfo":
+        o = PdcchInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(PdcchInfo))
+        o.sizes = tuple(self.sizes)
+        return o
+
+    def _n(self) -> int:
+        return min(max(int(self.n_sf), 0), PCFICH_MAX_SF)
+
+    @property
+    def cfi(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._cfi)[:self._n()]
+
+    @property
+    def n_reg(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._n_reg)[:self._n()]
+
+    @property
+    def n_cce(self):
+        import numpy as np
+        return np.ctypeslib.as_array(self._n_cce)[:self._n()]
+
+    @staticmethod
+    def slot_candidate(slot: int):
+        """(L, first CCE) of candidate slot 0 .. 5"""
+        return (4, 4 * slot) if slot < 4 else (8, 8 * (slot - 4))
+
+    def entries(self):
+        """(subframe, slot, size index, PdcchDec) of every decoded entry"""
+        for g in range(self._n()):
+            for s in range(PDCCH_SLOTS):
+                for i in range(PDCCH_MAX_SIZES):
+                    d = self.dec[g][s][i]
+                    if d.flags & 1:
+                        yield g, s, i, d
+
+    def messages(self) -> list:
+        """The accepted decodes as dicts: subframe, L, cce, kind ("si" / "paging" / "ra"), rnti, size (None when the record does not
+        know its call's sizes), bits (the payload as an int, bit t = the t-th bit sent), quality.  A DCI found at L = 8 and at L = 4
+        from the same first CCE with the same payload is listed once, the better quality kept."""
+        best = {}
+        for g, s, i, d in self.entries():
+            if not d.flags & 2:
+                continue
+            L, cce = self.slot_candidate(s)
+            kind = "si" if d.rnti_x == 0xFFFF else "paging" if d.rnti_x == 0xFFFE else "ra"
+            m = dict(subframe=g, L=L, cce=cce, kind=kind, rnti=int(d.rnti_x), size=(self.sizes[i] if i < len(self.sizes) else None), bits=int(d.bits),
+                     quality=float(d.quality))
+            key = (g, cce, i, int(d.bits), int(d.rnti_x))
+            if key not in best or m["quality"] > best[key]["quality"]:
+                best[key] = m
+        return sorted(best.values(), key=lambda m: (m["subframe"], m["cce"], m["L"], -1 if m["size"] is None else m["size"]))
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"PdcchInfo(n_sf={self.n_sf}, n_read={self.n_read}, n_accepted={self.n_accepted}, n_si={self.n_si}, n_paging={self.n_paging}, n_ra={self.n_ra})"
+
+
+assert C.sizeof(PdcchCfg) == 68 and C.sizeof(PdcchDec) == 24 and C.sizeof(PdcchInfo) == 21640
+
+# Payload sizes of the two DCI formats of the common search space (36.212 5.3.3.1.3, 5.3.3.1.4).
+# 1A = flag 1 + localized/distributed 1 + RIV ceil(log2(n_rb (n_rb + 1) / 2)) + MCS 5 + HARQ 3 + NDI 1 + RV 2 + TPC 2
+#    = 15 + ceil(log2(n_rb (n_rb + 1) / 2)); TDD has a 4-bit HARQ number and a 2-bit DAI: + 3.  One zero is appended when the size
+#    is one of the ambiguous sizes of table 5.3.3.1.2-1 (12, 14, 16, 20, 24, 26, 32, 40, 44, 56).
+# 1C = gap bit (n_rb >= 50) + ceil(log2(v (v + 1) / 2)) + TBS index 5, v = floor(N_VRB,gap1 / N_step), N_step = 2 (n_rb < 50) or 4,
+#    N_VRB,gap1 = 2 min(N_gap, n_rb - N_gap) with N_gap = 3, 8, 12, 27, 32, 48 (36.211 table 6.2.3.2-1): v = 3, 7, 12, 11, 16, 24.
+_DCI_SIZES = {6: (21, 23, 8), 15: (22, 25, 10), 25: (25, 27, 12), 50: (27, 29, 13), 75: (27, 30, 14), 100: (28, 31, 15)}
+_DCI_AMBIGUOUS = (12, 14, 16, 20, 24, 26, 32, 40, 44, 56)
+
+
+def dci_1a_size(n_rb: int, tdd: bool = False) -> int:
+    """the size of format 1A from its fields (what the table holds)"""
+    a = 15 + (n_rb * (n_rb + 1) // 2 - 1).bit_length() + (3 if tdd else 0)
+    return a + 1 if a in _DCI_AMBIGUOUS else a
+
+
+def dci_common_sizes(n_rb: int, tdd: bool = False):
+    """(size of DCI format 1A, size of format 1C) of the common search space of an n_rb cell"""
+    fdd, td, c = _DCI_SIZES[int(n_rb)]
+    return (td if tdd else fdd), c
+
+
+# 36.211 table 6.9-1: m_i per uplink-downlink configuration and subframe; None = an uplink subframe.  Only a default the caller may
+# override (lcs_pdcch_cfg.phich_mi): a wrong entry here is a wrong default, not a wrong kernel.
+_TDD_PHICH_MI = [[2, 1, None, None, None, 2, 1, None, None, None], [0, 1, None, None, 1, 0, 1, None, None, 1], [0, 0, None, 1, 0, 0, 0, None, 1, 0],
+                 [1, 0, None, None, None, 0, 0, 0, 1, 1], [0, 0, None, None, 0, 0, 0, 0, 1, 1], [0, 0, None, 0, 0, 0, 0, 0, 1, 0],
+                 [1, 1, None, None, None, 1, 1, None, None, 1]]
+
+
+def tdd_phich_mi(config: int) -> list:
+    """m_i of subframes 0 .. 9 of uplink-downlink configuration 0 .. 6 (None: uplink)"""
+    return list(_TDD_PHICH_MI[int(config)])
+
+
+def dci_1a_fields(bits, n_rb: int, tdd: bool = False) -> dict:
+    """The fields of a format 1A payload (36.212 5.3.3.1.3) as it is used with SI-, P- and RA-RNTI.  bits: the payload as an int (bit t
+    = the t-th bit sent: PdcchInfo.messages()' "bits") or a sequence of bits in the order sent."""
+    size = dci_common_sizes(n_rb, tdd)[0]
+    if isinstance(bits, int):
+        bits = [(bits >> t) & 1 for t in range(size)]
+    bits = [int(b) for b in bits]
+    pos = [0]
+
+    def take(n):
+        v = 0
+        for b in bits[pos[0]:pos[0] + n]:
+            v = (v << 1) | b
+        pos[0] += n
+        return v
+    out = dict(flag_1a=take(1), distributed=take(1))
+    riv = take((n_rb * (n_rb + 1) // 2 - 1).bit_length())
+    length, start = riv // n_rb + 1, riv % n_rb
+    if length + start > n_rb:
+        length, start = n_rb - length + 2, n_rb - 1 - start
+    out.update(riv=riv, rb_start=start, n_rb_alloc=length, mcs=take(5), harq=take(4 if tdd else 3), ndi=take(1), rv=take(2), tpc=take(2))
+    if tdd:
+        out["dai"] = take(2)
+    return out
+
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -318,6 +478,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_pcfich_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(PcfichInfo)]
         L.lcs_pcfich.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PcfichInfo)]
+    if hasattr(L, "lcs_pdcch_wide"):      # (likewise)
+        L.lcs_pdcch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
+        L.lcs_pdcch.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

@@ -14,6 +14,7 @@
 #include "cell_meas.h"
 #include "cell_meas_wide.h"
 #include "pcfich.h"
+#include "pdcch.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
 
@@ -1201,6 +1202,104 @@ int lcs_pcfich(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, 
   if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
   if ((rc = lcs_launch_pcfich(c, *cell, rows, n_sf, n_rb, dl_mask))) return rc;
   return pcfich_finish(c, out);
+}
+
+// ---- the PDCCH common search space on that grid (pdcch.hip, pdcch.h): the same blocks and the same isolation
+namespace {
+// what cfg and the cell say together, or the refusal
+int pdcch_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_pdcch_cfg *cfg, PdcchPlan *p) {
+  if (!cfg) return wide_refused(c, who, "a null pointer");
+  p->phich_duration = cfg->phich_duration ? cfg->phich_duration : cell->phich_duration;
+  p->phich_resource = cfg->phich_resource ? cfg->phich_resource : cell->phich_resource;
+  if (p->phich_duration == 0 || p->phich_resource == 0) return wide_refused(c, who, "the PHICH configuration is unknown: neither cfg nor the cell says it");
+  if (p->phich_duration < 1 || p->phich_duration > 2) return wide_refused(c, who, "phich_duration is outside 1 (normal) .. 2 (extended)");
+  if (p->phich_resource < 1 || p->phich_resource > 4) return wide_refused(c, who, "phich_resource is outside 1 (Ng = 1/6) .. 4 (Ng = 2)");
+  if (cfg->n_sizes < 1 || cfg->n_sizes > LCS_PDCCH_MAX_SIZES) return wide_refused(c, who, "n_sizes is outside 1 .. 2");
+  p->n_sizes = cfg->n_sizes;
+  p->size[0] = p->size[1] = 0;
+  for (int i = 0; i < cfg->n_sizes; ++i) {
+    if (cfg->size[i] < 8 || cfg->size[i] > 48) return wide_refused(c, who, "a payload size is outside 8 .. 48");
+    p->size[i] = cfg->size[i];
+  }
+  if (cfg->cfi_force < 0 || cfg->cfi_force > 3) return wide_refused(c, who, "cfi_force is outside 0 .. 3");
+  if (cfg->cfi_force && p->phich_duration == 2 && pdc_n_ctrl(cfg->cfi_force, n_rb) < 3)
+    return wide_refused(c, who, "the extended PHICH duration needs three control symbols: cfi_force gives fewer");
+  p->cfi_force = cfg->cfi_force;
+  for (int i = 0; i < 10; ++i) {
+    if (cfg->phich_mi[i] < -1 || cfg->phich_mi[i] > 2) return wide_refused(c, who, "an m_i is outside 0 .. 2 (-1: FDD's 1)");
+    p->mi[i] = cfg->phich_mi[i] < 0 ? 1 : cfg->phich_mi[i];
+  }
+  if (cfg->rnti_mask < 0 || cfg->rnti_mask > 7) return wide_refused(c, who, "rnti_mask is outside 0 .. 7");
+  p->rnti_mask = cfg->rnti_mask ? cfg->rnti_mask : 7;
+  return LCS_OK;
+}
+// rows4[4 g + l] for every subframe of the grid and l < 4, as pcfich_plan: a subframe is read when its bit of the mask is set and
+// its symbols 0 .. n_ctrl_max - 1 lie inside the grid; a TDD call (an m_i given) with the extended duration leaves out subframes 1, 6
+int pdcch_plan(const lcs_cell *cell, const lcs_pdcch_cfg *cfg, const PdcchPlan &p, int n_ofdm, int n_rb, int dl_mask, int *rows4, std::vector<int> *list) {
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_sf = pcf_n_sf(n_ofdm, n_symb), n_max = pdc_n_ctrl_max(n_rb);
+  bool tdd = false;
+  for (int i = 0; i < 10; ++i) tdd = tdd || cfg->phich_mi[i] >= 0;
+  for (int g = 0; g < n_sf; ++g) {
+    for (int l = 0; l < 4; ++l) rows4[4 * g + l] = -1;
+    const int r0 = 2 * g * n_symb, sf = g % 10;
+    if (!((dl_mask >> sf) & 1) || r0 + n_max - 1 >= n_ofdm) continue;
+    if (tdd && p.phich_duration == 2 && (sf == 1 || sf == 6)) continue;
+    for (int l = 0; l < n_max; ++l) {
+      if (list) { rows4[4 * g + l] = (int)list->size(); list->push_back(r0 + l); }
+      else rows4[4 * g + l] = r0 + l;
+    }
+  }
+  return n_sf;
+}
+int pdcch_finish(lcs_ctx *c, lcs_pdcch_info *out) {
+  HIPCHK(c, hipMemcpyAsync(out, c->pdcch.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_pdcch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                   int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdcch_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  PdcchPlan plan;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  int rows4[4 * PCF_MAX_SF];
+  std::vector<int> list;
+  const int n_sf = pdcch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, &list);
+  std::vector<double> ideal(list.size());
+  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
+  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
+  return pdcch_finish(c, out);
+}
+
+int lcs_pdcch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdcch";
+  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  int rc;
+  PdcchPlan plan;
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  int rows4[4 * PCF_MAX_SF];
+  const int n_sf = pdcch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, nullptr);
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
+  if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
+  return pdcch_finish(c, out);
 }
 
 // chan_est of decode_mib as a stage of its own (ref src/searcher.cpp:1369-1477, ce_interp_hex :1223-1362): the channel

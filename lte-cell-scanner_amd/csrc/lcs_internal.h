@@ -401,6 +401,23 @@ struct lcs_ctx : lcs_ctx_queues {
     uint32_t h_pcf_jump[64] = {};
     int pcf_jump_rb = 0;            // the n_rb pcf_jump holds the tables of, 0: none
   } meas_wide;
+  // the PDCCH common search space on that grid (pdcch.hip: lcs_pdcch_wide, lcs_pdcch), allocated by the first call of that stage.
+  // The tables are built on the host (pdcch.h) when the key changes, not per call.
+  struct Pdcch {
+    DevBuf<int> map;                // [3 m_i][3 cfi] PdcMap: n_reg, n_cce, re[576]
+    DevBuf<int16_t> derm;           // [2 sizes][2 levels][192][8]: the de-rate-matching lists
+    DevBuf<uint32_t> jump;          // [2][32]: jump-ahead to the call's reference sequence, and by 1600 clocks for the scrambling
+    DevBuf<int> sf;                 // [n_sf][4] grid rows of every subframe's symbols 0 .. 3 (-1: not read), m_i[10], [n_sf][2] the PCFICH's rows
+    DevBuf<double> llr;             // [LCS_PCFICH_MAX_SF][1152]
+    DevBuf<lcs_pdcch_info> rec;     // [1]
+    DevBuf<lcs_pcfich_info> pcf_rec;   // [1]: the PCFICH's decisions on the call's rows, a record of this stage's own
+    std::vector<int> h_map;         // the host blocks they are uploaded from
+    std::vector<int16_t> h_derm;
+    uint32_t h_jump[64] = {};
+    int h_sf[6 * LCS_PCFICH_MAX_SF + 10] = {};
+    int key[9] = {};                // n_rb, ports, cp_type, id, phich_duration, phich_resource, n_sizes, size[2] of the tables; n_rb 0: none
+    int jump_rb = 0;
+  } pdcch;
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -601,4 +618,9 @@ int lcs_pcfich_stage_grid(lcs_ctx *c, const double *h_grid, size_t n_elem);
 // the PCFICH of the n_sf subframes whose rows (rows[2 g], rows[2 g + 1]: symbols 0 and 1, -1: not read) c->meas_wide.grid holds
 // -> c->meas_wide.pcf_rec
 int lcs_launch_pcfich(lcs_ctx *c, const lcs_cell &cell, const int *rows, int n_sf, int n_rb, int dl_mask);
+// pdcch.hip
+// the resolved configuration of a call (lcs_api.hip: what cfg and the cell say together)
+struct PdcchPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[2], rnti_mask, cfi_force; };
+// rows4 [n_sf][4]: the rows of c->meas_wide.grid that hold symbols 0 .. 3 of every subframe (-1: not read) -> c->pdcch.rec
+int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

@@ -669,6 +669,84 @@ __device__ __forceinline__ unsigned long long vit_retrace_wave(const double *d0,
   return bits;
 }
 #endif
+// ---- the same decoder over n steps, 24 <= n <= 64 (the PDCCH's DCI sizes, pdcch.h).  The forms above stay as they are -- 40 steps,
+// tuned register by register --; these take n at run time and are otherwise the same code: vit_step / vit_lane_step, so the same
+// sums in the same order; the same rotating slots, walked in whole groups of six steps and then the n mod 6 steps left, after which
+// state s sits in slot (lane) rotl6(s, n mod 6); decisions in 2 x 32 bits; no survivor arrays, no scratch.  At n = 40 they return
+// the bits and end metrics of the forms above exactly (tests/test_pdcch_host.py).
+template <bool FAST>
+__host__ __device__ __forceinline__ double vit_end_metric_n(const double *d0, const double *d1, const double *d2, int n, int ss) {
+  double pm[64];
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(ss));      // (as vit_end_metric)
+#endif
+#pragma unroll
+  for (int s = 0; s < 64; ++s) pm[s] = (s == ss) ? 0.0 : INFINITY;
+  const int rem = n % 6, full = n - rem;
+#define VIT_S(K, T) vit_step<K, FAST>(pm, vit_branch(d0[T], d1[T], d2[T]))
+#pragma unroll 1
+  for (int t6 = 0; t6 < full; t6 += 6) { VIT_S(0, t6); VIT_S(1, t6 + 1); VIT_S(2, t6 + 2); VIT_S(3, t6 + 3); VIT_S(4, t6 + 4); VIT_S(5, t6 + 5); }
+  if (rem > 0) VIT_S(0, full);
+  if (rem > 1) VIT_S(1, full + 1);
+  if (rem > 2) VIT_S(2, full + 2);
+  if (rem > 3) VIT_S(3, full + 3);
+  if (rem > 4) VIT_S(4, full + 4);
+#undef VIT_S
+  const int slot = VIT_ROTL6(ss, rem);
+  double fin = INFINITY;
+#pragma unroll
+  for (int s = 0; s < 64; ++s) fin = (s == slot) ? pm[s] : fin;
+  return fin;
+}
+__host__ inline unsigned long long vit_retrace_host_n(const double *d0, const double *d1, const double *d2, int n, int ss, double *end_metric) {
+  double pm[64], nx[64];
+  unsigned long long dec[64];
+  for (int l = 0; l < 64; ++l) { pm[l] = (l == ss) ? 0.0 : INFINITY; dec[l] = 0ull; }
+  for (int t = 0; t < n; ++t) {
+    const int k = t % 6;
+    const VitBranch br = vit_branch(d0[t], d1[t], d2[t]);
+    for (int l = 0; l < 64; ++l) {
+      bool take1;
+      nx[l] = vit_lane_step(vit_lane_desc(VIT_ROTR6(l, k)), pm[l], pm[l ^ (1 << k)], br.d, &take1);
+      dec[l] |= (unsigned long long)(take1 ? 1 : 0) << t;
+    }
+    for (int l = 0; l < 64; ++l) pm[l] = nx[l];
+  }
+  if (end_metric) *end_metric = pm[VIT_ROTL6(ss, n % 6)];
+  unsigned long long bits = 0ull;
+  int s = ss;
+  for (int t = n - 1; t >= 0; --t) { const int l = VIT_TRACE_LANE(s, t); VIT_TRACE_STEP(bits, s, t, dec[l]); }
+  return bits;
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ unsigned long long vit_retrace_wave_n(const double *d0, const double *d1, const double *d2, int n, int ss, int lane) {
+  int desc[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) desc[k] = vit_lane_desc(VIT_ROTR6(lane, k));
+  double pm = (lane == ss) ? 0.0 : INFINITY;
+  unsigned dlo = 0u, dhi = 0u;
+  const int rem = n % 6, full = n - rem;
+#define VIT_R(K, T) do { const VitBranch br = vit_branch(d0[T], d1[T], d2[T]); bool tk;                                     \
+                         pm = vit_lane_step(desc[K], pm, __shfl_xor(pm, 1 << (K)), br.d, &tk);                              \
+                         if ((T) < 32) dlo |= (tk ? 1u : 0u) << ((T) & 31); else dhi |= (tk ? 1u : 0u) << ((T) & 31); } while (0)
+#pragma unroll 1
+  for (int t6 = 0; t6 < full; t6 += 6) { VIT_R(0, t6); VIT_R(1, t6 + 1); VIT_R(2, t6 + 2); VIT_R(3, t6 + 3); VIT_R(4, t6 + 4); VIT_R(5, t6 + 5); }
+  if (rem > 0) VIT_R(0, full);
+  if (rem > 1) VIT_R(1, full + 1);
+  if (rem > 2) VIT_R(2, full + 2);
+  if (rem > 3) VIT_R(3, full + 3);
+  if (rem > 4) VIT_R(4, full + 4);
+#undef VIT_R
+  unsigned long long bits = 0ull;
+  int s = __builtin_amdgcn_readfirstlane(ss);
+  for (int t = n - 1; t >= 0; --t) {
+    const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)(t < 32 ? dlo : dhi), VIT_TRACE_LANE(s, t));
+    bits |= (unsigned long long)((s >> 5) & 1) << t;
+    s = ((s << 1) & 63) | (int)((w >> (t & 31)) & 1u);
+  }
+  return bits;
+}
+#endif
 // CRC-16 (x^16+x^12+x^5+1, zero init) of the 24 payload bits against the received 16, with the antenna-port mask
 // (ref src/lte_lib.cpp:637-663, src/searcher.cpp:1628-1636)
 __host__ __device__ __forceinline__ int pbch_crc_ok(unsigned long long bits, int n_ports) {

@@ -538,8 +538,79 @@ def pcfich_symbols(n_id_cell, subframe, cfi):
     return ((1 - 2.0 * b[0::2]) + 1j * (1 - 2.0 * b[1::2])) / np.sqrt(2.0)
 
 
+def pdcch_layout(n_id_cell, n_rb, n_ports, cp_normal, cfi, phich_duration_ext=0, phich_res=2, mi=1):
+    """The control region of a subframe's first slot (36.211 6.2.4, 6.9.3, 6.8.5) -> (regs, n_cce, phich, cols): regs the PDCCH's
+    resource-element groups (k', l') in mapping order (sorted by k', then l'), n_cce = len(regs) // 9, phich the groups kept for the
+    PHICH (phich_res = the MIB's code: Ng = 1/6, 1/2, 1, 2; mi the m_i of 36.211 table 6.9-1, 1 in FDD), cols(k', l') the group's
+    four columns.  Symbol 0 has two groups per resource block (the four of six columns that no CRS of ports 0 / 1 may take), symbol
+    1 three (two with 4 ports), symbol 2 three, symbol 3 (n_rb <= 10 only) three, or two with the extended CP."""
+    n_ctrl = int(cfi) + (1 if n_rb <= 10 else 0)
+    if phich_duration_ext and n_ctrl < 3:
+        raise ValueError("pdcch_layout: the extended PHICH duration needs three control symbols")
+    per = lambda l: 2 if (l == 0 or (l == 1 and n_ports == 4) or (l == 3 and not cp_normal)) else 3
+    sym = [[12 * n + (6 if per(l) == 2 else 4) * j for n in range(n_rb) for j in range(per(l))] for l in range(n_ctrl)]
+    pcf = {(6 * (n_id_cell % (2 * n_rb)) + 6 * ((i * n_rb) // 2)) % (12 * n_rb) for i in range(4)}
+    free = [[k for k in sym[l] if l or k not in pcf] for l in range(n_ctrl)]
+    num, den = ((1, 6), (1, 2), (1, 1), (2, 1))[phich_res]
+    units = int(mi) * -(-(num * n_rb) // (8 * den))
+    phich = []
+    for mp in range(units):
+        for i in range(3):
+            l = i if phich_duration_ext else 0
+            nl = len(free[l])
+            phich.append((free[l][((n_id_cell * nl) // len(free[0]) + mp + (i * nl) // 3) % nl], l))
+    if len(set(phich)) != len(phich):
+        raise ValueError("pdcch_layout: the PHICH units do not fit their symbol")
+    taken = set(phich)
+    regs = sorted((k, l) for l in range(n_ctrl) for k in free[l] if (k, l) not in taken)
+
+    def cols(k, l):
+        return np.array([k + o for o in range(6) if (k + o) % 3 != n_id_cell % 3] if per(l) == 2 else [k, k + 1, k + 2, k + 3])
+    return regs, len(regs) // 9, phich, cols
+
+
+def dci_bits(payload, rnti, L):
+    """the 72 L bits of one DCI (36.212 5.3.3): payload, CRC-16 XORed with the RNTI MSB first, tail-biting code, rate matching"""
+    a = np.asarray(payload, np.uint8)
+    p = crc16(a) ^ np.array([(int(rnti) >> (15 - i)) & 1 for i in range(16)], np.uint8)
+    return conv_ratematch(conv_encode_tailbite(np.concatenate([a, p])), 72 * int(L))
+
+
+def pdcch_interleave(n):
+    """w: the order in which the sub-block interleaver of 36.212 5.1.4.2.1 reads n quadruplets (32 columns, the nulls in front)"""
+    rows = -(-n // 32)
+    y = np.concatenate([np.full(32 * rows - n, -1, np.int64), np.arange(n)]).reshape(rows, 32)[:, _PERM].T.reshape(-1)
+    return y[y >= 0]
+
+
+def pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, dcis, fill=0.0, rng=None, phich_duration_ext=0, phich_res=2, mi=1):
+    """What the PDCCH puts on the control region of a subframe (36.211 6.8): dcis = [dict(rnti, bits, L, cce)] multiplexed CCE by CCE
+    (an unused CCE is silent, or with probability `fill` random bits), scrambled with c_init = subframe 2^9 + n_id_cell, QPSK,
+    quadruplets interleaved and shifted by n_id_cell, each through the transmit diversity onto its group.
+    -> (n_ctrl, [(l, columns [4], values [n_ports][4])])"""
+    regs, n_cce, _, cols = pdcch_layout(n_id_cell, n_rb, n_ports, cp_normal, cfi, phich_duration_ext, phich_res, mi)
+    n = len(regs)
+    stream, used = np.zeros(8 * n, np.uint8), np.zeros(n, bool)
+    for d in dcis:
+        L, cce = int(d["L"]), int(d["cce"])
+        if cce < 0 or cce + L > n_cce or used[9 * cce:9 * (cce + L)].any():
+            raise ValueError("pdcch_region: a DCI outside the subframe's CCEs, or on top of another")
+        stream[72 * cce:72 * (cce + L)] = dci_bits(d["bits"], d["rnti"], L)
+        used[9 * cce:9 * (cce + L)] = True
+    if fill > 0:
+        for cce in range(n_cce):
+            if not used[9 * cce] and rng.random() < fill:
+                stream[72 * cce:72 * (cce + 1)] = rng.integers(0, 2, 72)
+                used[9 * cce:9 * (cce + 1)] = True
+    b = stream ^ _pn(subframe * 512 + n_id_cell, 8 * n)
+    z = (((1 - 2.0 * b[0::2]) + 1j * (1 - 2.0 * b[1::2])) / np.sqrt(2.0)).reshape(n, 4) * used[:, None]
+    wbar = pdcch_interleave(n)[(np.arange(n) + n_id_cell) % n]
+    n_ctrl = int(cfi) + (1 if n_rb <= 10 else 0)
+    return n_ctrl, [(l, cols(k, l), _tx_diversity(z[wbar[i]], n_ports)) for i, (k, l) in enumerate(regs)]
+
+
 def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
-                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None):
+                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None):
     """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,
     CP lengths R * {10, 9, 32}), n_frames * 19200 * R samples from the boundary of frame sfn0.  The 72 centre subcarriers carry what
     cell_waveform puts there -- PSS, SSS, PBCH (the MIB says n_rb_dl: n_rb where that is an LTE bandwidth, else 50), CRS and load --
@@ -548,9 +619,17 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
     tdd as for cell_waveform.  A function of its own: its draws from rng are not cell_waveform's.
     cfi: None sends no PCFICH (its elements carry load like any other).  An int 1 .. 3, or a callable (frame, subframe) -> 1 .. 3 with
     frame counting from 0 in this waveform, reserves the 16 PCFICH elements of symbol 0 of every subframe that is sent and puts the
-    scrambled codeword there through the PBCH's precoding."""
+    scrambled codeword there through the PBCH's precoding.
+    pdcch: None sends no PDCCH.  A callable (frame, subframe) -> [dict(rnti, bits, L, cce)] (it needs cfi) plants those DCIs in the
+    control region of every subframe that is sent (pdcch_region: the MIB's PHICH configuration, m_i = phich_mi[subframe] or 1); the
+    rest of the control region beside the CRS and the PCFICH stays silent -- the PHICH's groups are kept free --, except that
+    pdcch_fill puts random QPSK on that share of the unused CCEs, standing in for UE-specific traffic.  Without pdcch nothing more is
+    drawn from rng."""
     rng = rng or np.random.default_rng(0)
     R, n_rb = int(R), int(n_rb)
+    if pdcch is not None and cfi is None:
+        raise ValueError("cell_waveform_wide: pdcch needs cfi")
+    ctrl_n, ctrl = 0, []
     n_fft, nc, c0 = 128 * R, 12 * n_rb, 6 * n_rb - 36          # c0: the first of the 72 centre columns
     if R not in (1, 2, 4, 8, 16) or not 6 <= n_rb or 12 * n_rb >= n_fft:
         raise ValueError("cell_waveform_wide: R in 1, 2, 4, 8, 16 and 6 <= n_rb with 12 n_rb < 128 R")
@@ -632,6 +711,14 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
                     value = cfi(fr, slot >> 1) if callable(cfi) else cfi
                     grid[:, pcfich_cols] = _tx_diversity(pcfich_symbols(n_id_cell, slot >> 1, value), n_ports)
                     reserved[pcfich_cols] = True
+                    if pdcch is not None:
+                        ctrl_n, ctrl = pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, pdcch(fr, slot >> 1), pdcch_fill, rng,
+                                                    phich_duration_ext, phich_res, 1 if phich_mi is None else phich_mi[slot >> 1])
+                if pdcch is not None and not (slot & 1) and sym < ctrl_n and not is_sync:
+                    reserved[:] = True
+                    for l, cols, vals in ctrl:
+                        if l == sym:
+                            grid[:, cols] = vals
                 free = np.flatnonzero(~reserved)
                 on = free[rng.random(free.size) < load]
                 d = ((1 - 2.0 * rng.integers(0, 2, on.size)) + 1j * (1 - 2.0 * rng.integers(0, 2, on.size))) / np.sqrt(2.0)
@@ -659,7 +746,8 @@ def make_signal_wide(rng, fc, cd, R, n_rb, n_cap):
     n_frames = int(np.ceil((n_cap / (R * k_factor) + t0) / 19200)) + 1
     w = cell_waveform_wide(n_frames, cd["n_id_1"], cd["n_id_2"], R, n_rb, cd.get("cp_normal", True), cd.get("n_ports", 2), cd.get("load", 0.5), rng,
                            cd.get("port_gains"), tdd=cd.get("tdd"), n_rb_dl=cd.get("n_rb_dl"), phich_duration_ext=cd.get("phich_duration_ext", 0),
-                           phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))), cfi=cd.get("cfi"))
+                           phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))), cfi=cd.get("cfi"),
+                           pdcch=cd.get("pdcch"), pdcch_fill=cd.get("pdcch_fill", 0.0), phich_mi=cd.get("phich_mi"))
     y = frac_resample(w, t0 * R + n / k_factor)
     y = y * np.exp(2j * np.pi * f_off * n / (FS * R * k_factor))
     g = 10 ** (cd.get("gain_db", 0.0) / 20)
