@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -551,6 +551,53 @@ class Searcher:
         self._chk(self._lib.lcs_pdcch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
+
+    def pdsch_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                   cfg=None, pdsch_cfg=None, n_cap=None, want_pdcch: bool = False):
+        """The transport blocks behind the format 1A grants of the common search space (SI, paging, random-access responses) of every
+        downlink subframe from the same samples (lcs_pdsch_wide: every row of the subframes of the mask is transformed; PCFICH,
+        PDCCH, the grants' soft bits and the turbo decoder run on the device).  cfg: a capi.PdcchCfg as pdcch_wide's; pdsch_cfg: a
+        capi.PdschCfg or None -> PdschInfo, or (PdschInfo, PdcchInfo) with want_pdcch"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out, pd = capi.PdschInfo(), capi.PdcchInfo()
+        self._chk(self._lib.lcs_pdsch_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg),
+                                           C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None), "lcs_pdsch_wide")
+        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return (out, pd) if want_pdcch else out
+
+    def pdsch(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None, pdsch_cfg=None, want_pdcch: bool = False):
+        """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
+        (extract_tfg_wide's) (lcs_pdsch) -> PdschInfo, or (PdschInfo, PdcchInfo) with want_pdcch"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out, pd = capi.PdschInfo(), capi.PdcchInfo()
+        self._chk(self._lib.lcs_pdsch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg),
+                                      C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None), "lcs_pdsch")
+        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return (out, pd) if want_pdcch else out
+
+    def pdsch_last_soft(self, subframe: int, which: int, n: int):
+        """the first n soft bits of the which-th grant the last pdsch / pdsch_wide call followed in grid subframe `subframe`
+        (lcs_pdsch_last_soft)"""
+        out = np.zeros(max(int(n), 1))
+        self._chk(self._lib.lcs_pdsch_last_soft(self._h, int(subframe), int(which), _dp(out), int(n)), "lcs_pdsch_last_soft")
+        return out[:int(n)]
+
+    def turbo_decode(self, d, K: int, F: int = 0, max_iter: int = 0):
+        """The stage's turbo decoder alone (lcs_turbo_decode): d [3][K + 4] de-rate-matched values, positive means 0
+        -> (bits [K] uint8 with the fillers zero, iterations run, whether the CRC24A over bits F .. K - 1 is zero)"""
+        d = np.ascontiguousarray(d, np.float64)
+        if d.shape != (3, int(K) + 4):
+            raise ValueError("d is [3][K + 4]")
+        bits = np.zeros(max(int(K), 1), np.uint8)
+        n_iter, ok = C.c_int(0), C.c_int(0)
+        self._chk(self._lib.lcs_turbo_decode(self._h, _dp(d), int(K), int(F), int(max_iter), bits.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n_iter), C.byref(ok)),
+                  "lcs_turbo_decode")
+        return bits[:int(K)], n_iter.value, bool(ok.value)
 
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route

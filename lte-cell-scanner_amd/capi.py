@@ -393,11 +393,144 @@ def dci_1a_fields(bits, n_rb: int, tdd: bool = False) -> dict:
     return out
 
 
+# ---- the PDSCH behind the grants of the common search space (include/lcs.h: lcs_pdsch_info) ----
+PDSCH_MAX_BLOCKS, PDSCH_MAX_FORCED, PDSCH_PAYLOAD, PDSCH_N_STATUS = 32, 4, 280, 10
+PDSCH_OK, PDSCH_CRC, PDSCH_DISTRIBUTED, PDSCH_MCS, PDSCH_ROWS, PDSCH_SPECIAL, PDSCH_SILENT, PDSCH_BAD_ALLOC, PDSCH_NO_CFI = range(1, 10)
+PDSCH_STATUS = {0: "none", 1: "ok", 2: "crc", 3: "distributed", 4: "mcs", 5: "rows", 6: "special", 7: "silent", 8: "bad_alloc", 9: "no_cfi"}
+# 36.213 table 7.1.7.2.1-1, columns N_PRB = 2 and 3, I_TBS 0 .. 26: written from memory of the standard, as pdsch.h's copy (what pins
+# both is said there)
+_TBS_1A = [[32, 56, 72, 104, 120, 144, 176, 208, 256, 296, 328, 376, 440, 488, 552, 600, 632, 696, 776, 840, 904, 1000, 1064, 1128, 1192, 1256, 1480],
+           [56, 88, 144, 176, 208, 224, 256, 328, 392, 456, 504, 584, 680, 744, 840, 904, 968, 1064, 1160, 1288, 1384, 1480, 1608, 1736, 1800, 1864, 2216]]
+
+
+def tbs_1a(mcs: int, tpc: int) -> int:
+    """the transport block size of a format 1A grant with SI-, P- or RA-RNTI (36.213 7.1.7.2.1): I_TBS = mcs <= 26, column N_PRB = 2
+    where the low TPC bit is 0, else 3"""
+    return _TBS_1A[int(tpc) & 1][int(mcs)]
+
+
+class PdschGrant(C.Structure):
+    _fields_ = [("subframe", C.c_int32), ("rnti", C.c_int32), ("rb_start", C.c_int32), ("n_prb", C.c_int32), ("tbs", C.c_int32), ("rv", C.c_int32)]
+
+
+class PdschCfg(C.Structure):
+    """lcs_pdsch_cfg.  PdschCfg.make(i_1a, max_iter, rnti_mask, forced): zeros are the defaults; forced: up to four dicts or tuples
+    (subframe, rnti, rb_start, n_prb, tbs, rv) that replace the PDCCH's grants"""
+    _fields_ = [("i_1a", C.c_int32), ("max_iter", C.c_int32), ("rnti_mask", C.c_int32), ("n_forced", C.c_int32), ("forced", PdschGrant * PDSCH_MAX_FORCED)]
+
+    @classmethod
+    def make(cls, i_1a=0, max_iter=0, rnti_mask=0, forced=()) -> "PdschCfg":
+        forced = list(forced)
+        if len(forced) > PDSCH_MAX_FORCED:
+            raise ValueError("PdschCfg: at most four forced grants")
+        o = cls()
+        o.i_1a, o.max_iter, o.rnti_mask, o.n_forced = int(i_1a), int(max_iter), int(rnti_mask), len(forced)
+        for i, g in enumerate(forced):
+            v = [g[k] for k in ("subframe", "rnti", "rb_start", "n_prb", "tbs", "rv")] if isinstance(g, dict) else list(g)
+            o.forced[i] = PdschGrant(*[int(x) for x in v])
+        return o
+
+
+class PdschBlock(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("subframe", "slot", "rnti", "kind", "rb_start", "n_prb", "mcs", "rv", "tbs", "n_re", "K", "F", "n_iter", "status")] + \
+               [("payload", C.c_uint8 * PDSCH_PAYLOAD)]
+
+
+class PdschInfo(C.Structure):
+    """lcs_pdsch_info: the transport blocks behind the format 1A grants of every subframe of a full-bandwidth grid (include/lcs.h:
+    lcs_pdsch_wide, lcs_pdsch)"""
+    _fields_ = [(k, C.c_int32) for k in ("n_sf", "n_blocks", "n_ok", "n_si", "n_paging", "n_ra", "n_overflow", "dl_mask", "n_rb", "n_ports")] + \
+               [("n_status", C.c_int32 * PDSCH_N_STATUS), ("block", PdschBlock * PDSCH_MAX_BLOCKS)]
+
+    def copy(self) -> "PdschInfo":
+        o = PdschInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(PdschInfo))
+        return o
+
+    def blocks(self) -> list:
+        """the listed grants as dicts: the block's fields, kind and status as words, crc_ok, and bytes = the transport block (tbs / 8
+        bytes rounded up, MSB first; empty unless the block was decoded)"""
+        out = []
+        for i in range(min(max(int(self.n_blocks), 0), PDSCH_MAX_BLOCKS)):
+            b = self.block[i]
+            d = {k: int(getattr(b, k)) for k, _ in PdschBlock._fields_[:14]}
+            d["kind"] = {1: "si", 2: "paging", 4: "ra"}.get(b.kind, "other")
+            d["status"] = PDSCH_STATUS.get(b.status, "?")
+            d["crc_ok"] = b.status == PDSCH_OK
+            d["bytes"] = bytes(b.payload[:(b.tbs + 7) // 8]) if b.status in (PDSCH_OK, PDSCH_CRC) else b""
+            out.append(d)
+        return out
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"PdschInfo(n_sf={self.n_sf}, n_blocks={self.n_blocks}, n_ok={self.n_ok}, n_si={self.n_si}, n_paging={self.n_paging}, n_ra={self.n_ra})"
+
+
+assert C.sizeof(PdschCfg) == 112 and C.sizeof(PdschBlock) == 336 and C.sizeof(PdschInfo) == 10832
+
+
+def sib1_fields(payload):
+    """The fields of a BCCH-DL-SCH-Message that carries SystemInformationBlockType1, read in UPER up to and including tdd-Config
+    (written from memory of 36.331; synth.sib1_message is the matching writer: a convenience, not part of any kernel's rule).
+    payload: bytes (MSB first) or a sequence of bits.  -> dict(plmns [(mcc, mnc, reserved)], tac, cell_id, barred, intra_freq, csg,
+    csg_id, q_rx_lev_min and q_rx_lev_min_offset (the fields' values: dBm and dB are twice them), p_max, band, sched [(periodicity in
+    radio frames, [SIB numbers])],
+    tdd (subframeAssignment, specialSubframePatterns) or None, si_window (ms), value_tag), or None for a message that is not SIB1 or
+    runs out of bits."""
+    bits = [(byte >> (7 - i)) & 1 for byte in payload for i in range(8)] if isinstance(payload, (bytes, bytearray)) else [int(b) & 1 for b in payload]
+    pos = [0]
+
+    def take(n):
+        if pos[0] + n > len(bits):
+            raise IndexError
+        v = 0
+        for b in bits[pos[0]:pos[0] + n]:
+            v = (v << 1) | b
+        pos[0] += n
+        return v
+    try:
+        if take(1) != 0 or take(1) != 1:
+            return None
+        has_pmax, has_tdd, _ext = take(1), take(1), take(1)
+        has_csg_id = take(1)
+        plmns, mcc = [], None
+        for _ in range(take(3) + 1):
+            if take(1):
+                mcc = "".join(str(take(4)) for _ in range(3))
+            mnc = "".join(str(take(4)) for _ in range(2 + take(1)))
+            plmns.append((mcc, mnc, take(1) == 0))
+        if len(plmns) > 6 or plmns[0][0] is None:
+            return None
+        out = dict(plmns=plmns, tac=take(16), cell_id=take(28), barred=take(1) == 0, intra_freq=take(1) == 0, csg=bool(take(1)))
+        out["csg_id"] = take(27) if has_csg_id else None
+        has_off = take(1)
+        out["q_rx_lev_min"] = take(6) - 70
+        out["q_rx_lev_min_offset"] = take(3) + 1 if has_off else None
+        out["p_max"] = take(6) - 30 if has_pmax else None
+        out["band"] = take(6) + 1
+        sched = []
+        for _ in range(take(5) + 1):
+            per = take(3)
+            sibs = []
+            for _ in range(take(5)):
+                if take(1):
+                    return None          # an extended SIB type: beyond this reading
+                sibs.append(take(4) + 3)
+            sched.append((8 << per if per < 7 else None, sibs))
+        out["sched"] = sched
+        out["tdd"] = (take(3), take(4)) if has_tdd else None
+        w = take(3)
+        out["si_window"] = (1, 2, 5, 10, 15, 20, 40)[w] if w < 7 else None
+        out["value_tag"] = take(5)
+        return out
+    except IndexError:
+        return None
+
+
 EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -482,6 +615,12 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_pdcch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
         L.lcs_pdcch.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
+    if hasattr(L, "lcs_pdsch_wide"):      # (likewise)
+        L.lcs_pdsch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(PdcchCfg), C.POINTER(PdschCfg), C.POINTER(PdschInfo), C.POINTER(PdcchInfo)]
+        L.lcs_pdsch.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchCfg), C.POINTER(PdschCfg), C.POINTER(PdschInfo), C.POINTER(PdcchInfo)]
+        L.lcs_pdsch_last_soft.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
+        L.lcs_turbo_decode.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

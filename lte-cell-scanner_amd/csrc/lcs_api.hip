@@ -15,6 +15,7 @@
 #include "cell_meas_wide.h"
 #include "pcfich.h"
 #include "pdcch.h"
+#include "pdsch.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
 
@@ -1300,6 +1301,147 @@ int lcs_pdcch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, i
   if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
   if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
   return pdcch_finish(c, out);
+}
+
+// ---- the PDSCH behind the grants of that search space (pdsch.hip, pdsch.h): the same blocks and the same isolation
+namespace {
+int pdsch_resolve(lcs_ctx *c, const char *who, const lcs_pdcch_cfg *cfg, const PdcchPlan &plan, const lcs_pdsch_cfg *pc, int n_ofdm, int n_symb, int n_rb, PdschPlan *p) {
+  static const lcs_pdsch_cfg zero = {};
+  if (!pc) pc = &zero;
+  if (pc->max_iter < 0 || pc->max_iter > 16) return wide_refused(c, who, "max_iter is outside 1 .. 16 (0: 8)");
+  if (pc->rnti_mask < 0 || pc->rnti_mask > 7) return wide_refused(c, who, "the PDSCH rnti_mask is outside 0 .. 7");
+  if (pc->i_1a < 0 || pc->i_1a >= plan.n_sizes) return wide_refused(c, who, "i_1a is outside the PDCCH configuration's sizes");
+  if (pc->n_forced < 0 || pc->n_forced > LCS_PDSCH_MAX_FORCED) return wide_refused(c, who, "n_forced is outside 0 .. 4");
+  p->i_1a = pc->i_1a; p->max_iter = pc->max_iter ? pc->max_iter : 8; p->rnti_mask = pc->rnti_mask ? pc->rnti_mask : 7; p->n_forced = pc->n_forced;
+  p->tdd = 0;
+  for (int i = 0; i < 10; ++i) p->tdd = p->tdd || cfg->phich_mi[i] >= 0;
+  const int n_sf = pcf_n_sf(n_ofdm, n_symb);
+  for (int f = 0; f < LCS_PDSCH_MAX_FORCED; ++f) {
+    p->forced[f] = pc->forced[f];
+    if (f >= pc->n_forced) continue;
+    const lcs_pdsch_grant &g = pc->forced[f];
+    if (g.subframe < 0 || g.subframe >= n_sf) return wide_refused(c, who, "a forced grant lies outside the grid's subframes");
+    if (g.rb_start < 0 || g.n_prb < 1 || g.rb_start > n_rb - g.n_prb) return wide_refused(c, who, "a forced grant lies outside the grid's resource blocks");
+    if (g.rnti < 1 || g.rnti > 65535) return wide_refused(c, who, "a forced grant's rnti is outside 1 .. 65535");
+    if (g.rv < 0 || g.rv > 3) return wide_refused(c, who, "a forced grant's rv is outside 0 .. 3");
+    if (g.tbs < 1 || g.tbs > PDS_MAX_K - 24) return wide_refused(c, who, "a forced grant's tbs is outside 1 .. 2216");
+    int same = 0;
+    for (int u = 0; u < f; ++u) same += pc->forced[u].subframe == g.subframe;
+    if (same >= PDS_GRANTS) return wide_refused(c, who, "more than two forced grants in one subframe");
+  }
+  return LCS_OK;
+}
+// pdcch_plan with every row of a subframe that lies whole inside the grid: sfrow[g] = the place of its symbol 0 (in *list, or the row
+// itself), else -1
+int pdsch_plan(const lcs_cell *cell, const lcs_pdcch_cfg *cfg, const PdcchPlan &p, int n_ofdm, int n_rb, int dl_mask, int *rows4, int *sfrow, std::vector<int> *list) {
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_sf = pcf_n_sf(n_ofdm, n_symb), n_max = pdc_n_ctrl_max(n_rb);
+  bool tdd = false;
+  for (int i = 0; i < 10; ++i) tdd = tdd || cfg->phich_mi[i] >= 0;
+  for (int g = 0; g < n_sf; ++g) {
+    for (int l = 0; l < 4; ++l) rows4[4 * g + l] = -1;
+    sfrow[g] = -1;
+    const int r0 = 2 * g * n_symb, sf = g % 10;
+    if (!((dl_mask >> sf) & 1) || r0 + n_max - 1 >= n_ofdm) continue;
+    if (tdd && p.phich_duration == 2 && (sf == 1 || sf == 6)) continue;
+    const bool whole = r0 + 2 * n_symb <= n_ofdm && !(tdd && (sf == 1 || sf == 6));
+    const int first = list ? (int)list->size() : r0;
+    if (list) for (int l = 0; l < (whole ? 2 * n_symb : n_max); ++l) list->push_back(r0 + l);
+    for (int l = 0; l < n_max; ++l) rows4[4 * g + l] = first + l;
+    if (r0 + 2 * n_symb <= n_ofdm) sfrow[g] = whole ? first : -1;
+  }
+  return n_sf;
+}
+int pdsch_finish(lcs_ctx *c, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+  HIPCHK(c, hipMemcpyAsync(out, c->pdsch.rec, sizeof(lcs_pdsch_info), hipMemcpyDeviceToHost, c->stream));
+  if (pdcch_out) HIPCHK(c, hipMemcpyAsync(pdcch_out, c->pdsch.pdc.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_pdsch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                   int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdsch_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  PdcchPlan plan;
+  PdschPlan ps;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  if ((rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_rb, &ps))) return rc;
+  int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
+  std::vector<int> list;
+  const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, &list);
+  std::vector<double> ideal(list.size());
+  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
+  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps))) return rc;
+  return pdsch_finish(c, out, pdcch_out);
+}
+
+int lcs_pdsch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
+              lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdsch";
+  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  int rc;
+  PdcchPlan plan;
+  PdschPlan ps;
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan)) || (rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, n_symb, n_rb, &ps))) return rc;
+  int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
+  const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, nullptr);
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
+  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps))) return rc;
+  return pdsch_finish(c, out, pdcch_out);
+}
+
+int lcs_pdsch_last_soft(lcs_ctx *c, int subframe, int which, double *llr_out, int n) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdsch_last_soft";
+  if (!llr_out) return wide_refused(c, who, "a null pointer");
+  const lcs_ctx::Pdsch &p = c->pdsch;
+  if (subframe < 0 || subframe >= p.last_n_sf || which < 0 || which >= PDS_GRANTS || n < 0 || (size_t)n > p.last_stride)
+    return wide_refused(c, who, "no such grant slot of the last call, or more soft bits than a slot holds");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the slot's job as the plan left it: only a grant that was followed has soft bits of this call, G of them
+  PdsJob job;
+  HIPCHK(c, hipMemcpyAsync(&job, reinterpret_cast<const PdsJob *>(p.job.get()) + (PDS_GRANTS * subframe + which), sizeof(job), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (job.status != LCS_PDSCH_FOLLOW || n > job.G) return wide_refused(c, who, "that grant slot was not followed in the last call, or holds fewer soft bits");
+  HIPCHK(c, hipMemcpyAsync(llr_out, p.llr.get() + (size_t)(PDS_GRANTS * subframe + which) * p.last_stride, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+int lcs_turbo_decode(lcs_ctx *c, const double *d, int K, int F, int max_iter, uint8_t *bits_out, int *n_iter_out, int *crc_ok_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_turbo_decode";
+  if (!d || !bits_out || !n_iter_out || !crc_ok_out) return wide_refused(c, who, "a null pointer");
+  if (pds_k_index(K) < 0) return wide_refused(c, who, "K is not one of the 127 turbo block sizes up to 2240");
+  if (F < 0 || F >= K) return wide_refused(c, who, "F is outside 0 .. K - 1");
+  if (max_iter < 0 || max_iter > 16) return wide_refused(c, who, "max_iter is outside 1 .. 16 (0: 8)");
+  int rc, res[2];
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_launch_turbo(c, d, K, F, max_iter ? max_iter : 8))) return rc;
+  HIPCHK(c, hipMemcpyAsync(res, c->pdsch.res, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(bits_out, c->pdsch.hard, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (res[1] != LCS_PDSCH_OK && res[1] != LCS_PDSCH_CRC) std::memset(bits_out, 0, (size_t)K);
+  *n_iter_out = res[0];
+  *crc_ok_out = res[1] == LCS_PDSCH_OK;
+  return LCS_OK;
 }
 
 // chan_est of decode_mib as a stage of its own (ref src/searcher.cpp:1369-1477, ce_interp_hex :1223-1362): the channel

@@ -418,6 +418,35 @@ struct lcs_ctx : lcs_ctx_queues {
     int key[9] = {};                // n_rb, ports, cp_type, id, phich_duration, phich_resource, n_sizes, size[2] of the tables; n_rb 0: none
     int jump_rb = 0;
   } pdcch;
+  // the PDSCH behind that search space's grants (pdsch.hip: lcs_pdsch_wide, lcs_pdsch, lcs_turbo_decode), allocated by the first call
+  // of that stage.  The tables are built on the host (pdsch.h) once, a forced grant's when its (K, F) changes; not per call.
+  struct Pdsch {
+    Pdcch pdc;                      // the PDCCH's blocks of this stage's own: the PDCCH stage's are not touched
+    DevBuf<int> tabs;               // transport block sizes [2][27], QPP (f1, f2) [127][2]
+    DevBuf<int> heads;              // PdsTabHead [2 * 27 + 4]
+    DevBuf<int16_t> rank;           // [2 * 27 + 4][3][2244]: the de-rate-matching ranks
+    DevBuf<uint32_t> jump;          // [320]: to the reference sequence, by 1600 clocks, by 160 2^b clocks
+    DevBuf<uint32_t> x1s;           // [256]: the Gold sequence's first register 1600 + 160 j clocks on
+    DevBuf<int> sfrow;              // [n_sf]: the grid row of symbol 0 of every subframe that is there whole, else -1
+    DevBuf<lcs_pdsch_block> blk;    // [n_sf][2]: the plan's blocks
+    DevBuf<int> job;                // PdsJob [n_sf][2]
+    DevBuf<int> res;                // [n_sf][2][2]: n_iter, status
+    DevBuf<uint8_t> hard;           // [n_sf][2][2240]: the decisions
+    DevBuf<double> llr;             // [n_sf][2][2 * 12 n_rb * 14]
+    DevBuf<double> ws;              // [n_sf][2][32][8][72]: the forward metrics of the windows
+    DevBuf<double> din;             // [3][2244]: lcs_turbo_decode's input
+    DevBuf<lcs_pdsch_info> rec;     // [1]
+    std::vector<int> h_tabs, h_heads;   // the host blocks they are uploaded from
+    std::vector<int16_t> h_rank;
+    std::vector<double> h_din;
+    uint32_t h_jump[320] = {}, h_x1s[256] = {};
+    int h_sfrow[LCS_PCFICH_MAX_SF] = {}, h_job[32] = {};
+    int forced_key[LCS_PDSCH_MAX_FORCED][2] = {};   // K, F + 1 of the forced grants' rank tables; K 0: none
+    bool tables_ready = false;
+    int jump_rb = 0;
+    size_t last_stride = 0;         // of llr in the last call, and its subframes: lcs_pdsch_last_soft
+    int last_n_sf = 0;
+  } pdsch;
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -623,4 +652,13 @@ int lcs_launch_pcfich(lcs_ctx *c, const lcs_cell &cell, const int *rows, int n_s
 struct PdcchPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[2], rnti_mask, cfi_force; };
 // rows4 [n_sf][4]: the rows of c->meas_wide.grid that hold symbols 0 .. 3 of every subframe (-1: not read) -> c->pdcch.rec
 int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
+// the same into the blocks p (the PDSCH stage keeps a set of its own for the grants it follows) -> p.rec
+int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
+// pdsch.hip
+struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; };
+// the PCFICH and PDCCH of rows4 into c->pdsch.pdc, then the grants' blocks -> c->pdsch.rec.  sfrow [n_sf]: the row of c->meas_wide.grid
+// that holds symbol 0 of every subframe whose rows are all there, else -1
+int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps);
+// d [3][K + 4] from the host through the decode kernel -> c->pdsch.res[0 .. 1], c->pdsch.hard[0 .. K - 1]
+int lcs_launch_turbo(lcs_ctx *c, const double *h_d, int K, int F, int max_iter);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

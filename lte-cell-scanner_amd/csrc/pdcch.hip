@@ -143,7 +143,10 @@ __global__ __launch_bounds__(256) void k_pdcch_fin(lcs_pdcch_info *__restrict__ 
 
 // ------------------------------------------------------------------ launcher
 int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan) {
-  lcs_ctx::Pdcch &p = c->pdcch;
+  return lcs_launch_pdcch_in(c, c->pdcch, cell, rows4, n_sf, n_rb, dl_mask, plan);
+}
+// the same into the blocks p: the stage's own, or those the PDSCH stage keeps for its grants (pdsch.hip)
+int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan) {
   lcs_ctx::MeasWide &w = c->meas_wide;
   int rc;
   if (n_sf <= 0 || n_sf > PCF_MAX_SF) { c->err = "pdcch: no such number of subframes"; return LCS_ERR_BAD_ARG; }

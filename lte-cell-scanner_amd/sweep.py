@@ -207,7 +207,7 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
-                     carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None):
+                     carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -226,6 +226,9 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     the PCFICH), and entry k is (CellMeasWide, PdcchInfo) -- (CellMeasWide, PcfichInfo, PdcchInfo) with pcfich=True.  True takes the
     sizes of capi.dci_common_sizes for the cell's bandwidth and the searcher's duplex mode; in TDD with a known uplink-downlink
     configuration (tdd_config = 0 .. 6) the m_i of capi.tdd_phich_mi are passed, else FDD's.
+    pdsch=True (or a capi.PdschCfg) also follows the format 1A grants of that search space into the PDSCH (Searcher.pdsch_wide, with
+    the PDCCH configuration that pdcch names or, without one, its defaults) from the same buffer, mask and slots: a dict cell gets
+    cell["pdsch"] (a PdschInfo, or None as for the PDCCH), and the PdschInfo is appended to entry k's tuple.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -318,6 +321,18 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                 if d is not None:
                     d["pdcch"] = pd
                 rec = (rec if isinstance(rec, tuple) else (rec,)) + (pd,)
+            if pdsch:
+                ps = None
+                if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                    cfg = pdcch
+                    if cfg is True or not cfg:
+                        tdd = searcher.duplex != capi.DUPLEX_FDD
+                        cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
+                    ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg,
+                                             None if pdsch is True else pdsch, n_cap=n_cap)
+                if d is not None:
+                    d["pdsch"] = ps
+                rec = (rec if isinstance(rec, tuple) else (rec,)) + (ps,)
             row.append(rec)
         out.append(row)
     return out

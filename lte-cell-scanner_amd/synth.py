@@ -609,8 +609,192 @@ def pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, dcis, fill=
     return n_ctrl, [(l, cols(k, l), _tx_diversity(z[wbar[i]], n_ports)) for i, (k, l) in enumerate(regs)]
 
 
+# ---- the PDSCH behind a format 1A grant (36.212 5.1.1, 5.1.3.2, 5.1.4.1; 36.211 6.3, 6.4): what lcs_pdsch_wide decodes ----------------
+# 36.212 table 5.1.3-3 up to K = 2240, written from memory of the standard (as lte-cell-scanner_amd/csrc/pdsch.h's copy: what pins
+# both is said there): K -> (f1, f2)
+TURBO_K = list(range(40, 513, 8)) + list(range(528, 1025, 16)) + list(range(1056, 2049, 32)) + [2112, 2176, 2240]
+_QPP = """3,10 7,12 19,42 7,16 7,18 11,20 5,22 11,24 7,26 41,84 103,90 15,32 9,34 17,108 9,38 21,120 101,84 21,44 57,46 23,48 13,50 27,52 11,36
+27,56 85,58 29,60 33,62 15,32 17,198 33,68 103,210 19,36 19,74 37,76 19,78 21,120 21,82 115,84 193,86 21,44 133,90 81,46 45,94 23,48 243,98
+151,40 155,102 25,52 51,106 47,72 91,110 29,168 29,114 247,58 29,118 89,180 91,122 157,62 55,84 31,64 17,66 35,68 227,420 65,96 19,74 37,76
+41,234 39,80 185,82 43,252 21,86 155,44 79,120 139,92 23,94 217,48 25,98 17,80 127,102 25,52 239,106 17,48 137,110 215,112 29,114 15,58
+147,118 29,60 59,122 65,124 55,84 31,64 17,66 171,204 67,140 35,72 19,74 39,76 19,78 199,240 21,82 211,252 21,86 43,88 149,60 45,92 49,846
+71,48 13,28 17,80 25,102 183,104 55,954 127,96 27,110 29,112 29,114 57,116 45,354 31,120 59,610 185,124 113,420 31,64 17,66 171,136 209,420"""
+TURBO_QPP = {K: tuple(int(v) for v in f.split(",")) for K, f in zip(TURBO_K, _QPP.split())}
+_TURBO_PERM = [0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30, 1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31]
+
+
+def crc24a(bits):
+    """CRC24A (x^24 + x^23 + x^18 + x^17 + x^14 + x^11 + x^10 + x^7 + x^6 + x^5 + x^4 + x^3 + x + 1: 0x864CFB), zero initial state,
+    MSB first (36.212 5.1.1) -> the 24 parity bits"""
+    crc = 0
+    for b in np.asarray(bits, np.uint8):
+        msb = ((crc >> 23) & 1) ^ int(b)
+        crc = (crc << 1) & 0xFFFFFF
+        if msb:
+            crc ^= 0x864CFB
+    return np.array([(crc >> (23 - i)) & 1 for i in range(24)], np.uint8)
+
+
+def turbo_interleaver(K):
+    """the QPP interleaver of block size K: PI(i) = (f1 i + f2 i^2) mod K"""
+    f1, f2 = TURBO_QPP[int(K)]
+    i = np.arange(int(K), dtype=np.int64)
+    return (f1 * i + f2 * i * i) % int(K)
+
+
+def _rsc(c):
+    """one constituent (feedback 1 + D^2 + D^3, parity 1 + D + D^3) -> (parity [K], the three tail inputs, the three tail parities)"""
+    r1 = r2 = r3 = 0
+    z = np.empty(len(c), np.uint8)
+    for k, u in enumerate(c):
+        a = int(u) ^ r2 ^ r3
+        z[k] = a ^ r1 ^ r3
+        r1, r2, r3 = a, r1, r2
+    xt, zt = [], []
+    for _ in range(3):
+        xt.append(r2 ^ r3)            # the input that feeds back 0
+        zt.append(r1 ^ r3)
+        r1, r2, r3 = 0, r1, r2
+    return z, xt, zt
+
+
+def turbo_encode(c):
+    """36.212 5.1.3.2: the rate-1/3 turbo code of the K bits c (K a block size; the fillers, where there are any, are the leading
+    zeros of c and are marked null by turbo_ratematch's F) -> d [3][K + 4] with the twelve tail bits in the standard's order"""
+    c = np.asarray(c, np.uint8)
+    K = len(c)
+    z, xt, zt = _rsc(c)
+    zp, xpt, zpt = _rsc(c[turbo_interleaver(K)])
+    d = np.zeros((3, K + 4), np.uint8)
+    d[0, :K], d[1, :K], d[2, :K] = c, z, zp
+    d[0, K:] = [xt[0], zt[1], xpt[0], zpt[1]]
+    d[1, K:] = [zt[0], xt[2], zpt[0], xpt[2]]
+    d[2, K:] = [xt[1], zt[2], xpt[1], zpt[2]]
+    return d
+
+
+def turbo_ratematch(d, n_e, rv=0, F=0):
+    """36.212 5.1.4.1 for one code block without a soft-buffer limit (N_cb = K_w): sub-block interleavers of 32 columns (d2's with its
+    shift by one), bit collection (v0, then v1 and v2 interlaced), selection of n_e bits from k0 = R (2 ceil(N_cb / (8 R)) rv + 2)
+    without the nulls: the dummies, and the first F values of d0 and d1 (fillers).  d [3][D] of any integer type."""
+    d = np.asarray(d)
+    D = d.shape[1]
+    R = -(-D // 32)
+    KP = 32 * R
+    y = np.concatenate([np.full((3, KP - D), -1, np.int64), d.astype(np.int64)], axis=1)
+    y[0, KP - D:KP - D + F] = -1
+    y[1, KP - D:KP - D + F] = -1
+    v0 = y[0].reshape(R, 32)[:, _TURBO_PERM].T.reshape(-1)
+    v1 = y[1].reshape(R, 32)[:, _TURBO_PERM].T.reshape(-1)
+    k = np.arange(KP)
+    v2 = y[2][(np.array(_TURBO_PERM)[k // R] + 32 * (k % R) + 1) % KP]
+    w = np.concatenate([v0, np.stack([v1, v2], axis=1).reshape(-1)])
+    k0 = R * (2 * -(-3 * KP // (8 * R)) * int(rv) + 2)
+    live = np.flatnonzero(np.roll(w, -k0) >= 0)
+    return np.roll(w, -k0)[live[np.arange(int(n_e)) % live.size]].astype(d.dtype)
+
+
+def pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, rb_start, n_prb, tdd=False):
+    """[(l, k)]: the resource elements of a localized allocation in mapping order -- by symbol l = n_ctrl .. 2 n_symb - 1 of the
+    subframe, then by column --, without the reference elements of the cell's ports, the PBCH and the PSS / SSS"""
+    n_symb = 7 if cp_normal else 6
+    c0 = 6 * n_rb - 36
+    out = []
+    for l in range(n_ctrl, 2 * n_symb):
+        ls = l % n_symb
+        crs = set()
+        if ls in (0, n_symb - 3) or (ls == 1 and n_ports == 4):
+            if n_ports == 1:
+                crs = {((3 if ls else 0) + n_id_cell) % 6}
+            else:
+                crs = {n_id_cell % 3, n_id_cell % 3 + 3}
+        central = (subframe == 0 and n_symb <= l < n_symb + 4) or \
+                  (subframe in (0, 5) and ((l == 2 * n_symb - 1) if tdd else (l in (n_symb - 2, n_symb - 1))))
+        for k in range(12 * rb_start, 12 * (rb_start + n_prb)):
+            if k % 6 in crs or (central and c0 <= k < c0 + 72):
+                continue
+            out.append((l, k))
+    return out
+
+
+def pdsch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, grant, tdd=False):
+    """What the PDSCH of one grant puts on its subframe (36.211 6.3, 6.4): grant = dict(rnti, rb_start, n_prb, rv, bits) with bits the
+    transport block.  CRC24A, fillers up to the next block size, turbo code, rate matching to G = 2 N_RE, scrambling with c_init =
+    rnti 2^14 + subframe 2^9 + n_id_cell, QPSK, transmit diversity on consecutive elements.
+    -> [(l, columns, values [n_ports][len(columns)])] per symbol l of the subframe"""
+    n_ctrl = int(cfi) + (1 if n_rb <= 10 else 0)
+    el = pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, int(grant["rb_start"]), int(grant["n_prb"]), tdd)
+    a = np.asarray(grant["bits"], np.uint8)
+    B = len(a) + 24
+    K = next(k for k in TURBO_K if k >= B)
+    c = np.concatenate([np.zeros(K - B, np.uint8), a, crc24a(a)])
+    e = turbo_ratematch(turbo_encode(c), 2 * len(el), grant.get("rv", 0), K - B)
+    b = e ^ _pn((int(grant["rnti"]) << 14) + subframe * 512 + n_id_cell, 2 * len(el))
+    x = _tx_diversity(((1 - 2.0 * b[0::2]) + 1j * (1 - 2.0 * b[1::2])) / np.sqrt(2.0), n_ports)
+    ls = np.array([l for l, _ in el])
+    ks = np.array([k for _, k in el])
+    return [(int(l), ks[ls == l], x[:, ls == l]) for l in sorted(set(ls.tolist()))]
+
+
+def sib1_message(f):
+    """BCCH-DL-SCH-Message carrying SystemInformationBlockType1 up to and including tdd-Config, in UPER, as bits padded to whole
+    bytes (written from memory of 36.331; capi.sib1_fields is the matching reader and f its dict: a convenience, not part of any
+    kernel's rule).  Keys that may be missing: csg_id, q_rx_lev_min_offset, p_max, tdd (None), reserved flags (False).  An MCC is
+    sent where it differs from the PLMN before.  No extensions."""
+    out = []
+
+    def put(v, n):
+        out.extend((int(v) >> (n - 1 - i)) & 1 for i in range(n))
+    put(0, 1)                      # BCCH-DL-SCH-MessageType: c1
+    put(1, 1)                      # c1: systemInformationBlockType1
+    put(f.get("p_max") is not None, 1)
+    put(f.get("tdd") is not None, 1)
+    put(0, 1)                      # nonCriticalExtension absent
+    put(f.get("csg_id") is not None, 1)
+    put(len(f["plmns"]) - 1, 3)
+    last = None
+    for mcc, mnc, reserved in f["plmns"]:
+        put(mcc != last, 1)
+        if mcc != last:
+            for ch in mcc:
+                put(int(ch), 4)
+        last = mcc
+        put(len(mnc) - 2, 1)
+        for ch in mnc:
+            put(int(ch), 4)
+        put(0 if reserved else 1, 1)   # cellReservedForOperatorUse: reserved, notReserved
+    put(f["tac"], 16)
+    put(f["cell_id"], 28)
+    put(0 if f["barred"] else 1, 1)       # cellBarred: barred, notBarred
+    put(0 if f["intra_freq"] else 1, 1)   # intraFreqReselection: allowed, notAllowed
+    put(f["csg"], 1)
+    if f.get("csg_id") is not None:
+        put(f["csg_id"], 27)
+    put(f.get("q_rx_lev_min_offset") is not None, 1)
+    put(f["q_rx_lev_min"] + 70, 6)
+    if f.get("q_rx_lev_min_offset") is not None:
+        put(f["q_rx_lev_min_offset"] - 1, 3)
+    if f.get("p_max") is not None:
+        put(f["p_max"] + 30, 6)
+    put(f["band"] - 1, 6)
+    put(len(f["sched"]) - 1, 5)
+    for per, sibs in f["sched"]:
+        put((8, 16, 32, 64, 128, 256, 512).index(per), 3)
+        put(len(sibs), 5)
+        for t in sibs:
+            put(0, 1)              # SIB-Type: no extension
+            put(t - 3, 4)
+    if f.get("tdd") is not None:
+        put(f["tdd"][0], 3)
+        put(f["tdd"][1], 4)
+    put((1, 2, 5, 10, 15, 20, 40).index(f["si_window"]), 3)
+    put(f["value_tag"], 5)
+    out.extend([0] * (-len(out) % 8))
+    return np.array(out, np.uint8)
+
+
 def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
-                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None):
+                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None, pdsch=None):
     """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,
     CP lengths R * {10, 9, 32}), n_frames * 19200 * R samples from the boundary of frame sfn0.  The 72 centre subcarriers carry what
     cell_waveform puts there -- PSS, SSS, PBCH (the MIB says n_rb_dl: n_rb where that is an LTE bandwidth, else 50), CRS and load --
@@ -624,12 +808,15 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
     control region of every subframe that is sent (pdcch_region: the MIB's PHICH configuration, m_i = phich_mi[subframe] or 1); the
     rest of the control region beside the CRS and the PCFICH stays silent -- the PHICH's groups are kept free --, except that
     pdcch_fill puts random QPSK on that share of the unused CCEs, standing in for UE-specific traffic.  Without pdcch nothing more is
-    drawn from rng."""
+    drawn from rng.
+    pdsch: None plants no transport block.  A callable (frame, subframe) -> [dict(rnti, rb_start, n_prb, rv, bits)] (it needs cfi)
+    puts the PDSCH of those grants on their resource elements (pdsch_region; the matching format 1A DCIs are the pdcch callable's to
+    send); the elements carry no load then."""
     rng = rng or np.random.default_rng(0)
     R, n_rb = int(R), int(n_rb)
-    if pdcch is not None and cfi is None:
-        raise ValueError("cell_waveform_wide: pdcch needs cfi")
-    ctrl_n, ctrl = 0, []
+    if (pdcch is not None or pdsch is not None) and cfi is None:
+        raise ValueError("cell_waveform_wide: pdcch and pdsch need cfi")
+    ctrl_n, ctrl, data = 0, [], []
     n_fft, nc, c0 = 128 * R, 12 * n_rb, 6 * n_rb - 36          # c0: the first of the 72 centre columns
     if R not in (1, 2, 4, 8, 16) or not 6 <= n_rb or 12 * n_rb >= n_fft:
         raise ValueError("cell_waveform_wide: R in 1, 2, 4, 8, 16 and 6 <= n_rb with 12 n_rb < 128 R")
@@ -714,11 +901,17 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
                     if pdcch is not None:
                         ctrl_n, ctrl = pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, pdcch(fr, slot >> 1), pdcch_fill, rng,
                                                     phich_duration_ext, phich_res, 1 if phich_mi is None else phich_mi[slot >> 1])
+                    if pdsch is not None:
+                        data = [t for gr in pdsch(fr, slot >> 1) for t in pdsch_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, gr, tdd is not None)]
                 if pdcch is not None and not (slot & 1) and sym < ctrl_n and not is_sync:
                     reserved[:] = True
                     for l, cols, vals in ctrl:
                         if l == sym:
                             grid[:, cols] = vals
+                for l, cols, vals in data:
+                    if l == (slot & 1) * n_symb + sym:
+                        grid[:, cols] = vals
+                        reserved[cols] = True
                 free = np.flatnonzero(~reserved)
                 on = free[rng.random(free.size) < load]
                 d = ((1 - 2.0 * rng.integers(0, 2, on.size)) + 1j * (1 - 2.0 * rng.integers(0, 2, on.size))) / np.sqrt(2.0)
@@ -747,7 +940,7 @@ def make_signal_wide(rng, fc, cd, R, n_rb, n_cap):
     w = cell_waveform_wide(n_frames, cd["n_id_1"], cd["n_id_2"], R, n_rb, cd.get("cp_normal", True), cd.get("n_ports", 2), cd.get("load", 0.5), rng,
                            cd.get("port_gains"), tdd=cd.get("tdd"), n_rb_dl=cd.get("n_rb_dl"), phich_duration_ext=cd.get("phich_duration_ext", 0),
                            phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))), cfi=cd.get("cfi"),
-                           pdcch=cd.get("pdcch"), pdcch_fill=cd.get("pdcch_fill", 0.0), phich_mi=cd.get("phich_mi"))
+                           pdcch=cd.get("pdcch"), pdcch_fill=cd.get("pdcch_fill", 0.0), phich_mi=cd.get("phich_mi"), pdsch=cd.get("pdsch"))
     y = frac_resample(w, t0 * R + n / k_factor)
     y = y * np.exp(2j * np.pi * f_off * n / (FS * R * k_factor))
     g = 10 ** (cd.get("gain_db", 0.0) / 20)
