@@ -441,6 +441,49 @@ typedef struct lcs_pdsch_info {
   lcs_pdsch_block block[LCS_PDSCH_MAX_BLOCKS];
 } lcs_pdsch_info;         /* 10832 bytes */
 
+/* The redundancy versions of one SI transport block, combined (lcs_pdsch_comb_wide, lcs_pdsch_comb below: the PDSCH stage, then one
+ * more decode per group of blocks that repeat a transport block).  THE RULE (lte-cell-scanner_amd/csrc/pdsch_comb.h, host and device,
+ * on top of pdsch.h's functions):
+ *   members     the listed blocks of the PDSCH record (index < n_blocks) of kind SI whose status is LCS_PDSCH_OK or LCS_PDSCH_CRC: the
+ *               blocks whose soft bits were formed and decoded; forced grants with the SI-RNTI count like any other.  Paging and RA
+ *               blocks and blocks of any other status never become members
+ *   rule 1      (SIB1; on unless no_sib1) members with subframe % 10 == 5; key (tbs, (subframe / 10) % 2); all members of one key, in
+ *               block order, form a group; a group takes at most 4 members, a fifth opens the next group of that key
+ *   rule 2      (an SI window; on iff si_window > 0, in subframes, 1 .. 61) the members rule 1 did not take, walked in block order: a
+ *               member joins the open (the latest) group of its tbs if that group has fewer than 4 members and the member's subframe
+ *               minus the group's first member's is below si_window; otherwise it opens a new group for that tbs
+ *   listing     groups in the order of their first member, at most LCS_PDSCH_COMB_MAX_GROUPS (n_overflow counts the rest); a group of
+ *               one member is listed too
+ *   result      n_ok_members: the members of status OK.  If there is one: status LCS_PDSCH_COMB_MEMBER, n_iter 0, the payload of the
+ *               first such member, no decode; n_same: how many OK members carry a payload byte-equal to the first OK member's (below
+ *               n_ok_members: the content changed inside the group).  Otherwise n_same = 0 and, with at least 2 members, value k of
+ *               stream s is 0 + the sum over the members m, in ascending member order, of the member's de-rate-matched value (pdsch.h:
+ *               pds_derm_value(llr_m, G_m, N, base(rv_m), rank)); N and rank are those of (K, F), the same for every member since tbs
+ *               is part of the key; the members may differ in allocation, n_re, TBS column and mcs.  The silent check (status
+ *               LCS_PDSCH_COMB_SILENT, n_iter 0, a zero payload), the windows, the iteration rule, the CRC stop and max_iter are
+ *               exactly the stage's: status LCS_PDSCH_COMB_OK or LCS_PDSCH_COMB_CRC, n_iter and payload as for a block.  A single
+ *               member of status CRC: LCS_PDSCH_COMB_CRC, n_iter 0, the member's payload
+ * rv_mask: bit rv set for every member's rv.  n_status[] counts the listed groups by status. */
+#define LCS_PDSCH_COMB_MAX_GROUPS 8
+#define LCS_PDSCH_COMB_MAX_MEMBERS 4
+#define LCS_PDSCH_COMB_N_STATUS 5
+enum { LCS_PDSCH_COMB_MEMBER = 1, LCS_PDSCH_COMB_OK = 2, LCS_PDSCH_COMB_CRC = 3, LCS_PDSCH_COMB_SILENT = 4 };
+typedef struct lcs_pdsch_comb_cfg {       /* zero = defaults */
+  int32_t si_window;                      /* rule 2: 0 = off, else 1 .. 61 subframes */
+  int32_t no_sib1;                        /* 1: rule 1 off */
+  int32_t reserved[2];
+} lcs_pdsch_comb_cfg;     /* 16 bytes */
+typedef struct lcs_pdsch_comb_group {
+  int32_t n_members, member[LCS_PDSCH_COMB_MAX_MEMBERS] /* block indices; -1 beyond n_members */, rule /*1, 2*/, tbs, K, F, rv_mask,
+      n_ok_members, n_same, n_iter, status, reserved[2];
+  uint8_t payload[LCS_PDSCH_PAYLOAD];
+} lcs_pdsch_comb_group;   /* 344 bytes */
+typedef struct lcs_pdsch_comb_info {
+  int32_t n_groups, n_overflow, n_members /* of the listed groups */, n_decoded /* groups whose sum was decoded: OK + CRC with n_iter > 0 */;
+  int32_t n_status[LCS_PDSCH_COMB_N_STATUS], reserved[3];
+  lcs_pdsch_comb_group group[LCS_PDSCH_COMB_MAX_GROUPS];
+} lcs_pdsch_comb_info;    /* 2800 bytes */
+
 /* ---- stage entry points (host buffers in / out) ------------------------------------ */
 
 /* Replaces xcorr_pss -- include/searcher.h:22-41, src/searcher.cpp:389-419
@@ -594,6 +637,19 @@ int lcs_pdsch_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uin
                    int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out);
 int lcs_pdsch(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
               int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out);
+
+/* The same two calls with the redundancy versions combined (the rule: lcs_pdsch_comb_info above).  They take lcs_pdsch_wide's and
+ * lcs_pdsch's arguments, fill `out` and the optional pdcch_out exactly as those do, and after the stage's decode group the SI blocks
+ * on the device, decode every group that needs it from the sum of its members' soft bits and fill comb_out.  comb_cfg NULL =
+ * defaults (rule 1 on, rule 2 off).  Refused beyond those calls' refusals (LCS_ERR_BAD_ARG, a text, no launch): a null comb_out, an
+ * si_window outside 0 .. 61, a no_sib1 outside 0 .. 1. */
+int lcs_pdsch_comb_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                        double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                        int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
+                        const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out);
+int lcs_pdsch_comb(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
+                   int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
+                   const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out);
 
 /* The soft bits the last lcs_pdsch_wide / lcs_pdsch call of this context formed for grant slot `which` (0, 1) of grid `subframe` --
  * the subframe's grants in the order of the record's blocks, followed or not --, exported so that they can be tested directly: the

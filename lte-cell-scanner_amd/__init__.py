@@ -580,6 +580,36 @@ class Searcher:
         pd.sizes = tuple(cfg.size[:cfg.n_sizes])
         return (out, pd) if want_pdcch else out
 
+    def pdsch_comb_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                        cfg=None, pdsch_cfg=None, comb_cfg=None, n_cap=None, want_pdcch: bool = False):
+        """pdsch_wide, then the SI blocks that repeat one transport block are grouped and every group none of whose members decoded
+        is decoded from the sum of its members' soft bits, on the device (lcs_pdsch_comb_wide; the rule: include/lcs.h,
+        lcs_pdsch_comb_info).  comb_cfg: a capi.PdschCombCfg or None (SIB1 rule on, SI windows off)
+        -> (PdschInfo, PdschCombInfo), or (PdschInfo, PdschCombInfo, PdcchInfo) with want_pdcch"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out, pd, comb = capi.PdschInfo(), capi.PdcchInfo(), capi.PdschCombInfo()
+        self._chk(self._lib.lcs_pdsch_comb_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                                float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg),
+                                                C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None,
+                                                C.byref(comb_cfg) if comb_cfg is not None else None, C.byref(comb)), "lcs_pdsch_comb_wide")
+        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return (out, comb, pd) if want_pdcch else (out, comb)
+
+    def pdsch_comb(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None, pdsch_cfg=None, comb_cfg=None, want_pdcch: bool = False):
+        """The same on a grid from the host as pdsch takes it (lcs_pdsch_comb)
+        -> (PdschInfo, PdschCombInfo), or (PdschInfo, PdschCombInfo, PdcchInfo) with want_pdcch"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        cfg = self._pdcch_cfg(cfg, n_rb)
+        out, pd, comb = capi.PdschInfo(), capi.PdcchInfo(), capi.PdschCombInfo()
+        self._chk(self._lib.lcs_pdsch_comb(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg),
+                                           C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None,
+                                           C.byref(comb_cfg) if comb_cfg is not None else None, C.byref(comb)), "lcs_pdsch_comb")
+        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return (out, comb, pd) if want_pdcch else (out, comb)
+
     def pdsch_last_soft(self, subframe: int, which: int, n: int):
         """the first n soft bits of the which-th grant the last pdsch / pdsch_wide call followed in grid subframe `subframe`
         (lcs_pdsch_last_soft)"""

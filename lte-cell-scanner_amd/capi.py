@@ -467,6 +467,65 @@ class PdschInfo(C.Structure):
 
 assert C.sizeof(PdschCfg) == 112 and C.sizeof(PdschBlock) == 336 and C.sizeof(PdschInfo) == 10832
 
+# ---- the redundancy versions of an SI transport block, combined (include/lcs.h: lcs_pdsch_comb_info) ----
+PDSCH_COMB_MAX_GROUPS, PDSCH_COMB_MAX_MEMBERS, PDSCH_COMB_N_STATUS = 8, 4, 5
+PDSCH_COMB_MEMBER, PDSCH_COMB_OK, PDSCH_COMB_CRC, PDSCH_COMB_SILENT = range(1, 5)
+PDSCH_COMB_STATUS = {0: "none", 1: "member", 2: "ok", 3: "crc", 4: "silent"}
+
+
+def sib1_rv(sfn: int) -> int:
+    """the redundancy version of the SIB1 transmission in subframe 5 of (even) frame sfn: ceil(3 k / 2) mod 4 with k = (sfn / 2) mod 4
+    (36.321 5.3.1), i.e. 0, 2, 3, 1"""
+    k = (int(sfn) // 2) % 4
+    return -(-3 * k // 2) % 4
+
+
+class PdschCombCfg(C.Structure):
+    """lcs_pdsch_comb_cfg.  PdschCombCfg.make(si_window, sib1): si_window 0 = rule 2 off, else 1 .. 61 subframes; sib1=False switches
+    rule 1 off"""
+    _fields_ = [("si_window", C.c_int32), ("no_sib1", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    @classmethod
+    def make(cls, si_window=0, sib1=True) -> "PdschCombCfg":
+        o = cls()
+        o.si_window, o.no_sib1 = int(si_window), 0 if sib1 else 1
+        return o
+
+
+class PdschCombGroup(C.Structure):
+    _fields_ = [("n_members", C.c_int32), ("member", C.c_int32 * PDSCH_COMB_MAX_MEMBERS)] + \
+               [(k, C.c_int32) for k in ("rule", "tbs", "K", "F", "rv_mask", "n_ok_members", "n_same", "n_iter", "status")] + \
+               [("reserved", C.c_int32 * 2), ("payload", C.c_uint8 * PDSCH_PAYLOAD)]
+
+
+class PdschCombInfo(C.Structure):
+    """lcs_pdsch_comb_info: the groups of SI blocks that repeat one transport block and what the sum of their soft bits decodes to
+    (include/lcs.h: lcs_pdsch_comb_wide, lcs_pdsch_comb)"""
+    _fields_ = [(k, C.c_int32) for k in ("n_groups", "n_overflow", "n_members", "n_decoded")] + \
+               [("n_status", C.c_int32 * PDSCH_COMB_N_STATUS), ("reserved", C.c_int32 * 3), ("group", PdschCombGroup * PDSCH_COMB_MAX_GROUPS)]
+
+    def groups(self) -> list:
+        """the listed groups as dicts: members (block indices of the PDSCH record), rule, tbs, K, F, rvs, n_ok_members, n_same, n_iter,
+        status as a word, crc_ok (the payload passed a CRC: in a member, or combined) and bytes = the transport block (empty for a
+        silent sum)"""
+        out = []
+        for i in range(min(max(int(self.n_groups), 0), PDSCH_COMB_MAX_GROUPS)):
+            g = self.group[i]
+            d = {k: int(getattr(g, k)) for k in ("rule", "tbs", "K", "F", "n_ok_members", "n_same", "n_iter")}
+            d["members"] = [int(g.member[m]) for m in range(min(max(int(g.n_members), 0), PDSCH_COMB_MAX_MEMBERS))]
+            d["rvs"] = [rv for rv in range(4) if (g.rv_mask >> rv) & 1]
+            d["status"] = PDSCH_COMB_STATUS.get(g.status, "?")
+            d["crc_ok"] = g.status in (PDSCH_COMB_MEMBER, PDSCH_COMB_OK)
+            d["bytes"] = bytes(g.payload[:(g.tbs + 7) // 8]) if g.status in (PDSCH_COMB_MEMBER, PDSCH_COMB_OK, PDSCH_COMB_CRC) else b""
+            out.append(d)
+        return out
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"PdschCombInfo(n_groups={self.n_groups}, n_overflow={self.n_overflow}, n_status={list(self.n_status)})"
+
+
+assert C.sizeof(PdschCombCfg) == 16 and C.sizeof(PdschCombGroup) == 344 and C.sizeof(PdschCombInfo) == 2800
+
 
 def sib1_fields(payload):
     """The fields of a BCCH-DL-SCH-Message that carries SystemInformationBlockType1, read in UPER up to and including tdd-Config
@@ -530,7 +589,7 @@ EXPORTS = [
     "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -621,6 +680,9 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_pdsch.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchCfg), C.POINTER(PdschCfg), C.POINTER(PdschInfo), C.POINTER(PdcchInfo)]
         L.lcs_pdsch_last_soft.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
         L.lcs_turbo_decode.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "lcs_pdsch_comb_wide"):      # (likewise)
+        L.lcs_pdsch_comb_wide.argtypes = L.lcs_pdsch_wide.argtypes + [C.POINTER(PdschCombCfg), C.POINTER(PdschCombInfo)]
+        L.lcs_pdsch_comb.argtypes = L.lcs_pdsch.argtypes + [C.POINTER(PdschCombCfg), C.POINTER(PdschCombInfo)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

@@ -1351,28 +1351,38 @@ int pdsch_plan(const lcs_cell *cell, const lcs_pdcch_cfg *cfg, const PdcchPlan &
   }
   return n_sf;
 }
-int pdsch_finish(lcs_ctx *c, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+int pdsch_finish(lcs_ctx *c, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, lcs_pdsch_comb_info *comb_out = nullptr) {
   HIPCHK(c, hipMemcpyAsync(out, c->pdsch.rec, sizeof(lcs_pdsch_info), hipMemcpyDeviceToHost, c->stream));
+  if (comb_out) HIPCHK(c, hipMemcpyAsync(comb_out, c->pdsch.crec, sizeof(lcs_pdsch_comb_info), hipMemcpyDeviceToHost, c->stream));
   if (pdcch_out) HIPCHK(c, hipMemcpyAsync(pdcch_out, c->pdsch.pdc.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
 }
-}  // namespace
-
-int lcs_pdsch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
-                   int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdsch_wide";
+// the combining's configuration (null: defaults)
+int pdsch_comb_resolve(lcs_ctx *c, const char *who, const lcs_pdsch_comb_cfg *cc, PdschCombPlan *p) {
+  static const lcs_pdsch_comb_cfg zero = {};
+  if (!cc) cc = &zero;
+  if (cc->si_window < 0 || cc->si_window > 61) return wide_refused(c, who, "si_window is outside 0 .. 61");
+  if (cc->no_sib1 < 0 || cc->no_sib1 > 1) return wide_refused(c, who, "no_sib1 is outside 0 .. 1");
+  p->si_window = cc->si_window; p->no_sib1 = cc->no_sib1;
+  return LCS_OK;
+}
+// lcs_pdsch_wide and lcs_pdsch_comb_wide (comb_out non-null)
+int pdsch_wide_call(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog, int n_fft, int n_rb,
+                    int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
+                    const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
   if (!out) return wide_refused(c, who, "a null pointer");
   std::vector<double> ts;
   double kk;
   int rc;
   PdcchPlan plan;
   PdschPlan ps;
+  PdschCombPlan cp = {0, 0};
   if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
   if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
   if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
   if ((rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_rb, &ps))) return rc;
+  if (comb_out && (rc = pdsch_comb_resolve(c, who, comb_cfg, &cp))) return rc;
   int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
   std::vector<int> list;
   const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, &list);
@@ -1381,31 +1391,58 @@ int lcs_pdsch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint3
   if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps))) return rc;
-  return pdsch_finish(c, out, pdcch_out);
+  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps, comb_out ? &cp : nullptr))) return rc;
+  return pdsch_finish(c, out, pdcch_out, comb_out);
 }
 
-int lcs_pdsch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
-              lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdsch";
+// lcs_pdsch and lcs_pdsch_comb (comb_out non-null)
+int pdsch_grid_call(lcs_ctx *c, const char *who, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg,
+                    const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
   if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
   if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
   int rc;
   PdcchPlan plan;
   PdschPlan ps;
+  PdschCombPlan cp = {0, 0};
   if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
   const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
   if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
   if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
   if ((rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan)) || (rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, n_symb, n_rb, &ps))) return rc;
+  if (comb_out && (rc = pdsch_comb_resolve(c, who, comb_cfg, &cp))) return rc;
   int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
   const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, nullptr);
   HIPCHK(c, hipSetDevice(c->device));
   if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps))) return rc;
-  return pdsch_finish(c, out, pdcch_out);
+  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps, comb_out ? &cp : nullptr))) return rc;
+  return pdsch_finish(c, out, pdcch_out, comb_out);
 }
+}  // namespace
+
+int lcs_pdsch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                   int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  return pdsch_wide_call(c, "lcs_pdsch_wide", cell, d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
+}
+int lcs_pdsch_comb_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                        int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
+                        const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (!comb_out) return wide_refused(c, "lcs_pdsch_comb_wide", "a null pointer");
+  return pdsch_wide_call(c, "lcs_pdsch_comb_wide", cell, d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, comb_cfg, comb_out);
+}
+int lcs_pdsch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
+              lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  return pdsch_grid_call(c, "lcs_pdsch", cell, tfg, n_ofdm, n_rb, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
+}
+int lcs_pdsch_comb(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
+                   lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (!comb_out) return wide_refused(c, "lcs_pdsch_comb", "a null pointer");
+  return pdsch_grid_call(c, "lcs_pdsch_comb", cell, tfg, n_ofdm, n_rb, dl_mask, cfg, pdsch_cfg, out, pdcch_out, comb_cfg, comb_out);
+}
+
 
 int lcs_pdsch_last_soft(lcs_ctx *c, int subframe, int which, double *llr_out, int n) {
   if (!c) return LCS_ERR_BAD_ARG;

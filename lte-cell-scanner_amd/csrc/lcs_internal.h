@@ -436,6 +436,12 @@ struct lcs_ctx : lcs_ctx_queues {
     DevBuf<double> ws;              // [n_sf][2][32][8][72]: the forward metrics of the windows
     DevBuf<double> din;             // [3][2244]: lcs_turbo_decode's input
     DevBuf<lcs_pdsch_info> rec;     // [1]
+    // the combined redundancy versions (lcs_pdsch_comb_wide, lcs_pdsch_comb), allocated by the first call of those
+    DevBuf<int> cjob;               // PdsCombJob [8]
+    DevBuf<int> cres;               // [8][2]: n_iter, status
+    DevBuf<uint8_t> chard;          // [8][2240]: the decisions of the groups that are decoded
+    DevBuf<double> cws;             // [8][32][8][72]
+    DevBuf<lcs_pdsch_comb_info> crec;   // [1]
     std::vector<int> h_tabs, h_heads;   // the host blocks they are uploaded from
     std::vector<int16_t> h_rank;
     std::vector<double> h_din;
@@ -658,7 +664,11 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
 struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; };
 // the PCFICH and PDCCH of rows4 into c->pdsch.pdc, then the grants' blocks -> c->pdsch.rec.  sfrow [n_sf]: the row of c->meas_wide.grid
 // that holds symbol 0 of every subframe whose rows are all there, else -1
-int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps);
+// comb (or null): after the decode the SI blocks are grouped and every group that needs it is decoded from the sum of its members'
+// soft bits -> c->pdsch.crec
+struct PdschCombPlan { int si_window, no_sib1; };
+int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps,
+                     const PdschCombPlan *comb = nullptr);
 // d [3][K + 4] from the host through the decode kernel -> c->pdsch.res[0 .. 1], c->pdsch.hard[0 .. K - 1]
 int lcs_launch_turbo(lcs_ctx *c, const double *h_d, int K, int F, int max_iter);
 void lcs_chan_est_np_layout(int *first, int *per_port, int *n_rs_first);   // where k_chan_est leaves its noise-power partial sums in cell_scratch

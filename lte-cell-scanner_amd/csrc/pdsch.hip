@@ -3,7 +3,10 @@
 // context that never calls the stage runs no kernel of this file and allocates none of its buffers, and the code objects of the
 // chain, of the measurement, of the PCFICH and of the PDCCH are what they are without it.  No atomics, no scratch, every result
 // written by exactly one lane, nothing depends on the order in which workgroups run; fp64 throughout and bit-equal to the host twin
-// (tests/host/pdsch_host.cpp).
+// (tests/host/pdsch_host.cpp).  lcs_pdsch_comb_wide and lcs_pdsch_comb add three kernels between the decode and the record
+// (k_pdsch_comb_group, k_pdsch_comb_dec, k_pdsch_comb_fin; the rule: pdsch_comb.h): the SI blocks that repeat one transport block are
+// grouped and decoded once more from the sum of their soft bits.  k_pdsch_dec and k_pdsch_comb_dec are one function, pds_dec_block,
+// behind two gathers.
 //
 // WHAT LIVES WHERE in k_pdsch_dec.  LDS (about 100 KB of the CU's 160): the three de-rate-matched streams (3 x 2244 doubles, every
 // window of 32 steps one double further on so that the lanes of a wave read different banks), the extrinsics (one array in natural
@@ -16,12 +19,14 @@
 #include "lcs_internal.h"
 #include "lte_device.h"
 #include "pdsch.h"
+#include "pdsch_comb.h"
 
 #define PDS_LLR_THREADS 256
 #define PDS_DEC_THREADS 128
 #define PDS_WS_LANES 72                   // lanes of the forward-metric workspace (>= PDS_MAX_WIN)
 #define PDS_WS_DOUBLES (PDS_WIN * 8 * PDS_WS_LANES)
 static_assert(PDS_MAX_WIN <= PDS_WS_LANES && PDS_MAX_WIN <= PDS_DEC_THREADS, "one lane per window");
+static_assert(PDS_COMB_GROUPS * sizeof(PdsCombJob) / sizeof(int) <= 256, "k_pdsch_comb_fin copies the jobs with one thread per word");
 
 // ------------------------------------------------------------------ the plan: one thread per subframe
 // Thread g reads the PDCCH record of grid subframe g on the device and writes the subframe's two grant slots: the public block and
@@ -90,94 +95,241 @@ __global__ __launch_bounds__(PDS_LLR_THREADS) void k_pdsch_llr(const double2 *__
 // first decoder, of the second, .. with the window's eight forward and backward metrics in registers: a window starts from the
 // metrics its neighbours left in the previous iteration (read by every lane before any lane writes).  After every iteration the
 // lanes pack the decisions, thread 0 takes the CRC, and the workgroup stops together.
-__global__ __launch_bounds__(PDS_DEC_THREADS) void k_pdsch_dec(const PdsJob *__restrict__ jobs, const double *__restrict__ llr, size_t llr_stride, const double *__restrict__ din,
-                                                               const int16_t *__restrict__ rank /*[PDS_TABS][3][PDS_MAX_D]*/, double *__restrict__ ws_all,
-                                                               int *__restrict__ res /*[slots][2]: n_iter, status*/, uint8_t *__restrict__ hard_out /*[slots][2240]*/) {
-  const int slot = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_d[3][PDS_PAD_D];
-  __shared__ double s_ext[PDS_PAD_D];
-  __shared__ double s_ab[2][2][PDS_MAX_WIN + 1][8];      // [decoder][forward, backward][window boundary][state]
-  __shared__ uint16_t s_perm[PDS_MAX_K];
-  __shared__ uint8_t s_hard[PDS_MAX_K];
-  __shared__ uint32_t s_word[PDS_MAX_WIN];
-  __shared__ int s_stop;
-  const PdsJob job = jobs[slot];
-  if (job.status != LCS_PDSCH_FOLLOW) {                    // the same for the whole workgroup
-    if (tid == 0) { res[2 * slot] = 0; res[2 * slot + 1] = job.status; }
-    return;
-  }
-  const int K = job.K, F = job.F, D = K + 4, n_win = (K + PDS_WIN - 1) / PDS_WIN;
+// what a decode workgroup keeps in LDS
+struct PdsDecLds {
+  double d[3][PDS_PAD_D];
+  double ext[PDS_PAD_D];
+  double ab[2][2][PDS_MAX_WIN + 1][8];                   // [decoder][forward, backward][window boundary][state]
+  uint16_t perm[PDS_MAX_K];
+  uint8_t hard[PDS_MAX_K];
+  uint32_t word[PDS_MAX_WIN];
+  int stop;
+};
+// One block through the decoder by one workgroup of PDS_DEC_THREADS: value(s, k, i) is value k of stream s (i = s (K + 4) + k), ws
+// the workgroup's forward-metric room, res -> {n_iter, status}, hard_out the decisions.  k_pdsch_dec and k_pdsch_comb_dec differ in
+// what they gather and in the words for the three outcomes; everything from the gather on is this function.
+template <class Value>
+__device__ __forceinline__ void pds_dec_block(PdsDecLds &L, int K, int F, int f1, int f2, int max_iter, Value value, double *__restrict__ ws_block, int *__restrict__ res,
+                                              uint8_t *__restrict__ hard_out, int st_ok, int st_crc, int st_silent) {
+  const int tid = threadIdx.x;
+  const int D = K + 4, n_win = (K + PDS_WIN - 1) / PDS_WIN;
   int any = 0, bad = 0;
-  const double *sl = llr + (size_t)slot * llr_stride;
-  const int16_t *rk = rank + (size_t)job.tab * 3 * PDS_MAX_D;
 #pragma unroll 1
   for (int i = tid; i < 3 * D; i += PDS_DEC_THREADS) {
     const int s = i / D, k = i - s * D;
-    const double v = job.direct ? din[i] : pds_derm_value(sl, job.G, job.N, job.base, rk[s * PDS_MAX_D + k]);
-    s_d[s][pds_pad(k)] = v;
+    const double v = value(s, k, i);
+    L.d[s][pds_pad(k)] = v;
     any |= v != 0.0;
     bad |= !vit_finite(v);
   }
-  for (int i = tid; i < K; i += PDS_DEC_THREADS) { s_perm[i] = (uint16_t)pds_qpp(job.f1, job.f2, K, i); s_hard[i] = 0; s_ext[pds_pad(i)] = 0.0; }
+  for (int i = tid; i < K; i += PDS_DEC_THREADS) { L.perm[i] = (uint16_t)pds_qpp(f1, f2, K, i); L.hard[i] = 0; L.ext[pds_pad(i)] = 0.0; }
   for (int i = tid; i < 2 * 2 * (PDS_MAX_WIN + 1) * 8; i += PDS_DEC_THREADS) {
     const int st = i & 7, w = (i >> 3) % (PDS_MAX_WIN + 1), fb = (i >> 3) / (PDS_MAX_WIN + 1) & 1;
-    (&s_ab[0][0][0][0])[i] = (fb == 0 && w == 0 && st != 0) ? -INFINITY : 0.0;
+    (&L.ab[0][0][0][0])[i] = (fb == 0 && w == 0 && st != 0) ? -INFINITY : 0.0;
   }
   any = __syncthreads_or(any);
   bad = __syncthreads_or(bad);
   if (!any || bad) {
-    if (tid == 0) { res[2 * slot] = 0; res[2 * slot + 1] = LCS_PDSCH_SILENT; }
+    if (tid == 0) { res[0] = 0; res[1] = st_silent; }
     return;
   }
   if (tid < 2) {                                           // the tail of decoder tid: its values lie at K + 2 tid, K + 2 tid + 1 of the streams
     const int o = K + 2 * tid;
-    const double x[3] = {s_d[0][pds_pad(o)], s_d[2][pds_pad(o)], s_d[1][pds_pad(o + 1)]};
-    const double z[3] = {s_d[1][pds_pad(o)], s_d[0][pds_pad(o + 1)], s_d[2][pds_pad(o + 1)]};
+    const double x[3] = {L.d[0][pds_pad(o)], L.d[2][pds_pad(o)], L.d[1][pds_pad(o + 1)]};
+    const double z[3] = {L.d[1][pds_pad(o)], L.d[0][pds_pad(o + 1)], L.d[2][pds_pad(o + 1)]};
     double b[8];
     pds_tail_beta(x, z, b);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) s_ab[tid][1][n_win][s] = b[s];
+    for (int s = 0; s < 8; ++s) L.ab[tid][1][n_win][s] = b[s];
   }
   __syncthreads();
   const bool lane_on = tid < n_win;
   const int k0 = PDS_WIN * tid, n = lane_on ? (K - k0 < PDS_WIN ? K - k0 : PDS_WIN) : 0;
-  double *ws = ws_all + (size_t)slot * PDS_WS_DOUBLES + tid;
+  double *ws = ws_block + tid;
   int n_iter = 0, ok = 0;
 #pragma unroll 1
-  for (int it = 1; it <= job.max_iter; ++it) {
+  for (int it = 1; it <= max_iter; ++it) {
 #pragma unroll 1
     for (int dec = 0; dec < 2; ++dec) {
       double a[8], b[8];
 #pragma unroll
-      for (int s = 0; s < 8; ++s) { a[s] = lane_on ? s_ab[dec][0][tid][s] : 0.0; b[s] = lane_on ? s_ab[dec][1][tid + 1][s] : 0.0; }
+      for (int s = 0; s < 8; ++s) { a[s] = lane_on ? L.ab[dec][0][tid][s] : 0.0; b[s] = lane_on ? L.ab[dec][1][tid + 1][s] : 0.0; }
       __syncthreads();
       if (lane_on) {
-        pds_window(s_d[0], s_d[1 + dec], s_ext, dec ? s_perm : nullptr, dec ? s_hard : nullptr, F, k0, n, a, b, ws, PDS_WS_LANES);
+        pds_window(L.d[0], L.d[1 + dec], L.ext, dec ? L.perm : nullptr, dec ? L.hard : nullptr, F, k0, n, a, b, ws, PDS_WS_LANES);
         if (tid + 1 < n_win) {
 #pragma unroll
-          for (int s = 0; s < 8; ++s) s_ab[dec][0][tid + 1][s] = a[s];
+          for (int s = 0; s < 8; ++s) L.ab[dec][0][tid + 1][s] = a[s];
         }
         if (tid > 0) {
 #pragma unroll
-          for (int s = 0; s < 8; ++s) s_ab[dec][1][tid][s] = b[s];
+          for (int s = 0; s < 8; ++s) L.ab[dec][1][tid][s] = b[s];
         }
       }
       __syncthreads();
     }
     if (lane_on) {
       uint32_t word = 0;
-      for (int t = 0; t < n; ++t) word |= (uint32_t)((k0 + t >= F) ? (s_hard[k0 + t] & 1) : 0) << t;
-      s_word[tid] = word;
+      for (int t = 0; t < n; ++t) word |= (uint32_t)((k0 + t >= F) ? (L.hard[k0 + t] & 1) : 0) << t;
+      L.word[tid] = word;
     }
     __syncthreads();
-    if (tid == 0) s_stop = pds_crc24a(s_word, K) == 0u;
+    if (tid == 0) L.stop = pds_crc24a(L.word, K) == 0u;
     __syncthreads();
     n_iter = it;
-    ok = s_stop;
+    ok = L.stop;
     if (ok) break;
   }
-  for (int i = tid; i < K; i += PDS_DEC_THREADS) hard_out[(size_t)slot * PDS_MAX_K + i] = i >= F ? (s_hard[i] & 1) : 0;
-  if (tid == 0) { res[2 * slot] = n_iter; res[2 * slot + 1] = ok ? LCS_PDSCH_OK : LCS_PDSCH_CRC; }
+  for (int i = tid; i < K; i += PDS_DEC_THREADS) hard_out[i] = i >= F ? (L.hard[i] & 1) : 0;
+  if (tid == 0) { res[0] = n_iter; res[1] = ok ? st_ok : st_crc; }
+}
+
+__global__ __launch_bounds__(PDS_DEC_THREADS) void k_pdsch_dec(const PdsJob *__restrict__ jobs, const double *__restrict__ llr, size_t llr_stride, const double *__restrict__ din,
+                                                               const int16_t *__restrict__ rank /*[PDS_TABS][3][PDS_MAX_D]*/, double *__restrict__ ws_all,
+                                                               int *__restrict__ res /*[slots][2]: n_iter, status*/, uint8_t *__restrict__ hard_out /*[slots][2240]*/) {
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  __shared__ PdsDecLds L;
+  const PdsJob job = jobs[slot];
+  if (job.status != LCS_PDSCH_FOLLOW) {                    // the same for the whole workgroup
+    if (tid == 0) { res[2 * slot] = 0; res[2 * slot + 1] = job.status; }
+    return;
+  }
+  const double *sl = llr + (size_t)slot * llr_stride;
+  const int16_t *rk = rank + (size_t)job.tab * 3 * PDS_MAX_D;
+  pds_dec_block(L, job.K, job.F, job.f1, job.f2, job.max_iter,
+                [&](int s, int k, int i) { return job.direct ? din[i] : pds_derm_value(sl, job.G, job.N, job.base, rk[s * PDS_MAX_D + k]); },
+                ws_all + (size_t)slot * PDS_WS_DOUBLES, res + 2 * slot, hard_out + (size_t)slot * PDS_MAX_K, LCS_PDSCH_OK, LCS_PDSCH_CRC, LCS_PDSCH_SILENT);
+}
+
+// ------------------------------------------------------------------ the redundancy versions combined (pdsch_comb.h)
+// The grouping: one workgroup.  Thread 0 lists the slots that hold a grant as k_pdsch_fin does; thread i reads block i as the grouping
+// sees it (its status is what the decode left); thread 0 forms the groups; thread g completes group slot g: its members' grant slots,
+// the sizes and the table of its first member, whether it is decoded and whose decisions its payload is.  No atomics.
+__global__ __launch_bounds__(64) void k_pdsch_comb_group(const lcs_pdsch_block *__restrict__ blk, const PdsJob *__restrict__ jobs, const int *__restrict__ res,
+                                                         PdsCombJob *__restrict__ cjobs, int n_sf, int si_window, int no_sib1) {
+  const int tid = threadIdx.x;
+  __shared__ int s_map[LCS_PDSCH_MAX_BLOCKS], s_n[3], s_work[PDS_COMB_WORK];
+  __shared__ PdsCombBlock s_blk[LCS_PDSCH_MAX_BLOCKS];
+  __shared__ PdsCombJob s_job[PDS_COMB_GROUPS];
+  if (tid == 0) {
+    int n = 0;
+    for (int i = 0; i < PDS_GRANTS * n_sf && n < LCS_PDSCH_MAX_BLOCKS; ++i)
+      if (jobs[i].status != 0) s_map[n++] = i;
+    s_n[0] = n;
+  }
+  __syncthreads();
+  const int n = s_n[0];
+  if (tid < n) {
+    const lcs_pdsch_block &b = blk[s_map[tid]];
+    PdsCombBlock v;
+    v.kind = b.kind; v.status = res[2 * s_map[tid] + 1]; v.subframe = b.subframe; v.tbs = b.tbs; v.rv = b.rv;
+    s_blk[tid] = v;
+  }
+  __syncthreads();
+  if (tid == 0) s_n[1] = pds_comb_groups(s_blk, n, si_window, no_sib1, s_work, s_job, &s_n[2]);
+  __syncthreads();
+  if (tid < PDS_COMB_GROUPS) {
+    PdsCombJob *o = &cjobs[tid];
+    if (tid >= s_n[1]) {
+      o->status = 0; o->n_members = 0; o->rule = o->tbs = o->K = o->F = o->f1 = o->f2 = o->tab = o->N = o->max_iter = o->rv_mask = o->n_ok = 0; o->src = -1;
+      for (int m = 0; m < PDS_COMB_MEMBERS; ++m) o->slot[m] = o->block[m] = -1;
+    } else {
+      const PdsCombJob &g = s_job[tid];
+      int src = -1;
+      for (int m = 0; m < PDS_COMB_MEMBERS; ++m) {
+        const int sl = m < g.n_members ? s_map[g.block[m]] : -1;
+        o->slot[m] = sl; o->block[m] = m < g.n_members ? g.block[m] : -1;
+        if (sl >= 0 && src < 0 && (g.n_ok == 0 || res[2 * sl + 1] == LCS_PDSCH_OK)) src = sl;
+      }
+      const PdsJob &j0 = jobs[s_map[g.block[0]]];
+      o->n_members = g.n_members; o->rule = g.rule; o->tbs = g.tbs; o->K = j0.K; o->F = j0.F; o->f1 = j0.f1; o->f2 = j0.f2; o->tab = j0.tab; o->N = j0.N;
+      o->max_iter = j0.max_iter; o->rv_mask = g.rv_mask; o->n_ok = g.n_ok;
+      const bool decode = g.n_ok == 0 && g.n_members >= 2;
+      o->status = g.n_ok > 0 ? LCS_PDSCH_COMB_MEMBER : decode ? LCS_PDSCH_FOLLOW : LCS_PDSCH_COMB_CRC;
+      o->src = decode ? -1 : src;
+    }
+    o->n_overflow = s_n[2]; o->reserved = 0;
+  }
+}
+
+// Combine and decode: one workgroup per group slot, laid out as k_pdsch_dec.  A group that needs no decode ends before any LDS set-up.
+// The gather sums the members' de-rate-matched values in member order (pds_comb_value); from there on it is pds_dec_block.
+__global__ __launch_bounds__(PDS_DEC_THREADS) void k_pdsch_comb_dec(const PdsCombJob *__restrict__ cjobs, const PdsJob *__restrict__ jobs, const double *__restrict__ llr,
+                                                                    size_t llr_stride, const int16_t *__restrict__ rank, double *__restrict__ ws_all,
+                                                                    int *__restrict__ res /*[groups][2]*/, uint8_t *__restrict__ hard_out /*[groups][2240]*/) {
+  const int g = blockIdx.x, tid = threadIdx.x;
+  __shared__ PdsDecLds L;
+  const PdsCombJob job = cjobs[g];
+  if (job.status != LCS_PDSCH_FOLLOW) {                    // the same for the whole workgroup
+    if (tid == 0) { res[2 * g] = 0; res[2 * g + 1] = job.status; }
+    return;
+  }
+  const double *ml[PDS_COMB_MEMBERS];
+  int mG[PDS_COMB_MEMBERS], mbase[PDS_COMB_MEMBERS];
+#pragma unroll
+  for (int m = 0; m < PDS_COMB_MEMBERS; ++m) {
+    const int sl = m < job.n_members ? job.slot[m] : job.slot[0];
+    ml[m] = llr + (size_t)sl * llr_stride; mG[m] = jobs[sl].G; mbase[m] = jobs[sl].base;
+  }
+  const int16_t *rk = rank + (size_t)job.tab * 3 * PDS_MAX_D;
+  pds_dec_block(L, job.K, job.F, job.f1, job.f2, job.max_iter,
+                [&](int s, int k, int) { return pds_comb_value(ml, mG, mbase, job.n_members, job.N, rk[s * PDS_MAX_D + k]); },
+                ws_all + (size_t)g * PDS_WS_DOUBLES, res + 2 * g, hard_out + (size_t)g * PDS_MAX_K, LCS_PDSCH_COMB_OK, LCS_PDSCH_COMB_CRC, LCS_PDSCH_COMB_SILENT);
+}
+
+// The combined record: one workgroup.  Thread g writes group g's fields and counts the OK members whose payload equals the first's;
+// all threads form the payload bytes (from the decisions of the member named by the grouping, or the group's own); thread 0 the head.
+__global__ __launch_bounds__(256) void k_pdsch_comb_fin(const PdsCombJob *__restrict__ cjobs, const int *__restrict__ res, const uint8_t *__restrict__ hard,
+                                                        const int *__restrict__ cres, const uint8_t *__restrict__ chard, lcs_pdsch_comb_info *__restrict__ out) {
+  const int tid = threadIdx.x;
+  constexpr int JOB_INTS = (int)(sizeof(PdsCombJob) / sizeof(int));
+  __shared__ PdsCombJob s_job[PDS_COMB_GROUPS];          // the eight jobs, read once: every loop bound and barrier below depends on LDS alone
+  __shared__ int s_ok[PDS_COMB_GROUPS][PDS_COMB_MEMBERS], s_same[PDS_COMB_GROUPS];
+  if (tid < PDS_COMB_GROUPS * JOB_INTS) reinterpret_cast<int *>(s_job)[tid] = reinterpret_cast<const int *>(cjobs)[tid];
+  __syncthreads();
+  if (tid < PDS_COMB_GROUPS * PDS_COMB_MEMBERS) {
+    const int gi = tid / PDS_COMB_MEMBERS, m = tid % PDS_COMB_MEMBERS, sl = s_job[gi].slot[m];
+    s_ok[gi][m] = s_job[gi].n_ok > 0 && m < s_job[gi].n_members && sl >= 0 && res[2 * sl + 1] == LCS_PDSCH_OK;
+  }
+  __syncthreads();
+  // n_same: all threads compare the tbs decisions of every OK member with the first OK member's (the payload bytes are those bits)
+#pragma unroll 1
+  for (int gi = 0; gi < PDS_COMB_GROUPS; ++gi) {
+    const PdsCombJob &j = s_job[gi];
+    int same = 0;
+#pragma unroll 1
+    for (int m = 0; m < PDS_COMB_MEMBERS; ++m) {
+      if (!s_ok[gi][m]) continue;                          // (the same for the whole workgroup)
+      int diff = 0;
+      for (int i = tid; i < j.tbs; i += 256) diff |= hard[(size_t)j.slot[m] * PDS_MAX_K + j.F + i] != hard[(size_t)j.src * PDS_MAX_K + j.F + i];
+      same += !__syncthreads_or(diff);
+    }
+    if (tid == 0) s_same[gi] = same;
+  }
+  __syncthreads();
+  if (tid < PDS_COMB_GROUPS) {
+    const PdsCombJob &j = s_job[tid];
+    lcs_pdsch_comb_group *o = &out->group[tid];
+    o->n_members = j.n_members; o->rule = j.rule; o->tbs = j.tbs; o->K = j.K; o->F = j.F; o->rv_mask = j.rv_mask; o->n_ok_members = j.n_ok;
+    for (int m = 0; m < PDS_COMB_MEMBERS; ++m) o->member[m] = j.status ? j.block[m] : 0;
+    o->n_iter = cres[2 * tid]; o->status = cres[2 * tid + 1]; o->reserved[0] = o->reserved[1] = 0;
+    o->n_same = s_same[tid];
+  }
+  for (int i = tid; i < PDS_COMB_GROUPS * LCS_PDSCH_PAYLOAD; i += 256) {
+    const int gi = i / LCS_PDSCH_PAYLOAD, t = i - gi * LCS_PDSCH_PAYLOAD;
+    const PdsCombJob &j = s_job[gi];
+    const int st = cres[2 * gi + 1];
+    uint8_t v = 0;
+    if (st == LCS_PDSCH_COMB_MEMBER || st == LCS_PDSCH_COMB_OK || st == LCS_PDSCH_COMB_CRC)
+      v = pds_payload_byte(j.src >= 0 ? hard + (size_t)j.src * PDS_MAX_K : chard + (size_t)gi * PDS_MAX_K, j.F, j.tbs, t);
+    out->group[gi].payload[t] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int n = 0;
+    for (int gi = 0; gi < PDS_COMB_GROUPS; ++gi) n += s_job[gi].status != 0;
+    pds_comb_summary(out, n, s_job[0].n_overflow);
+  }
 }
 
 // ------------------------------------------------------------------ the record: one workgroup
@@ -268,11 +420,15 @@ int pdsch_forced_table(lcs_ctx *c, int f, int K, int F) {
 }
 }  // namespace
 
-int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps) {
+int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps,
+                     const PdschCombPlan *comb) {
   lcs_ctx::Pdsch &p = c->pdsch;
   lcs_ctx::MeasWide &w = c->meas_wide;
   int rc;
   if (n_sf <= 0 || n_sf > PCF_MAX_SF) { c->err = "pdsch: no such number of subframes"; return LCS_ERR_BAD_ARG; }
+  if (comb && ((rc = p.cjob.reserve(c, (size_t)PDS_COMB_GROUPS * sizeof(PdsCombJob) / sizeof(int))) || (rc = p.cres.reserve(c, 2 * PDS_COMB_GROUPS)) ||
+               (rc = p.chard.reserve(c, (size_t)PDS_COMB_GROUPS * PDS_MAX_K)) || (rc = p.cws.reserve(c, (size_t)PDS_COMB_GROUPS * PDS_WS_DOUBLES)) ||
+               (rc = p.crec.reserve(c, 1)))) return rc;
   const int n_symb = cell.cp_type == LCS_CP_NORMAL ? 7 : 6, id = cell.n_id_2 + 3 * cell.n_id_1, ports = pcf_ports(cell.n_ports);
   if ((rc = pdsch_tables(c))) return rc;
   PdsPlanIn in;
@@ -311,6 +467,18 @@ int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const i
                      (const int16_t *)p.rank.get(), p.ws.get(), p.res.get(), p.hard.get());
   HIPCHK(c, hipGetLastError());
   p.last_stride = llr_stride; p.last_n_sf = n_sf;
+  if (comb) {
+    PdsCombJob *cjobs = reinterpret_cast<PdsCombJob *>(p.cjob.get());
+    hipLaunchKernelGGL(k_pdsch_comb_group, dim3(1), dim3(64), 0, c->stream, (const lcs_pdsch_block *)p.blk.get(), (const PdsJob *)jobs, (const int *)p.res.get(), cjobs, n_sf,
+                       comb->si_window, comb->no_sib1);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_pdsch_comb_dec, dim3(PDS_COMB_GROUPS), dim3(PDS_DEC_THREADS), 0, c->stream, (const PdsCombJob *)cjobs, (const PdsJob *)jobs, (const double *)p.llr.get(),
+                       llr_stride, (const int16_t *)p.rank.get(), p.cws.get(), p.cres.get(), p.chard.get());
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_pdsch_comb_fin, dim3(1), dim3(256), 0, c->stream, (const PdsCombJob *)cjobs, (const int *)p.res.get(), (const uint8_t *)p.hard.get(),
+                       (const int *)p.cres.get(), (const uint8_t *)p.chard.get(), p.crec.get());
+    HIPCHK(c, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_pdsch_fin, dim3(1), dim3(256), 0, c->stream, (const lcs_pdsch_block *)p.blk.get(), (const PdsJob *)jobs, (const int *)p.res.get(),
                      (const uint8_t *)p.hard.get(), p.rec.get(), n_sf, dl_mask, n_rb, ports);
   HIPCHK(c, hipGetLastError());

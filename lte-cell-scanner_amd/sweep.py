@@ -207,7 +207,8 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
-                     carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False):
+                     carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False,
+                     pdsch_comb=False):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -229,6 +230,10 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     pdsch=True (or a capi.PdschCfg) also follows the format 1A grants of that search space into the PDSCH (Searcher.pdsch_wide, with
     the PDCCH configuration that pdcch names or, without one, its defaults) from the same buffer, mask and slots: a dict cell gets
     cell["pdsch"] (a PdschInfo, or None as for the PDCCH), and the PdschInfo is appended to entry k's tuple.
+    pdsch_comb=True (or a capi.PdschCombCfg) takes Searcher.pdsch_comb_wide for that step (it implies pdsch): the redundancy versions
+    of SIB1 (and, with an si_window in the configuration, of other SI messages) are combined.  A dict cell also gets
+    cell["pdsch_comb"] (a PdschCombInfo, or None) and, where the payload of a rule-1 group that passed a CRC parses,
+    cell["sib1"] = capi.sib1_fields(...); the PdschCombInfo is appended to entry k's tuple after the PdschInfo.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -321,18 +326,30 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                 if d is not None:
                     d["pdcch"] = pd
                 rec = (rec if isinstance(rec, tuple) else (rec,)) + (pd,)
-            if pdsch:
-                ps = None
+            if pdsch or pdsch_comb:
+                ps = pc = None
                 if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
                     cfg = pdcch
                     if cfg is True or not cfg:
                         tdd = searcher.duplex != capi.DUPLEX_FDD
                         cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
-                    ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg,
-                                             None if pdsch is True else pdsch, n_cap=n_cap)
+                    pcfg = None if pdsch is True or not pdsch else pdsch
+                    if pdsch_comb:
+                        ps, pc = searcher.pdsch_comb_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg,
+                                                          None if pdsch_comb is True else pdsch_comb, n_cap=n_cap)
+                    else:
+                        ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg, n_cap=n_cap)
                 if d is not None:
                     d["pdsch"] = ps
                 rec = (rec if isinstance(rec, tuple) else (rec,)) + (ps,)
+                if pdsch_comb:
+                    if d is not None:
+                        d["pdsch_comb"] = pc
+                        sib = [capi.sib1_fields(g["bytes"]) for g in (pc.groups() if pc is not None else []) if g["rule"] == 1 and g["crc_ok"]]
+                        sib = [x for x in sib if x is not None]
+                        if sib:
+                            d["sib1"] = sib[0]
+                    rec = rec + (pc,)
             row.append(rec)
         out.append(row)
     return out

@@ -793,6 +793,37 @@ def sib1_message(f):
     return np.array(out, np.uint8)
 
 
+def sib1_schedule(message, n_rb, sfn0, rb_start=0, n_prb=None, L=4, cce=0, tdd=False, mcs=None):
+    """The `pdcch` / `pdsch` callables (of cell_waveform_wide and make_wideband_cell's cells) of a SIB1 schedule: the same message
+    (bits; padded with zeros to the smallest transport block size of format 1A's TBS column 2 that holds it) in subframe 5 of every
+    frame whose number sfn0 + frame is even, with the redundancy version capi.sib1_rv(sfn0 + frame), granted by a format 1A DCI
+    with the SI-RNTI on L CCEs from `cce`; nothing in any other subframe.  mcs: a larger transport block than the message needs (more
+    padding).  -> (pdcch, pdsch, dict(mcs, tbs, bits))"""
+    n_prb = min(n_rb, 6) if n_prb is None else int(n_prb)
+    message = np.asarray(message, np.uint8)
+    mcs = max(next(m for m in range(27) if capi.tbs_1a(m, 0) >= len(message)), 0 if mcs is None else int(mcs))
+    tbs = capi.tbs_1a(mcs, 0)
+    bits = np.concatenate([message, np.zeros(tbs - len(message), np.uint8)])
+    riv = n_rb * (n_prb - 1) + rb_start if n_prb - 1 <= n_rb // 2 else n_rb * (n_rb - n_prb + 1) + (n_rb - 1 - rb_start)
+    size = capi.dci_common_sizes(n_rb, tdd)[0]
+
+    def dci(rv):
+        out = []
+        for v, n in ((1, 1), (0, 1), (riv, (n_rb * (n_rb + 1) // 2 - 1).bit_length()), (mcs, 5), (0, 4 if tdd else 3), (0, 1), (rv, 2), (0, 2)):
+            out += [(v >> (n - 1 - i)) & 1 for i in range(n)]
+        return out + [0] * (size - len(out))
+
+    def on(frame, sf):
+        return sf == 5 and (sfn0 + frame) % 2 == 0
+
+    def pdcch(frame, sf):
+        return [dict(rnti=0xFFFF, bits=dci(capi.sib1_rv(sfn0 + frame)), L=L, cce=cce)] if on(frame, sf) else []
+
+    def pdsch(frame, sf):
+        return [dict(rnti=0xFFFF, rb_start=rb_start, n_prb=n_prb, mcs=mcs, tpc=0, rv=capi.sib1_rv(sfn0 + frame), bits=bits)] if on(frame, sf) else []
+    return pdcch, pdsch, dict(mcs=mcs, tbs=tbs, bits=bits)
+
+
 def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
                        tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None, pdsch=None):
     """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,

@@ -41,12 +41,16 @@ def pack_1a(n_rb, start, length, mcs, rv, tpc, size):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="A/B runs: load this build of liblcs_amd.so instead of the in-tree one")
+    ap.add_argument("--quick", action="store_true", help="the (4, 25) shapes only")
     a = ap.parse_args()
     import torch
     pkg = load_pkg()
+    if a.lib:
+        pkg.capi.LIB_PATH = os.path.abspath(a.lib)
     n_ofdm = 280
     doc = {"n_ofdm": n_ofdm, "subframes": 20, "stage": []}
-    for R, n_rb in ((4, 25), (16, 100)):
+    for R, n_rb in (((4, 25),) if a.quick else ((4, 25), (16, 100))):
         sizes = pkg.capi.dci_common_sizes(n_rb)
         for n_ports in (2, 4):
             tbs = pkg.capi.tbs_1a(26, 1)
