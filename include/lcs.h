@@ -441,6 +441,52 @@ typedef struct lcs_pdsch_info {
   lcs_pdsch_block block[LCS_PDSCH_MAX_BLOCKS];
 } lcs_pdsch_info;         /* 10832 bytes */
 
+/* Distributed allocations and format 1C (lcs_set_pdsch_alloc, lcs_pdsch_last_alloc below): a setting of the context that the PDSCH
+ * calls read; zero = the stage as stated above, in which a distributed 1A grant is listed as LCS_PDSCH_DISTRIBUTED and format 1C is
+ * not read.  THE RULE (pdsch.h, host and device; this project's reading of 36.211 6.2.3.2, 36.212 5.3.3.1.3 / .4, 36.213 7.1.6.3 /
+ * 7.1.7.2.3 and 36.321 5.3.1, WRITTEN FROM MEMORY OF THE STANDARD; what pins it is said in pdsch.h and DESIGN.md):
+ *   gap         N_gap,1 = ceil(n_rb / 2) for n_rb 6 .. 10, 4 for 11, 8 for 12 .. 19, 12 for 20 .. 26, 18 for 27 .. 44, 27 for 45 .. 63,
+ *               32 for 64 .. 79, 48 for 80 .. 110; N_gap,2 = 9 for 50 .. 63, 16 for 64 .. 110, none below 50
+ *   sizes       N_VRB = 2 min(N_gap, n_rb - N_gap) (gap 1), floor(n_rb / (2 N_gap)) 2 N_gap (gap 2); the interleaving unit N~ = N_VRB
+ *               (gap 1), 2 N_gap (gap 2); P = 1 / 2 / 3 / 4 for n_rb <= 10 / 26 / 63 / 110; N_row = ceil(N~ / (4 P)) P; N_null =
+ *               4 N_row - N~
+ *   map         VRB v: t = v mod N~, o = N~ floor(v / N~), a = 2 N_row (t mod 2) + floor(t / 2), b = N_row (t mod 4) + floor(t / 4).
+ *               Even slot: with N_null != 0 and t >= N~ - N_null, r = a - N_row (t odd) or a - N_row + N_null / 2 (t even); with
+ *               N_null != 0, t < N~ - N_null and t mod 4 >= 2, r = b - N_null / 2; otherwise r = b.  Odd slot: r <- (r + N~ / 2)
+ *               mod N~.  PRB = o + (r < N~ / 2 ? r : r + N_gap - N~ / 2)
+ *   1A          (flags bit 0) a grant with the distributed bit set: fields as before; (rb_start, n_prb) from the RIV read with n_rb
+ *               are VRBs; rb_start + n_prb > N_VRB gives LCS_PDSCH_BAD_ALLOC; gap 2 iff n_rb >= 50 and the NDI bit is 1
+ *   1C          (flags bit 1) the accepted entries at the PDCCH configuration's other size index, 1 - i_1a.  Bits in the order sent:
+ *               one gap bit iff n_rb >= 50 (1 = gap 2), the RIV, I_TBS in 5 bits.  N_step = 2 for n_rb < 50, else 4; the RIV is
+ *               ceil(log2(v1 (v1 + 1) / 2)) bits wide, v1 = floor(N_VRB,gap1 / N_step); with N' = floor(N_VRB / N_step) of the
+ *               indicated gap: L' = floor(RIV / N') + 1, S' = RIV mod N', and if L' + S' > N': L' = N' - L' + 2, S' = N' - 1 - S';
+ *               rb_start = N_step S', n_prb = N_step L' (VRBs); RIV >= N' (N' + 1) / 2 gives LCS_PDSCH_BAD_ALLOC.  Always distributed
+ *               and QPSK; mcs = I_TBS; tbs = entry I_TBS of 40, 56, 72, 120, 136, 144, 176, 208, 224, 256, 280, 296, 328, 336, 392, 488,
+ *               552, 600, 632, 696, 776, 840, 904, 1000, 1064, 1128, 1224, 1288, 1384, 1480, 1608, 1736
+ *   1C's rv     format 1C carries none; the block's rv says what was ASSUMED: 0 for paging and RA.  For SI with sfn0 >= 0 (sfn =
+ *               (sfn0 + floor(g / 10)) mod 1024, sf = g mod 10): in subframe 5 of an even frame ceil(3 k / 2) mod 4 with k =
+ *               floor(sfn / 2) mod 4; otherwise, with si_window = w > 0 and w != 15, the same with k = ((10 sfn + sf) mod w) mod 4.
+ *               In every other case 0.  A WRONG ASSUMPTION SHOWS AS STATUS LCS_PDSCH_CRC, not as a wrong payload
+ *   grants      per subframe by ascending candidate slot, then size index; a payload accepted at both sizes is two grants, the same
+ *               payload, RNTI and size found again (L = 4 and L = 8) is one; still at most two are followed
+ *   elements    as above, over the slot's own set of resource blocks: the PRBs of the grant's VRBs in slot 0 for the symbols of the
+ *               first slot, those in slot 1 for the second; within a symbol by ascending column over the set.  The exclusions are
+ *               unchanged; the central 72 columns cut a resource block in half when n_rb is odd
+ * Such a block is listed like any other: rb_start / n_prb are VRBs.  Not read: 1C's rv where sfn0 or the window is unknown or the
+ * window is 15 subframes (0 is assumed), TDD special subframes, distributed forced grants (forced grants are localized). */
+#define LCS_PDSCH_ALLOC_RB 112
+typedef struct lcs_pdsch_alloc_cfg {      /* zero = the stage without distributed allocations and format 1C */
+  int32_t flags;                          /* bit 0: follow distributed 1A grants; bit 1: follow format 1C (needs two PDCCH sizes) */
+  int32_t sfn0;                           /* the frame number of grid subframe 0, 0 .. 1023; -1: unknown */
+  int32_t si_window;                      /* the SI window in subframes, 0 .. 61; 0: unknown */
+  int32_t reserved;
+} lcs_pdsch_alloc_cfg;    /* 16 bytes */
+typedef struct lcs_pdsch_alloc {
+  int32_t format /*0: 1A or forced, 1: 1C*/, distributed, gap /*0: N_gap,1; 1: N_gap,2*/, n_gap /*0: localized*/, n_vrb /*n_rb: localized*/,
+      n_step, n_prb /*entries of each list; 0 where the allocation was not followed or lies outside N_VRB*/, reserved;
+  uint8_t prb[2][LCS_PDSCH_ALLOC_RB];     /* [slot of the subframe][i]: the PRB of VRB rb_start + i */
+} lcs_pdsch_alloc;        /* 256 bytes */
+
 /* The redundancy versions of one SI transport block, combined (lcs_pdsch_comb_wide, lcs_pdsch_comb below: the PDSCH stage, then one
  * more decode per group of blocks that repeat a transport block).  THE RULE (lte-cell-scanner_amd/csrc/pdsch_comb.h, host and device,
  * on top of pdsch.h's functions):
@@ -657,6 +703,16 @@ int lcs_pdsch_comb(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re
  * call's, a slot whose grant was not followed in that call (no grant, or a status other than OK, CRC and SILENT), an n beyond its G,
  * and any call after lcs_turbo_decode, which takes over the stage's job block. */
 int lcs_pdsch_last_soft(lcs_ctx *ctx, int subframe, int which, double *llr_out, int n);
+
+/* Distributed allocations and format 1C (the rule: lcs_pdsch_alloc_cfg above).  lcs_set_pdsch_alloc stores the setting that every later
+ * lcs_pdsch_wide / lcs_pdsch / lcs_pdsch_comb_wide / lcs_pdsch_comb call of the context reads; NULL or zeros restores the stage
+ * without them, whose records are what they were.  Refused (LCS_ERR_BAD_ARG, a text): flags outside 0 .. 3, sfn0 outside -1 .. 1023,
+ * si_window outside 0 .. 61, a non-zero reserved field; and, by the PDSCH calls, flags bit 1 with a PDCCH configuration of fewer
+ * than two sizes or whose other size (index 1 - i_1a) is not format 1C's for n_rb.  lcs_pdsch_last_alloc says how block `block_index` of the record of the last such call was allocated: a localized
+ * block gives the trivial lists.  It refuses a null pointer, an index that is no listed block of the last call, and any call after
+ * lcs_turbo_decode. */
+int lcs_set_pdsch_alloc(lcs_ctx *ctx, const lcs_pdsch_alloc_cfg *cfg);
+int lcs_pdsch_last_alloc(lcs_ctx *ctx, int block_index, lcs_pdsch_alloc *out);
 
 /* The turbo decoder of that rule as a stage of its own: d [3][K + 4] de-rate-matched values (d0, d1, d2; positive means 0), K one
  * of the 127 block sizes up to 2240, F fillers, max_iter 1 .. 16 (0 = 8) -> bits_out [K] (one byte per bit, the fillers zero),

@@ -617,6 +617,24 @@ class Searcher:
         self._chk(self._lib.lcs_pdsch_last_soft(self._h, int(subframe), int(which), _dp(out), int(n)), "lcs_pdsch_last_soft")
         return out[:int(n)]
 
+    def set_pdsch_alloc(self, cfg=None):
+        """which grants beyond localized format 1A the pdsch calls of this searcher follow (lcs_set_pdsch_alloc): cfg a
+        capi.PdschAllocCfg, or None for the stage without distributed allocations and format 1C"""
+        self._chk(self._lib.lcs_set_pdsch_alloc(self._h, C.byref(cfg) if cfg is not None else None), "lcs_set_pdsch_alloc")
+        self._pdsch_alloc = cfg
+
+    @property
+    def pdsch_alloc(self):
+        """the setting last given to set_pdsch_alloc (None: the stage without distributed allocations and format 1C)"""
+        return getattr(self, "_pdsch_alloc", None)
+
+    def pdsch_last_alloc(self, block_index: int) -> dict:
+        """how block `block_index` of the last pdsch call's record was allocated (lcs_pdsch_last_alloc): format "1a" / "1c",
+        distributed, gap, n_gap, n_vrb, n_step, n_prb and prb [2][n_prb], the PRBs of its VRBs in the subframe's two slots"""
+        out = capi.PdschAlloc()
+        self._chk(self._lib.lcs_pdsch_last_alloc(self._h, int(block_index), C.byref(out)), "lcs_pdsch_last_alloc")
+        return out.as_dict()
+
     def turbo_decode(self, d, K: int, F: int = 0, max_iter: int = 0):
         """The stage's turbo decoder alone (lcs_turbo_decode): d [3][K + 4] de-rate-matched values, positive means 0
         -> (bits [K] uint8 with the fillers zero, iterations run, whether the CRC24A over bits F .. K - 1 is zero)"""

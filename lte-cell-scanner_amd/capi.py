@@ -467,6 +467,114 @@ class PdschInfo(C.Structure):
 
 assert C.sizeof(PdschCfg) == 112 and C.sizeof(PdschBlock) == 336 and C.sizeof(PdschInfo) == 10832
 
+# ---- distributed allocations and format 1C (include/lcs.h: lcs_pdsch_alloc_cfg; the rule is written from memory of the standard) ----
+PDSCH_ALLOC_RB = 112
+# 36.213 table 7.1.7.2.3-1: the transport block sizes of format 1C, as pdsch.h's copy
+_TBS_1C = [40, 56, 72, 120, 136, 144, 176, 208, 224, 256, 280, 296, 328, 336, 392, 488, 552, 600, 632, 696, 776, 840, 904, 1000, 1064, 1128, 1224, 1288, 1384, 1480,
+           1608, 1736]
+
+
+def tbs_1c(i: int) -> int:
+    """the transport block size of a format 1C grant with I_TBS = i (36.213 7.1.7.2.3)"""
+    return _TBS_1C[int(i)]
+
+
+def dvrb_gap(n_rb: int):
+    """(N_gap,1, N_gap,2 or None) of an n_rb cell (36.211 table 6.2.3.2-1)"""
+    n_rb = int(n_rb)
+    g1 = -(-n_rb // 2) if n_rb <= 10 else 4 if n_rb == 11 else 8 if n_rb <= 19 else 12 if n_rb <= 26 else 18 if n_rb <= 44 else 27 if n_rb <= 63 else 32 if n_rb <= 79 else 48
+    return g1, (None if n_rb < 50 else 9 if n_rb <= 63 else 16)
+
+
+def dvrb_sizes(n_rb: int, gap: int) -> dict:
+    """n_gap, n_vrb, the interleaving unit, n_row and n_null of gap index 0 (N_gap,1) or 1 (N_gap,2; n_rb >= 50)"""
+    n_rb = int(n_rb)
+    n_gap = dvrb_gap(n_rb)[1 if gap else 0]
+    if n_gap is None:
+        raise ValueError("dvrb: no second gap below 50 resource blocks")
+    n_vrb = (n_rb // (2 * n_gap)) * 2 * n_gap if gap else 2 * min(n_gap, n_rb - n_gap)
+    unit = 2 * n_gap if gap else n_vrb
+    p = 1 if n_rb <= 10 else 2 if n_rb <= 26 else 3 if n_rb <= 63 else 4
+    n_row = -(-unit // (4 * p)) * p
+    return dict(n_gap=n_gap, n_vrb=n_vrb, unit=unit, n_row=n_row, n_null=4 * n_row - unit)
+
+
+def dvrb_prb(n_rb: int, gap: int, vrb: int, slot: int) -> int:
+    """the PRB that distributed VRB `vrb` takes in a slot of that parity (36.211 6.2.3.2)"""
+    z = dvrb_sizes(n_rb, gap)
+    unit, n_row, n_null = z["unit"], z["n_row"], z["n_null"]
+    if not 0 <= int(vrb) < z["n_vrb"]:
+        raise ValueError("dvrb_prb: the VRB is outside N_VRB")
+    t, o = int(vrb) % unit, unit * (int(vrb) // unit)
+    a, b = 2 * n_row * (t % 2) + t // 2, n_row * (t % 4) + t // 4
+    r = b
+    if n_null and t >= unit - n_null:
+        r = a - n_row if t % 2 else a - n_row + n_null // 2
+    elif n_null and t % 4 >= 2:
+        r = b - n_null // 2
+    if int(slot) & 1:
+        r = (r + unit // 2) % unit
+    return o + (r if r < unit // 2 else r + z["n_gap"] - unit // 2)
+
+
+def dci_1c_riv_bits(n_rb: int) -> int:
+    v1 = dvrb_sizes(n_rb, 0)["n_vrb"] // (2 if int(n_rb) < 50 else 4)
+    return (v1 * (v1 + 1) // 2 - 1).bit_length()
+
+
+def dci_1c_fields(bits, n_rb: int) -> dict:
+    """The fields of a format 1C payload (36.212 5.3.3.1.4).  bits: the payload as an int (bit t = the t-th bit sent) or a sequence of
+    bits in the order sent -> gap, riv, riv_ok, rb_start and n_rb_alloc (VRBs), n_step, i_tbs, tbs"""
+    n_rb = int(n_rb)
+    size = (1 if n_rb >= 50 else 0) + dci_1c_riv_bits(n_rb) + 5
+    if isinstance(bits, int):
+        bits = [(bits >> t) & 1 for t in range(size)]
+    bits = [int(b) for b in bits]
+    pos = [0]
+
+    def take(n):
+        v = 0
+        for b in bits[pos[0]:pos[0] + n]:
+            v = (v << 1) | b
+        pos[0] += n
+        return v
+    gap = take(1) if n_rb >= 50 else 0
+    step = 2 if n_rb < 50 else 4
+    riv = take(dci_1c_riv_bits(n_rb))
+    n = dvrb_sizes(n_rb, gap)["n_vrb"] // step
+    length, start = riv // n + 1, riv % n
+    if length + start > n:
+        length, start = n - length + 2, n - 1 - start
+    i_tbs = take(5)
+    return dict(gap=gap, riv=riv, riv_ok=riv < n * (n + 1) // 2, rb_start=step * start, n_rb_alloc=step * length, n_step=step, i_tbs=i_tbs, tbs=_TBS_1C[i_tbs])
+
+
+class PdschAllocCfg(C.Structure):
+    """lcs_pdsch_alloc_cfg.  PdschAllocCfg.make(distributed, format_1c, sfn0, si_window): which grants beyond localized 1A the PDSCH
+    calls follow; sfn0 = the frame number of grid subframe 0 (-1: unknown) and si_window in subframes (0: unknown) give a 1C SI
+    grant its assumed redundancy version"""
+    _fields_ = [("flags", C.c_int32), ("sfn0", C.c_int32), ("si_window", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, distributed=False, format_1c=False, sfn0=-1, si_window=0) -> "PdschAllocCfg":
+        o = cls()
+        o.flags, o.sfn0, o.si_window = (1 if distributed else 0) | (2 if format_1c else 0), int(sfn0), int(si_window)
+        return o
+
+
+class PdschAlloc(C.Structure):
+    """lcs_pdsch_alloc: how a listed block was allocated (lcs_pdsch_last_alloc)"""
+    _fields_ = [(k, C.c_int32) for k in ("format", "distributed", "gap", "n_gap", "n_vrb", "n_step", "n_prb", "reserved")] + [("prb", (C.c_uint8 * PDSCH_ALLOC_RB) * 2)]
+
+    def as_dict(self) -> dict:
+        d = {k: int(getattr(self, k)) for k in ("distributed", "gap", "n_gap", "n_vrb", "n_step", "n_prb")}
+        d["format"] = "1c" if self.format else "1a"
+        d["prb"] = [[int(self.prb[s][i]) for i in range(self.n_prb)] for s in range(2)]
+        return d
+
+
+assert C.sizeof(PdschAllocCfg) == 16 and C.sizeof(PdschAlloc) == 256
+
 # ---- the redundancy versions of an SI transport block, combined (include/lcs.h: lcs_pdsch_comb_info) ----
 PDSCH_COMB_MAX_GROUPS, PDSCH_COMB_MAX_MEMBERS, PDSCH_COMB_N_STATUS = 8, 4, 5
 PDSCH_COMB_MEMBER, PDSCH_COMB_OK, PDSCH_COMB_CRC, PDSCH_COMB_SILENT = range(1, 5)
@@ -590,6 +698,7 @@ EXPORTS = [
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
     "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
+    "lcs_set_pdsch_alloc", "lcs_pdsch_last_alloc",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
     "lcs_batch_collect", "lcs_batch_readback", "lcs_batch_enqueue_host", "lcs_host_alloc", "lcs_host_free", "lcs_device_alloc", "lcs_device_free", "lcs_device_upload", "lcs_device_count",
@@ -683,6 +792,9 @@ def _declare(L: C.CDLL) -> C.CDLL:
     if hasattr(L, "lcs_pdsch_comb_wide"):      # (likewise)
         L.lcs_pdsch_comb_wide.argtypes = L.lcs_pdsch_wide.argtypes + [C.POINTER(PdschCombCfg), C.POINTER(PdschCombInfo)]
         L.lcs_pdsch_comb.argtypes = L.lcs_pdsch.argtypes + [C.POINTER(PdschCombCfg), C.POINTER(PdschCombInfo)]
+    if hasattr(L, "lcs_set_pdsch_alloc"):      # (likewise)
+        L.lcs_set_pdsch_alloc.argtypes = [vp, C.POINTER(PdschAllocCfg)]
+        L.lcs_pdsch_last_alloc.argtypes = [vp, C.c_int, C.POINTER(PdschAlloc)]
     L.lcs_xcorr_pss.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_uint8, C.c_double, C.c_double, C.c_double,
                                 dp, ip, fp, fp, dp, fp, dp, u16p, u16p]
     L.lcs_peak_search.argtypes = [vp, dp, ip, dp, dp, C.c_uint16, C.c_double, C.c_double, fp, C.c_uint8, cp, C.c_int,

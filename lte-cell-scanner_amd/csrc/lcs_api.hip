@@ -1315,6 +1315,11 @@ int pdsch_resolve(lcs_ctx *c, const char *who, const lcs_pdcch_cfg *cfg, const P
   p->i_1a = pc->i_1a; p->max_iter = pc->max_iter ? pc->max_iter : 8; p->rnti_mask = pc->rnti_mask ? pc->rnti_mask : 7; p->n_forced = pc->n_forced;
   p->tdd = 0;
   for (int i = 0; i < 10; ++i) p->tdd = p->tdd || cfg->phich_mi[i] >= 0;
+  const lcs_pdsch_alloc_cfg &al = c->pdsch.alloc;           // lcs_set_pdsch_alloc: the launch takes it as an argument
+  if ((al.flags & 2) && plan.n_sizes < 2) return wide_refused(c, who, "format 1C is followed (lcs_set_pdsch_alloc) but the PDCCH configuration has one size");
+  if ((al.flags & 2) && plan.size[1 - pc->i_1a] != (n_rb >= 50 ? 1 : 0) + pds_1c_riv_bits(n_rb) + 5)
+    return wide_refused(c, who, "format 1C is followed (lcs_set_pdsch_alloc) but the PDCCH configuration's other size is not format 1C's for this bandwidth");
+  p->alloc_flags = al.flags; p->sfn0 = al.sfn0; p->si_window = al.si_window;
   const int n_sf = pcf_n_sf(n_ofdm, n_symb);
   for (int f = 0; f < LCS_PDSCH_MAX_FORCED; ++f) {
     p->forced[f] = pc->forced[f];
@@ -1459,6 +1464,42 @@ int lcs_pdsch_last_soft(lcs_ctx *c, int subframe, int which, double *llr_out, in
   if (job.status != LCS_PDSCH_FOLLOW || n > job.G) return wide_refused(c, who, "that grant slot was not followed in the last call, or holds fewer soft bits");
   HIPCHK(c, hipMemcpyAsync(llr_out, p.llr.get() + (size_t)(PDS_GRANTS * subframe + which) * p.last_stride, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
+}
+
+int lcs_set_pdsch_alloc(lcs_ctx *c, const lcs_pdsch_alloc_cfg *cfg) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_set_pdsch_alloc";
+  static const lcs_pdsch_alloc_cfg zero = {0, 0, 0, 0};
+  if (!cfg) cfg = &zero;
+  if (cfg->flags < 0 || cfg->flags > 3) return wide_refused(c, who, "flags is outside 0 .. 3");
+  if (cfg->sfn0 < -1 || cfg->sfn0 > 1023) return wide_refused(c, who, "sfn0 is outside -1 .. 1023");
+  if (cfg->si_window < 0 || cfg->si_window > 61) return wide_refused(c, who, "si_window is outside 0 .. 61");
+  if (cfg->reserved != 0) return wide_refused(c, who, "a non-zero reserved field");
+  c->pdsch.alloc = *cfg;
+  return LCS_OK;
+}
+
+int lcs_pdsch_last_alloc(lcs_ctx *c, int block_index, lcs_pdsch_alloc *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdsch_last_alloc";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  const lcs_ctx::Pdsch &p = c->pdsch;
+  if (block_index < 0 || block_index >= LCS_PDSCH_MAX_BLOCKS || p.last_n_sf <= 0) return wide_refused(c, who, "no such block of the last call");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the grant slots as the plan left them: block i of the record is the i-th slot that holds a grant (k_pdsch_fin).  A diagnostic
+  // query, not a hot path: every call copies the whole job array and one block back and waits for the stream twice
+  std::vector<PdsJob> jobs((size_t)PDS_GRANTS * p.last_n_sf);
+  HIPCHK(c, hipMemcpyAsync(jobs.data(), p.job.get(), sizeof(PdsJob) * jobs.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int slot = -1, n = 0;
+  for (size_t i = 0; i < jobs.size() && slot < 0; ++i)
+    if (jobs[i].status != 0 && n++ == block_index) slot = (int)i;
+  if (slot < 0) return wide_refused(c, who, "no such block of the last call");
+  lcs_pdsch_block b;
+  HIPCHK(c, hipMemcpyAsync(&b, p.blk.get() + slot, sizeof(b), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  pds_alloc_of(p.last_n_rb, b, jobs[(size_t)slot].reserved, out);
   return LCS_OK;
 }
 

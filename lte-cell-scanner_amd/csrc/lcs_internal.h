@@ -423,8 +423,8 @@ struct lcs_ctx : lcs_ctx_queues {
   struct Pdsch {
     Pdcch pdc;                      // the PDCCH's blocks of this stage's own: the PDCCH stage's are not touched
     DevBuf<int> tabs;               // transport block sizes [2][27], QPP (f1, f2) [127][2]
-    DevBuf<int> heads;              // PdsTabHead [2 * 27 + 4]
-    DevBuf<int16_t> rank;           // [2 * 27 + 4][3][2244]: the de-rate-matching ranks
+    DevBuf<int> heads;              // PdsTabHead [2 * 27 + 4 + 32]
+    DevBuf<int16_t> rank;           // [2 * 27 + 4 + 32][3][2244]: the de-rate-matching ranks (1A, forced, 1C)
     DevBuf<uint32_t> jump;          // [320]: to the reference sequence, by 1600 clocks, by 160 2^b clocks
     DevBuf<uint32_t> x1s;           // [256]: the Gold sequence's first register 1600 + 160 j clocks on
     DevBuf<int> sfrow;              // [n_sf]: the grid row of symbol 0 of every subframe that is there whole, else -1
@@ -436,6 +436,10 @@ struct lcs_ctx : lcs_ctx_queues {
     DevBuf<double> ws;              // [n_sf][2][32][8][72]: the forward metrics of the windows
     DevBuf<double> din;             // [3][2244]: lcs_turbo_decode's input
     DevBuf<lcs_pdsch_info> rec;     // [1]
+    DevBuf<unsigned long long> sets;    // [n_sf][2][4]: the two sets of PRBs of every grant slot; allocated by the first call with a non-zero lcs_set_pdsch_alloc
+    lcs_pdsch_alloc_cfg alloc = {0, -1, 0, 0};   // lcs_set_pdsch_alloc: stored here, handed to the launch as an argument
+    bool tables_1c_ready = false;   // the 32 rank tables of format 1C behind the others: built by the first call that follows 1C
+    int last_n_rb = 0;              // of the last call: lcs_pdsch_last_alloc
     // the combined redundancy versions (lcs_pdsch_comb_wide, lcs_pdsch_comb), allocated by the first call of those
     DevBuf<int> cjob;               // PdsCombJob [8]
     DevBuf<int> cres;               // [8][2]: n_iter, status
@@ -661,7 +665,7 @@ int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_s
 // the same into the blocks p (the PDSCH stage keeps a set of its own for the grants it follows) -> p.rec
 int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
 // pdsch.hip
-struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; };
+struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; int alloc_flags, sfn0, si_window; };
 // the PCFICH and PDCCH of rows4 into c->pdsch.pdc, then the grants' blocks -> c->pdsch.rec.  sfrow [n_sf]: the row of c->meas_wide.grid
 // that holds symbol 0 of every subframe whose rows are all there, else -1
 // comb (or null): after the decode the SI blocks are grouped and every group that needs it is decoded from the sum of its members'

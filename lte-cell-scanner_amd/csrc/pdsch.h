@@ -40,6 +40,14 @@ struct PdsJob {
   int status, K, F, f1, f2, tab, G, N, base, max_iter, direct, c_init, row0, n_ctrl, k_lo, k_hi, sf, n_re, tdd, reserved;
 };
 #define LCS_PDSCH_FOLLOW (-1)
+// PdsJob.reserved: how the grant's resource blocks are given
+#define PDS_MODE_SET 1                   // by the grant slot's two sets (the side buffer), not by [k_lo, k_hi)
+#define PDS_MODE_1C 2                    // a format 1C grant
+#define PDS_MODE_GAP2 4                  // N_gap,2
+#define PDS_MODE_UNREAD 8                // a distributed grant that the setting does not follow
+#define PDS_N_1C 32                      // the transport block sizes of format 1C; their rank tables lie behind PDS_TABS
+#define PDS_SET_RB 112                   // room of a slot's list of resource blocks
+#define PDS_SET_WORDS 4                  // a grant slot's sets in the side buffer: [slot of the subframe][lo, hi] 64-bit masks of PRBs
 struct PdsTabHead { int K, F, N, base[4]; };     // N non-nulls of the circular buffer, base[rv]: how many of them lie before k0(rv)
 struct PdsGeom { int n_rb, ports, n_symb, id, sf, tdd, n_ctrl, k_lo, k_hi; };
 
@@ -62,7 +70,7 @@ __host__ __device__ __forceinline__ int pds_pad(int k) { return k + (k >> 5); } 
 #define PDS_PAD_D (PDS_MAX_D + PDS_MAX_D / 32 + 2)
 
 // ------------------------------------------------------------------ the grant
-struct Pds1a { int flag, distributed, rb_start, n_prb, mcs, rv, tpc; };
+struct Pds1a { int flag, distributed, rb_start, n_prb, mcs, rv, tpc, ndi; };
 // format 1A as it is sent with SI-, P- and RA-RNTI (36.212 5.3.3.1.3; capi.dci_1a_fields): bit t of `bits` = the t-th bit sent
 __host__ __device__ __forceinline__ Pds1a pds_1a_fields(unsigned long long bits, int n_rb, int tdd) {
   int pos = 0;
@@ -77,10 +85,101 @@ __host__ __device__ __forceinline__ Pds1a pds_1a_fields(unsigned long long bits,
   f.rb_start = start; f.n_prb = length;
   f.mcs = take(5);
   take(tdd ? 4 : 3);
-  take(1);
+  f.ndi = take(1);
   f.rv = take(2);
   f.tpc = take(2);
   return f;
+}
+
+// ------------------------------------------------------------------ distributed allocations and format 1C (the rule: include/lcs.h,
+// lcs_pdsch_alloc_cfg; 36.211 6.2.3.2, 36.212 5.3.3.1.4, 36.213 7.1.6.3 -- WRITTEN FROM MEMORY OF THE STANDARD.  What pins it:
+// tests/test_pdsch_dvrb_host.py -- every slot's map is a permutation, a VRB's two PRBs lie N_gap apart, the 1C width is the PDCCH
+// table's)
+struct PdsDvrb { int n_gap, n_vrb, unit, n_row, n_null; };      // unit: the interleaving unit N~
+// gap: 0 = N_gap,1; 1 = N_gap,2 (n_rb >= 50 only; n_vrb = 0 below that)
+__host__ __device__ __forceinline__ PdsDvrb pds_dvrb(int n_rb, int gap) {
+  PdsDvrb d;
+  const int g1 = n_rb <= 10 ? (n_rb + 1) / 2 : n_rb == 11 ? 4 : n_rb <= 19 ? 8 : n_rb <= 26 ? 12 : n_rb <= 44 ? 18 : n_rb <= 63 ? 27 : n_rb <= 79 ? 32 : 48;
+  const int g2 = n_rb < 50 ? 0 : n_rb <= 63 ? 9 : 16;
+  const int P = n_rb <= 10 ? 1 : n_rb <= 26 ? 2 : n_rb <= 63 ? 3 : 4;
+  if (gap == 0) { d.n_gap = g1; d.n_vrb = 2 * (g1 < n_rb - g1 ? g1 : n_rb - g1); d.unit = d.n_vrb; }
+  else { d.n_gap = g2; d.n_vrb = g2 ? (n_rb / (2 * g2)) * 2 * g2 : 0; d.unit = 2 * g2; }
+  d.n_row = d.unit ? ((d.unit + 4 * P - 1) / (4 * P)) * P : 0;
+  d.n_null = 4 * d.n_row - d.unit;
+  return d;
+}
+// the PRB of VRB v < n_vrb in a slot of parity `odd`
+__host__ __device__ __forceinline__ int pds_dvrb_prb(const PdsDvrb &d, int v, int odd) {
+  const int t = v % d.unit, o = d.unit * (v / d.unit);
+  const int a = 2 * d.n_row * (t % 2) + t / 2, b = d.n_row * (t % 4) + t / 4;
+  int r = b;
+  if (d.n_null != 0) {
+    if (t >= d.unit - d.n_null) r = (t % 2) ? a - d.n_row : a - d.n_row + d.n_null / 2;
+    else if (t % 4 >= 2) r = b - d.n_null / 2;
+  }
+  if (odd) r = (r + d.unit / 2) % d.unit;
+  return o + (r < d.unit / 2 ? r : r + d.n_gap - d.unit / 2);
+}
+struct Pds1c { int gap, riv, riv_ok, rb_start, n_prb, i_tbs, n_step; };
+__host__ __device__ __forceinline__ int pds_1c_riv_bits(int n_rb) {
+  const int v1 = pds_dvrb(n_rb, 0).n_vrb / (n_rb < 50 ? 2 : 4);
+  int nb = 0;
+  while ((1 << nb) < v1 * (v1 + 1) / 2) nb += 1;
+  return nb;
+}
+// format 1C as it is sent (36.212 5.3.3.1.4): bit t of `bits` = the t-th bit sent
+__host__ __device__ __forceinline__ Pds1c pds_1c_fields(unsigned long long bits, int n_rb) {
+  int pos = 0;
+  auto take = [&](int n) { int v = 0; for (int i = 0; i < n; ++i) v = (v << 1) | (int)((bits >> (pos + i)) & 1ull); pos += n; return v; };
+  Pds1c f;
+  f.gap = n_rb >= 50 ? take(1) : 0;
+  f.n_step = n_rb < 50 ? 2 : 4;
+  f.riv = take(pds_1c_riv_bits(n_rb));
+  const int n = pds_dvrb(n_rb, f.gap).n_vrb / f.n_step;
+  f.riv_ok = f.riv < n * (n + 1) / 2;
+  int length = f.riv / n + 1, start = f.riv % n;
+  if (length + start > n) { length = n - length + 2; start = n - 1 - start; }
+  f.rb_start = f.n_step * start; f.n_prb = f.n_step * length;
+  f.i_tbs = take(5);
+  return f;
+}
+// the setting (lcs_pdsch_alloc_cfg resolved): flags bit 0 follows distributed 1A, bit 1 format 1C at size index i_1c
+struct PdsAllocIn { int flags, sfn0, si_window, i_1c; };
+// the redundancy version a 1C grant of `kind` in grid subframe g is assumed to have
+__host__ __device__ __forceinline__ int pds_1c_rv(int kind, int g, const PdsAllocIn &a) {
+  if (kind != 1 || a.sfn0 < 0) return 0;
+  const int sfn = (a.sfn0 + g / 10) % 1024, sf = g % 10;
+  int k;
+  if (sf == 5 && sfn % 2 == 0) k = (sfn / 2) % 4;
+  else if (a.si_window > 0 && a.si_window != 15) k = ((10 * sfn + sf) % a.si_window) % 4;
+  else return 0;
+  return ((3 * k + 1) / 2) % 4;
+}
+// the two sets of VRBs [v0, v0 + n) (inside n_vrb): m[2 slot], m[2 slot + 1] = PRBs 0 .. 63, 64 .. 127
+__host__ __device__ __forceinline__ void pds_set_masks(const PdsDvrb &d, int v0, int n, unsigned long long (&m)[PDS_SET_WORDS]) {
+  unsigned long long a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+  for (int v = v0; v < v0 + n; ++v) {
+    const int p = pds_dvrb_prb(d, v, 0), q = pds_dvrb_prb(d, v, 1);
+    if (p < 64) a0 |= 1ull << p; else a1 |= 1ull << (p - 64);
+    if (q < 64) b0 |= 1ull << q; else b1 |= 1ull << (q - 64);
+  }
+  m[0] = a0; m[1] = a1; m[2] = b0; m[3] = b1;
+}
+__host__ __device__ __forceinline__ bool pds_set_has(unsigned long long lo, unsigned long long hi, int p) { return p < 64 ? (lo >> p) & 1ull : (hi >> (p - 64)) & 1ull; }
+// cut[0]: the half blocks (six columns) of the set below the central 72 columns, cut[1]: those inside them
+__host__ __device__ __forceinline__ void pds_set_cut(int n_rb, unsigned long long lo, unsigned long long hi, int *cut /*[2]*/) {
+  int below = 0, inside = 0;
+  for (int p = 0; p < n_rb; ++p) {
+    if (!pds_set_has(lo, hi, p)) continue;
+    for (int h = 2 * p; h < 2 * p + 2; ++h) { below += h < n_rb - 6; inside += h >= n_rb - 6 && h < n_rb + 6; }
+  }
+  cut[0] = below; cut[1] = inside;
+}
+// the set's resource blocks in ascending order -> prb[]; returns how many
+__host__ __device__ __forceinline__ int pds_set_list(int n_rb, unsigned long long lo, unsigned long long hi, uint8_t *prb /*[PDS_SET_RB]*/) {
+  int n = 0;
+  for (int p = 0; p < n_rb; ++p) if (pds_set_has(lo, hi, p)) prb[n++] = (uint8_t)p;
+  return n;
 }
 
 // ------------------------------------------------------------------ resource elements
@@ -138,6 +237,41 @@ __host__ __device__ __forceinline__ void pds_elem_at(const PdsGeom &q, const int
   while (i + 1 < 2 * q.n_symb - q.n_ctrl && base[i + 1] <= e) i += 1;
   *l = q.n_ctrl + i;
   *k = pds_col_at(q, *l, e - base[i]);
+}
+
+// The same over a set of resource blocks per slot (q.k_lo, q.k_hi unused).  A half block of six columns lies whole inside or outside
+// the central 72 columns (which cut a resource block in half when n_rb is odd) and keeps 6, 5 or 4 elements in every symbol, so a
+// symbol holds that many times the slot's half blocks outside the cut.  cut [2][2]: pds_set_cut of slot 0, slot 1.
+__host__ __device__ __forceinline__ int pds_set_per_half(const PdsGeom &q, int l) {
+  int m, r;
+  return pds_crs(q, l, &m, &r) ? 6 - 6 / m : 6;
+}
+__host__ __device__ __forceinline__ int pds_set_count(const PdsGeom &q, int n_prb, const int *cut, int l) {
+  return pds_set_per_half(q, l) * (2 * n_prb - (pds_central(q, l) ? cut[2 * (l >= q.n_symb) + 1] : 0));
+}
+__host__ __device__ __forceinline__ int pds_set_bases(const PdsGeom &q, int n_prb, const int *cut, int *base /*[PDS_MAX_SYM + 1]*/) {
+  int n = 0;
+  for (int l = q.n_ctrl; l < 2 * q.n_symb; ++l) { base[l - q.n_ctrl] = n; n += pds_set_count(q, n_prb, cut, l); }
+  base[2 * q.n_symb - q.n_ctrl] = n;
+  return n;
+}
+// element e -> (l, k); prb [2][PDS_SET_RB]: pds_set_list of slot 0, slot 1
+__host__ __device__ __forceinline__ void pds_set_elem_at(const PdsGeom &q, const uint8_t *prb, const int *cut, const int *base, int e, int *l, int *k) {
+  int i = 0;
+  while (i + 1 < 2 * q.n_symb - q.n_ctrl && base[i + 1] <= e) i += 1;
+  const int ll = q.n_ctrl + i, si = ll >= q.n_symb, per = pds_set_per_half(q, ll), r = e - base[i];
+  int h = r / per, j = r - h * per, m = 1, rr = -1;
+  if (pds_central(q, ll) && h >= cut[2 * si]) h += cut[2 * si + 1];
+  pds_crs(q, ll, &m, &rr);
+  int col = 12 * (int)prb[PDS_SET_RB * si + (h >> 1)] + 6 * (h & 1);
+  for (int c = 0; c < 6; ++c) {                // the j-th column of the half block that is no reference element
+    const bool taken = rr >= 0 && (col % m) == rr;
+    if (!taken && j == 0) break;
+    if (!taken) j -= 1;
+    col += 1;
+  }
+  *l = ll;
+  *k = col;
 }
 
 // ------------------------------------------------------------------ channel and soft bits
@@ -307,14 +441,19 @@ __host__ __device__ __forceinline__ void pds_block_zero(lcs_pdsch_block *b) {
   b->subframe = b->slot = b->rnti = b->kind = b->rb_start = b->n_prb = b->mcs = b->rv = b->tbs = b->n_re = b->K = b->F = b->n_iter = b->status = 0;
   for (int i = 0; i < LCS_PDSCH_PAYLOAD; ++i) b->payload[i] = 0;
 }
-// the grant's geometry, sizes and job once its fields stand in *b (rb_start, n_prb, rv, tbs, rnti); tab: its rank table
+// the grant's geometry, sizes and job once its fields stand in *b (rb_start, n_prb, rv, tbs, rnti); tab: its rank table.  mode: PDS_MODE_*;
+// with PDS_MODE_SET rb_start and n_prb are VRBs and set [PDS_SET_WORDS] takes the two sets of PRBs.  ALLOC = false: the instantiation of
+// the stage without the setting, in which nothing of the set-based geometry is compiled
+template <bool ALLOC>
 __host__ __device__ inline void pds_plan_grant(const PdsPlanIn &in, int g, int row0, int cfi, int tab, const int *__restrict__ qpp /*[127][2]*/,
-                                               const PdsTabHead *__restrict__ heads, lcs_pdsch_block *b, PdsJob *j) {
+                                               const PdsTabHead *__restrict__ heads, lcs_pdsch_block *b, PdsJob *j, int mode = 0,
+                                               unsigned long long *set = nullptr) {
   const int sf = g % 10;
-  j->status = 0; j->direct = 0; j->tdd = in.tdd; j->reserved = 0; j->tab = tab; j->max_iter = in.max_iter; j->sf = sf; j->row0 = row0;
+  j->status = 0; j->direct = 0; j->tdd = in.tdd; j->reserved = mode; j->tab = tab; j->max_iter = in.max_iter; j->sf = sf; j->row0 = row0;
   j->K = j->F = j->f1 = j->f2 = j->G = j->N = j->base = j->n_re = j->n_ctrl = j->k_lo = j->k_hi = 0; j->c_init = 0;
   if (b->status) { j->status = b->status; return; }
-  if (b->rb_start < 0 || b->n_prb < 1 || b->rb_start + b->n_prb > in.n_rb) b->status = LCS_PDSCH_BAD_ALLOC;
+  const int n_limit = (ALLOC && (mode & PDS_MODE_SET)) ? pds_dvrb(in.n_rb, (mode & PDS_MODE_GAP2) ? 1 : 0).n_vrb : in.n_rb;
+  if (b->rb_start < 0 || b->n_prb < 1 || b->rb_start + b->n_prb > n_limit) b->status = LCS_PDSCH_BAD_ALLOC;
   else if (in.tdd && (sf == 1 || sf == 6)) b->status = LCS_PDSCH_SPECIAL;
   else if (row0 < 0) b->status = LCS_PDSCH_ROWS;
   else if (cfi < 1 || cfi > 3) b->status = LCS_PDSCH_NO_CFI;
@@ -325,7 +464,16 @@ __host__ __device__ inline void pds_plan_grant(const PdsPlanIn &in, int g, int r
   q.n_rb = in.n_rb; q.ports = in.ports; q.n_symb = in.n_symb; q.id = in.id; q.sf = sf; q.tdd = in.tdd;
   q.n_ctrl = pdc_n_ctrl(cfi, in.n_rb); q.k_lo = 12 * b->rb_start; q.k_hi = 12 * (b->rb_start + b->n_prb);
   int base[PDS_MAX_SYM + 1];
-  b->n_re = pds_bases(q, base);
+  if (ALLOC && (mode & PDS_MODE_SET)) {
+    unsigned long long m[PDS_SET_WORDS];
+    int cut[4];
+    pds_set_masks(pds_dvrb(in.n_rb, (mode & PDS_MODE_GAP2) ? 1 : 0), b->rb_start, b->n_prb, m);
+    pds_set_cut(in.n_rb, m[0], m[1], cut);
+    pds_set_cut(in.n_rb, m[2], m[3], cut + 2);
+    for (int i = 0; i < PDS_SET_WORDS; ++i) set[i] = m[i];
+    b->n_re = pds_set_bases(q, b->n_prb, cut, base);
+    q.k_lo = q.k_hi = 0;
+  } else b->n_re = pds_bases(q, base);
   b->K = pds_k_at(ki); b->F = b->K - (b->tbs + 24);
   j->status = LCS_PDSCH_FOLLOW;
   j->K = b->K; j->F = b->F; j->f1 = qpp[2 * ki]; j->f2 = qpp[2 * ki + 1];
@@ -333,13 +481,19 @@ __host__ __device__ inline void pds_plan_grant(const PdsPlanIn &in, int g, int r
   j->c_init = (int)pds_c_init(b->rnti, sf, in.id);
   j->n_ctrl = q.n_ctrl; j->k_lo = q.k_lo; j->k_hi = q.k_hi; j->n_re = b->n_re;
 }
-// the PDS_GRANTS grant slots of grid subframe g: from the forced list, or from the accepted format 1A entries of the PDCCH record.
-// row0: the grid row of the subframe's symbol 0 when every row of the subframe is there, else -1.  tbs_tab [2][27].
-__host__ __device__ inline void pds_plan_sf(const PdsPlanIn &in, int g, int row0, const lcs_pdcch_info *__restrict__ pdc, const int *__restrict__ tbs_tab,
-                                            const int *__restrict__ qpp, const PdsTabHead *__restrict__ heads, lcs_pdsch_block *blk /*[2]*/, PdsJob *job /*[2]*/) {
+// the PDS_GRANTS grant slots of grid subframe g: from the forced list, or from the accepted entries of the PDCCH record -- format 1A
+// at size index i_1a and, where the setting follows it, format 1C at i_1c; by ascending candidate slot, then size index.
+// row0: the grid row of the subframe's symbol 0 when every row of the subframe is there, else -1.  tbs_tab [2][27]; tbs_1c [32] and
+// sets [PDS_GRANTS][PDS_SET_WORDS] are read and written with a non-zero setting only.  ALLOC = false (al.flags = 0): format 1A's size alone is walked
+template <bool ALLOC>
+__host__ __device__ inline void pds_plan_sf_alloc(const PdsPlanIn &in, const PdsAllocIn &al, int g, int row0, const lcs_pdcch_info *__restrict__ pdc,
+                                                  const int *__restrict__ tbs_tab, const int *__restrict__ tbs_1c, const int *__restrict__ qpp,
+                                                  const PdsTabHead *__restrict__ heads, lcs_pdsch_block *blk /*[2]*/, PdsJob *job /*[2]*/, unsigned long long *sets) {
   int n = 0;
   const int cfi = pdc->cfi[g];
   for (int u = 0; u < PDS_GRANTS; ++u) pds_block_zero(&blk[u]);
+  if (ALLOC && al.flags)
+    for (int i = 0; i < PDS_GRANTS * PDS_SET_WORDS; ++i) sets[i] = 0ull;
   if (in.n_forced > 0) {
     for (int f = 0; f < in.n_forced && n < PDS_GRANTS; ++f) {
       const lcs_pdsch_grant &fg = in.forced[f];
@@ -347,31 +501,66 @@ __host__ __device__ inline void pds_plan_sf(const PdsPlanIn &in, int g, int row0
       lcs_pdsch_block *b = &blk[n];
       b->subframe = g; b->slot = f; b->rnti = fg.rnti; b->kind = pdc_kind((uint32_t)fg.rnti); b->rb_start = fg.rb_start; b->n_prb = fg.n_prb;
       b->mcs = -1; b->rv = fg.rv & 3; b->tbs = fg.tbs;
-      pds_plan_grant(in, g, row0, cfi, 2 * PDS_N_MCS + f, qpp, heads, b, &job[n]);
+      pds_plan_grant<ALLOC>(in, g, row0, cfi, 2 * PDS_N_MCS + f, qpp, heads, b, &job[n]);
       n += 1;
     }
   } else if (cfi) {
     unsigned long long seen_bits[PDS_GRANTS];
     uint32_t seen_rnti[PDS_GRANTS];
+    int seen_size[PDS_GRANTS];
     for (int s = 0; s < PDC_SLOTS && n < PDS_GRANTS; ++s) {
-      const lcs_pdcch_dec &d = pdc->dec[g][s][in.i_1a];
-      if (!(d.flags & 2) || !(d.bits & 1ull) || !(pdc_kind(d.rnti_x) & in.rnti_mask)) continue;
-      bool dup = false;
-      for (int u = 0; u < n; ++u) dup = dup || (seen_bits[u] == d.bits && seen_rnti[u] == d.rnti_x);
-      if (dup) continue;
-      seen_bits[n] = d.bits; seen_rnti[n] = d.rnti_x;
-      const Pds1a f = pds_1a_fields(d.bits, in.n_rb, in.tdd);
-      lcs_pdsch_block *b = &blk[n];
-      b->subframe = g; b->slot = s; b->rnti = (int)d.rnti_x; b->kind = pdc_kind(d.rnti_x); b->rb_start = f.rb_start; b->n_prb = f.n_prb;
-      b->mcs = f.mcs; b->rv = f.rv;
-      if (f.distributed) b->status = LCS_PDSCH_DISTRIBUTED;
-      else if (f.mcs > 26) b->status = LCS_PDSCH_MCS;
-      else b->tbs = tbs_tab[PDS_N_MCS * (f.tpc & 1) + f.mcs];
-      pds_plan_grant(in, g, row0, cfi, PDS_N_MCS * (f.tpc & 1) + (f.mcs <= 26 ? f.mcs : 0), qpp, heads, b, &job[n]);
-      n += 1;
+      for (int i = ALLOC ? 0 : in.i_1a; i < (ALLOC ? PDC_SIZES : in.i_1a + 1) && n < PDS_GRANTS; ++i) {
+        const bool is_1c = ALLOC && (al.flags & 2) && i == al.i_1c;
+        if (i != in.i_1a && !is_1c) continue;
+        const lcs_pdcch_dec &d = pdc->dec[g][s][i];
+        if (!(d.flags & 2) || (!is_1c && !(d.bits & 1ull)) || !(pdc_kind(d.rnti_x) & in.rnti_mask)) continue;
+        bool dup = false;
+        for (int u = 0; u < n; ++u) dup = dup || (seen_bits[u] == d.bits && seen_rnti[u] == d.rnti_x && seen_size[u] == i);
+        if (dup) continue;
+        seen_bits[n] = d.bits; seen_rnti[n] = d.rnti_x; seen_size[n] = i;
+        lcs_pdsch_block *b = &blk[n];
+        b->subframe = g; b->slot = s; b->rnti = (int)d.rnti_x; b->kind = pdc_kind(d.rnti_x);
+        int tab = 0, mode = 0;
+        if (is_1c) {
+          const Pds1c f = pds_1c_fields(d.bits, in.n_rb);
+          b->rb_start = f.rb_start; b->n_prb = f.n_prb; b->mcs = f.i_tbs; b->rv = pds_1c_rv(b->kind, g, al);
+          mode = PDS_MODE_SET | PDS_MODE_1C | (f.gap ? PDS_MODE_GAP2 : 0);
+          if (!f.riv_ok) b->status = LCS_PDSCH_BAD_ALLOC;
+          else b->tbs = tbs_1c[f.i_tbs];
+          tab = PDS_TABS + f.i_tbs;
+        } else {
+          const Pds1a f = pds_1a_fields(d.bits, in.n_rb, in.tdd);
+          b->rb_start = f.rb_start; b->n_prb = f.n_prb; b->mcs = f.mcs; b->rv = f.rv;
+          if (f.distributed) mode = (ALLOC && (al.flags & 1)) ? PDS_MODE_SET | ((in.n_rb >= 50 && f.ndi) ? PDS_MODE_GAP2 : 0) : PDS_MODE_UNREAD;
+          if (mode == PDS_MODE_UNREAD) b->status = LCS_PDSCH_DISTRIBUTED;
+          else if (f.mcs > 26) b->status = LCS_PDSCH_MCS;
+          else b->tbs = tbs_tab[PDS_N_MCS * (f.tpc & 1) + f.mcs];
+          tab = PDS_N_MCS * (f.tpc & 1) + (f.mcs <= 26 ? f.mcs : 0);
+        }
+        pds_plan_grant<ALLOC>(in, g, row0, cfi, tab, qpp, heads, b, &job[n], mode, (ALLOC && al.flags) ? sets + PDS_SET_WORDS * n : nullptr);
+        n += 1;
+      }
     }
   }
   for (int u = n; u < PDS_GRANTS; ++u) { PdsJob z = {}; job[u] = z; }
+}
+// the same with the setting off: format 1A's localized grants alone
+__host__ __device__ inline void pds_plan_sf(const PdsPlanIn &in, int g, int row0, const lcs_pdcch_info *__restrict__ pdc, const int *__restrict__ tbs_tab,
+                                            const int *__restrict__ qpp, const PdsTabHead *__restrict__ heads, lcs_pdsch_block *blk /*[2]*/, PdsJob *job /*[2]*/) {
+  const PdsAllocIn off = {0, -1, 0, 0};
+  pds_plan_sf_alloc<false>(in, off, g, row0, pdc, tbs_tab, nullptr, qpp, heads, blk, job, nullptr);
+}
+// what lcs_pdsch_last_alloc says of a listed block: from its public fields and its job's mode
+__host__ __device__ inline void pds_alloc_of(int n_rb, const lcs_pdsch_block &b, int mode, lcs_pdsch_alloc *o) {
+  const bool set = (mode & PDS_MODE_SET) != 0;
+  const PdsDvrb dv = pds_dvrb(n_rb, (mode & PDS_MODE_GAP2) ? 1 : 0);
+  o->format = (mode & PDS_MODE_1C) ? 1 : 0; o->distributed = (set || (mode & PDS_MODE_UNREAD)) ? 1 : 0; o->gap = (mode & PDS_MODE_GAP2) ? 1 : 0;
+  o->n_gap = o->distributed ? dv.n_gap : 0; o->n_vrb = o->distributed ? dv.n_vrb : n_rb; o->n_step = (mode & PDS_MODE_1C) ? (n_rb < 50 ? 2 : 4) : 1;
+  o->reserved = 0;
+  const bool inside = !(mode & PDS_MODE_UNREAD) && b.rb_start >= 0 && b.n_prb >= 1 && b.rb_start + b.n_prb <= o->n_vrb;
+  o->n_prb = inside ? b.n_prb : 0;
+  for (int s = 0; s < 2; ++s)
+    for (int i = 0; i < LCS_PDSCH_ALLOC_RB; ++i) o->prb[s][i] = (uint8_t)(i >= o->n_prb ? 0 : set ? pds_dvrb_prb(dv, b.rb_start + i, s) : b.rb_start + i);
 }
 // the head of the record from its blocks, in order
 __host__ __device__ inline void pds_summary(lcs_pdsch_info *o, int n_sf, int n_blocks, int n_overflow, int dl_mask, int n_rb, int ports) {
@@ -389,6 +578,9 @@ __host__ __device__ inline void pds_summary(lcs_pdsch_info *o, int n_sf, int n_b
 
 // ------------------------------------------------------------------ the tables (host)
 // 36.213 table 7.1.7.2.1-1, columns N_PRB = 2 and 3, I_TBS = 0 .. 26 (from memory: see the head of this file)
+// 36.213 table 7.1.7.2.3-1: the transport block sizes of format 1C by I_TBS (from memory; every entry + 24 is a turbo block size)
+static const int PDS_TBS_1C[PDS_N_1C] = {40, 56, 72, 120, 136, 144, 176, 208, 224, 256, 280, 296, 328, 336, 392, 488, 552, 600, 632, 696, 776, 840, 904, 1000, 1064, 1128,
+                                         1224, 1288, 1384, 1480, 1608, 1736};
 static const int PDS_TBS[2][PDS_N_MCS] = {
     {32, 56, 72, 104, 120, 144, 176, 208, 256, 296, 328, 376, 440, 488, 552, 600, 632, 696, 776, 840, 904, 1000, 1064, 1128, 1192, 1256, 1480},
     {56, 88, 144, 176, 208, 224, 256, 328, 392, 456, 504, 584, 680, 744, 840, 904, 968, 1064, 1160, 1288, 1384, 1480, 1608, 1736, 1800, 1864, 2216}};

@@ -37,6 +37,17 @@ __global__ __launch_bounds__(128) void k_pdsch_plan(const lcs_pdcch_info *__rest
   if (g >= n_sf) return;
   pds_plan_sf(in, g, sfrow[g], pdc, tabs, tabs + 2 * PDS_N_MCS, heads, blk + PDS_GRANTS * g, job + PDS_GRANTS * g);
 }
+// The same with a non-zero lcs_set_pdsch_alloc: format 1C's entries, 1A's distributed grants and the two sets of PRBs of every grant slot.
+// A kernel of its own, so that k_pdsch_plan is the code it was.
+__global__ __launch_bounds__(128) void k_pdsch_plan_alloc(const lcs_pdcch_info *__restrict__ pdc, const int *__restrict__ sfrow,
+                                                    const int *__restrict__ tabs /*tbs [54], qpp [254], 1C's tbs [32]*/, const PdsTabHead *__restrict__ heads,
+                                                    lcs_pdsch_block *__restrict__ blk, PdsJob *__restrict__ job, unsigned long long *__restrict__ sets,
+                                                    int n_sf, PdsPlanIn in, PdsAllocIn al) {
+  const int g = blockIdx.x * 128 + threadIdx.x;
+  if (g >= n_sf) return;
+  pds_plan_sf_alloc<true>(in, al, g, sfrow[g], pdc, tabs, tabs + 2 * PDS_N_MCS + 2 * PDS_N_K, tabs + 2 * PDS_N_MCS, heads, blk + PDS_GRANTS * g, job + PDS_GRANTS * g,
+                    sets ? sets + (size_t)PDS_GRANTS * PDS_SET_WORDS * g : nullptr);
+}
 
 // ------------------------------------------------------------------ the soft bits: one workgroup per grant slot
 // Threads 0 .. 5 build the sequences of the subframe's six reference rows (4 and 5 with four ports only), thread 6 the elements before
@@ -53,7 +64,7 @@ __global__ __launch_bounds__(PDS_LLR_THREADS) void k_pdsch_llr(const double2 *__
   __shared__ uint32_t s_scr[PDS_SCR_WORDS];
   __shared__ int s_base[PDS_MAX_SYM + 1];
   const PdsJob job = jobs[slot];
-  if (job.status != LCS_PDSCH_FOLLOW) return;              // the same for the whole workgroup
+  if (job.status != LCS_PDSCH_FOLLOW || job.reserved != 0) return;      // the same for the whole workgroup; a set-based grant is k_pdsch_llr_set's
   PdsGeom q;
   q.n_rb = n_rb; q.ports = ports; q.n_symb = n_symb; q.id = id; q.sf = job.sf; q.tdd = job.tdd; q.n_ctrl = job.n_ctrl; q.k_lo = job.k_lo; q.k_hi = job.k_hi;
   if (tid < 24) s_shift[tid >> 2][tid & 3] = 0.0;
@@ -75,6 +86,66 @@ __global__ __launch_bounds__(PDS_LLR_THREADS) void k_pdsch_llr(const double2 *__
     const bool live = e < n_re;
     int l = q.n_ctrl, k = q.k_lo;
     if (live) pds_elem_at(q, s_base, e, &l, &k);
+    cd2 y, ha, hb;
+    pds_elem(e, l, k, n_rb, ports, n_symb, sfrow, s_bits, s_shift, &y, &ha, &hb);
+    if (!live) { y = mk(0.0, 0.0); hb = mk(0.0, 0.0); }
+    const cd2 hb_pair = mk(__shfl_xor(hb.re, 1), __shfl_xor(hb.im, 1)), y_pair = mk(__shfl_xor(y.re, 1), __shfl_xor(y.im, 1));
+    const cd2 s = pcf_soft(e, ports, y, ha, hb_pair, y_pair);
+    if (live) {
+      double l0, l1;
+      pdc_llr(e, s_scr[(2 * e) >> 5], s, &l0, &l1);
+      out[2 * e] = l0;
+      out[2 * e + 1] = l1;
+    }
+  }
+}
+
+// The same for a grant whose resource blocks are two sets (a distributed 1A or a 1C grant; launched only with a non-zero
+// lcs_set_pdsch_alloc): thread 6 counts the sets' half blocks below and inside the central columns and the elements before every
+// symbol, threads 7 and 8 list the PRBs of slot 0 and slot 1 in ascending order; element e's (l, k) comes from pds_set_elem_at.  A
+// kernel of its own, so that k_pdsch_llr is the code it was.
+__global__ __launch_bounds__(PDS_LLR_THREADS) void k_pdsch_llr_set(const double2 *__restrict__ grid, const PdsJob *__restrict__ jobs, const uint32_t *__restrict__ jump /*[320]*/,
+                                                               const uint32_t *__restrict__ x1s /*[256]*/, double *__restrict__ llr, size_t llr_stride, int id, int cp_type,
+                                                               int n_symb, int ports, int n_rb, const unsigned long long *__restrict__ sets) {
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  __shared__ uint32_t s_bits[6][RS_DL_WIDE_WORDS];
+  __shared__ double s_shift[6][4];
+  __shared__ uint32_t s_scr[PDS_SCR_WORDS];
+  __shared__ int s_base[PDS_MAX_SYM + 1];
+  __shared__ uint8_t s_prb[2 * PDS_SET_RB];                // a distributed grant's resource blocks, ascending, per slot of the subframe
+  __shared__ int s_cut[4];
+  const PdsJob job = jobs[slot];
+  if (job.status != LCS_PDSCH_FOLLOW || !(job.reserved & PDS_MODE_SET)) return;      // the same for the whole workgroup
+  const int n_prb_set = (int)__popcll(sets[PDS_SET_WORDS * slot]) + (int)__popcll(sets[PDS_SET_WORDS * slot + 1]);
+  PdsGeom q;
+  q.n_rb = n_rb; q.ports = ports; q.n_symb = n_symb; q.id = id; q.sf = job.sf; q.tdd = job.tdd; q.n_ctrl = job.n_ctrl; q.k_lo = job.k_lo; q.k_hi = job.k_hi;
+  if (tid < 24) s_shift[tid >> 2][tid & 3] = 0.0;
+  __syncthreads();
+  if (tid < (ports == 4 ? 6 : 4)) pds_ref_row(tid, job.sf, id, cp_type, n_symb, n_rb, jump, s_bits[tid], s_shift[tid]);
+  if (tid == 6) {
+    const unsigned long long *m = sets + PDS_SET_WORDS * slot;
+    int cut[4];
+    pds_set_cut(n_rb, m[0], m[1], cut);
+    pds_set_cut(n_rb, m[2], m[3], cut + 2);
+    for (int i = 0; i < 4; ++i) s_cut[i] = cut[i];
+    pds_set_bases(q, n_prb_set, cut, s_base);
+  }
+  if (tid == 7 || tid == 8) pds_set_list(n_rb, sets[PDS_SET_WORDS * slot + 2 * (tid - 7)], sets[PDS_SET_WORDS * slot + 2 * (tid - 7) + 1], s_prb + PDS_SET_RB * (tid - 7));
+  const int n_re = job.n_re, n_chunk = (2 * n_re + 32 * PDS_SCR_CHUNK - 1) / (32 * PDS_SCR_CHUNK);
+  if (tid < n_chunk) {
+    uint32_t x2 = pds_x2_jump((uint32_t)job.c_init, jump + 32);
+#pragma unroll 1
+    for (int b = 0; b < 8; ++b) if ((tid >> b) & 1) x2 = pds_x2_jump(x2, jump + 64 + 32 * b);
+    pds_scr_chunk(x1s[tid], x2, s_scr + PDS_SCR_CHUNK * tid);
+  }
+  __syncthreads();
+  const double *sfrow = reinterpret_cast<const double *>(grid + (size_t)job.row0 * 12 * n_rb);
+  double *out = llr + (size_t)slot * llr_stride;
+#pragma unroll 1
+  for (int e = tid; e < ((n_re + PDS_LLR_THREADS - 1) / PDS_LLR_THREADS) * PDS_LLR_THREADS; e += PDS_LLR_THREADS) {
+    const bool live = e < n_re;
+    int l = q.n_ctrl, k = 0;
+    if (live) pds_set_elem_at(q, s_prb, s_cut, s_base, e, &l, &k);
     cd2 y, ha, hb;
     pds_elem(e, l, k, n_rb, ports, n_symb, sfrow, s_bits, s_shift, &y, &ha, &hb);
     if (!live) { y = mk(0.0, 0.0); hb = mk(0.0, 0.0); }
@@ -378,7 +449,8 @@ namespace {
 int pdsch_tables(lcs_ctx *c) {
   lcs_ctx::Pdsch &p = c->pdsch;
   int rc;
-  const size_t n_tabs = 2 * PDS_N_MCS + 2 * PDS_N_K, n_heads = (size_t)PDS_TABS * sizeof(PdsTabHead) / sizeof(int), n_rank = (size_t)PDS_TABS * 3 * PDS_MAX_D;
+  const size_t n_tabs = 2 * PDS_N_MCS + 2 * PDS_N_K + PDS_N_1C, n_heads = (size_t)(PDS_TABS + PDS_N_1C) * sizeof(PdsTabHead) / sizeof(int),
+               n_rank = (size_t)(PDS_TABS + PDS_N_1C) * 3 * PDS_MAX_D;
   if ((rc = p.tabs.reserve(c, n_tabs)) || (rc = p.heads.reserve(c, n_heads)) || (rc = p.rank.reserve(c, n_rank)) || (rc = p.x1s.reserve(c, 256)) ||
       (rc = p.res.reserve(c, 2 * PDS_GRANTS * PCF_MAX_SF)) || (rc = p.hard.reserve(c, (size_t)PDS_GRANTS * PCF_MAX_SF * PDS_MAX_K)) ||
       (rc = p.job.reserve(c, (size_t)PDS_GRANTS * PCF_MAX_SF * sizeof(PdsJob) / sizeof(int))) || (rc = p.blk.reserve(c, (size_t)PDS_GRANTS * PCF_MAX_SF)) ||
@@ -388,6 +460,7 @@ int pdsch_tables(lcs_ctx *c) {
   p.h_tabs.assign(n_tabs, 0);
   for (int i = 0; i < 2 * PDS_N_MCS; ++i) p.h_tabs[(size_t)i] = PDS_TBS[i / PDS_N_MCS][i % PDS_N_MCS];
   for (int i = 0; i < 2 * PDS_N_K; ++i) p.h_tabs[(size_t)(2 * PDS_N_MCS + i)] = PDS_QPP[i / 2][i % 2];
+  for (int i = 0; i < PDS_N_1C; ++i) p.h_tabs[(size_t)(2 * PDS_N_MCS + 2 * PDS_N_K + i)] = PDS_TBS_1C[i];
   p.h_heads.assign(n_heads, 0);
   p.h_rank.assign(n_rank, (int16_t)-1);
   PdsTabHead *heads = reinterpret_cast<PdsTabHead *>(p.h_heads.data());
@@ -401,6 +474,7 @@ int pdsch_tables(lcs_ctx *c) {
   HIPCHK(c, hipMemcpyAsync(p.heads, p.h_heads.data(), sizeof(int) * n_heads, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(p.rank, p.h_rank.data(), sizeof(int16_t) * n_rank, hipMemcpyHostToDevice, c->stream));
   p.tables_ready = true;
+  p.tables_1c_ready = false;
   for (int f = 0; f < LCS_PDSCH_MAX_FORCED; ++f) p.forced_key[f][0] = p.forced_key[f][1] = 0;
   return LCS_OK;
 }
@@ -418,6 +492,22 @@ int pdsch_forced_table(lcs_ctx *c, int f, int K, int F) {
   p.forced_key[f][0] = K; p.forced_key[f][1] = F + 1;
   return LCS_OK;
 }
+// the rank tables of format 1C's 32 sizes, behind the others: built by the first call that follows 1C
+int pdsch_tables_1c(lcs_ctx *c) {
+  lcs_ctx::Pdsch &p = c->pdsch;
+  if (p.tables_1c_ready) return LCS_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  PdsTabHead *heads = reinterpret_cast<PdsTabHead *>(p.h_heads.data());
+  for (int i = 0; i < PDS_N_1C; ++i) {
+    const int K = pds_k_at(pds_k_ceil_index(PDS_TBS_1C[i] + 24)), t = PDS_TABS + i;
+    pds_rank_build(K, K - (PDS_TBS_1C[i] + 24), &heads[t], p.h_rank.data() + (size_t)t * 3 * PDS_MAX_D);
+  }
+  HIPCHK(c, hipMemcpyAsync(reinterpret_cast<PdsTabHead *>(p.heads.get()) + PDS_TABS, &heads[PDS_TABS], sizeof(PdsTabHead) * PDS_N_1C, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(p.rank.get() + (size_t)PDS_TABS * 3 * PDS_MAX_D, p.h_rank.data() + (size_t)PDS_TABS * 3 * PDS_MAX_D, sizeof(int16_t) * PDS_N_1C * 3 * PDS_MAX_D,
+                           hipMemcpyHostToDevice, c->stream));
+  p.tables_1c_ready = true;
+  return LCS_OK;
+}
 }  // namespace
 
 int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const int *sfrow, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan, const PdschPlan &ps,
@@ -431,6 +521,10 @@ int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const i
                (rc = p.crec.reserve(c, 1)))) return rc;
   const int n_symb = cell.cp_type == LCS_CP_NORMAL ? 7 : 6, id = cell.n_id_2 + 3 * cell.n_id_1, ports = pcf_ports(cell.n_ports);
   if ((rc = pdsch_tables(c))) return rc;
+  const PdsAllocIn al = {ps.alloc_flags, ps.sfn0, ps.si_window, 1 - ps.i_1a};
+  if ((al.flags & 2) && (rc = pdsch_tables_1c(c))) return rc;
+  if (al.flags && (rc = p.sets.reserve(c, (size_t)PDS_GRANTS * PDS_SET_WORDS * PCF_MAX_SF))) return rc;
+  unsigned long long *sets = al.flags ? p.sets.get() : nullptr;
   PdsPlanIn in;
   in.n_rb = n_rb; in.ports = ports; in.n_symb = n_symb; in.id = id; in.tdd = ps.tdd; in.i_1a = ps.i_1a; in.rnti_mask = ps.rnti_mask; in.max_iter = ps.max_iter;
   in.n_forced = ps.n_forced;
@@ -457,16 +551,27 @@ int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const i
   for (int g = 0; g < n_sf; ++g) p.h_sfrow[g] = sfrow[g];
   HIPCHK(c, hipMemcpyAsync(p.sfrow, p.h_sfrow, sizeof(int) * n_sf, hipMemcpyHostToDevice, c->stream));
   PdsJob *jobs = reinterpret_cast<PdsJob *>(p.job.get());
-  hipLaunchKernelGGL(k_pdsch_plan, dim3((n_sf + 127) / 128), dim3(128), 0, c->stream, (const lcs_pdcch_info *)p.pdc.rec.get(), (const int *)p.sfrow.get(),
-                     (const int *)p.tabs.get(), reinterpret_cast<const PdsTabHead *>(p.heads.get()), p.blk.get(), jobs, n_sf, in);
-  HIPCHK(c, hipGetLastError());
+  if (!sets) {
+    hipLaunchKernelGGL(k_pdsch_plan, dim3((n_sf + 127) / 128), dim3(128), 0, c->stream, (const lcs_pdcch_info *)p.pdc.rec.get(), (const int *)p.sfrow.get(),
+                       (const int *)p.tabs.get(), reinterpret_cast<const PdsTabHead *>(p.heads.get()), p.blk.get(), jobs, n_sf, in);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(k_pdsch_plan_alloc, dim3((n_sf + 127) / 128), dim3(128), 0, c->stream, (const lcs_pdcch_info *)p.pdc.rec.get(), (const int *)p.sfrow.get(),
+                       (const int *)p.tabs.get(), reinterpret_cast<const PdsTabHead *>(p.heads.get()), p.blk.get(), jobs, sets, n_sf, in, al);
+    HIPCHK(c, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_pdsch_llr, dim3(n_slots), dim3(PDS_LLR_THREADS), 0, c->stream, (const double2 *)w.grid.get(), (const PdsJob *)jobs, (const uint32_t *)p.jump.get(),
                      (const uint32_t *)p.x1s.get(), p.llr.get(), llr_stride, id, (int)cell.cp_type, n_symb, ports, n_rb);
   HIPCHK(c, hipGetLastError());
+  if (sets) {
+    hipLaunchKernelGGL(k_pdsch_llr_set, dim3(n_slots), dim3(PDS_LLR_THREADS), 0, c->stream, (const double2 *)w.grid.get(), (const PdsJob *)jobs, (const uint32_t *)p.jump.get(),
+                       (const uint32_t *)p.x1s.get(), p.llr.get(), llr_stride, id, (int)cell.cp_type, n_symb, ports, n_rb, (const unsigned long long *)sets);
+    HIPCHK(c, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_pdsch_dec, dim3(n_slots), dim3(PDS_DEC_THREADS), 0, c->stream, (const PdsJob *)jobs, (const double *)p.llr.get(), llr_stride, (const double *)nullptr,
                      (const int16_t *)p.rank.get(), p.ws.get(), p.res.get(), p.hard.get());
   HIPCHK(c, hipGetLastError());
-  p.last_stride = llr_stride; p.last_n_sf = n_sf;
+  p.last_stride = llr_stride; p.last_n_sf = n_sf; p.last_n_rb = n_rb;
   if (comb) {
     PdsCombJob *cjobs = reinterpret_cast<PdsCombJob *>(p.cjob.get());
     hipLaunchKernelGGL(k_pdsch_comb_group, dim3(1), dim3(64), 0, c->stream, (const lcs_pdsch_block *)p.blk.get(), (const PdsJob *)jobs, (const int *)p.res.get(), cjobs, n_sf,

@@ -208,7 +208,7 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
                      carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False,
-                     pdsch_comb=False):
+                     pdsch_comb=False, pdsch_alloc=None):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -234,6 +234,10 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     of SIB1 (and, with an si_window in the configuration, of other SI messages) are combined.  A dict cell also gets
     cell["pdsch_comb"] (a PdschCombInfo, or None) and, where the payload of a rule-1 group that passed a CRC parses,
     cell["sib1"] = capi.sib1_fields(...); the PdschCombInfo is appended to entry k's tuple after the PdschInfo.
+    pdsch_alloc (a capi.PdschAllocCfg) is the searcher's setting (Searcher.set_pdsch_alloc) for the length of this call, so that
+    distributed 1A grants and format 1C grants are followed too; the setting the searcher had comes back afterwards.  Its sfn0 is
+    the caller's: the frame number of the first frame the stage reads, ONE value for every cell -- right only where the cells share
+    their frame timing; pass -1 where they do not or it is not known.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -250,108 +254,116 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     tdev = torch.device("cuda", dev if dev >= 0 else torch.cuda.current_device())
     bufs = {}                                             # decim_meas -> (buffer, the carrier it holds)
     out = []
-    for fc, cells in zip(carriers, cells_per_carrier):
-        row = []
-        for cell in cells:
-            d = cell if isinstance(cell, dict) else None
-            get = (lambda k: d[k]) if d is not None else (lambda k: getattr(cell, k))
-            if get("n_rb_dl") not in (6, 15, 25, 50, 75, 100) or get("cp_type") not in (1, 2):
-                row.append(None)
-                continue
-            rb = int(n_rb) if n_rb is not None else int(get("n_rb_dl"))
-            R = meas_rate(rb)
-            if K % R or K < R:
-                raise ValueError(f"measure_wideband: {rb} resource blocks need 1.92e6 x {R} samples per second, which fs_in = {fs_in} (K = {K}) does not give by an integer decimation")
-            D_m = K // R
-            if D_m == 1:
-                if fmt != capi.FMT_C64 or float(fc) != float(fc_centre):
-                    raise ValueError("measure_wideband: K / R < 2 -- the capture is used in place, which takes a complex64 capture centred on the cell's carrier")
-                ptr, n_cap = int(d_wide_ptr), int(n_in)
-            else:
-                if not 2 <= D_m <= 16:
-                    raise ValueError(f"measure_wideband: decim_meas = {D_m} is outside the channelizer's 2 .. 16")
-                n_cap = (int(n_in) - 16 * D_m) // D_m + 1
-                if D_m not in bufs:
-                    bufs[D_m] = [torch.empty(max(n_cap, 1), dtype=torch.complex64, device=tdev), None]
-                if bufs[D_m][1] != float(fc):
-                    searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, D_m, [float(fc) - float(fc_centre)], bufs[D_m][0].data_ptr(), n_cap)
-                    bufs[D_m][1] = float(fc)
-                ptr = bufs[D_m][0].data_ptr()
-            fs_m = float(fs_in) / D_m
-            n_symb = 7 if get("cp_type") == 1 else 6      # LCS_CP_NORMAL / LCS_CP_EXTENDED
-            k_factor = (float(fc) - get("freq_fine")) / float(fc)
-            frame = 0.01 * fs_m * k_factor
-            start = map_frame_start(get("frame_start"), D_s, D_m)
-            while start < 0:
-                start += frame
-            # whole slots between the first DFT the stage takes (it moves 10 ms back where it can) and the buffer's end
-            first = start + (10 if n_symb == 7 else 32) * R * k_factor
-            if first - frame > -0.5:
-                first -= frame
-            n_slots = int((n_cap - 128 * R - first) / (frame / 20)) - 1
-            if n_slots < 2:
-                raise ValueError("measure_wideband: the capture holds less than two slots of the cell at the measurement rate")
-            if d is None:
-                mc = capi.LcsCell.from_buffer_copy(bytes(cell))
-            else:
-                mc = capi.LcsCell()
-                searcher._lib.lcs_cell_init(C.byref(mc))
-                for f in FIELDS:
-                    setattr(mc, f, d[f])
-            mc.frame_start = start
-            if dl_mask is not None:
-                mask = int(dl_mask)
-            elif d is not None and getattr(d.get("meas"), "status", -1) == 0:
-                mask = int(d["meas"].dl_mask)
-            else:
-                mask = 0x3FF if searcher.duplex == capi.DUPLEX_FDD else 0x021
-            rec = searcher.cell_meas_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
-            if d is not None:
-                d["meas_wide"] = rec
-            if pcfich:
-                pc = None
-                if rb == int(get("n_rb_dl")):
-                    pc = searcher.pcfich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
+    set_alloc = bool(pdsch or pdsch_comb) and pdsch_alloc is not None
+    before = getattr(searcher, "pdsch_alloc", None)
+    if set_alloc:
+        searcher.set_pdsch_alloc(pdsch_alloc)
+    try:
+        for fc, cells in zip(carriers, cells_per_carrier):
+            row = []
+            for cell in cells:
+                d = cell if isinstance(cell, dict) else None
+                get = (lambda k: d[k]) if d is not None else (lambda k: getattr(cell, k))
+                if get("n_rb_dl") not in (6, 15, 25, 50, 75, 100) or get("cp_type") not in (1, 2):
+                    row.append(None)
+                    continue
+                rb = int(n_rb) if n_rb is not None else int(get("n_rb_dl"))
+                R = meas_rate(rb)
+                if K % R or K < R:
+                    raise ValueError(f"measure_wideband: {rb} resource blocks need 1.92e6 x {R} samples per second, which fs_in = {fs_in} (K = {K}) does not give by an integer decimation")
+                D_m = K // R
+                if D_m == 1:
+                    if fmt != capi.FMT_C64 or float(fc) != float(fc_centre):
+                        raise ValueError("measure_wideband: K / R < 2 -- the capture is used in place, which takes a complex64 capture centred on the cell's carrier")
+                    ptr, n_cap = int(d_wide_ptr), int(n_in)
+                else:
+                    if not 2 <= D_m <= 16:
+                        raise ValueError(f"measure_wideband: decim_meas = {D_m} is outside the channelizer's 2 .. 16")
+                    n_cap = (int(n_in) - 16 * D_m) // D_m + 1
+                    if D_m not in bufs:
+                        bufs[D_m] = [torch.empty(max(n_cap, 1), dtype=torch.complex64, device=tdev), None]
+                    if bufs[D_m][1] != float(fc):
+                        searcher.channelize(d_wide_ptr, fmt, n_in, fs_in, D_m, [float(fc) - float(fc_centre)], bufs[D_m][0].data_ptr(), n_cap)
+                        bufs[D_m][1] = float(fc)
+                    ptr = bufs[D_m][0].data_ptr()
+                fs_m = float(fs_in) / D_m
+                n_symb = 7 if get("cp_type") == 1 else 6      # LCS_CP_NORMAL / LCS_CP_EXTENDED
+                k_factor = (float(fc) - get("freq_fine")) / float(fc)
+                frame = 0.01 * fs_m * k_factor
+                start = map_frame_start(get("frame_start"), D_s, D_m)
+                while start < 0:
+                    start += frame
+                # whole slots between the first DFT the stage takes (it moves 10 ms back where it can) and the buffer's end
+                first = start + (10 if n_symb == 7 else 32) * R * k_factor
+                if first - frame > -0.5:
+                    first -= frame
+                n_slots = int((n_cap - 128 * R - first) / (frame / 20)) - 1
+                if n_slots < 2:
+                    raise ValueError("measure_wideband: the capture holds less than two slots of the cell at the measurement rate")
+                if d is None:
+                    mc = capi.LcsCell.from_buffer_copy(bytes(cell))
+                else:
+                    mc = capi.LcsCell()
+                    searcher._lib.lcs_cell_init(C.byref(mc))
+                    for f in FIELDS:
+                        setattr(mc, f, d[f])
+                mc.frame_start = start
+                if dl_mask is not None:
+                    mask = int(dl_mask)
+                elif d is not None and getattr(d.get("meas"), "status", -1) == 0:
+                    mask = int(d["meas"].dl_mask)
+                else:
+                    mask = 0x3FF if searcher.duplex == capi.DUPLEX_FDD else 0x021
+                rec = searcher.cell_meas_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
                 if d is not None:
-                    d["pcfich"] = pc
-                rec = (rec, pc)
-            if pdcch:
-                pd = None
-                if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
-                    cfg = pdcch
-                    if pdcch is True:
-                        tdd = searcher.duplex != capi.DUPLEX_FDD
-                        cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
-                    pd = searcher.pdcch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, n_cap=n_cap)
-                if d is not None:
-                    d["pdcch"] = pd
-                rec = (rec if isinstance(rec, tuple) else (rec,)) + (pd,)
-            if pdsch or pdsch_comb:
-                ps = pc = None
-                if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
-                    cfg = pdcch
-                    if cfg is True or not cfg:
-                        tdd = searcher.duplex != capi.DUPLEX_FDD
-                        cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
-                    pcfg = None if pdsch is True or not pdsch else pdsch
-                    if pdsch_comb:
-                        ps, pc = searcher.pdsch_comb_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg,
-                                                          None if pdsch_comb is True else pdsch_comb, n_cap=n_cap)
-                    else:
-                        ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg, n_cap=n_cap)
-                if d is not None:
-                    d["pdsch"] = ps
-                rec = (rec if isinstance(rec, tuple) else (rec,)) + (ps,)
-                if pdsch_comb:
+                    d["meas_wide"] = rec
+                if pcfich:
+                    pc = None
+                    if rb == int(get("n_rb_dl")):
+                        pc = searcher.pcfich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
                     if d is not None:
-                        d["pdsch_comb"] = pc
-                        sib = [capi.sib1_fields(g["bytes"]) for g in (pc.groups() if pc is not None else []) if g["rule"] == 1 and g["crc_ok"]]
-                        sib = [x for x in sib if x is not None]
-                        if sib:
-                            d["sib1"] = sib[0]
-                    rec = rec + (pc,)
-            row.append(rec)
-        out.append(row)
+                        d["pcfich"] = pc
+                    rec = (rec, pc)
+                if pdcch:
+                    pd = None
+                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                        cfg = pdcch
+                        if pdcch is True:
+                            tdd = searcher.duplex != capi.DUPLEX_FDD
+                            cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
+                        pd = searcher.pdcch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, n_cap=n_cap)
+                    if d is not None:
+                        d["pdcch"] = pd
+                    rec = (rec if isinstance(rec, tuple) else (rec,)) + (pd,)
+                if pdsch or pdsch_comb:
+                    ps = pc = None
+                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                        cfg = pdcch
+                        if cfg is True or not cfg:
+                            tdd = searcher.duplex != capi.DUPLEX_FDD
+                            cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
+                        pcfg = None if pdsch is True or not pdsch else pdsch
+                        if pdsch_comb:
+                            ps, pc = searcher.pdsch_comb_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg,
+                                                              None if pdsch_comb is True else pdsch_comb, n_cap=n_cap)
+                        else:
+                            ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg, n_cap=n_cap)
+                    if d is not None:
+                        d["pdsch"] = ps
+                    rec = (rec if isinstance(rec, tuple) else (rec,)) + (ps,)
+                    if pdsch_comb:
+                        if d is not None:
+                            d["pdsch_comb"] = pc
+                            sib = [capi.sib1_fields(g["bytes"]) for g in (pc.groups() if pc is not None else []) if g["rule"] == 1 and g["crc_ok"]]
+                            sib = [x for x in sib if x is not None]
+                            if sib:
+                                d["sib1"] = sib[0]
+                        rec = rec + (pc,)
+                row.append(rec)
+            out.append(row)
+    finally:
+        if set_alloc:
+            searcher.set_pdsch_alloc(before)
     return out
 
 

@@ -694,12 +694,20 @@ def turbo_ratematch(d, n_e, rv=0, F=0):
     return np.roll(w, -k0)[live[np.arange(int(n_e)) % live.size]].astype(d.dtype)
 
 
-def pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, rb_start, n_prb, tdd=False):
-    """[(l, k)]: the resource elements of a localized allocation in mapping order -- by symbol l = n_ctrl .. 2 n_symb - 1 of the
-    subframe, then by column --, without the reference elements of the cell's ports, the PBCH and the PSS / SSS"""
+def pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, rb_start, n_prb, tdd=False, distributed=False, gap=0):
+    """[(l, k)]: the resource elements of an allocation in mapping order -- by symbol l = n_ctrl .. 2 n_symb - 1 of the
+    subframe, then by column --, without the reference elements of the cell's ports, the PBCH and the PSS / SSS.  distributed:
+    rb_start and n_prb are VRBs, mapped per slot by capi.dvrb_prb with gap index `gap` (36.211 6.2.3.2)"""
     n_symb = 7 if cp_normal else 6
     c0 = 6 * n_rb - 36
     out = []
+    if distributed:
+        sets = [sorted(capi.dvrb_prb(n_rb, gap, v, s) for v in range(rb_start, rb_start + n_prb)) for s in range(2)]
+        one = {p: pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, p, 1, tdd) for p in set(sets[0]) | set(sets[1])}
+        for l in range(n_ctrl, 2 * n_symb):
+            for p in sets[l // n_symb]:
+                out += [e for e in one[p] if e[0] == l]
+        return out
     for l in range(n_ctrl, 2 * n_symb):
         ls = l % n_symb
         crs = set()
@@ -719,11 +727,12 @@ def pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, rb_sta
 
 def pdsch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, grant, tdd=False):
     """What the PDSCH of one grant puts on its subframe (36.211 6.3, 6.4): grant = dict(rnti, rb_start, n_prb, rv, bits) with bits the
-    transport block.  CRC24A, fillers up to the next block size, turbo code, rate matching to G = 2 N_RE, scrambling with c_init =
+    transport block; optional distributed (or format = "1c", which is always distributed) and gap (0, 1) for VRBs that are mapped per slot.  CRC24A, fillers up to the next block size, turbo code, rate matching to G = 2 N_RE, scrambling with c_init =
     rnti 2^14 + subframe 2^9 + n_id_cell, QPSK, transmit diversity on consecutive elements.
     -> [(l, columns, values [n_ports][len(columns)])] per symbol l of the subframe"""
     n_ctrl = int(cfi) + (1 if n_rb <= 10 else 0)
-    el = pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, int(grant["rb_start"]), int(grant["n_prb"]), tdd)
+    el = pdsch_elements(n_id_cell, n_rb, n_ports, cp_normal, subframe, n_ctrl, int(grant["rb_start"]), int(grant["n_prb"]), tdd,
+                        bool(grant.get("distributed")) or grant.get("format", "1a") == "1c", int(grant.get("gap", 0)))
     a = np.asarray(grant["bits"], np.uint8)
     B = len(a) + 24
     K = next(k for k in TURBO_K if k >= B)
@@ -734,6 +743,35 @@ def pdsch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, grant, tdd=
     ls = np.array([l for l, _ in el])
     ks = np.array([k for _, k in el])
     return [(int(l), ks[ls == l], x[:, ls == l]) for l in sorted(set(ls.tolist()))]
+
+
+def dci_1a_payload(grant, n_rb, tdd=False):
+    """the payload bits of format 1A as sent with SI-, P- and RA-RNTI (36.212 5.3.3.1.3) from grant = dict(rb_start, n_prb, mcs, rv,
+    tpc) with optional distributed and gap: a distributed grant's gap index travels in the NDI bit (n_rb >= 50); padded to
+    capi.dci_common_sizes' size"""
+    L, S = int(grant["n_prb"]), int(grant["rb_start"])
+    riv = n_rb * (L - 1) + S if L - 1 <= n_rb // 2 else n_rb * (n_rb - L + 1) + (n_rb - 1 - S)
+    dist = 1 if grant.get("distributed") else 0
+    out = []
+    for v, n in ((1, 1), (dist, 1), (riv, (n_rb * (n_rb + 1) // 2 - 1).bit_length()), (int(grant["mcs"]), 5), (0, 4 if tdd else 3),
+                 (int(grant.get("gap", 0)) if dist and n_rb >= 50 else 0, 1), (int(grant.get("rv", 0)), 2), (int(grant.get("tpc", 0)), 2)):
+        out += [(v >> (n - 1 - i)) & 1 for i in range(n)]
+    return out + [0] * (capi.dci_common_sizes(n_rb, tdd)[0] - len(out))
+
+
+def dci_1c_payload(grant, n_rb):
+    """the payload bits of format 1C (36.212 5.3.3.1.4) from grant = dict(rb_start, n_prb, i_tbs) with optional gap: rb_start and
+    n_prb are VRBs and multiples of N_step (2 below 50 resource blocks, else 4)"""
+    gap, step = int(grant.get("gap", 0)), 2 if n_rb < 50 else 4
+    n = capi.dvrb_sizes(n_rb, gap)["n_vrb"] // step
+    L, S = int(grant["n_prb"]) // step, int(grant["rb_start"]) // step
+    if L * step != int(grant["n_prb"]) or S * step != int(grant["rb_start"]) or L < 1 or L + S > n:
+        raise ValueError("dci_1c_payload: the allocation is no multiple of N_step inside N_VRB")
+    riv = n * (L - 1) + S if L - 1 <= n // 2 else n * (n - L + 1) + (n - 1 - S)
+    out = []
+    for v, w in ([(gap, 1)] if n_rb >= 50 else []) + [(riv, capi.dci_1c_riv_bits(n_rb)), (int(grant["i_tbs"]), 5)]:
+        out += [(v >> (w - 1 - i)) & 1 for i in range(w)]
+    return out
 
 
 def sib1_message(f):

@@ -15,6 +15,10 @@ PDSCH transforms all 280 rows, the PDCCH 60, the PCFICH 20 (two ports) or 40 (fo
 Writes one JSON document (--out) and prints it.
 
     python tools/pdsch_bench.py --out profiles/pdsch/pdsch_bench.json
+
+--alloc localized | distributed | 1c: the same workload on 24 resource blocks (N_VRB of 25) with every grant localized, a distributed
+format 1A grant (Searcher.set_pdsch_alloc on), or a format 1C grant (its largest transport block: 1736 bits, K = 1760): what the
+set-based enumeration of k_pdsch_llr costs against the closed form of the same build.
 """
 import argparse
 import json
@@ -43,14 +47,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--lib", default=None, help="A/B runs: load this build of liblcs_amd.so instead of the in-tree one")
     ap.add_argument("--quick", action="store_true", help="the (4, 25) shapes only")
+    ap.add_argument("--alloc", default=None, choices=["localized", "distributed", "1c"], help="24 resource blocks per grant, allocated this way (25 RB shapes only)")
     a = ap.parse_args()
     import torch
     pkg = load_pkg()
     if a.lib:
         pkg.capi.LIB_PATH = os.path.abspath(a.lib)
     n_ofdm = 280
-    doc = {"n_ofdm": n_ofdm, "subframes": 20, "stage": []}
-    for R, n_rb in (((4, 25),) if a.quick else ((4, 25), (16, 100))):
+    doc = {"n_ofdm": n_ofdm, "subframes": 20, "alloc": a.alloc, "stage": []}
+    for R, n_rb in (((4, 25),) if a.quick or a.alloc else ((4, 25), (16, 100))):
         sizes = pkg.capi.dci_common_sizes(n_rb)
         for n_ports in (2, 4):
             tbs = pkg.capi.tbs_1a(26, 1)
@@ -58,6 +63,15 @@ def main():
             cellcfg = dict(n_id_1=52, n_id_2=1, cp_normal=True, n_ports=n_ports, f_off=0.0, t0=100.0, sfn0=8, n_rb_dl=n_rb, cfi=2,
                            pdcch=lambda fr, sf: [dict(rnti=0xFFFF, bits=pack_1a(n_rb, 0, 25, 26, sf % 4, 1, sizes[0]), L=4, cce=0)],
                            pdsch=lambda fr, sf: [dict(rnti=0xFFFF, rb_start=0, n_prb=25, rv=sf % 4, bits=bits(fr, sf))])
+            if a.alloc == "1c":
+                tbs = pkg.capi.tbs_1c(31)
+                g1c = dict(rnti=0xFFFF, rb_start=0, n_prb=24, i_tbs=31, format="1c", rv=0)
+                cellcfg.update(pdcch=lambda fr, sf: [dict(rnti=0xFFFF, bits=pkg.synth.dci_1c_payload(g1c, n_rb), L=4, cce=0)],
+                               pdsch=lambda fr, sf: [dict(g1c, bits=bits(fr, sf))])
+            elif a.alloc:
+                g1a = lambda sf: dict(rnti=0xFFFF, rb_start=0, n_prb=24, mcs=26, tpc=1, rv=sf % 4, distributed=int(a.alloc == "distributed"))
+                cellcfg.update(pdcch=lambda fr, sf: [dict(rnti=0xFFFF, bits=pkg.synth.dci_1a_payload(g1a(sf), n_rb), L=4, cce=0)],
+                               pdsch=lambda fr, sf: [dict(g1a(sf), bits=bits(fr, sf))])
             x, _, _ = pkg.synth.make_wideband_cell(7, FC, R, [(FC, R, n_rb, cellcfg)], snr_db=20.0, n_in=int(3.05 * 19200 * R))
             d = torch.from_numpy(x).cuda()
             with pkg.Searcher(0) as s:                                   # a fresh context: the first call is a first call
@@ -66,6 +80,8 @@ def main():
                 cell.n_rb_dl, cell.phich_duration, cell.phich_resource = n_rb, 1, 3
                 args = (cell, d, FC, FC, FS * R, 128 * R, n_rb, n_ofdm)
                 cfg = pkg.capi.PdcchCfg.make(sizes)
+                if a.alloc in ("distributed", "1c"):
+                    s.set_pdsch_alloc(pkg.capi.PdschAllocCfg.make(distributed=True, format_1c=True))
                 s.pcfich_wide(*args)                                     # (the transform's twiddles and the grid are the PCFICH's to allocate)
                 first = once(lambda: s.pdsch_wide(*args, 0x3FF, cfg))
                 second = once(lambda: s.pdsch_wide(*args, 0x3FF, cfg))
