@@ -799,6 +799,22 @@ int lcs_last_batch_stats(lcs_ctx *ctx, int stats[8]);
 /* Debug readback of the last batch (after lcs_batch_collect / lcs_search_batch_*): the xcorr_pss outputs of
  * buffer `buf` in the layouts of lcs_xcorr_pss, plus the detection threshold Z_th1 (src/CellSearch.cpp:500-503).
  * Every pointer may be NULL.  This is how the tests pin the batched kernels to the oracle array by array. */
+/* Batches on the int8 kernel with two or more combining windows are SCREENED (on by default): the correlation runs two of the
+ * template integers' three base-256 digits over every lag tile, and all three only over the tiles in which a collapsed power can
+ * reach the buffer's smallest Z_th1 by a data-independent bound on what the dropped digit changes.  The records a
+ * batch returns are the unscreened batch's, byte for byte.  The debug arrays are completed on demand: the first lcs_batch_readback,
+ * lcs_last_frq_repairs or lcs_last_frq_repair_stats after a screened batch runs the three-digit kernel over every tile of the
+ * context's own int8 copies (valid until the next enqueue), the full collapse and the full repair, and then answers with exactly
+ * what a batch without the screen leaves -- the cost lands on that debug call, never on enqueue or collect.
+ * The screen pays while few tiles are flagged (two digit passes over everything + three over the flagged tiles against three over
+ * everything: break-even near a quarter).  A collected batch that flagged more than a fifth of its tiles -- a busy band -- makes the
+ * context's next 63 batches run unscreened before one is screened again; lcs_set_batch_screen forgets that count. */
+int lcs_set_batch_screen(lcs_ctx *ctx, int on);
+int lcs_get_batch_screen(const lcs_ctx *ctx, int *on);
+/* Of the last collected batch: stats[0] = lag tiles (512 lags of one buffer) flagged for the three-digit kernel, [1] = tiles in
+ * all, [2] = work items (tile x template group) that kernel ran, [3] = buffers that flagged everything because no usable bound
+ * exists for them (a silent buffer).  All 0 for a batch that was not screened.  The numbers arrive with the collect's header copy. */
+int lcs_last_screen_stats(lcs_ctx *ctx, int stats[4]);
 int lcs_batch_readback(lcs_ctx *ctx, int buf, float *xc_incoherent_single /*[3][9600][n_f]*/,
                        double *xc_incoherent_collapsed_pow /*[3][9600]*/, int32_t *xc_incoherent_collapsed_frq /*[3][9600]*/,
                        double *sp_incoherent /*[9600]*/, double *z_th1 /*[9600]*/);

@@ -647,6 +647,23 @@ class Searcher:
                   "lcs_turbo_decode")
         return bits[:int(K)], n_iter.value, bool(ok.value)
 
+    def set_batch_screen(self, on: bool):
+        """int8 batches run a two-digit screen and the exact kernel only where a detection is possible (lcs_set_batch_screen,
+        include/lcs.h); on by default, the records are the same either way."""
+        self._chk(self._lib.lcs_set_batch_screen(self._h, 1 if on else 0), "lcs_set_batch_screen")
+
+    def get_batch_screen(self) -> bool:
+        on = C.c_int(0)
+        self._chk(self._lib.lcs_get_batch_screen(self._h, C.byref(on)), "lcs_get_batch_screen")
+        return bool(on.value)
+
+    def last_screen_stats(self):
+        """(lag tiles flagged, tiles in all, work items recomputed, buffers that flagged everything) of the last collected batch
+        (lcs_last_screen_stats)."""
+        st = (C.c_int * 4)()
+        self._chk(self._lib.lcs_last_screen_stats(self._h, st), "lcs_last_screen_stats")
+        return tuple(int(x) for x in st)
+
     def set_float_batch_probe(self, on: bool):
         """complex<float> batches (FMT_C64) are checked for dongle data on the device and then take the u8 / int8 route
         (lcs_set_float_batch_probe, include/lcs.h); off by default."""

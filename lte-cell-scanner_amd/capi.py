@@ -694,7 +694,8 @@ def sib1_fields(payload):
 
 
 EXPORTS = [
-    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
+    "lcs_create", "lcs_destroy", "lcs_last_error", "lcs_version", "lcs_cell_init", "lcs_set_max_cells_in_flight", "lcs_set_float_batch_probe",
+    "lcs_set_batch_screen", "lcs_get_batch_screen", "lcs_last_screen_stats", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
     "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
@@ -836,6 +837,10 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.lcs_track_stream_block.argtypes = [vp, C.POINTER(LcsTrackCell), C.c_int, C.c_int, vp, dp, dp, dp, C.c_double, C.c_double, C.c_double,
                                          dp, dp, dp, C.c_int, i64p, ip, dp, dp, dp, C.c_int, ip, ip, C.POINTER(C.c_uint64), C.c_int, i64p, ip]
     L.lcs_track_stream_reset.argtypes = [vp]
+    if hasattr(L, "lcs_set_batch_screen"):
+        L.lcs_set_batch_screen.argtypes = [vp, C.c_int]
+        L.lcs_get_batch_screen.argtypes = [vp, C.POINTER(C.c_int)]
+        L.lcs_last_screen_stats.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(L, "lcs_set_float_batch_probe"):
         L.lcs_set_float_batch_probe.argtypes = [vp, C.c_int]
     if hasattr(L, "lcs_track_cut"):

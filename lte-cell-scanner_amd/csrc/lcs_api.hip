@@ -51,6 +51,7 @@ int ensure_ws(lcs_ctx *c, int n_slots, uint32_t n_cap, int n_f, bool debug, int 
     return rc;
   c->foe_ready = false;      // (a pending lcs_foe_partial result lived in the buffers just replaced)
   c->batch = BatchRecord();  // ... and so did the last batch: its record points into them (lcs_batch_collect / _readback then refuse)
+  c->screen_pending = false;
   c->cap_slots = n_slots;
   c->cap_n_cap = n_cap;
   c->cap_n_f = n_f;
@@ -387,6 +388,29 @@ int lcs_set_float_batch_probe(lcs_ctx *c, int on) {
   return LCS_OK;
 }
 
+int lcs_set_batch_screen(lcs_ctx *c, int on) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  c->batch_screen = on != 0;
+  c->screen_skip = 0;
+  return LCS_OK;
+}
+int lcs_get_batch_screen(const lcs_ctx *c, int *on) {
+  if (!c || !on) return LCS_ERR_BAD_ARG;
+  *on = c->batch_screen ? 1 : 0;
+  return LCS_OK;
+}
+// From the header the last lcs_batch_collect brought over (k_pack_results copies the screen's counters into it)
+int lcs_last_screen_stats(lcs_ctx *c, int stats[4]) {
+  if (!c || !stats || !c->h_res || c->batch.l.n_buf <= 0) return LCS_ERR_BAD_ARG;
+  const int *hdr = reinterpret_cast<const int *>(c->h_res.get());
+  const Launch &L = c->batch.l;
+  stats[0] = L.screen ? hdr[2] : 0;
+  stats[1] = L.screen ? L.n_buf * LCS_I8_TILES : 0;
+  stats[2] = L.screen ? hdr[2] * L.geo.G : 0;
+  stats[3] = L.screen ? hdr[3] >> 16 : 0;
+  return LCS_OK;
+}
+
 int lcs_set_duplex(lcs_ctx *c, int duplex) {
   if (!c) return LCS_ERR_BAD_ARG;
   if (duplex != LCS_DUPLEX_FDD && duplex != LCS_DUPLEX_TDD) { c->err = "duplex is neither LCS_DUPLEX_FDD nor LCS_DUPLEX_TDD"; return LCS_ERR_BAD_ARG; }
@@ -548,7 +572,12 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   if ((rc = probe_c64_batch(c, xc_route(facts).may_probe, d_capbufs, (size_t)2 * n_cap * n_buf))) return rc;
   const int fmt_in = fmt;      // what the caller handed over: the hint bookkeeping goes by it
   if (c->last_c64_routed) { d_capbufs = c->c64_u8; fmt = LCS_FMT_IQ_U8; facts.u8 = true; }
+  // the screen pays while few tiles are flagged: after a batch that flagged many (lcs_batch_collect) the next LCS_SCREEN_SKIP batches that
+  // would be screened run the three-digit kernel alone -- the records are the same either way, so a wrong guess costs time only
+  // (under an open stream the screen's work list could not be allocated: such batches run unscreened)
+  facts.screen_on = c->batch_screen && c->screen_skip == 0 && !c->st_open;
   const XcRoute r = xc_route(facts);
+  if (c->batch_screen && c->screen_skip > 0 && r.kernel == XcKernel::i8) --c->screen_skip;
   if ((rc = lcs_ensure_xc(c, r.sets))) return rc;
   // ingest: int8 copies of a u8 source (the fp64 stages read them), fp16 hi / lo pairs of a complex<float> one that holds the fp16 set
   CapSrc src;
@@ -557,6 +586,7 @@ int lcs_batch_enqueue(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uin
   Launch L = make_launch(c, n_buf, n_cap, src);
   L.geo = geo;
   L.xc = r.kernel;
+  L.screen = r.screen;
   L.needed_rows_only = true;
   L.tfoec_parts = 2;
   if ((rc = lcs_launch_xcorr(c, L, false, true))) return rc;
@@ -624,6 +654,11 @@ int lcs_batch_collect(lcs_ctx *c, lcs_cell *cells, int max_cells_per_buf, int *n
       batch.cell_rounds = rounds;
       if ((rc = lcs_launch_pack_results(c, L, true))) return rc;
       continue;
+    }
+    if (L.screen && !batch.list_ops_counted) {      // the three-digit launch over the flagged tiles: counted once its size is known
+      c->last_xc_ops += lcs_i8_list_ops(L.geo, hdr[2], hdr[3] & 0xFFFF);
+      batch.list_ops_counted = true;
+      if (LCS_SCREEN_DENSE * hdr[2] > nb * LCS_I8_TILES) c->screen_skip = LCS_SCREEN_SKIP;
     }
     const int total = hdr[0];
     if ((size_t)total > first) {
@@ -776,6 +811,7 @@ int lcs_batch_readback(lcs_ctx *c, int buf, float *single, double *pow_, int32_t
   const XcGeom &geo = c->batch.l.geo;
   const size_t NE = 3 * LCS_N_IDX;
   int rc;
+  if ((rc = lcs_launch_xcorr_complete(c, c->batch.l))) return rc;      // a screened batch: the arrays become the exact path's first
   if (single) {
     if ((rc = lcs_launch_single_layout(c, c->batch.l, buf, c->sref, 1))) return rc;
     HIPCHK(c, hipMemcpyAsync(single, c->sref, sizeof(float) * NE * geo.n_f, hipMemcpyDeviceToHost, c->stream));
@@ -1660,7 +1696,7 @@ int lcs_foe_finish(lcs_ctx *c, const void *d_words, const double *d_meta, const 
 // that the graph's copy nodes read at execution time.
 namespace {
 // xc_route for the stream: the sets its open allocates, the kernel its chain runs
-XcRoute stream_route(const lcs_ctx *c, int fmt, const XcGeom &geo) { return xc_route(route_facts(c, XcCaller::stream, fmt == LCS_FMT_IQ_U8, geo.n_comb)); }
+extern "C++" XcRoute stream_route(const lcs_ctx *c, int fmt, const XcGeom &geo) { return xc_route(route_facts(c, XcCaller::stream, fmt == LCS_FMT_IQ_U8, geo.n_comb)); }
 // the chain as slot k sees it: its own pinned input buffer and parameter / result block, the shared device workspace.  Its kernels
 // take the slot parameters and the hypothesis from the stream's device mirror (one copy per push), not from the workspace arrays the
 // other entry points fill.
@@ -1841,6 +1877,7 @@ int lcs_last_xcorr_ms(lcs_ctx *c, float *ms, int *n_launches) {
 int lcs_last_frq_repairs(lcs_ctx *c, int *n_positions) {
   if (!c || !n_positions || !c->n_fix) return LCS_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = lcs_launch_xcorr_complete(c, c->batch.l)) return rc;
   HIPCHK(c, hipMemcpyAsync(n_positions, c->n_fix, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
@@ -1852,6 +1889,7 @@ int lcs_last_frq_repair_stats(lcs_ctx *c, int *n_listed, int *n_unrepaired) {
   if (!c || !n_listed || !n_unrepaired || !c->n_fix) return LCS_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   int v[2] = {0, 0};
+  if (int rc = lcs_launch_xcorr_complete(c, c->batch.l)) return rc;
   HIPCHK(c, hipMemcpyAsync(v, c->n_fix, sizeof(v), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *n_listed = v[0];

@@ -49,6 +49,10 @@
 #define LCS_FRQ_TIE_EPS 4e-6f
 #define LCS_I8_KB 5          // 32-tap blocks of the int8 correlation kernel
 #define LCS_I8_IMG 17024     // dwords of the int8 kernel's operand image per (buffer, group) (pss_xcorr_i8.hip)
+#define LCS_I8_LAGS 512      // lags per workgroup (lag tile) of the int8 kernel, and its tiles per buffer: what the batch screen flags
+#define LCS_I8_TILES ((LCS_N_IDX + LCS_I8_LAGS - 1) / LCS_I8_LAGS)
+#define LCS_SCREEN_SKIP 63   // batches that go unscreened after one that flagged more than 1 / LCS_SCREEN_DENSE of its tiles
+#define LCS_SCREEN_DENSE 5
 #define LCS_F16_IMG 11840    // the same for the fp16 kernel (pss_xcorr_f16.hip)
 #define LCS_MAX_WORK 1024    // most cells carried into the TFG/MIB stages per round (~6 MB each)
 #define LCS_WORK_DEFAULT 512 // cells per round a context starts with (3 GB, allocated on first use); it doubles by itself when a batch carries more
@@ -183,6 +187,7 @@ struct Launch {
   XcKernel xc = XcKernel::fp32;         // xc_route's choice (xcorr_route.h)
   CapSrc src{};                         // what the fp64 stages read: decided where the data is ingested (lcs_launch_ingest*)
   FrqRepair repair = FrqRepair::all;
+  bool screen = false;                  // xc_route's `screen`: the int8 kernel's two-digit pass, then three digits over the flagged tiles
   bool single_stream = false;           // everything on `stream`, no hand-over to stream_xc (a context with an open stream)
   bool needed_rows_only = false;        // fused chains: compute only the grid rows later stages read (tfg_mib.hip)
   int grid_items = 64;                  // workgroups per work-list axis of the per-cell kernels (they loop over the list)
@@ -201,6 +206,7 @@ struct BatchRecord {
   int stage_mask = 0;
   int fmt = 0;                          // the format the caller handed over
   int cell_rounds = 0;                  // per-cell rounds launched so far (l.round_cells cells each)
+  bool list_ops_counted = false;        // a screened batch: lcs_batch_collect has added the flagged tiles' launch to last_xc_ops
 };
 
 // Pinned block shared with the captured graph of the streaming mode.
@@ -262,6 +268,11 @@ struct I8Set {
   DevBuf<uint32_t> brow8;            // int8 three-digit template operands: one image of resident rows per (slot, group)
   DevBuf<double> tq;                 // per template: integer scale q
   DevBuf<float> tsc;                 // per template: 1 / (128 q)
+  // the batch screen (k_screen_flag): what the three-digit kernel redoes
+  DevBuf<int> scr_state;             // [4]: work items, tiles flagged, buffers that flagged everything, last tiles among the flagged
+  DevBuf<int> scr_tile;              // [S][LCS_I8_TILES]: 1 = the tile is flagged
+  DevBuf<unsigned> scr_items;        // [S * LCS_I8_TILES * G]: the work items of k_xcorr_i8x3<3, true>
+  DevBuf<float> scr_zmin;            // [S]: the buffer's smallest Z_th1, rounded down (0: the buffer flagged everything)
   bool ready = false;
 };
 struct F16Set {
@@ -457,6 +468,11 @@ struct lcs_ctx : lcs_ctx_queues {
     size_t last_stride = 0;         // of llr in the last call, and its subframes: lcs_pdsch_last_soft
     int last_n_sf = 0;
   } pdsch;
+  bool batch_screen = true;         // lcs_set_batch_screen: int8 batches of two or more windows are screened (xcorr_route.h)
+  int screen_skip = 0;              // batches left unscreened before the next one is screened again: a batch that flagged more than a fifth of
+                                    // its tiles (a busy band) costs more screened than not, and the next ones will be alike (lcs_batch_collect)
+  bool screen_pending = false;      // the last correlation call was a screened batch: outside its flagged tiles the arrays hold the screen's
+                                    // values until a debug call completes them (lcs_launch_xcorr_complete)
   bool c64_probe = false;           // lcs_set_float_batch_probe: complex<float> batches are checked for dongle data (every component k/128) and then take the u8 route
   DevBuf<uint8_t> c64_u8;           // ... the bytes such a batch is turned into
   int c64_skip = 0;                 // batches left before the next probe (after a batch that was NOT dongle data)
@@ -608,13 +624,16 @@ bool pbch_derm_inv(int n_e, int16_t *out /*[120][16]*/);    // its inverse: per 
 int lcs_launch_ingest(lcs_ctx *c, const void *d_src, int fmt, int n_buf, uint32_t n_cap, CapSrc *src);
 int lcs_launch_ingest_c128(lcs_ctx *c, uint32_t n_cap, bool *exact, CapSrc *src);   // cap64 -> cap32 + int8 copies; exact: every component is (u8 - 127) / 128
 int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it);
+int lcs_launch_xcorr_complete(lcs_ctx *c, const Launch &L);   // after a screened batch: the three-digit kernel over every tile, full collapse, full repair
 int lcs_ensure_xc(lcs_ctx *c, unsigned sets);   // XcSet bits: the sets a call needs, allocated for the current workspace on first use
 int lcs_launch_single_layout(lcs_ctx *c, const Launch &L, int slot, float *ref_layout, int to_ref);   // group-major <-> [t][idx][foi]
 int lcs_launch_foe_contend(lcs_ctx *c, const Launch &L, const double *fset_g, const long long *d_words, long long *d_words2);
 int lcs_launch_foe_resolve(lcs_ctx *c, long long *d_words, const long long *d_words2);
 // pss_xcorr_i8.hip
 int lcs_launch_fill_brow_i8(lcs_ctx *c, const Launch &L);
-int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map);
+int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map);   // L.screen: the two-digit pass
+int lcs_launch_screen_refine(lcs_ctx *c, const Launch &L);   // behind the screen's collapse: flags, work list, the three-digit kernel over it
+double lcs_i8_list_ops(const XcGeom &geo, int tiles, int last_tiles);   // matrix-core operations of that launch, once the host knows the counts
 // pss_xcorr_f16.hip
 int lcs_launch_ingest_f16(lcs_ctx *c, const void *d_src, int n_buf, uint32_t n_cap, CapSrc *src);   // complex<float> -> fp16 hi / lo pairs + per-buffer scale (+ cap32 unless read in place)
 int lcs_launch_fill_brow_f16(lcs_ctx *c, const Launch &L);

@@ -518,6 +518,7 @@ __device__ __forceinline__ void collapse_merge(CollapseBest &b, int lane_xor) {
 // the power's own ~1e-7): most near-ties sit in the noise, and in latency mode the repair is on the critical path.
 __device__ __forceinline__ void collapse_flag(const CollapseBest &r, unsigned pos, unsigned *__restrict__ fix_list, int *__restrict__ n_fix,
                                               const double *__restrict__ zth) {
+  if (!fix_list) return;      // the screen's first collapse: its near-ties are looked for once the flagged tiles hold exact values
   if (r.v > 0.f && r.s >= r.v * (1.0f - LCS_FRQ_TIE_EPS)) {
     if (zth && (double)r.v < 0.999 * zth[(pos / (3 * LCS_N_IDX)) * LCS_N_IDX + pos % LCS_N_IDX]) return;
     fix_list[atomicAdd(n_fix, 1)] = pos;
@@ -529,11 +530,17 @@ __device__ __forceinline__ float4 collapse_row(collapse_gptr base, unsigned byte
   const collapse_f4 r = *reinterpret_cast<const __attribute__((address_space(1))) collapse_f4 *>(base + byte_off);
   return make_float4(r.x, r.y, r.z, r.w);
 }
-template <int DS, bool INCOH>
+// LIST (the batch screen's second collapse): only positions whose whole box -- idx - ds .. idx + ds -- lies in lag tiles the three-digit
+// kernel has redone (tile_flag, k_screen_flag) are formed and written, in the arithmetic of the full collapse (k_collapse_arm2's
+// quotient is the correctly rounded one as well); every other position keeps the screen's value, which is below the buffer's
+// smallest threshold.  Near-ties are listed from zmin[slot] on (with the 0.1 % of collapse_flag to spare): every entry that can
+// reach a threshold is repaired as in a batch without the screen.
+template <int DS, bool INCOH, bool LIST = false>
 __global__ __launch_bounds__(256) void k_collapse(const float *__restrict__ sg, float *__restrict__ incoh,
                                                    double *__restrict__ pow_, float *__restrict__ pow32,
                                                    int *__restrict__ frq, unsigned *__restrict__ fix_list, int *__restrict__ n_fix,
-                                                   const double *__restrict__ zth, float *__restrict__ second32, XcGeom geo, int n_buf) {
+                                                   const double *__restrict__ zth, float *__restrict__ second32, XcGeom geo, int n_buf,
+                                                   const int *__restrict__ tile_flag = nullptr, const float *__restrict__ zmin = nullptr) {
   LCS_TAIL_PRIO();
   constexpr int CT = 64;                           // positions per workgroup
   static_assert(LCS_N_IDX % CT == 0 && LCS_TG == 16, "k_collapse tiles 9600 positions x 16 columns");
@@ -545,6 +552,15 @@ __global__ __launch_bounds__(256) void k_collapse(const float *__restrict__ sg, 
   for (int vb = blockIdx.x; vb < NT * n_buf; vb += gridDim.x) {       // (position tile, slot), tile fastest
     const int slot = vb / NT;
     const int idx = (vb % NT) * CT + (tid >> 2);
+    bool mine = true;
+    if (LIST) {
+      static_assert(LCS_I8_LAGS % CT == 0, "a workgroup's positions lie in one lag tile");
+      const int *tf = tile_flag + slot * LCS_I8_TILES;
+      const int t0 = (vb % NT) * CT / LCS_I8_LAGS;
+      if (!tf[t0]) continue;                                            // (uniform)
+      const int lo = idx - ds < 0 ? idx - ds + LCS_N_IDX : idx - ds, hi = idx + ds >= LCS_N_IDX ? idx + ds - LCS_N_IDX : idx + ds;
+      mine = tf[lo / LCS_I8_LAGS] && tf[hi / LCS_I8_LAGS];
+    }
     // byte offsets of this lane's 16 bytes of the rows idx, idx -+ d (circular in idx, ref :336) within one group
     const unsigned o0 = ((unsigned)idx * 4u + q) * 16u;
     unsigned om[NA], op[NA];
@@ -597,13 +613,14 @@ __global__ __launch_bounds__(256) void k_collapse(const float *__restrict__ sg, 
     collapse_merge(b0, 1); collapse_merge(b0, 2);
     collapse_merge(b1, 1); collapse_merge(b1, 2);
     collapse_merge(b2, 1); collapse_merge(b2, 2);
-    if (q < 3) {                                                       // lane q of the position writes PSS q
+    if (q < 3 && mine) {                                               // lane q of the position writes PSS q
       const CollapseBest r = (q == 0) ? b0 : (q == 1 ? b1 : b2);
       const size_t o = ((size_t)slot * 3 + q) * LCS_N_IDX + idx;
       pow_[o] = (double)r.v;
       pow32[o] = r.v;                                                  // what the fused peak search loads
       frq[o] = r.foi;
       if (second32) second32[o] = r.s;                                 // hypotheses split over GPUs: lcs_foe_contend compares it with the GLOBAL maximum
+      if (LIST) { if (r.v < 0.999f * zmin[slot]) continue; }
       collapse_flag(r, (unsigned)o, fix_list, n_fix, zth);
     }
   }
@@ -1163,11 +1180,12 @@ static void xc_collapse(lcs_ctx *c, const Launch &L, bool want_incoh) {
   float *pow32 = reinterpret_cast<float *>(c->work.get());
   const double *zf = L.repair == FrqRepair::peaks_only ? c->zth : nullptr;         // only near-ties that can become a peak
   float *s2 = L.repair == FrqRepair::none_keep_2nd ? c->second32 : nullptr;        // the runner-up values for lcs_foe_contend
+  unsigned *fix_list = L.screen ? nullptr : c->fix_list.get();                     // the screen lists near-ties behind its second collapse (xc_screen_refine)
   if (geo.ds == 2 && !incoh && geo.cpg == LCS_TG)
-    hipLaunchKernelGGL(k_collapse_arm2, dim3((LCS_N_IDX / (4 * COLLAPSE_OUT)) * n_buf), block, 0, c->stream, c->single, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
-  else if (geo.ds == 2 && !incoh) hipLaunchKernelGGL((k_collapse<2, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
-  else if (!incoh) hipLaunchKernelGGL((k_collapse<-1, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);   // any arm, no debug copy
-  else hipLaunchKernelGGL((k_collapse<-1, true>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, zf, s2, geo, n_buf);
+    hipLaunchKernelGGL(k_collapse_arm2, dim3((LCS_N_IDX / (4 * COLLAPSE_OUT)) * n_buf), block, 0, c->stream, c->single, c->pow_, pow32, c->frq, fix_list, c->n_fix, zf, s2, geo, n_buf);
+  else if (geo.ds == 2 && !incoh) hipLaunchKernelGGL((k_collapse<2, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, fix_list, c->n_fix, zf, s2, geo, n_buf);
+  else if (!incoh) hipLaunchKernelGGL((k_collapse<-1, false>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, fix_list, c->n_fix, zf, s2, geo, n_buf);   // any arm, no debug copy
+  else hipLaunchKernelGGL((k_collapse<-1, true>), grid, block, 0, c->stream, c->single, incoh, c->pow_, pow32, c->frq, fix_list, c->n_fix, zf, s2, geo, n_buf);
 }
 
 // near-ties of the arg-max, recomputed in the reference's arithmetic (a few positions per buffer; the kernel loops over the list)
@@ -1184,17 +1202,62 @@ static void xc_tie_repair(lcs_ctx *c, const Launch &L) {
   });
 }
 
+// The screened batch (L.screen, xcorr_route.h).  The correlation launch above made two digit passes, and the collapse
+// behind it listed no near-ties.  Now: flags and work list, the three-digit kernel over the flagged tiles (lcs_launch_screen_refine),
+// the collapse once more over the positions whose whole box lies in flagged tiles, and the tie repair of the near-ties among them
+// that reach the buffer's smallest threshold.  Every entry the peak search can act on then holds the bits of the unscreened batch.
+static int xc_screen_refine(lcs_ctx *c, const Launch &L) {
+  const XcGeom &geo = L.geo;
+  if (int rc = lcs_launch_screen_refine(c, L)) return rc;
+  float *pow32 = reinterpret_cast<float *>(c->work.get());
+  const dim3 grid((LCS_N_IDX / 64) * L.n_buf), block(256);
+  if (geo.ds == 2)
+    hipLaunchKernelGGL((k_collapse<2, false, true>), grid, block, 0, c->stream, c->single, nullptr, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, nullptr, nullptr, geo, L.n_buf,
+                       c->xcb.i8.scr_tile, c->xcb.i8.scr_zmin);
+  else
+    hipLaunchKernelGGL((k_collapse<-1, false, true>), grid, block, 0, c->stream, c->single, nullptr, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, nullptr, nullptr, geo, L.n_buf,
+                       c->xcb.i8.scr_tile, c->xcb.i8.scr_zmin);
+  return LCS_OK;
+}
+
 int lcs_launch_xcorr(lcs_ctx *c, const Launch &L, bool want_incoh, bool time_it) {
   hipStream_t sxc = L.single_stream ? c->stream : c->stream_xc;      // a context with an open stream keeps everything on its main stream: no hand-over
   int rc;
+  if (L.screen && (L.xc != XcKernel::i8 || want_incoh || L.repair != FrqRepair::all)) { c->err = "the screen serves int8 batches"; return LCS_ERR_BAD_ARG; }
+  c->screen_pending = false;
   if ((rc = xc_tables_and_operands(c, L))) return rc;
   if (!L.single_stream && (rc = xc_hand_over(c, sxc))) return rc;
   xc_signal_power(c, L);
   if ((rc = xc_correlate(c, sxc, L, time_it))) return rc;
   if (!L.single_stream && (rc = xc_hand_back(c, sxc))) return rc;
   xc_collapse(c, L, want_incoh);
+  if (L.screen && (rc = xc_screen_refine(c, L))) return rc;
   xc_tie_repair(c, L);
   HIPCHK(c, hipGetLastError());
+  c->screen_pending = L.screen;
+  return LCS_OK;
+}
+
+// The debug arrays of a screened batch (lcs_batch_readback, lcs_last_frq_repairs, lcs_last_frq_repair_stats): outside the flagged
+// tiles they hold the screen's values.  The first debug call completes them -- the three-digit kernel over every tile of the
+// context's own int8 copies (valid until the next enqueue, like the tables), the full collapse, the full repair: what a batch
+// without the screen leaves, bit for bit.  The cost lands on the debug call.
+int lcs_launch_xcorr_complete(lcs_ctx *c, const Launch &L_batch) {
+  if (!c->screen_pending) return LCS_OK;
+  Launch L = L_batch;
+  L.screen = false;
+  hipStream_t sxc = L.single_stream ? c->stream : c->stream_xc;
+  const double ops = c->last_xc_ops;      // (lcs_last_xcorr_info keeps describing the batch)
+  int rc;
+  HIPCHK(c, hipMemsetAsync(c->n_fix, 0, 2 * sizeof(int), c->stream));
+  if (!L.single_stream && (rc = xc_hand_over(c, sxc))) return rc;
+  if ((rc = xc_correlate(c, sxc, L, false))) return rc;
+  if (!L.single_stream && (rc = xc_hand_back(c, sxc))) return rc;
+  c->last_xc_ops = ops;
+  xc_collapse(c, L, false);
+  xc_tie_repair(c, L);
+  HIPCHK(c, hipGetLastError());
+  c->screen_pending = false;
   return LCS_OK;
 }
 

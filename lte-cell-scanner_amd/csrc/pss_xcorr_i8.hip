@@ -39,6 +39,7 @@
 // (profiles/r04/experiments/ab_i8_resident_rows.txt; a single-copy variant that shifts odd delays into place with
 // v_alignbyte_b32 -- 44 KB of LDS -- was 8 % slower, same file).
 #include "lcs_internal.h"
+#include "screen_bound.h"
 #include <algorithm>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -162,24 +163,24 @@ __global__ __launch_bounds__(256) void k_fill_brow_i8(const float2 *__restrict__
 // Measured (isolated, 16x16x64 issues every ~18 cycles: tools/microbench/mfma_rate.hip): 240 MFMAs x 18 cycles x 15
 // windows x 2 waves per SIMD = 130 k of a workgroup's ~160 k cycles; the rest is the image load, the per-window operand
 // latency in front of the first MFMA, and the share of the epilogues the SIMD's other wave does not cover.
-__global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restrict__ cap8, const uint16_t *__restrict__ cap8s,
-                                                          const int *__restrict__ smin, const int *__restrict__ start,
-                                                          const uint32_t *__restrict__ brow,
-                                                          const float *__restrict__ sc, float *__restrict__ sg, XcGeom geo,
-                                                          int slot0, int n_slots, int xcd_map) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int per_slot = I8_TILES * geo.G;
-  int q, sidx;
-  if (xcd_map) { sidx = blockIdx.x & 7; q = blockIdx.x >> 3; sidx += 8 * (q / per_slot); q = q % per_slot; }
-  else { sidx = blockIdx.x / per_slot; q = blockIdx.x % per_slot; }
-  if (sidx >= n_slots) return;
-  const int slot = slot0 + sidx, g = q / I8_TILES, idx0 = (q % I8_TILES) * I8_LAGS;
+//
+// ND, the digit count.  3: every element exact to ~1e-7, as described above.  2: the SCREEN of a batch (lcs_launch_xcorr) -- digit
+// passes 2 and 1 only, into the one shared accumulator (|S2| <= 4.5e6 as well: 256 S2 + S1 stays below 2^31), one conversion per
+// output, the factor 256 folded into the final scale; the digit-0 blocks of the image are not loaded.  160 MFMAs per wave-window
+// instead of 240, no second accumulator set.  What the dropped digit can change is bounded in screen_bound.h.
+// One tile of one (buffer, group): the body of a workgroup of the grid form, of a work item of the list form.
+template <int ND>
+__device__ __forceinline__ void i8_tile(const uint16_t *__restrict__ cap8, const uint16_t *__restrict__ cap8s,
+                                        const int *__restrict__ smin, const int *__restrict__ start, const uint32_t *__restrict__ brow,
+                                        const float *__restrict__ sc, float *__restrict__ sg, const XcGeom &geo, int slot, int g, int idx0, int tid) {
+  static_assert(ND == 2 || ND == 3, "two digits (the screen) or three");
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int widx0 = idx0 + wave * (I8_MT * 16);
 
   constexpr int PCPY = I8_PCPY, PBUF = 2 * PCPY;
   __shared__ uint32_t ldsA0[4][PBUF], ldsA1[4][PBUF];      // per wave: [natural copy | shifted copy], two buffers (two VARIABLES, see below)
   __shared__ uint32_t ldsR[I8R_IMG];
-  constexpr int NBLK = 3 * I8_NKB;
+  constexpr int NBLK = ND * I8_NKB;
   const size_t cstride = lcs_cap8_stride(geo.n_cap);
   // (uniform pointers and 32-bit per-lane offsets wherever a lane's address is formed: the kernel sits at its register budget)
   const uint32_t *capd = reinterpret_cast<const uint32_t *>(cap8 + (size_t)slot * cstride);     // dword j = samples (2j, 2j+1)
@@ -198,7 +199,10 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
 #pragma unroll
     for (int c_ = 0; c_ < (NCI + 3) / 4; ++c_) {
       const int ch_ = wave + 4 * c_;
-      if (ch_ < NCI)
+      // (the screen reads no digit-0 block: the two of them open each copy, and a chunk that lies wholly inside them stays away)
+      const int in_cpy_ = ch_ * 256 - (ch_ * 256 >= I8R_COPY ? I8R_COPY : 0);
+      const bool unread_ = ND == 2 && in_cpy_ + 256 <= 2 * I8R_BLK && (ch_ * 256 >= I8R_COPY || ch_ * 256 + 256 <= I8R_COPY);
+      if (ch_ < NCI && !unread_)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(img + ch_ * 256 + lane * 4),
                                          (__attribute__((address_space(3))) void *)(ldsR + ch_ * 256), 16, 0, 0);
     }
@@ -269,14 +273,14 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
     for (int op = 0; op < 2; ++op) I8_RD_B(2, 0, op, Bq[0][op]);
 #define I8_PF_MFMA(MT)                                                                                       \
   {                                                                                                          \
-    if (d == 0) {                                                                                            \
+    if (ND == 3 && d == 0) {                                                                                 \
       const i32x4 cr = (j == 0) ? (i32x4){0, 0, 0, 0} : tR[MT];                                              \
       const i32x4 ci = (j == 0) ? (i32x4){0, 0, 0, 0} : tI[MT];                                              \
       tR[MT] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Aw[2 * kb + (MT)], Bq[e & 1][0], cr, 0, 0, 0);          \
       tI[MT] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Aw[2 * kb + (MT)], Bq[e & 1][1], ci, 0, 0, 0);          \
-    } else {                                                                                                 \
-      const i32x4 cr = (d == 1 && j == 0) ? (i32x4){0, 0, 0, 0} : (d == 2 && j == 0) ? aR[MT] << 8 : aR[MT]; \
-      const i32x4 ci = (d == 1 && j == 0) ? (i32x4){0, 0, 0, 0} : (d == 2 && j == 0) ? aI[MT] << 8 : aI[MT]; \
+    } else {      /* the shared accumulator: opened by pass ND - 2, shifted in front of pass ND - 1 */        \
+      const i32x4 cr = (d == ND - 2 && j == 0) ? (i32x4){0, 0, 0, 0} : (d == ND - 1 && j == 0) ? aR[MT] << 8 : aR[MT]; \
+      const i32x4 ci = (d == ND - 2 && j == 0) ? (i32x4){0, 0, 0, 0} : (d == ND - 1 && j == 0) ? aI[MT] << 8 : aI[MT]; \
       aR[MT] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Aw[2 * kb + (MT)], Bq[e & 1][0], cr, 0, 0, 0);          \
       aI[MT] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Aw[2 * kb + (MT)], Bq[e & 1][1], ci, 0, 0, 0);          \
     }                                                                                                        \
@@ -301,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int mt = 1; mt < I8_MT; ++mt) I8_PF_MFMA(mt);
-      if (d == 1) {                        // digit-1 pass: the finished digit-2 sums of sub-tiles j, j + NKB go to float
+      if (ND == 3 && d == 1) {             // digit-1 pass: the finished digit-2 sums of sub-tiles j, j + NKB go to float
 #pragma unroll
         for (int mt = j; mt < I8_MT; mt += I8_NKB)
 #pragma unroll
@@ -314,8 +318,9 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
     for (int mt = 0; mt < I8_MT; ++mt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {     // integer correlation S2 * 65536 + (256 S1 + S0) in fp32; scaled by 1 / (128 q)^2 at the end
-        const float xr = fmaf(fR[mt][r], 65536.f, (float)aR[mt][r]);
-        const float xi = fmaf(fI[mt][r], 65536.f, (float)aI[mt][r]);
+        // (the screen: 256 S2 + S1 in one rounding; the factor 256 waits in the final scale)
+        const float xr = ND == 3 ? fmaf(fR[mt][r], 65536.f, (float)aR[mt][r]) : (float)aR[mt][r];
+        const float xi = ND == 3 ? fmaf(fI[mt][r], 65536.f, (float)aI[mt][r]) : (float)aI[mt][r];
         P[mt][r] = fmaf(xi, xi, fmaf(xr, xr, P[mt][r]));
       }
   };
@@ -332,7 +337,8 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
 #undef I8_DELAY_AND_PREFETCH
 #undef I8_RD_B
   const float ncomb = (float)geo.n_comb;
-  const float my_sc = sc[(size_t)slot * GM * LCS_TG + g * LCS_TG + (lane & 15)];
+  const float col_sc = sc[(size_t)slot * GM * LCS_TG + g * LCS_TG + (lane & 15)];
+  const float my_sc = ND == 3 ? col_sc : col_sc * 256.f;
   float *o = sg + (((size_t)slot * geo.G + g) * LCS_N_IDX) * LCS_TG + (lane & 15);
 #pragma unroll
   for (int mt = 0; mt < I8_MT; ++mt)
@@ -341,6 +347,105 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
       const int idx = widx0 + mt * 16 + 4 * (lane >> 4) + r;
       if (idx < LCS_N_IDX) o[(size_t)idx * LCS_TG] = __fdiv_rn(P[mt][r] * (my_sc * my_sc), ncomb);
     }
+}
+
+// A work item of the list form: slot << 16 | group << 5 | lag tile (shifts only: the decoded item stays in scalar registers)
+static_assert(I8_TILES <= 32, "a work item keeps its lag tile in five bits");
+#define I8_ITEM_SLOTS 65536
+#define I8_ITEM_GROUPS 2048
+__host__ __device__ static inline unsigned i8_item(int slot, int g, int tile) { return ((unsigned)slot << 16) | ((unsigned)g << 5) | (unsigned)tile; }
+
+// LIST = false, the grid form: workgroup q of a slot is (group q / 19, lag tile q % 19).  LIST = true: a fixed grid walks the
+// *n_items work items of `items` (device memory: the launch needs no count on the host, and a list of every tile is the whole
+// batch); each item overwrites its tile of `sg` exactly as a workgroup of the grid form would.  The barrier in front of an item's
+// image load keeps it from the rows the slower waves of the item before still read.
+template <int ND, bool LIST>
+__global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restrict__ cap8, const uint16_t *__restrict__ cap8s,
+                                                          const int *__restrict__ smin, const int *__restrict__ start,
+                                                          const uint32_t *__restrict__ brow,
+                                                          const float *__restrict__ sc, float *__restrict__ sg, XcGeom geo,
+                                                          int slot0, int n_slots, int xcd_map,
+                                                          const unsigned *__restrict__ items, const int *__restrict__ n_items) {
+  if (LIST) {
+    const int n = *n_items;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+      if (i != (int)blockIdx.x) __syncthreads();
+      const unsigned it = (unsigned)__builtin_amdgcn_readfirstlane((int)items[i]);
+      // (the lane's own constants are formed anew per item: hoisted out of this loop they cost 10 registers the kernel does not have)
+      int tid = threadIdx.x;
+      asm volatile("" : "+v"(tid));
+      i8_tile<ND>(cap8, cap8s, smin, start, brow, sc, sg, geo, (int)(it >> 16), (int)((it >> 5) & (I8_ITEM_GROUPS - 1)), (int)(it & 31u) * I8_LAGS, tid);
+    }
+  } else {
+    const int per_slot = I8_TILES * geo.G;
+    int q, sidx;
+    if (xcd_map) { sidx = blockIdx.x & 7; q = blockIdx.x >> 3; sidx += 8 * (q / per_slot); q = q % per_slot; }
+    else { sidx = blockIdx.x / per_slot; q = blockIdx.x % per_slot; }
+    if (sidx >= n_slots) return;
+    i8_tile<ND>(cap8, cap8s, smin, start, brow, sc, sg, geo, slot0 + sidx, q / I8_TILES, (q % I8_TILES) * I8_LAGS, threadIdx.x);
+  }
+}
+
+// ---------------------------------------------------------------- the screen of a batch: which tiles the three-digit kernel redoes
+// One workgroup per buffer, behind the collapse of the screened array.  Zmin = the smallest Z_th1 of the buffer's 9600 lags;
+// T = lcs_screen_threshold(Zmin) with the buffer's largest column scale (screen_bound.h): a (PSS, lag) whose screened collapsed
+// power is below T has an exact collapsed power below Zmin <= every threshold and can neither be recorded nor stop the peak search
+// differently.  Every other one -- "hot" -- must come out with the exact path's bits: its collapse reads `single` at
+// the lags idx - ds .. idx + ds (circular), the tie repair and the peak search's refinement the same ones, so the lag tiles of idx - ds,
+// idx and idx + ds are flagged.  A buffer without a usable T (a silent one: Zmin not above e^2) flags every tile.
+// state: [0] work items, [1] tiles flagged, [2] buffers that flagged everything, [3] last (three-wave) tiles among the flagged.
+__global__ __launch_bounds__(256) void k_screen_flag(const float *__restrict__ pow32, const double *__restrict__ zth, const float *__restrict__ sc,
+                                                     XcGeom geo, float *__restrict__ zmin, int *__restrict__ state, int *__restrict__ tile_flag,
+                                                     unsigned *__restrict__ items) {
+  LCS_TAIL_PRIO();
+  const int slot = blockIdx.x, tid = threadIdx.x;
+  __shared__ double s_z[4];
+  __shared__ float s_sc[4];
+  __shared__ int s_bad[4];
+  __shared__ int s_flag[I8_TILES];
+  const double *z = zth + (size_t)slot * LCS_N_IDX;
+  double zm = INFINITY;
+  int bad = 0;
+  for (int i = tid; i < LCS_N_IDX; i += 256) { const double v = z[i]; bad |= !(v > 0.0); zm = fmin(zm, v); }
+  float sm = 0.f;
+  for (int i = tid; i < geo.G * LCS_TG; i += 256) sm = fmaxf(sm, sc[(size_t)slot * GM * LCS_TG + i]);
+  for (int o = 32; o; o >>= 1) { zm = fmin(zm, __shfl_xor(zm, o)); sm = fmaxf(sm, __shfl_xor(sm, o)); }
+  bad = __any(bad);
+  if ((tid & 63) == 0) { s_z[tid >> 6] = zm; s_sc[tid >> 6] = sm; s_bad[tid >> 6] = bad; }
+  if (tid < I8_TILES) s_flag[tid] = 0;
+  __syncthreads();
+  zm = fmin(fmin(s_z[0], s_z[1]), fmin(s_z[2], s_z[3]));
+  sm = fmaxf(fmaxf(s_sc[0], s_sc[1]), fmaxf(s_sc[2], s_sc[3]));
+  bad = s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3];
+  const double T = bad ? -1.0 : lcs_screen_threshold(geo.n_comb, geo.ds, (double)sm, zm);
+  const bool all = !(T > 0.0);
+  const float *pw = pow32 + (size_t)slot * 3 * LCS_N_IDX;
+  if (all) { if (tid < I8_TILES) s_flag[tid] = 1; }
+  else
+    for (int e = tid; e < 3 * LCS_N_IDX; e += 256) {
+      if ((double)pw[e] < T) continue;                  // (a NaN is hot)
+      const int idx = e % LCS_N_IDX;
+      const int lo = idx - geo.ds < 0 ? idx - geo.ds + LCS_N_IDX : idx - geo.ds, hi = idx + geo.ds >= LCS_N_IDX ? idx + geo.ds - LCS_N_IDX : idx + geo.ds;
+      s_flag[idx / I8_LAGS] = 1; s_flag[lo / I8_LAGS] = 1; s_flag[hi / I8_LAGS] = 1;
+    }
+  __syncthreads();
+  if (tid < I8_TILES) {
+    const int f = s_flag[tid];
+    tile_flag[slot * I8_TILES + tid] = f;
+    if (f) {
+      const int at = atomicAdd(state, geo.G);
+      for (int g = 0; g < geo.G; ++g) items[at + g] = i8_item(slot, g, tid);
+      atomicAdd(state + 1, 1);
+      if (tid == I8_TILES - 1) atomicAdd(state + 3, 1);
+    }
+  }
+  if (tid == 0) {
+    // what the second collapse lists near-ties by: rounded down, so that no entry at or above Zmin is left out
+    float zf = (float)zm;
+    if ((double)zf > zm) zf = __uint_as_float(__float_as_uint(zf) - 1u);
+    zmin[slot] = all ? 0.f : zf;
+    if (all) atomicAdd(state + 2, 1);
+  }
 }
 
 int lcs_launch_fill_brow_i8(lcs_ctx *c, const Launch &L) {
@@ -354,12 +459,51 @@ int lcs_launch_fill_brow_i8(lcs_ctx *c, const Launch &L) {
 int lcs_launch_xcorr_i8(lcs_ctx *c, hipStream_t sxc, const Launch &L, int slot0, int n_slots, int xcd_map) {
   const XcGeom &geo = L.geo;
   const unsigned grid = (unsigned)(I8_TILES * geo.G * n_slots);
-  hipLaunchKernelGGL(k_xcorr_i8x3, dim3(grid), dim3(256), 0, sxc, c->xcb.i8.cap8, c->xcb.i8.cap8s, c->smin, c->start, c->xcb.i8.brow8, c->xcb.i8.tsc, c->single, geo, slot0,
-                     n_slots, xcd_map);
+  const I8Set &s = c->xcb.i8;
+  if (L.screen)
+    hipLaunchKernelGGL((k_xcorr_i8x3<2, false>), dim3(grid), dim3(256), 0, sxc, s.cap8, s.cap8s, c->smin, c->start, s.brow8, s.tsc, c->single, geo, slot0, n_slots, xcd_map,
+                       nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((k_xcorr_i8x3<3, false>), dim3(grid), dim3(256), 0, sxc, s.cap8, s.cap8s, c->smin, c->start, s.brow8, s.tsc, c->single, geo, slot0, n_slots, xcd_map,
+                       nullptr, nullptr);
   HIPCHK(c, hipGetLastError());
-  // executed work: per wave and window 3 digits x I8_NKB tap blocks x I8_MT sub-tiles x (re, im) MFMAs of 16x16x64 MACs
+  // executed work: per wave and window 3 (the screen: 2) digits x I8_NKB tap blocks x I8_MT sub-tiles x (re, im) MFMAs of 16x16x64 MACs
   const double waves = (double)n_slots * geo.G * ((LCS_N_IDX + I8_MT * 16 - 1) / (I8_MT * 16));      // the waves that own lags (75 of a group's 76)
-  c->last_xc_ops += waves * geo.n_comb * (3.0 * I8_NKB * I8_MT * 2) * (2.0 * 16 * 16 * 64);
+  c->last_xc_ops += waves * geo.n_comb * ((L.screen ? 2.0 : 3.0) * I8_NKB * I8_MT * 2) * (2.0 * 16 * 16 * 64);
   c->last_xc_kernel = "k_xcorr_i8x3";
+  return LCS_OK;
+}
+// a flagged tile is G work items of four waves each, the buffer's last tile of three
+double lcs_i8_list_ops(const XcGeom &geo, int tiles, int last_tiles) {
+  static_assert(LCS_I8_LAGS == I8_LAGS && LCS_I8_TILES == I8_TILES, "lcs_internal.h names the kernel's tiling");
+  const double waves = (double)geo.G * (4.0 * tiles - (4 - (LCS_N_IDX - (I8_TILES - 1) * I8_LAGS + I8_MT * 16 - 1) / (I8_MT * 16)) * (double)last_tiles);
+  return waves * geo.n_comb * (3.0 * I8_NKB * I8_MT * 2) * (2.0 * 16 * 16 * 64);
+}
+// The screen's second half, on the main stream behind the collapse of the screened array: which tiles can matter, and the
+// three-digit kernel over those.  A fixed grid of two workgroups per compute unit reads the item count on the device -- no host
+// synchronisation, and no capacity to overflow: the list holds at most every tile.  The launch is a few per cent of a full one and
+// runs beside the next context's screen; the rule that two FULL correlation launches do not interleave (lcs_launch_xcorr) is the screen's.
+int lcs_launch_screen_refine(lcs_ctx *c, const Launch &L) {
+  const XcGeom &geo = L.geo;
+  I8Set &s = c->xcb.i8;
+  const size_t S = (size_t)c->cap_slots;
+  if (L.n_buf > I8_ITEM_SLOTS || geo.G > I8_ITEM_GROUPS) { c->err = "batch too large for the screen's work items"; return LCS_ERR_BAD_ARG; }
+  if (s.scr_tile.capacity() < S * I8_TILES || s.scr_items.capacity() < S * I8_TILES * (size_t)c->cap_G) {
+    if (c->st_open) { c->err = "the screen's buffers cannot be allocated while a stream is open: lcs_stream_close first"; return LCS_ERR_BAD_ARG; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int rc;
+    if ((rc = s.scr_state.alloc(c, 4)) || (rc = s.scr_tile.alloc(c, S * I8_TILES)) || (rc = s.scr_items.alloc(c, S * I8_TILES * (size_t)c->cap_G)) ||
+        (rc = s.scr_zmin.alloc(c, S)))
+      return rc;
+  }
+  HIPCHK(c, hipMemsetAsync(s.scr_state, 0, 4 * sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_screen_flag, dim3(L.n_buf), dim3(256), 0, c->stream, reinterpret_cast<const float *>(c->work.get()), c->zth, s.tsc, geo, s.scr_zmin, s.scr_state,
+                     s.scr_tile, s.scr_items);
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const unsigned grid = (unsigned)std::min<long long>(2LL * cus, (long long)L.n_buf * I8_TILES * geo.G);
+  hipLaunchKernelGGL((k_xcorr_i8x3<3, true>), dim3(grid), dim3(256), 0, c->stream, s.cap8, s.cap8s, c->smin, c->start, s.brow8, s.tsc, c->single, geo, 0, L.n_buf, 0,
+                     s.scr_items, s.scr_state);
+  HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

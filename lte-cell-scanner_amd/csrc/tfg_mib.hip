@@ -84,13 +84,14 @@ __global__ __launch_bounds__(64) void k_gather_work(const lcs_cell *__restrict__
   if (lane == 0) { n_work[0] = min(max(base - skip, 0), limit); n_work[1] = base; n_work[2] = dup; if (skip == 0) n_work[3] = 0; /* PBCH candidates decoded by the batch (k_pbch counts) */ }
 }
 // Results of a batch, compacted on the device for lcs_batch_collect: hdr[0] = records written, hdr[1] = 1 if a buffer
-// found more peaks than LCS_MAXP holds (impossible for a buffer with positive thresholds, lcs.h), hdr[4..7] = n_work;
+// found more peaks than LCS_MAXP holds (impossible for a buffer with positive thresholds, lcs.h), hdr[4..7] = n_work; of a screened
+// batch (scr = k_screen_flag's counters) hdr[2] = lag tiles flagged, hdr[3] = buffers that flagged everything << 16 | last tiles flagged;
 // cnt[b] = records of buffer b; rec = the records, buffer after buffer.  full: only peaks with SSS and MIB (the reference
 // erases the others, src/CellSearch.cpp:530-534, :554-558); otherwise every peak.  The host then copies a few KB from
 // ONE place instead of n_buf x LCS_MAXP records.
 __global__ __launch_bounds__(64) void k_pack_results(const lcs_cell *__restrict__ peaks, const int *__restrict__ npeaks, int n_buf, int full,
                                                      const int *__restrict__ n_work, int *__restrict__ hdr, int *__restrict__ cnt,
-                                                     lcs_cell *__restrict__ rec) {
+                                                     lcs_cell *__restrict__ rec, const int *__restrict__ scr) {
   LCS_TAIL_PRIO();
   const int lane = threadIdx.x;
   int base = 0, ovf = 0;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(64) void k_pack_results(const lcs_cell *__restrict_
     base += __shfl(incl, 63);
   }
   ovf = __any(ovf);
-  if (lane == 0) { hdr[0] = base; hdr[1] = ovf; hdr[2] = 0; hdr[3] = 0; }
+  if (lane == 0) { hdr[0] = base; hdr[1] = ovf; hdr[2] = scr ? scr[1] : 0; hdr[3] = scr ? (scr[2] << 16) | scr[3] : 0; }
   if (lane < 4) hdr[4 + lane] = n_work ? n_work[lane] : 0;
 }
 // ------------------------------------------------------------ extract_tfg: timestamps
@@ -1048,7 +1049,7 @@ int lcs_launch_pack_results(lcs_ctx *c, const Launch &L, bool full) {
   const int n_buf = L.n_buf;
   int *hdr = reinterpret_cast<int *>(c->res_pack.get());
   hipLaunchKernelGGL(k_pack_results, dim3(1), dim3(64), 0, c->stream, c->peaks, c->npeaks, n_buf, full ? 1 : 0, full ? c->n_work : nullptr, hdr, hdr + 8,
-                     reinterpret_cast<lcs_cell *>(c->res_pack + lcs_pack_rec_offset(n_buf)));
+                     reinterpret_cast<lcs_cell *>(c->res_pack + lcs_pack_rec_offset(n_buf)), L.screen ? c->xcb.i8.scr_state.get() : nullptr);
   HIPCHK(c, hipGetLastError());
   return LCS_OK;
 }

@@ -28,6 +28,7 @@ struct XcFacts {
   int n_comb;                // combining windows
   XcVerdict verdict;         // host caller: unknown until the ingest has run
   bool probe_on, probe_fits; // batch caller: lcs_set_float_batch_probe; xc_probe_fits of the batch
+  bool screen_on = false;    // batch caller: lcs_set_batch_screen (the context's default is on)
 };
 struct XcRoute {
   unsigned sets;             // XcSet bits the caller ensures before it ingests (a stream: at open).  Holding the int8 set, the host caller
@@ -35,6 +36,8 @@ struct XcRoute {
   bool may_probe;            // a complex<float> batch is probed for dongle data first (the caller keeps the c64_skip countdown)
   XcKernel kernel;
   int pack_taps;             // the tap limit the launch's grid is packed for
+  bool screen = false;       // int8 batches of two or more windows: a two-digit pass over every tile, the three-digit kernel over the tiles
+                             // whose collapsed power can reach the detection threshold (pss_xcorr_i8.hip, screen_bound.h)
 };
 inline bool xc_probe_fits(size_t n_samples, uintptr_t src) { return n_samples % 2 == 0 && (src & 15) == 0; }   // k_c64_probe_u8 reads float4
 
@@ -59,5 +62,6 @@ inline XcRoute xc_route(const XcFacts &f) {
     if (f.u8) r.kernel = XcKernel::i8;
   }
   if (f.n_comb == 1) r.kernel = XcKernel::single_exact;
+  r.screen = f.caller == XcCaller::batch && r.kernel == XcKernel::i8 && f.n_comb >= 2 && f.screen_on;
   return r;
 }
