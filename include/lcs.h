@@ -801,8 +801,8 @@ int lcs_last_batch_stats(lcs_ctx *ctx, int stats[8]);
  * Every pointer may be NULL.  This is how the tests pin the batched kernels to the oracle array by array. */
 /* Batches on the int8 kernel with two or more combining windows are SCREENED (on by default): the correlation runs two of the
  * template integers' three base-256 digits over every lag tile, and all three only over the tiles in which a collapsed power can
- * reach the buffer's smallest Z_th1 by a data-independent bound on what the dropped digit changes.  The records a
- * batch returns are the unscreened batch's, byte for byte.  The debug arrays are completed on demand: the first lcs_batch_readback,
+ * reach the buffer's theta -- the smallest value that an entry which reaches the Z_th1 of its own lag can have -- by a
+ * data-independent bound on what the dropped digit changes.  The records a batch returns are the unscreened batch's, byte for byte.  The debug arrays are completed on demand: the first lcs_batch_readback,
  * lcs_last_frq_repairs or lcs_last_frq_repair_stats after a screened batch runs the three-digit kernel over every tile of the
  * context's own int8 copies (valid until the next enqueue), the full collapse and the full repair, and then answers with exactly
  * what a batch without the screen leaves -- the cost lands on that debug call, never on enqueue or collect.

@@ -272,7 +272,7 @@ struct I8Set {
   DevBuf<int> scr_state;             // [4]: work items, tiles flagged, buffers that flagged everything, last tiles among the flagged
   DevBuf<int> scr_tile;              // [S][LCS_I8_TILES]: 1 = the tile is flagged
   DevBuf<unsigned> scr_items;        // [S * LCS_I8_TILES * G]: the work items of k_xcorr_i8x3<3, true>
-  DevBuf<float> scr_zmin;            // [S]: the buffer's smallest Z_th1, rounded down (0: the buffer flagged everything)
+  DevBuf<float> scr_theta;            // [S]: the buffer's theta (screen_bound.h), rounded down: nothing below it is recordable (0: the buffer flagged everything, or nothing)
   bool ready = false;
 };
 struct F16Set {

@@ -532,15 +532,15 @@ __device__ __forceinline__ float4 collapse_row(collapse_gptr base, unsigned byte
 }
 // LIST (the batch screen's second collapse): only positions whose whole box -- idx - ds .. idx + ds -- lies in lag tiles the three-digit
 // kernel has redone (tile_flag, k_screen_flag) are formed and written, in the arithmetic of the full collapse (k_collapse_arm2's
-// quotient is the correctly rounded one as well); every other position keeps the screen's value, which is below the buffer's
-// smallest threshold.  Near-ties are listed from zmin[slot] on (with the 0.1 % of collapse_flag to spare): every entry that can
-// reach a threshold is repaired as in a batch without the screen.
+// quotient is the correctly rounded one as well); every other position keeps the screen's value, which is below T(theta) of the
+// buffer (screen_bound.h).  Near-ties are listed from theta[slot] on (with the 0.1 % of collapse_flag to spare): no entry below theta
+// can be recorded, and every one from theta on is repaired as in a batch without the screen.
 template <int DS, bool INCOH, bool LIST = false>
 __global__ __launch_bounds__(256) void k_collapse(const float *__restrict__ sg, float *__restrict__ incoh,
                                                    double *__restrict__ pow_, float *__restrict__ pow32,
                                                    int *__restrict__ frq, unsigned *__restrict__ fix_list, int *__restrict__ n_fix,
                                                    const double *__restrict__ zth, float *__restrict__ second32, XcGeom geo, int n_buf,
-                                                   const int *__restrict__ tile_flag = nullptr, const float *__restrict__ zmin = nullptr) {
+                                                   const int *__restrict__ tile_flag = nullptr, const float *__restrict__ theta = nullptr) {
   LCS_TAIL_PRIO();
   constexpr int CT = 64;                           // positions per workgroup
   static_assert(LCS_N_IDX % CT == 0 && LCS_TG == 16, "k_collapse tiles 9600 positions x 16 columns");
@@ -620,7 +620,7 @@ __global__ __launch_bounds__(256) void k_collapse(const float *__restrict__ sg, 
       pow32[o] = r.v;                                                  // what the fused peak search loads
       frq[o] = r.foi;
       if (second32) second32[o] = r.s;                                 // hypotheses split over GPUs: lcs_foe_contend compares it with the GLOBAL maximum
-      if (LIST) { if (r.v < 0.999f * zmin[slot]) continue; }
+      if (LIST) { if (r.v < 0.999f * theta[slot]) continue; }
       collapse_flag(r, (unsigned)o, fix_list, n_fix, zth);
     }
   }
@@ -1205,7 +1205,8 @@ static void xc_tie_repair(lcs_ctx *c, const Launch &L) {
 // The screened batch (L.screen, xcorr_route.h).  The correlation launch above made two digit passes, and the collapse
 // behind it listed no near-ties.  Now: flags and work list, the three-digit kernel over the flagged tiles (lcs_launch_screen_refine),
 // the collapse once more over the positions whose whole box lies in flagged tiles, and the tie repair of the near-ties among them
-// that reach the buffer's smallest threshold.  Every entry the peak search can act on then holds the bits of the unscreened batch.
+// that reach the buffer's theta (scr_theta: the lower bound of everything recordable, k_screen_flag).  Every entry the peak search can
+// act on then holds the bits of the unscreened batch.
 static int xc_screen_refine(lcs_ctx *c, const Launch &L) {
   const XcGeom &geo = L.geo;
   if (int rc = lcs_launch_screen_refine(c, L)) return rc;
@@ -1213,10 +1214,10 @@ static int xc_screen_refine(lcs_ctx *c, const Launch &L) {
   const dim3 grid((LCS_N_IDX / 64) * L.n_buf), block(256);
   if (geo.ds == 2)
     hipLaunchKernelGGL((k_collapse<2, false, true>), grid, block, 0, c->stream, c->single, nullptr, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, nullptr, nullptr, geo, L.n_buf,
-                       c->xcb.i8.scr_tile, c->xcb.i8.scr_zmin);
+                       c->xcb.i8.scr_tile, c->xcb.i8.scr_theta);
   else
     hipLaunchKernelGGL((k_collapse<-1, false, true>), grid, block, 0, c->stream, c->single, nullptr, c->pow_, pow32, c->frq, c->fix_list, c->n_fix, nullptr, nullptr, geo, L.n_buf,
-                       c->xcb.i8.scr_tile, c->xcb.i8.scr_zmin);
+                       c->xcb.i8.scr_tile, c->xcb.i8.scr_theta);
   return LCS_OK;
 }
 

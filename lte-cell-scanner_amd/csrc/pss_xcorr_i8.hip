@@ -387,26 +387,38 @@ __global__ __launch_bounds__(256, 2) void k_xcorr_i8x3(const uint16_t *__restric
 }
 
 // ---------------------------------------------------------------- the screen of a batch: which tiles the three-digit kernel redoes
-// One workgroup per buffer, behind the collapse of the screened array.  Zmin = the smallest Z_th1 of the buffer's 9600 lags;
-// T = lcs_screen_threshold(Zmin) with the buffer's largest column scale (screen_bound.h): a (PSS, lag) whose screened collapsed
-// power is below T has an exact collapsed power below Zmin <= every threshold and can neither be recorded nor stop the peak search
-// differently.  Every other one -- "hot" -- must come out with the exact path's bits: its collapse reads `single` at
-// the lags idx - ds .. idx + ds (circular), the tie repair and the peak search's refinement the same ones, so the lag tiles of idx - ds,
-// idx and idx + ds are flagged.  A buffer without a usable T (a silent one: Zmin not above e^2) flags every tile.
+// One workgroup per buffer, behind the collapse of the screened array.  The rule is screen_bound.h's (lcs_screen_in_s, _decide, _hot;
+// DESIGN 3.0), with the buffer's largest column scale: S = the (PSS, lag) whose screened collapsed power reaches T(z[lag]), the
+// threshold of its OWN lag; theta = the smallest lower bound L_e(V') of an exact value over S.  An entry whose screened power is below
+// T(theta) has an exact power below theta: it cannot be recorded (every recordable entry is in S and is >= theta) and cannot stop the
+// peak search differently.  Every other one -- "hot" -- must come out with the exact path's bits: its collapse reads `single` at the
+// lags idx - ds .. idx + ds (circular), the tie repair and the peak search's refinement the same ones, so the lag tiles of idx - ds,
+// idx and idx + ds are flagged.  Every tile is flagged where the rule has nothing to stand on: a z or a V' that is not a positive finite
+// number, no usable T for the smallest threshold (a silent buffer), theta <= e^2 or T(theta) not positive.  An empty S flags nothing.
+// Three passes: z and the scales; pow32 for S and theta (a workgroup reduction); pow32 for the flags.  The second pass asks the
+// double-precision rule only where V' reaches 0.999 T(Zmin) -- T increases with z, so no member of S lies below that (the 0.1 % is for
+// the rounding of T itself).
 // state: [0] work items, [1] tiles flagged, [2] buffers that flagged everything, [3] last (three-wave) tiles among the flagged.
 __global__ __launch_bounds__(256) void k_screen_flag(const float *__restrict__ pow32, const double *__restrict__ zth, const float *__restrict__ sc,
-                                                     XcGeom geo, float *__restrict__ zmin, int *__restrict__ state, int *__restrict__ tile_flag,
+                                                     XcGeom geo, float *__restrict__ theta_out, int *__restrict__ state, int *__restrict__ tile_flag,
                                                      unsigned *__restrict__ items) {
   LCS_TAIL_PRIO();
   const int slot = blockIdx.x, tid = threadIdx.x;
-  __shared__ double s_z[4];
+  __shared__ double s_z[4], s_l[4];
   __shared__ float s_sc[4];
-  __shared__ int s_bad[4];
+  __shared__ int s_bad[4], s_badv[4];
   __shared__ int s_flag[I8_TILES];
   const double *z = zth + (size_t)slot * LCS_N_IDX;
   double zm = INFINITY;
   int bad = 0;
-  for (int i = tid; i < LCS_N_IDX; i += 256) { const double v = z[i]; bad |= !(v > 0.0); zm = fmin(zm, v); }
+  // (both arrays are read 16 bytes per lane: the kernel's time is the latency of its dependent loads -- 113 per thread and pass over
+  // pow32 one float at a time, 29 so)
+  static_assert(LCS_N_IDX % 4 == 0, "a float4 of pow32 lies within one PSS; a double2 of zth within the buffer");
+  for (int i = tid; i < LCS_N_IDX / 2; i += 256) {
+    const double2 v = reinterpret_cast<const double2 *>(z)[i];
+    bad |= !(v.x > 0.0 && v.x < INFINITY) | !(v.y > 0.0 && v.y < INFINITY);
+    zm = fmin(zm, fmin(v.x, v.y));
+  }
   float sm = 0.f;
   for (int i = tid; i < geo.G * LCS_TG; i += 256) sm = fmaxf(sm, sc[(size_t)slot * GM * LCS_TG + i]);
   for (int o = 32; o; o >>= 1) { zm = fmin(zm, __shfl_xor(zm, o)); sm = fmaxf(sm, __shfl_xor(sm, o)); }
@@ -417,16 +429,47 @@ __global__ __launch_bounds__(256) void k_screen_flag(const float *__restrict__ p
   zm = fmin(fmin(s_z[0], s_z[1]), fmin(s_z[2], s_z[3]));
   sm = fmaxf(fmaxf(s_sc[0], s_sc[1]), fmaxf(s_sc[2], s_sc[3]));
   bad = s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3];
-  const double T = bad ? -1.0 : lcs_screen_threshold(geo.n_comb, geo.ds, (double)sm, zm);
-  const bool all = !(T > 0.0);
+  const double Tmin = bad ? -1.0 : lcs_screen_threshold(geo.n_comb, geo.ds, (double)sm, zm);
   const float *pw = pow32 + (size_t)slot * 3 * LCS_N_IDX;
-  if (all) { if (tid < I8_TILES) s_flag[tid] = 1; }
-  else
-    for (int e = tid; e < 3 * LCS_N_IDX; e += 256) {
-      if ((double)pw[e] < T) continue;                  // (a NaN is hot)
-      const int idx = e % LCS_N_IDX;
-      const int lo = idx - geo.ds < 0 ? idx - geo.ds + LCS_N_IDX : idx - geo.ds, hi = idx + geo.ds >= LCS_N_IDX ? idx + geo.ds - LCS_N_IDX : idx + geo.ds;
-      s_flag[idx / I8_LAGS] = 1; s_flag[lo / I8_LAGS] = 1; s_flag[hi / I8_LAGS] = 1;
+  int mode = LCS_SCREEN_ALL;
+  float theta = 0.f;
+  double T = -1.0;
+  if (Tmin > 0.0) {                                      // (uniform)
+    const float pre = (float)(0.999 * Tmin);
+    double lm = INFINITY;
+    int badv = 0;
+    for (int q = tid; q < 3 * LCS_N_IDX / 4; q += 256) {
+      const float4 v4 = reinterpret_cast<const float4 *>(pw)[q];
+      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = vv[j];
+        badv |= !(v > 0.f && v < INFINITY);
+        if (v < pre) continue;
+        if (!lcs_screen_in_s(geo.n_comb, geo.ds, (double)sm, z[(4 * q + j) % LCS_N_IDX], (double)v)) continue;
+        lm = fmin(lm, lcs_screen_lower(geo.n_comb, geo.ds, (double)sm, (double)v));
+      }
+    }
+    for (int o = 32; o; o >>= 1) lm = fmin(lm, __shfl_xor(lm, o));
+    badv = __any(badv);
+    if ((tid & 63) == 0) { s_l[tid >> 6] = lm; s_badv[tid >> 6] = badv; }
+    __syncthreads();
+    lm = fmin(fmin(s_l[0], s_l[1]), fmin(s_l[2], s_l[3]));
+    badv = s_badv[0] | s_badv[1] | s_badv[2] | s_badv[3];
+    if (!badv) mode = lcs_screen_decide(geo.n_comb, geo.ds, (double)sm, lm, &theta, &T);
+  }
+  if (mode == LCS_SCREEN_ALL) { if (tid < I8_TILES) s_flag[tid] = 1; }
+  else if (mode == LCS_SCREEN_BY_T)
+    for (int q = tid; q < 3 * LCS_N_IDX / 4; q += 256) {
+      const float4 v4 = reinterpret_cast<const float4 *>(pw)[q];
+      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (!lcs_screen_hot(T, (double)vv[j])) continue;
+        const int idx = (4 * q + j) % LCS_N_IDX;
+        const int lo = idx - geo.ds < 0 ? idx - geo.ds + LCS_N_IDX : idx - geo.ds, hi = idx + geo.ds >= LCS_N_IDX ? idx + geo.ds - LCS_N_IDX : idx + geo.ds;
+        s_flag[idx / I8_LAGS] = 1; s_flag[lo / I8_LAGS] = 1; s_flag[hi / I8_LAGS] = 1;
+      }
     }
   __syncthreads();
   if (tid < I8_TILES) {
@@ -440,11 +483,9 @@ __global__ __launch_bounds__(256) void k_screen_flag(const float *__restrict__ p
     }
   }
   if (tid == 0) {
-    // what the second collapse lists near-ties by: rounded down, so that no entry at or above Zmin is left out
-    float zf = (float)zm;
-    if ((double)zf > zm) zf = __uint_as_float(__float_as_uint(zf) - 1u);
-    zmin[slot] = all ? 0.f : zf;
-    if (all) atomicAdd(state + 2, 1);
+    // what the second collapse lists near-ties by: theta, rounded down (0 where everything -- or nothing -- was flagged)
+    theta_out[slot] = theta;
+    if (mode == LCS_SCREEN_ALL) atomicAdd(state + 2, 1);
   }
 }
 
@@ -493,11 +534,11 @@ int lcs_launch_screen_refine(lcs_ctx *c, const Launch &L) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int rc;
     if ((rc = s.scr_state.alloc(c, 4)) || (rc = s.scr_tile.alloc(c, S * I8_TILES)) || (rc = s.scr_items.alloc(c, S * I8_TILES * (size_t)c->cap_G)) ||
-        (rc = s.scr_zmin.alloc(c, S)))
+        (rc = s.scr_theta.alloc(c, S)))
       return rc;
   }
   HIPCHK(c, hipMemsetAsync(s.scr_state, 0, 4 * sizeof(int), c->stream));
-  hipLaunchKernelGGL(k_screen_flag, dim3(L.n_buf), dim3(256), 0, c->stream, reinterpret_cast<const float *>(c->work.get()), c->zth, s.tsc, geo, s.scr_zmin, s.scr_state,
+  hipLaunchKernelGGL(k_screen_flag, dim3(L.n_buf), dim3(256), 0, c->stream, reinterpret_cast<const float *>(c->work.get()), c->zth, s.tsc, geo, s.scr_theta, s.scr_state,
                      s.scr_tile, s.scr_items);
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);

@@ -41,3 +41,48 @@ LCS_SCREEN_HD static inline double lcs_screen_threshold(int n_comb, int ds, doub
   const double T = (Z - lcs_screen_bound(e, Z)) * (1.0 - lcs_screen_slack(n_comb, ds));
   return T > 0.0 ? T : -1.0;
 }
+
+// ---------------------------------------------------------------- the theta rule: refine down to theta, not to the smallest threshold
+// The other direction of the same inequality.  |v' - v| <= 2 e sqrt(v) + e^2 gives v' <= (sqrt(v) + e)^2, so sqrt(v) >= sqrt(v') - e and
+//     v >= L_e(v') := max(sqrt(v') - e, 0)^2:
+// a LOWER bound of the exact power from the screened one.  It carries through the box filter and the maximum like B_e does: with
+// m = mean of the box's exact values and m' of their screened twins, m' <= mean (sqrt(v_i) + e)^2 = m + 2 e mean sqrt(v_i) + e^2
+// <= (sqrt(m) + e)^2 (sqrt is concave), hence m >= L_e(m'); and with the largest e of the buffer's columns (L_e decreases in e) the
+// hypothesis that holds the screened maximum V' has an exact box value >= L_e(V'), so the exact maximum V >= L_e(V') (L_e increases in v').
+// The fp32 roundings: the screened kernel's float is at most (1 + s) times its real-arithmetic value and the exact kernel's float at
+// least (1 - s) times its own, s = (4 n + 2 ds + 4) 2^-24 each (lcs_screen_slack's count); the repaired positions add the 4e-7.  A
+// relative slack does not pass through sqrt(v') - e unchanged, so it is applied on both sides of it -- to the argument and to the result,
+// lcs_screen_slack each time (1 / (1 + s) >= 1 - slack, and L_e increases in its argument).
+LCS_SCREEN_HD static inline double lcs_screen_lower(int n_comb, int ds, double sc, double vs) {
+  const double e = lcs_screen_err(sc), k = 1.0 - lcs_screen_slack(n_comb, ds);
+  const double r = sqrt(vs * k) - e;
+  return r > 0.0 ? r * r * k : 0.0;      // (a NaN gives 0: theta <= e^2, everything is flagged)
+}
+// The rule of a buffer, with its largest column scale sc.  S = the entries (PSS, lag) whose screened collapsed power V'
+// is not below T(z[lag]) -- hot against their OWN threshold; theta = the smallest L_e(V') over S, rounded down to float; an entry is hot
+// when V' is not below T(theta).  The three steps below are the text both k_screen_flag and the host tests run.
+// step 1, per entry: is it in S?  (No usable T(z): it is.)
+LCS_SCREEN_HD static inline bool lcs_screen_in_s(int n_comb, int ds, double sc, double z, double vs) {
+  return !(vs < lcs_screen_threshold(n_comb, ds, sc, z));
+}
+// step 2, per buffer: from lmin = the minimum of lcs_screen_lower over S (INFINITY: S is empty) to theta and T(theta).
+// 0: S is empty -- nothing can be recorded, nothing is flagged; 1: *T > 0 decides; 2: flag every tile (theta <= e^2 or T(theta) not positive).
+// Whoever found a z or a V' that is not a positive finite number flags every tile without asking.
+#define LCS_SCREEN_NONE 0
+#define LCS_SCREEN_BY_T 1
+#define LCS_SCREEN_ALL 2
+LCS_SCREEN_HD static inline int lcs_screen_decide(int n_comb, int ds, double sc, double lmin, float *theta, double *T) {
+  *theta = 0.f;
+  *T = -1.0;
+  if (lmin == INFINITY) return LCS_SCREEN_NONE;
+  if (!(lmin > 0.0) || !(lmin < 3.0e38)) return LCS_SCREEN_ALL;
+  float tf = (float)lmin;
+  if ((double)tf > lmin) tf = nextafterf(tf, 0.f);      // rounded DOWN: theta stays a lower bound of every exact value in S
+  if (!(tf > 0.f)) return LCS_SCREEN_ALL;
+  *T = lcs_screen_threshold(n_comb, ds, sc, (double)tf);      // -1: theta <= e^2, or T not positive
+  if (!(*T > 0.0)) return LCS_SCREEN_ALL;
+  *theta = tf;
+  return LCS_SCREEN_BY_T;
+}
+// step 3, per entry: hot -- its box is redone with three digits (a NaN is hot)
+LCS_SCREEN_HD static inline bool lcs_screen_hot(double T, double vs) { return !(vs < T); }
