@@ -378,6 +378,63 @@ typedef struct lcs_pdcch_info {
   lcs_pdcch_dec dec[LCS_PCFICH_MAX_SF][LCS_PDCCH_SLOTS][LCS_PDCCH_MAX_SIZES];
 } lcs_pdcch_info;         /* 21640 bytes */
 
+/* The blind search of the whole control region: every CCE of every downlink subframe, at every aggregation level, for the grants
+ * the cell gives to its users (lcs_pdcch_scan_wide, lcs_pdcch_scan, lcs_pdcch_scan_decodes below; a stage of its own beside the
+ * PDCCH stage, which it leaves as it is).  THE RULE (lte-cell-scanner_amd/csrc/pdcch_scan.h, host and device; everything up to the
+ * soft bit as lcs_pdcch_info's, with pdcch.h's functions):
+ *   soft bits   of quadruplets 0 .. 9 N_CCE - 1, N_CCE <= 88: 6336 per subframe at most; the first 1152 are lcs_pdcch_info's
+ *   candidates  every L in {1, 2, 4, 8} and every first CCE c with c mod L = 0 and c + L <= N_CCE, by L ascending and then c (165 at
+ *               most).  At payload size A (K = A + 16) a candidate is formed only if 4 K <= 3 * 72 L (a code rate of 3/4 at most);
+ *               otherwise it leaves a zero entry
+ *   decoding    coded bit d_b = the sum of its soft bits in ascending position (fp64).  m = max |d_b|; a value that is not finite
+ *               leaves a zero entry; m = 0 is a silent candidate: decoded, all zero, never accepted.  q_b = rint(127.0 d_b / m)
+ *               (round half to even), -127 .. 127.  From there integers only: a wrap-around Viterbi decoder with int32 path metrics
+ *               that start at 0 and are carried through three passes over the K steps; branch metric -sum_j (1 - 2 w_j) q_j;
+ *               predecessors 2 j and 2 j + 1 lead to state j + 32 b, the odd one taken only if strictly smaller; decisions kept for
+ *               the last pass; end state = the lowest state among the smallest metrics; K steps of traceback
+ *   reported    tb_ok: the traced start state equals the end state.  The K bits are re-encoded with the tail-biting code: n_obs =
+ *               the coded bits with q_b != 0, n_err = those whose sign disagrees with the re-encoded bit c_b, quality =
+ *               sum q_b (1 - 2 c_b) / sum |q_b| (integer sums, one fp64 division).  rnti_x as lcs_pdcch_info's
+ *   common      rnti_x is SI, paging or RA per rnti_mask, L in {4, 8}, c < 16: accepted (as lcs_pdcch_info's)
+ *   in space    0x003D <= rnti_x <= 0xFFF3 and the candidate lies in that RNTI's search space of the subframe (36.213 9.1.1):
+ *               Y_-1 = rnti, Y_k = 39827 Y_(k-1) mod 65537, k = g mod 10; c = L ((Y_k + m') mod floor(N_CCE / L)) for an
+ *               m' < M(L) = 6, 6, 2, 2
+ *   UE accept   in space, quality >= min_quality, and n_repeat >= min_repeat: n_repeat = the number of distinct subframes of the
+ *               call in which the same rnti_x has an in-space decode of that quality, at any size and level
+ * flags: 1 decoded, 2 accepted, 4 in space, 8 tb_ok, 16 common kind.  msg[] lists every entry that is in space with quality >=
+ * min_quality or an accepted common one, ordered by subframe, L, c and size; entries beyond LCS_PDCCH_SCAN_MAX_MSG are counted in
+ * n_dropped and not written.  sf[g]: what the subframe was read with, its candidates, the accepted common and UE entries, and the
+ * CCEs that accepted entries cover.  n_rnti counts the distinct RNTIs of accepted UE entries.  Nothing depends on the order in which
+ * workgroups run: the list is placed by ordered prefix sums. */
+#define LCS_PDCCH_SCAN_MAX_SIZES 6
+#define LCS_PDCCH_SCAN_MAX_CCE 88
+#define LCS_PDCCH_SCAN_MAX_CAND 165
+#define LCS_PDCCH_SCAN_MAX_MSG 1024
+#define LCS_PDCCH_SCAN_MIN_QUALITY 0.75   /* what the bindings pass for min_quality when the caller names none */
+typedef struct lcs_pdcch_scan_cfg {
+  int32_t phich_duration, phich_resource, phich_mi[10];   /* as lcs_pdcch_cfg's */
+  int32_t n_sizes, size[LCS_PDCCH_SCAN_MAX_SIZES];        /* payload sizes A, 8 .. 64 */
+  int32_t rnti_mask, cfi_force;           /* as lcs_pdcch_cfg's */
+  int32_t min_repeat;                     /* >= 1; 2 is the bindings' default, 1 turns the recurrence rule off */
+  int32_t reserved[2];                    /* zero */
+  double min_quality;                     /* 0 .. 1; the bindings' default is LCS_PDCCH_SCAN_MIN_QUALITY */
+} lcs_pdcch_scan_cfg;     /* 104 bytes */
+typedef struct lcs_pdcch_scan_dec {
+  uint64_t bits;                          /* the A payload bits, bit t = the t-th bit sent */
+  uint32_t rnti_x;
+  int32_t flags;
+  int16_t n_err, n_obs;
+  int32_t n_repeat;                       /* of an entry in space with quality >= min_quality, else 0 */
+  double quality;
+} lcs_pdcch_scan_dec;     /* 32 bytes */
+typedef struct lcs_pdcch_scan_msg { int16_t g; uint8_t L, cce, size_index, pad[3]; lcs_pdcch_scan_dec d; } lcs_pdcch_scan_msg;   /* 40 bytes */
+typedef struct lcs_pdcch_scan_sf { int32_t cfi, n_reg, n_cce, n_cand, n_common, n_ue; uint32_t cce_mask[3]; } lcs_pdcch_scan_sf;   /* 36 bytes */
+typedef struct lcs_pdcch_scan_info {
+  int32_t n_sf, n_read, n_accepted, n_si, n_paging, n_ra, dl_mask, n_rb, n_ports, n_ue, n_rnti, n_msg, n_dropped, n_sizes, reserved[2];
+  lcs_pdcch_scan_sf sf[LCS_PCFICH_MAX_SF];
+  lcs_pdcch_scan_msg msg[LCS_PDCCH_SCAN_MAX_MSG];
+} lcs_pdcch_scan_info;    /* 43616 bytes */
+
 /* The PDSCH behind the format 1A grants of that search space: the transport blocks of SI, paging and random-access responses
  * (lcs_pdsch_wide, lcs_pdsch, lcs_turbo_decode below; a stage of its own beside the chain).  THE RULE (lte-cell-scanner_amd/csrc/
  * pdsch.h, host and device; grid, subframes, channel values and combining as for lcs_pcfich_info, the grants as lcs_pdcch_info):
@@ -667,6 +724,23 @@ int lcs_pdcch_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uin
                    int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out);
 int lcs_pdcch(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
               int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out);
+
+/* The blind search of the whole control region (the rule: lcs_pdcch_scan_info above).  The two take lcs_pdcch_wide's and lcs_pdcch's
+ * arguments, with their conventions and refusals, and a configuration of their own (cfg == NULL is refused).  The PCFICH (unless
+ * cfi_force says the CFI), the soft bits of every CCE, one decode per (subframe, candidate, size) and the acceptance run on the
+ * device without a host round trip, in blocks of this stage's own: the records of the PCFICH, PDCCH and PDSCH stages are not
+ * touched.  Refused beyond the PDCCH's refusals, with LCS_ERR_BAD_ARG, a text and no launch: n_sizes outside 1 .. 6, a size outside
+ * 8 .. 64, min_repeat < 1, a min_quality outside 0 .. 1 or not a number, a non-zero reserved field.  The tables (the REG maps of 792
+ * quadruplets, the de-rate-matching lists of every size and level, the scrambling jumps) are built on the host once per key.
+ * lcs_pdcch_scan_decodes copies the decode table of grid subframe g of the context's last scan to out: n_cand * n_sizes entries in
+ * candidate and size order; it returns their number, or LCS_ERR_BAD_ARG before any scan, for a g outside the scan's subframes or
+ * a cap that is too small. */
+int lcs_pdcch_scan_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                        double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                        int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out);
+int lcs_pdcch_scan(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
+                   int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out);
+int lcs_pdcch_scan_decodes(lcs_ctx *ctx, int g, lcs_pdcch_scan_dec *out, int cap);
 
 /* The PDSCH of the common search space's grants (the rule: lcs_pdsch_info above).  The two take lcs_pdcch_wide's and lcs_pdcch's
  * arguments with their conventions and refusals, the stage's configuration (NULL = defaults) and, optionally, a place for the PDCCH

@@ -129,6 +129,28 @@ class Searcher {
     for (int r = 0; r < n; ++r)
       for (int c = 0; c < nc; ++c) tfg(r, c) = std::complex<double>(g[((size_t)r * nc + c) * 2], g[((size_t)r * nc + c) * 2 + 1]);
   }
+  // The blind search of every CCE of the cell's control region from the same samples, or on a grid as extract_tfg_wide gives it
+  // (lcs_pdcch_scan_wide, lcs_pdcch_scan: the rule is stated at lcs_pdcch_scan_info).  The record is 43 KB: it goes through `out`.
+  void pdcch_scan_wide(const Cell &cell, const void *d_capbuf, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed,
+                       int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_scan_cfg &cfg, lcs_pdcch_scan_info &out) {
+    check(lcs_pdcch_scan_wide(h_, &cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm, dl_mask, &cfg, &out));
+  }
+  void pdcch_scan(const Cell &cell, const cn::cmat &tfg, int n_rb, int dl_mask, const lcs_pdcch_scan_cfg &cfg, lcs_pdcch_scan_info &out) {
+    const int n = tfg.rows(), nc = tfg.cols();
+    std::vector<double> g((size_t)n * nc * 2);
+    for (int r = 0; r < n; ++r)
+      for (int c = 0; c < nc; ++c) { g[((size_t)r * nc + c) * 2] = tfg(r, c).real(); g[((size_t)r * nc + c) * 2 + 1] = tfg(r, c).imag(); }
+    if (nc != 12 * n_rb) throw error("pdcch_scan: the grid is [n_ofdm][12 n_rb]");
+    check(lcs_pdcch_scan(h_, &cell, g.data(), n, n_rb, dl_mask, &cfg, &out));
+  }
+  // every decode of grid subframe g of the last scan, n_cand x n_sizes in candidate and size order (lcs_pdcch_scan_decodes)
+  std::vector<lcs_pdcch_scan_dec> pdcch_scan_decodes(int g) {
+    std::vector<lcs_pdcch_scan_dec> v((size_t)LCS_PDCCH_SCAN_MAX_CAND * LCS_PDCCH_SCAN_MAX_SIZES);
+    const int n = lcs_pdcch_scan_decodes(h_, g, v.data(), (int)v.size());
+    if (n < 0) check(n);
+    v.resize((size_t)n);
+    return v;
+  }
   static double sinr(const lcs_meas_wide_info &m, int p = 0) { return m.noise[p] > 0 ? m.rsrp[p] / m.noise[p] : std::numeric_limits<double>::infinity(); }
   static int tdd_dl_mask(int ul_dl_config) { return lcs_tdd_dl_mask(ul_dl_config); }
   // the SINR of port p of a record: rsrp / noise, infinite where noise <= 0

@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdcchScanCfg, PdcchScanInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -551,6 +551,42 @@ class Searcher:
         self._chk(self._lib.lcs_pdcch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
+
+    def pdcch_scan_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                        cfg=None, n_cap=None):
+        """The blind search of every CCE of every downlink subframe from the same samples (lcs_pdcch_scan_wide): the grants the cell
+        gives to its users, their RNTIs and the CCEs they cover.  cfg: a capi.PdcchScanCfg (its sizes have no default: capi.dci_ue_sizes
+        names the formats' for a cell) -> PdcchScanInfo"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        if cfg is None:
+            raise ValueError("pdcch_scan_wide needs a capi.PdcchScanCfg")
+        out = capi.PdcchScanInfo()
+        self._chk(self._lib.lcs_pdcch_scan_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                                float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan_wide")
+        out.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return out
+
+    def pdcch_scan(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
+        """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex (lcs_pdcch_scan) -> PdcchScanInfo"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        if cfg is None:
+            raise ValueError("pdcch_scan needs a capi.PdcchScanCfg")
+        out = capi.PdcchScanInfo()
+        self._chk(self._lib.lcs_pdcch_scan(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan")
+        out.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return out
+
+    def pdcch_scan_decodes(self, g: int) -> list:
+        """Every decode of grid subframe g of this context's last scan (lcs_pdcch_scan_decodes): a list of capi.PdcchScanDec, n_cand x
+        n_sizes of them in candidate (capi.scan_candidates) and size order"""
+        cap = capi.PDCCH_SCAN_MAX_CAND * capi.PDCCH_SCAN_MAX_SIZES
+        buf = (capi.PdcchScanDec * cap)()
+        n = self._lib.lcs_pdcch_scan_decodes(self._h, int(g), buf, cap)
+        if n < 0:
+            self._chk(n, "lcs_pdcch_scan_decodes")
+        return [buf[i] for i in range(n)]
 
     def pdsch_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
                    cfg=None, pdsch_cfg=None, n_cap=None, want_pdcch: bool = False):

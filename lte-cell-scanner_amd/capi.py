@@ -355,6 +355,327 @@ def dci_common_sizes(n_rb: int, tdd: bool = False):
     return (td if tdd else fdd), c
 
 
+# ---------------------------------------------------------------- the blind search of every CCE (include/lcs.h: lcs_pdcch_scan_info)
+PDCCH_SCAN_MAX_SIZES, PDCCH_SCAN_MAX_CCE, PDCCH_SCAN_MAX_CAND, PDCCH_SCAN_MAX_MSG = 6, 88, 165, 1024
+PDCCH_SCAN_MIN_QUALITY = 0.75             # LCS_PDCCH_SCAN_MIN_QUALITY: tools/pdcch_scan_accuracy.py measures it
+SCAN_DECODED, SCAN_ACCEPTED, SCAN_IN_SPACE, SCAN_TB_OK, SCAN_COMMON = 1, 2, 4, 8, 16
+
+
+class PdcchScanCfg(C.Structure):
+    """lcs_pdcch_scan_cfg.  PdcchScanCfg.make(sizes, ...): up to six payload sizes A in 8 .. 64; min_quality None = the default;
+    min_repeat 1 turns the recurrence rule off; the other arguments as PdcchCfg.make's."""
+    _fields_ = [("phich_duration", C.c_int32), ("phich_resource", C.c_int32), ("phich_mi", C.c_int32 * 10), ("n_sizes", C.c_int32),
+                ("size", C.c_int32 * PDCCH_SCAN_MAX_SIZES), ("rnti_mask", C.c_int32), ("cfi_force", C.c_int32), ("min_repeat", C.c_int32),
+                ("reserved", C.c_int32 * 2), ("min_quality", C.c_double)]
+
+    @classmethod
+    def make(cls, sizes, min_quality=None, min_repeat=2, phich_duration=0, phich_resource=0, phich_mi=None, rnti_mask=0, cfi_force=0) -> "PdcchScanCfg":
+        sizes = [int(a) for a in sizes]
+        if not 1 <= len(sizes) <= PDCCH_SCAN_MAX_SIZES:
+            raise ValueError("PdcchScanCfg: one to six payload sizes")
+        o = cls()
+        o.phich_duration, o.phich_resource, o.rnti_mask, o.cfi_force, o.n_sizes = int(phich_duration), int(phich_resource), int(rnti_mask), int(cfi_force), len(sizes)
+        o.min_repeat, o.min_quality = int(min_repeat), PDCCH_SCAN_MIN_QUALITY if min_quality is None else float(min_quality)
+        for i, a in enumerate(sizes):
+            o.size[i] = a
+        for i in range(10):
+            o.phich_mi[i] = -1 if phich_mi is None else (0 if phich_mi[i] is None else int(phich_mi[i]))
+        return o
+
+
+class PdcchScanDec(C.Structure):
+    """lcs_pdcch_scan_dec: flags 1 decoded, 2 accepted, 4 in space, 8 tb_ok, 16 common kind"""
+    _fields_ = [("bits", C.c_uint64), ("rnti_x", C.c_uint32), ("flags", C.c_int32), ("n_err", C.c_int16), ("n_obs", C.c_int16), ("n_repeat", C.c_int32),
+                ("quality", C.c_double)]
+
+
+class PdcchScanMsg(C.Structure):
+    _fields_ = [("g", C.c_int16), ("L", C.c_uint8), ("cce", C.c_uint8), ("size_index", C.c_uint8), ("pad", C.c_uint8 * 3), ("d", PdcchScanDec)]
+
+
+class PdcchScanSf(C.Structure):
+    _fields_ = [("cfi", C.c_int32), ("n_reg", C.c_int32), ("n_cce", C.c_int32), ("n_cand", C.c_int32), ("n_common", C.c_int32), ("n_ue", C.c_int32),
+                ("cce_mask", C.c_uint32 * 3)]
+
+
+def scan_candidates(n_cce: int) -> list:
+    """[(L, first CCE)] of a subframe with n_cce CCEs in the record's order: by L ascending, then by CCE"""
+    return [(L, c) for L in (1, 2, 4, 8) for c in range(0, n_cce - L + 1, L)]
+
+
+def ue_search_space(rnti: int, sf: int, n_cce: int, L: int) -> list:
+    """The first CCEs of the candidates of the UE-specific search space of `rnti` in subframe sf at level L (36.213 9.1.1), in the
+    order m' = 0 .. M(L) - 1 (duplicates where floor(n_cce / L) < M(L); none where it is 0)"""
+    y = int(rnti)
+    for _ in range(int(sf) % 10 + 1):
+        y = (39827 * y) % 65537
+    n = int(n_cce) // int(L)
+    return [int(L) * ((y + m) % n) for m in range(6 if L <= 2 else 2)] if n else []
+
+
+class PdcchScanInfo(C.Structure):
+    """lcs_pdcch_scan_info: what the blind search of every CCE found (include/lcs.h: lcs_pdcch_scan_wide, lcs_pdcch_scan).  sf[g]: cfi,
+    n_reg, n_cce, n_cand, the accepted common and UE entries and the CCEs they cover; msg[: n_msg]: every entry in space with
+    sufficient quality and every accepted common one.  sizes: the payload sizes of the call."""
+    _fields_ = [("n_sf", C.c_int32), ("n_read", C.c_int32), ("n_accepted", C.c_int32), ("n_si", C.c_int32), ("n_paging", C.c_int32), ("n_ra", C.c_int32),
+                ("dl_mask", C.c_int32), ("n_rb", C.c_int32), ("n_ports", C.c_int32), ("n_ue", C.c_int32), ("n_rnti", C.c_int32), ("n_msg", C.c_int32),
+                ("n_dropped", C.c_int32), ("n_sizes", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("sf", PdcchScanSf * PCFICH_MAX_SF), ("msg", PdcchScanMsg * PDCCH_SCAN_MAX_MSG)]
+    sizes = ()
+
+    def copy(self) -> "PdcchScanInfo":
+        o = PdcchScanInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(PdcchScanInfo))
+        o.sizes = tuple(self.sizes)
+        return o
+
+    def _n(self) -> int:
+        return min(max(int(self.n_sf), 0), PCFICH_MAX_SF)
+
+    @property
+    def cfi(self):
+        import numpy as np
+        return np.array([self.sf[g].cfi for g in range(self._n())], np.int32)
+
+    @property
+    def n_cce(self):
+        import numpy as np
+        return np.array([self.sf[g].n_cce for g in range(self._n())], np.int32)
+
+    def listed(self) -> list:
+        """every entry of msg[: n_msg] as a dict, in the record's order"""
+        out = []
+        for i in range(min(max(int(self.n_msg), 0), PDCCH_SCAN_MAX_MSG)):
+            m, d = self.msg[i], self.msg[i].d
+            kind = "si" if d.rnti_x == 0xFFFF else "paging" if d.rnti_x == 0xFFFE else "ra" if d.flags & SCAN_COMMON else "ue"
+            out.append(dict(subframe=int(m.g), L=int(m.L), cce=int(m.cce), size_index=int(m.size_index), kind=kind, rnti=int(d.rnti_x),
+                            size=(self.sizes[m.size_index] if m.size_index < len(self.sizes) else None), bits=int(d.bits), quality=float(d.quality),
+                            flags=int(d.flags), n_repeat=int(d.n_repeat), n_err=int(d.n_err), n_obs=int(d.n_obs)))
+        return out
+
+    def messages(self) -> list:
+        """The accepted entries.  A DCI that is read again at a lower level or at an overlapping start -- the same subframe, RNTI, size
+        and bits, on CCEs that overlap -- is listed once, at the largest accepted L (the better quality among equals)."""
+        acc = sorted((m for m in self.listed() if m["flags"] & SCAN_ACCEPTED), key=lambda m: (-m["L"], -m["quality"]))
+        kept = []
+        for m in acc:
+            same = lambda k: (k["subframe"], k["rnti"], k["size_index"], k["bits"]) == (m["subframe"], m["rnti"], m["size_index"], m["bits"])
+            if not any(same(k) and k["cce"] < m["cce"] + m["L"] and m["cce"] < k["cce"] + k["L"] for k in kept):
+                kept.append(m)
+        return sorted(kept, key=lambda m: (m["subframe"], m["cce"], m["L"], m["size_index"]))
+
+    def rntis(self) -> dict:
+        """{C-RNTI: number of its grants} over messages()"""
+        out = {}
+        for m in self.messages():
+            if m["kind"] == "ue":
+                out[m["rnti"]] = out.get(m["rnti"], 0) + 1
+        return out
+
+    def load(self, n_rb: int, tdd: bool = False) -> list:
+        """Per subframe read: dict(subframe, n_cce, cce_used, dl_grants, ul_grants, dl_prb, ul_prb, rntis) from the UE grants of
+        messages(): format 0 and 1A by their first bit, formats 1, 1B/1D, 2A and 2 by their size (dci_ue_sizes with the record's port
+        count); a grant whose size is none of them, or whose allocation does not read, counts as a grant without PRBs."""
+        ports = int(self.n_ports)
+        by_size = {}
+        for name, a in dci_ue_sizes(n_rb, ports, tdd).items():
+            by_size.setdefault(a, name)
+        out = []
+        msgs = self.messages()
+        for g in range(self._n()):
+            s = self.sf[g]
+            if not s.cfi:
+                continue
+            row = dict(subframe=g, n_cce=int(s.n_cce), cce_used=sum(bin(w).count("1") for w in s.cce_mask), dl_grants=0, ul_grants=0, dl_prb=0, ul_prb=0, rntis=set())
+            for m in msgs:
+                if m["subframe"] != g or m["kind"] != "ue":
+                    continue
+                row["rntis"].add(m["rnti"])
+                name = by_size.get(m["size"])
+                f = None
+                if name == "0/1A":
+                    f = dci_0_fields(m["bits"], n_rb, tdd) if not m["bits"] & 1 else dci_1a_fields(m["bits"], n_rb, tdd)
+                    if f is not None and "n_rb_alloc" in f and "prbs" not in f:
+                        f = dict(f, prbs=list(range(f["rb_start"], f["rb_start"] + f["n_rb_alloc"])))
+                elif name == "1":
+                    f = dci_1_fields(m["bits"], n_rb, tdd)
+                elif name in ("2A", "2"):
+                    f = dci_2x_fields(m["bits"], n_rb, ports, name, tdd)
+                up = name == "0/1A" and not m["bits"] & 1
+                row["ul_grants" if up else "dl_grants"] += 1
+                if f is not None and f.get("prbs") is not None:
+                    row["ul_prb" if up else "dl_prb"] += len(f["prbs"])
+            row["rntis"] = sorted(row["rntis"])
+            out.append(row)
+        return out
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return (f"PdcchScanInfo(n_sf={self.n_sf}, n_read={self.n_read}, n_accepted={self.n_accepted}, n_ue={self.n_ue}, n_rnti={self.n_rnti}, "
+                f"n_msg={self.n_msg}, n_dropped={self.n_dropped})")
+
+
+assert C.sizeof(PdcchScanCfg) == 104 and C.sizeof(PdcchScanDec) == 32 and C.sizeof(PdcchScanMsg) == 40 and C.sizeof(PdcchScanSf) == 36 and C.sizeof(PdcchScanInfo) == 43616
+
+# Payload sizes of the DCI formats of the UE-specific search space, Release 8/9, no carrier indicator (36.212 5.3.3.1).  THE TABLE IS
+# FROM MEMORY OF THE STANDARD; dci_ue_size_derived recomputes it from the field widths, and tests/test_pdcch_scan_host.py holds the
+# two together.  With RIV = ceil(log2(n_rb (n_rb + 1) / 2)), RBG size P = 1, 2, 2, 3, 4, 4 for 6 .. 100 resource blocks, the bitmap
+# B = ceil(n_rb / P), the header H = 1 where n_rb > 10, and T = 3 more bits in TDD (a 4-bit HARQ number and a 2-bit DAI):
+#   0      flag 1 + hopping 1 + RIV + MCS/RV 5 + NDI 1 + TPC 2 + cyclic shift 3 + CQI request 1 (+ UL index / DAI 2 in TDD), padded to 1A
+#   1A     flag 1 + localized/distributed 1 + RIV + MCS 5 + HARQ 3 + NDI 1 + RV 2 + TPC 2 + T (dci_1a_size)
+#   1      H + B + MCS 5 + HARQ 3 + NDI 1 + RV 2 + TPC 2 + T
+#   1B/1D  localized/distributed 1 + RIV + MCS 5 + HARQ 3 + NDI 1 + RV 2 + TPC 2 + TPMI 2 (2 ports) or 4
+#          (4 ports) + PMI confirmation (1B) or power offset (1D) 1 + T
+#   2A     H + B + TPC 2 + HARQ 3 + swap flag 1 + 2 x (MCS 5 + NDI 1 + RV 2) + precoding 0 (2 ports) or 2 (4 ports) + T
+#   2      the same with precoding 3 (2 ports) or 6 (4 ports)
+# Padding: a format other than 0/1A whose size equals 0/1A's gets one zero; then zeros are appended while the size is one of the
+# ambiguous sizes 12, 14, 16, 20, 24, 26, 32, 40, 44, 56 (and, for format 1, while it equals 0/1A's).
+_RBG_P = {6: 1, 15: 2, 25: 2, 50: 3, 75: 4, 100: 4}
+_DCI_UE_SIZES = {      # (n_rb, ports) -> sizes of formats 1, 1B/1D, 2A, 2 in FDD (0/1A: dci_1a_size)
+    (6, 1): (19, None, None, None), (6, 2): (19, 22, 28, 31), (6, 4): (19, 25, 30, 34),
+    (15, 1): (23, None, None, None), (15, 2): (23, 25, 31, 34), (15, 4): (23, 27, 33, 37),
+    (25, 1): (27, None, None, None), (25, 2): (27, 27, 36, 39), (25, 4): (27, 28, 38, 42),
+    (50, 1): (31, None, None, None), (50, 2): (31, 28, 41, 43), (50, 4): (31, 30, 42, 46),
+    (75, 1): (33, None, None, None), (75, 2): (33, 29, 42, 45), (75, 4): (33, 31, 45, 48),
+    (100, 1): (39, None, None, None), (100, 2): (39, 30, 48, 51), (100, 4): (39, 33, 50, 54),
+}
+_DCI_UE_NAMES = ("1", "1B/1D", "2A", "2")
+
+
+def dci_ue_size_derived(fmt: str, n_rb: int, ports: int, tdd: bool = False):
+    """the size of a format of the UE-specific search space from its field widths and the padding rules (None: the format needs
+    more ports)"""
+    n_rb, ports, t = int(n_rb), int(ports), 3 if tdd else 0
+    riv = (n_rb * (n_rb + 1) // 2 - 1).bit_length()
+    a01 = dci_1a_size(n_rb, tdd)
+    if fmt == "0/1A":
+        return a01
+    ra = (1 if n_rb > 10 else 0) + -(-n_rb // _RBG_P[n_rb])
+    if fmt == "1":
+        a = ra + 13 + t
+    elif ports < 2:
+        return None
+    elif fmt == "1B/1D":
+        a = 14 + riv + (2 if ports == 2 else 4) + 1 + t
+    elif fmt == "2A":
+        a = ra + 22 + (0 if ports == 2 else 2) + t
+    elif fmt == "2":
+        a = ra + 22 + (3 if ports == 2 else 6) + t
+    else:
+        raise ValueError("no such format")
+    if a == a01:
+        a += 1
+    while a in _DCI_AMBIGUOUS or (fmt == "1" and a == a01):
+        a += 1
+    return a
+
+
+def dci_ue_sizes(n_rb: int, ports: int, tdd: bool = False) -> dict:
+    """{"0/1A", "1", "1B/1D", "2A", "2"} -> payload size for an n_rb cell with 1, 2 or 4 ports (the formats that need two ports are
+    left out with one).  FDD from the table; TDD from the derivation (the table holds FDD alone)."""
+    ports = 4 if int(ports) == 4 else 2 if int(ports) == 2 else 1
+    out = {"0/1A": dci_1a_size(int(n_rb), tdd)}
+    for name, a in zip(_DCI_UE_NAMES, _DCI_UE_SIZES[(int(n_rb), ports)]):
+        if a is not None:
+            out[name] = dci_ue_size_derived(name, n_rb, ports, True) if tdd else a
+    return out
+
+
+def _dci_take(bits, size):
+    if isinstance(bits, int):
+        bits = [(bits >> t) & 1 for t in range(size)]
+    bits = [int(b) for b in bits]
+    pos = [0]
+
+    def take(n):
+        v = 0
+        for _ in range(n):
+            v = (v << 1) | bits[pos[0]]
+            pos[0] += 1
+        return v
+    return take
+
+
+def _riv_decode(riv, n_rb):
+    """-> (rb_start, n_rb_alloc) or None for a value no allocation gives"""
+    l1, s = riv // n_rb + 1, riv % n_rb
+    if s + l1 > n_rb:
+        l1, s = n_rb + 2 - l1, n_rb - 1 - s
+    return (s, l1) if 1 <= l1 <= n_rb - s and riv < n_rb * (n_rb + 1) // 2 else None
+
+
+def ra_type01_prbs(header: int, field: int, n_rb: int) -> list:
+    """The PRB set of a type 0 (header 0: one bit per RBG, the first RBG on the field's MSB) or type 1 (header 1: subset, shift, one
+    bit per PRB of the subset) allocation of ceil(n_rb / P) bits (36.213 7.1.6.1, 7.1.6.2)"""
+    n_rb = int(n_rb)
+    P = _RBG_P[n_rb]
+    nb = -(-n_rb // P)
+    bit = lambda i, width: (field >> (width - 1 - i)) & 1
+    if not header:
+        return [r for i in range(nb) if bit(i, nb) for r in range(P * i, min(P * i + P, n_rb))]
+    lp = (P - 1).bit_length()
+    n1 = nb - lp - 1
+    p, shift = field >> (nb - lp), bit(lp, nb)
+    if p >= P:
+        return None
+    q = (n_rb - 1) // P
+    n_sub = (n_rb - 1) // (P * P) * P + (P if p < q % P else (n_rb - 1) % P + 1 if p == q % P else 0)
+    delta = n_sub - n1 if shift else 0
+    out = []
+    for i in range(n1):
+        if bit(lp + 1 + i, nb):
+            v = (i + delta) // P * P * P + p * P + (i + delta) % P
+            if v < n_rb:
+                out.append(v)
+    return out
+
+
+def dci_0_fields(bits, n_rb: int, tdd: bool = False):
+    """The fields of a format 0 payload (36.212 5.3.3.1.1; the first bit is 0, format 1A's is 1) -> dict with rb_start, n_rb_alloc and
+    prbs (None for a RIV that no allocation gives), or None when the first bit says 1A"""
+    n_rb = int(n_rb)
+    take = _dci_take(bits, dci_1a_size(n_rb, tdd))
+    if take(1):
+        return None
+    out = dict(format="0", hopping=take(1))
+    riv = take((n_rb * (n_rb + 1) // 2 - 1).bit_length())
+    out.update(mcs=take(5), ndi=take(1), tpc=take(2), cyclic_shift=take(3))
+    if tdd:
+        out["ul_index_dai"] = take(2)
+    out["cqi_request"] = take(1)
+    al = _riv_decode(riv, n_rb)
+    out.update(riv=riv, rb_start=None if al is None else al[0], n_rb_alloc=None if al is None else al[1], prbs=None if al is None else list(range(al[0], al[0] + al[1])))
+    return out
+
+
+def dci_1_fields(bits, n_rb: int, tdd: bool = False) -> dict:
+    """The fields of a format 1 payload (36.212 5.3.3.1.2): type 0 or type 1 resource allocation -> prbs"""
+    n_rb = int(n_rb)
+    take = _dci_take(bits, dci_ue_size_derived("1", n_rb, 1, tdd))
+    header = take(1) if n_rb > 10 else 0
+    field = take(-(-n_rb // _RBG_P[n_rb]))
+    out = dict(format="1", ra_type=header, ra=field, mcs=take(5), harq=take(4 if tdd else 3), ndi=take(1), rv=take(2), tpc=take(2))
+    if tdd:
+        out["dai"] = take(2)
+    out["prbs"] = ra_type01_prbs(header, field, n_rb)
+    return out
+
+
+def dci_2x_fields(bits, n_rb: int, ports: int, fmt: str = "2A", tdd: bool = False) -> dict:
+    """The fields of a format 2 or 2A payload (36.212 5.3.3.1.5, 5.3.3.1.5A) with 2 or 4 ports -> prbs, two transport blocks"""
+    n_rb, ports = int(n_rb), int(ports)
+    take = _dci_take(bits, dci_ue_size_derived(fmt, n_rb, ports, tdd))
+    header = take(1) if n_rb > 10 else 0
+    field = take(-(-n_rb // _RBG_P[n_rb]))
+    out = dict(format=fmt, ra_type=header, ra=field, tpc=take(2))
+    if tdd:
+        out["dai"] = take(2)
+    out.update(harq=take(4 if tdd else 3), swap=take(1))
+    out["tb"] = [dict(mcs=take(5), ndi=take(1), rv=take(2)) for _ in range(2)]
+    out["precoding"] = take({("2A", 2): 0, ("2A", 4): 2, ("2", 2): 3, ("2", 4): 6}[(fmt, ports)])
+    out["prbs"] = ra_type01_prbs(header, field, n_rb)
+    return out
+
+
 # 36.211 table 6.9-1: m_i per uplink-downlink configuration and subframe; None = an uplink subframe.  Only a default the caller may
 # override (lcs_pdcch_cfg.phich_mi): a wrong entry here is a wrong default, not a wrong kernel.
 _TDD_PHICH_MI = [[2, 1, None, None, None, 2, 1, None, None, None], [0, 1, None, None, 1, 0, 1, None, None, 1], [0, 0, None, 1, 0, 0, 0, None, 1, 0],
@@ -698,7 +1019,7 @@ EXPORTS = [
     "lcs_set_batch_screen", "lcs_get_batch_screen", "lcs_last_screen_stats", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdcch_scan_wide", "lcs_pdcch_scan", "lcs_pdcch_scan_decodes", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
     "lcs_set_pdsch_alloc", "lcs_pdsch_last_alloc",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
@@ -784,6 +1105,11 @@ def _declare(L: C.CDLL) -> C.CDLL:
         L.lcs_pdcch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
         L.lcs_pdcch.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchCfg), C.POINTER(PdcchInfo)]
+    if hasattr(L, "lcs_pdcch_scan_wide"):      # (likewise)
+        L.lcs_pdcch_scan_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(PdcchScanCfg), C.POINTER(PdcchScanInfo)]
+        L.lcs_pdcch_scan.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchScanCfg), C.POINTER(PdcchScanInfo)]
+        L.lcs_pdcch_scan_decodes.argtypes = [vp, C.c_int, C.POINTER(PdcchScanDec), C.c_int]
     if hasattr(L, "lcs_pdsch_wide"):      # (likewise)
         L.lcs_pdsch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(PdcchCfg), C.POINTER(PdschCfg), C.POINTER(PdschInfo), C.POINTER(PdcchInfo)]

@@ -15,6 +15,7 @@
 #include "cell_meas_wide.h"
 #include "pcfich.h"
 #include "pdcch.h"
+#include "pdcch_scan.h"
 #include "pdsch.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
@@ -1337,6 +1338,112 @@ int lcs_pdcch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, i
   if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
   if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
   return pdcch_finish(c, out);
+}
+
+// ---- the blind search of every CCE on that grid (pdcch_scan.hip, pdcch_scan.h): the same blocks and the same isolation
+namespace {
+// the PDCCH's refusals on the fields the two configurations share, then this stage's own
+int pdcch_scan_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_cfg *shared, PdcchPlan *pp, PdcchScanPlan *p) {
+  if (!cfg) return wide_refused(c, who, "a null pointer");
+  std::memset(shared, 0, sizeof(*shared));
+  shared->phich_duration = cfg->phich_duration; shared->phich_resource = cfg->phich_resource;
+  for (int i = 0; i < 10; ++i) shared->phich_mi[i] = cfg->phich_mi[i];
+  shared->n_sizes = 1; shared->size[0] = 8;                  // the sizes are this stage's own, checked below
+  shared->rnti_mask = cfg->rnti_mask; shared->cfi_force = cfg->cfi_force;
+  int rc;
+  if ((rc = pdcch_resolve(c, who, cell, n_rb, shared, pp))) return rc;
+  if (cfg->n_sizes < 1 || cfg->n_sizes > LCS_PDCCH_SCAN_MAX_SIZES) return wide_refused(c, who, "n_sizes is outside 1 .. 6");
+  for (int i = 0; i < LCS_PDCCH_SCAN_MAX_SIZES; ++i) p->size[i] = 0;
+  for (int i = 0; i < cfg->n_sizes; ++i) {
+    if (cfg->size[i] < 8 || cfg->size[i] > 64) return wide_refused(c, who, "a payload size is outside 8 .. 64");
+    p->size[i] = cfg->size[i];
+  }
+  if (cfg->min_repeat < 1) return wide_refused(c, who, "min_repeat is below 1");
+  if (!(cfg->min_quality >= 0.0 && cfg->min_quality <= 1.0)) return wide_refused(c, who, "min_quality is outside 0 .. 1");
+  if (cfg->reserved[0] || cfg->reserved[1]) return wide_refused(c, who, "a reserved field is not zero");
+  p->phich_duration = pp->phich_duration; p->phich_resource = pp->phich_resource;
+  for (int i = 0; i < 10; ++i) p->mi[i] = pp->mi[i];
+  p->n_sizes = cfg->n_sizes; p->rnti_mask = pp->rnti_mask; p->cfi_force = pp->cfi_force;
+  p->min_repeat = cfg->min_repeat; p->min_quality = cfg->min_quality;
+  return LCS_OK;
+}
+int pdcch_scan_finish(lcs_ctx *c, int n_sf, int n_sizes, lcs_pdcch_scan_info *out) {
+  lcs_ctx::PdcchScan &p = c->pdcch_scan;
+  HIPCHK(c, hipMemcpyAsync(out, p.rec, sizeof(lcs_pdcch_scan_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int g = 0; g < n_sf; ++g) p.last_n_cand[g] = out->sf[g].n_cand;
+  p.last_n_sizes = n_sizes;
+  p.last_n_sf = n_sf;
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_pdcch_scan_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                        int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdcch_scan_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  lcs_pdcch_cfg shared;
+  PdcchPlan pp;
+  PdcchScanPlan plan;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_scan_resolve(c, who, cell, n_rb, cfg, &shared, &pp, &plan))) return rc;
+  int rows4[4 * PCF_MAX_SF];
+  std::vector<int> list;
+  const int n_sf = pdcch_plan(cell, &shared, pp, n_ofdm, n_rb, dl_mask, rows4, &list);
+  std::vector<double> ideal(list.size());
+  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
+  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_pdcch_scan(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
+  return pdcch_scan_finish(c, n_sf, plan.n_sizes, out);
+}
+
+int lcs_pdcch_scan(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdcch_scan";
+  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  int rc;
+  lcs_pdcch_cfg shared;
+  PdcchPlan pp;
+  PdcchScanPlan plan;
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pdcch_scan_resolve(c, who, cell, n_rb, cfg, &shared, &pp, &plan))) return rc;
+  int rows4[4 * PCF_MAX_SF];
+  const int n_sf = pdcch_plan(cell, &shared, pp, n_ofdm, n_rb, dl_mask, rows4, nullptr);
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
+  if ((rc = lcs_launch_pdcch_scan(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
+  return pdcch_scan_finish(c, n_sf, plan.n_sizes, out);
+}
+
+int lcs_pdcch_scan_decodes(lcs_ctx *c, int g, lcs_pdcch_scan_dec *out, int cap) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_pdcch_scan_decodes";
+  lcs_ctx::PdcchScan &p = c->pdcch_scan;
+  if (!out) return wide_refused(c, who, "a null pointer");
+  if (p.last_n_sf == 0) return wide_refused(c, who, "the context has run no scan");
+  if (g < 0 || g >= p.last_n_sf) return wide_refused(c, who, "g is outside the subframes of the last scan");
+  const int n_cand = p.last_n_cand[g], n = n_cand * p.last_n_sizes;
+  if (cap < n) return wide_refused(c, who, "cap is below n_cand * n_sizes of that subframe");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  p.h_tab.resize((size_t)PSC_MAX_CAND * PSC_SIZES);
+  HIPCHK(c, hipMemcpyAsync(p.h_tab.data(), p.tab.get() + (size_t)g * PSC_MAX_CAND * PSC_SIZES, sizeof(lcs_pdcch_scan_dec) * (size_t)n_cand * PSC_SIZES,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n_cand; ++i)
+    for (int si = 0; si < p.last_n_sizes; ++si) out[i * p.last_n_sizes + si] = p.h_tab[(size_t)i * PSC_SIZES + si];
+  return n;
 }
 
 // ---- the PDSCH behind the grants of that search space (pdsch.hip, pdsch.h): the same blocks and the same isolation

@@ -429,6 +429,30 @@ struct lcs_ctx : lcs_ctx_queues {
     int key[9] = {};                // n_rb, ports, cp_type, id, phich_duration, phich_resource, n_sizes, size[2] of the tables; n_rb 0: none
     int jump_rb = 0;
   } pdcch;
+  // the blind search of every CCE on that grid (pdcch_scan.hip: lcs_pdcch_scan_wide, lcs_pdcch_scan), allocated by the first call of
+  // that stage.  The tables are built on the host (pdcch_scan.h) when the key changes, not per call.
+  struct PdcchScan {
+    DevBuf<int> map;                // [3 m_i][3 cfi] PscMap: n_reg, n_cce, re[3168]
+    DevBuf<int16_t> derm;           // [6 sizes][4 levels][240][8]: the de-rate-matching lists
+    DevBuf<uint32_t> jump;          // [32] to the call's reference sequence, then psc_build_jump's [544]
+    DevBuf<int> sf;                 // as Pdcch::sf
+    DevBuf<double> llr;             // [LCS_PCFICH_MAX_SF][6336]
+    DevBuf<lcs_pdcch_scan_dec> tab; // [LCS_PCFICH_MAX_SF][165][6]: every decode of the last scan
+    DevBuf<lcs_pdcch_scan_msg> stage;   // [LCS_PCFICH_MAX_SF][990]: every subframe's listed entries in order, before the cap
+    DevBuf<int> sfc;                // [LCS_PCFICH_MAX_SF][8]: every subframe's counts for the head
+    DevBuf<unsigned char> pres;     // [65536][LCS_PCFICH_MAX_SF]: the subframes in which an RNTI has an in-space decode of sufficient quality
+    DevBuf<lcs_pdcch_scan_info> rec;   // [1]
+    DevBuf<lcs_pcfich_info> pcf_rec;   // [1]: the PCFICH's decisions on the call's rows, a record of this stage's own
+    std::vector<int> h_map;         // the host blocks they are uploaded from
+    std::vector<int16_t> h_derm;
+    std::vector<lcs_pdcch_scan_dec> h_tab;   // one subframe of tab, for lcs_pdcch_scan_decodes
+    uint32_t h_jump[32 + 544] = {};
+    int h_sf[6 * LCS_PCFICH_MAX_SF + 10] = {};
+    int key[13] = {};               // n_rb, ports, cp_type, id, phich_duration, phich_resource, n_sizes, size[6] of the tables; n_rb 0: none
+    int jump_rb = 0;
+    int cand_cap = 0;               // the candidates of the largest N_CCE among the key's maps
+    int last_n_sf = 0, last_n_sizes = 0, last_n_cand[LCS_PCFICH_MAX_SF] = {};   // the last scan, for lcs_pdcch_scan_decodes; n_sf 0: none
+  } pdcch_scan;
   // the PDSCH behind that search space's grants (pdsch.hip: lcs_pdsch_wide, lcs_pdsch, lcs_turbo_decode), allocated by the first call
   // of that stage.  The tables are built on the host (pdsch.h) once, a forced grant's when its (K, F) changes; not per call.
   struct Pdsch {
@@ -683,6 +707,10 @@ struct PdcchPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[2],
 int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
 // the same into the blocks p (the PDSCH stage keeps a set of its own for the grants it follows) -> p.rec
 int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
+// pdcch_scan.hip
+struct PdcchScanPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[LCS_PDCCH_SCAN_MAX_SIZES], rnti_mask, cfi_force, min_repeat; double min_quality; };
+// rows4 as lcs_launch_pdcch's -> c->pdcch_scan.rec, c->pdcch_scan.tab
+int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchScanPlan &plan);
 // pdsch.hip
 struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; int alloc_flags, sfn0, si_window; };
 // the PCFICH and PDCCH of rows4 into c->pdsch.pdc, then the grants' blocks -> c->pdsch.rec.  sfrow [n_sf]: the row of c->meas_wide.grid

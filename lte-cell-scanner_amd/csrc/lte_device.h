@@ -604,14 +604,16 @@ __host__ __device__ __forceinline__ int vit_lane_desc(int s) {
   return (n0 ? ((7 - w0) & 3) : (w0 & 3)) | ((n1 ? ((7 - w1) & 3) : (w1 & 3)) << 2) | (n0 << 4) | (n1 << 5) | (b << 6);
 }
 // the survivor this lane forms from its own metric and its partner's; *take1 = the decision (predecessor 2j + 1 only when STRICTLY better)
-__host__ __device__ __forceinline__ double vit_lane_step(int desc, double self, double partner, const double (&d)[4], bool *take1) {
+// (T: double here and in the PBCH / PDCCH decoders; int32 in the blind search's 8-bit decoder, pdcch_scan.h)
+template <class T>
+__host__ __device__ __forceinline__ T vit_lane_step(int desc, T self, T partner, const T (&d)[4], bool *take1) {
   const int i0 = desc & 3, i1 = (desc >> 2) & 3;
-  const double s0 = (i0 == 0) ? d[0] : (i0 == 1) ? d[1] : (i0 == 2) ? d[2] : d[3];
-  const double s1 = (i1 == 0) ? d[0] : (i1 == 1) ? d[1] : (i1 == 2) ? d[2] : d[3];
+  const T s0 = (i0 == 0) ? d[0] : (i0 == 1) ? d[1] : (i0 == 2) ? d[2] : d[3];
+  const T s1 = (i1 == 0) ? d[0] : (i1 == 1) ? d[1] : (i1 == 2) ? d[2] : d[3];
   const bool odd = (desc >> 6) & 1;                    // this lane holds old state 2j + 1
-  const double o0 = odd ? partner : self, o1 = odd ? self : partner;
-  const double m0 = o0 + (((desc >> 4) & 1) ? -s0 : s0);
-  const double m1 = o1 + (((desc >> 5) & 1) ? -s1 : s1);
+  const T o0 = odd ? partner : self, o1 = odd ? self : partner;
+  const T m0 = o0 + (((desc >> 4) & 1) ? -s0 : s0);
+  const T m1 = o1 + (((desc >> 5) & 1) ? -s1 : s1);
   *take1 = m1 < m0;
   return *take1 ? m1 : m0;
 }

@@ -31,7 +31,9 @@
 static_assert(sizeof(lcs_pdcch_cfg) == 68 && sizeof(lcs_pdcch_dec) == 24 &&
               sizeof(lcs_pdcch_info) == 40 + PCF_MAX_SF * 12 + PCF_MAX_SF * PDC_SLOTS * PDC_SIZES * 24, "include/lcs.h: lcs_pdcch_info");
 
-struct PdcMap { int n_reg, n_cce; int re[PDC_NRE]; };
+// a map of the first NQ quadruplets: the PDCCH stage reads PDC_MAX_QUAD of them, the blind search (pdcch_scan.h) every one
+template <int NQ> struct PdcMapT { int n_reg, n_cce; int re[4 * NQ]; };
+typedef PdcMapT<PDC_MAX_QUAD> PdcMap;
 
 __host__ __device__ __forceinline__ int pdc_n_ctrl(int cfi, int n_rb) { return cfi + (n_rb <= 10 ? 1 : 0); }
 __host__ __device__ __forceinline__ int pdc_n_ctrl_max(int n_rb) { return n_rb <= 10 ? 4 : 3; }
@@ -177,10 +179,11 @@ inline std::vector<PdcReg> pdc_regs_of_symbol(int l, int n_rb, int ports, int cp
 }
 // The map of (m_i, cfi).  phich_duration 1 / 2, phich_resource 1 .. 4 as lcs_cell's.  pcfich / phich / order (each may be null):
 // the REGs of the three kinds as (k' << 2 | l'), order in the PDCCH's REG order.  false: refused (the map is empty)
-inline bool pdc_build_map(int n_rb, int ports, int cp_type, int id, int phich_duration, int phich_resource, int mi, int cfi, PdcMap *m,
-                          std::vector<int> *pcfich = nullptr, std::vector<int> *phich = nullptr, std::vector<int> *order = nullptr) {
+template <int NQ>
+inline bool pdc_build_map_t(int n_rb, int ports, int cp_type, int id, int phich_duration, int phich_resource, int mi, int cfi, PdcMapT<NQ> *m,
+                            std::vector<int> *pcfich = nullptr, std::vector<int> *phich = nullptr, std::vector<int> *order = nullptr) {
   m->n_reg = m->n_cce = 0;
-  for (int i = 0; i < PDC_NRE; ++i) m->re[i] = -1;
+  for (int i = 0; i < 4 * NQ; ++i) m->re[i] = -1;
   const int n_ctrl = pdc_n_ctrl(cfi, n_rb);
   if (cfi < 1 || cfi > 3 || mi < 0 || mi > 2) return false;
   if (phich_duration == 2 && n_ctrl < 3) return false;
@@ -220,11 +223,15 @@ inline bool pdc_build_map(int n_rb, int ports, int cp_type, int id, int phich_du
   const std::vector<int> w = pdc_interleave(n);
   for (int i = 0; i < n; ++i) {
     const int q = w[(size_t)((i + id) % n)];          // REG i carries quadruplet q
-    if (q >= PDC_MAX_QUAD || q >= 9 * m->n_cce) continue;
+    if (q >= NQ || q >= 9 * m->n_cce) continue;
     const int per = pdc_regs_per_rb(regs[i].l, ports, cp_type);
     for (int j = 0; j < 4; ++j) m->re[4 * q + j] = (regs[i].l << 16) | pdc_reg_col(regs[i].k, per, j, id);
   }
   return true;
+}
+inline bool pdc_build_map(int n_rb, int ports, int cp_type, int id, int phich_duration, int phich_resource, int mi, int cfi, PdcMap *m,
+                          std::vector<int> *pcfich = nullptr, std::vector<int> *phich = nullptr, std::vector<int> *order = nullptr) {
+  return pdc_build_map_t<PDC_MAX_QUAD>(n_rb, ports, cp_type, id, phich_duration, phich_resource, mi, cfi, m, pcfich, phich, order);
 }
 // out[3 K][width]: the positions among the E rate-matched bits that carry coded bit s K + t, ascending, -1 padded (36.212 5.1.4.2:
 // three sub-block interleavers of 32 columns, the streams one after the other, read cyclically without the nulls).  false when a

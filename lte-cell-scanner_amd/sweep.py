@@ -208,7 +208,7 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
                      carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False,
-                     pdsch_comb=False, pdsch_alloc=None):
+                     pdsch_comb=False, pdsch_alloc=None, pdcch_scan=None):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -238,6 +238,9 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     distributed 1A grants and format 1C grants are followed too; the setting the searcher had comes back afterwards.  Its sfn0 is
     the caller's: the frame number of the first frame the stage reads, ONE value for every cell -- right only where the cells share
     their frame timing; pass -1 where they do not or it is not known.
+    pdcch_scan (a capi.PdcchScanCfg) also runs the blind search of every CCE (Searcher.pdcch_scan_wide) of every such cell whose MIB
+    says its PHICH configuration, from the same buffer, mask and slots: a dict cell gets cell["pdcch_scan"] (a PdcchScanInfo, or None
+    as for the PDCCH), and the record is appended to entry k's tuple after every other one.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -359,6 +362,13 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                             if sib:
                                 d["sib1"] = sib[0]
                         rec = rec + (pc,)
+                if pdcch_scan is not None:
+                    sc = None
+                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                        sc = searcher.pdcch_scan_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, pdcch_scan, n_cap=n_cap)
+                    if d is not None:
+                        d["pdcch_scan"] = sc
+                    rec = (rec if isinstance(rec, tuple) else (rec,)) + (sc,)
                 row.append(rec)
             out.append(row)
     finally:
