@@ -7,7 +7,10 @@ every port on all its reference rows; load on every other element; the PCFICH of
 subframe one format 1A DCI (two in subframe 6) and the transport block behind it; noise 20 dB below a resource element.  The plan of
 subframe g (PLAN): 0 every resource block (across PBCH, PSS and SSS); 1 one resource block at the band's edge; 2 a distributed
 grant; 3 a grant whose PDSCH is silent; 4 mcs 27; 5 the centre blocks (across PSS and SSS); 6 two grants side by side; 7 .. 11 other
-allocations; 12 a grant whose rows leave the grid.  rv = g mod 4, the TBS column g mod 2, the RNTIs cycle through SI, paging and RA."""
+allocations; 12 a grant whose rows leave the grid.  rv = g mod 4, the TBS column g mod 2, the RNTIs cycle through SI, paging and RA.
+
+For tests/test_pdsch_sizes_host.py and tests/test_gpu_pdsch_sizes.py: the same grids at 100, 75 and 50 resource blocks (WIDE_CASES), the
+decoder's inputs at all 127 block sizes (size_blocks) and forced grants at the largest sizes on the 25 RB grid (large_forced)."""
 import ctypes as C
 import functools
 import os
@@ -28,6 +31,9 @@ CASES = [
     (141, 1, 2, 15, 1, None), (256, 2, 4, 15, 4, None), (329, 1, 1, 15, 3, None),
     (7, 1, 2, 25, 3, None), (329, 2, 4, 25, 1, None), (142, 1, 2, 25, 3, (0, 1, None, None, 1, 0, 1, None, None, 1)),
 ]
+# the bandwidths at which a block's scrambling sequence needs every jump of the chunk number (bit 7 from 20 480 soft bits on) and an
+# allocation crosses the 64th resource block: one grid each at 100, 75 and 50 resource blocks, numbered after CASES
+WIDE_CASES = [(4, 1, 1, 100, 1, None), (2, 2, 4, 75, 3, None), (141, 1, 2, 50, 2, None)]
 RNTIS = [0xFFFF, 0xFFFE, 17, 0xFFFF, 60, 0xFFFE, 1]
 SNR_DB = 20.0
 N_SF = 13
@@ -36,6 +42,11 @@ SILENT_SF, DISTRIBUTED_SF, MCS_SF, TWO_SF, ROWS_SF = 3, 2, 4, 6, 12
 
 def case_id(case):
     return "id%d-cp%d-p%d-rb%d-r%d%s" % (case[:5] + ("-tdd" if case[5] else "",))
+
+
+def case_no(case):
+    """the case's number in the plan and the seeds: CASES first, WIDE_CASES after them"""
+    return CASES.index(case) if case in CASES else len(CASES) + WIDE_CASES.index(case)
 
 
 def pdcch_case(case):
@@ -62,13 +73,13 @@ def pack_1a(f, n_rb, tdd):
 
 def plan_of(case, g):
     """the grants of grid subframe g: [dict(rb_start, n_prb, mcs, rv, tpc, distributed, rnti, silent)]"""
-    n_rb, c_no = case[3], CASES.index(case)
+    n_rb, c_no = case[3], case_no(case)
     rv, tpc = g % 4, g % 2
     rnti = RNTIS[(g + c_no) % len(RNTIS)]
     mk = lambda s, n, mcs, **kw: dict(dict(rb_start=s, n_prb=n, mcs=mcs, rv=rv, tpc=tpc, distributed=0, rnti=rnti, silent=False), **kw)
     mid = n_rb // 2 - 1
     if g == 0:
-        return [mk(0, n_rb, {6: 9, 15: 20, 25: 26}[n_rb])]
+        return [mk(0, n_rb, {6: 9, 15: 20, 25: 26, 50: 26, 75: 24, 100: 26}[n_rb])]
     if g == 1:
         return [mk(n_rb - 1, 1, 0)]
     if g == DISTRIBUTED_SF:
@@ -80,9 +91,25 @@ def plan_of(case, g):
     if g == 5:
         return [mk(mid, 3, 2)]
     if g == TWO_SF:
-        return [mk(0, 2, 1), mk(2, n_rb - 2, {6: 6, 15: 12, 25: 17}[n_rb], rnti=RNTIS[(g + c_no + 1) % len(RNTIS)], rv=(rv + 1) % 4)]
+        return [mk(0, 2, 1), mk(2, n_rb - 2, {6: 6, 15: 12, 25: 17, 50: 20, 75: 22, 100: 25}[n_rb], rnti=RNTIS[(g + c_no + 1) % len(RNTIS)], rv=(rv + 1) % 4)]
     start = (3 * g + c_no) % (n_rb - 2)
     return [mk(start, 1 + (g + c_no) % min(4, n_rb - start), (2 * g + c_no) % 8)]
+
+
+def grid_seed(case, seed=0):
+    return 9000 + case_no(case) + 100 * seed
+
+
+def channel_of(case, rng):
+    """the grid's channel chan(port, row, columns), from the first twelve draws of the grid's generator"""
+    n_rb, nc = case[3], 12 * case[3]
+    gain = np.exp(2j * np.pi * rng.random(4)) * (0.7 + 0.6 * rng.random(4))
+    tau = 0.2 + 0.5 * rng.random(4)
+
+    def chan(p, row, cols):
+        cols = np.asarray(cols)
+        return gain[p] * np.exp(-2j * np.pi * tau[p] * (cols - nc / 2) / (128.0 * n_rb / 6)) * (1.0 + 0.3 * (cols / nc - 0.5)) * np.exp(2j * np.pi * 0.002 * row)
+    return chan
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,20 +119,15 @@ def crafted(case, snr_db=SNR_DB, seed=0):
     n_id, cp, ports, n_rb, res, mi = case
     pkg = load_pkg()
     synth, capi = pkg.synth, pkg.capi
-    c_no = CASES.index(case)
+    c_no = case_no(case)
     n, nc = PR.n_symb_of(cp), 12 * n_rb
     n_ofdm = 24 * n + (4 if n_rb <= 10 else 3)
-    rng = np.random.default_rng(9000 + c_no + 100 * seed)
-    gain = np.exp(2j * np.pi * rng.random(4)) * (0.7 + 0.6 * rng.random(4))
-    tau = 0.2 + 0.5 * rng.random(4)
+    rng = np.random.default_rng(grid_seed(case, seed))
+    chan = channel_of(case, rng)
     tdd = mi is not None
     size = capi.dci_common_sizes(n_rb, tdd)[0]
     mask = DC.dl_mask_of(pdcch_case(case))
     mis = DC.mi_of(pdcch_case(case))
-
-    def chan(p, row, cols):
-        cols = np.asarray(cols)
-        return gain[p] * np.exp(-2j * np.pi * tau[p] * (cols - nc / 2) / (128.0 * n_rb / 6)) * (1.0 + 0.3 * (cols / nc - 0.5)) * np.exp(2j * np.pi * 0.002 * row)
 
     k = np.arange(nc)
     qpsk = lambda m: ((1 - 2.0 * rng.integers(0, 2, m)) + 1j * (1 - 2.0 * rng.integers(0, 2, m))) / np.sqrt(2.0)
@@ -267,6 +289,102 @@ def assert_blocks_against_numpy(rec, blocks, what=""):
         assert (b.n_iter, b.status) == (r["n_iter"], r["status"]), (what, i, b.n_iter, b.status, r["n_iter"], r["status"])
         assert np.array_equal(np.ctypeslib.as_array(b.payload), r["payload"]), (what, i)
     return len(blocks), excused
+
+
+# ---------------------------------------------------------------- every block size (tests/test_pdsch_sizes_host.py, tests/test_gpu_pdsch_sizes.py)
+NOISY_K = (40, 48, 56, 2048, 2112, 2176, 2240)      # the ends of the table, every length of the last window, both sides of the second wave
+SLOW_SIGMA = 1.05       # blocks of the three sizes that need the second wave, with noise enough for three iterations and more
+
+
+def filler_step(K):
+    """the largest F + 1 that segmentation into one block can leave at size K: the distance to the size below"""
+    return 8 if K <= 512 else 16 if K <= 1024 else 32 if K <= 2048 else 64
+
+
+def _noisy_block(rng, K, F, sigma):
+    synth = load_pkg().synth
+    a = rng.integers(0, 2, K - F - 24).astype(np.uint8)
+    c = np.concatenate([np.zeros(F, np.uint8), a, synth.crc24a(a)])
+    d = (1 - 2.0 * synth.turbo_encode(c)) + sigma * rng.standard_normal((3, K + 4))
+    d[:2, :F] = 0
+    d.setflags(write=False)
+    return c, d
+
+
+@functools.lru_cache(maxsize=None)
+def size_blocks():
+    """The decoder's inputs at all 127 block sizes, built as tests/test_pdsch_host.py's test_decoder_against_numpy builds its own: per
+    K the first block of default_rng(10 K + F) for (F = 0, sigma = 0.85) and (F = filler_step - 1, sigma = 0.95); for K in NOISY_K the
+    second block of the F = 0 generator at sigma = 3.0, which runs out of iterations, at max_iter 1 and 16; for the three sizes of
+    the second wave the third block of that generator at SLOW_SIGMA.
+    -> list of dict(K, F, sigma, max_iter, c (the encoded block), d [3][K + 4])"""
+    out = []
+    for K in load_pkg().synth.TURBO_K:
+        for F, sigma in ((0, 0.85), (filler_step(K) - 1, 0.95)):
+            rng = np.random.default_rng(10 * K + F)
+            c, d = _noisy_block(rng, K, F, sigma)
+            out.append(dict(K=K, F=F, sigma=sigma, max_iter=8, c=c, d=d))
+            if F == 0 and K in NOISY_K:
+                c, d = _noisy_block(rng, K, 0, 3.0)
+                out += [dict(K=K, F=0, sigma=3.0, max_iter=it, c=c, d=d) for it in (1, 16)]
+                if K > 2048:
+                    c, d = _noisy_block(rng, K, 0, SLOW_SIGMA)
+                    out.append(dict(K=K, F=0, sigma=SLOW_SIGMA, max_iter=8, c=c, d=d))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def size_blocks_twin():
+    """the host twin's (bits, n_iter, status) of every block of size_blocks(): computed once, shared"""
+    H = load_twin(load_pkg().capi)
+    return [twin_turbo(H, b["d"], b["K"], b["F"], b["max_iter"]) for b in size_blocks()]
+
+
+# Forced grants at the sizes the crafted grids do not reach, on a copy of the 25 RB grid CASES[6] (CFI 3, 1, 2, 3 in subframes 1 .. 4 and
+# 2, 3, 1 in 6 .. 8: 240, 288 or 264 soft bits per resource block): (call, subframe, rb_start, n_prb, K, F, rv, rnti, noise in dB below a
+# resource element).  Both blocks of the second wave with and without fillers, the wave's boundary from both sides, the first sizes
+# of the 32 and 16 steps with their largest F, and a last window of 24 steps with F = 7; every rv; G < N (punctured) in the three
+# blocks that share or nearly fill a subframe and in the smallest, G > N (wrapped) in the others.  The noise is what makes the
+# blocks above K = 1056 take two iterations and the first block of subframe 3 three.
+LARGE_PLAN = [
+    (0, 1, 0, 25, 2240, 63, 2, 0xFFFF, 5.0), (0, 3, 0, 13, 2240, 0, 0, 0xFFFE, 7.0), (0, 3, 13, 12, 2176, 20, 0, 17, 7.0), (0, 2, 0, 25, 2112, 55, 3, 61, 5.0),
+    (1, 8, 0, 25, 2048, 0, 1, 0xFFFF, 5.0), (1, 6, 0, 13, 1056, 31, 1, 0xFFFE, 5.0), (1, 6, 13, 7, 528, 15, 3, 60, 5.0), (1, 7, 20, 5, 472, 7, 2, 61, 5.0),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def large_forced():
+    """-> (case, tfg: the case's grid with LARGE_PLAN's blocks planted by pdsch_ref.plant and noise on their elements, calls: per call
+    the list of forced grants (subframe, rnti, rb_start, n_prb, tbs, rv), planted: per call the transport blocks in the same order)"""
+    case = CASES[6]
+    n_id, cp, ports, n_rb, _, mi = case
+    base, cfi, _ = crafted(case)
+    tfg = np.array(base)
+    chan = channel_of(case, np.random.default_rng(grid_seed(case)))
+    rng = np.random.default_rng(9500)
+    n = PR.n_symb_of(cp)
+    calls, planted = [[], []], [[], []]
+    for call, g, start, n_prb, K, F, rv, rnti, snr_db in LARGE_PLAN:
+        tbs = K - F - 24
+        assert SR.block_size(tbs) == (K, F)
+        bits = rng.integers(0, 2, tbs).astype(np.uint8)
+        SR.plant(tfg, g, n_id, cp, ports, n_rb, int(cfi[g]), dict(rnti=rnti, rb_start=start, n_prb=n_prb, rv=rv, bits=bits), chan, mi is not None)
+        el = SR.elements(n_id, cp, ports, n_rb, g % 10, DR.n_ctrl_of(int(cfi[g]), n_rb), start, n_prb, mi is not None)
+        ls, ks = 2 * g * n + np.array([l for l, _ in el]), np.array([k for _, k in el])
+        sigma = 10 ** (-snr_db / 20) / np.sqrt(2.0)
+        tfg[ls, ks] += sigma * (rng.standard_normal(len(el)) + 1j * rng.standard_normal(len(el)))
+        calls[call].append((g, rnti, start, n_prb, tbs, rv))
+        planted[call].append(bits)
+    tfg.setflags(write=False)
+    return case, tfg, calls, planted
+
+
+@functools.lru_cache(maxsize=None)
+def large_forced_reference(call):
+    """pdsch_ref.receive's blocks of one call of large_forced(): computed once, shared"""
+    case, tfg, calls, _ = large_forced()
+    n_id, cp, ports, n_rb = case[:4]
+    return SR.receive(tfg, n_id, cp, ports, n_rb, reference(case)[0], forced=calls[call])
 
 
 # ---------------------------------------------------------------- captures with the generator's PCFICH, PDCCH and PDSCH in them

@@ -186,6 +186,9 @@ def test_foe_split_two_contexts_emulate_two_ranks():
             S.foe_partial(cap, f, a, n, fc, fc, fs, w.data_ptr(), m.data_ptr())
         assert int(words[2].max()) == -1                       # the empty share never wins
         red = torch.maximum(torch.maximum(words[0], words[1]), words[2])
+        # torch's stream and the contexts' own (non-blocking) streams do not wait for one another: what torch computes is finished before a
+        # context reads it, as sweep.search_capbuf_foe_split_dev sees to after its collectives
+        torch.cuda.synchronize()
         # round 5: near-ties of the arg-max -- inside a share or across the two -- are settled in the reference's arithmetic: every
         # context packs the exact maxima of the positions it contends for, their MAX replaces the approximate words
         w2 = [torch.empty(3 * 9600, dtype=torch.int64, device="cuda") for _ in ctxs]
@@ -194,6 +197,7 @@ def test_foe_split_two_contexts_emulate_two_ranks():
         assert int(w2[2].max()) == -1
         red2 = torch.maximum(torch.maximum(w2[0], w2[1]), w2[2])
         reds = [red.clone() for _ in ctxs]
+        torch.cuda.synchronize()
         for S, x in zip(ctxs, reds):
             S.foe_resolve(x.data_ptr(), red2.data_ptr())
         assert torch.equal(reds[0], reds[1]) and torch.equal(reds[0], reds[2])
@@ -209,10 +213,12 @@ def test_foe_split_two_contexts_emulate_two_ranks():
             for S, (a, n), w in zip(ctxs, shares_b, wb):
                 S.foe_partial(cap, f, a, n, fc, fc, fs, w.data_ptr(), meta[1].data_ptr())
             rb = wb[0] if len(wb) == 1 else torch.maximum(wb[0], wb[1])
+            torch.cuda.synchronize()
             wb2 = [torch.empty(3 * 9600, dtype=torch.int64, device="cuda") for _ in shares_b]
             for S, x in zip(ctxs, wb2):
                 S.foe_contend(f, rb.data_ptr(), x.data_ptr())
             rb2 = wb2[0] if len(wb2) == 1 else torch.maximum(wb2[0], wb2[1])
+            torch.cuda.synchronize()
             ctxs[0].foe_resolve(rb.data_ptr(), rb2.data_ptr())
             assert torch.equal(rb, reds[0]), shares_b
         # (back to the first split for the per-peak stages: the contexts' partial state is the last partial call's)
