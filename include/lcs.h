@@ -435,6 +435,68 @@ typedef struct lcs_pdcch_scan_info {
   lcs_pdcch_scan_msg msg[LCS_PDCCH_SCAN_MAX_MSG];
 } lcs_pdcch_scan_info;    /* 43616 bytes */
 
+/* The PHICH of a wide cell: the HARQ indicators (ACK / NACK of uplink transport blocks) of every downlink subframe of a
+ * full-bandwidth grid (lcs_phich_wide, lcs_phich, lcs_phich_values below; a stage of its own beside the others, which it leaves as
+ * they are).  THE RULE (lte-cell-scanner_amd/csrc/phich.h, host and device) IS WRITTEN FROM MEMORY OF 36.211 6.9 AND 36.212 5.3.5, NOT
+ * FROM THEIR TEXT: what pins it is the generator (synth.phich_region, written from the same memory but as a transmitter), the numpy
+ * statement tests/phich_ref.py, and the REG list, which is the PDCCH stage's own (pdc_build_map_t, pinned there).  It needs no CFI:
+ *   grid        as lcs_pcfich_info's.  Grid subframe g is read iff its bit of dl_mask is set, the rows of symbol 0 (symbols 0 .. 2
+ *               with the extended PHICH duration, symbols 0 and 1 with 4 ports) lie inside n_ofdm, and the PHICH map of m_i of
+ *               subframe g mod 10 is not refused (the units do not fit their symbol).  A TDD call is one with any phich_mi >= 0: at
+ *               the extended duration its subframes 1 and 6 are not read, as in the PDCCH stage
+ *   channel     the PDCCH stage's: symbol 0's reference row for ports 0 and 1, symbol 1's for ports 2 and 3, at the element's
+ *               column whatever its own symbol, interpolated as the PCFICH's
+ *   units       U = m_i ceil(Ng n_rb / 8) mapping units of three REGs: exactly the `phich` list of pdc_build_map_t (the rule of
+ *               lcs_pdcch_info above, line PHICH), called with cfi 3; REG i = 0, 1, 2 of unit m' holds quadruplet i, four elements
+ *               in increasing column.  U = 0 is a subframe that is read with nothing in it
+ *   groups      normal CP: group n = unit n, N_SF = 4, 8 sequences.  Extended CP: groups 2 m' and 2 m' + 1 share unit m', N_SF = 2,
+ *               4 sequences; the even group sits on elements 0, 1 of each quadruplet, the odd one on elements 2, 3
+ *   sequences   36.211 table 6.9.1-2.  Normal CP: w = ++++, +-+-, ++--, +--+ for seq 0 .. 3 and j times the same for seq 4 .. 7.
+ *               Extended CP: ++, +- for seq 0, 1 and j times the same for seq 2, 3
+ *   modulation  HI = 1 (ACK) is 111, HI = 0 (NACK) is 000; BPSK, bit 0 -> (1 + j) / sqrt 2, bit 1 -> -(1 + j) / sqrt 2;
+ *               d(i) = w(i mod N_SF) (1 - 2 c(i)) z(floor(i / N_SF)), i < 3 N_SF: repetition r of the indicator lies on quadruplet r.
+ *               c is the Gold sequence with the PCFICH's c_init = (sf + 1) (2 n_id_cell + 1) 2^9 + n_id_cell
+ *   combining   1 and 2 ports: as the PCFICH's on the pairs (elements 0, 1 and 2, 3) of a quadruplet.  4 ports: quadruplet i of
+ *               unit m' goes through ports (0, 2) when i + m' is even and through ports (1, 3) when it is odd, for the WHOLE
+ *               quadruplet (not the PDCCH's alternation inside a quadruplet).  The gain of element e is G_e = |h_a(k_e)|^2 +
+ *               |h_b(k_e')|^2, e' the other element of its pair (|h(k_e)|^2 with one port); nothing is divided by it
+ *   despreading per (group, seq) and repetition r: X = sum_j Re(w_j) or Im(w_j) times (1 - 2 c(i)) s_e over the N_SF elements (a
+ *               Hadamard butterfly), a_r = K (Re X + Im X) for a real sequence and K (Im X - Re X) for one with j, K = 1 / sqrt 2
+ *               with one port and 1 with two or four; d_r = the sum of G_e over the same elements.
+ *               value = (a_0 + a_1 + a_2) / (d_0 + d_1 + d_2): a PHICH planted at the amplitude of one unit-power resource element
+ *               reads +1 for NACK and -1 for ACK on a noise-free grid at every port count
+ *   noise       per (group, seq), S = sum_r d_r (a_r / d_r - value)^2 (a repetition with d_r = 0 adds nothing): the spread of the
+ *               three repetitions around their weighted mean, free of the signal whatever the loading.  noise[g] = the mean of S
+ *               over all (group, seq) of the subframe whose d sum is above zero (0 without one: an entry that does not read has
+ *               no spread to add); sigma = sqrt(noise[g] / (2 (d_0 + d_1 + d_2))): in white noise S is the element noise power
+ *               times a chi-square of 2 degrees of freedom over 2, so value / sigma of a silent entry has unit variance but for
+ *               the factor nu / (nu - 2) of a t distribution with nu = 2 N entries of the subframe
+ *   decision    present iff |value| >= min_amp and |value| >= min_sigma sigma; a present entry is an ACK iff value < 0.  An entry
+ *               whose d sum is zero, or whose value is not finite, is absent with value 0 (sigma 0 too)
+ * The order of every sum is fixed in phich.h; plain fp64, so the device and the host twin agree byte for byte.  sf[g]: n_unit (-1: not
+ * read; then the other fields are zero), n_group, the counts of present entries and noise[g].  hi[] lists the present entries by (g,
+ * group, seq), placed by ordered prefix sums without atomics; those beyond LCS_PHICH_MAX_HI are counted in n_dropped and not
+ * written, n_hi are listed.  NOT READ: TDD grant timing (which uplink subframe an indicator answers) and I_PHICH beyond the bindings'
+ * argument; subframes 1 and 6 of a TDD cell at the extended duration; MBSFN subframes; nothing of this is in the streaming mode,
+ * and the blind search does not use a grant's PHICH as an acceptance condition. */
+#define LCS_PHICH_MAX_HI 1024
+#define LCS_PHICH_MAX_GROUP 100           /* 25 units x m_i 2, x 2 groups per unit with the extended CP */
+#define LCS_PHICH_MAX_ENTRIES 400         /* (group, seq) pairs of a subframe */
+#define LCS_PHICH_MIN_AMP 0.25            /* a design floor: a PHICH 12 dB below a reference element is not worth reporting */
+#define LCS_PHICH_MIN_SIGMA 3.5           /* measured: tools/phich_accuracy.py, profiles/phich/accuracy.json */
+typedef struct lcs_phich_cfg {
+  int32_t phich_duration, phich_resource, phich_mi[10];   /* as lcs_pdcch_cfg's */
+  int32_t reserved[2];                    /* zero */
+  double min_amp, min_sigma;              /* >= 0; the bindings' defaults are LCS_PHICH_MIN_AMP and LCS_PHICH_MIN_SIGMA */
+} lcs_phich_cfg;          /* 72 bytes */
+typedef struct lcs_phich_sf { int32_t n_unit, n_group, n_present, n_ack, n_nack, reserved; double noise; } lcs_phich_sf;   /* 32 bytes */
+typedef struct lcs_phich_hi { int16_t g; uint8_t group, seq; int32_t flags /*1 present, 2 ack*/; double value, sigma; } lcs_phich_hi;   /* 24 bytes */
+typedef struct lcs_phich_info {
+  int32_t n_sf, n_read, n_present, n_ack, n_nack, n_hi, n_dropped, dl_mask, n_rb, n_ports, reserved[2];
+  lcs_phich_sf sf[LCS_PCFICH_MAX_SF];
+  lcs_phich_hi hi[LCS_PHICH_MAX_HI];
+} lcs_phich_info;         /* 26928 bytes */
+
 /* The PDSCH behind the format 1A grants of that search space: the transport blocks of SI, paging and random-access responses
  * (lcs_pdsch_wide, lcs_pdsch, lcs_turbo_decode below; a stage of its own beside the chain).  THE RULE (lte-cell-scanner_amd/csrc/
  * pdsch.h, host and device; grid, subframes, channel values and combining as for lcs_pcfich_info, the grants as lcs_pdcch_info):
@@ -741,6 +803,23 @@ int lcs_pdcch_scan_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf
 int lcs_pdcch_scan(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
                    int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out);
 int lcs_pdcch_scan_decodes(lcs_ctx *ctx, int g, lcs_pdcch_scan_dec *out, int cap);
+
+/* The PHICH (the rule: lcs_phich_info above).  The two take lcs_pdcch_wide's and lcs_pdcch's arguments, with their conventions and
+ * the PCFICH's refusals; cfg == NULL means the cell's PHICH configuration, FDD (every m_i 1) and the default thresholds.
+ * lcs_phich_wide transforms only the rows the rule reads: symbol 0 of every subframe read, symbol 1 too with 4 ports, symbols
+ * 0 .. 2 at the extended duration.  Two kernels, no host round trip.  Refused with LCS_ERR_BAD_ARG, a text and no launch: the PDCCH
+ * stage's refusals for the PHICH duration / resource and the m_i; a min_amp or min_sigma that is negative or not finite; a non-zero
+ * reserved field.  The unit tables are built on the host once per (n_rb, ports, CP, n_id_cell, PHICH duration and Ng) and kept in
+ * the context.  Isolation as the PCFICH's: the blocks are this stage's own, allocated by its first call.
+ * lcs_phich_values copies the full table of grid subframe g of the context's last call to out: n_group * n_seq values (n_seq = 8
+ * with the normal CP, 4 with the extended), group by group; it returns their number (0 for a subframe that was not read or holds
+ * no unit), or LCS_ERR_BAD_ARG before any call, for a g outside the call's subframes or a cap that is too small. */
+int lcs_phich_wide(lcs_ctx *ctx, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap,
+                   double fc_requested, double fc_programmed, double fs_programmed, int n_fft, int n_rb, int n_ofdm,
+                   int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out);
+int lcs_phich(lcs_ctx *ctx, const lcs_cell *cell, const double *tfg_wide_re_im /*host [n_ofdm][12 n_rb][2]*/, int n_ofdm, int n_rb,
+              int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out);
+int lcs_phich_values(lcs_ctx *ctx, int g, double *out, int cap);
 
 /* The PDSCH of the common search space's grants (the rule: lcs_pdsch_info above).  The two take lcs_pdcch_wide's and lcs_pdcch's
  * arguments with their conventions and refusals, the stage's configuration (NULL = defaults) and, optionally, a place for the PDCCH

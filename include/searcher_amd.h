@@ -151,6 +151,28 @@ class Searcher {
     v.resize((size_t)n);
     return v;
   }
+  // the HARQ indicators of every downlink subframe (lcs_phich_wide, lcs_phich: the rule is stated at lcs_phich_info).  cfg == nullptr: the
+  // cell's PHICH configuration, FDD, the default thresholds.  The record is 27 KB: it goes through `out`.
+  void phich_wide(const Cell &cell, const void *d_capbuf, uint32_t n_cap, double fc_requested, double fc_programmed, double fs_programmed,
+                  int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info &out) {
+    check(lcs_phich_wide(h_, &cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm, dl_mask, cfg, &out));
+  }
+  void phich(const Cell &cell, const cn::cmat &tfg, int n_rb, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info &out) {
+    const int n = tfg.rows(), nc = tfg.cols();
+    std::vector<double> g((size_t)n * nc * 2);
+    for (int r = 0; r < n; ++r)
+      for (int c = 0; c < nc; ++c) { g[((size_t)r * nc + c) * 2] = tfg(r, c).real(); g[((size_t)r * nc + c) * 2 + 1] = tfg(r, c).imag(); }
+    if (nc != 12 * n_rb) throw error("phich: the grid is [n_ofdm][12 n_rb]");
+    check(lcs_phich(h_, &cell, g.data(), n, n_rb, dl_mask, cfg, &out));
+  }
+  // the values of every (group, seq) of grid subframe g of the last PHICH call, group by group (lcs_phich_values)
+  std::vector<double> phich_values(int g) {
+    std::vector<double> v((size_t)LCS_PHICH_MAX_ENTRIES);
+    const int n = lcs_phich_values(h_, g, v.data(), (int)v.size());
+    if (n < 0) check(n);
+    v.resize((size_t)n);
+    return v;
+  }
   static double sinr(const lcs_meas_wide_info &m, int p = 0) { return m.noise[p] > 0 ? m.rsrp[p] / m.noise[p] : std::numeric_limits<double>::infinity(); }
   static int tdd_dl_mask(int ul_dl_config) { return lcs_tdd_dl_mask(ul_dl_config); }
   // the SINR of port p of a record: rsrp / noise, infinite where noise <= 0

@@ -20,7 +20,7 @@ from . import synth
 from . import sweep
 from . import itfile
 from . import tracker
-from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdcchScanCfg, PdcchScanInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdcchScanCfg, PdcchScanInfo, PhichCfg, PhichInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -72,6 +72,7 @@ class Searcher:
             raise SearcherError(f"lcs_create failed: {capi.ERRORS.get(rc, rc)} (an MI355X is required; no CPU fallback)")
         self._h = h
         self.device = device
+        self._phich_cp_normal = True
 
     def close(self):
         if getattr(self, "_h", None):
@@ -587,6 +588,44 @@ class Searcher:
         if n < 0:
             self._chk(n, "lcs_pdcch_scan_decodes")
         return [buf[i] for i in range(n)]
+
+    def phich_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
+                   cfg=None, n_cap=None):
+        """The HARQ indicators (ACK / NACK of uplink transport blocks) of every downlink subframe from the same samples
+        (lcs_phich_wide: symbol 0 of every subframe read is transformed, symbol 1 too with 4 ports, symbols 0 .. 2 at the extended
+        PHICH duration; no CFI is needed).  cfg: a capi.PhichCfg; None = the cell's PHICH configuration, FDD, the default thresholds
+        -> PhichInfo"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        out = capi.PhichInfo()
+        self._chk(self._lib.lcs_phich_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
+                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)),
+                  "lcs_phich_wide")
+        out.tdd = cfg is not None and cfg.tdd
+        self._phich_cp_normal = int(cell.cp_type) == 1      # the shape of phich_values' table
+        return out
+
+    def phich(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
+        """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
+        (extract_tfg_wide's) (lcs_phich) -> PhichInfo"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        out = capi.PhichInfo()
+        self._chk(self._lib.lcs_phich(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)),
+                  "lcs_phich")
+        out.tdd = cfg is not None and cfg.tdd
+        self._phich_cp_normal = int(cell.cp_type) == 1      # the shape of phich_values' table
+        return out
+
+    def phich_values(self, g: int):
+        """The full table of grid subframe g of this context's last PHICH call (lcs_phich_values): values [n_group][n_seq], n_seq = 8
+        with the normal CP and 4 with the extended (an empty array for a subframe that was not read or holds no unit)"""
+        buf = np.zeros(capi.PHICH_MAX_ENTRIES)
+        n = self._lib.lcs_phich_values(self._h, int(g), _dp(buf), buf.size)
+        if n < 0:
+            self._chk(n, "lcs_phich_values")
+        n_seq = 8 if self._phich_cp_normal else 4
+        return buf[:n].reshape(-1, n_seq).copy()
 
     def pdsch_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
                    cfg=None, pdsch_cfg=None, n_cap=None, want_pdcch: bool = False):

@@ -516,6 +516,141 @@ class PdcchScanInfo(C.Structure):
 
 assert C.sizeof(PdcchScanCfg) == 104 and C.sizeof(PdcchScanDec) == 32 and C.sizeof(PdcchScanMsg) == 40 and C.sizeof(PdcchScanSf) == 36 and C.sizeof(PdcchScanInfo) == 43616
 
+PHICH_MAX_HI, PHICH_MAX_GROUP, PHICH_MAX_ENTRIES = 1024, 100, 400   # LCS_PHICH_MAX_HI, LCS_PHICH_MAX_GROUP, LCS_PHICH_MAX_ENTRIES
+PHICH_MIN_AMP = 0.25                      # LCS_PHICH_MIN_AMP: a design floor
+PHICH_MIN_SIGMA = 3.5                     # LCS_PHICH_MIN_SIGMA: tools/phich_accuracy.py measures it
+PHICH_PRESENT, PHICH_ACK = 1, 2
+
+
+class PhichCfg(C.Structure):
+    """lcs_phich_cfg.  PhichCfg.make(...): the PHICH configuration as PdcchCfg.make's (0 = the cell's, phich_mi None = FDD); min_amp /
+    min_sigma None = the defaults."""
+    _fields_ = [("phich_duration", C.c_int32), ("phich_resource", C.c_int32), ("phich_mi", C.c_int32 * 10), ("reserved", C.c_int32 * 2),
+                ("min_amp", C.c_double), ("min_sigma", C.c_double)]
+
+    @classmethod
+    def make(cls, phich_duration=0, phich_resource=0, phich_mi=None, min_amp=None, min_sigma=None) -> "PhichCfg":
+        o = cls()
+        o.phich_duration, o.phich_resource = int(phich_duration), int(phich_resource)
+        o.min_amp = PHICH_MIN_AMP if min_amp is None else float(min_amp)
+        o.min_sigma = PHICH_MIN_SIGMA if min_sigma is None else float(min_sigma)
+        for i in range(10):
+            o.phich_mi[i] = -1 if phich_mi is None else (0 if phich_mi[i] is None else int(phich_mi[i]))
+        return o
+
+    @property
+    def tdd(self) -> bool:
+        return any(m >= 0 for m in self.phich_mi)
+
+
+class PhichSf(C.Structure):
+    """lcs_phich_sf: n_unit -1 = the subframe was not read"""
+    _fields_ = [("n_unit", C.c_int32), ("n_group", C.c_int32), ("n_present", C.c_int32), ("n_ack", C.c_int32), ("n_nack", C.c_int32), ("reserved", C.c_int32),
+                ("noise", C.c_double)]
+
+
+class PhichHi(C.Structure):
+    """lcs_phich_hi: flags 1 present, 2 ack"""
+    _fields_ = [("g", C.c_int16), ("group", C.c_uint8), ("seq", C.c_uint8), ("flags", C.c_int32), ("value", C.c_double), ("sigma", C.c_double)]
+
+
+class PhichInfo(C.Structure):
+    """lcs_phich_info: the HARQ indicators of every subframe of a full-bandwidth grid (include/lcs.h: lcs_phich_wide, lcs_phich).
+    sf[g]: the subframe's units, groups, counts and noise; hi[: n_hi]: the present entries by (g, group, seq).  tdd: whether the call
+    that made the record gave any m_i."""
+    _fields_ = [("n_sf", C.c_int32), ("n_read", C.c_int32), ("n_present", C.c_int32), ("n_ack", C.c_int32), ("n_nack", C.c_int32), ("n_hi", C.c_int32),
+                ("n_dropped", C.c_int32), ("dl_mask", C.c_int32), ("n_rb", C.c_int32), ("n_ports", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("sf", PhichSf * PCFICH_MAX_SF), ("hi", PhichHi * PHICH_MAX_HI)]
+    tdd = False
+
+    def copy(self) -> "PhichInfo":
+        o = PhichInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(PhichInfo))
+        o.tdd = self.tdd
+        return o
+
+    def _n(self) -> int:
+        return min(max(int(self.n_sf), 0), PCFICH_MAX_SF)
+
+    @property
+    def n_unit(self):
+        import numpy as np
+        return np.array([self.sf[g].n_unit for g in range(self._n())], np.int32)
+
+    @property
+    def noise(self):
+        import numpy as np
+        return np.array([self.sf[g].noise for g in range(self._n())])
+
+    def indicators(self) -> list:
+        """the present entries as dicts, in the record's order: subframe, group, seq, ack, value, sigma"""
+        out = []
+        for i in range(min(max(int(self.n_hi), 0), PHICH_MAX_HI)):
+            h = self.hi[i]
+            out.append(dict(subframe=int(h.g), group=int(h.group), seq=int(h.seq), ack=bool(h.flags & PHICH_ACK), value=float(h.value), sigma=float(h.sigma)))
+        return out
+
+    def ack_rate(self):
+        """the ACK share of the present entries (None without one): 1 - the cell's uplink block error rate"""
+        return None if self.n_present <= 0 else self.n_ack / self.n_present
+
+    def __repr__(self) -> str:  # pragma: no cover
+        return f"PhichInfo(n_sf={self.n_sf}, n_read={self.n_read}, n_present={self.n_present}, n_ack={self.n_ack}, n_nack={self.n_nack}, n_dropped={self.n_dropped})"
+
+
+assert C.sizeof(PhichCfg) == 72 and C.sizeof(PhichSf) == 32 and C.sizeof(PhichHi) == 24 and C.sizeof(PhichInfo) == 26928
+
+
+def phich_n_group(n_rb: int, phich_resource: int, cp_normal: bool, mi: int = 1) -> int:
+    """PHICH groups of a subframe (36.211 6.9): m_i ceil(Ng n_rb / 8), twice that with the extended CP.  phich_resource as lcs_cell's:
+    1 .. 4 for Ng = 1/6, 1/2, 1, 2"""
+    num, den = ((1, 6), (1, 2), (1, 1), (2, 1))[int(phich_resource) - 1]
+    return int(mi) * -(-(num * int(n_rb)) // (8 * den)) * (1 if cp_normal else 2)
+
+
+def phich_index(rb_start: int, cyclic_shift: int, n_group: int, cp_normal: bool, i_phich: int = 0):
+    """(group, seq) of the indicator that answers an uplink grant (36.213 9.1.2): n_group = (I_PRB + n_DMRS) mod N_group + I_PHICH
+    N_group, n_seq = (floor(I_PRB / N_group) + n_DMRS) mod 2 N_SF, with I_PRB = the grant's lowest PRB, n_DMRS = its cyclic-shift field
+    (36.213 table 9.1.2-2 maps the field 0 .. 7 onto itself) and N_group = the groups of the subframe with m_i = 1"""
+    rb_start, n_dmrs, n_group = int(rb_start), int(cyclic_shift), int(n_group)
+    if n_group <= 0 or rb_start < 0 or not 0 <= n_dmrs <= 7 or i_phich not in (0, 1):
+        raise ValueError("phich_index: needs n_group >= 1, rb_start >= 0, a cyclic shift field 0 .. 7 and I_PHICH 0 or 1")
+    return (rb_start + n_dmrs) % n_group + int(i_phich) * n_group, (rb_start // n_group + n_dmrs) % (8 if cp_normal else 4)
+
+
+def phich_for_grants(scan_info, phich_info, n_rb: int) -> list:
+    """For every accepted format 0 message of a scan (PdcchScanInfo.messages()) at grid subframe g: the indicator of phich_info at
+    subframe g + 8 and the index phich_index derives from the grant (N_group and the CP from what phich_info read that subframe
+    with).  -> [dict(subframe, rnti, rb_start, cyclic_shift, phich_subframe, group, seq, status, value)] with status "ack", "nack",
+    "absent", or "outside" when g + 8 is no subframe that phich_info read.  FDD only: a record of a TDD call raises (the TDD timing
+    of 36.213 table 9.1.2-1 is not implemented)."""
+    if getattr(phich_info, "tdd", False):
+        raise ValueError("phich_for_grants: FDD only, and the PHICH record is a TDD call's")
+    n_rb = int(n_rb)
+    a01 = dci_1a_size(n_rb, False)
+    present = {(h["subframe"], h["group"], h["seq"]): h for h in phich_info.indicators()}
+    out = []
+    for m in scan_info.messages():
+        if m["kind"] != "ue" or m["size"] != a01 or m["bits"] & 1:
+            continue
+        f = dci_0_fields(m["bits"], n_rb, False)
+        if f is None or f["rb_start"] is None:
+            continue
+        g8 = m["subframe"] + 8
+        row = dict(subframe=m["subframe"], rnti=m["rnti"], rb_start=f["rb_start"], cyclic_shift=f["cyclic_shift"], phich_subframe=g8, group=None, seq=None,
+                   status="outside", value=None)
+        if g8 < phich_info._n() and phich_info.sf[g8].n_unit >= 0:
+            s8 = phich_info.sf[g8]
+            row["status"] = "absent"
+            if s8.n_group > 0:
+                row["group"], row["seq"] = phich_index(f["rb_start"], f["cyclic_shift"], int(s8.n_group), s8.n_group == s8.n_unit)
+                h = present.get((g8, row["group"], row["seq"]))
+                if h is not None:
+                    row["status"], row["value"] = ("ack" if h["ack"] else "nack"), h["value"]
+        out.append(row)
+    return out
+
+
 # Payload sizes of the DCI formats of the UE-specific search space, Release 8/9, no carrier indicator (36.212 5.3.3.1).  THE TABLE IS
 # FROM MEMORY OF THE STANDARD; dci_ue_size_derived recomputes it from the field widths, and tests/test_pdcch_scan_host.py holds the
 # two together.  With RIV = ceil(log2(n_rb (n_rb + 1) / 2)), RBG size P = 1, 2, 2, 3, 4, 4 for 6 .. 100 resource blocks, the bitmap
@@ -1019,7 +1154,7 @@ EXPORTS = [
     "lcs_set_batch_screen", "lcs_get_batch_screen", "lcs_last_screen_stats", "lcs_set_duplex", "lcs_get_duplex", "lcs_set_foe_unwrap", "lcs_get_foe_unwrap", "lcs_pss_foe_coarse",
     "lcs_set_tdd_config", "lcs_get_tdd_config", "lcs_tdd_config", "lcs_last_tdd_info",
     "lcs_set_cell_meas", "lcs_get_cell_meas", "lcs_cell_meas", "lcs_last_cell_meas", "lcs_tdd_dl_mask",
-    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdcch_scan_wide", "lcs_pdcch_scan", "lcs_pdcch_scan_decodes", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
+    "lcs_extract_tfg_wide", "lcs_cell_meas_wide", "lcs_pcfich_wide", "lcs_pcfich", "lcs_pdcch_wide", "lcs_pdcch", "lcs_pdcch_scan_wide", "lcs_pdcch_scan", "lcs_pdcch_scan_decodes", "lcs_phich_wide", "lcs_phich", "lcs_phich_values", "lcs_pdsch_wide", "lcs_pdsch", "lcs_turbo_decode", "lcs_pdsch_last_soft", "lcs_pdsch_comb_wide", "lcs_pdsch_comb",
     "lcs_set_pdsch_alloc", "lcs_pdsch_last_alloc",
     "lcs_xcorr_pss", "lcs_peak_search", "lcs_sss_detect", "lcs_pss_sss_foe", "lcs_extract_tfg", "lcs_tfoec",
     "lcs_decode_mib", "lcs_pbch_soft", "lcs_chan_est", "lcs_search_capbuf", "lcs_search_batch_dev", "lcs_search_batch_host", "lcs_batch_enqueue",
@@ -1110,6 +1245,11 @@ def _declare(L: C.CDLL) -> C.CDLL:
                                           C.POINTER(PdcchScanCfg), C.POINTER(PdcchScanInfo)]
         L.lcs_pdcch_scan.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PdcchScanCfg), C.POINTER(PdcchScanInfo)]
         L.lcs_pdcch_scan_decodes.argtypes = [vp, C.c_int, C.POINTER(PdcchScanDec), C.c_int]
+    if hasattr(L, "lcs_phich_wide"):       # (likewise)
+        L.lcs_phich_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(PhichCfg), C.POINTER(PhichInfo)]
+        L.lcs_phich.argtypes = [vp, C.POINTER(LcsCell), dp, C.c_int, C.c_int, C.c_int, C.POINTER(PhichCfg), C.POINTER(PhichInfo)]
+        L.lcs_phich_values.argtypes = [vp, C.c_int, dp, C.c_int]
     if hasattr(L, "lcs_pdsch_wide"):      # (likewise)
         L.lcs_pdsch_wide.argtypes = [vp, C.POINTER(LcsCell), vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(PdcchCfg), C.POINTER(PdschCfg), C.POINTER(PdschInfo), C.POINTER(PdcchInfo)]

@@ -16,6 +16,7 @@
 #include "pcfich.h"
 #include "pdcch.h"
 #include "pdcch_scan.h"
+#include "phich.h"
 #include "pdsch.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
@@ -1443,6 +1444,123 @@ int lcs_pdcch_scan_decodes(lcs_ctx *c, int g, lcs_pdcch_scan_dec *out, int cap) 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < n_cand; ++i)
     for (int si = 0; si < p.last_n_sizes; ++si) out[i * p.last_n_sizes + si] = p.h_tab[(size_t)i * PSC_SIZES + si];
+  return n;
+}
+
+// ---- the PHICH on that grid (phich.hip, phich.h): blocks of its own and the same isolation
+namespace {
+// what cfg (or its absence) and the cell say together, or the refusal: plan_pdcch's for the PHICH configuration and the m_i
+int phich_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_phich_cfg *cfg, lcs_pdcch_cfg *shared, PhichPlan *p) {
+  std::memset(shared, 0, sizeof(*shared));
+  for (int i = 0; i < 10; ++i) shared->phich_mi[i] = -1;
+  shared->n_sizes = 1; shared->size[0] = 8;                  // the PDCCH's own fields: valid, and not this stage's
+  p->min_amp = LCS_PHICH_MIN_AMP; p->min_sigma = LCS_PHICH_MIN_SIGMA;
+  if (cfg) {
+    shared->phich_duration = cfg->phich_duration; shared->phich_resource = cfg->phich_resource;
+    for (int i = 0; i < 10; ++i) shared->phich_mi[i] = cfg->phich_mi[i];
+    p->min_amp = cfg->min_amp; p->min_sigma = cfg->min_sigma;
+  }
+  PdcchPlan pp;
+  int rc;
+  if ((rc = pdcch_resolve(c, who, cell, n_rb, shared, &pp))) return rc;
+  if (!(p->min_amp >= 0.0) || !std::isfinite(p->min_amp)) return wide_refused(c, who, "min_amp is negative or not finite");
+  if (!(p->min_sigma >= 0.0) || !std::isfinite(p->min_sigma)) return wide_refused(c, who, "min_sigma is negative or not finite");
+  if (cfg && (cfg->reserved[0] || cfg->reserved[1])) return wide_refused(c, who, "a reserved field is not zero");
+  p->phich_duration = pp.phich_duration; p->phich_resource = pp.phich_resource;
+  for (int i = 0; i < 10; ++i) p->mi[i] = pp.mi[i];
+  return LCS_OK;
+}
+// rows3[3 g + l] for every subframe of the grid and l < 3, as pcfich_plan: the rows the rule reads of a subframe that is read (symbol
+// 0; symbol 1 with 4 ports; symbols 0 .. 2 at the extended duration), -1 otherwise.  The tables of the call are in place.
+int phich_plan(const lcs_ctx *c, const lcs_cell *cell, const lcs_pdcch_cfg *shared, const PhichPlan &p, int n_ofdm, int dl_mask, int *rows3, std::vector<int> *list) {
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, ports = pcf_ports(cell->n_ports), n_sf = pcf_n_sf(n_ofdm, n_symb);
+  bool tdd = false;
+  for (int i = 0; i < 10; ++i) tdd = tdd || shared->phich_mi[i] >= 0;
+  for (int g = 0; g < n_sf; ++g) {
+    for (int l = 0; l < 3; ++l) rows3[3 * g + l] = -1;
+    if (!phi_sf_used(g, n_ofdm, n_symb, ports, p.phich_duration, tdd, dl_mask) || lcs_phich_map_units(c, p.mi[g % 10]) < 0) continue;
+    for (int l = 0; l < phi_rows_needed(ports, p.phich_duration); ++l) {
+      const int r = 2 * g * n_symb + l;
+      if (list) { rows3[3 * g + l] = (int)list->size(); list->push_back(r); }
+      else rows3[3 * g + l] = r;
+    }
+  }
+  return n_sf;
+}
+int phich_finish(lcs_ctx *c, int n_sf, lcs_phich_info *out) {
+  lcs_ctx::Phich &p = c->phich;
+  p.last_n_sf = 0;
+  HIPCHK(c, hipMemcpyAsync(out, p.rec, sizeof(lcs_phich_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int g = 0; g < n_sf; ++g) p.last_n_unit[g] = out->sf[g].n_unit;
+  p.last_n_sf = n_sf;
+  return LCS_OK;
+}
+}  // namespace
+
+int lcs_phich_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
+                   int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_phich_wide";
+  if (!out) return wide_refused(c, who, "a null pointer");
+  std::vector<double> ts;
+  double kk;
+  int rc;
+  lcs_pdcch_cfg shared;
+  PhichPlan plan;
+  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = phich_resolve(c, who, cell, n_rb, cfg, &shared, &plan))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_phich_tables(c, *cell, n_rb, plan))) return rc;
+  int rows3[3 * PCF_MAX_SF];
+  std::vector<int> list;
+  const int n_sf = phich_plan(c, cell, &shared, plan, n_ofdm, dl_mask, rows3, &list);
+  std::vector<double> ideal(list.size());
+  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
+  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
+  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
+  if ((rc = lcs_launch_phich(c, *cell, rows3, n_sf, n_rb, dl_mask, plan))) return rc;
+  return phich_finish(c, n_sf, out);
+}
+
+int lcs_phich(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_phich";
+  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
+  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
+  int rc;
+  lcs_pdcch_cfg shared;
+  PhichPlan plan;
+  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
+  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
+  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = phich_resolve(c, who, cell, n_rb, cfg, &shared, &plan))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = lcs_phich_tables(c, *cell, n_rb, plan))) return rc;
+  int rows3[3 * PCF_MAX_SF];
+  const int n_sf = phich_plan(c, cell, &shared, plan, n_ofdm, dl_mask, rows3, nullptr);
+  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
+  if ((rc = lcs_launch_phich(c, *cell, rows3, n_sf, n_rb, dl_mask, plan))) return rc;
+  return phich_finish(c, n_sf, out);
+}
+
+int lcs_phich_values(lcs_ctx *c, int g, double *out, int cap) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  static const char who[] = "lcs_phich_values";
+  lcs_ctx::Phich &p = c->phich;
+  if (!out) return wide_refused(c, who, "a null pointer");
+  if (p.last_n_sf == 0) return wide_refused(c, who, "the context has run no PHICH call");
+  if (g < 0 || g >= p.last_n_sf) return wide_refused(c, who, "g is outside the subframes of the last call");
+  const int n = p.last_n_unit[g] > 0 ? 8 * p.last_n_unit[g] : 0;
+  if (cap < n) return wide_refused(c, who, "cap is below n_group * n_seq of that subframe");
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  p.h_tab.resize((size_t)LCS_PHICH_MAX_ENTRIES);
+  HIPCHK(c, hipMemcpyAsync(p.h_tab.data(), p.tab.get() + (size_t)g * LCS_PHICH_MAX_ENTRIES, sizeof(lcs_ctx::PhichEntry) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; ++i) out[i] = p.h_tab[(size_t)i].value;
   return n;
 }
 

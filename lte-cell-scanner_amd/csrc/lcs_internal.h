@@ -453,6 +453,24 @@ struct lcs_ctx : lcs_ctx_queues {
     int cand_cap = 0;               // the candidates of the largest N_CCE among the key's maps
     int last_n_sf = 0, last_n_sizes = 0, last_n_cand[LCS_PCFICH_MAX_SF] = {};   // the last scan, for lcs_pdcch_scan_decodes; n_sf 0: none
   } pdcch_scan;
+  // the PHICH on that grid (phich.hip: lcs_phich_wide, lcs_phich, lcs_phich_values), allocated by the first call of that stage.  The
+  // unit tables are built on the host (phich.h) when the key changes, not per call.
+  struct PhichEntry { double value, dsum, S; };   // phich.h: PhiEntry
+  struct Phich {
+    DevBuf<int> map;                // [3 m_i] PhiMap: n_unit, re[600]
+    DevBuf<uint32_t> jump;          // [2][32]: jump-ahead to the call's reference sequence, and by 1600 clocks for the scrambling
+    DevBuf<int> sf;                 // [n_sf][3] grid rows of every subframe's symbols 0 .. 2 (-1: not read / not needed), m_i[10]
+    DevBuf<PhichEntry> tab;         // [LCS_PCFICH_MAX_SF][400]: every (group, seq) of the last call
+    DevBuf<int> sfu;                // [LCS_PCFICH_MAX_SF]: n_unit of every subframe, -1: not read
+    DevBuf<lcs_phich_info> rec;     // [1]
+    std::vector<int> h_map;         // the host blocks they are uploaded from
+    std::vector<PhichEntry> h_tab;  // one subframe of tab, for lcs_phich_values
+    uint32_t h_jump[64] = {};
+    int h_sf[3 * LCS_PCFICH_MAX_SF + 10] = {};
+    int key[6] = {};                // n_rb, ports, cp_type, id, phich_duration, phich_resource of the tables; n_rb 0: none
+    int jump_rb = 0;
+    int last_n_sf = 0, last_n_unit[LCS_PCFICH_MAX_SF] = {};   // the last call, for lcs_phich_values; n_sf 0: none
+  } phich;
   // the PDSCH behind that search space's grants (pdsch.hip: lcs_pdsch_wide, lcs_pdsch, lcs_turbo_decode), allocated by the first call
   // of that stage.  The tables are built on the host (pdsch.h) once, a forced grant's when its (K, F) changes; not per call.
   struct Pdsch {
@@ -711,6 +729,15 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
 struct PdcchScanPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[LCS_PDCCH_SCAN_MAX_SIZES], rnti_mask, cfi_force, min_repeat; double min_quality; };
 // rows4 as lcs_launch_pdcch's -> c->pdcch_scan.rec, c->pdcch_scan.tab
 int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchScanPlan &plan);
+// phich.hip
+struct PhichPlan { int phich_duration, phich_resource, mi[10]; double min_amp, min_sigma; };
+// the unit tables of (n_rb, ports, CP, id, PHICH duration and Ng), on the host and on the device: built when that key changes
+int lcs_phich_tables(lcs_ctx *c, const lcs_cell &cell, int n_rb, const PhichPlan &plan);
+// n_unit of the table of m_i (0 .. 2) that lcs_phich_tables left: -1 for a refused map
+int lcs_phich_map_units(const lcs_ctx *c, int mi);
+// rows3 [n_sf][3]: the rows of c->meas_wide.grid that hold symbols 0 .. 2 of every subframe (-1: not read, or not needed)
+// -> c->phich.rec, c->phich.tab
+int lcs_launch_phich(lcs_ctx *c, const lcs_cell &cell, const int *rows3, int n_sf, int n_rb, int dl_mask, const PhichPlan &plan);
 // pdsch.hip
 struct PdschPlan { int i_1a, max_iter, rnti_mask, n_forced, tdd; lcs_pdsch_grant forced[LCS_PDSCH_MAX_FORCED]; int alloc_flags, sfn0, si_window; };
 // the PCFICH and PDCCH of rows4 into c->pdsch.pdc, then the grants' blocks -> c->pdsch.rec.  sfrow [n_sf]: the row of c->meas_wide.grid

@@ -208,7 +208,7 @@ def map_frame_start(frame_start: float, decim_search: int, decim_meas: int) -> f
 
 def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, fc_centre: float, decim_search: int, cells_per_carrier,
                      carriers, n_rb: int = None, dl_mask: int = None, pcfich: bool = False, pdcch=False, tdd_config: int = None, pdsch=False,
-                     pdsch_comb=False, pdsch_alloc=None, pdcch_scan=None):
+                     pdsch_comb=False, pdsch_alloc=None, pdcch_scan=None, phich=False):
     """The full-bandwidth measurement (Searcher.cell_meas_wide) of what search_wideband found in the SAME capture, still in HBM:
     cells_per_carrier is its result (lists of LcsCell, or of dicts with meas=True) for `carriers`, searched at decim_search.
     For every cell with a MIB: R = meas_rate(n_rb or the cell's n_rb_dl), the capture is channelized once more at the cell's
@@ -241,6 +241,10 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
     pdcch_scan (a capi.PdcchScanCfg) also runs the blind search of every CCE (Searcher.pdcch_scan_wide) of every such cell whose MIB
     says its PHICH configuration, from the same buffer, mask and slots: a dict cell gets cell["pdcch_scan"] (a PdcchScanInfo, or None
     as for the PDCCH), and the record is appended to entry k's tuple after every other one.
+    phich=True (or a capi.PhichCfg) also reads the PHICH (Searcher.phich_wide) of every such cell whose MIB says its PHICH
+    configuration, from the same buffer, mask and slots and with no channelizer call of its own: a dict cell gets cell["phich"] (a
+    PhichInfo, or None as for the PDCCH), and the record is appended to entry k's tuple after every other one.  True takes the cell's
+    PHICH configuration and, in TDD with a known tdd_config, the m_i of capi.tdd_phich_mi.
     Raises ValueError for a capture whose rate is no integer multiple of 1.92 Msps (rational rates), for K / R < 2 off the
     carrier or in an integer format, and for a capture too short for two slots of the cell."""
     import ctypes as C
@@ -369,6 +373,17 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                     if d is not None:
                         d["pdcch_scan"] = sc
                     rec = (rec if isinstance(rec, tuple) else (rec,)) + (sc,)
+                if phich:
+                    ph = None
+                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                        cfg = phich
+                        if phich is True:
+                            tdd = searcher.duplex != capi.DUPLEX_FDD
+                            cfg = capi.PhichCfg.make(phich_mi=capi.tdd_phich_mi(tdd_config)) if tdd and tdd_config is not None else None
+                        ph = searcher.phich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, n_cap=n_cap)
+                    if d is not None:
+                        d["phich"] = ph
+                    rec = (rec if isinstance(rec, tuple) else (rec,)) + (ph,)
                 row.append(rec)
             out.append(row)
     finally:

@@ -609,6 +609,55 @@ def pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, dcis, fill=
     return n_ctrl, [(l, cols(k, l), _tx_diversity(z[wbar[i]], n_ports)) for i, (k, l) in enumerate(regs)]
 
 
+# 36.211 table 6.9.1-2: the orthogonal sequences of the PHICH, normal CP (N_SF = 4) and extended CP (N_SF = 2)
+_PHICH_W4 = np.array([[1, 1, 1, 1], [1, -1, 1, -1], [1, 1, -1, -1], [1, -1, -1, 1]], np.complex128)
+PHICH_SEQ = {True: np.concatenate([_PHICH_W4, 1j * _PHICH_W4]), False: np.array([[1, 1], [1, -1], [1j, 1j], [1j, -1j]], np.complex128)}
+
+
+def phich_n_group(n_rb, phich_res, cp_normal, mi=1):
+    """PHICH groups of a subframe (36.211 6.9): m_i ceil(Ng n_rb / 8), twice that with the extended CP; phich_res = the MIB's code"""
+    num, den = ((1, 6), (1, 2), (1, 1), (2, 1))[phich_res]
+    return int(mi) * -(-(num * n_rb) // (8 * den)) * (1 if cp_normal else 2)
+
+
+def phich_region(n_id_cell, n_rb, n_ports, cp_normal, subframe, cfi, his, phich_duration_ext=0, phich_res=2, mi=1):
+    """What the PHICH puts on its resource-element groups of a subframe (36.211 6.9): his = [dict(group, seq, ack, amp=1.0)], each the
+    HARQ indicator (ack: 1 -> bits 111, 0 -> 000) BPSK-modulated onto (1 + j) / sqrt 2, spread with its orthogonal sequence, scrambled
+    with the PCFICH's c_init, times amp; the sequences of a group add up; with the extended CP groups 2 m' and 2 m' + 1 share mapping
+    unit m' (elements 0, 1 and 2, 3 of each quadruplet).  Quadruplet i of unit m' goes through the transmit diversity onto REG i of
+    the unit (pdcch_layout's phich list), with four ports through ports (0, 2) when i + m' is even and (1, 3) when it is odd, for the
+    whole quadruplet.  -> [(l, columns [4], values [n_ports][4])] for every PHICH group of the subframe, silent ones included"""
+    _, _, regs, cols = pdcch_layout(n_id_cell, n_rb, n_ports, cp_normal, cfi, phich_duration_ext, phich_res, mi)
+    n_sf, n_unit = (4 if cp_normal else 2), len(regs) // 3
+    n_group = n_unit * (1 if cp_normal else 2)
+    seqs = PHICH_SEQ[bool(cp_normal)]
+    c = 1 - 2.0 * _pn((subframe + 1) * (2 * n_id_cell + 1) * 512 + n_id_cell, 3 * n_sf)
+    y = np.zeros((n_unit, 3, 4), np.complex128)
+    seen = set()
+    for h in his:
+        grp, seq = int(h["group"]), int(h["seq"])
+        if not (0 <= grp < n_group and 0 <= seq < 2 * n_sf) or (grp, seq) in seen:
+            raise ValueError("phich_region: an indicator outside the subframe's groups and sequences, or given twice")
+        seen.add((grp, seq))
+        z = (-1.0 if int(h["ack"]) else 1.0) * (1 + 1j) / np.sqrt(2.0) * float(h.get("amp", 1.0))
+        d = (np.tile(seqs[seq], 3) * c * z).reshape(3, n_sf)
+        if cp_normal:
+            y[grp] += d
+        else:
+            y[grp // 2, :, 2 * (grp & 1):2 * (grp & 1) + 2] += d
+    out = []
+    for u in range(n_unit):
+        for i in range(3):
+            k, l = regs[3 * u + i]
+            v = _tx_diversity(y[u, i], min(n_ports, 2))
+            if n_ports == 4:
+                q, v4 = (i + u) & 1, np.zeros((4, 4), np.complex128)
+                v4[q], v4[q + 2] = v[0], v[1]
+                v = v4
+            out.append((l, cols(k, l), v))
+    return out
+
+
 # ---- the PDSCH behind a format 1A grant (36.212 5.1.1, 5.1.3.2, 5.1.4.1; 36.211 6.3, 6.4): what lcs_pdsch_wide decodes ----------------
 # 36.212 table 5.1.3-3 up to K = 2240, written from memory of the standard (as lte-cell-scanner_amd/csrc/pdsch.h's copy: what pins
 # both is said there): K -> (f1, f2)
@@ -863,7 +912,7 @@ def sib1_schedule(message, n_rb, sfn0, rb_start=0, n_prb=None, L=4, cce=0, tdd=F
 
 
 def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_ports=2, load=0.5, rng=None, port_gains=None, per_port=False,
-                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None, pdsch=None):
+                       tdd=None, n_rb_dl=None, phich_duration_ext=0, phich_res=2, sfn0=0, cfi=None, pdcch=None, pdcch_fill=0.0, phich_mi=None, pdsch=None, phich=None):
     """cell_waveform for a carrier of n_rb resource blocks at 1.92e6 * R samples per second (R in 1, 2, 4, 8, 16; 128 R-point IDFT,
     CP lengths R * {10, 9, 32}), n_frames * 19200 * R samples from the boundary of frame sfn0.  The 72 centre subcarriers carry what
     cell_waveform puts there -- PSS, SSS, PBCH (the MIB says n_rb_dl: n_rb where that is an LTE bandwidth, else 50), CRS and load --
@@ -880,12 +929,16 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
     drawn from rng.
     pdsch: None plants no transport block.  A callable (frame, subframe) -> [dict(rnti, rb_start, n_prb, rv, bits)] (it needs cfi)
     puts the PDSCH of those grants on their resource elements (pdsch_region; the matching format 1A DCIs are the pdcch callable's to
-    send); the elements carry no load then."""
+    send); the elements carry no load then.
+    phich: None sends no PHICH.  A callable (frame, subframe) -> [dict(group, seq, ack, amp=1.0)] (it needs cfi) reserves the PHICH's
+    resource-element groups of every subframe that is sent (that subframe's map: the MIB's PHICH configuration, m_i as for pdcch) and
+    puts the sum of those indicators there (phich_region).  Without phich nothing more is drawn from rng and the waveform is what it
+    was."""
     rng = rng or np.random.default_rng(0)
     R, n_rb = int(R), int(n_rb)
-    if (pdcch is not None or pdsch is not None) and cfi is None:
-        raise ValueError("cell_waveform_wide: pdcch and pdsch need cfi")
-    ctrl_n, ctrl, data = 0, [], []
+    if (pdcch is not None or pdsch is not None or phich is not None) and cfi is None:
+        raise ValueError("cell_waveform_wide: pdcch, pdsch and phich need cfi")
+    ctrl_n, ctrl, data, hich = 0, [], [], []
     n_fft, nc, c0 = 128 * R, 12 * n_rb, 6 * n_rb - 36          # c0: the first of the 72 centre columns
     if R not in (1, 2, 4, 8, 16) or not 6 <= n_rb or 12 * n_rb >= n_fft:
         raise ValueError("cell_waveform_wide: R in 1, 2, 4, 8, 16 and 6 <= n_rb with 12 n_rb < 128 R")
@@ -970,6 +1023,9 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
                     if pdcch is not None:
                         ctrl_n, ctrl = pdcch_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, pdcch(fr, slot >> 1), pdcch_fill, rng,
                                                     phich_duration_ext, phich_res, 1 if phich_mi is None else phich_mi[slot >> 1])
+                    if phich is not None:
+                        hich = phich_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, phich(fr, slot >> 1), phich_duration_ext, phich_res,
+                                            1 if phich_mi is None else phich_mi[slot >> 1])
                     if pdsch is not None:
                         data = [t for gr in pdsch(fr, slot >> 1) for t in pdsch_region(n_id_cell, n_rb, n_ports, cp_normal, slot >> 1, value, gr, tdd is not None)]
                 if pdcch is not None and not (slot & 1) and sym < ctrl_n and not is_sync:
@@ -977,6 +1033,11 @@ def cell_waveform_wide(n_frames, n_id_1, n_id_2, R, n_rb, cp_normal=True, n_port
                     for l, cols, vals in ctrl:
                         if l == sym:
                             grid[:, cols] = vals
+                if phich is not None and not (slot & 1) and not is_sync:
+                    for l, cols, vals in hich:
+                        if l == sym:
+                            grid[:, cols] = vals
+                            reserved[cols] = True
                 for l, cols, vals in data:
                     if l == (slot & 1) * n_symb + sym:
                         grid[:, cols] = vals
@@ -1009,7 +1070,7 @@ def make_signal_wide(rng, fc, cd, R, n_rb, n_cap):
     w = cell_waveform_wide(n_frames, cd["n_id_1"], cd["n_id_2"], R, n_rb, cd.get("cp_normal", True), cd.get("n_ports", 2), cd.get("load", 0.5), rng,
                            cd.get("port_gains"), tdd=cd.get("tdd"), n_rb_dl=cd.get("n_rb_dl"), phich_duration_ext=cd.get("phich_duration_ext", 0),
                            phich_res=cd.get("phich_res", 2), sfn0=cd.get("sfn0", int(rng.integers(0, 1024))), cfi=cd.get("cfi"),
-                           pdcch=cd.get("pdcch"), pdcch_fill=cd.get("pdcch_fill", 0.0), phich_mi=cd.get("phich_mi"), pdsch=cd.get("pdsch"))
+                           pdcch=cd.get("pdcch"), pdcch_fill=cd.get("pdcch_fill", 0.0), phich_mi=cd.get("phich_mi"), pdsch=cd.get("pdsch"), phich=cd.get("phich"))
     y = frac_resample(w, t0 * R + n / k_factor)
     y = y * np.exp(2j * np.pi * f_off * n / (FS * R * k_factor))
     g = 10 ** (cd.get("gain_db", 0.0) / 20)
