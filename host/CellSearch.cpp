@@ -64,6 +64,7 @@ struct Options {
   int duplex = LCS_DUPLEX_FDD;   // -x: the band's duplex mode, set on every context
   bool foe_unwrap = false;       // -u: pss_sss_foe unwrapped by the PSS-only coarse estimate (lcs_set_foe_unwrap), set on every context
   bool tdd_config = false;       // -T: estimate every TDD cell's uplink-downlink configuration (lcs_set_tdd_config) and add it to the report
+  long sic = 0;                  // -S: search with cancellation rounds (lcs_search_capbuf_sic), 0: the plain search
   bool meas = false;             // -M: measure every cell's RSRP, RSRQ and CRS SINR (lcs_set_cell_meas) and add them to the report
   int verbosity = 1;
 };
@@ -87,6 +88,7 @@ const OptSpec kSpecs[] = {
     {'u', "foe-unwrap", FLAG, 0, {"unwrap the PSS/SSS frequency estimate with a PSS-only one: a tdd search then keeps the 5 kHz frequency grid (half the hypotheses)", 0}},
     {'T', "tdd-config", FLAG, 0, {"with -x tdd: estimate each cell's uplink-downlink configuration and DwPTS class from its reference signals; two more columns in the report", 0}},
     {'M', "meas", FLAG, 0, {"measure each cell's RSRP, RSRQ and SINR on its reference signals (with -x tdd on subframes 0 and 5, with --tdd-config on the downlink subframes found); three more columns in the report", 0}},
+    {'S', "sic", INDEX, "cancellation rounds", {"search in N rounds (1..4): after each, the decoded cells' PSS, SSS, CRS and PBCH are subtracted from the capture and the residual is searched again; one more column (the round) in the report", 0}},
     {'s', "freq-start", REAL, "start frequency", {"frequency where cell search should start", 0}},
     {'e', "freq-end", REAL, "end frequency", {"frequency where cell search should end", 0}},
     {'p', "ppm", REAL, "ppm value", {"crystal remaining PPM error", 0}},
@@ -101,7 +103,7 @@ void usage() {
   std::cout << "LTE CellSearch v" << VERSION_STRING << " (MI355X) help screen\n\n"
             << "CellSearch -s start_frequency [optional_parameters]\n";
   const struct { const char *title; const char *letters; } sections[] = {
-      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexuTM"}, {"Dongle LO correction options:", "pc"},
+      {"Basic options", "hvbigB"}, {"Frequency search options:", "sexuTMS"}, {"Dongle LO correction options:", "pc"},
       {"Capture buffer save/ load options:", "rld"}};
   for (const auto &sec : sections) {
     std::cout << "  " << sec.title << "\n";
@@ -164,6 +166,7 @@ void store(Options &o, const OptSpec &s, const char *value) {
       const long v = std::strtol(value, &end, 10);
       if (end == value || *end) die(std::string("could not parse ") + s.what);
       if (v < 0) die(s.letter == 'i' ? "device index cannot be negative" : s.letter == 'g' ? "could not parse gpu index" : "could not parse batch size");
+      if (s.letter == 'S') { if (v < 1 || v > LCS_SIC_MAX_ROUNDS) die("cancellation rounds must be 1..4"); o.sic = v; return; }
       if (s.letter == 'B') { if (v < 1 || v > 512) die("batch size must be 1..512"); o.batch = v; return; }
       (s.letter == 'i' ? o.device_index : o.gpu) = v;
       return;
@@ -340,6 +343,7 @@ struct Sweep {
   std::vector<std::list<Cell> > detected;
   std::vector<std::vector<lcs_tdd_info> > tdd;       // --tdd-config: per carrier, one record per detected cell
   std::vector<std::vector<lcs_meas_info> > meas;     // --meas: likewise
+  std::vector<std::vector<int> > rounds;             // --sic: per carrier, the round every detected cell was found in
   std::vector<char> fc_matches, batched;
   std::vector<char> batch_done;
   std::string failure;
@@ -399,13 +403,14 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
         const double fc = sw->opt.freq_start + 100e3 * f.single_carriers[j];
         lcsc::cvec capbuf((int)f.singles[j].samples.size());
         std::memcpy(capbuf._data(), f.singles[j].samples.data(), f.singles[j].samples.size() * sizeof(std::complex<double>));
-        one->search_capbuf(capbuf, sw->f_search_set, fc, fc, sw->fs_programmed, sw->detected[f.single_carriers[j]]);
+        if (sw->opt.sic) one->search_capbuf_sic(capbuf, sw->f_search_set, fc, fc, sw->fs_programmed, sw->detected[f.single_carriers[j]], (int)sw->opt.sic, LCS_SIC_ALL, &sw->rounds[f.single_carriers[j]]);
+        else one->search_capbuf(capbuf, sw->f_search_set, fc, fc, sw->fs_programmed, sw->detected[f.single_carriers[j]]);
         if (sw->opt.tdd_config) {
-          const std::vector<lcs_tdd_info> info = one->last_tdd_info(1, LCS_MAX_PEAKS);
+          const std::vector<lcs_tdd_info> info = sw->opt.sic ? one->last_sic_tdd_info(1, LCS_MAX_PEAKS) : one->last_tdd_info(1, LCS_MAX_PEAKS);
           sw->tdd[f.single_carriers[j]].assign(info.begin(), info.begin() + sw->detected[f.single_carriers[j]].size());
         }
         if (sw->opt.meas) {
-          const std::vector<lcs_meas_info> info = one->last_cell_meas(1, LCS_MAX_PEAKS);
+          const std::vector<lcs_meas_info> info = sw->opt.sic ? one->last_sic_cell_meas(1, LCS_MAX_PEAKS) : one->last_cell_meas(1, LCS_MAX_PEAKS);
           sw->meas[f.single_carriers[j]].assign(info.begin(), info.begin() + sw->detected[f.single_carriers[j]].size());
         }
       }
@@ -448,7 +453,7 @@ void device_thread(Sweep *sw, int device, int first_batch, int stride) {
       size_t n_cap = 0;
       for (int k = 0; k < n && !n_cap; ++k) if (!caps[k].iq_u8.empty()) n_cap = caps[k].samples.size();
       for (int k = 0; k < n; ++k) {
-        const bool bytes = n_cap && !caps[k].iq_u8.empty() && caps[k].samples.size() == n_cap;
+        const bool bytes = !sw->opt.sic && n_cap && !caps[k].iq_u8.empty() && caps[k].samples.size() == n_cap;
         sw->batched[first + k] = bytes;
         if (bytes) f.carriers.push_back(first + k);
         else { f.single_carriers.push_back(first + k); f.singles.push_back(Capture()); f.singles.back().samples.swap(caps[k].samples); }
@@ -504,6 +509,7 @@ int main(int argc, char *const argv[]) {
   sw.detected.resize(sw.n_fc);
   sw.tdd.resize(sw.n_fc);
   sw.meas.resize(sw.n_fc);
+  sw.rounds.resize(sw.n_fc);
   sw.fc_matches.assign(sw.n_fc, 1);
   sw.batched.assign(sw.n_fc, 0);
   sw.batch_done.assign(sw.n_batches, 0);
@@ -562,11 +568,13 @@ int main(int argc, char *const argv[]) {
     std::cout << "Detected the following cells:\n"
               << "A: #antenna ports C: CP type ; P: PHICH duration ; PR: PHICH resource type\n"
               << (opt.tdd_config ? "UD: uplink-downlink configuration ; DW: DwPTS class (port-0 reference rows in the special subframe)\n" : "")
+              << (opt.sic ? "R: the cancellation round the cell was found in (0: the plain search)\n" : "")
               << (opt.meas ? "RSRP: power per reference resource element of port 0, dB re full scale ; RSRQ: 6 RSRP / RSSI, dB ; SINR: RSRP / noise on port 0's reference signals, dB\n" : "")
-              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor" << (opt.tdd_config ? " UD DW" : "") << (opt.meas ? "  RSRP  RSRQ  SINR" : "") << "\n";
+              << "CID A      fc   foff RXPWR C nRB P  PR CrystalCorrectionFactor" << (opt.tdd_config ? " UD DW" : "") << (opt.meas ? "  RSRP  RSRQ  SINR" : "") << (opt.sic ? " R" : "") << "\n";
     for (size_t i = 0; i < cells.size(); ++i)
       std::cout << table_row(cells[i], opt.correction) << (opt.tdd_config ? tdd_columns(sw.tdd[origin[i].first][origin[i].second]) : std::string())
-                << (opt.meas ? meas_columns(sw.meas[origin[i].first][origin[i].second]) : std::string()) << "\n";
+                << (opt.meas ? meas_columns(sw.meas[origin[i].first][origin[i].second]) : std::string())
+                << (opt.sic ? fmt(" %d", sw.rounds[origin[i].first][origin[i].second]) : std::string()) << "\n";
     std::cout.flush();
   }
   return 0;

@@ -1315,6 +1315,74 @@ int lcs_chan_stream_push_u8(lcs_ctx *ctx, const void *d_chunk /*DEVICE, n_chunk 
  * through the call's last kernel), as lcs_last_xcorr_ms */
 int lcs_last_channelize_ms(lcs_ctx *ctx, float *ms);
 
+/* ---- successive cancellation (csrc/sic.h, sic.hip) --------------------------------------------------------------------
+ * peak_search reports one peak per 549 lags of a PSS row and nothing 12 dB below a buffer's strongest peak: a cell under a
+ * synchronised neighbour with the same n_id_2 is never listed.  What a decoded MIB makes known of a cell -- PSS, SSS, the
+ * cell-specific reference signals of its ports and the PBCH of every frame -- is rebuilt here through the cell's own channel
+ * estimate (from the CRS alone) over the WHOLE capture and subtracted on the device; the unchanged chain then searches the
+ * residual.  csrc/sic.h states the rule, tests/sic_ref.py restates it in numpy.
+ *
+ * lcs_sic_cancel_dev: n_buf device-resident captures (LCS_FMT_IQ_U8 or LCS_FMT_C64, n_cap samples each), cells
+ * [n_buf][max_cells_per_buf] with n_cells_per_buf[b] records in use, -> d_residual_c64 [n_buf][n_cap] complex<float> (the
+ * LCS_FMT_C64 batch layout; a buffer without cells is copied).  Records without a decoded MIB (n_rb_dl, n_ports or cp_type
+ * unknown) are left in the capture: their info has n_sym == 0.  On a context in LCS_DUPLEX_TDD the sync signals are taken at the
+ * TDD positions and CRS / PBCH are cancelled in subframes 0 and 5 only -- a record carries no uplink-downlink configuration;
+ * lcs_sic_cancel_cfg_dev takes one per record (ul_dl_config, laid out like cells, nullable; 0 .. 6 as lcs_last_tdd_info reports it,
+ * anything else: none) and then cancels CRS / PBCH in that configuration's downlink subframes (lcs_tdd_dl_mask) and in symbol 0 of
+ * subframes 1 and 6 as well: the mask rule of lcs_cell_meas.  mask selects the components; 0, or bits beyond LCS_SIC_ALL, is
+ * refused.  So is a capture of more than 268800 samples (14 frames at 1.92 Msps), or one that spans more than 16 frames of a cell: the
+ * per-cell PBCH table holds 16.  info (nullable) is [n_buf][max_cells_per_buf]. */
+#define LCS_SIC_PSS 1
+#define LCS_SIC_SSS 2
+#define LCS_SIC_CRS 4
+#define LCS_SIC_PBCH 8
+#define LCS_SIC_ALL 15
+#define LCS_SIC_MAX_ROUNDS 4
+typedef struct lcs_sic_info {
+  double power[4];          /* energy of the rebuilt PSS, SSS, CRS, PBCH over the symbols' transform windows (sum |x|^2 of the samples) */
+  double gain_re, gain_im;  /* the sync gain: received SSS over (port-0 channel x sequence) */
+  double pss_before;        /* energy of the 62 PSS subcarriers over the cell's PSS symbols in the capture ... */
+  double pss_after;         /* ... and in the residual (every cell of the buffer cancelled): the suppression is their ratio */
+  int32_t n_sym;            /* OFDM symbols covered, 0: the cell was not cancelled */
+  int32_t n_pss;            /* PSS symbols among them */
+  int32_t n_dup;            /* lcs_search_*_sic: times a later round found this identity again (the record was dropped) */
+  int32_t ul_dl_config;     /* the TDD configuration whose downlink subframes were cancelled, LCS_TDD_NOT_ESTIMATED: subframes 0 and 5 (TDD) / all (FDD) */
+} lcs_sic_info;             /* 80 bytes */
+int lcs_sic_cancel_dev(lcs_ctx *ctx, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const lcs_cell *cells,
+                       const int *n_cells_per_buf, int max_cells_per_buf, const double *fc_requested, const double *fc_programmed,
+                       double fs_programmed, int mask, void *d_residual_c64, lcs_sic_info *info);
+int lcs_sic_cancel_cfg_dev(lcs_ctx *ctx, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const lcs_cell *cells,
+                           const int *n_cells_per_buf, int max_cells_per_buf, const int32_t *ul_dl_config, const double *fc_requested,
+                           const double *fc_programmed, double fs_programmed, int mask, void *d_residual_c64, lcs_sic_info *info);
+/* The search with cancellation rounds.  Round 0 is the plain call (lcs_search_capbuf / lcs_search_batch_dev: the same records,
+ * the u8 route kept).  Every further round (max_rounds 1 .. LCS_SIC_MAX_ROUNDS in all; 2 = one cancellation) cancels ALL cells
+ * found so far from the ORIGINAL capture and runs the chain on the residual as complex<float>; cells whose n_id_cell the buffer
+ * already lists are dropped (n_dup of the listed record counts them), the others are appended with their round in round_of_cell.
+ * A buffer whose last round added nothing, or that has no cell, takes no further part; the call ends when no buffer does.
+ * round_of_cell and info (both nullable) are laid out like cells; info holds what the last cancellation a cell took part in
+ * reported.  peaks / n_peaks are round 0's.
+ * On a context in LCS_DUPLEX_TDD with lcs_set_tdd_config on, every cell is cancelled with the uplink-downlink configuration its own
+ * round's chain found for it (lcs_sic_cancel_cfg_dev's rule; info.ul_dl_config says which).
+ * Every round >= 1 is a fused call of its own on a COMPACTED batch of residuals: after lcs_search_*_sic the context's
+ * lcs_last_tdd_info, lcs_last_cell_meas, lcs_last_xcorr_ms and lcs_last_batch_stats describe the last round's batch, not the caller's
+ * buffers.  The side-table records of the cells this call handed out are gathered round by round instead: lcs_last_sic_tdd_info and
+ * lcs_last_sic_cell_meas, laid out like cells ([n_buf][max_cells_per_buf], the call's own max_cells_per_buf -- another value is
+ * refused), a cell of round r carrying what round r's chain measured on ITS input (the residual for r >= 1), and
+ * LCS_TDD_NOT_ESTIMATED / LCS_MEAS_NOT_MEASURED where the mode was off. */
+int lcs_search_capbuf_sic(lcs_ctx *ctx, const double *capbuf_re_im, uint32_t n_cap, const double *f_search_set, uint16_t n_f,
+                          double fc_requested, double fc_programmed, double fs_programmed, lcs_cell *cells, int max_cells,
+                          int *n_cells, lcs_cell *peaks, int max_peaks, int *n_peaks, int max_rounds, int mask,
+                          int32_t *round_of_cell, lcs_sic_info *info);
+int lcs_search_batch_sic_dev(lcs_ctx *ctx, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const double *f_search_set,
+                             uint16_t n_f, const double *fc_requested, const double *fc_programmed, double fs_programmed,
+                             lcs_cell *cells, int max_cells_per_buf, int *n_cells, int max_rounds, int mask,
+                             int32_t *round_of_cell, lcs_sic_info *info);
+/* The last lcs_search_*_sic call: stats[0] rounds run (1: round 0 alone), [1] cancellation launches, [2] cells appended by
+ * rounds >= 1, [3] records dropped as already listed. */
+int lcs_last_sic_stats(lcs_ctx *ctx, int stats[4]);
+int lcs_last_sic_tdd_info(lcs_ctx *ctx, lcs_tdd_info *info, int max_cells_per_buf);
+int lcs_last_sic_cell_meas(lcs_ctx *ctx, lcs_meas_info *info, int max_cells_per_buf);
+
 /* Stream the context launches on (hipStream_t as void*), for external event timing. */
 void *lcs_stream(lcs_ctx *ctx);
 int lcs_sync(lcs_ctx *ctx);
@@ -1325,6 +1393,9 @@ int lcs_table_pss_fd(int n_id_2, double *out_re_im /*62*2*/);     /* src/lte_lib
 int lcs_table_sss_fd(int n_id_1, int n_id_2, int slot_num, int32_t *out /*62*/); /* :199-257 */
 int lcs_table_lte_pn(uint32_t c_init, uint32_t len, uint8_t *out);               /* :41-147 */
 double lcs_chi2cdf_inv(double p, double k);                       /* include/dsp.h:188-193 */
+/* The QPSK symbols of one 40 ms PBCH period from a record's fields (csrc/lte_pbch_enc.cpp): 960 (normal CP) or 864 pairs */
+int lcs_table_pbch_symbols(int n_id_cell, int n_ports, int n_rb_dl, int phich_duration, int phich_resource, int sfn, int cp_type,
+                           double *out_re_im);
 
 #ifdef __cplusplus
 }

@@ -313,6 +313,58 @@ class Searcher {
     for (int i = 0; i < n && i < (int)out.size(); ++i) cells.push_back(Cell(out[i]));
   }
 
+  // The same with cancellation rounds (lcs_search_capbuf_sic): round 0 is search_capbuf; every further round (max_rounds 1 .. 4 in
+  // all) rebuilds PSS, SSS, CRS and PBCH (`mask`) of the cells found so far, subtracts them from the capture and searches the
+  // residual.  rounds[k] / info[k] (nullable) belong to the k-th cell appended by this call.
+  void search_capbuf_sic(const cn::cvec &capbuf, const cn::vec &f_search_set, double fc_requested, double fc_programmed, double fs_programmed,
+                         std::list<Cell> &cells, int max_rounds = 2, int mask = LCS_SIC_ALL, std::vector<int> *rounds = 0,
+                         std::vector<lcs_sic_info> *info = 0) {
+    std::vector<lcs_cell> out(LCS_MAX_PEAKS);
+    std::vector<int32_t> r(LCS_MAX_PEAKS);
+    std::vector<lcs_sic_info> inf(LCS_MAX_PEAKS);
+    int n = 0;
+    check(lcs_search_capbuf_sic(h_, reinterpret_cast<const double *>(capbuf._data()), (uint32_t)capbuf.length(), f_search_set._data(),
+                                (uint16_t)f_search_set.length(), fc_requested, fc_programmed, fs_programmed, out.data(), (int)out.size(), &n,
+                                0, 0, 0, max_rounds, mask, r.data(), inf.data()));
+    for (int i = 0; i < n && i < (int)out.size(); ++i) {
+      cells.push_back(Cell(out[i]));
+      if (rounds) rounds->push_back(r[i]);
+      if (info) info->push_back(inf[i]);
+    }
+  }
+  // the side-table records of the cells the last search_*_sic call handed out, laid out like them ([n_buf][max_cells_per_buf], the
+  // call's own max_cells_per_buf: LCS_MAX_PEAKS for search_capbuf_sic); last_tdd_info / last_cell_meas describe the last ROUND
+  std::vector<lcs_tdd_info> last_sic_tdd_info(int n_buf = 1, int max_cells_per_buf = LCS_MAX_PEAKS) { return last_records(lcs_last_sic_tdd_info, n_buf, max_cells_per_buf); }
+  std::vector<lcs_meas_info> last_sic_cell_meas(int n_buf = 1, int max_cells_per_buf = LCS_MAX_PEAKS) { return last_records(lcs_last_sic_cell_meas, n_buf, max_cells_per_buf); }
+  // ... over a batch of device-resident captures (lcs_search_batch_sic_dev), and the cancellation alone (lcs_sic_cancel_dev: cells
+  // [n_buf][max_cells_per_buf] with n_cells_per_buf[b] in use -> d_residual_c64 [n_buf][n_cap] complex<float>, info like cells)
+  void search_batch_sic_dev(const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const cn::vec &f_search_set, const std::vector<double> &fc_requested,
+                            const std::vector<double> &fc_programmed, double fs_programmed, std::vector<std::list<Cell> > &cells,
+                            std::vector<std::vector<int> > *rounds = 0, int max_rounds = 2, int mask = LCS_SIC_ALL, int max_cells_per_buf = 16) {
+    std::vector<lcs_cell> out((size_t)n_buf * max_cells_per_buf);
+    std::vector<int32_t> r((size_t)n_buf * max_cells_per_buf);
+    std::vector<int> cnt(n_buf);
+    const int rc = lcs_search_batch_sic_dev(h_, d_capbufs, fmt, n_buf, n_cap, f_search_set._data(), (uint16_t)f_search_set.length(), &fc_requested[0],
+                                            &fc_programmed[0], fs_programmed, out.data(), max_cells_per_buf, cnt.data(), max_rounds, mask, r.data(), 0);
+    if (rc != LCS_OK && rc != LCS_ERR_OVERFLOW) check(rc);
+    overflowed_ = rc == LCS_ERR_OVERFLOW;
+    cells.assign(n_buf, std::list<Cell>());
+    if (rounds) rounds->assign(n_buf, std::vector<int>());
+    for (int b = 0; b < n_buf; ++b)
+      for (int i = 0; i < cnt[b] && i < max_cells_per_buf; ++i) {
+        cells[b].push_back(Cell(out[(size_t)b * max_cells_per_buf + i]));
+        if (rounds) (*rounds)[b].push_back(r[(size_t)b * max_cells_per_buf + i]);
+      }
+  }
+  std::vector<lcs_sic_info> sic_cancel_dev(const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const std::vector<lcs_cell> &cells,
+                                           const std::vector<int> &n_cells_per_buf, int max_cells_per_buf, const std::vector<double> &fc_requested,
+                                           const std::vector<double> &fc_programmed, double fs_programmed, void *d_residual_c64, int mask = LCS_SIC_ALL) {
+    std::vector<lcs_sic_info> info((size_t)n_buf * max_cells_per_buf);
+    check(lcs_sic_cancel_dev(h_, d_capbufs, fmt, n_buf, n_cap, cells.data(), n_cells_per_buf.data(), max_cells_per_buf, &fc_requested[0],
+                             &fc_programmed[0], fs_programmed, mask, d_residual_c64, info.data()));
+    return info;
+  }
+
   // A sweep's worth of recorded captures at once (the carrier loop of src/CellSearch.cpp:471-569): n_buf host buffers
   // of n_cap samples each as raw RTL-SDR bytes (LCS_FMT_IQ_U8; captures are exactly (u8-127)/128, src/capbuf.cpp:
   // 172-181) or complex<float> (LCS_FMT_C64), one carrier frequency per buffer.  cells[b] receives buffer b's cells.

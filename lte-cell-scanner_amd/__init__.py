@@ -21,6 +21,7 @@ from . import sweep
 from . import itfile
 from . import tracker
 from .capi import LcsCell, LcsTrackCell, TddInfo, CellMeas, CellMeasWide, PcfichInfo, PdcchCfg, PdcchInfo, PdcchScanCfg, PdcchScanInfo, PhichCfg, PhichInfo, PdschCfg, PdschInfo, FMT_C64, FMT_IQ_U8, FMT_C128, FMT_IQ_S8, FMT_IQ_S16, STAGE_PSS, STAGE_FULL, MAX_PEAKS, DUPLEX_FDD, DUPLEX_TDD, TDD_NOT_ESTIMATED, MEAS_NOT_MEASURED
+from .capi import SicInfo, SIC_PSS, SIC_SSS, SIC_CRS, SIC_PBCH, SIC_ALL, SIC_MAX_ROUNDS
 
 FS_LTE = 30720000.0        # include/constants.h:32
 DS_COMB_ARM = 2            # src/CellSearch.cpp:484
@@ -333,6 +334,81 @@ class Searcher:
                      fs_programmed: float, stage_mask: int = STAGE_FULL, max_cells_per_buf: int = 16):
         self.batch_enqueue(d_ptr, fmt, n_buf, n_cap, f_search_set, fc_requested, fc_programmed, fs_programmed, stage_mask)
         return self.batch_collect(n_buf, max_cells_per_buf)
+
+    # ---- successive cancellation (include/lcs.h: lcs_sic_cancel_dev, lcs_search_*_sic; the rule: csrc/sic.h) ----
+    def sic_cancel(self, d_ptr: int, fmt: int, n_buf: int, n_cap: int, cells, fc_requested, fc_programmed, fs_programmed: float,
+                   d_residual_ptr: int, mask: int = SIC_ALL, ul_dl_config=None):
+        """Rebuild the known signals (PSS, SSS, CRS, PBCH: `mask`) of cells[b] -- the decoded records of buffer b -- and subtract them
+        from the n_buf device-resident captures at d_ptr (FMT_IQ_U8 or FMT_C64) into the complex64 buffer [n_buf][n_cap] at
+        d_residual_ptr.  ul_dl_config (TDD): per buffer a list with each record's uplink-downlink configuration (0..6 as last_tdd_info
+        reports it, anything else: none) -- CRS and PBCH then go in that configuration's downlink subframes and in symbol 0 of
+        subframes 1 and 6 too, not in subframes 0 and 5 alone.  -> [n_buf] lists of SicInfo, one per record."""
+        per = max(1, max((len(c) for c in cells), default=1))
+        arr = (LcsCell * (n_buf * per))()
+        for b in range(n_buf):
+            for i, c in enumerate(cells[b]):
+                arr[b * per + i] = c
+        cnt = np.array([len(cells[b]) for b in range(n_buf)], np.int32)
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(fc_requested, np.float64), (n_buf,)))
+        fp_ = np.ascontiguousarray(np.broadcast_to(np.asarray(fc_programmed, np.float64), (n_buf,)))
+        info = (SicInfo * (n_buf * per))()
+        cfg = None
+        if ul_dl_config is not None:
+            cfg = np.full(n_buf * per, capi.TDD_NOT_ESTIMATED, np.int32)
+            for b in range(n_buf):
+                for i, v in enumerate(ul_dl_config[b]):
+                    cfg[b * per + i] = int(v)
+        rc = self._lib.lcs_sic_cancel_cfg_dev(self._h, C.c_void_p(d_ptr), fmt, n_buf, n_cap, arr, _ip(cnt), per, _ip(cfg), _dp(fr), _dp(fp_),
+                                              fs_programmed, int(mask), C.c_void_p(d_residual_ptr), info)
+        self._chk(rc, "lcs_sic_cancel_cfg_dev")
+        return [[info[b * per + i].copy() for i in range(cnt[b])] for b in range(n_buf)]
+
+    def search_capbuf_sic(self, capbuf, f_search_set, fc_requested, fc_programmed, fs_programmed, max_rounds: int = 2, mask: int = SIC_ALL,
+                          max_cells=MAX_PEAKS):
+        """search_capbuf, then up to max_rounds - 1 rounds that cancel every cell found so far from the capture and search the
+        residual.  -> (cells, rounds, info): the round each cell was found in (0: the plain search, whose records these are) and the
+        SicInfo of the last cancellation it took part in."""
+        cap = np.ascontiguousarray(capbuf, np.complex128)
+        f = np.ascontiguousarray(f_search_set, np.float64)
+        cells, peaks = (LcsCell * max_cells)(), (LcsCell * MAX_PEAKS)()
+        n, npk = C.c_int(0), C.c_int(0)
+        rounds, info = np.zeros(max_cells, np.int32), (SicInfo * max_cells)()
+        rc = self._lib.lcs_search_capbuf_sic(self._h, _dp(cap), cap.size, _dp(f), f.size, fc_requested, fc_programmed, fs_programmed, cells,
+                                             max_cells, C.byref(n), peaks, MAX_PEAKS, C.byref(npk), int(max_rounds), int(mask), _ip(rounds), info)
+        self._chk(rc, "lcs_search_capbuf_sic")
+        k = min(n.value, max_cells)
+        return [cells[i].copy() for i in range(k)], [int(r) for r in rounds[:k]], [info[i].copy() for i in range(k)]
+
+    def search_batch_sic(self, d_ptr: int, fmt: int, n_buf: int, n_cap: int, f_search_set, fc_requested, fc_programmed, fs_programmed: float,
+                         max_rounds: int = 2, mask: int = SIC_ALL, max_cells_per_buf: int = 16):
+        """search_batch (the full chain) with cancellation rounds, per buffer as search_capbuf_sic -> (cells, rounds, info), each [n_buf] lists"""
+        f = np.ascontiguousarray(f_search_set, np.float64)
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(fc_requested, np.float64), (n_buf,)))
+        fp_ = np.ascontiguousarray(np.broadcast_to(np.asarray(fc_programmed, np.float64), (n_buf,)))
+        m = max_cells_per_buf
+        cells, info = (LcsCell * (n_buf * m))(), (SicInfo * (n_buf * m))()
+        n, rounds = np.zeros(n_buf, np.int32), np.zeros(n_buf * m, np.int32)
+        rc = self._lib.lcs_search_batch_sic_dev(self._h, C.c_void_p(d_ptr), fmt, n_buf, n_cap, _dp(f), f.size, _dp(fr), _dp(fp_), fs_programmed, cells, m,
+                                                n.ctypes.data_as(C.POINTER(C.c_int)), int(max_rounds), int(mask), _ip(rounds), info)
+        self._chk(rc, "lcs_search_batch_sic_dev")
+        k = [min(int(x), m) for x in n]
+        return ([[cells[b * m + i].copy() for i in range(k[b])] for b in range(n_buf)], [[int(rounds[b * m + i]) for i in range(k[b])] for b in range(n_buf)],
+                [[info[b * m + i].copy() for i in range(k[b])] for b in range(n_buf)])
+
+    def last_sic_tdd_info(self, n_buf: int = 1, max_cells_per_buf: int = MAX_PEAKS):
+        """The TddInfo of every cell the last search_*_sic call returned, laid out like its cells (a cell of round r: what round r's chain
+        estimated); max_cells_per_buf is that call's (search_capbuf_sic: max_cells).  last_tdd_info() itself describes the last ROUND."""
+        return self._last_records("lcs_last_sic_tdd_info", capi.TddInfo, n_buf, max_cells_per_buf)
+
+    def last_sic_cell_meas(self, n_buf: int = 1, max_cells_per_buf: int = MAX_PEAKS):
+        """likewise the CellMeas records (a cell found in round r >= 1 is measured on the residual it was found in)"""
+        return self._last_records("lcs_last_sic_cell_meas", capi.CellMeas, n_buf, max_cells_per_buf)
+
+    def last_sic_stats(self) -> dict:
+        """the last search_*_sic call: rounds run (1: the plain search alone), cancellation launches, cells added, duplicates dropped"""
+        st = (C.c_int * 4)()
+        self._chk(self._lib.lcs_last_sic_stats(self._h, C.byref(st)), "lcs_last_sic_stats")
+        return dict(rounds=st[0], cancellations=st[1], added=st[2], dropped=st[3])
 
     # ---- LTE-Tracker's per-symbol pipeline on a block of symbols (src/tracker_thread.cpp:823-1068) ----
     def track_block(self, cells, td, freq_off, frame_timing, late, fc_requested, fc_programmed, fs_programmed,

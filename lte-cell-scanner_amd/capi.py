@@ -87,6 +87,42 @@ class TddInfo(C.Structure):
 assert C.sizeof(TddInfo) == 128
 
 
+SIC_PSS, SIC_SSS, SIC_CRS, SIC_PBCH, SIC_ALL = 1, 2, 4, 8, 15      # LCS_SIC_*: the components a cancellation takes out
+SIC_MAX_ROUNDS = 4
+
+
+class SicInfo(C.Structure):
+    """lcs_sic_info: what a cancellation did to one cell (include/lcs.h: lcs_sic_cancel_dev).  power = the energy of the rebuilt PSS,
+    SSS, CRS and PBCH, gain = the sync gain, pss_before / pss_after = the energy of the cell's PSS subcarriers in the capture and in the
+    residual, n_sym = symbols covered (0: not cancelled), n_pss of them PSS symbols, n_dup = times a later round found the cell again,
+    ul_dl_config = the TDD configuration whose downlink subframes were cancelled (TDD_NOT_ESTIMATED: subframes 0 and 5, or FDD)."""
+    _fields_ = [("power", C.c_double * 4), ("gain_re", C.c_double), ("gain_im", C.c_double), ("pss_before", C.c_double), ("pss_after", C.c_double),
+                ("n_sym", C.c_int32), ("n_pss", C.c_int32), ("n_dup", C.c_int32), ("ul_dl_config", C.c_int32)]
+
+    def copy(self) -> "SicInfo":
+        o = SicInfo()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(SicInfo))
+        return o
+
+    @property
+    def cancelled(self) -> bool:
+        return self.n_sym > 0
+
+    @property
+    def gain(self) -> complex:
+        return complex(self.gain_re, self.gain_im)
+
+    @property
+    def suppression_db(self) -> float:
+        """10 log10(pss_before / pss_after); inf when nothing is left, nan when the cell was not cancelled"""
+        if self.n_sym <= 0 or self.pss_before <= 0:
+            return math.nan
+        return math.inf if self.pss_after <= 0 else 10.0 * math.log10(self.pss_before / self.pss_after)
+
+
+assert C.sizeof(SicInfo) == 80
+
+
 class CellMeas(C.Structure):
     """lcs_meas_info: RSRP, RSSI, RSRQ and the noise power of a cell from its cell-specific reference signals (include/lcs.h:
     lcs_set_cell_meas).  status 0 measured, -1 no number, MEAS_NOT_MEASURED never written; n_rows reference rows of the subframes in
@@ -1165,6 +1201,8 @@ EXPORTS = [
     "lcs_channelizer_proto", "lcs_channelize_rational", "lcs_channelize_u8",
     "lcs_chan_stream_open", "lcs_chan_stream_count", "lcs_chan_stream_push", "lcs_chan_stream_close",
     "lcs_chan_stream_open_u8", "lcs_chan_stream_count_u8", "lcs_chan_stream_push_u8",
+    "lcs_sic_cancel_dev", "lcs_search_capbuf_sic", "lcs_search_batch_sic_dev", "lcs_last_sic_stats", "lcs_table_pbch_symbols",
+    "lcs_sic_cancel_cfg_dev", "lcs_last_sic_tdd_info", "lcs_last_sic_cell_meas",
 ]
 
 _lib = None
@@ -1280,6 +1318,18 @@ def _declare(L: C.CDLL) -> C.CDLL:
     L.lcs_search_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, dp, C.c_uint16, dp, dp, C.c_double,
                                        C.c_int, cp, C.c_int, C.POINTER(C.c_int)]
     L.lcs_search_batch_host.argtypes = L.lcs_search_batch_dev.argtypes
+    if hasattr(L, "lcs_sic_cancel_dev"):      # (a parent commit's library loaded by load_other has none)
+        sp = C.POINTER(SicInfo)
+        L.lcs_sic_cancel_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, cp, ip, C.c_int, dp, dp, C.c_double, C.c_int, vp, sp]
+        L.lcs_search_capbuf_sic.argtypes = [vp, dp, C.c_uint32, dp, C.c_uint16, C.c_double, C.c_double, C.c_double, cp, C.c_int, C.POINTER(C.c_int),
+                                            cp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, ip, sp]
+        L.lcs_search_batch_sic_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, dp, C.c_uint16, dp, dp, C.c_double, cp, C.c_int,
+                                               C.POINTER(C.c_int), C.c_int, C.c_int, ip, sp]
+        L.lcs_last_sic_stats.argtypes = [vp, C.POINTER(C.c_int * 4)]
+        L.lcs_sic_cancel_cfg_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, cp, ip, C.c_int, ip, dp, dp, C.c_double, C.c_int, vp, sp]
+        L.lcs_last_sic_tdd_info.argtypes = [vp, C.POINTER(TddInfo), C.c_int]
+        L.lcs_last_sic_cell_meas.argtypes = [vp, C.POINTER(CellMeas), C.c_int]
+        L.lcs_table_pbch_symbols.argtypes = [C.c_int] * 7 + [dp]
     L.lcs_batch_readback.argtypes = [vp, C.c_int, fp, dp, ip, dp, dp]
     L.lcs_batch_enqueue.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, dp, C.c_uint16, dp, dp, C.c_double, C.c_int]
     L.lcs_batch_enqueue_host.argtypes = L.lcs_batch_enqueue.argtypes

@@ -1828,6 +1828,178 @@ int lcs_search_capbuf(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const do
   return read_cells_and_peaks(c, cells, nullptr, max_cells, n_cells, peaks, max_peaks, n_peaks);
 }
 
+// ------------------------------------------------------------------- successive cancellation (sic.hip; the rule: sic.h)
+static int sic_check(lcs_ctx *c, int fmt, int n_buf, uint32_t n_cap, int mask) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (mask <= 0 || (mask & ~LCS_SIC_ALL)) { c->err = "lcs_sic: mask selects no component (LCS_SIC_PSS | _SSS | _CRS | _PBCH)"; return LCS_ERR_BAD_ARG; }
+  if (fmt != LCS_FMT_C64 && fmt != LCS_FMT_IQ_U8) { c->err = "lcs_sic: captures are LCS_FMT_C64 or LCS_FMT_IQ_U8"; return LCS_ERR_BAD_ARG; }
+  if (n_buf < 1 || n_cap < 9600 || n_cap > 268800) { c->err = "lcs_sic: n_buf >= 1, 9600 <= n_cap <= 268800 (the per-cell PBCH table holds 16 frames)"; return LCS_ERR_BAD_ARG; }
+  return LCS_OK;
+}
+
+int lcs_sic_cancel_cfg_dev(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const lcs_cell *cells, const int *n_cells_per_buf,
+                           int max_cells_per_buf, const int32_t *ul_dl_config, const double *fc_requested, const double *fc_programmed,
+                           double fs_programmed, int mask, void *d_residual_c64, lcs_sic_info *info) {
+  int rc = sic_check(c, fmt, n_buf, n_cap, mask);
+  if (rc) return rc;
+  if (!d_capbufs || !cells || !n_cells_per_buf || !fc_requested || !fc_programmed || !d_residual_c64 || max_cells_per_buf < 1) { c->err = "null argument"; return LCS_ERR_BAD_ARG; }
+  for (int b = 0; b < n_buf; ++b)
+    if (n_cells_per_buf[b] < 0 || n_cells_per_buf[b] > max_cells_per_buf) { c->err = "lcs_sic_cancel_dev: n_cells_per_buf beyond max_cells_per_buf"; return LCS_ERR_BAD_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  return lcs_launch_sic(c, d_capbufs, fmt, n_buf, n_cap, cells, n_cells_per_buf, max_cells_per_buf, fc_requested, fc_programmed, fs_programmed,
+                        mask, c->duplex, nullptr, ul_dl_config, static_cast<float2 *>(d_residual_c64), info);
+}
+
+int lcs_sic_cancel_dev(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const lcs_cell *cells, const int *n_cells_per_buf,
+                       int max_cells_per_buf, const double *fc_requested, const double *fc_programmed, double fs_programmed, int mask,
+                       void *d_residual_c64, lcs_sic_info *info) {
+  return lcs_sic_cancel_cfg_dev(c, d_capbufs, fmt, n_buf, n_cap, cells, n_cells_per_buf, max_cells_per_buf, nullptr, fc_requested, fc_programmed,
+                                fs_programmed, mask, d_residual_c64, info);
+}
+
+// The side tables of the fused call that has just returned (n buffers), as lcs_last_tdd_info / lcs_last_cell_meas lay them out; a mode
+// that is off leaves its sentinel everywhere.
+static int sic_read_side(lcs_ctx *c, int n, int max_cells, std::vector<lcs_tdd_info> *tdd, std::vector<lcs_meas_info> *meas) {
+  lcs_tdd_info t0{}; t0.ul_dl_config = t0.dwpts_rs_rows = LCS_TDD_NOT_ESTIMATED;
+  lcs_meas_info m0{}; meas_clear(&m0, LCS_MEAS_NOT_MEASURED);
+  tdd->assign((size_t)n * max_cells, t0);
+  meas->assign((size_t)n * max_cells, m0);
+  int rc;
+  if (c->tdd_config && c->duplex == LCS_DUPLEX_TDD && (rc = lcs_last_tdd_info(c, tdd->data(), max_cells)) && rc != LCS_ERR_OVERFLOW) return rc;
+  if (c->cell_meas && (rc = lcs_last_cell_meas(c, meas->data(), max_cells)) && rc != LCS_ERR_OVERFLOW) return rc;
+  return LCS_OK;
+}
+
+// Rounds 1 .. max_rounds - 1 behind a round 0 whose records the caller holds in cells / n_cells.
+static int sic_rounds(lcs_ctx *c, const void *d_cap, int fmt, int n_buf, uint32_t n_cap, const double *f_search_set, uint16_t n_f,
+                      const double *fc_req, const double *fc_prog, double fs_prog, lcs_cell *cells, int max_cells, int *n_cells, int max_rounds,
+                      int mask, int32_t *round_of_cell, lcs_sic_info *info) {
+  int *st = c->sic.stats;
+  st[0] = 1; st[1] = st[2] = st[3] = 0;
+  int overflow = LCS_OK;
+  if (round_of_cell) std::fill(round_of_cell, round_of_cell + (size_t)n_buf * max_cells, 0);
+  lcs_sic_info none{};
+  none.ul_dl_config = LCS_TDD_NOT_ESTIMATED;
+  if (info) std::fill(info, info + (size_t)n_buf * max_cells, none);
+  std::vector<int> held(n_buf), active;
+  for (int b = 0; b < n_buf; ++b) { held[b] = std::min(n_cells[b], max_cells); if (held[b] > 0) active.push_back(b); }
+  // round 0's side tables belong to the caller's buffers as they are; later rounds' records are put in their cells' places
+  std::vector<lcs_tdd_info> &all_tdd = c->sic.h_tdd;
+  std::vector<lcs_meas_info> &all_meas = c->sic.h_meas;
+  c->sic.h_n_buf = n_buf; c->sic.h_max_cells = max_cells;
+  int rc0 = sic_read_side(c, n_buf, max_cells, &all_tdd, &all_meas);
+  if (rc0) return rc0;
+  for (int round = 1; round < max_rounds && !active.empty(); ++round) {
+    const int na = (int)active.size();
+    std::vector<lcs_cell> known((size_t)na * max_cells), found((size_t)na * max_cells);
+    std::vector<lcs_sic_info> inf((size_t)na * max_cells);
+    std::vector<int> nk(na), nf(na);
+    std::vector<int32_t> cfg((size_t)na * max_cells, LCS_TDD_NOT_ESTIMATED);
+    std::vector<lcs_tdd_info> r_tdd;
+    std::vector<lcs_meas_info> r_meas;
+    std::vector<double> fr(na), fp(na);
+    for (int a = 0; a < na; ++a) {
+      const int b = active[a];
+      nk[a] = held[b]; fr[a] = fc_req[b]; fp[a] = fc_prog[b];
+      std::copy(cells + (size_t)b * max_cells, cells + (size_t)b * max_cells + held[b], known.begin() + (size_t)a * max_cells);
+      for (int i = 0; i < held[b]; ++i) cfg[(size_t)a * max_cells + i] = all_tdd[(size_t)b * max_cells + i].ul_dl_config;
+    }
+    int rc = c->sic.res.reserve(c, (size_t)na * n_cap);
+    if (rc) return rc;
+    if ((rc = lcs_launch_sic(c, d_cap, fmt, na, n_cap, known.data(), nk.data(), max_cells, fr.data(), fp.data(), fs_prog, mask, c->duplex,
+                             active.data(), cfg.data(), c->sic.res, inf.data())))
+      return rc;
+    ++st[1];
+    rc = lcs_search_batch_dev(c, c->sic.res, LCS_FMT_C64, na, n_cap, f_search_set, n_f, fr.data(), fp.data(), fs_prog, LCS_STAGE_FULL, found.data(),
+                              max_cells, nf.data());
+    if (rc && rc != LCS_ERR_OVERFLOW) return rc;
+    ++st[0];
+    if ((rc = sic_read_side(c, na, max_cells, &r_tdd, &r_meas))) return rc;
+    std::vector<int> next;
+    for (int a = 0; a < na; ++a) {
+      const int b = active[a];
+      lcs_cell *mine = cells + (size_t)b * max_cells;
+      // the n_dup counts live in the caller's array across rounds; everything else of the record is this round's
+      for (int i = 0; i < held[b] && info; ++i) { const int32_t dup = info[(size_t)b * max_cells + i].n_dup; info[(size_t)b * max_cells + i] = inf[(size_t)a * max_cells + i]; info[(size_t)b * max_cells + i].n_dup = dup; }
+      int added = 0;
+      const int before = held[b];
+      for (int i = 0; i < std::min(nf[a], max_cells); ++i) {
+        const lcs_cell &f = found[(size_t)a * max_cells + i];
+        int listed = -1;
+        for (int k = 0; k < held[b]; ++k)
+          if (mine[k].n_id_1 == f.n_id_1 && mine[k].n_id_2 == f.n_id_2) listed = k;
+        if (listed >= 0) { ++st[3]; if (info) ++info[(size_t)b * max_cells + listed].n_dup; continue; }
+        if (held[b] >= max_cells) { overflow = LCS_ERR_OVERFLOW; continue; }
+        if (round_of_cell) round_of_cell[(size_t)b * max_cells + held[b]] = round;
+        all_tdd[(size_t)b * max_cells + held[b]] = r_tdd[(size_t)a * max_cells + i];
+        all_meas[(size_t)b * max_cells + held[b]] = r_meas[(size_t)a * max_cells + i];
+        mine[held[b]++] = f;
+        ++added; ++st[2];
+      }
+      n_cells[b] = std::max(n_cells[b], before) + added;
+      if (added) next.push_back(b);
+    }
+    active.swap(next);
+  }
+  if (overflow) c->err = "more results than the output array holds";
+  return overflow;
+}
+
+int lcs_search_capbuf_sic(lcs_ctx *c, const double *capbuf, uint32_t n_cap, const double *f_search_set, uint16_t n_f, double fc_req,
+                          double fc_prog, double fs_prog, lcs_cell *cells, int max_cells, int *n_cells, lcs_cell *peaks, int max_peaks,
+                          int *n_peaks, int max_rounds, int mask, int32_t *round_of_cell, lcs_sic_info *info) {
+  int rc = sic_check(c, LCS_FMT_C64, 1, n_cap, mask);
+  if (rc) return rc;
+  if (max_rounds < 1 || max_rounds > LCS_SIC_MAX_ROUNDS || max_cells < 1) { c->err = "lcs_search_capbuf_sic: max_rounds 1 .. 4, max_cells >= 1"; return LCS_ERR_BAD_ARG; }
+  rc = lcs_search_capbuf(c, capbuf, n_cap, f_search_set, n_f, fc_req, fc_prog, fs_prog, cells, max_cells, n_cells, peaks, max_peaks, n_peaks);
+  if (rc) return rc;
+  if (max_rounds > 1 && *n_cells > 0) {      // the capture as complex<float> (exact for dongle data) for the cancellation to read
+    std::vector<float2> h(n_cap);
+    for (uint32_t i = 0; i < n_cap; ++i) h[i] = make_float2((float)capbuf[2 * i], (float)capbuf[2 * i + 1]);
+    if ((rc = c->sic.cap.reserve(c, n_cap))) return rc;
+    HIPCHK(c, hipMemcpy(c->sic.cap.get(), h.data(), (size_t)n_cap * sizeof(float2), hipMemcpyHostToDevice));
+  }
+  return sic_rounds(c, c->sic.cap, LCS_FMT_C64, 1, n_cap, f_search_set, n_f, &fc_req, &fc_prog, fs_prog, cells, max_cells, n_cells, max_rounds, mask,
+                    round_of_cell, info);
+}
+
+int lcs_search_batch_sic_dev(lcs_ctx *c, const void *d_capbufs, int fmt, int n_buf, uint32_t n_cap, const double *f_search_set, uint16_t n_f,
+                             const double *fc_requested, const double *fc_programmed, double fs_programmed, lcs_cell *cells,
+                             int max_cells_per_buf, int *n_cells, int max_rounds, int mask, int32_t *round_of_cell, lcs_sic_info *info) {
+  int rc = sic_check(c, fmt, n_buf, n_cap, mask);
+  if (rc) return rc;
+  if (max_rounds < 1 || max_rounds > LCS_SIC_MAX_ROUNDS || max_cells_per_buf < 1) { c->err = "lcs_search_batch_sic_dev: max_rounds 1 .. 4, max_cells_per_buf >= 1"; return LCS_ERR_BAD_ARG; }
+  rc = lcs_search_batch_dev(c, d_capbufs, fmt, n_buf, n_cap, f_search_set, n_f, fc_requested, fc_programmed, fs_programmed, LCS_STAGE_FULL, cells,
+                            max_cells_per_buf, n_cells);
+  if (rc) return rc;
+  return sic_rounds(c, d_capbufs, fmt, n_buf, n_cap, f_search_set, n_f, fc_requested, fc_programmed, fs_programmed, cells, max_cells_per_buf, n_cells,
+                    max_rounds, mask, round_of_cell, info);
+}
+
+int lcs_last_sic_stats(lcs_ctx *c, int stats[4]) {
+  if (!c || !stats) return LCS_ERR_BAD_ARG;
+  for (int i = 0; i < 4; ++i) stats[i] = c->sic.stats[i];
+  return LCS_OK;
+}
+
+int lcs_last_sic_tdd_info(lcs_ctx *c, lcs_tdd_info *info, int max_cells_per_buf) {
+  if (!c || !info) return LCS_ERR_BAD_ARG;
+  if (max_cells_per_buf != c->sic.h_max_cells || c->sic.h_n_buf < 1) { c->err = "lcs_last_sic_tdd_info: no lcs_search_*_sic call with this max_cells_per_buf"; return LCS_ERR_BAD_ARG; }
+  std::copy(c->sic.h_tdd.begin(), c->sic.h_tdd.end(), info);
+  return LCS_OK;
+}
+int lcs_last_sic_cell_meas(lcs_ctx *c, lcs_meas_info *info, int max_cells_per_buf) {
+  if (!c || !info) return LCS_ERR_BAD_ARG;
+  if (max_cells_per_buf != c->sic.h_max_cells || c->sic.h_n_buf < 1) { c->err = "lcs_last_sic_cell_meas: no lcs_search_*_sic call with this max_cells_per_buf"; return LCS_ERR_BAD_ARG; }
+  std::copy(c->sic.h_meas.begin(), c->sic.h_meas.end(), info);
+  return LCS_OK;
+}
+
+int lcs_table_pbch_symbols(int n_id_cell, int n_ports, int n_rb_dl, int phich_duration, int phich_resource, int sfn, int cp_type, double *out) {
+  if (!out || sfn < 0 || sfn > 1023) return LCS_ERR_BAD_ARG;
+  return lcs_tables::pbch_encode(n_id_cell, n_ports, n_rb_dl, phich_duration, phich_resource, sfn, cp_type, out) ? LCS_OK : LCS_ERR_BAD_ARG;
+}
+
 // ------------------------------------------------------------------- one buffer, hypotheses split over GPUs
 // SURVEY 8e "latency mode": every rank correlates its contiguous share of f_search_set; the shares meet where the
 // reference takes the maximum over the frequency axis (src/searcher.cpp:369-382).  RCCL has no arg-max: the collapsed

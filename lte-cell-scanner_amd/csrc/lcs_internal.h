@@ -570,6 +570,24 @@ struct lcs_ctx : lcs_ctx_queues {
     DevBuf<float2> cap;             // [n_ch][n_cap], and one sample of padding (k_chan_cap_power)
     DevBuf<float> cap_part;         // [n_ch][cap_power_blocks(n_cap)] sums of |y|^2 (k_chan_cap_power)
   } chan_stream;
+  // the cancellation stage (sic.hip): every block is allocated by the first call that needs it and grown on demand
+  struct Sic {
+    DevBuf<char> cells;             // [n] SicCell records of the call, then [n_buf][2] first cell / cell count per buffer
+    DevBuf<float2> pbch;            // [n][SIC_MAX_FRAMES][240]: the PBCH symbols of every frame of every cell
+    DevBuf<double2> grid, grid_res; // [symbols of all cells][72]: the capture's grid, and the residual's
+    DevBuf<double2> chan;           // [slots of all cells][4][72]
+    DevBuf<double2> gain;           // [n]
+    DevBuf<float2> td;              // [symbols of all cells][128]: what each symbol subtracts, before the carrier rotation
+    DevBuf<double> part;            // [symbols of all cells][4]: energy per component
+    DevBuf<lcs_sic_info> info;      // [n]
+    DevBuf<float2> cap, res;        // lcs_search_*_sic: the single-buffer call's capture as complex<float>, and the residuals
+    int stats[4] = {0, 0, 0, 0};    // lcs_last_sic_stats
+    // lcs_search_*_sic: the side-table records of every cell the call handed out, gathered round by round on the host
+    // (lcs_last_sic_tdd_info, lcs_last_sic_cell_meas), [h_n_buf][h_max_cells]
+    std::vector<lcs_tdd_info> h_tdd;
+    std::vector<lcs_meas_info> h_meas;
+    int h_n_buf = 0, h_max_cells = 0;
+  } sic;
   // results of a batch, compacted on the device (k_pack_results): [8 ints header][n_buf counts][records]; h_res = its page-locked mirror
   DevBuf<char> res_pack;
   PinnedBuf<char> h_res;
@@ -657,7 +675,16 @@ void pn_jump_table(uint32_t steps, uint32_t out[32]);
 double chi2cdf_inv(double p, double k);
 void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.cpp:409-463 via :473-478
 bool pbch_derm_inv(int n_e, int16_t *out /*[120][16]*/);    // its inverse: per coded bit the positions carrying it (ascending, -1 padded)
+// lte_pbch_enc.cpp: the QPSK symbols of one PBCH period from a record's fields (960 / 864 pairs); false: no MIB carries them
+bool pbch_encode(int n_id_cell, int n_ports, int n_rb_dl, int phich_duration, int phich_resource, int sfn, int cp_type, double *out_re_im);
 }  // namespace lcs_tables
+
+// sic.hip: the cancellation of `cells` (records of buffer b at cells[b * max_cells_per_buf], n_cells_per_buf[b] of them) from the
+// n_buf captures at d_cap (fmt U8 / C64) into d_res [n_buf][n_cap]; src_of (nullable: the identity): the capture of d_cap that slot b --
+// its records, its carrier, its residual -- belongs to
+int lcs_launch_sic(lcs_ctx *c, const void *d_cap, int fmt, int n_buf, uint32_t n_cap, const lcs_cell *cells, const int *n_cells_per_buf,
+                   int max_cells_per_buf, const double *fc_req, const double *fc_prog, double fs_prog, int mask, int duplex, const int *src_of,
+                   const int32_t *ul_dl_config /*like cells, nullable: the TDD cells' configurations, < 0 where there is none*/, float2 *d_res, lcs_sic_info *info);
 
 // ---- kernel launchers (one per .hip file) -------------------------------------------
 // pss_xcorr.hip

@@ -118,7 +118,8 @@ def meas_with_gain(meas_per_carrier, gain) -> list:
 
 
 def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float, decim: int, fc_centre: float, carriers, f_search_set,
-                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64", meas: bool = False):
+                    n_out: int = None, chunk: int = 128, max_cells_per_buf: int = 16, rate=None, out: str = "c64", meas: bool = False,
+                    sic_rounds: int = 0):
     """A band search from ONE wideband capture resident in HBM (n_in samples of fmt at fs_in, centred on fc_centre): the
     carriers (absolute Hz, e.g. fc_search_set(...)) are channelized `chunk` at a time (Searcher.channelize: mix, low-pass,
     decimate by decim) into a torch buffer this function owns, and every chunk goes through the full chain as a
@@ -137,7 +138,11 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
     per carrier, in the order of `carriers`: ``dedup([[record_to_dict(r) for r in cells_to_records(c)] for c in result])`` merges them as a sweep's.
     meas=True turns Searcher.set_cell_meas on for these batches (and puts the mode back afterwards) and returns the cells as
     record_to_dict dicts instead, each with its measurement (capi.CellMeas) as cell["meas"]; with out="u8" the measurement and
-    pss_pow are already on one power scale over the carriers (meas_with_gain, records_with_gain)."""
+    pss_pow are already on one power scale over the carriers (meas_with_gain, records_with_gain).
+    sic_rounds=N (2..4; 0, the default, and 1: the search as it always was) runs every chunk through Searcher.search_batch_sic with
+    max_rounds=N instead: after each round the decoded cells' PSS, SSS, CRS and PBCH are subtracted from their carrier's buffer and the
+    residual is searched again; the function then returns (cells, rounds): per carrier the cells and the round each was found in
+    (0: the plain search).  Not together with meas (the measurement belongs to one fused call, the rounds are several)."""
     import torch
     from . import capi
     carriers = np.ascontiguousarray(np.atleast_1d(carriers), np.float64)
@@ -158,7 +163,18 @@ def search_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: float
         buf, batch_fmt, channelize = torch.empty((chunk, int(n_out), 2), dtype=torch.uint8, device=tdev), capi.FMT_IQ_U8, searcher.channelize_u8
     else:
         buf, batch_fmt, channelize = torch.empty((chunk, int(n_out)), dtype=torch.complex64, device=tdev), capi.FMT_C64, searcher.channelize_rational
-    cells = []
+    cells, all_rounds = [], []
+    if int(sic_rounds) > 1:
+        if meas:
+            raise ValueError("search_wideband: sic_rounds and meas do not go together")
+        for a in range(0, carriers.size, chunk):
+            fc = carriers[a:a + chunk]
+            channelize(d_wide_ptr, fmt, n_in, fs_in, up, down, fc - float(fc_centre), buf.data_ptr(), n_out)
+            found, rounds, _ = searcher.search_batch_sic(buf.data_ptr(), batch_fmt, fc.size, int(n_out), f_search_set, fc, fc, fs_out,
+                                                         max_rounds=int(sic_rounds), max_cells_per_buf=max_cells_per_buf)
+            cells += found
+            all_rounds += rounds
+        return cells, all_rounds
     if not meas:
         for a in range(0, carriers.size, chunk):
             fc = carriers[a:a + chunk]
