@@ -32,6 +32,11 @@ class SearcherError(RuntimeError):
     pass
 
 
+def _ref(rec):
+    """a ctypes record by reference; None: a null pointer"""
+    return None if rec is None else C.byref(rec)
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
@@ -558,45 +563,53 @@ class Searcher:
             raise ValueError("a device pointer needs n_cap")
         return int(d_capbuf), int(n_cap)
 
+    def _wide_args(self, cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm):
+        """the arguments every entry point on device samples starts with: the context, the cell, the samples, the frequencies, the
+        grid's shape"""
+        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        return (self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed), float(fs_programmed), int(n_fft), int(n_rb),
+                int(n_ofdm))
+
+    def _grid_args(self, cell, tfg_wide, n_rb):
+        """the same for the entry points on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex"""
+        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
+        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
+            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        return (self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb))
+
     def extract_tfg_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, n_cap=None):
         """The grid of a cell over n_rb resource blocks from complex64 samples at fs_programmed = 15 kHz x n_fft that are on the
         device, centred on the cell (a channel of channelize at decim = K / R): n_fft = 128 R, R in 1, 2, 4, 8, 16; cell.frame_start
         counts in those samples.  -> (tfg [n_ofdm][12 n_rb] complex128, the rows' ideal locations [n_ofdm])."""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
         tfg = np.empty((max(int(n_ofdm), 0), 12 * max(int(n_rb), 0)), np.complex128)
         ts = np.empty(max(int(n_ofdm), 0))
-        self._chk(self._lib.lcs_extract_tfg_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                                 float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), _dp(tfg), _dp(ts)), "lcs_extract_tfg_wide")
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
+        self._chk(self._lib.lcs_extract_tfg_wide(*args, _dp(tfg), _dp(ts)), "lcs_extract_tfg_wide")
         return tfg, ts
 
     def cell_meas_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
                        n_cap=None):
         """RSRP, RSSI, RSRQ and the noise power over n_rb resource blocks, with the per-RB profile, from the same samples
         (lcs_cell_meas_wide: only port 0's reference rows are transformed) -> CellMeasWide"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
         out = capi.CellMeasWide()
-        self._chk(self._lib.lcs_cell_meas_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                               float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(out)), "lcs_cell_meas_wide")
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
+        self._chk(self._lib.lcs_cell_meas_wide(*args, int(dl_mask), C.byref(out)), "lcs_cell_meas_wide")
         return out
 
     def pcfich_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
                     n_cap=None):
         """The control format indicator of every downlink subframe from the same samples (lcs_pcfich_wide: only symbol 0 of every
         subframe of the mask is transformed, and symbol 1 for a 4-port cell); n_rb is the cell's bandwidth -> PcfichInfo"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
         out = capi.PcfichInfo()
-        self._chk(self._lib.lcs_pcfich_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                            float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(out)), "lcs_pcfich_wide")
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
+        self._chk(self._lib.lcs_pcfich_wide(*args, int(dl_mask), C.byref(out)), "lcs_pcfich_wide")
         return out
 
     def pcfich(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF):
         """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
         (extract_tfg_wide's) (lcs_pcfich) -> PcfichInfo"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
         out = capi.PcfichInfo()
-        self._chk(self._lib.lcs_pcfich(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(out)), "lcs_pcfich")
+        self._chk(self._lib.lcs_pcfich(*self._grid_args(cell, tfg_wide, n_rb), int(dl_mask), C.byref(out)), "lcs_pcfich")
         return out
 
     @staticmethod
@@ -609,23 +622,20 @@ class Searcher:
         """The DCIs of the PDCCH common search space (SI, paging, random-access responses) of every downlink subframe from the same
         samples (lcs_pdcch_wide: symbols 0 .. 2 of every subframe of the mask are transformed, 0 .. 3 up to 10 resource blocks; the
         CFI is the PCFICH's, decided on the device).  cfg: a capi.PdcchCfg; None = FDD defaults -> PdcchInfo"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out = capi.PdcchInfo()
-        self._chk(self._lib.lcs_pdcch_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_wide")
+        self._chk(self._lib.lcs_pdcch_wide(*args, int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_wide")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
 
     def pdcch(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
         """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
         (extract_tfg_wide's) (lcs_pdcch) -> PdcchInfo"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        args = self._grid_args(cell, tfg_wide, n_rb)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out = capi.PdcchInfo()
-        self._chk(self._lib.lcs_pdcch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch")
+        self._chk(self._lib.lcs_pdcch(*args, int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
 
@@ -634,24 +644,21 @@ class Searcher:
         """The blind search of every CCE of every downlink subframe from the same samples (lcs_pdcch_scan_wide): the grants the cell
         gives to its users, their RNTIs and the CCEs they cover.  cfg: a capi.PdcchScanCfg (its sizes have no default: capi.dci_ue_sizes
         names the formats' for a cell) -> PdcchScanInfo"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
         if cfg is None:
             raise ValueError("pdcch_scan_wide needs a capi.PdcchScanCfg")
         out = capi.PdcchScanInfo()
-        self._chk(self._lib.lcs_pdcch_scan_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                                float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan_wide")
+        self._chk(self._lib.lcs_pdcch_scan_wide(*args, int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan_wide")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
 
     def pdcch_scan(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
         """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex (lcs_pdcch_scan) -> PdcchScanInfo"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        args = self._grid_args(cell, tfg_wide, n_rb)
         if cfg is None:
             raise ValueError("pdcch_scan needs a capi.PdcchScanCfg")
         out = capi.PdcchScanInfo()
-        self._chk(self._lib.lcs_pdcch_scan(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan")
+        self._chk(self._lib.lcs_pdcch_scan(*args, int(dl_mask), C.byref(cfg), C.byref(out)), "lcs_pdcch_scan")
         out.sizes = tuple(cfg.size[:cfg.n_sizes])
         return out
 
@@ -671,11 +678,9 @@ class Searcher:
         (lcs_phich_wide: symbol 0 of every subframe read is transformed, symbol 1 too with 4 ports, symbols 0 .. 2 at the extended
         PHICH duration; no CFI is needed).  cfg: a capi.PhichCfg; None = the cell's PHICH configuration, FDD, the default thresholds
         -> PhichInfo"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
         out = capi.PhichInfo()
-        self._chk(self._lib.lcs_phich_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)),
-                  "lcs_phich_wide")
+        self._chk(self._lib.lcs_phich_wide(*args, int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)), "lcs_phich_wide")
         out.tdd = cfg is not None and cfg.tdd
         self._phich_cp_normal = int(cell.cp_type) == 1      # the shape of phich_values' table
         return out
@@ -683,12 +688,9 @@ class Searcher:
     def phich(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None):
         """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
         (extract_tfg_wide's) (lcs_phich) -> PhichInfo"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        args = self._grid_args(cell, tfg_wide, n_rb)
         out = capi.PhichInfo()
-        self._chk(self._lib.lcs_phich(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)),
-                  "lcs_phich")
+        self._chk(self._lib.lcs_phich(*args, int(dl_mask), None if cfg is None else C.byref(cfg), C.byref(out)), "lcs_phich")
         out.tdd = cfg is not None and cfg.tdd
         self._phich_cp_normal = int(cell.cp_type) == 1      # the shape of phich_values' table
         return out
@@ -709,26 +711,19 @@ class Searcher:
         downlink subframe from the same samples (lcs_pdsch_wide: every row of the subframes of the mask is transformed; PCFICH,
         PDCCH, the grants' soft bits and the turbo decoder run on the device).  cfg: a capi.PdcchCfg as pdcch_wide's; pdsch_cfg: a
         capi.PdschCfg or None -> PdschInfo, or (PdschInfo, PdcchInfo) with want_pdcch"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out, pd = capi.PdschInfo(), capi.PdcchInfo()
-        self._chk(self._lib.lcs_pdsch_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                           float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg),
-                                           C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None), "lcs_pdsch_wide")
-        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        self._chk(self._lib.lcs_pdsch_wide(*args, int(dl_mask), *self._pdsch_own(cfg, pdsch_cfg, out, pd, want_pdcch)), "lcs_pdsch_wide")
         return (out, pd) if want_pdcch else out
 
     def pdsch(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None, pdsch_cfg=None, want_pdcch: bool = False):
         """The same stage on a grid from the host, tfg_wide [n_ofdm][12 n_rb] complex whose row 0 is symbol 0 of slot 0 of a frame
         (extract_tfg_wide's) (lcs_pdsch) -> PdschInfo, or (PdschInfo, PdcchInfo) with want_pdcch"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        args = self._grid_args(cell, tfg_wide, n_rb)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out, pd = capi.PdschInfo(), capi.PdcchInfo()
-        self._chk(self._lib.lcs_pdsch(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg),
-                                      C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None), "lcs_pdsch")
-        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        self._chk(self._lib.lcs_pdsch(*args, int(dl_mask), *self._pdsch_own(cfg, pdsch_cfg, out, pd, want_pdcch)), "lcs_pdsch")
         return (out, pd) if want_pdcch else out
 
     def pdsch_comb_wide(self, cell, d_capbuf, fc_requested, fc_programmed, fs_programmed, n_fft: int, n_rb: int, n_ofdm: int, dl_mask: int = 0x3FF,
@@ -737,29 +732,28 @@ class Searcher:
         is decoded from the sum of its members' soft bits, on the device (lcs_pdsch_comb_wide; the rule: include/lcs.h,
         lcs_pdsch_comb_info).  comb_cfg: a capi.PdschCombCfg or None (SIB1 rule on, SI windows off)
         -> (PdschInfo, PdschCombInfo), or (PdschInfo, PdschCombInfo, PdcchInfo) with want_pdcch"""
-        ptr, n_cap = self._wide_samples(d_capbuf, n_cap)
+        args = self._wide_args(cell, d_capbuf, n_cap, fc_requested, fc_programmed, fs_programmed, n_fft, n_rb, n_ofdm)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out, pd, comb = capi.PdschInfo(), capi.PdcchInfo(), capi.PdschCombInfo()
-        self._chk(self._lib.lcs_pdsch_comb_wide(self._h, C.byref(cell), C.c_void_p(ptr), n_cap, float(fc_requested), float(fc_programmed),
-                                                float(fs_programmed), int(n_fft), int(n_rb), int(n_ofdm), int(dl_mask), C.byref(cfg),
-                                                C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None,
-                                                C.byref(comb_cfg) if comb_cfg is not None else None, C.byref(comb)), "lcs_pdsch_comb_wide")
-        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        own = self._pdsch_own(cfg, pdsch_cfg, out, pd, want_pdcch)
+        self._chk(self._lib.lcs_pdsch_comb_wide(*args, int(dl_mask), *own, _ref(comb_cfg), C.byref(comb)), "lcs_pdsch_comb_wide")
         return (out, comb, pd) if want_pdcch else (out, comb)
 
     def pdsch_comb(self, cell, tfg_wide, n_rb: int, dl_mask: int = 0x3FF, cfg=None, pdsch_cfg=None, comb_cfg=None, want_pdcch: bool = False):
         """The same on a grid from the host as pdsch takes it (lcs_pdsch_comb)
         -> (PdschInfo, PdschCombInfo), or (PdschInfo, PdschCombInfo, PdcchInfo) with want_pdcch"""
-        tfg = np.ascontiguousarray(tfg_wide, np.complex128)
-        if tfg.ndim != 2 or tfg.shape[1] != 12 * int(n_rb):
-            raise ValueError("tfg_wide is [n_ofdm][12 n_rb]")
+        args = self._grid_args(cell, tfg_wide, n_rb)
         cfg = self._pdcch_cfg(cfg, n_rb)
         out, pd, comb = capi.PdschInfo(), capi.PdcchInfo(), capi.PdschCombInfo()
-        self._chk(self._lib.lcs_pdsch_comb(self._h, C.byref(cell), _dp(tfg), int(tfg.shape[0]), int(n_rb), int(dl_mask), C.byref(cfg),
-                                           C.byref(pdsch_cfg) if pdsch_cfg is not None else None, C.byref(out), C.byref(pd) if want_pdcch else None,
-                                           C.byref(comb_cfg) if comb_cfg is not None else None, C.byref(comb)), "lcs_pdsch_comb")
-        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        own = self._pdsch_own(cfg, pdsch_cfg, out, pd, want_pdcch)
+        self._chk(self._lib.lcs_pdsch_comb(*args, int(dl_mask), *own, _ref(comb_cfg), C.byref(comb)), "lcs_pdsch_comb")
         return (out, comb, pd) if want_pdcch else (out, comb)
+
+    @staticmethod
+    def _pdsch_own(cfg, pdsch_cfg, out, pd, want_pdcch):
+        """what the four PDSCH entries take behind the mask: the two configurations and the two records (the PDCCH's only on demand)"""
+        pd.sizes = tuple(cfg.size[:cfg.n_sizes])
+        return C.byref(cfg), _ref(pdsch_cfg), C.byref(out), C.byref(pd) if want_pdcch else None
 
     def pdsch_last_soft(self, subframe: int, which: int, n: int):
         """the first n soft bits of the which-th grant the last pdsch / pdsch_wide call followed in grid subframe `subframe`

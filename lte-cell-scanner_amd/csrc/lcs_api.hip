@@ -17,6 +17,7 @@
 #include "pdcch.h"
 #include "pdcch_scan.h"
 #include "phich.h"
+#include "wide_call.h"
 #include "pdsch.h"
 #include "tfg_layout.h"
 #include "pss_ref.h"
@@ -856,9 +857,7 @@ int n_ofdm_for(const lcs_cell *cell) {
   return cell->cp_type == LCS_CP_NORMAL ? 854 : (cell->cp_type == LCS_CP_EXTENDED ? 732 : -1);
 }
 // a cell with n_id_1 in 0 .. 167, n_id_2 in 0 .. 2 and a known cp_type
-bool cell_identified(const lcs_cell *cell) {
-  return n_ofdm_for(cell) >= 0 && cell->n_id_1 >= 0 && cell->n_id_1 <= 167 && cell->n_id_2 >= 0 && cell->n_id_2 <= 2;
-}
+bool cell_identified(const lcs_cell *cell) { return wide_cell_identified(cell); }
 // What the stages that take the caller's grid share: the workspace, the one-cell work list, the grid in `dst` (c->tfg: in the
 // chain's raw grid's place, c->tfg_comp: in the compensated one's) and the cell's RS_DL table (k_cell_prep).  *L: the launch of
 // the stage's own kernels.
@@ -1081,26 +1080,62 @@ int lcs_cell_meas(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofd
   return read_dbg_record(c, out, sizeof(*out));
 }
 
-// ---- the full-bandwidth grid and measurement (tfg_wide.hip, cell_meas_wide.h).  They touch the context's stream and the blocks of
-// c->meas_wide and nothing else: no workspace, no mode, no table of a fused call -- so they run beside an open stream as well.
+// ---- the stages on the full-bandwidth grid (tfg_wide.hip, cell_meas_wide.h, pcfich.hip, pdcch.hip, pdcch_scan.hip, phich.hip,
+// pdsch.hip; what they refuse and plan alike: wide_call.h).  They touch the context's stream, the blocks of c->meas_wide and their own
+// and nothing else: no workspace, no mode, no table of a fused call -- so they run beside an open stream as well.
 namespace {
 int wide_refused(lcs_ctx *c, const char *who, const char *what) {
   c->err = std::string(who) + ": " + what;
   return LCS_ERR_BAD_ARG;
 }
-// What the two entry points refuse alike, then extract_tfg's walk (ref src/searcher.cpp:875-920) with the caller's rate: ts[t] = the
-// ideal location of row t; *kk = the frequency correction's phase step in half turns per sample (fshift, ref dsp.h:40-53)
-int wide_rows(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_cap, double fc_req, double fc_prog, double fs_prog, int n_fft,
-              int n_rb, int n_ofdm, std::vector<double> *ts, double *kk) {
-  if (!cell || !d_cap) return wide_refused(c, who, "a null pointer");
-  if (reinterpret_cast<uintptr_t>(d_cap) & 7) return wide_refused(c, who, "d_capbuf is not aligned to a complex<float>");
-  if (measw_log2r(n_fft) < 0) return wide_refused(c, who, "n_fft is not 128, 256, 512, 1024 or 2048");
-  if (!(fabs(fs_prog / (15000.0 * n_fft) - 1.0) < 1e-3)) return wide_refused(c, who, "fs_programmed is not 15 kHz x n_fft to within 1e-3");
-  if (!measw_rb_ok(n_fft, n_rb)) return wide_refused(c, who, "n_rb is outside 6 .. {6, 15, 25, 50, 100} for n_fft = 128 {1, 2, 4, 8, 16}");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  const double k_factor = (fc_req - cell->freq_fine) / fc_prog;
+// where a call's grid comes from: complex<float> samples on the device, of which the rows it needs are transformed, or the whole grid
+// [n_ofdm][12 n_rb] from the host
+struct WideSource {
+  bool samples;
+  const void *d_capbuf; uint32_t n_cap; double fc_req, fc_prog, fs_prog; int n_fft;
+  const double *tfg;
+};
+WideSource wide_samples(const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog, int n_fft) {
+  return WideSource{true, d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft, nullptr};
+}
+WideSource wide_host_grid(const double *tfg) { return WideSource{false, nullptr, 0, 0.0, 0.0, 0.0, 0, tfg}; }
+// what wide_begin leaves for the plan and for wide_fill_grid.  Of samples: ts[t] = the ideal location of row t, kk = the frequency
+// correction's phase step in half turns per sample (fshift, ref dsp.h:40-53); ideal[0 .. n_ideal - 1]: the locations of the rows a
+// transform is asked for.  The plan of a stage: need, first, rows and n_sf as wide_plan_rows gives them.
+struct WideCall {
+  int n_symb = 0;
+  bool samples = false, device_set = false;
+  std::vector<double> ts, gathered;
+  double kk = 0.0;
+  const double *ideal = nullptr;
+  size_t n_ideal = 0;
+  int n_sf = 0, need[PCF_MAX_SF], first[PCF_MAX_SF], rows[4 * PCF_MAX_SF];
+  // need -> first, rows, n_sf; of samples also the locations of the planned rows (one block for the list, one for the locations)
+  void plan(int n_ofdm, int keep, int rec) {
+    std::vector<int> list;
+    if (samples) {
+      size_t n = 0;
+      for (int g = 0; g < pcf_n_sf(n_ofdm, n_symb); ++g) n += (size_t)need[g];
+      list.reserve(n);
+    }
+    n_sf = wide_plan_rows(n_symb, n_ofdm, keep, rec, need, rows, first, samples ? &list : nullptr);
+    gathered.resize(list.size());
+    for (size_t i = 0; i < list.size(); ++i) gathered[i] = ts[(size_t)list[i]];
+    ideal = gathered.data(); n_ideal = gathered.size();
+  }
+};
+// What the sample entries refuse alike, then extract_tfg's walk (ref src/searcher.cpp:875-920) with the caller's rate
+int wide_rows(lcs_ctx *c, const char *who, const lcs_cell *cell, const WideSource &s, int n_rb, int n_ofdm, WideCall *w) {
+  const char *what;
+  if (!cell || !s.d_capbuf) return wide_refused(c, who, "a null pointer");
+  if (reinterpret_cast<uintptr_t>(s.d_capbuf) & 7) return wide_refused(c, who, "d_capbuf is not aligned to a complex<float>");
+  if (measw_log2r(s.n_fft) < 0) return wide_refused(c, who, "n_fft is not 128, 256, 512, 1024 or 2048");
+  if (!(fabs(s.fs_prog / (15000.0 * s.n_fft) - 1.0) < 1e-3)) return wide_refused(c, who, "fs_programmed is not 15 kHz x n_fft to within 1e-3");
+  if (!measw_rb_ok(s.n_fft, n_rb)) return wide_refused(c, who, "n_rb is outside 6 .. {6, 15, 25, 50, 100} for n_fft = 128 {1, 2, 4, 8, 16}");
+  if ((what = wide_refuse_cell(cell))) return wide_refused(c, who, what);
+  const int n_symb = w->n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+  if ((what = wide_refuse_n_ofdm(n_ofdm, n_symb))) return wide_refused(c, who, what);
+  const double fs_prog = s.fs_prog, k_factor = (s.fc_req - cell->freq_fine) / s.fc_prog;
   double loc;
   if (cell->cp_type == LCS_CP_NORMAL) loc = cell->frame_start + 10 * 16 / FS_LTE * fs_prog * k_factor;
   else loc = cell->frame_start + 32 * 16 / FS_LTE * fs_prog * k_factor;
@@ -1108,251 +1143,163 @@ int wide_rows(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_c
   const double inc_ext = (128 + 32) * 16 / FS_LTE * fs_prog * k_factor;
   const double inc_10 = (128 + 10) * 16 / FS_LTE * fs_prog * k_factor;
   const double inc_9 = (128 + 9) * 16 / FS_LTE * fs_prog * k_factor;
-  ts->resize((size_t)n_ofdm);
+  w->ts.resize((size_t)n_ofdm);
   int sym_num = 0;
   for (int t = 0; t < n_ofdm; ++t) {
-    (*ts)[t] = loc;
+    w->ts[t] = loc;
     if (n_symb == 6) loc += inc_ext;
     else { loc += (sym_num == 6) ? inc_10 : inc_9; sym_num = (sym_num + 1) % 7; }
   }
-  *kk = (-cell->freq_fine) / ((fs_prog * k_factor) / 2);
-  if (!std::isfinite((*ts)[0]) || !std::isfinite((*ts)[(size_t)n_ofdm - 1]) || !std::isfinite(*kk))
+  w->kk = (-cell->freq_fine) / ((fs_prog * k_factor) / 2);
+  if (!std::isfinite(w->ts[0]) || !std::isfinite(w->ts[(size_t)n_ofdm - 1]) || !std::isfinite(w->kk))
     return wide_refused(c, who, "the cell's frame_start / freq_fine and the frequencies give no finite positions");
   return LCS_OK;
 }
-// every requested row inside the capture: the locations grow, so the first and the last decide
-int wide_rows_fit(lcs_ctx *c, const char *who, const std::vector<double> &ideal, int n_fft, uint32_t n_cap) {
-  const double first = rint(ideal.front()), last = rint(ideal.back());
-  if (first < 0.0) return wide_refused(c, who, "the first requested row starts before sample 0 of the capture");
-  if (last + (double)n_fft > (double)n_cap) return wide_refused(c, who, "the capture does not hold the last requested row (round_i(location) + n_fft > n_cap)");
+// The refusals every entry point shares, in one order for both sources: the record `out`, the source's own, the cell, n_ofdm; then
+// the mask (dl_mask null: the entry takes none) and, for the stages that decode (lte_rb), the bandwidth.  Nothing is launched.
+int wide_begin(lcs_ctx *c, const char *who, const WideSource &s, const lcs_cell *cell, const void *out, int n_rb, int n_ofdm, const int *dl_mask, bool lte_rb,
+               WideCall *w) {
+  if (!c) return LCS_ERR_BAD_ARG;
+  if (!out) return wide_refused(c, who, "a null pointer");
+  const char *what;
+  int rc;
+  w->samples = s.samples;
+  if (s.samples) {
+    if ((rc = wide_rows(c, who, cell, s, n_rb, n_ofdm, w))) return rc;
+  } else {
+    if (!cell || !s.tfg) return wide_refused(c, who, "a null pointer");
+    if ((what = wide_refuse_cell(cell))) return wide_refused(c, who, what);
+    w->n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
+    if ((what = wide_refuse_n_ofdm(n_ofdm, w->n_symb))) return wide_refused(c, who, what);
+  }
+  if (dl_mask && (what = wide_refuse_mask(*dl_mask))) return wide_refused(c, who, what);
+  if (lte_rb && (what = wide_refuse_rb(cell->n_rb_dl, n_rb))) return wide_refused(c, who, what);
+  static_assert(122 * 7 <= LCS_TFG_MAX_OFDM && 61 <= PCF_MAX_SF, "the subframes of 122 slots fit the records");
+  return LCS_OK;
+}
+// The rows of the call into c->meas_wide.grid.  Samples: the rows at w.ideal, which must all lie inside the capture -- the locations
+// grow, so the first and the last decide -- (none: nothing to transform); a host grid: all of it.
+int wide_fill_grid(lcs_ctx *c, const char *who, const WideSource &s, const WideCall &w, int n_rb, int n_ofdm) {
+  if (s.samples && w.n_ideal) {
+    if (rint(w.ideal[0]) < 0.0) return wide_refused(c, who, "the first requested row starts before sample 0 of the capture");
+    if (rint(w.ideal[w.n_ideal - 1]) + (double)s.n_fft > (double)s.n_cap)
+      return wide_refused(c, who, "the capture does not hold the last requested row (round_i(location) + n_fft > n_cap)");
+  }
+  if (!w.device_set) HIPCHK(c, hipSetDevice(c->device));      // (the PHICH has set it for its tables)
+  if (!s.samples) return lcs_pcfich_stage_grid(c, s.tfg, (size_t)n_ofdm * 12 * n_rb);
+  if (!w.n_ideal) return LCS_OK;
+  return lcs_launch_tfg_wide(c, static_cast<const float2 *>(s.d_capbuf), s.n_cap, w.ideal, (int)w.n_ideal, w.kk, s.n_fft, n_rb);
+}
+// how a stage's record comes back
+int wide_read_record(lcs_ctx *c, void *out, const void *d_rec, size_t bytes) {
+  HIPCHK(c, hipMemcpyAsync(out, d_rec, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return LCS_OK;
 }
 }  // namespace
 
 int lcs_extract_tfg_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                          int n_fft, int n_rb, int n_ofdm, double *tfg, double *timestamp) {
-  if (!c) return LCS_ERR_BAD_ARG;
   static const char who[] = "lcs_extract_tfg_wide";
-  if (!tfg) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
+  const WideSource src = wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft);
+  WideCall w;
   int rc;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if ((rc = wide_rows_fit(c, who, ts, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ts.data(), n_ofdm, kk, n_fft, n_rb))) return rc;
+  if ((rc = wide_begin(c, who, src, cell, tfg, n_rb, n_ofdm, nullptr, false, &w))) return rc;
+  w.ideal = w.ts.data(); w.n_ideal = w.ts.size();      // every row
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
   HIPCHK(c, hipMemcpyAsync(tfg, c->meas_wide.grid, sizeof(double2) * (size_t)n_ofdm * 12 * n_rb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (timestamp) std::memcpy(timestamp, ts.data(), sizeof(double) * (size_t)n_ofdm);
+  if (timestamp) std::memcpy(timestamp, w.ts.data(), sizeof(double) * (size_t)n_ofdm);
   return LCS_OK;
 }
 
 int lcs_cell_meas_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                        int n_fft, int n_rb, int n_ofdm, int dl_mask, lcs_meas_wide_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
   static const char who[] = "lcs_cell_meas_wide";
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
+  const WideSource src = wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft);
+  WideCall w;
   int rc;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, false, &w))) return rc;
   // port 0's reference rows only: reference row q is row q of the device's grid
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_q = tdd_n_ref_rows(n_ofdm, n_symb);
+  const int n_q = tdd_n_ref_rows(n_ofdm, w.n_symb);
   static_assert(2 * 122 <= TC_MAX_Q, "the reference rows of 122 slots fit the per-row table");
-  std::vector<double> ideal((size_t)n_q);
-  for (int q = 0; q < n_q; ++q) ideal[q] = ts[(size_t)tdd_grid_row(q, n_symb)];
-  if ((rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), n_q, kk, n_fft, n_rb))) return rc;
+  w.gathered.resize((size_t)n_q);
+  for (int q = 0; q < n_q; ++q) w.gathered[q] = w.ts[(size_t)tdd_grid_row(q, w.n_symb)];
+  w.ideal = w.gathered.data(); w.n_ideal = w.gathered.size();
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
   if ((rc = lcs_launch_cell_meas_wide(c, *cell, n_q, n_fft, n_rb, dl_mask))) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, c->meas_wide.rec, sizeof(lcs_meas_wide_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
+  return wide_read_record(c, out, c->meas_wide.rec.get(), sizeof(*out));
 }
 
-// ---- the PCFICH on that grid (pcfich.hip, pcfich.h): the same blocks and the same isolation
+// ---- the PCFICH on that grid (pcfich.hip, pcfich.h).  Every stage below is one function over a WideSource -- begin, resolve, plan,
+// fill, launch, read -- and two entry points that name the source.
 namespace {
-// what both entry points refuse about n_rb beyond the measurement's range
-int pcfich_rb_refused(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb) {
-  if (!pcf_rb_ok(n_rb)) return wide_refused(c, who, "n_rb is not an LTE bandwidth (6, 15, 25, 50, 75 or 100)");
-  if (pcf_rb_ok(cell->n_rb_dl) && cell->n_rb_dl != n_rb) return wide_refused(c, who, "n_rb contradicts the cell's n_rb_dl");
-  return LCS_OK;
-}
-// rows[2 g], rows[2 g + 1] for every subframe of the grid: the rows themselves (list == nullptr: the whole grid is there), or their
-// places in *list, the rows a transform is asked for
-int pcfich_plan(const lcs_cell *cell, int n_ofdm, int dl_mask, int *rows, std::vector<int> *list) {
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, ports = pcf_ports(cell->n_ports), n_sf = pcf_n_sf(n_ofdm, n_symb);
-  for (int g = 0; g < n_sf; ++g) {
-    rows[2 * g] = rows[2 * g + 1] = -1;
-    if (!pcf_sf_used(g, n_ofdm, n_symb, ports, dl_mask)) continue;
-    for (int t = 0; t < (ports == 4 ? 2 : 1); ++t) {
-      const int r = 2 * g * n_symb + t;
-      if (list) { rows[2 * g + t] = (int)list->size(); list->push_back(r); }
-      else rows[2 * g + t] = r;
-    }
-  }
-  return n_sf;
-}
-int pcfich_finish(lcs_ctx *c, lcs_pcfich_info *out) {
-  HIPCHK(c, hipMemcpyAsync(out, c->meas_wide.pcf_rec, sizeof(lcs_pcfich_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
+int pcfich_call(lcs_ctx *c, const char *who, const WideSource &src, const lcs_cell *cell, int n_rb, int n_ofdm, int dl_mask, lcs_pcfich_info *out) {
+  WideCall w;
+  int rc;
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, true, &w))) return rc;
+  pcfich_need(w.n_symb, n_ofdm, pcf_ports(cell->n_ports), dl_mask, w.need);
+  w.plan(n_ofdm, 2, 2);
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
+  if ((rc = lcs_launch_pcfich(c, *cell, w.rows, w.n_sf, n_rb, dl_mask))) return rc;
+  return wide_read_record(c, out, c->meas_wide.pcf_rec.get(), sizeof(*out));
 }
 }  // namespace
 
 int lcs_pcfich_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                     int n_fft, int n_rb, int n_ofdm, int dl_mask, lcs_pcfich_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pcfich_wide";
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
-  int rc;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  static_assert(122 * 7 <= LCS_TFG_MAX_OFDM && 61 <= PCF_MAX_SF, "the subframes of 122 slots fit the record");
-  int rows[2 * PCF_MAX_SF];
-  std::vector<int> list;
-  const int n_sf = pcfich_plan(cell, n_ofdm, dl_mask, rows, &list);
-  std::vector<double> ideal(list.size());
-  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
-  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_pcfich(c, *cell, rows, n_sf, n_rb, dl_mask))) return rc;
-  return pcfich_finish(c, out);
+  return pcfich_call(c, "lcs_pcfich_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, out);
 }
-
 int lcs_pcfich(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, lcs_pcfich_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pcfich";
-  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  int rc;
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  int rows[2 * PCF_MAX_SF];
-  const int n_sf = pcfich_plan(cell, n_ofdm, dl_mask, rows, nullptr);
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_pcfich(c, *cell, rows, n_sf, n_rb, dl_mask))) return rc;
-  return pcfich_finish(c, out);
+  return pcfich_call(c, "lcs_pcfich", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, out);
 }
 
-// ---- the PDCCH common search space on that grid (pdcch.hip, pdcch.h): the same blocks and the same isolation
+// ---- the PDCCH common search space on that grid (pdcch.hip, pdcch.h)
 namespace {
 // what cfg and the cell say together, or the refusal
 int pdcch_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_pdcch_cfg *cfg, PdcchPlan *p) {
   if (!cfg) return wide_refused(c, who, "a null pointer");
-  p->phich_duration = cfg->phich_duration ? cfg->phich_duration : cell->phich_duration;
-  p->phich_resource = cfg->phich_resource ? cfg->phich_resource : cell->phich_resource;
-  if (p->phich_duration == 0 || p->phich_resource == 0) return wide_refused(c, who, "the PHICH configuration is unknown: neither cfg nor the cell says it");
-  if (p->phich_duration < 1 || p->phich_duration > 2) return wide_refused(c, who, "phich_duration is outside 1 (normal) .. 2 (extended)");
-  if (p->phich_resource < 1 || p->phich_resource > 4) return wide_refused(c, who, "phich_resource is outside 1 (Ng = 1/6) .. 4 (Ng = 2)");
-  if (cfg->n_sizes < 1 || cfg->n_sizes > LCS_PDCCH_MAX_SIZES) return wide_refused(c, who, "n_sizes is outside 1 .. 2");
+  const char *sizes = nullptr;
   p->n_sizes = cfg->n_sizes;
   p->size[0] = p->size[1] = 0;
-  for (int i = 0; i < cfg->n_sizes; ++i) {
-    if (cfg->size[i] < 8 || cfg->size[i] > 48) return wide_refused(c, who, "a payload size is outside 8 .. 48");
+  if (cfg->n_sizes < 1 || cfg->n_sizes > LCS_PDCCH_MAX_SIZES) sizes = "n_sizes is outside 1 .. 2";
+  for (int i = 0; !sizes && i < cfg->n_sizes; ++i) {
+    if (cfg->size[i] < 8 || cfg->size[i] > 48) sizes = "a payload size is outside 8 .. 48";
     p->size[i] = cfg->size[i];
   }
-  if (cfg->cfi_force < 0 || cfg->cfi_force > 3) return wide_refused(c, who, "cfi_force is outside 0 .. 3");
-  if (cfg->cfi_force && p->phich_duration == 2 && pdc_n_ctrl(cfg->cfi_force, n_rb) < 3)
-    return wide_refused(c, who, "the extended PHICH duration needs three control symbols: cfi_force gives fewer");
-  p->cfi_force = cfg->cfi_force;
-  for (int i = 0; i < 10; ++i) {
-    if (cfg->phich_mi[i] < -1 || cfg->phich_mi[i] > 2) return wide_refused(c, who, "an m_i is outside 0 .. 2 (-1: FDD's 1)");
-    p->mi[i] = cfg->phich_mi[i] < 0 ? 1 : cfg->phich_mi[i];
-  }
-  if (cfg->rnti_mask < 0 || cfg->rnti_mask > 7) return wide_refused(c, who, "rnti_mask is outside 0 .. 7");
-  p->rnti_mask = cfg->rnti_mask ? cfg->rnti_mask : 7;
-  return LCS_OK;
+  const char *what = wide_resolve_shared(cell->phich_duration, cell->phich_resource, cfg->phich_duration, cfg->phich_resource, cfg->phich_mi, cfg->rnti_mask,
+                                         cfg->cfi_force, n_rb, sizes, &p->sh);
+  return what ? wide_refused(c, who, what) : LCS_OK;
 }
-// rows4[4 g + l] for every subframe of the grid and l < 4, as pcfich_plan: a subframe is read when its bit of the mask is set and
-// its symbols 0 .. n_ctrl_max - 1 lie inside the grid; a TDD call (an m_i given) with the extended duration leaves out subframes 1, 6
-int pdcch_plan(const lcs_cell *cell, const lcs_pdcch_cfg *cfg, const PdcchPlan &p, int n_ofdm, int n_rb, int dl_mask, int *rows4, std::vector<int> *list) {
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_sf = pcf_n_sf(n_ofdm, n_symb), n_max = pdc_n_ctrl_max(n_rb);
-  bool tdd = false;
-  for (int i = 0; i < 10; ++i) tdd = tdd || cfg->phich_mi[i] >= 0;
-  for (int g = 0; g < n_sf; ++g) {
-    for (int l = 0; l < 4; ++l) rows4[4 * g + l] = -1;
-    const int r0 = 2 * g * n_symb, sf = g % 10;
-    if (!((dl_mask >> sf) & 1) || r0 + n_max - 1 >= n_ofdm) continue;
-    if (tdd && p.phich_duration == 2 && (sf == 1 || sf == 6)) continue;
-    for (int l = 0; l < n_max; ++l) {
-      if (list) { rows4[4 * g + l] = (int)list->size(); list->push_back(r0 + l); }
-      else rows4[4 * g + l] = r0 + l;
-    }
-  }
-  return n_sf;
-}
-int pdcch_finish(lcs_ctx *c, lcs_pdcch_info *out) {
-  HIPCHK(c, hipMemcpyAsync(out, c->pdcch.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
+int pdcch_call(lcs_ctx *c, const char *who, const WideSource &src, const lcs_cell *cell, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out) {
+  WideCall w;
+  PdcchPlan plan;
+  int rc;
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, true, &w)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  pdcch_need(w.n_symb, n_ofdm, n_rb, dl_mask, plan.sh, w.need);
+  w.plan(n_ofdm, 4, 4);
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
+  if ((rc = lcs_launch_pdcch(c, *cell, w.rows, w.n_sf, n_rb, dl_mask, plan))) return rc;
+  return wide_read_record(c, out, c->pdcch.rec.get(), sizeof(*out));
 }
 }  // namespace
 
 int lcs_pdcch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                    int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdcch_wide";
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
-  int rc;
-  PdcchPlan plan;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
-  int rows4[4 * PCF_MAX_SF];
-  std::vector<int> list;
-  const int n_sf = pdcch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, &list);
-  std::vector<double> ideal(list.size());
-  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
-  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
-  return pdcch_finish(c, out);
+  return pdcch_call(c, "lcs_pdcch_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
-
 int lcs_pdcch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, lcs_pdcch_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdcch";
-  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  int rc;
-  PdcchPlan plan;
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
-  int rows4[4 * PCF_MAX_SF];
-  const int n_sf = pdcch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, nullptr);
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_pdcch(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
-  return pdcch_finish(c, out);
+  return pdcch_call(c, "lcs_pdcch", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
 
-// ---- the blind search of every CCE on that grid (pdcch_scan.hip, pdcch_scan.h): the same blocks and the same isolation
+// ---- the blind search of every CCE on that grid (pdcch_scan.hip, pdcch_scan.h)
 namespace {
-// the PDCCH's refusals on the fields the two configurations share, then this stage's own
-int pdcch_scan_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_cfg *shared, PdcchPlan *pp, PdcchScanPlan *p) {
+// the refusals on the fields the configurations share, then this stage's own
+int pdcch_scan_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_pdcch_scan_cfg *cfg, PdcchScanPlan *p) {
   if (!cfg) return wide_refused(c, who, "a null pointer");
-  std::memset(shared, 0, sizeof(*shared));
-  shared->phich_duration = cfg->phich_duration; shared->phich_resource = cfg->phich_resource;
-  for (int i = 0; i < 10; ++i) shared->phich_mi[i] = cfg->phich_mi[i];
-  shared->n_sizes = 1; shared->size[0] = 8;                  // the sizes are this stage's own, checked below
-  shared->rnti_mask = cfg->rnti_mask; shared->cfi_force = cfg->cfi_force;
-  int rc;
-  if ((rc = pdcch_resolve(c, who, cell, n_rb, shared, pp))) return rc;
+  const char *what = wide_resolve_shared(cell->phich_duration, cell->phich_resource, cfg->phich_duration, cfg->phich_resource, cfg->phich_mi, cfg->rnti_mask,
+                                         cfg->cfi_force, n_rb, nullptr, &p->sh);
+  if (what) return wide_refused(c, who, what);
   if (cfg->n_sizes < 1 || cfg->n_sizes > LCS_PDCCH_SCAN_MAX_SIZES) return wide_refused(c, who, "n_sizes is outside 1 .. 6");
   for (int i = 0; i < LCS_PDCCH_SCAN_MAX_SIZES; ++i) p->size[i] = 0;
   for (int i = 0; i < cfg->n_sizes; ++i) {
@@ -1362,69 +1309,34 @@ int pdcch_scan_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_
   if (cfg->min_repeat < 1) return wide_refused(c, who, "min_repeat is below 1");
   if (!(cfg->min_quality >= 0.0 && cfg->min_quality <= 1.0)) return wide_refused(c, who, "min_quality is outside 0 .. 1");
   if (cfg->reserved[0] || cfg->reserved[1]) return wide_refused(c, who, "a reserved field is not zero");
-  p->phich_duration = pp->phich_duration; p->phich_resource = pp->phich_resource;
-  for (int i = 0; i < 10; ++i) p->mi[i] = pp->mi[i];
-  p->n_sizes = cfg->n_sizes; p->rnti_mask = pp->rnti_mask; p->cfi_force = pp->cfi_force;
-  p->min_repeat = cfg->min_repeat; p->min_quality = cfg->min_quality;
+  p->n_sizes = cfg->n_sizes; p->min_repeat = cfg->min_repeat; p->min_quality = cfg->min_quality;
   return LCS_OK;
 }
-int pdcch_scan_finish(lcs_ctx *c, int n_sf, int n_sizes, lcs_pdcch_scan_info *out) {
+int pdcch_scan_call(lcs_ctx *c, const char *who, const WideSource &src, const lcs_cell *cell, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_scan_cfg *cfg,
+                    lcs_pdcch_scan_info *out) {
+  WideCall w;
+  PdcchScanPlan plan;
+  int rc;
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, true, &w)) || (rc = pdcch_scan_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  pdcch_need(w.n_symb, n_ofdm, n_rb, dl_mask, plan.sh, w.need);
+  w.plan(n_ofdm, 4, 4);
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
+  if ((rc = lcs_launch_pdcch_scan(c, *cell, w.rows, w.n_sf, n_rb, dl_mask, plan))) return rc;
   lcs_ctx::PdcchScan &p = c->pdcch_scan;
-  HIPCHK(c, hipMemcpyAsync(out, p.rec, sizeof(lcs_pdcch_scan_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int g = 0; g < n_sf; ++g) p.last_n_cand[g] = out->sf[g].n_cand;
-  p.last_n_sizes = n_sizes;
-  p.last_n_sf = n_sf;
+  if ((rc = wide_read_record(c, out, p.rec.get(), sizeof(*out)))) return rc;
+  for (int g = 0; g < w.n_sf; ++g) p.last_n_cand[g] = out->sf[g].n_cand;
+  p.last_n_sizes = plan.n_sizes;
+  p.last_n_sf = w.n_sf;
   return LCS_OK;
 }
 }  // namespace
 
 int lcs_pdcch_scan_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                         int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdcch_scan_wide";
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
-  int rc;
-  lcs_pdcch_cfg shared;
-  PdcchPlan pp;
-  PdcchScanPlan plan;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_scan_resolve(c, who, cell, n_rb, cfg, &shared, &pp, &plan))) return rc;
-  int rows4[4 * PCF_MAX_SF];
-  std::vector<int> list;
-  const int n_sf = pdcch_plan(cell, &shared, pp, n_ofdm, n_rb, dl_mask, rows4, &list);
-  std::vector<double> ideal(list.size());
-  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
-  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_pdcch_scan(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
-  return pdcch_scan_finish(c, n_sf, plan.n_sizes, out);
+  return pdcch_scan_call(c, "lcs_pdcch_scan_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
-
 int lcs_pdcch_scan(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_scan_cfg *cfg, lcs_pdcch_scan_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_pdcch_scan";
-  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  int rc;
-  lcs_pdcch_cfg shared;
-  PdcchPlan pp;
-  PdcchScanPlan plan;
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pdcch_scan_resolve(c, who, cell, n_rb, cfg, &shared, &pp, &plan))) return rc;
-  int rows4[4 * PCF_MAX_SF];
-  const int n_sf = pdcch_plan(cell, &shared, pp, n_ofdm, n_rb, dl_mask, rows4, nullptr);
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_pdcch_scan(c, *cell, rows4, n_sf, n_rb, dl_mask, plan))) return rc;
-  return pdcch_scan_finish(c, n_sf, plan.n_sizes, out);
+  return pdcch_scan_call(c, "lcs_pdcch_scan", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
 
 int lcs_pdcch_scan_decodes(lcs_ctx *c, int g, lcs_pdcch_scan_dec *out, int cap) {
@@ -1447,103 +1359,49 @@ int lcs_pdcch_scan_decodes(lcs_ctx *c, int g, lcs_pdcch_scan_dec *out, int cap) 
   return n;
 }
 
-// ---- the PHICH on that grid (phich.hip, phich.h): blocks of its own and the same isolation
+// ---- the PHICH on that grid (phich.hip, phich.h): blocks of its own
 namespace {
-// what cfg (or its absence) and the cell say together, or the refusal: plan_pdcch's for the PHICH configuration and the m_i
-int phich_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_phich_cfg *cfg, lcs_pdcch_cfg *shared, PhichPlan *p) {
-  std::memset(shared, 0, sizeof(*shared));
-  for (int i = 0; i < 10; ++i) shared->phich_mi[i] = -1;
-  shared->n_sizes = 1; shared->size[0] = 8;                  // the PDCCH's own fields: valid, and not this stage's
-  p->min_amp = LCS_PHICH_MIN_AMP; p->min_sigma = LCS_PHICH_MIN_SIGMA;
-  if (cfg) {
-    shared->phich_duration = cfg->phich_duration; shared->phich_resource = cfg->phich_resource;
-    for (int i = 0; i < 10; ++i) shared->phich_mi[i] = cfg->phich_mi[i];
-    p->min_amp = cfg->min_amp; p->min_sigma = cfg->min_sigma;
-  }
-  PdcchPlan pp;
-  int rc;
-  if ((rc = pdcch_resolve(c, who, cell, n_rb, shared, &pp))) return rc;
+// what cfg (or its absence) and the cell say together, or the refusal
+int phich_resolve(lcs_ctx *c, const char *who, const lcs_cell *cell, int n_rb, const lcs_phich_cfg *cfg, PhichPlan *p) {
+  p->min_amp = cfg ? cfg->min_amp : LCS_PHICH_MIN_AMP;
+  p->min_sigma = cfg ? cfg->min_sigma : LCS_PHICH_MIN_SIGMA;
+  const char *what = wide_resolve_shared(cell->phich_duration, cell->phich_resource, cfg ? cfg->phich_duration : 0, cfg ? cfg->phich_resource : 0,
+                                         cfg ? cfg->phich_mi : nullptr, 0, 0, n_rb, nullptr, &p->sh);
+  if (what) return wide_refused(c, who, what);
   if (!(p->min_amp >= 0.0) || !std::isfinite(p->min_amp)) return wide_refused(c, who, "min_amp is negative or not finite");
   if (!(p->min_sigma >= 0.0) || !std::isfinite(p->min_sigma)) return wide_refused(c, who, "min_sigma is negative or not finite");
   if (cfg && (cfg->reserved[0] || cfg->reserved[1])) return wide_refused(c, who, "a reserved field is not zero");
-  p->phich_duration = pp.phich_duration; p->phich_resource = pp.phich_resource;
-  for (int i = 0; i < 10; ++i) p->mi[i] = pp.mi[i];
   return LCS_OK;
 }
-// rows3[3 g + l] for every subframe of the grid and l < 3, as pcfich_plan: the rows the rule reads of a subframe that is read (symbol
-// 0; symbol 1 with 4 ports; symbols 0 .. 2 at the extended duration), -1 otherwise.  The tables of the call are in place.
-int phich_plan(const lcs_ctx *c, const lcs_cell *cell, const lcs_pdcch_cfg *shared, const PhichPlan &p, int n_ofdm, int dl_mask, int *rows3, std::vector<int> *list) {
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, ports = pcf_ports(cell->n_ports), n_sf = pcf_n_sf(n_ofdm, n_symb);
-  bool tdd = false;
-  for (int i = 0; i < 10; ++i) tdd = tdd || shared->phich_mi[i] >= 0;
-  for (int g = 0; g < n_sf; ++g) {
-    for (int l = 0; l < 3; ++l) rows3[3 * g + l] = -1;
-    if (!phi_sf_used(g, n_ofdm, n_symb, ports, p.phich_duration, tdd, dl_mask) || lcs_phich_map_units(c, p.mi[g % 10]) < 0) continue;
-    for (int l = 0; l < phi_rows_needed(ports, p.phich_duration); ++l) {
-      const int r = 2 * g * n_symb + l;
-      if (list) { rows3[3 * g + l] = (int)list->size(); list->push_back(r); }
-      else rows3[3 * g + l] = r;
-    }
-  }
-  return n_sf;
-}
-int phich_finish(lcs_ctx *c, int n_sf, lcs_phich_info *out) {
+int phich_call(lcs_ctx *c, const char *who, const WideSource &src, const lcs_cell *cell, int n_rb, int n_ofdm, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out) {
+  WideCall w;
+  PhichPlan plan;
+  int rc;
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, true, &w)) || (rc = phich_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  // the tables before the plan: a subframe whose map is refused is not read
+  HIPCHK(c, hipSetDevice(c->device));
+  w.device_set = true;
+  if ((rc = lcs_phich_tables(c, *cell, n_rb, plan))) return rc;
+  const int units[3] = {lcs_phich_map_units(c, 0), lcs_phich_map_units(c, 1), lcs_phich_map_units(c, 2)};
+  phich_need(w.n_symb, n_ofdm, pcf_ports(cell->n_ports), dl_mask, plan.sh, units, w.need);
+  w.plan(n_ofdm, 3, 3);
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
+  if ((rc = lcs_launch_phich(c, *cell, w.rows, w.n_sf, n_rb, dl_mask, plan))) return rc;
   lcs_ctx::Phich &p = c->phich;
   p.last_n_sf = 0;
-  HIPCHK(c, hipMemcpyAsync(out, p.rec, sizeof(lcs_phich_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int g = 0; g < n_sf; ++g) p.last_n_unit[g] = out->sf[g].n_unit;
-  p.last_n_sf = n_sf;
+  if ((rc = wide_read_record(c, out, p.rec.get(), sizeof(*out)))) return rc;
+  for (int g = 0; g < w.n_sf; ++g) p.last_n_unit[g] = out->sf[g].n_unit;
+  p.last_n_sf = w.n_sf;
   return LCS_OK;
 }
 }  // namespace
 
 int lcs_phich_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                    int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_phich_wide";
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
-  int rc;
-  lcs_pdcch_cfg shared;
-  PhichPlan plan;
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = phich_resolve(c, who, cell, n_rb, cfg, &shared, &plan))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_phich_tables(c, *cell, n_rb, plan))) return rc;
-  int rows3[3 * PCF_MAX_SF];
-  std::vector<int> list;
-  const int n_sf = phich_plan(c, cell, &shared, plan, n_ofdm, dl_mask, rows3, &list);
-  std::vector<double> ideal(list.size());
-  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
-  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_phich(c, *cell, rows3, n_sf, n_rb, dl_mask, plan))) return rc;
-  return phich_finish(c, n_sf, out);
+  return phich_call(c, "lcs_phich_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
-
 int lcs_phich(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_phich_cfg *cfg, lcs_phich_info *out) {
-  if (!c) return LCS_ERR_BAD_ARG;
-  static const char who[] = "lcs_phich";
-  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
-  int rc;
-  lcs_pdcch_cfg shared;
-  PhichPlan plan;
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = phich_resolve(c, who, cell, n_rb, cfg, &shared, &plan))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_phich_tables(c, *cell, n_rb, plan))) return rc;
-  int rows3[3 * PCF_MAX_SF];
-  const int n_sf = phich_plan(c, cell, &shared, plan, n_ofdm, dl_mask, rows3, nullptr);
-  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_phich(c, *cell, rows3, n_sf, n_rb, dl_mask, plan))) return rc;
-  return phich_finish(c, n_sf, out);
+  return phich_call(c, "lcs_phich", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, cfg, out);
 }
 
 int lcs_phich_values(lcs_ctx *c, int g, double *out, int cap) {
@@ -1564,9 +1422,9 @@ int lcs_phich_values(lcs_ctx *c, int g, double *out, int cap) {
   return n;
 }
 
-// ---- the PDSCH behind the grants of that search space (pdsch.hip, pdsch.h): the same blocks and the same isolation
+// ---- the PDSCH behind the grants of that search space (pdsch.hip, pdsch.h)
 namespace {
-int pdsch_resolve(lcs_ctx *c, const char *who, const lcs_pdcch_cfg *cfg, const PdcchPlan &plan, const lcs_pdsch_cfg *pc, int n_ofdm, int n_symb, int n_rb, PdschPlan *p) {
+int pdsch_resolve(lcs_ctx *c, const char *who, const PdcchPlan &plan, const lcs_pdsch_cfg *pc, int n_ofdm, int n_symb, int n_rb, PdschPlan *p) {
   static const lcs_pdsch_cfg zero = {};
   if (!pc) pc = &zero;
   if (pc->max_iter < 0 || pc->max_iter > 16) return wide_refused(c, who, "max_iter is outside 1 .. 16 (0: 8)");
@@ -1574,8 +1432,7 @@ int pdsch_resolve(lcs_ctx *c, const char *who, const lcs_pdcch_cfg *cfg, const P
   if (pc->i_1a < 0 || pc->i_1a >= plan.n_sizes) return wide_refused(c, who, "i_1a is outside the PDCCH configuration's sizes");
   if (pc->n_forced < 0 || pc->n_forced > LCS_PDSCH_MAX_FORCED) return wide_refused(c, who, "n_forced is outside 0 .. 4");
   p->i_1a = pc->i_1a; p->max_iter = pc->max_iter ? pc->max_iter : 8; p->rnti_mask = pc->rnti_mask ? pc->rnti_mask : 7; p->n_forced = pc->n_forced;
-  p->tdd = 0;
-  for (int i = 0; i < 10; ++i) p->tdd = p->tdd || cfg->phich_mi[i] >= 0;
+  p->tdd = plan.sh.tdd;
   const lcs_pdsch_alloc_cfg &al = c->pdsch.alloc;           // lcs_set_pdsch_alloc: the launch takes it as an argument
   if ((al.flags & 2) && plan.n_sizes < 2) return wide_refused(c, who, "format 1C is followed (lcs_set_pdsch_alloc) but the PDCCH configuration has one size");
   if ((al.flags & 2) && plan.size[1 - pc->i_1a] != (n_rb >= 50 ? 1 : 0) + pds_1c_riv_bits(n_rb) + 5)
@@ -1597,33 +1454,6 @@ int pdsch_resolve(lcs_ctx *c, const char *who, const lcs_pdcch_cfg *cfg, const P
   }
   return LCS_OK;
 }
-// pdcch_plan with every row of a subframe that lies whole inside the grid: sfrow[g] = the place of its symbol 0 (in *list, or the row
-// itself), else -1
-int pdsch_plan(const lcs_cell *cell, const lcs_pdcch_cfg *cfg, const PdcchPlan &p, int n_ofdm, int n_rb, int dl_mask, int *rows4, int *sfrow, std::vector<int> *list) {
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_sf = pcf_n_sf(n_ofdm, n_symb), n_max = pdc_n_ctrl_max(n_rb);
-  bool tdd = false;
-  for (int i = 0; i < 10; ++i) tdd = tdd || cfg->phich_mi[i] >= 0;
-  for (int g = 0; g < n_sf; ++g) {
-    for (int l = 0; l < 4; ++l) rows4[4 * g + l] = -1;
-    sfrow[g] = -1;
-    const int r0 = 2 * g * n_symb, sf = g % 10;
-    if (!((dl_mask >> sf) & 1) || r0 + n_max - 1 >= n_ofdm) continue;
-    if (tdd && p.phich_duration == 2 && (sf == 1 || sf == 6)) continue;
-    const bool whole = r0 + 2 * n_symb <= n_ofdm && !(tdd && (sf == 1 || sf == 6));
-    const int first = list ? (int)list->size() : r0;
-    if (list) for (int l = 0; l < (whole ? 2 * n_symb : n_max); ++l) list->push_back(r0 + l);
-    for (int l = 0; l < n_max; ++l) rows4[4 * g + l] = first + l;
-    if (r0 + 2 * n_symb <= n_ofdm) sfrow[g] = whole ? first : -1;
-  }
-  return n_sf;
-}
-int pdsch_finish(lcs_ctx *c, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, lcs_pdsch_comb_info *comb_out = nullptr) {
-  HIPCHK(c, hipMemcpyAsync(out, c->pdsch.rec, sizeof(lcs_pdsch_info), hipMemcpyDeviceToHost, c->stream));
-  if (comb_out) HIPCHK(c, hipMemcpyAsync(comb_out, c->pdsch.crec, sizeof(lcs_pdsch_comb_info), hipMemcpyDeviceToHost, c->stream));
-  if (pdcch_out) HIPCHK(c, hipMemcpyAsync(pdcch_out, c->pdsch.pdc.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return LCS_OK;
-}
 // the combining's configuration (null: defaults)
 int pdsch_comb_resolve(lcs_ctx *c, const char *who, const lcs_pdsch_comb_cfg *cc, PdschCombPlan *p) {
   static const lcs_pdsch_comb_cfg zero = {};
@@ -1633,80 +1463,54 @@ int pdsch_comb_resolve(lcs_ctx *c, const char *who, const lcs_pdsch_comb_cfg *cc
   p->si_window = cc->si_window; p->no_sib1 = cc->no_sib1;
   return LCS_OK;
 }
-// lcs_pdsch_wide and lcs_pdsch_comb_wide (comb_out non-null)
-int pdsch_wide_call(lcs_ctx *c, const char *who, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog, int n_fft, int n_rb,
-                    int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
-                    const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
-  if (!out) return wide_refused(c, who, "a null pointer");
-  std::vector<double> ts;
-  double kk;
-  int rc;
+// the four entry points: with comb_out the redundancy versions are combined behind the decode
+int pdsch_call(lcs_ctx *c, const char *who, const WideSource &src, const lcs_cell *cell, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg,
+               const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
+  WideCall w;
   PdcchPlan plan;
   PdschPlan ps;
   PdschCombPlan cp = {0, 0};
-  if ((rc = wide_rows(c, who, cell, d_capbuf, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, &ts, &kk))) return rc;
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
-  if ((rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, cell->cp_type == LCS_CP_NORMAL ? 7 : 6, n_rb, &ps))) return rc;
-  if (comb_out && (rc = pdsch_comb_resolve(c, who, comb_cfg, &cp))) return rc;
-  int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
-  std::vector<int> list;
-  const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, &list);
-  std::vector<double> ideal(list.size());
-  for (size_t i = 0; i < list.size(); ++i) ideal[i] = ts[(size_t)list[i]];
-  if (!list.empty() && (rc = wide_rows_fit(c, who, ideal, n_fft, n_cap))) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!list.empty() && (rc = lcs_launch_tfg_wide(c, static_cast<const float2 *>(d_capbuf), n_cap, ideal.data(), (int)list.size(), kk, n_fft, n_rb))) return rc;
-  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps, comb_out ? &cp : nullptr))) return rc;
-  return pdsch_finish(c, out, pdcch_out, comb_out);
-}
-
-// lcs_pdsch and lcs_pdsch_comb (comb_out non-null)
-int pdsch_grid_call(lcs_ctx *c, const char *who, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg,
-                    const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
-  if (!cell || !tfg || !out) return wide_refused(c, who, "a null pointer");
-  if (!cell_identified(cell)) return wide_refused(c, who, "needs a cell with n_id_1, n_id_2 and a known cp_type");
   int rc;
-  PdcchPlan plan;
-  PdschPlan ps;
-  PdschCombPlan cp = {0, 0};
-  if ((rc = pcfich_rb_refused(c, who, cell, n_rb))) return rc;
-  const int n_symb = cell->cp_type == LCS_CP_NORMAL ? 7 : 6;
-  if (n_ofdm < 2 * n_symb || n_ofdm > 122 * n_symb) return wide_refused(c, who, "n_ofdm is outside 2 n_symb .. 122 n_symb (14 .. 854 normal CP, 12 .. 732 extended)");
-  if (!meas_mask_ok(dl_mask)) return wide_refused(c, who, "needs a dl_mask with at least one of the bits 0 .. 9 and none above");
-  if ((rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan)) || (rc = pdsch_resolve(c, who, cfg, plan, pdsch_cfg, n_ofdm, n_symb, n_rb, &ps))) return rc;
+  if ((rc = wide_begin(c, who, src, cell, out, n_rb, n_ofdm, &dl_mask, true, &w)) || (rc = pdcch_resolve(c, who, cell, n_rb, cfg, &plan))) return rc;
+  if ((rc = pdsch_resolve(c, who, plan, pdsch_cfg, n_ofdm, w.n_symb, n_rb, &ps))) return rc;
   if (comb_out && (rc = pdsch_comb_resolve(c, who, comb_cfg, &cp))) return rc;
-  int rows4[4 * PCF_MAX_SF], sfrow[PCF_MAX_SF];
-  const int n_sf = pdsch_plan(cell, cfg, plan, n_ofdm, n_rb, dl_mask, rows4, sfrow, nullptr);
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((rc = lcs_pcfich_stage_grid(c, tfg, (size_t)n_ofdm * 12 * n_rb))) return rc;
-  if ((rc = lcs_launch_pdsch(c, *cell, rows4, sfrow, n_sf, n_rb, dl_mask, plan, ps, comb_out ? &cp : nullptr))) return rc;
-  return pdsch_finish(c, out, pdcch_out, comb_out);
+  int sfrow[PCF_MAX_SF];
+  pdsch_need(w.n_symb, n_ofdm, n_rb, dl_mask, plan.sh, w.need);
+  w.plan(n_ofdm, 4, pdc_n_ctrl_max(n_rb));
+  pdsch_sfrow(w.n_symb, w.n_sf, w.need, w.first, sfrow);
+  if ((rc = wide_fill_grid(c, who, src, w, n_rb, n_ofdm))) return rc;
+  if ((rc = lcs_launch_pdsch(c, *cell, w.rows, sfrow, w.n_sf, n_rb, dl_mask, plan, ps, comb_out ? &cp : nullptr))) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->pdsch.rec, sizeof(lcs_pdsch_info), hipMemcpyDeviceToHost, c->stream));
+  if (comb_out) HIPCHK(c, hipMemcpyAsync(comb_out, c->pdsch.crec, sizeof(lcs_pdsch_comb_info), hipMemcpyDeviceToHost, c->stream));
+  if (pdcch_out) HIPCHK(c, hipMemcpyAsync(pdcch_out, c->pdsch.pdc.rec, sizeof(lcs_pdcch_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return LCS_OK;
 }
 }  // namespace
 
 int lcs_pdsch_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                    int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
   if (!c) return LCS_ERR_BAD_ARG;
-  return pdsch_wide_call(c, "lcs_pdsch_wide", cell, d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
+  return pdsch_call(c, "lcs_pdsch_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
 }
 int lcs_pdsch_comb_wide(lcs_ctx *c, const lcs_cell *cell, const void *d_capbuf, uint32_t n_cap, double fc_req, double fc_prog, double fs_prog,
                         int n_fft, int n_rb, int n_ofdm, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg, lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out,
                         const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
   if (!c) return LCS_ERR_BAD_ARG;
   if (!comb_out) return wide_refused(c, "lcs_pdsch_comb_wide", "a null pointer");
-  return pdsch_wide_call(c, "lcs_pdsch_comb_wide", cell, d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, comb_cfg, comb_out);
+  return pdsch_call(c, "lcs_pdsch_comb_wide", wide_samples(d_capbuf, n_cap, fc_req, fc_prog, fs_prog, n_fft), cell, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out,
+                    comb_cfg, comb_out);
 }
 int lcs_pdsch(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
               lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out) {
   if (!c) return LCS_ERR_BAD_ARG;
-  return pdsch_grid_call(c, "lcs_pdsch", cell, tfg, n_ofdm, n_rb, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
+  return pdsch_call(c, "lcs_pdsch", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, nullptr, nullptr);
 }
 int lcs_pdsch_comb(lcs_ctx *c, const lcs_cell *cell, const double *tfg, int n_ofdm, int n_rb, int dl_mask, const lcs_pdcch_cfg *cfg, const lcs_pdsch_cfg *pdsch_cfg,
                    lcs_pdsch_info *out, lcs_pdcch_info *pdcch_out, const lcs_pdsch_comb_cfg *comb_cfg, lcs_pdsch_comb_info *comb_out) {
   if (!c) return LCS_ERR_BAD_ARG;
   if (!comb_out) return wide_refused(c, "lcs_pdsch_comb", "a null pointer");
-  return pdsch_grid_call(c, "lcs_pdsch_comb", cell, tfg, n_ofdm, n_rb, dl_mask, cfg, pdsch_cfg, out, pdcch_out, comb_cfg, comb_out);
+  return pdsch_call(c, "lcs_pdsch_comb", wide_host_grid(tfg), cell, n_rb, n_ofdm, dl_mask, cfg, pdsch_cfg, out, pdcch_out, comb_cfg, comb_out);
 }
 
 

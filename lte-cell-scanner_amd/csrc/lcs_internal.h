@@ -672,6 +672,13 @@ void pss_td(int n_id_2, double *re_im /*137*2*/);
 void sss_fd(int n_id_1, int n_id_2, int slot_num, int32_t *out /*62*/);
 void lte_pn(uint32_t c_init, uint32_t len, uint8_t *out);
 void pn_jump_table(uint32_t steps, uint32_t out[32]);
+// the block every stage on the full-bandwidth grid hands its kernels: [0 .. 31] to the reference sequence of n_rb resource blocks,
+// [32 .. 63] by 1600 clocks for the scrambling.  32 x 1600-odd clocks of host work apiece: a stage builds it when its bandwidth
+// changes, into a block of its own
+inline void wide_jump_block(int n_rb, uint32_t out[64]) {
+  pn_jump_table(1600 + 2 * (110 - n_rb), out);
+  pn_jump_table(1600, out + 32);
+}
 double chi2cdf_inv(double p, double k);
 void pbch_deratematch_map(int n_e, uint8_t *out /*n_e*/);   // ref src/lte_lib.cpp:409-463 via :473-478
 bool pbch_derm_inv(int n_e, int16_t *out /*[120][16]*/);    // its inverse: per coded bit the positions carrying it (ascending, -1 padded)
@@ -746,18 +753,18 @@ int lcs_pcfich_stage_grid(lcs_ctx *c, const double *h_grid, size_t n_elem);
 // -> c->meas_wide.pcf_rec
 int lcs_launch_pcfich(lcs_ctx *c, const lcs_cell &cell, const int *rows, int n_sf, int n_rb, int dl_mask);
 // pdcch.hip
-// the resolved configuration of a call (lcs_api.hip: what cfg and the cell say together)
-struct PdcchPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[2], rnti_mask, cfi_force; };
+// the resolved configuration of a call (wide_call.h: what cfg and the cell say together)
+struct PdcchPlan;
 // rows4 [n_sf][4]: the rows of c->meas_wide.grid that hold symbols 0 .. 3 of every subframe (-1: not read) -> c->pdcch.rec
 int lcs_launch_pdcch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
 // the same into the blocks p (the PDSCH stage keeps a set of its own for the grants it follows) -> p.rec
 int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchPlan &plan);
 // pdcch_scan.hip
-struct PdcchScanPlan { int phich_duration, phich_resource, mi[10], n_sizes, size[LCS_PDCCH_SCAN_MAX_SIZES], rnti_mask, cfi_force, min_repeat; double min_quality; };
+struct PdcchScanPlan;
 // rows4 as lcs_launch_pdcch's -> c->pdcch_scan.rec, c->pdcch_scan.tab
 int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, int n_sf, int n_rb, int dl_mask, const PdcchScanPlan &plan);
 // phich.hip
-struct PhichPlan { int phich_duration, phich_resource, mi[10]; double min_amp, min_sigma; };
+struct PhichPlan;
 // the unit tables of (n_rb, ports, CP, id, PHICH duration and Ng), on the host and on the device: built when that key changes
 int lcs_phich_tables(lcs_ctx *c, const lcs_cell &cell, int n_rb, const PhichPlan &plan);
 // n_unit of the table of m_i (0 .. 2) that lcs_phich_tables left: -1 for a refused map

@@ -81,10 +81,9 @@ int lcs_launch_pcfich(lcs_ctx *c, const lcs_cell &cell, const int *rows, int n_s
   for (int i = 0; i < 2 * n_sf; ++i) w.h_pcf_rows[i] = rows[i];
   HIPCHK(c, hipMemcpyAsync(w.pcf_rows, w.h_pcf_rows, sizeof(int) * 2 * n_sf, hipMemcpyHostToDevice, c->stream));
   if (w.pcf_jump_rb != n_rb) {
-    // the tables are 32 x 1600-odd clocks of host work apiece, a quarter of the call: built when the bandwidth changes, not per call
+    // a quarter of the call: built when the bandwidth changes, not per call
     w.pcf_jump_rb = 0;
-    lcs_tables::pn_jump_table(1600 + 2 * (110 - n_rb), w.h_pcf_jump);
-    lcs_tables::pn_jump_table(1600, w.h_pcf_jump + 32);
+    lcs_tables::wide_jump_block(n_rb, w.h_pcf_jump);
     HIPCHK(c, hipMemcpyAsync(w.pcf_jump, w.h_pcf_jump, sizeof(w.h_pcf_jump), hipMemcpyHostToDevice, c->stream));
     w.pcf_jump_rb = n_rb;
   }

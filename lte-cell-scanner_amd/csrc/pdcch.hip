@@ -7,6 +7,7 @@
 #include "lcs_internal.h"
 #include "lte_device.h"
 #include "pdcch.h"
+#include "wide_call.h"
 
 // pcfich.hip's kernels, launched here into a record of this stage's own (their definitions and code objects are that file's)
 __global__ void k_pcfich(const double2 *__restrict__ grid, const int *__restrict__ rows, const uint32_t *__restrict__ jump, lcs_pcfich_info *__restrict__ out,
@@ -156,7 +157,7 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
       (rc = p.sf.reserve(c, sizeof(p.h_sf) / sizeof(int))) || (rc = p.llr.reserve(c, (size_t)PCF_MAX_SF * PDC_NLLR)) || (rc = p.rec.reserve(c, 1)) ||
       (rc = p.pcf_rec.reserve(c, 1))) return rc;
   // the tables: host work that grows with N_REG, so built when their key changes and not per call
-  const int key[9] = {n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource, plan.n_sizes, plan.size[0], plan.n_sizes > 1 ? plan.size[1] : 0};
+  const int key[9] = {n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource, plan.n_sizes, plan.size[0], plan.n_sizes > 1 ? plan.size[1] : 0};
   if (std::memcmp(key, p.key, sizeof(key)) != 0) {
     p.key[0] = 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));              // nothing reads the host blocks that are rewritten
@@ -165,7 +166,7 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
     PdcMap *maps = reinterpret_cast<PdcMap *>(p.h_map.data());
     for (int mi = 0; mi < 3; ++mi)
       for (int cfi = 1; cfi <= 3; ++cfi)
-        pdc_build_map(n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource, mi, cfi, &maps[3 * mi + cfi - 1]);
+        pdc_build_map(n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource, mi, cfi, &maps[3 * mi + cfi - 1]);
     for (int si = 0; si < plan.n_sizes; ++si)
       for (int lv = 0; lv < 2; ++lv)
         if (!pdc_derm_build(plan.size[si] + 16, lv ? 576 : 288, PDC_DERM_W, p.h_derm.data() + (size_t)(2 * si + lv) * PDC_MAX_CODED * PDC_DERM_W)) {
@@ -178,18 +179,17 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
   }
   if (p.jump_rb != n_rb) {
     p.jump_rb = 0;
-    lcs_tables::pn_jump_table(1600 + 2 * (110 - n_rb), p.h_jump);
-    lcs_tables::pn_jump_table(1600, p.h_jump + 32);
+    lcs_tables::wide_jump_block(n_rb, p.h_jump);
     HIPCHK(c, hipMemcpyAsync(p.jump, p.h_jump, sizeof(p.h_jump), hipMemcpyHostToDevice, c->stream));
     p.jump_rb = n_rb;
   }
   for (int i = 0; i < 4 * n_sf; ++i) p.h_sf[i] = rows4[i];
-  for (int i = 0; i < 10; ++i) p.h_sf[4 * n_sf + i] = plan.mi[i];
+  for (int i = 0; i < 10; ++i) p.h_sf[4 * n_sf + i] = plan.sh.mi[i];
   // ... and the PCFICH's two rows of every subframe behind them
   int *rows2 = p.h_sf + 4 * n_sf + 10;
   for (int g = 0; g < n_sf; ++g) { rows2[2 * g] = rows4[4 * g]; rows2[2 * g + 1] = (ports == 4 && rows4[4 * g] >= 0) ? rows4[4 * g + 1] : -1; }
   HIPCHK(c, hipMemcpyAsync(p.sf, p.h_sf, sizeof(int) * (6 * n_sf + 10), hipMemcpyHostToDevice, c->stream));
-  if (!plan.cfi_force) {
+  if (!plan.sh.cfi_force) {
     // the PCFICH of the same rows into a record of this stage's own: the PCFICH stage's blocks are not touched
     hipLaunchKernelGGL(k_pcfich, dim3(n_sf), dim3(PCF_LANES), 0, c->stream, (const double2 *)w.grid.get(), (const int *)(p.sf.get() + 4 * n_sf + 10),
                        (const uint32_t *)p.jump.get(), p.pcf_rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb);
@@ -199,11 +199,11 @@ int lcs_launch_pdcch_in(lcs_ctx *c, lcs_ctx::Pdcch &p, const lcs_cell &cell, con
   }
   hipLaunchKernelGGL(k_pdcch_llr, dim3(n_sf), dim3(PDC_LLR_THREADS), 0, c->stream, (const double2 *)w.grid.get(), (const int *)p.sf.get(),
                      (const uint32_t *)p.jump.get(), (const lcs_pcfich_info *)p.pcf_rec.get(), reinterpret_cast<const PdcMap *>(p.map.get()), p.llr.get(),
-                     p.rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb, plan.cfi_force);
+                     p.rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb, plan.sh.cfi_force);
   HIPCHK(c, hipGetLastError());
   const int n_waves = n_sf * PDC_SLOTS * PDC_SIZES;
   hipLaunchKernelGGL(k_pdcch_dec, dim3((n_waves + PDC_DEC_WAVES - 1) / PDC_DEC_WAVES), dim3(64 * PDC_DEC_WAVES), 0, c->stream, (const double *)p.llr.get(),
-                     (const int16_t *)p.derm.get(), p.rec.get(), n_sf, plan.n_sizes, plan.size[0], plan.n_sizes > 1 ? plan.size[1] : 0, plan.rnti_mask);
+                     (const int16_t *)p.derm.get(), p.rec.get(), n_sf, plan.n_sizes, plan.size[0], plan.n_sizes > 1 ? plan.size[1] : 0, plan.sh.rnti_mask);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_pdcch_fin, dim3(1), dim3(256), 0, c->stream, p.rec.get(), n_sf, dl_mask, n_rb, ports);
   HIPCHK(c, hipGetLastError());

@@ -7,6 +7,7 @@
 #include "lcs_internal.h"
 #include "lte_device.h"
 #include "pdcch_scan.h"
+#include "wide_call.h"
 
 // pcfich.hip's kernels, launched here into a record of this stage's own (as pdcch.hip does)
 __global__ void k_pcfich(const double2 *__restrict__ grid, const int *__restrict__ rows, const uint32_t *__restrict__ jump, lcs_pcfich_info *__restrict__ out,
@@ -326,7 +327,7 @@ int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, in
   if ((rc = p.map.reserve(c, map_ints)) || (rc = p.derm.reserve(c, derm_n)) || (rc = p.jump.reserve(c, 32 + PSC_JUMP_WORDS)) ||
       (rc = p.sf.reserve(c, sizeof(p.h_sf) / sizeof(int))) || (rc = p.llr.reserve(c, (size_t)PCF_MAX_SF * PSC_NLLR)) || (rc = p.tab.reserve(c, tab_n)) ||
       (rc = p.pres.reserve(c, pres_n)) || (rc = p.stage.reserve(c, tab_n)) || (rc = p.sfc.reserve(c, (size_t)PCF_MAX_SF * PSC_SFC)) || (rc = p.rec.reserve(c, 1)) || (rc = p.pcf_rec.reserve(c, 1))) return rc;
-  int key[13] = {n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource, plan.n_sizes, 0, 0, 0, 0, 0, 0};
+  int key[13] = {n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource, plan.n_sizes, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < plan.n_sizes; ++i) key[7 + i] = plan.size[i];
   if (std::memcmp(key, p.key, sizeof(key)) != 0) {
     p.key[0] = 0;
@@ -338,7 +339,7 @@ int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, in
     for (int mi = 0; mi < 3; ++mi)
       for (int cfi = 1; cfi <= 3; ++cfi) {
         PscMap &m = maps[3 * mi + cfi - 1];
-        pdc_build_map_t<PSC_MAX_QUAD>(n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource, mi, cfi, &m);
+        pdc_build_map_t<PSC_MAX_QUAD>(n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource, mi, cfi, &m);
         if (m.n_cce > PSC_MAX_CCE) { c->err = "pdcch_scan: more CCEs than the stage reads"; return LCS_ERR_BAD_ARG; }
         max_cce = m.n_cce > max_cce ? m.n_cce : max_cce;
       }
@@ -363,13 +364,13 @@ int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, in
     p.jump_rb = n_rb;
   }
   for (int i = 0; i < 4 * n_sf; ++i) p.h_sf[i] = rows4[i];
-  for (int i = 0; i < 10; ++i) p.h_sf[4 * n_sf + i] = plan.mi[i];
+  for (int i = 0; i < 10; ++i) p.h_sf[4 * n_sf + i] = plan.sh.mi[i];
   int *rows2 = p.h_sf + 4 * n_sf + 10;
   for (int g = 0; g < n_sf; ++g) { rows2[2 * g] = rows4[4 * g]; rows2[2 * g + 1] = (ports == 4 && rows4[4 * g] >= 0) ? rows4[4 * g + 1] : -1; }
   HIPCHK(c, hipMemcpyAsync(p.sf, p.h_sf, sizeof(int) * (6 * n_sf + 10), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(p.rec.get(), 0, sizeof(lcs_pdcch_scan_info), c->stream));
   HIPCHK(c, hipMemsetAsync(p.pres.get(), 0, pres_n, c->stream));
-  if (!plan.cfi_force) {
+  if (!plan.sh.cfi_force) {
     hipLaunchKernelGGL(k_pcfich, dim3(n_sf), dim3(PCF_LANES), 0, c->stream, (const double2 *)w.grid.get(), (const int *)(p.sf.get() + 4 * n_sf + 10),
                        (const uint32_t *)p.jump.get(), p.pcf_rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb);
     HIPCHK(c, hipGetLastError());
@@ -378,7 +379,7 @@ int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, in
   }
   hipLaunchKernelGGL(k_pscan_llr, dim3(n_sf), dim3(PSC_LLR_THREADS), 0, c->stream, (const double2 *)w.grid.get(), (const int *)p.sf.get(),
                      (const uint32_t *)p.jump.get(), (const lcs_pcfich_info *)p.pcf_rec.get(), reinterpret_cast<const PscMap *>(p.map.get()), p.llr.get(),
-                     p.rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb, plan.cfi_force);
+                     p.rec.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb, plan.sh.cfi_force);
   HIPCHK(c, hipGetLastError());
   PscSizes sizes;
   for (int i = 0; i < PSC_SIZES; ++i) sizes.a[i] = i < plan.n_sizes ? plan.size[i] : 0;
@@ -386,7 +387,7 @@ int lcs_launch_pdcch_scan(lcs_ctx *c, const lcs_cell &cell, const int *rows4, in
     const int n_waves = n_sf * p.cand_cap;
     hipLaunchKernelGGL(k_pscan_dec, dim3((n_waves + PSC_DEC_WAVES - 1) / PSC_DEC_WAVES), dim3(64 * PSC_DEC_WAVES), 0, c->stream, (const double *)p.llr.get(),
                        (const int16_t *)p.derm.get(), (const lcs_pdcch_scan_info *)p.rec.get(), p.tab.get(), p.pres.get(), n_sf, p.cand_cap, plan.n_sizes, sizes,
-                       plan.rnti_mask, plan.min_quality);
+                       plan.sh.rnti_mask, plan.min_quality);
     HIPCHK(c, hipGetLastError());
   }
   hipLaunchKernelGGL(k_pscan_acc, dim3(n_sf), dim3(PSC_FIN_THREADS), 0, c->stream, p.rec.get(), p.tab.get(), (const unsigned char *)p.pres.get(), p.stage.get(),

@@ -540,8 +540,7 @@ int lcs_launch_pdsch(lcs_ctx *c, const lcs_cell &cell, const int *rows4, const i
   if (p.jump_rb != n_rb) {
     p.jump_rb = 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    lcs_tables::pn_jump_table(1600 + 2 * (110 - n_rb), p.h_jump);
-    lcs_tables::pn_jump_table(1600, p.h_jump + 32);
+    lcs_tables::wide_jump_block(n_rb, p.h_jump);
     for (int b = 0; b < 8; ++b) lcs_tables::pn_jump_table((32 * PDS_SCR_CHUNK) << b, p.h_jump + 64 + 32 * b);
     HIPCHK(c, hipMemcpyAsync(p.jump, p.h_jump, sizeof(p.h_jump), hipMemcpyHostToDevice, c->stream));
     p.jump_rb = n_rb;

@@ -7,6 +7,7 @@
 #include "lcs_internal.h"
 #include "lte_device.h"
 #include "phich.h"
+#include "wide_call.h"
 
 static_assert(sizeof(PhiEntry) == sizeof(lcs_ctx::PhichEntry), "lcs_internal.h: PhichEntry is phich.h's PhiEntry");
 #define PHI_THREADS 256
@@ -156,20 +157,19 @@ int lcs_phich_tables(lcs_ctx *c, const lcs_cell &cell, int n_rb, const PhichPlan
   const size_t map_ints = 3 * sizeof(PhiMap) / sizeof(int);
   if ((rc = p.map.reserve(c, map_ints)) || (rc = p.jump.reserve(c, 64)) || (rc = p.sf.reserve(c, sizeof(p.h_sf) / sizeof(int))) ||
       (rc = p.tab.reserve(c, (size_t)PCF_MAX_SF * PHI_MAX_ENT)) || (rc = p.sfu.reserve(c, PCF_MAX_SF)) || (rc = p.rec.reserve(c, 1))) return rc;
-  const int key[6] = {n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource};
+  const int key[6] = {n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource};
   if (std::memcmp(key, p.key, sizeof(key)) != 0) {
     p.key[0] = 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));              // nothing reads the host block that is rewritten
     p.h_map.assign(map_ints, 0);
     PhiMap *maps = reinterpret_cast<PhiMap *>(p.h_map.data());
-    phi_build_maps(n_rb, ports, (int)cell.cp_type, id, plan.phich_duration, plan.phich_resource, maps);
+    phi_build_maps(n_rb, ports, (int)cell.cp_type, id, plan.sh.phich_duration, plan.sh.phich_resource, maps);
     HIPCHK(c, hipMemcpyAsync(p.map, p.h_map.data(), sizeof(int) * map_ints, hipMemcpyHostToDevice, c->stream));
     std::memcpy(p.key, key, sizeof(key));
   }
   if (p.jump_rb != n_rb) {
     p.jump_rb = 0;
-    lcs_tables::pn_jump_table(1600 + 2 * (110 - n_rb), p.h_jump);
-    lcs_tables::pn_jump_table(1600, p.h_jump + 32);
+    lcs_tables::wide_jump_block(n_rb, p.h_jump);
     HIPCHK(c, hipMemcpyAsync(p.jump, p.h_jump, sizeof(p.h_jump), hipMemcpyHostToDevice, c->stream));
     p.jump_rb = n_rb;
   }
@@ -185,7 +185,7 @@ int lcs_launch_phich(lcs_ctx *c, const lcs_cell &cell, const int *rows3, int n_s
   if (n_sf <= 0 || n_sf > PCF_MAX_SF) { c->err = "phich: no such number of subframes"; return LCS_ERR_BAD_ARG; }
   const int n_symb = cell.cp_type == LCS_CP_NORMAL ? 7 : 6, id = cell.n_id_2 + 3 * cell.n_id_1, ports = pcf_ports(cell.n_ports);
   for (int i = 0; i < 3 * n_sf; ++i) p.h_sf[i] = rows3[i];
-  for (int i = 0; i < 10; ++i) p.h_sf[3 * n_sf + i] = plan.mi[i];
+  for (int i = 0; i < 10; ++i) p.h_sf[3 * n_sf + i] = plan.sh.mi[i];
   HIPCHK(c, hipMemcpyAsync(p.sf, p.h_sf, sizeof(int) * (3 * n_sf + 10), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_phich, dim3(n_sf), dim3(PHI_THREADS), 0, c->stream, (const double2 *)w.grid.get(), (const int *)p.sf.get(), (const uint32_t *)p.jump.get(),
                      reinterpret_cast<const PhiMap *>(p.map.get()), reinterpret_cast<PhiEntry *>(p.tab.get()), p.sfu.get(), n_sf, id, (int)cell.cp_type, n_symb, ports, n_rb);

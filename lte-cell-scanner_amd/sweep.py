@@ -337,40 +337,38 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                     mask = int(d["meas"].dl_mask)
                 else:
                     mask = 0x3FF if searcher.duplex == capi.DUPLEX_FDD else 0x021
-                rec = searcher.cell_meas_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
+                # what every stage below takes: the cell, its samples and rate, the grid's shape, the mask
+                wide = (mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask)
+                # the stages that decode span the cell's own bandwidth, and all but the PCFICH need its PHICH configuration
+                own_rb = lambda: rb == int(get("n_rb_dl"))
+                decodable = lambda: own_rb() and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4)
+                tdd = searcher.duplex != capi.DUPLEX_FDD
+                tdd_mi = lambda: capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None      # None: FDD's
+                default_pdcch_cfg = lambda: capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=tdd_mi())
+                rec = searcher.cell_meas_wide(*wide, n_cap=n_cap)
                 if d is not None:
                     d["meas_wide"] = rec
                 if pcfich:
-                    pc = None
-                    if rb == int(get("n_rb_dl")):
-                        pc = searcher.pcfich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, n_cap=n_cap)
+                    pc = searcher.pcfich_wide(*wide, n_cap=n_cap) if own_rb() else None
                     if d is not None:
                         d["pcfich"] = pc
                     rec = (rec, pc)
                 if pdcch:
                     pd = None
-                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
-                        cfg = pdcch
-                        if pdcch is True:
-                            tdd = searcher.duplex != capi.DUPLEX_FDD
-                            cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
-                        pd = searcher.pdcch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, n_cap=n_cap)
+                    if decodable():
+                        pd = searcher.pdcch_wide(*wide, default_pdcch_cfg() if pdcch is True else pdcch, n_cap=n_cap)
                     if d is not None:
                         d["pdcch"] = pd
                     rec = (rec if isinstance(rec, tuple) else (rec,)) + (pd,)
                 if pdsch or pdsch_comb:
                     ps = pc = None
-                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
-                        cfg = pdcch
-                        if cfg is True or not cfg:
-                            tdd = searcher.duplex != capi.DUPLEX_FDD
-                            cfg = capi.PdcchCfg.make(capi.dci_common_sizes(rb, tdd), phich_mi=capi.tdd_phich_mi(tdd_config) if tdd and tdd_config is not None else None)
+                    if decodable():
+                        cfg = default_pdcch_cfg() if pdcch is True or not pdcch else pdcch
                         pcfg = None if pdsch is True or not pdsch else pdsch
                         if pdsch_comb:
-                            ps, pc = searcher.pdsch_comb_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg,
-                                                              None if pdsch_comb is True else pdsch_comb, n_cap=n_cap)
+                            ps, pc = searcher.pdsch_comb_wide(*wide, cfg, pcfg, None if pdsch_comb is True else pdsch_comb, n_cap=n_cap)
                         else:
-                            ps = searcher.pdsch_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, pcfg, n_cap=n_cap)
+                            ps = searcher.pdsch_wide(*wide, cfg, pcfg, n_cap=n_cap)
                     if d is not None:
                         d["pdsch"] = ps
                     rec = (rec if isinstance(rec, tuple) else (rec,)) + (ps,)
@@ -383,20 +381,17 @@ def measure_wideband(searcher, d_wide_ptr: int, fmt: int, n_in: int, fs_in: floa
                                 d["sib1"] = sib[0]
                         rec = rec + (pc,)
                 if pdcch_scan is not None:
-                    sc = None
-                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
-                        sc = searcher.pdcch_scan_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, pdcch_scan, n_cap=n_cap)
+                    sc = searcher.pdcch_scan_wide(*wide, pdcch_scan, n_cap=n_cap) if decodable() else None
                     if d is not None:
                         d["pdcch_scan"] = sc
                     rec = (rec if isinstance(rec, tuple) else (rec,)) + (sc,)
                 if phich:
                     ph = None
-                    if rb == int(get("n_rb_dl")) and get("phich_duration") in (1, 2) and get("phich_resource") in (1, 2, 3, 4):
+                    if decodable():
                         cfg = phich
                         if phich is True:
-                            tdd = searcher.duplex != capi.DUPLEX_FDD
-                            cfg = capi.PhichCfg.make(phich_mi=capi.tdd_phich_mi(tdd_config)) if tdd and tdd_config is not None else None
-                        ph = searcher.phich_wide(mc, ptr, float(fc), float(fc), fs_m, 128 * R, rb, min(122, n_slots) * n_symb, mask, cfg, n_cap=n_cap)
+                            cfg = capi.PhichCfg.make(phich_mi=tdd_mi()) if tdd_mi() is not None else None
+                        ph = searcher.phich_wide(*wide, cfg, n_cap=n_cap)
                     if d is not None:
                         d["phich"] = ph
                     rec = (rec if isinstance(rec, tuple) else (rec,)) + (ph,)
