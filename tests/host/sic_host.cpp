@@ -89,6 +89,13 @@ int main() {
   for (int cp = 1; cp <= 2; ++cp)
     for (double ppm = -120.0; ppm <= 120.0; ppm += 120.0)
       for (double fs0 = 0.0; fs0 < 19200.0; fs0 += 1371.3) bad += sic_host_tiles(fs0, -ppm * 1e-6 * fc, cp, 153600, fc, fc, 1.92e6) != 0;
+  // off-nominal rates: fs_programmed +- 3e-4, fc_programmed 40 kHz below fc_requested, on the shortest and the longest capture
+  for (int cp = 1; cp <= 2; ++cp)
+    for (double rate = -3e-4; rate <= 3e-4; rate += 6e-4)
+      for (double fs0 = -2.5; fs0 < 19200.0; fs0 += 2371.3) {
+        bad += sic_host_tiles(fs0, rate > 0 ? 5000.0 : -5000.0, cp, 9600, fc, fc - 40e3, 1.92e6 * (1.0 + rate)) != 0;
+        bad += sic_host_tiles(fs0, rate > 0 ? 5000.0 : -5000.0, cp, 268800, fc, fc - 40e3, 1.92e6 * (1.0 + rate)) != 0;
+      }
   std::printf("sic_host: %d failures\n", bad);
   return bad != 0;
 }

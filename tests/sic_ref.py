@@ -43,27 +43,47 @@ def geometry(cell, n_cap, fc_req, fc_prog, fs):
     def a(t):
         return w(t) - cp(t) + WIN_IN_CP
 
-    t_all = np.arange(-20 * n_symb - 2, 12 * 20 * n_symb)
+    # every symbol that can touch the capture: a slot is 960 nominal samples and n_symb symbols, so the symbols whose nominal
+    # position lies within a slot of sample 0 and of sample n_cap bracket t_lo and t_hi whatever n_cap, d0 and step are
+    first = int(np.floor((-d0 / step - 960.0) * n_symb / 960.0)) - 1
+    last = int(np.ceil(((n_cap - d0) / step + 960.0) * n_symb / 960.0)) + 1
+    t_all = np.arange(first, last + 1)
     ok = (a(t_all) >= 0) & (w(t_all) + 128 <= n_cap)
     t_lo, t_hi = int(t_all[ok][0]), int(t_all[ok][-1])
+    assert first < t_lo and t_hi < last                           # the bracket held: both neighbours were looked at and refused
+    j_lo, j_hi = t_lo // n_symb, t_hi // n_symb
     return dict(n_symb=n_symb, normal=normal, k=k, step=step, d0=d0, d=d, w=w, a=a, t_lo=t_lo, t_hi=t_hi, n_sym=t_hi - t_lo + 1,
+                j_lo=j_lo, n_slots=j_hi - j_lo + 1, f_lo=j_lo // 20, n_frames=j_hi // 20 - j_lo // 20 + 1,      # as sic.h's SicGeom
                 rot=cell.freq_superfine / (fs * k))               # cycles per sample of the cell's carrier offset
 
 
-def owner(geo, n):
-    """sample -> (symbol, offset into the periodic extension of its window), by the closed form of sic.h; symbol < t_lo: none"""
-    n = np.asarray(n, np.int64)
+def owner_nominal(geo, n):
+    """the symbol whose nominal stretch holds sample n"""
     r = (n - geo["d0"]) / geo["step"] + ((10 if geo["normal"] else 32) - WIN_IN_CP)
     if geo["normal"]:
         slot = np.floor(r / 960.0)
         rr = r - 960.0 * slot
         sym = np.where(rr < 138.0, 0, np.minimum(6, 1 + np.floor((rr - 138.0) / 137.0)))
-        t = (7 * slot + sym).astype(np.int64)
-    else:
-        t = np.floor(r / 160.0).astype(np.int64)
-    t = np.where(n < geo["a"](t), t - 1, np.where(n >= geo["a"](t + 1), t + 1, t))
+        return (7 * slot + sym).astype(np.int64)
+    return np.floor(r / 160.0).astype(np.int64)
+
+
+def owner_corrected(geo, n, t):
+    """... corrected by at most one symbol to the rounded boundaries a(t)"""
+    return np.where(n < geo["a"](t), t - 1, np.where(n >= geo["a"](t + 1), t + 1, t))
+
+
+def window_offset(n, w):
+    """offset of sample n into the periodic extension of the window at w, backwards into the cyclic prefix too"""
+    return (n - w) % 128
+
+
+def owner(geo, n):
+    """sample -> (symbol, offset into the periodic extension of its window), by the closed form of sic.h; symbol < t_lo: none"""
+    n = np.asarray(n, np.int64)
+    t = owner_corrected(geo, n, owner_nominal(geo, n))
     inside = (t >= geo["t_lo"]) & ((t < geo["t_hi"]) | ((t == geo["t_hi"]) & (n < geo["w"](t) + 128)))
-    return np.where(inside, t, geo["t_lo"] - 1), (n - geo["w"](t)) % 128
+    return np.where(inside, t, geo["t_lo"] - 1), window_offset(n, geo["w"](t))
 
 
 def cn():
@@ -97,6 +117,16 @@ def usable(geo, t, dl_mask, special):
     return bool((dl_mask >> sf) & 1) or (special and sf in (1, 6) and (s & 1) == 0 and sym == 0)
 
 
+def crs_third_symbol(n_symb):
+    """the second symbol of a slot with the CRS of ports 0 and 1 (36.211 6.10.1.2: l = N_symb - 3)"""
+    return n_symb - 3
+
+
+def crs_v23(s):
+    """v of port 2 in symbol 1 of slot-in-frame s (port 3: 3 more): it alternates with the slot's parity"""
+    return 3 * (s & 1)
+
+
 def crs_of(geo, ident, cell, t):
     """{port: (first subcarrier, 12 values)} of symbol t"""
     n_symb = geo["n_symb"]
@@ -104,10 +134,10 @@ def crs_of(geo, ident, cell, t):
     s = j % 20
     if sym == 0:
         v = {0: 0, 1: 3}
-    elif sym == n_symb - 3:
+    elif sym == crs_third_symbol(n_symb):
         v = {0: 3, 1: 0}
     elif sym == 1:
-        v = {2: 3 * (s & 1), 3: 3 + 3 * (s & 1)}
+        v = {2: crs_v23(s), 3: 3 + crs_v23(s)}
     else:
         return {}
     rs = ident["rs"][s * n_symb + sym]
@@ -166,15 +196,31 @@ def sync_symbols(geo, duplex):
     return out
 
 
+def frame_sfn(cell, geo, frame):
+    """the system frame number of frame `frame` of the grid (frame 0 carries the record's sfn: decode_mib's rule; frames before it
+    and frames past 1023 wrap)"""
+    return (cell.sfn + frame) % 1024
+
+
 def pbch_quarter(cell, ident, geo, frame):
-    """the PBCH symbols of frame `frame` of the grid (frame 0 carries the record's sfn: decode_mib's rule)"""
+    """the PBCH symbols of frame `frame` of the grid"""
     synth = load_pkg().synth
-    sfn = (cell.sfn + frame) % 1024
+    sfn = frame_sfn(cell, geo, frame)
     key = sfn - sfn % 4
     if key not in ident["pbch"]:
         ident["pbch"][key] = synth.pbch_symbols(ident["id"], cell.n_ports, cell.n_rb_dl, 1 if cell.phich_duration == 2 else 0,
                                                 cell.phich_resource - 1, key, geo["normal"]).reshape(4, -1)
     return ident["pbch"][key][sfn % 4]
+
+
+def pbch_mate(s):
+    """element i's partner in its SFBC pair: element i ^ 1"""
+    return s.reshape(-1, 2)[:, ::-1].reshape(-1)
+
+
+def pbch_skip(sym, normal):
+    """whether symbol `sym` of slot 1 leaves out the subcarriers k mod 3 == id mod 3 (where the CRS of any of four ports may lie)"""
+    return sym in (0, 1) or (sym == 3 and not normal)
 
 
 def pbch_layers(s, n_ports):
@@ -184,8 +230,9 @@ def pbch_layers(s, n_ports):
         x[0] = s
         return x
     a = np.empty((2, s.size), np.complex128)
-    a[0, 0::2], a[0, 1::2] = s[0::2], s[1::2]
-    a[1, 0::2], a[1, 1::2] = -np.conj(s[1::2]), np.conj(s[0::2])
+    m = pbch_mate(s)
+    a[0] = s
+    a[1, 0::2], a[1, 1::2] = -np.conj(m[0::2]), np.conj(m[1::2])
     a /= np.sqrt(2.0)
     if n_ports == 2:
         return a
@@ -218,11 +265,14 @@ def known(G, H, j_lo, geo, ident, cell, duplex, mask, dl_mask, special):
             k = sh + 6 * np.arange(12)
             T[2, t - geo["t_lo"], k] += H[j - j_lo, p, k] * rs
         if j % 20 == 1 and sym <= 3:
-            skip = sym in (0, 1) or (sym == 3 and not geo["normal"])
+            skip = pbch_skip(sym, geo["normal"])
             sc = np.array([k for k in range(72) if not (skip and k % 3 == ident["id"] % 3)])
             per = [48, 48, 72, 72] if geo["normal"] else [48, 48, 72, 48]
             q = pbch_quarter(cell, ident, geo, j // 20)
-            x = pbch_layers(q[sum(per[:sym]):sum(per[:sym]) + per[sym]], cell.n_ports)
+            seg = np.zeros(sc.size, np.complex128)               # sc.size == per[sym]: the quarter's share of this symbol
+            part = q[sum(per[:sym]):sum(per[:sym]) + sc.size]
+            seg[:part.size] = part
+            x = pbch_layers(seg, cell.n_ports)
             T[3, t - geo["t_lo"], sc] = np.sum(H[j - j_lo, :, sc].T * x, axis=0)
     for i, bit in enumerate((PSS, SSS, CRS, PBCH)):
         if not mask & bit:
@@ -236,6 +286,12 @@ def identity(cell):
     ident["pss"] = O.pss_fd(cell.n_id_2)
     ident["sss"] = {s: O.sss_fd(cell.n_id_1, cell.n_id_2, s).astype(np.float64) for s in (0, 10)}
     return ident
+
+
+def synthesis_phase(geo, t):
+    """[len(t)][72]: the grid's `late` phase put back before the inverse transform"""
+    late = geo["w"](t) - geo["d"](t)
+    return np.exp(2j * np.pi * late[:, None] * cn()[None, :] / 128)
 
 
 def pss_energy(G, geo, duplex):
@@ -252,14 +308,16 @@ def dl_mask_for(duplex, ul_dl_config=None):
     return load_pkg().capi.load().lcs_tdd_dl_mask(int(ul_dl_config)), True
 
 
-def cancel(cap, cells, fc_req, fc_prog, fs, duplex=FDD, mask=ALL, ul_dl_config=None):
-    """-> (residual complex128, [dict per cell: power [4], gain, n_sym, pss_before, pss_after, suppression_db]).
+def cancel(cap, cells, fc_req, fc_prog, fs, duplex=FDD, mask=ALL, ul_dl_config=None, waveforms=False):
+    """-> (residual complex128, [dict per cell: power [4], gain, n_sym, n_pss, pss_before, pss_after, suppression_db]); with
+    `waveforms` also [per cell: the waveform y_c that was subtracted].  One capture, the cells of its buffer in list order: a batch
+    is one call per buffer, each with the buffer's own fc_req / fc_prog.
     ul_dl_config: one uplink-downlink configuration for every cell, or a list with one per cell (None / outside 0..6: not known)"""
     cap = np.asarray(cap, np.complex128)
     res = cap.copy()
     configs = list(ul_dl_config) if isinstance(ul_dl_config, (list, tuple)) else [ul_dl_config] * len(cells)
     n = np.arange(cap.size)
-    work = []
+    work, ys = [], []
     for cell, config in zip(cells, configs):
         dl_mask, special = dl_mask_for(duplex, config)
         geo, ident = geometry(cell, cap.size, fc_req, fc_prog, fs), identity(cell)
@@ -268,17 +326,18 @@ def cancel(cap, cells, fc_req, fc_prog, fs, duplex=FDD, mask=ALL, ul_dl_config=N
         T, gain = known(G, H, j_lo, geo, ident, cell, duplex, mask, dl_mask, special)
         X = np.zeros((geo["n_sym"], 128), np.complex128)
         t = np.arange(geo["t_lo"], geo["t_hi"] + 1)
-        late = geo["w"](t) - geo["d"](t)
-        X[:, bins()] = T.sum(0) * np.exp(2j * np.pi * late[:, None] * cn()[None, :] / 128)
+        X[:, bins()] = T.sum(0) * synthesis_phase(geo, t)
         td = np.fft.ifft(X, axis=1)
         sym, off = owner(geo, n)
         inside = sym >= geo["t_lo"]
         ph = geo["rot"] * n
         y = np.where(inside, td[np.where(inside, sym - geo["t_lo"], 0), off], 0) * np.exp(2j * np.pi * (ph - np.rint(ph)))
         res -= y
-        work.append((geo, G, dict(power=[float(np.sum(np.abs(T[i]) ** 2) / 128) for i in range(4)], gain=complex(gain), n_sym=geo["n_sym"])))
+        ys.append(y)
+        work.append((geo, G, dict(power=[float(np.sum(np.abs(T[i]) ** 2) / 128) for i in range(4)], gain=complex(gain), n_sym=geo["n_sym"],
+                                  n_pss=sum(kind == "pss" for _, kind, _ in sync_symbols(geo, duplex)))))
     for geo, G, info in work:
         info["pss_before"] = float(pss_energy(G, geo, duplex))
         info["pss_after"] = float(pss_energy(grid(res, geo), geo, duplex))
         info["suppression_db"] = 10 * np.log10(info["pss_before"] / info["pss_after"]) if info["pss_after"] > 0 else np.inf
-    return res, [w[2] for w in work]
+    return (res, [w[2] for w in work], ys) if waveforms else (res, [w[2] for w in work])

@@ -10,6 +10,7 @@ import pytest
 
 import oracle as O
 import sic_cases as K
+import sic_edge_cases as E
 import sic_ref as R
 from conftest import load_pkg
 
@@ -88,6 +89,42 @@ def test_geometry_equals_ref(H):
         assert out[4] == (geo["t_lo"] // n_symb) // 20 and out[5] <= 10
     assert H.sic_host_geometry(float("nan"), 0.0, 1, 153600, K.FC, K.FC, K.FS, (C.c_int * 6)()) == 0
     assert H.sic_host_geometry(100.0, 0.0, 0, 153600, K.FC, K.FC, K.FS, (C.c_int * 6)()) == 0
+
+
+def test_geometry_equals_ref_on_the_edge_table(H):
+    """every record of tests/sic_edge_cases.py: the symbols, slots and frames sic_geometry finds are sic_ref.geometry's"""
+    n = 0
+    for c in E.CASES:
+        for b, buf in enumerate(c["bufs"]):
+            for i, spec in enumerate(buf["cells"]):
+                geo = E.case_geo(c, b, i)
+                out = (C.c_int * 6)()
+                assert H.sic_host_geometry(spec["frame_start"], spec["ff"], spec["cp"], c["n_cap"], buf["fc"][0], buf["fc"][1], c["fs"], out) == 1
+                assert list(out) == [geo[k] for k in ("t_lo", "t_hi", "j_lo", "n_slots", "f_lo", "n_frames")], (c["name"], b, i)
+                # ... and sic_owner names the walk's symbol and offset for every sample of the case's capture
+                assert H.sic_host_tiles(spec["frame_start"], spec["ff"], spec["cp"], c["n_cap"], buf["fc"][0], buf["fc"][1], c["fs"]) == 0, (c["name"], b, i)
+                n += 1
+    assert n >= len(E.CASES)
+    # the launcher's refusal (tests/test_gpu_sic_edges.py): at 1.0 Msps a 268800-sample capture spans more frames than a PBCH table holds
+    out = (C.c_int * 6)()
+    assert H.sic_host_geometry(5000.3, 0.0, 1, 268800, E.FC, E.FC, 1.0e6, out) == 1 and out[5] > 16
+    assert out[5] == E.geo_of(E.rec(155, 2, 1, 5000.3), 268800, fs=1.0e6)["n_frames"]
+
+
+@pytest.mark.parametrize("cp_type", [1, 2])
+@pytest.mark.parametrize("rate", [-3e-4, 3e-4])
+def test_intervals_tile_off_nominal_rates(H, cp_type, rate):
+    """the walk with fs_programmed away from 1.92 MHz and fc_programmed away from fc_requested (step = 1 +- 3e-4 and a bit): the cases
+    of the table's rates group, and every frame_start on the 0.37-sample raster across a frame on a capture of two slots and a bit"""
+    rates = [c for c in E.CASES if c["group"] == "rates" and (c["fs"] > E.FS) == (rate > 0) and c["bufs"][0]["cells"][0]["cp"] == cp_type]
+    assert rates
+    for c in rates:
+        spec, buf = c["bufs"][0]["cells"][0], c["bufs"][0]
+        assert H.sic_host_tiles(spec["frame_start"], spec["ff"], cp_type, c["n_cap"], buf["fc"][0], buf["fc"][1], c["fs"]) == 0, c["name"]
+    why = C.c_int(0)
+    bad = H.sic_host_tiles_raster(-3.0, 0.37, 51908, 5000.0 if rate > 0 else -5000.0, cp_type, 2400, E.FC_OFF[0], E.FC_OFF[1], E.FS * (1 + rate), C.byref(why))
+    assert bad == -1, (bad, -3.0 + 0.37 * bad, why.value)
+    assert H.sic_host_tiles(14198.0, 0.0, cp_type, 268800, E.FC_OFF[0], E.FC_OFF[1], E.FS * (1 + rate)) == 0      # the longest capture
 
 
 @pytest.mark.parametrize("normal", [True, False])
